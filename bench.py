@@ -30,6 +30,17 @@ One JSON line on stdout (rank 0).  `roofline` is computed for the kernel with th
 launch stream.  `cpu_baseline` times the reference program itself (oracle/_ref/gnumap_ref, the unmodified src/Driver.cpp -c
 pthread path; kind "reference") on a bounded sample of the same reads on this box's host cores, or the CPU restatement (kind
 "port") when the reference binary did not travel.
+
+A plain run (no `--full`) does only what `value` needs: reference + index + reads, one untimed pass and the warm-up, the timed
+steps (with the per-kernel times, counters and roofline they yield), the outputs of `--dump-outputs`, the JSON line.  `--full` adds
+the legs that run work of their own: the PCIe-inclusive rate (a fresh upload before the untimed pass), the ABI leg, the parity
+sample against the oracle, the coverage all-reduce leg, the CPU baseline and the byte-for-byte comparison with the reference
+program; in a plain run their fields are null.
+
+`--dump-outputs DIR`: after the timed steps, what the last step computed as gm_batch_raw_hits hands it to a caller (per read:
+status, self score, top score; per accepted candidate: read, position, strand, score, seed step), for a fixed seeded sample of
+the reads, as DIR/<name>.npy in float32 / float64 (64 MB at most).  The reads and the reference are seeded, so two builds run with
+the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -375,8 +386,37 @@ def reference_key(a):
     return f"g{a.genome_mbp:g}m_c{a.contigs}_s42" + ("r" if a.repeats else "")
 
 
-def run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup):
-    """one flag set on the resident reference + reads: timed steps, ABI leg, parity sample, all-reduce, CPU baseline -> the JSON dict"""
+def dump_outputs(batch, n_reads, out_dir, max_bytes=64 << 20, sample=1 << 18):
+    """what the last map_device left on the device, as gm_batch_raw_hits hands it to a caller, for a seeded sample of the reads
+    (the same reads every run): per read status / self score / top score, per accepted candidate read / position / strand / score /
+    seed step; positions and read indices as float64 (exact up to 2^53), the rest float32.  The sample halves until it fits max_bytes."""
+    hits, status, self_score, top = batch.raw_hits()
+    order = np.random.default_rng(20240601).permutation(n_reads)
+    per_read = np.bincount(hits["read"], minlength=n_reads)
+    k = min(sample, n_reads)
+    while True:
+        pick = np.sort(order[:k])
+        n_hits = int(per_read[pick].sum())
+        if k == 1 or k * (8 + 3 * 4) + n_hits * (2 * 8 + 3 * 4) <= max_bytes:
+            break
+        k //= 2
+    keep = np.zeros(n_reads, bool)
+    keep[pick] = True
+    h = hits[keep[hits["read"]]]
+    arrays = {"read_index": pick.astype(np.float64), "status": status[pick].astype(np.float32),
+              "self_score": self_score[pick].astype(np.float32), "top_score": top[pick].astype(np.float32),
+              "hit_read": h["read"].astype(np.float64), "hit_pos": h["pos"].astype(np.float64),
+              "hit_strand": h["strand"].astype(np.float32), "hit_score": h["score"].astype(np.float32),
+              "hit_step": h["step"].astype(np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    log(f"[bench] outputs of the last step: {len(pick)} of {n_reads} reads, {len(h)} of {len(hits)} hits -> {out_dir}")
+
+
+def run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup, dump_dir=None):
+    """one flag set on the resident reference + reads: timed steps (+ outputs of the last one); with --full also the PCIe-inclusive
+    pass, ABI leg, parity sample, all-reduce, CPU baseline -> the JSON dict"""
     barrier = gd.barrier
     for kv in a.opt:
         g.set_option(*kv.split("=", 1))
@@ -387,12 +427,14 @@ def run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup)
     batch.upload(p, B, Q, Ln)                   # reads resident in HBM from here on
     ix.coverage_reset(p.bin_size)
     torch.cuda.synchronize()
-    # PCIe-inclusive rate (never `value`): host -> HBM upload of the batch + one pass, measured once outside the timed region
+    # one pass before the warm-up in every run, so that the timed steps start from the same state whatever --warmup is; with --full
+    # the batch is uploaded again first and the two give the PCIe-inclusive rate (never `value`), measured outside the timed region
     t_up = time.perf_counter()
-    batch.upload(p, B, Q, Ln)
+    if a.full:
+        batch.upload(p, B, Q, Ln)
     batch.map_device(p)
     torch.cuda.synchronize()
-    pcie_inclusive = a.reads / (time.perf_counter() - t_up)
+    pcie_inclusive = a.reads / (time.perf_counter() - t_up) if a.full else None
     log(f"[bench] rank {rank}: setup {time.time() - t_setup:.1f} s, index {ix.info.hbm_bytes / 1e9:.2f} GB in HBM, {a.reads} reads resident")
 
     for _ in range(a.warmup):
@@ -411,16 +453,18 @@ def run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup)
     counters = batch.counters()
     kernel_path = batch.path()
     batch.set_profiling(False)
+    if dump_dir and rank == 0:
+        dump_outputs(batch, a.reads, dump_dir)
 
     # the path the ABI exports to a host driver (N = 1 only: it is a per-GPU figure and the host is shared)
     abi = None
-    if a.abi_reads > 0 and world == 1:
+    if a.full and a.abi_reads > 0 and world == 1:
         abi = abi_rate(g, ix, p, B, Q, Ln, a.abi_reads, a.abi_block, a.abi_threads, torch, a.abi_in_flight, a.abi_passes)
         log(f"[bench] ABI leg: {abi}")
 
     # self-check at the bench's own size: a sample of the benchmark reads against the oracle (rank 0, outside the timed region)
     parity = None
-    if a.parity_sample > 0 and rank == 0:
+    if a.full and a.parity_sample > 0 and rank == 0:
         parity = parity_sample(g, ix, p, fa, B, Q, Ln, a.read_len, kw, a.parity_sample, min(a.abi_block, 262144))
         log(f"[bench] parity sample: {parity}")
         if parity and parity["mismatches"]:
@@ -432,7 +476,7 @@ def run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup)
     # (one common place, one own place); afterwards the pattern is checked bin by bin and the reduced track's total against the
     # sum of the per-rank totals.
     allreduce = None
-    if world > 1 or os.environ.get("GM_FORCE_DIST") == "1":
+    if a.full and (world > 1 or os.environ.get("GM_FORCE_DIST") == "1"):
         import torch.distributed as tdist
         ix.coverage_reset(p.bin_size)
         if p.mode:
@@ -514,7 +558,7 @@ def run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup)
                         traffic=traffic, traffic_source=traffic_source, avg_kernel_ms=round(per_kernel[dom]["ms"], 4),
                         alg_bytes_per_launch=int(per_kernel[dom]["alg_bytes"]))
         cpu = None
-        if a.cpu_seconds > 0 and world == 1:         # rank 0 at N = 1 only
+        if a.full and a.cpu_seconds > 0 and world == 1:         # rank 0 at N = 1 only
             threads = a.cpu_threads or min(16, os.cpu_count() or 1)
             if a.cpu_kind in ("auto", "reference"):
                 cpu = cpu_baseline_reference(fa, B, Q, a.read_len, a, a.cpu_seconds, threads, wd)
@@ -559,7 +603,7 @@ def run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup)
             "kernels": {k: {"ms_per_step": round(v["ms_per_step"], 4), "launches_per_step": v["launches"] // a.steps, "alg_GBps": round(v["GBps"], 2)} for k, v in per_kernel.items()},
             "counters_per_step": counters,
             "coverage_allreduce": allreduce,
-            "pcie_inclusive_reads_per_s": round(pcie_inclusive, 1),
+            "pcie_inclusive_reads_per_s": round(pcie_inclusive, 1) if pcie_inclusive else None,
         }
     batch.destroy()
     for kv in a.opt:
@@ -572,8 +616,13 @@ def run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup)
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beside the headline: PCIe-inclusive pass, ABI leg, parity sample, coverage all-reduce, CPU baseline, "
+                         "comparison with the reference program (a plain run leaves their fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (a seeded sample of the reads) as DIR/<name>.npy")
     ap.add_argument("--genome-mbp", type=float, default=3100.0)
     ap.add_argument("--contigs", type=int, default=24)
     ap.add_argument("--repeats", action="store_true", help="repeat-rich reference (SURVEY.md 8d): 10 %% of the bases from 1000 families of 300-bp elements, 5 %% divergence")
@@ -613,9 +662,12 @@ def setup_reference(a, g, gd, torch, local):
         os.makedirs(wd, exist_ok=True)
         if not os.path.exists(ready):
             log(f"[bench] generating {a.genome_mbp:g} Mbp {'repeat-rich ' if a.repeats else ''}reference and building its index (once; untimed)")
+            t0 = time.time()
             make_genome(fa, a.genome_mbp, 42, a.contigs, a.repeats)
+            t1 = time.time()
             g.index_build(fa)
             open(ready, "w").write("ok\n")
+            log(f"[bench] reference written in {t1 - t0:.1f} s, index built in {time.time() - t1:.1f} s")
     else:
         while not os.path.exists(ready):
             time.sleep(1.0)
@@ -625,6 +677,8 @@ def setup_reference(a, g, gd, torch, local):
 def main():
     ap = build_parser()
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import gnumap_amd as g
@@ -649,7 +703,7 @@ def main():
     B, Q, Ln = make_reads(codes_t, a.reads, a.read_len, gd.read_seed(1000, rank), dev)
     del codes_t
     torch.cuda.empty_cache()
-    out = run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup)
+    out = run_config(a, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, t_setup, a.dump_outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     for extra in a.also:                                     # same reference (and its flags), same reads, other mapping flags
@@ -664,6 +718,7 @@ def main():
                 base.append(x)
         a2 = ap.parse_args(base + shlex.split(extra))
         a2.also = []
+        a2.dump_outputs = None
         for fixed in ("genome_mbp", "contigs", "repeats", "reads", "read_len", "locate", "workdir"):
             setattr(a2, fixed, getattr(a, fixed))
         o2 = run_config(a2, g, gd, torch, ix, fa, wd, B, Q, Ln, dev, rank, world, time.time())

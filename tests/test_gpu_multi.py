@@ -86,7 +86,7 @@ def test_bench_allreduce_leg_with_real_coverage(extra, tmp_path):
     all-reduced in place, reduced totals = sum of the per-rank totals; the parity sample of the same run has no mismatch"""
     env = dict(os.environ, GM_FORCE_DIST="1", GM_BENCH_DIR=str(tmp_path), MASTER_ADDR="127.0.0.1", MASTER_PORT="29591")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--genome-mbp", "6", "--contigs", "3", "--reads", "40000", "--mer", "9", "--jump", "5",
-                        "--steps", "1", "--cpu-seconds", "0", "--abi-reads", "16384", "--abi-block", "8192", "--parity-sample", "24"] + extra,
+                        "--steps", "1", "--full", "--cpu-seconds", "0", "--abi-reads", "16384", "--abi-block", "8192", "--parity-sample", "24"] + extra,
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2500:]
     j = json.loads(r.stdout.strip().splitlines()[-1])

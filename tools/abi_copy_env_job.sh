@@ -1,6 +1,6 @@
 # ABI leg under the HIP runtime's copy-path switches (the leg's uploads run as blit kernels at 34 GB/s: profiles/r04_abi_timeline.txt).
 # 100 Mbp / -m 12 (k_vote_pair, same per-block device work as the headline; the leg is copy-bound), one process per setting.
-B="python3 bench.py --genome-mbp 100 --contigs 6 --mer 12 --steps 2 --cpu-seconds 0 --parity-sample 16 --reads 8388608 --abi-reads 8388608 --abi-passes 6"
+B="python3 bench.py --full --genome-mbp 100 --contigs 6 --mer 12 --steps 2 --cpu-seconds 0 --parity-sample 16 --reads 8388608 --abi-reads 8388608 --abi-passes 6"
 run() {  # name, env assignments...
   name=$1; shift
   env "$@" timeout -k 10 200 $B > gpurun_out/abienv_$name.json 2> gpurun_out/abienv_$name.err || echo "$name: rc $?"

@@ -1,4 +1,4 @@
-B="python bench.py --steps 2 --cpu-seconds 0 --parity-sample 0 --reads 12582912 --abi-reads 12582912 --abi-passes 8 --abi-threads 2"
+B="python bench.py --full --steps 2 --cpu-seconds 0 --parity-sample 0 --reads 12582912 --abi-reads 12582912 --abi-passes 8 --abi-threads 2"
 timeout 250 $B --abi-in-flight 3 --abi-block 1048576 > gpurun_out/abi_a.json 2> gpurun_out/abi_a.err
 timeout 250 $B --abi-in-flight 2 --abi-block 2097152 > gpurun_out/abi_b.json 2> gpurun_out/abi_b.err
 timeout 250 $B --abi-in-flight 2 --abi-block 4194304 > gpurun_out/abi_c.json 2> gpurun_out/abi_c.err

@@ -2,7 +2,7 @@
 # Collect the measurements kept under profiles/ (run on an MI355X box from the repo root):
 #   tools/collect_profiles.sh <tag>        e.g. r01b  ->  profiles/<tag>_*  and profiles/pmc_latest.json
 # Kernel trace + stats, the PMC passes (each counter set in its own run, never mixed with a trace domain other than the kernel
-# trace), the sampled phase clocks of the vote kernel, and a plain bench.py line.  Raw output goes to gpurun_out/<tag>/.
+# trace), the sampled phase clocks of the vote kernel, and a full bench.py line (--full).  Raw output goes to $OUT below.
 set -eo pipefail
 TAG=${1:-rNN}
 ROOT=$(pwd)
@@ -14,10 +14,10 @@ KEY=${KEY:-g3100m_c24_s42_L100_m14_full}    # workload key of profiles/pmc_lates
 cd /tmp                                            # rocprofv3 scratch files go to the cwd
 B="python3 $ROOT/bench.py ${BENCH_ARGS:-}"
 if [ "${MATRIX:-1}" != "only" ]; then
-echo "[collect] plain bench"
-$B > "$OUT/bench.json" 2> "$OUT/bench.log"
+echo "[collect] full bench line"
+$B --full > "$OUT/bench.json" 2> "$OUT/bench.log"
 echo "[collect] kernel trace + stats"
-# the same workload and timed region as the plain run; only the two side legs (CPU baseline, ABI leg: extra launches of the same
+# the same workload and timed region as the full run; only the two side legs (CPU baseline, ABI leg: extra launches of the same
 # kernels on 262 144-read blocks) are off so that the per-kernel averages are those of the timed steps
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" ${BENCH_ARGS:-} --cpu-seconds 0 --abi-reads 0 --parity-sample 0 > "$OUT/bench_traced.json" 2> "$OUT/stats.log"
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum" TCC_EA0_RDREQ_sum; do
@@ -38,7 +38,7 @@ if [ "${MATRIX:-1}" = "1" ] || [ "${MATRIX:-1}" = "only" ]; then
     echo "[collect] bench matrix over the BASELINE configurations (10 M reads per step, CPU baseline 5 s each; rows that share a reference and its reads run in one process: --also)"
     : > "$OUT/matrix.jsonl"
     C="--cpu-seconds 5 --abi-reads 4194304"
-    run() { echo "[collect]   bench.py $*"; $B "$@" >> "$OUT/matrix.jsonl" 2>> "$OUT/matrix.log"; }
+    run() { echo "[collect]   bench.py --full $*"; $B --full "$@" >> "$OUT/matrix.jsonl" 2>> "$OUT/matrix.log"; }
     if [ "${MATRIX_PART:-all}" != "2" ]; then
     # human scale, i.i.d.: the default run, --no_nw (configs[4] shape), the flags SURVEY 8(d) suggests for human
     run $C --also="--no-nw $C" --also="--mer 20 --jump 10 --max-kmer-hits 150 $C" --also="--mer 20 --jump 10 --max-kmer-hits 150 --no-nw $C" --also="--max-kmer-hits 150 $C" --also="--opt GM_VOTE_PAIR=0 $C" --also="--opt GM_NW=lane $C"

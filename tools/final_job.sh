@@ -2,7 +2,7 @@
 set -e
 MATRIX=0 bash tools/collect_profiles.sh r04 > gpurun_out/collect_r04.log 2>&1 || { tail -20 gpurun_out/collect_r04.log; exit 1; }
 tail -3 gpurun_out/collect_r04.log
-C="--cpu-seconds 5 --abi-reads 4194304"
+C="--full --cpu-seconds 5 --abi-reads 4194304"
 : > gpurun_out/r04_matrix_part3.jsonl
 python3 bench.py --genome-mbp 100 --contigs 6 --mer 10 $C --also="--mer 10 --no-nw $C" >> gpurun_out/r04_matrix_part3.jsonl 2>> gpurun_out/r04_matrix_part3.log
 python3 bench.py --genome-mbp 156 --contigs 1 --mer 10 $C --also="--mer 10 --max-kmer-hits 150 $C" >> gpurun_out/r04_matrix_part3.jsonl 2>> gpurun_out/r04_matrix_part3.log

@@ -2,7 +2,7 @@
 set -e
 python -m pytest tests -q -m gpu -x > gpurun_out/r4_full_t3.log 2>&1 || { tail -30 gpurun_out/r4_full_t3.log; exit 1; }
 tail -2 gpurun_out/r4_full_t3.log
-C="--cpu-seconds 5 --abi-reads 4194304"
+C="--full --cpu-seconds 5 --abi-reads 4194304"
 : > gpurun_out/r04_matrix_part4.jsonl
 python3 bench.py --genome-mbp 156 --contigs 1 --mer 10 $C --also="--mer 10 --max-kmer-hits 150 $C" >> gpurun_out/r04_matrix_part4.jsonl 2>> gpurun_out/r04_matrix_part4.log
 python3 -c "

@@ -7,8 +7,8 @@ TAG=$1
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp; cd /tmp
 A14="--locate sampled --reads 1000000 --steps 3 --abi-reads 0 --cpu-seconds 5"
 A20="--locate sampled --reads 4000000 --steps 3 --abi-reads 0 --cpu-seconds 5 --mer 20 --jump 10 --max-kmer-hits 150"
-python3 "$ROOT/bench.py" $A14 > "$OUT/bench_m14.json" 2> "$OUT/bench_m14.log"
-python3 "$ROOT/bench.py" $A20 > "$OUT/bench_m20.json" 2> "$OUT/bench_m20.log"
+python3 "$ROOT/bench.py" --full $A14 > "$OUT/bench_m14.json" 2> "$OUT/bench_m14.log"
+python3 "$ROOT/bench.py" --full $A20 > "$OUT/bench_m20.json" 2> "$OUT/bench_m20.log"
 for cfg in m14 m20; do
     if [ $cfg = m14 ]; then A="$A14"; else A="$A20"; fi
     rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$cfg" -- python3 "$ROOT/bench.py" $A --cpu-seconds 0 --parity-sample 0 > "$OUT/traced_$cfg.json" 2> "$OUT/stats_$cfg.log"

@@ -1,7 +1,7 @@
 set -e
 python -m pytest tests/test_gpu_bucket.py -x -q > gpurun_out/r4_prep_t.log 2>&1 || { tail -30 gpurun_out/r4_prep_t.log; exit 1; }
 tail -2 gpurun_out/r4_prep_t.log
-C="--cpu-seconds 0 --abi-reads 0"
+C="--full --cpu-seconds 0 --abi-reads 0"
 python bench.py --steps 10 $C > gpurun_out/r4_prep_b.json 2> gpurun_out/r4_prep_b.err
 python bench.py --steps 5 --genome-mbp 100 --contigs 6 --mer 12 --jump 6 $C > gpurun_out/r4_prep_c.json 2> gpurun_out/r4_prep_c.err
 python -c "

@@ -1,5 +1,5 @@
 set -e
-C="--cpu-seconds 0 --abi-reads 0 --steps 3"
+C="--full --cpu-seconds 0 --abi-reads 0 --steps 3"
 python bench.py --genome-mbp 100 --contigs 6 --mer 10 $C --also="--mer 10 --opt GM_NW=lane $C" > gpurun_out/r4_rows_a.jsonl 2> gpurun_out/r4_rows_a.err
 python bench.py --genome-mbp 156 --contigs 1 --mer 10 --max-kmer-hits 150 $C > gpurun_out/r4_rows_b.jsonl 2> gpurun_out/r4_rows_b.err
 python bench.py --mer 20 --jump 10 --max-kmer-hits 150 $C --also="--read-len 150 --reads 4000000 $C" > gpurun_out/r4_rows_c.jsonl 2> gpurun_out/r4_rows_c.err

@@ -1,6 +1,6 @@
 # one box, several builds of the slots kernels (tools/ubench/lib_*.so: scratch builds): configs[1] and chrX-shape rows each
 set -e
-C="--cpu-seconds 0 --abi-reads 0"
+C="--full --cpu-seconds 0 --abi-reads 0"
 : > gpurun_out/ab_rows.jsonl
 cp gnumap_amd/libgnumap_hip.so /tmp/lib_main.so
 for f in /tmp/lib_main.so tools/ubench/lib_*.so; do

@@ -1,6 +1,6 @@
 # quick A/B of the slots kernels: configs[1] and the chrX shape, with / without the line-aligned copy of the suffix-array runs; GM_TRACE shows what was built
 set -e
-C="--cpu-seconds 0 --abi-reads 0"
+C="--full --cpu-seconds 0 --abi-reads 0"
 : > gpurun_out/pp_rows.jsonl; : > gpurun_out/pp_rows.err
 for e in "" "--opt GM_ASA=0"; do
   GM_TRACE=1 timeout -k 10 300 python bench.py --steps 5 --genome-mbp 100 --contigs 6 --mer 10 --jump 5 $C $e >> gpurun_out/pp_rows.jsonl 2>> gpurun_out/pp_rows.err
