@@ -345,3 +345,14 @@ __device__ __forceinline__ const GmKArgs* gm_kargs() {
     return nullptr;
 #endif
 }
+
+// grid of a persistent kernel: exactly the workgroups the device keeps resident (CUs x workgroups per CU for this kernel and
+// its dynamic LDS).  A larger static grid makes the surplus workgroups run as a second, half-empty round.
+template <class K>
+static uint32_t resident_grid(K kernel, int threads, size_t dyn_lds, uint32_t fallback) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fallback;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return fallback;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, dyn_lds) != hipSuccess || per_cu <= 0) return fallback;
+    return (uint32_t)cus * (uint32_t)per_cu;
+}

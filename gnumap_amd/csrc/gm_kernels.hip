@@ -3247,17 +3247,6 @@ __global__ void __launch_bounds__(256) k_locate(GmDevIndex ix, const uint32_t* r
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
-// grid of a persistent kernel: exactly the workgroups the device keeps resident (CUs x workgroups per CU for this kernel and
-// its dynamic LDS).  A larger static grid makes the surplus workgroups run as a second, half-empty round.
-template <class K>
-static uint32_t resident_grid(K kernel, int threads, size_t dyn_lds, uint32_t fallback) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fallback;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return fallback;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, dyn_lds) != hipSuccess || per_cu <= 0) return fallback;
-    return (uint32_t)cus * (uint32_t)per_cu;
-}
-
 
 int gmk_expand_full_sa(const GmDevIndex& ix, uint32_t* full_sa, void* stream) {
     uint32_t n_sa = (uint32_t)(((uint64_t)ix.seq_len + ix.sa_mask + 1) >> ix.sa_shift);

@@ -265,9 +265,14 @@ int gmk_nw_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b,
     if (b.n == 0) return 0;
     const uint32_t ntab = b.illumina_until ? 2u : 1u;
     const size_t lds = (size_t)ntab * GM_NWR_TAB_BYTES;
+    // the workgroups stride over the candidates: one resident round of them (4 per CU for <13> with one table; fewer with two tables or
+    // for <19>).  The earlier grid of n_cands / 1024 workgroups (10 449 at 10.7 M candidates) left its last round a fifth full and
+    // built the value table 10 times per CU: 2.04 -> 1.85 ms
     const uint32_t nw_fixed = (uint32_t)gm_opt_ll("GM_NW_GRID", 0);
-    const uint32_t grid = nw_fixed ? nw_fixed : std::min<uint32_t>(16384u, std::max<uint32_t>(2048u, n_cands / 1024u));
-    if (L <= 104) hipLaunchKernelGGL((k_nw_rows<13>), dim3(grid), dim3(256), lds, S_(stream), ix, p, b, L, ntab);
+    const bool narrow = L <= 104;
+    const uint32_t grid = nw_fixed ? nw_fixed
+                        : narrow ? resident_grid(k_nw_rows<13>, 256, lds, 1024u) : resident_grid(k_nw_rows<19>, 256, lds, 768u);
+    if (narrow) hipLaunchKernelGGL((k_nw_rows<13>), dim3(grid), dim3(256), lds, S_(stream), ix, p, b, L, ntab);
     else hipLaunchKernelGGL((k_nw_rows<19>), dim3(grid), dim3(256), lds, S_(stream), ix, p, b, L, ntab);
     return (int)hipGetLastError();
 }
