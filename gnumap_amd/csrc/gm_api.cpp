@@ -820,7 +820,7 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     const uint32_t heavy_min = (uint32_t)gm_opt_ll("GM_HEAVY_MIN", 16384);
     const uint64_t heavy_budget = (uint64_t)gm_opt_ll("GM_HEAVY_BUDGET", 1ll << 27);
     dp.heavy_min = heavy_min;
-    bool use_bucket = false, use_pair = false; uint32_t bucket_reg = 0;
+    bool use_bucket = false, use_pair = false, pair_direct = false; uint32_t bucket_reg = 0;
     // seed lookup inside the vote kernels that take one read x strand per wave / workgroup (full SA, the k-mer table covering the
     // whole seed): no k_seed launch, no seed rows through HBM.  A k-mer that does not occur changes the positions of all later ones;
     // the wave then walks again round by round (gm_seed_rewalk_ool), one probe round trip per failing k-mer.  That stays rare while
@@ -845,14 +845,18 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
         if (use_bucket) { dp.fused = 1; bucket_reg = max_reg; } else dp.bucket = nullptr;
         // ... two reads per wavefront (gm_pair.hip) where a strand has at most 16 seeds; GM_VOTE_PAIR=0: one read per wavefront always
         use_pair = use_bucket && !dp.bucket_ctx && max_reg <= 16 && !(p->nw && p->fast) && !gm_opt_is("GM_VOTE_PAIR", "0") && !(dp.dbg & (64 | 256 | 512 | 1024 | 2048));       // (GM_DBG 4096 .. 32768: timing experiments of k_vote_pair)
-        if (use_pair && (b->pair_fb.ensure((size_t)b->n + 64) || b->pair_list.ensure(((size_t)b->n + 16) * 4))) return GM_E_NOMEM;
+        // hand-off of k_vote_pair's results: straight into the candidate shards and the flagged reads' list at each 16-pair flush (default),
+        // or GM_PAIR_HANDOFF=gather: own candidate slots + one flag byte per read, read back by k_cand_gather / k_pair_collect / k_heavy_collect
+        pair_direct = use_pair && !gm_opt_is("GM_PAIR_HANDOFF", "gather");
+        if (use_pair && b->pair_list.ensure(((size_t)b->n + 16) * 4)) return GM_E_NOMEM;
+        if (use_pair && !pair_direct && b->pair_fb.ensure((size_t)b->n + 64)) return GM_E_NOMEM;
         b->use_pack = dp.fused != 0;
         if (b->use_pack && b->pack.ensure((size_t)b->n * gm_pack_words(b->stride) * 4 + 64)) return GM_E_NOMEM;
     }
     // the one-wave vote kernels leave their candidates in per read x strand slots (no bump counter on the wave's critical path)
     {
         const bool fixed_ok = !gm_opt_is("GM_VOTE_FIXED", "0");
-        b->use_fixed = fixed_ok && (use_bucket || ((dense == 1 || dense == 2) && !gm_opt("GM_VOTE_KERNEL")));      // k_vote_bucket, k_vote_tiny*, k_vote_slots (all forms)
+        b->use_fixed = fixed_ok && !pair_direct && (use_bucket || ((dense == 1 || dense == 2) && !gm_opt("GM_VOTE_KERNEL")));      // k_vote_bucket, k_vote_tiny*, k_vote_slots (all forms)
         if (b->use_fixed) {
             const size_t cap_before = b->fixed_cands.cap;       // by CAPACITY: hipFree + a larger hipMalloc may hand back the same base address
             if (b->fixed_cands.ensure(((2 * (size_t)b->n + 63) / 64) * 64 * GM_FIXED_C * sizeof(GmCand)) || b->fixed_cnt.ensure(2 * (size_t)b->n + 64)) return GM_E_NOMEM;
@@ -896,7 +900,8 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     unsigned long long* const hs_ctr = reinterpret_cast<unsigned long long*>(b->h_stat.as<uint8_t>() + 64);
     auto collect_heavy_enqueue = [&]() -> int {      // (the count is read back with the phase's status words)
         HIPCHK(hipMemsetAsync(b->small.as<uint32_t>() + 3, 0, 4, st));
-        KCHK(gmk_heavy_collect(b->dev, heavy_min, b->small.as<uint32_t>() + 3, b->heavy_list.as<uint32_t>(), dp.fused, st));
+        KCHK(gmk_heavy_collect(b->dev, heavy_min, b->small.as<uint32_t>() + 3, b->heavy_list.as<uint32_t>(), dp.fused,
+                               pair_direct ? b->pair_list.as<uint32_t>() + 4 : nullptr, pair_direct ? b->pair_list.as<uint32_t>() : nullptr, st));
         return GM_OK;
     };
     auto fetch_heavy = [&](uint32_t nh) -> int {
@@ -971,10 +976,11 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
         {
             KTimer t(b, GM_K_VOTE, st);
             if (use_bucket && use_pair) {
-                // two reads per wavefront for the reads without complications; the flagged ones go through k_vote_bucket
-                HIPCHK(hipMemsetAsync(b->pair_fb.p, 0, (size_t)b->n + 16, st));
+                // two reads per wavefront for the reads without complications; the flagged ones go through k_vote_bucket (direct hand-off:
+                // no own slots - k_vote_bucket and the list kernel append their candidates and list entries as they go)
+                if (!pair_direct) HIPCHK(hipMemsetAsync(b->pair_fb.p, 0, (size_t)b->n + 16, st));
                 HIPCHK(hipMemsetAsync(b->pair_list.p, 0, 16, st));
-                KCHK(gmk_vote_pair(ix->dev, dp, b->dev, bucket_reg, b->pair_fb.as<uint8_t>(), b->pair_list.as<uint32_t>() + 4, b->pair_list.as<uint32_t>(), st));
+                KCHK(gmk_vote_pair(ix->dev, dp, b->dev, bucket_reg, pair_direct ? nullptr : b->pair_fb.as<uint8_t>(), b->pair_list.as<uint32_t>() + 4, b->pair_list.as<uint32_t>(), st));
                 KCHK(gmk_vote_bucket(ix->dev, dp, b->dev, bucket_reg, b->pair_list.as<uint32_t>() + 4, b->pair_list.as<uint32_t>(), st));
                 KCHK(gmk_vote_list(ix->dev, dp, b->dev, use_full, st));
             } else if (use_bucket) { KCHK(gmk_vote_bucket(ix->dev, dp, b->dev, bucket_reg, nullptr, nullptr, st)); KCHK(gmk_vote_list(ix->dev, dp, b->dev, use_full, st)); }

@@ -21,9 +21,11 @@
 #include "gm_internal.h"
 
 // sum_counters: the seeds were looked up inside the vote kernel (GmDevParams::fused), which leaves the per read x strand counts only:
-// the work counters k_seed keeps (one k-mer and one table probe per seed; SA hits) are summed here, one atomic per wave
+// the work counters k_seed keeps (one k-mer and one table probe per seed; SA hits) are summed here, one atomic per wave.
+// rlist / n_rlist (k_vote_pair's direct hand-off): only the READS of this list are visited, both strands each - k_vote_pair routed and
+// counted all others itself (none of them is heavy: it flags a strand with more than heavy_min SA hits)
 __global__ void __launch_bounds__(256) k_heavy_collect(GmDevBatch b, uint32_t heavy_min, uint32_t* n_heavy, uint32_t* heavy_list /* {rs, n_seeds, SA hits} triples */,
-                                                       int sum_counters) {
+                                                       int sum_counters, const uint32_t* rlist, const uint32_t* n_rlist) {
     unsigned long long a = 0, e = 0;
     const uint32_t n2 = 2 * b.n, n4 = n2 >> 2;           // four read x strands per thread and step: one 8-byte and one 16-byte load
     auto take = [&](uint32_t rs, uint32_t ns, uint32_t ne) {
@@ -33,12 +35,22 @@ __global__ void __launch_bounds__(256) k_heavy_collect(GmDevBatch b, uint32_t he
         heavy_list[3 * j] = rs; heavy_list[3 * j + 1] = ns; heavy_list[3 * j + 2] = ne;
         b.n_seeds[rs] = 0;                               // the ordinary vote kernels see nothing to do
     };
-    for (uint32_t q = blockIdx.x * 256 + threadIdx.x; q < n4; q += gridDim.x * 256) {
-        const uint2 s4 = reinterpret_cast<const uint2*>(b.n_seeds)[q];
-        const uint4 e4 = reinterpret_cast<const uint4*>(b.n_entries)[q];
-        take(4 * q, s4.x & 0xFFFFu, e4.x); take(4 * q + 1, s4.x >> 16, e4.y); take(4 * q + 2, s4.y & 0xFFFFu, e4.z); take(4 * q + 3, s4.y >> 16, e4.w);
+    if (rlist) {
+        const uint32_t nl = *n_rlist;
+        for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < nl; j += gridDim.x * 256) {
+            const uint32_t r = rlist[j];
+            const uint32_t s2 = reinterpret_cast<const uint32_t*>(b.n_seeds)[r];
+            const uint2 e2 = reinterpret_cast<const uint2*>(b.n_entries)[r];
+            take(2 * r, s2 & 0xFFFFu, e2.x); take(2 * r + 1, s2 >> 16, e2.y);
+        }
+    } else {
+        for (uint32_t q = blockIdx.x * 256 + threadIdx.x; q < n4; q += gridDim.x * 256) {
+            const uint2 s4 = reinterpret_cast<const uint2*>(b.n_seeds)[q];
+            const uint4 e4 = reinterpret_cast<const uint4*>(b.n_entries)[q];
+            take(4 * q, s4.x & 0xFFFFu, e4.x); take(4 * q + 1, s4.x >> 16, e4.y); take(4 * q + 2, s4.y & 0xFFFFu, e4.z); take(4 * q + 3, s4.y >> 16, e4.w);
+        }
+        if (blockIdx.x == 0 && threadIdx.x < (n2 & 3u)) { const uint32_t rs = 4 * n4 + threadIdx.x; take(rs, b.n_seeds[rs], b.n_entries[rs]); }
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n2 & 3u)) { const uint32_t rs = 4 * n4 + threadIdx.x; take(rs, b.n_seeds[rs], b.n_entries[rs]); }
     if (sum_counters) {                                  // one set of atomics per workgroup of a small grid (they all hit one line)
         __shared__ unsigned long long s_a[4], s_e[4];
 #pragma unroll
@@ -129,9 +141,13 @@ __global__ void __launch_bounds__(256) k_heavy_runs(GmDevBatch b, const uint32_t
 
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-int gmk_heavy_collect(const GmDevBatch& b, uint32_t heavy_min, uint32_t* n_heavy, uint32_t* heavy_list, int sum_counters, void* stream) {
+int gmk_heavy_collect(const GmDevBatch& b, uint32_t heavy_min, uint32_t* n_heavy, uint32_t* heavy_list, int sum_counters, const uint32_t* rlist, const uint32_t* n_rlist,
+                      void* stream) {
     if (b.n == 0) return 0;
-    hipLaunchKernelGGL(k_heavy_collect, dim3((uint32_t)std::min<unsigned long long>((2ull * b.n / 4 + 255) / 256 + 1, 1024ull)), dim3(256), 0, S_(stream), b, heavy_min, n_heavy, heavy_list, sum_counters);
+    // (list form: the count is on the device; the list is a few reads per thousand - a quarter of the full form's grid is plenty)
+    const unsigned long long items = rlist ? (b.n + 3ull) / 4 : 2ull * b.n / 4;
+    const uint32_t grid = (uint32_t)std::min<unsigned long long>((items + 255) / 256 + 1, rlist ? 256ull : 1024ull);
+    hipLaunchKernelGGL(k_heavy_collect, dim3(grid), dim3(256), 0, S_(stream), b, heavy_min, n_heavy, heavy_list, sum_counters, rlist, n_rlist);
     return (int)hipGetLastError();
 }
 

@@ -184,7 +184,8 @@ int gmk_vote_bucket(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch
 int gmk_vote_pair(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t max_reg, uint8_t* fallback, uint32_t* list, uint32_t* n_list, void* stream);
 int gmk_vote_list(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, int use_full_sa, void* stream);     // k_vote_fast_list over b.big_list
 // gm_heavy.hip: read x strands with more than heavy_min SA hits (sorted-key vote path)
-int gmk_heavy_collect(const GmDevBatch& b, uint32_t heavy_min, uint32_t* n_heavy, uint32_t* heavy_list /* {rs, n_seeds, SA hits} triples */, int sum_counters, void* stream);
+int gmk_heavy_collect(const GmDevBatch& b, uint32_t heavy_min, uint32_t* n_heavy, uint32_t* heavy_list /* {rs, n_seeds, SA hits} triples */, int sum_counters,
+                      const uint32_t* rlist /* nullptr: all 2n read x strands; else only the reads listed here (device count n_rlist) */, const uint32_t* n_rlist, void* stream);
 inline uint32_t gm_pack_w2(uint32_t stride) { return (stride + 15u) / 16u; }
 inline uint32_t gm_pack_words(uint32_t stride) { const uint32_t w2 = gm_pack_w2(stride); return (1u + 2u * (w2 + 1u) + 3u) & ~3u; }
 size_t gmk_heavy_sort_temp_bytes(size_t n_keys);

@@ -2854,13 +2854,24 @@ __global__ void __launch_bounds__(256) k_shard_stats(GmDevBatch b, uint32_t* out
     __shared__ uint32_t s_sum[4], s_max[4];
     uint32_t sum = 0, mx = 0;
     unsigned long long dropped = 0;                       // word 1 of a shard: k-mers tried and dropped by the walks of k_vote_bucket (taken out as they are summed)
+    unsigned long long seeds = 0, hits = 0;               // words 2 / 3: seeds and SA hits of the read x strands k_vote_pair kept (direct hand-off; likewise)
     for (uint32_t q = threadIdx.x; q < GM_NSHARD; q += 256) {
-        const uint32_t c = b.shard_cnt[(size_t)q * GM_SHARD_STRIDE]; sum += c; mx = c > mx ? c : mx;
-        const uint32_t d = b.shard_cnt[(size_t)q * GM_SHARD_STRIDE + 1]; if (d) { dropped += d; b.shard_cnt[(size_t)q * GM_SHARD_STRIDE + 1] = 0; }
+        uint32_t* const w = b.shard_cnt + (size_t)q * GM_SHARD_STRIDE;
+        const uint32_t c = w[0]; sum += c; mx = c > mx ? c : mx;
+        const uint32_t d = w[1]; if (d) { dropped += d; w[1] = 0; }
+        const uint32_t s2 = w[2], s3 = w[3]; if (s2 | s3) { seeds += s2; hits += s3; w[2] = 0; w[3] = 0; }
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { sum += __shfl_xor(sum, off); const uint32_t o = __shfl_xor(mx, off); mx = o > mx ? o : mx; dropped += __shfl_xor(dropped, off); }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = sum; s_max[threadIdx.x >> 6] = mx; if (dropped) { atomicAdd(&b.counters[GMK_KMERS], dropped); atomicAdd(&b.counters[GMK_TAB_LOOKUPS], dropped); } }
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off); const uint32_t o = __shfl_xor(mx, off); mx = o > mx ? o : mx; dropped += __shfl_xor(dropped, off);
+        seeds += __shfl_xor(seeds, off); hits += __shfl_xor(hits, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_sum[threadIdx.x >> 6] = sum; s_max[threadIdx.x >> 6] = mx;
+        if (dropped + seeds) { atomicAdd(&b.counters[GMK_KMERS], dropped + seeds); atomicAdd(&b.counters[GMK_TAB_LOOKUPS], dropped + seeds); }
+        if (seeds) atomicAdd(&b.counters[GMK_SEEDS], seeds);              // (as k_heavy_collect counts a seed: one k-mer, one table probe, one seed)
+        if (hits) atomicAdd(&b.counters[GMK_SA_HITS], hits);
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         out[0] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];

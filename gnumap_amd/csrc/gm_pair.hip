@@ -10,9 +10,15 @@
 //
 // Only the common case lives here: every k-mer at the regular positions occurs (and stays within -h), no record beyond its 28 inline
 // positions, no early position, at most 384 hits per strand, at most 16 seeds per strand, ACGT only, at most GMP_LCAP second arrivals.
-// A read with anything else is FLAGGED (one byte) and left untouched; k_pair_collect lists the flagged reads and k_vote_bucket - which
-// knows how to walk again, follow the suffix array, hand over to the list / heavy kernels - takes exactly those.  Same candidates,
-// same counters: the flagged reads are a few per thousand on an i.i.d. reference, more on repeats, and parity does not depend on how many.
+// A read with anything else is FLAGGED and left untouched; k_vote_bucket - which knows how to walk again, follow the suffix array, hand
+// over to the list / heavy kernels - takes exactly the flagged reads.  Same candidates, same counters: the flagged reads are a few per
+// thousand on an i.i.d. reference, more on repeats, and parity does not depend on how many.
+//
+// Hand-off (every 16 pairs = 64 read x strands, the "flush"): with own candidate slots (b.fixed_cands, GM_PAIR_HANDOFF=gather) the
+// group's first candidates go to their slots as whole lines, the flags to one byte per read, and k_cand_gather / k_pair_collect /
+// k_heavy_collect read all of it back.  Without (the default): the flush appends the group's candidates to its shard ((rs >> 6) as
+// k_cand_gather chose it) and its flagged reads to the list, one returning atomic each, and the work counters of the reads it kept
+// are summed per workgroup into shard counter words 2 / 3 (k_shard_stats adds them up); k_heavy_collect then visits the list only.
 //
 // Votes as in k_vote_bucket: one returning LDS atomic per hit into a 16384-bit filter of its strand (slot = low bits of the window
 // start), a second arrival's window start goes to the strand's key list unless it is the strand's latest key, one sweep per distinct key
@@ -26,6 +32,8 @@
 #define GMP_LCAP 16                      // second-or-later arrivals listed per strand; more: the read is flagged
 #define GMP_ECAP 384u                    // SA hits per strand voted on here
 #define GMP_FWORDS 512                   // filter words per strand
+#define GMP_XCAP 16                      // further candidates of a 16-pair group kept in LDS until its flush (16 x 16 bytes: 16 workgroups of
+                                         // 10 176 bytes still fit one CU's 160 KB)
 
 struct GmPairLds {
     uint4 filt[4 * GMP_FWORDS / 4];      // [4 strands][512 words]
@@ -37,6 +45,7 @@ struct GmPairLds {
     GmCand cbuf[64];
     uint32_t nebuf[64];
     uint16_t nsbuf[64];
+    GmCand xbuf[GMP_XCAP];               // direct hand-off: 2nd and later candidates of the group's read x strands (more: one atomic each)
 };
 
 __device__ __forceinline__ int gmp_lane_again() {
@@ -53,7 +62,8 @@ __device__ __forceinline__ uint4 gmp_zero4() {        // (made here: a hoisted z
 __device__ __forceinline__ uint32_t gmp_qbits(unsigned long long m, uint32_t qsh) { return (uint32_t)(m >> qsh) & 0xFFFFu; }
 
 template <int STEPS>
-__global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams p, GmDevBatch b, uint8_t* fallback, const uint32_t chunk /* pairs per workgroup, a multiple of 16 */) {
+__global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams p, GmDevBatch b, uint8_t* fallback, uint32_t* list, uint32_t* n_list,
+                                                     const uint32_t chunk /* pairs per workgroup, a multiple of 16 */) {
     __shared__ GmPairLds S;
     const uint32_t m = (uint32_t)p.mer, jump = (uint32_t)p.jump, w2 = b.pack_w2;
     const uint32_t cmask = m >= 16u ? 0xFFFFFFFFu : ((1u << (2u * m)) - 1u);
@@ -61,6 +71,9 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
     const uint4* const bucket = reinterpret_cast<const uint4*>(p.bucket);
     const uint32_t npairs = (b.n + 1u) >> 1;
     const uint32_t pr0 = blockIdx.x * chunk, pend = pr0 + chunk < npairs ? pr0 + chunk : npairs;
+    const bool direct = b.fixed_cands == nullptr;       // the hand-off (see the head of this file)
+    uint32_t fmask = 0, n_x = 0;                        // direct: flagged reads of the group (bit 2 x (pair & 15) + read), its candidates in xbuf
+    uint32_t acc_s = 0, acc_e = 0;                      // direct: seeds / SA hits of the workgroup's read x strands whose read stays here (wave-uniform)
     // Software pipeline over the CONSECUTIVE pairs of a workgroup (pairs pr0 .. pend - 1): while pair i is voted
     // on, the RECORDS of pair i + 1 are in flight (their codes come from the 2-bit words requested an iteration earlier) and the words of
     // pair i + 2 are requested - the vote phase's instructions and the two dependent HBM trips of a read no longer take turns.
@@ -116,6 +129,12 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
         const uint32_t rd = (uint32_t)lane >> 5, sd = ((uint32_t)lane >> 4) & 1u, qt = (uint32_t)lane >> 4, jj = (uint32_t)lane & 15u, g = ((uint32_t)lane >> 3) & 1u,
                        q = (uint32_t)lane & 7u, qbase = (uint32_t)lane & 48u, qsh = 16u * qt;
         const uint32_t r = 2u * pr + rd, rs = 2u * r + sd;
+        auto flag_reads = [&](const bool f) {           // (wave-uniform call: lane 0 / 32 of a flagged read say so)
+            if (direct) {
+                const unsigned long long fm = __builtin_amdgcn_ballot_w64(f);
+                fmask |= (((uint32_t)fm & 1u) | ((uint32_t)(fm >> 31) & 2u)) << (2u * (pr & 15u));
+            } else if (f) fallback[r] = 1;
+        };
         // this pair's state out of the pipeline registers, then the next pair's loads go out
         const uint32_t hdr = N_hdr, ns_q = N_ns;
         bool fb = N_fb;
@@ -160,7 +179,7 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
         if (rv && !fb_read && jj == 0u) { S.nsbuf[rs & 63u] = (uint16_t)(dead ? 0u : ns_q); S.nebuf[rs & 63u] = dead ? 0u : E_q; }
         bool vote = rv && !dead && !fb_read && ns_q != 0u;
         if (__builtin_amdgcn_ballot_w64(vote) == 0ull) {
-            if (rv && fb_read && jj == 0u && sd == 0u) fallback[r] = 1;
+            flag_reads(rv && fb_read && jj == 0u && sd == 0u);
             break;
         }
         if (p.dbg & 32768) break;                      // (GM_DBG 32768: timing experiment, stop before the votes)
@@ -233,7 +252,7 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
                 if (over_read) { fb_read = true; vote = false; lc_q = 0; }
             }
         }
-        if (rv && fb_read && jj == 0u && sd == 0u) fallback[r] = 1;
+        flag_reads(rv && fb_read && jj == 0u && sd == 0u);
         if (__builtin_amdgcn_ballot_w64(vote && lc_q != 0u) == 0ull || (p.dbg & 16384)) break;      // (GM_DBG 16384: timing experiment, no sweeps)       // no second arrival anywhere: no window start with two votes
         __syncthreads();
         // ---- sweeps: one per distinct key of a strand's list (all four strands in the same instructions) ----
@@ -273,8 +292,23 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
                 else step = votes;
                 GmCand c;
                 c.rs = rs; c.b = key; c.step = (uint16_t)step; c.flags = 4; c.pad = 0; c.score = 0.0f;
-                if (em && b.fixed_cands != nullptr && n_em == 0u) first_c = c;
-                else if (em && b.fixed_cands != nullptr && n_em < GM_FIXED_C) b.fixed_cands[GM_FIXED_AT(b, rs, n_em)] = c;
+                if (direct) {                             // the first candidate waits in cbuf, a further one in the group's LDS list (past its end: the shard directly)
+                    const bool ex = em && n_em != 0u;
+                    if (em && n_em == 0u) first_c = c;
+                    const unsigned long long xm = __builtin_amdgcn_ballot_w64(ex);
+                    if (xm != 0ull) {
+                        const uint32_t at = n_x + __builtin_amdgcn_mbcnt_hi((uint32_t)(xm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)xm, 0u));
+                        if (ex && at < GMP_XCAP) S.xbuf[at] = c;
+                        else if (ex) {
+                            const uint32_t xs = (rs >> 6) & (GM_NSHARD - 1);
+                            const uint32_t at2 = atomicAdd(&b.shard_cnt[xs * GM_SHARD_STRIDE], 1u);
+                            if (at2 < b.cand_region) b.cands[(size_t)xs * b.cand_region + at2] = c;
+                        }
+                        n_x += (uint32_t)__popcll(xm);
+                    }
+                }
+                else if (em && n_em == 0u) first_c = c;
+                else if (em && n_em < GM_FIXED_C) b.fixed_cands[GM_FIXED_AT(b, rs, n_em)] = c;
                 else if (em) {
                     const uint32_t at = atomicAdd(&b.shard_cnt[shard * GM_SHARD_STRIDE], 1u);
                     if (at < b.cand_region) b.cands[(size_t)shard * b.cand_region + at] = c;
@@ -282,10 +316,12 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
                 if (em) ++n_em;
             }
         }
-        if (jj == 0u && b.fixed_cands != nullptr && n_em != 0u) {
-            first_c.pad = (uint8_t)(n_em < GM_FIXED_C ? n_em : GM_FIXED_C);
-            first_c.score = __uint_as_float(b.fixed_epoch);       // k_cand_gather takes slots stamped with this launch only
-            S.cbuf[rs & 63u] = first_c;
+        if (jj == 0u && n_em != 0u) {
+            if (!direct) {
+                first_c.pad = (uint8_t)(n_em < GM_FIXED_C ? n_em : GM_FIXED_C);
+                first_c.score = __uint_as_float(b.fixed_epoch);   // k_cand_gather takes slots stamped with this launch only
+            }
+            S.cbuf[rs & 63u] = first_c;                           // (direct: flags = 4 marks the slot as taken)
         }
         } while (0);
         // ---- the group's results: slot 0 of 64 read x strands is one 1 KB stretch (GM_FIXED_AT), their seed / hit counts 128 / 256 bytes ----
@@ -293,8 +329,45 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
             __syncthreads();
             const uint32_t rs_l = ((pr >> 4) << 6) + (uint32_t)lane;
             if (rs_l < 2u * b.n && !(p.dbg & 4096)) { b.n_seeds[rs_l] = S.nsbuf[lane]; b.n_entries[rs_l] = S.nebuf[lane]; }
-            if (rs_l < 2u * b.n && b.fixed_cands != nullptr && !(p.dbg & 8192)) b.fixed_cands[GM_FIXED_AT(b, rs_l, 0u)] = S.cbuf[lane];
+            if (!direct) {
+                if (rs_l < 2u * b.n && !(p.dbg & 8192)) b.fixed_cands[GM_FIXED_AT(b, rs_l, 0u)] = S.cbuf[lane];
+            } else {
+                const uint32_t grp = pr >> 4;
+                if (fmask != 0u) {                        // the group's flagged reads -> k_vote_bucket's list
+                    uint32_t lb = 0;
+                    if (lane == 0) lb = atomicAdd(n_list, (uint32_t)__popc(fmask));
+                    lb = (uint32_t)__builtin_amdgcn_readfirstlane((int)lb);
+                    if (lane < 32 && ((fmask >> lane) & 1u)) list[lb + (uint32_t)__popc(fmask & ((1u << lane) - 1u))] = 32u * grp + (uint32_t)lane;
+                }
+                // the group's candidates -> shard grp: the first ones in read x strand order, then the further ones
+                const GmCand c = S.cbuf[lane];
+                const bool has = rs_l < 2u * b.n && c.flags != 0;
+                const unsigned long long cm = __builtin_amdgcn_ballot_w64(has);
+                const uint32_t n_xl = n_x < GMP_XCAP ? n_x : GMP_XCAP;          // (the ones past the LDS list have their slots already)
+                const uint32_t n_first = (uint32_t)__popcll(cm), n_tot = n_first + n_xl;
+                if (n_tot != 0u) {
+                    const uint32_t shard = grp & (GM_NSHARD - 1);
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(&b.shard_cnt[shard * GM_SHARD_STRIDE], n_tot);
+                    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                    GmCand* const dst = b.cands + (size_t)shard * b.cand_region;
+                    const uint32_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u));
+                    if (has && at < b.cand_region) dst[at] = c;
+                    const uint32_t atx = base + n_first + (uint32_t)lane;
+                    if ((uint32_t)lane < n_xl && atx < b.cand_region) dst[atx] = S.xbuf[lane];
+                }
+                // work counters of the read x strands that stay here (a flagged read's are counted where its list entry is walked)
+                // (packed: at most 64 x 16 seeds and 64 x GMP_ECAP hits per group)
+                const uint32_t se = rs_l < 2u * b.n && ((fmask >> (lane >> 1)) & 1u) == 0u ? (uint32_t)S.nsbuf[lane] | (S.nebuf[lane] << 16) : 0u;
+                const uint32_t gs = (uint32_t)__builtin_amdgcn_readlane((int)gm_wave_scan_incl(se), 63);
+                acc_s += gs & 0xFFFFu; acc_e += gs >> 16;
+                fmask = 0u; n_x = 0u;
+            }
         }
+    }
+    if (direct) {                                         // one pair of atomics per workgroup, spread over the shards' counter lines
+        const uint32_t sh = blockIdx.x & (GM_NSHARD - 1);
+        if (gmp_lane_again() == 0 && acc_s != 0u) { atomicAdd(&b.shard_cnt[sh * GM_SHARD_STRIDE + 2u], acc_s); atomicAdd(&b.shard_cnt[sh * GM_SHARD_STRIDE + 3u], acc_e); }
     }
 }
 
@@ -324,7 +397,8 @@ __global__ void __launch_bounds__(256) k_pair_collect(const uint8_t* fallback, u
 
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// max_reg = seeds per strand the longest read needs; fallback: n bytes, zeroed by the caller; list / n_list: n words + 1 counter (zeroed)
+// max_reg = seeds per strand the longest read needs; list / n_list: n words + 1 counter (zeroed); fallback: n bytes, zeroed by the caller -
+// only with own candidate slots (b.fixed_cands, the gather hand-off), where k_pair_collect turns them into the list
 int gmk_vote_pair(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t max_reg, uint8_t* fallback, uint32_t* list, uint32_t* n_list, void* stream) {
     if (b.n == 0) return 0;
     if (max_reg > 16 || p.bucket_ctx || p.mer != p.bucket_T) return (int)hipErrorInvalidValue;
@@ -337,9 +411,11 @@ int gmk_vote_pair(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& 
     uint32_t chunk = (uint32_t)std::max<long long>(16, gm_opt_ll("GM_PAIR_CHUNK", 32)) / 16u * 16u;
     while (chunk > 16u && (npairs + chunk - 1u) / chunk < 4096u) chunk -= 16u;
     const dim3 grid((npairs + chunk - 1u) / chunk), blk(64);
-    if (max_reg <= 8) hipLaunchKernelGGL((k_vote_pair<4>), grid, blk, 0, S_(stream), ix, p, b, fallback, chunk);
-    else if (max_reg <= 14) hipLaunchKernelGGL((k_vote_pair<7>), grid, blk, 0, S_(stream), ix, p, b, fallback, chunk);
-    else hipLaunchKernelGGL((k_vote_pair<8>), grid, blk, 0, S_(stream), ix, p, b, fallback, chunk);
-    hipLaunchKernelGGL(k_pair_collect, dim3((b.n + 4095u) / 4096u), dim3(256), 0, S_(stream), fallback, b.n, list, n_list);
+    const bool direct = b.fixed_cands == nullptr;
+    if (!direct && fallback == nullptr) return (int)hipErrorInvalidValue;
+    if (max_reg <= 8) hipLaunchKernelGGL((k_vote_pair<4>), grid, blk, 0, S_(stream), ix, p, b, fallback, list, n_list, chunk);
+    else if (max_reg <= 14) hipLaunchKernelGGL((k_vote_pair<7>), grid, blk, 0, S_(stream), ix, p, b, fallback, list, n_list, chunk);
+    else hipLaunchKernelGGL((k_vote_pair<8>), grid, blk, 0, S_(stream), ix, p, b, fallback, list, n_list, chunk);
+    if (!direct) hipLaunchKernelGGL(k_pair_collect, dim3((b.n + 4095u) / 4096u), dim3(256), 0, S_(stream), fallback, b.n, list, n_list);
     return (int)hipGetLastError();
 }
