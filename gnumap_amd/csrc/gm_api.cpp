@@ -729,7 +729,7 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
         }
         if (mx > region) { overflow = true; return GM_OK; }
         ncand[i] = (uint32_t)total;
-        { KTimer t(b, GM_K_NW, ss); KCHK(gmk_nw(ix->dev, dp, view[i], ncand[i], (b->len_min == b->len_max && !ctr[GMK_HIGH_QUAL]) ? b->len_max : 0u, ss)); }
+        { KTimer t(b, GM_K_NW, ss); KCHK(gmk_nw(ix->dev, dp, view[i], ncand[i], (b->len_min == b->len_max && !ctr[GMK_HIGH_QUAL]) ? b->len_max : 0u, gm_qual_lo(ctr), gm_qual_hi(ctr), ss)); }
         return GM_OK;
     };
     uint32_t next_finish = 0;
@@ -1071,8 +1071,8 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     fill_dev_batch(b);
     // one read length in the block and no quality character above 127 (k_prep counted them): the DP kernel with the rows in DP order
     const uint32_t nw_rows_len = (b->len_min == b->len_max && ctr[GMK_HIGH_QUAL] == 0) ? b->len_max : 0u;
-    b->path += std::string(" nw=") + gmk_nw_form(dp, b->dev, b->n_cands, nw_rows_len);
-    { KTimer t(b, GM_K_NW, st); KCHK(gmk_nw(ix->dev, dp, b->dev, b->n_cands, nw_rows_len, st)); }
+    b->path += std::string(" nw=") + gmk_nw_form(dp, b->dev, b->n_cands, nw_rows_len, gm_qual_lo(ctr), gm_qual_hi(ctr));
+    { KTimer t(b, GM_K_NW, st); KCHK(gmk_nw(ix->dev, dp, b->dev, b->n_cands, nw_rows_len, gm_qual_lo(ctr), gm_qual_hi(ctr), st)); }
     { KTimer t(b, GM_K_COMPACT, st); KCHK(gmk_compact(b->dev, st)); }
     if (gm_trace_on()) { HIPCHK(hipStreamSynchronize(st)); GM_TRACE("NW + compaction done"); }
     b->mapped = true;
@@ -1762,7 +1762,10 @@ extern "C" int gm_dev_nw_score(gm_index* ix, const gm_params* p, const gm_reads*
         if (hipMemcpy(b->shards.p, &n, 4, hipMemcpyHostToDevice) != hipSuccess) { rc = GM_E_HIP; break; }
         uint32_t rows_len = (b->len_min == b->len_max) ? b->len_max : 0u;          // (no k_prep here: the quality characters are looked at on the host)
         for (size_t q = 0; q < (size_t)reads->n * reads->stride && rows_len; ++q) if (reads->quals[q] >= 128) rows_len = 0;
-        if (gmk_nw(ix->dev, dp, b->dev, n, rows_len, nullptr)) { rc = GM_E_HIP; break; }
+        uint32_t qlo = 255, qhi = 0;
+        for (uint32_t r = 0; r < reads->n; ++r)
+            for (uint32_t i = 0; i < reads->len[r] && i < reads->stride; ++i) { const uint32_t qc = reads->quals[(size_t)r * reads->stride + i]; qlo = std::min(qlo, qc); qhi = std::max(qhi, qc); }
+        if (gmk_nw(ix->dev, dp, b->dev, n, rows_len, qlo, qhi, nullptr)) { rc = GM_E_HIP; break; }
         if (n && hipMemcpy(c.data(), b->cands.p, (size_t)n * sizeof(GmCand), hipMemcpyDeviceToHost) != hipSuccess) { rc = GM_E_HIP; break; }
     } while (0);
     gm_batch_destroy(b);

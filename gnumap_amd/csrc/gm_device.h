@@ -31,6 +31,22 @@ __device__ __forceinline__ void gm_count(const GmDevBatch& b, int which, unsigne
     if (gm_lane() == 0 && s) atomicAdd(&b.counters[which], s);
 }
 
+// the quality range of a workgroup's reads (lane values qlo / qhi, 255 / 0 = none) into GMK_QUAL_MIN / GMK_QUAL_MAX: one atomic pair per
+// workgroup.  Every thread of the workgroup calls it (it holds a barrier)
+__device__ __forceinline__ void gm_count_qual_range(const GmDevBatch& b, uint32_t qlo, uint32_t qhi) {
+    __shared__ uint32_t s_qr[2];
+    if (threadIdx.x == 0) { s_qr[0] = 255u; s_qr[1] = 0u; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { qlo = min(qlo, (uint32_t)__shfl_xor((int)qlo, off)); qhi = max(qhi, (uint32_t)__shfl_xor((int)qhi, off)); }
+    __syncthreads();
+    if (gm_lane() == 0) { atomicMin(&s_qr[0], qlo); atomicMax(&s_qr[1], qhi); }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_qr[0] <= s_qr[1]) {
+        atomicMax(&b.counters[GMK_QUAL_MIN], (unsigned long long)(255u - s_qr[0]));
+        atomicMax(&b.counters[GMK_QUAL_MAX], (unsigned long long)s_qr[1]);
+    }
+}
+
 // number of bases == c among the first `take` (clamped to 0..32) bases of a word holding 32 bases MSB first
 __device__ __forceinline__ uint32_t gm_count_base(unsigned long long w, uint32_t c, int take) {
     unsigned long long pat = ((c & 1u) ? 0x5555555555555555ull : 0ull) | ((c & 2u) ? 0xAAAAAAAAAAAAAAAAull : 0ull);

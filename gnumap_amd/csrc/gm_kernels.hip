@@ -185,6 +185,7 @@ __global__ void __launch_bounds__(256) k_prep(GmDevIndex ix, GmDevParams p, GmDe
     // tile_reads = reads per tile that fit the LDS budget (256 at 100 bp); 0 = rows too long to stage, lanes read HBM directly
     extern __shared__ __attribute__((aligned(16))) unsigned char s_tile[];          // bases of a tile, then quals
     unsigned long long bad = 0, high = 0;
+    uint32_t qlo = 255u, qhi = 0u;                   // the range of the quality characters (GMK_QUAL_MIN / GMK_QUAL_MAX)
     const bool staged = tile_reads != 0;
     const uint32_t TR = staged ? tile_reads : 256u;
     const uint32_t n_tiles = (b.n + TR - 1u) / TR;
@@ -246,6 +247,7 @@ __global__ void __launch_bounds__(256) k_prep(GmDevIndex ix, GmDevParams p, GmDe
                     }
                     if (v != v) bad = 1;                     // negative probability (SeqReader.cpp:1171-1189)
                     if (qc >= 128u) high = 1;                // (k_nw_rows' table of row values covers the characters below 128)
+                    qlo = min(qlo, qc); qhi = max(qhi, qc);
                     score = __fadd_rn(score, v);
                 }
             }
@@ -287,6 +289,7 @@ __global__ void __launch_bounds__(256) k_prep(GmDevIndex ix, GmDevParams p, GmDe
     }
     gm_count(b, GMK_BAD_QUAL, bad);
     gm_count(b, GMK_HIGH_QUAL, high);
+    gm_count_qual_range(b, qlo, qhi);
 }
 
 
@@ -3467,18 +3470,18 @@ static inline uint32_t lp_of(uint32_t stride) { return (stride + 7u) & ~7u; }
 static bool nw_rows_ok(const GmDevParams& p, const GmDevBatch& b, uint32_t rows_len) {
     return p.max_gap == 3 && p.nw && !gm_opt_is("GM_NW", "wave") && !gm_opt_is("GM_NW", "lane") && rows_len >= 24 && rows_len <= 152 && rows_len <= b.stride;
 }
-const char* gmk_nw_form(const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len) {
+const char* gmk_nw_form(const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, uint32_t qual_lo, uint32_t qual_hi) {
     (void)n_cands;
     if (p.max_gap != 3) return "k_nw_band";
-    if (nw_rows_ok(p, b, rows_len)) return "k_nw_rows";
+    if (nw_rows_ok(p, b, rows_len)) return gmk_nw_rows_pairs(b, rows_len, qual_lo, qual_hi) ? "k_nw_rows/pairs" : "k_nw_rows/cells";
     return gm_opt_is("GM_NW", "wave") ? "k_nw" : "k_nw_lane";
 }
 
-int gmk_nw(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, void* stream) {
+int gmk_nw(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, uint32_t qual_lo, uint32_t qual_hi, void* stream) {
     if (b.n == 0) return 0;
     if (p.max_gap != 3) return gmk_nw_band(ix, p, b, n_cands, p.max_gap, stream);
     const bool wave_form = gm_opt_is("GM_NW", "wave");
-    if (nw_rows_ok(p, b, rows_len)) return gmk_nw_rows(ix, p, b, n_cands, rows_len, stream);
+    if (nw_rows_ok(p, b, rows_len)) return gmk_nw_rows(ix, p, b, n_cands, rows_len, qual_lo, qual_hi, stream);
     if (!wave_form) {
         // ~4 candidates per lane: fewer, larger workgroups leave a long tail (measured at 17 M candidates: 2048 workgroups 6.1 ms,
         // 16384 5.6 ms), more, smaller ones pay their set-up (LDS tables, shard prefix) too often (2 M candidates: 0.77 against 1.02 ms)

@@ -16,8 +16,15 @@
 //     record + column offset (the first form picked it out of the row's float4 with three v_cndmask on two lane masks per column: 21 of
 //     the 57 instructions of a row; as LDS reads the row is 45 and the kernel 5 % faster - the LDS has the room);
 //     sliding the band is register renaming inside the unrolled rows;
+//   * PAIRS (the default where it fits): the record of a (quality character, class) holds the values of two adjacent band columns for
+//     each of the 16 code pairs, {val(x), val(y)} at byte 8 (4x + y).  An interior row reads cells (0,1), (2,3), (4,5) and (6, -) with
+//     one ds_read_b64 each: 4 LDS reads instead of 7.  On gfx950 ds_read_b64 banks over 64 dwords instead of 32, so a half-wave of
+//     random entries meets about as many conflicts per instruction as one ds_read_b32 did, for fewer instructions (LDS cycles -29 %,
+//     DESIGN.md §4).  The table holds only the quality characters of the block (its range is reduced by the prep kernels into
+//     GMK_QUAL_MIN / GMK_QUAL_MAX) and 5 classes, so the host sizes the LDS from that range;
 //   * the first 8 and the last 9 .. 16 rows (which touch row L, column L or column -1) run a generic row; the rows between them test nothing.
-// The host launches it only for blocks it has checked: one read length L (24 <= L <= 8 NCH), no quality character above 127, -M 3.
+// The host launches it only for blocks it has checked: one read length L (24 <= L <= 8 NCH), no quality character above 127, -M 3; the
+// pair form only with the block's quality range, inside which every quality character of the block lies.
 #include <hip/hip_runtime.h>
 #include "gm_device.h"
 
@@ -26,12 +33,19 @@ static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s);
 #define GM_NWR_NCOFF 1024u                  // contig offsets cached in LDS when there are at most this many
 #define GM_NWR_QSTRIDE 144u                 // bytes per quality character in the value table: 8 class records of 16 bytes + 16 bytes of skew (banks)
 #define GM_NWR_TAB_BYTES (128u * GM_NWR_QSTRIDE)
+#define GM_NWR_PAIR_SKEW 8u                 // bytes of skew after each 128-byte pair record (GM_NW_PAIR_SKEW): record r starts 34 r dwords in
 
-template <int NCH>
-__global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex ix, GmDevParams p, GmDevBatch b, const uint32_t L, const uint32_t ntab) {
+// PAIRS: qlo = the block's smallest quality character, nq = the number of characters in its range, rs = bytes per pair record
+template <int NCH, bool PAIRS>
+__global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex ix, GmDevParams p, GmDevBatch b, const uint32_t L, const uint32_t ntab,
+                                                                    const uint32_t qlo, const uint32_t nq, const uint32_t rs) {
     constexpr int NHW = (8 * NCH + 3) / 16 + 1;                                // 16-column words of the window stream
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_tab[];       // [ntab][128 quality characters][8 classes] float4 {val(a), val(c), val(g), val(t)}
-    __shared__ uint16_t s_cls[2][2][256];                                        // [phred table][strand][read character] -> byte offset of its class record (+ its table's)
+    // cells: [ntab][128 quality characters][8 classes] float4 {val(a), val(c), val(g), val(t)};
+    // PAIRS: [ntab][nq quality characters][5 classes] 16 x float2 {val(x), val(y)}, records rs bytes apart
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_tab[];
+    // [phred table][strand][read character] -> byte offset of its class record (+ its table's; PAIRS: - qlo x the quality stride, mod 2^32)
+    __shared__ std::conditional_t<PAIRS, uint32_t, uint16_t> s_cls[2][2][256];
+    const uint32_t qstride = PAIRS ? 5u * rs : GM_NWR_QSTRIDE, tabb = PAIRS ? nq * qstride : GM_NWR_TAB_BYTES;
     __shared__ uint32_t s_coff[GM_NWR_NCOFF];
     __shared__ uint32_t s_pre[GM_NSHARD + 4];
     {
@@ -40,21 +54,38 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
         for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int k = 0; k < 4; ++k) sg[g][k] = p.S256[(size_t)("acgt"[g]) * 4 + k];     // windows are lowercase acgt (GetString)
-        for (uint32_t e = threadIdx.x; e < ntab * 1024u; e += 256) {
-            const uint32_t tab = e >> 10, q = (e >> 3) & 127u, cl = e & 7u;
-            const uint32_t code = cl < 4u ? cl : 4u;                             // classes 4 .. 7: any character outside ACGTacgt
-            const float2 pq = p.lut[tab * 256u + q];
-            float4 v;
-            v.x = gm_get_val(code, pq.x, pq.y, sg[0]); v.y = gm_get_val(code, pq.x, pq.y, sg[1]);
-            v.z = gm_get_val(code, pq.x, pq.y, sg[2]); v.w = gm_get_val(code, pq.x, pq.y, sg[3]);
-            *reinterpret_cast<float4*>(s_tab + tab * GM_NWR_TAB_BYTES + q * GM_NWR_QSTRIDE + cl * 16u) = v;
+        if (PAIRS) {
+            for (uint32_t e = threadIdx.x; e < ntab * nq * 80u; e += 256) {     // 16 entries of 5 class records per quality character
+                const uint32_t n = e & 15u, rec = e >> 4, tq = rec / 5u, code = rec - 5u * tq;        // class 4: any character outside ACGTacgt
+                const uint32_t tab = tq / nq, qi = tq - tab * nq;
+                const float2 pq = p.lut[tab * 256u + qlo + qi];
+                float v[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) v[g] = gm_get_val(code, pq.x, pq.y, sg[g]);
+                const uint32_t x = n >> 2, y = n & 3u;
+                const float2 o = make_float2(x == 0 ? v[0] : x == 1 ? v[1] : x == 2 ? v[2] : v[3], y == 0 ? v[0] : y == 1 ? v[1] : y == 2 ? v[2] : v[3]);
+                *reinterpret_cast<float2*>(s_tab + tab * tabb + qi * qstride + code * rs + 8u * n) = o;
+            }
+        } else {
+            for (uint32_t e = threadIdx.x; e < ntab * 1024u; e += 256) {
+                const uint32_t tab = e >> 10, q = (e >> 3) & 127u, cl = e & 7u;
+                const uint32_t code = cl < 4u ? cl : 4u;                         // classes 4 .. 7: any character outside ACGTacgt
+                const float2 pq = p.lut[tab * 256u + q];
+                float4 v;
+                v.x = gm_get_val(code, pq.x, pq.y, sg[0]); v.y = gm_get_val(code, pq.x, pq.y, sg[1]);
+                v.z = gm_get_val(code, pq.x, pq.y, sg[2]); v.w = gm_get_val(code, pq.x, pq.y, sg[3]);
+                *reinterpret_cast<float4*>(s_tab + tab * GM_NWR_TAB_BYTES + q * GM_NWR_QSTRIDE + cl * 16u) = v;
+            }
         }
         const uint32_t ch = threadIdx.x, code = gm_nt4(ch);
 #pragma unroll
         for (uint32_t tab = 0; tab < 2; ++tab)
 #pragma unroll
-            for (uint32_t st = 0; st < 2; ++st)                                   // the reverse strand reads the complemented PWM row (reverse_comp_cpy)
-                s_cls[tab][st][ch] = (uint16_t)((tab < ntab ? tab : 0u) * GM_NWR_TAB_BYTES + ((code < 4u && st) ? 3u - code : code) * 16u);
+            for (uint32_t st = 0; st < 2; ++st) {                                 // the reverse strand reads the complemented PWM row (reverse_comp_cpy)
+                const uint32_t cl = (code < 4u && st) ? 3u - code : code;
+                const uint32_t tb = (tab < ntab ? tab : 0u) * tabb;
+                s_cls[tab][st][ch] = PAIRS ? tb + cl * rs - qlo * qstride : tb + cl * 16u;
+            }
     }
     const bool lds_coff = ix.n_seqs + 1 <= GM_NWR_NCOFF;
     if (lds_coff) for (uint32_t q = threadIdx.x; q <= ix.n_seqs; q += 256) s_coff[q] = ix.contig_off[q];
@@ -118,33 +149,50 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
                 for (int m = 0; m < NHW; ++m) HW[m] = __builtin_amdgcn_alignbit(W[m + 1], W[m], s);
             }
             const uint32_t tab = (ntab > 1u && r < b.illumina_until) ? 1u : 0u;
-            const uint16_t* const clsrow = s_cls[tab][strand];
+            const auto* const clsrow = s_cls[tab][strand];
             // band row of i + 1: P[d] = nm[i+1][i+1+d-3].  Row L: gGAP * (L - j) for j <= L (bin_seq.cpp:805-808)
             float P[7];
 #pragma unroll
             for (int d = 0; d < 7; ++d) P[d] = d <= 3 ? __fmul_rn(gap, (float)(3 - d)) : GM_NEG_INF;
-            // the base of band column d as 4 x its 2-bit code (its byte offset in a value record); row L - 1: columns j = L-4+d, valid for d <= 3
+            // the base of band column d (row t: H[t + 3 - d]) as its byte offset in a value record.  cells: 4 x its 2-bit code.  PAIRS: the
+            // offset of the pair entry (column d, column d + 1) = 8 x the 4 stream bits of H[t + 2 - d] .. H[t + 3 - d]: the entry's x half
+            // is column d's value, a ds_read_b64 there returns columns d and d + 1.  Row L - 1: columns j = L-4+d, valid for d <= 3
             uint32_t cc[7];
 #pragma unroll
-            for (int d = 0; d < 7; ++d) cc[d] = d <= 3 ? ((HW[0] >> (2 * (3 - d))) & 3u) << 2 : 0u;
-            // a row's value record {val(a), val(c), val(g), val(t)} as its LDS byte offset
+            for (int d = 0; d < 7; ++d) cc[d] = d > 3 ? 0u : PAIRS ? (((HW[0] << 2) >> (2 * (3 - d))) & 15u) << 3 : ((HW[0] >> (2 * (3 - d))) & 3u) << 2;
+            // a row's value record as its LDS byte offset
             auto row_vals = [&](uint32_t bword, uint32_t qword, uint32_t shift) -> uint32_t {
                 const uint32_t chv = (bword >> shift) & 255u;
                 const uint32_t co = clsrow[chv];
                 const uint32_t qv = (qword >> shift) & 255u;
-                return qv * GM_NWR_QSTRIDE + co;
+                return __umul24(qv, qstride) + co;                              // (a 24-bit multiply: qstride is a kernel argument in the pair form)
             };
             auto cell_val = [&](const uint32_t v, int d) -> float { return *reinterpret_cast<const float*>(s_tab + v + cc[d]); };
-            auto slide = [&](uint32_t hw, uint32_t pos) {                       // band columns of the next row; the new one is H[t + 4] (j = i - 4)
+            // band columns of the next row; the new one is H[t + 4] (j = i - 4), at bit pos of hw.  PAIRS: the new entry takes H[t + 3] too,
+            // the two bits below pos - from the word before (hwp) when pos = 0
+            auto slide = [&](uint32_t hw, uint32_t hwp, uint32_t pos) {
 #pragma unroll
                 for (int d = 6; d >= 1; --d) cc[d] = cc[d - 1];
-                cc[0] = ((hw >> pos) & 3u) << 2;
+                if (PAIRS) cc[0] = (uint32_t)((((unsigned long long)hw << 32) | hwp) >> (27u + pos)) & 0x78u;
+                else cc[0] = ((hw >> pos) & 3u) << 2;
             };
             // an interior row (4 <= i <= L - 5): every cell inside the matrix, band edges are NEG_INF
-            auto row_int = [&](const uint32_t v, uint32_t hw, uint32_t pos) {
-                float val[7], mm[7], g1[7];
+            auto row_int = [&](const uint32_t v, uint32_t hw, uint32_t hwp, uint32_t pos) {
+                float val[7], mm[7], g1[7], unused = 0.0f;
+                if (PAIRS) {
 #pragma unroll
-                for (int d = 0; d < 7; ++d) val[d] = cell_val(v, d);
+                    for (int d = 0; d < 6; d += 2) {
+                        const float2 pv = *reinterpret_cast<const float2*>(s_tab + v + cc[d]);
+                        val[d] = pv.x; val[d + 1] = pv.y;
+                    }
+                    // cell 6 is the x half of its own pair entry, read as the whole entry: an 8-byte-aligned ds_read_b32 would meet only the
+                    // even banks of its 32, a ds_read_b64 spreads over all 64 (the y half is kept alive below so that the read stays 8 bytes)
+                    const float2 pv = *reinterpret_cast<const float2*>(s_tab + v + cc[6]);
+                    val[6] = pv.x; unused = pv.y;
+                } else {
+#pragma unroll
+                    for (int d = 0; d < 7; ++d) val[d] = cell_val(v, d);
+                }
 #pragma unroll
                 for (int d = 0; d < 7; ++d) { mm[d] = __fadd_rn(P[d], val[d]); g1[d] = d > 0 ? __fadd_rn(P[d - 1], gap) : ninf_gap; }
                 float left = ninf_gap;                                          // nm[i][j+1] + gGAP beyond the band
@@ -154,10 +202,11 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
                     P[d] = best;
                     left = __fadd_rn(best, gap);
                 }
-                slide(hw, pos);
+                if (PAIRS) asm volatile("" ::"v"(unused));                       // (no instruction)
+                slide(hw, hwp, pos);
             };
             // a row near a matrix edge: exactly k_nw_lane's EDGE row
-            auto row_edge = [&](const int t, const uint32_t v, uint32_t hw, uint32_t pos) {
+            auto row_edge = [&](const int t, const uint32_t v, uint32_t hw, uint32_t hwp, uint32_t pos) {
                 const int i = Li - 1 - t;
                 const float lastcol = __fmul_rn(gap, (float)(unsigned)(Li - i));                  // nm[i][L] = gGAP * (L - i)
 #pragma unroll
@@ -169,7 +218,7 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
                     const float best = fmaxf(fmaxf(__fadd_rn(P[d], val), __fadd_rn(up, gap)), __fadd_rn(left, gap));
                     P[d] = (j >= 0 && j < Li) ? best : (j == Li ? lastcol : GM_NEG_INF);
                 }
-                slide(hw, pos);
+                slide(hw, hwp, pos);
             };
             auto pick2 = [&](const uint2* X, int k) -> uint2 {                  // k is wave-uniform: a branch tree, one move per word
                 uint2 o = X[0];
@@ -200,8 +249,9 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
                     const uint32_t bsel = (t & 4) ? bw.y : bw.x, qsel = (t & 4) ? qw.y : qw.x;
                     const uint32_t v = row_vals(bsel, qsel, (uint32_t)(t & 3) << 3);
                     const int u = t + 4;
-                    if (EDGE) row_edge(t, v, pick_hw(u >> 4), 2u * (uint32_t)(u & 15));
-                    else row_int(v, pick_hw(u >> 4), 2u * (uint32_t)(u & 15));
+                    const uint32_t hw = pick_hw(u >> 4), hwp = (PAIRS && (u & 15) == 0) ? pick_hw((u >> 4) - 1) : hw;       // (u >= 16 there)
+                    if (EDGE) row_edge(t, v, hw, hwp, 2u * (uint32_t)(u & 15));
+                    else row_int(v, hw, hwp, 2u * (uint32_t)(u & 15));
                 }
             };
             // interior rows [B0, 8) of chunk k at compile-time positions; PAR = k & 1 fixes where the rows' new columns sit in the window
@@ -216,9 +266,9 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
                 for (int bb = B0; bb < 8; ++bb) co[bb] = clsrow[((bb < 4 ? bw.x : bw.y) >> ((bb & 3) << 3)) & 255u];
 #pragma unroll
                 for (int bb = B0; bb < 8; ++bb) {
-                    const uint32_t v = (((bb < 4 ? qw.x : qw.y) >> ((bb & 3) << 3)) & 255u) * GM_NWR_QSTRIDE + co[bb];
-                    if (PAR) { if (bb < 4) row_int(v, hw_lo, 2u * (12u + bb)); else row_int(v, hw_hi, 2u * (bb - 4u)); }
-                    else row_int(v, hw_lo, 2u * (4u + bb));
+                    const uint32_t v = __umul24(((bb < 4 ? qw.x : qw.y) >> ((bb & 3) << 3)) & 255u, qstride) + co[bb];
+                    if (PAR) { if (bb < 4) row_int(v, hw_lo, hw_lo, 2u * (12u + bb)); else row_int(v, hw_hi, hw_lo, 2u * (bb - 4u)); }
+                    else row_int(v, hw_lo, hw_lo, 2u * (4u + bb));
                 }
             };
             if (nchunk >= 4) {
@@ -260,19 +310,55 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
     gm_count(b, GMK_ACCEPTED, accepted);
 }
 
-// L = the one read length of the block; illumina = some reads of the block use the Phred+64 table (both tables are then resident)
-int gmk_nw_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t L, void* stream) {
+// bytes per pair record: 128 + a skew of 0 .. 64 bytes in steps of 8 (the entries stay 8-byte aligned for ds_read_b64)
+static uint32_t nw_pair_rs() {
+    const long long k = gm_opt_ll("GM_NW_PAIR_SKEW", GM_NWR_PAIR_SKEW);
+    return 128u + ((k >= 0 && k <= 64 && k % 8 == 0) ? (uint32_t)k : GM_NWR_PAIR_SKEW);
+}
+// the pair form's dynamic LDS for the quality characters [qlo, qhi] of a block, 0 = none (no valid range)
+static size_t nw_pair_lds(uint32_t ntab, uint32_t qlo, uint32_t qhi) {
+    return (qlo <= qhi && qhi < 128u) ? (size_t)ntab * (qhi - qlo + 1u) * 5u * nw_pair_rs() : 0;
+}
+
+// the pair table unless it would leave fewer workgroups per CU than the cells table (wide quality ranges, two tables), or GM_NW_CELLS=b32
+bool gmk_nw_rows_pairs(const GmDevBatch& b, uint32_t L, uint32_t qlo, uint32_t qhi) {
+    if (gm_opt_is("GM_NW_CELLS", "b32")) return false;
+    const uint32_t ntab = b.illumina_until ? 2u : 1u;
+    const size_t lds = nw_pair_lds(ntab, qlo, qhi);
+    if (!lds) return false;
+    int per_cells = 0, per_pairs = 0;
+    const bool narrow = L <= 104;
+    hipError_t e0, e1;
+    if (narrow) {
+        e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cells, k_nw_rows<13, false>, 256, (size_t)ntab * GM_NWR_TAB_BYTES);
+        e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_pairs, k_nw_rows<13, true>, 256, lds);
+    } else {
+        e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cells, k_nw_rows<19, false>, 256, (size_t)ntab * GM_NWR_TAB_BYTES);
+        e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_pairs, k_nw_rows<19, true>, 256, lds);
+    }
+    return e0 == hipSuccess && e1 == hipSuccess && per_pairs > 0 && per_pairs >= per_cells;
+}
+
+// L = the one read length of the block; [qlo, qhi] = the range of its quality characters (all below 128); illumina = some reads of the
+// block use the Phred+64 table (both tables are then resident)
+int gmk_nw_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t L, uint32_t qlo, uint32_t qhi, void* stream) {
     if (b.n == 0) return 0;
     const uint32_t ntab = b.illumina_until ? 2u : 1u;
-    const size_t lds = (size_t)ntab * GM_NWR_TAB_BYTES;
+    const bool pairs = gmk_nw_rows_pairs(b, L, qlo, qhi);
+    const size_t lds = pairs ? nw_pair_lds(ntab, qlo, qhi) : (size_t)ntab * GM_NWR_TAB_BYTES;
+    const uint32_t nq = pairs ? qhi - qlo + 1u : 0u, q0 = pairs ? qlo : 0u;
     // the workgroups stride over the candidates: one resident round of them (4 per CU for <13> with one table; fewer with two tables or
     // for <19>).  The earlier grid of n_cands / 1024 workgroups (10 449 at 10.7 M candidates) left its last round a fifth full and
     // built the value table 10 times per CU: 2.04 -> 1.85 ms
     const uint32_t nw_fixed = (uint32_t)gm_opt_ll("GM_NW_GRID", 0);
     const bool narrow = L <= 104;
-    const uint32_t grid = nw_fixed ? nw_fixed
-                        : narrow ? resident_grid(k_nw_rows<13>, 256, lds, 1024u) : resident_grid(k_nw_rows<19>, 256, lds, 768u);
-    if (narrow) hipLaunchKernelGGL((k_nw_rows<13>), dim3(grid), dim3(256), lds, S_(stream), ix, p, b, L, ntab);
-    else hipLaunchKernelGGL((k_nw_rows<19>), dim3(grid), dim3(256), lds, S_(stream), ix, p, b, L, ntab);
+#define GM_NWR_LAUNCH(N, PR, FB)                                                                                                        \
+    hipLaunchKernelGGL((k_nw_rows<N, PR>), dim3(nw_fixed ? nw_fixed : resident_grid(k_nw_rows<N, PR>, 256, lds, FB)), dim3(256), lds, \
+                       S_(stream), ix, p, b, L, ntab, q0, nq, nw_pair_rs())
+    if (narrow && pairs) GM_NWR_LAUNCH(13, true, 1024u);
+    else if (narrow) GM_NWR_LAUNCH(13, false, 1024u);
+    else if (pairs) GM_NWR_LAUNCH(19, true, 768u);
+    else GM_NWR_LAUNCH(19, false, 768u);
+#undef GM_NWR_LAUNCH
     return (int)hipGetLastError();
 }

@@ -53,6 +53,7 @@ __global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p,
     const uint32_t pw = b.pack ? b.pack_words : 0u;
     uint32_t* const myrow = s_rows + (size_t)threadIdx.x * pw;
     unsigned long long bad = 0, high = 0;
+    uint32_t qlo = 255u, qhi = 0u;                           // the range of the quality characters (below 128 when it matters: GMK_QUAL_MIN)
     for (uint32_t base = blockIdx.x * 256u; base < b.n; base += gridDim.x * 256u) {
         const uint32_t r = base + threadIdx.x;
         const bool rv = r < b.n;
@@ -104,6 +105,11 @@ __global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p,
                     for (uint32_t t = 0; t < 8; ++t) v[t] = term[cl[t]][((t < 4 ? qw.x : qw.y) >> ((t & 3) * 8)) & 127u];     // NaN when the probability is negative, like the direct form
                     qor |= qw.x | qw.y;
 #pragma unroll
+                    for (uint32_t t = 0; t < 8; t += 2) {
+                        const uint32_t q0 = ((t < 4 ? qw.x : qw.y) >> ((t & 3) * 8)) & 127u, q1 = ((t < 4 ? qw.x : qw.y) >> (((t + 1) & 3) * 8)) & 127u;
+                        qlo = min(qlo, min(q0, q1)); qhi = max(qhi, max(q0, q1));         // (v_min3 / v_max3)
+                    }
+#pragma unroll
                     for (uint32_t t = 0; t < 8; ++t) {
                         pk |= (cl[t] & 3u) << ((((uint32_t)(8 * k) & 8u) + t) << 1); any_n |= cl[t];
                         score = __fadd_rn(score, v[t]);
@@ -119,6 +125,7 @@ __global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p,
                         const float v1 = term[c1][qc & 127u];
                         pk |= (c1 & 3u) << ((((uint32_t)(8 * k) & 8u) + t) << 1); any_n |= c1;
                         qor |= qc;
+                        qlo = min(qlo, qc); qhi = max(qhi, qc);
                         nan_l |= v1 != v1;
                         score = __fadd_rn(score, v1);
                     }
@@ -204,6 +211,7 @@ __global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p,
     }
     gm_count(b, GMK_BAD_QUAL, bad);
     gm_count(b, GMK_HIGH_QUAL, high);
+    gm_count_qual_range(b, qlo, qhi);
 }
 
 int gmk_prep_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, void* stream) {
