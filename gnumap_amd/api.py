@@ -76,6 +76,8 @@ MATCH_DTYPE = np.dtype([("read", "<u4"), ("score", "<f4"), ("first_pos", "<u8"),
 POS_DTYPE = np.dtype([("pos", "<u8"), ("strand", "u1")], align=True)
 SAM_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u8"), ("contig", "<u4"), ("chr_pos", "<u8"), ("strand", "u1"), ("mapq", "<i4"),
                       ("a_score", "<f4"), ("post_prob", "<f4"), ("sim_matches", "<i4"), ("cigar_off", "<u4")], align=True)
+SNP_DTYPE = np.dtype([("pos", "<u8"), ("contig", "<u4"), ("chr_pos", "<u8"), ("total", "<f4"), ("nuc", "<f4", (5,)), ("p_val", "<f8"), ("ref", "u1"),
+                      ("alt1", "u1"), ("alt2", "u1"), ("diploid", "u1")], align=True)
 
 # every symbol include/gnumap_hip.h declares
 EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_parallel", "gm_index_build", "gm_index_build_on", "gm_index_open", "gm_index_close", "gm_index_prepare", "gm_index_get_info", "gm_index_contig_name",
@@ -85,7 +87,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait",
            "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
            "gm_coverage_device_ptr", "gm_coverage_add", "gm_coverage_download", "gm_coverage_allreduce", "gm_coverage_write_sgr", "gm_coverage_enable_nuc", "gm_coverage_nuc_device_ptr",
-           "gm_coverage_download_nuc", "gm_coverage_write_gmp"]
+           "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls"]
 
 
 def library_path():
@@ -152,6 +154,9 @@ def load_library():
     L.gm_coverage_nuc_device_ptr.argtypes = [C.c_void_p]; L.gm_coverage_nuc_device_ptr.restype = C.c_void_p
     L.gm_coverage_download_nuc.argtypes = [C.c_void_p, C.c_void_p]
     L.gm_coverage_write_gmp.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    L.gm_snp_calls.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
+    L.gm_dev_snp_stat.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gm_coverage_write_gmp_calls.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_char_p, C.c_int]
     _LIB = L
     return L
 
@@ -325,6 +330,31 @@ class Index:
     def coverage_write_sgr(self, bins, path):
         bins = np.ascontiguousarray(bins, np.float32)
         _chk(lib().gm_coverage_write_sgr(self.h, bins.ctypes.data, os.fsencode(path), 0))
+
+    # ---- SNP calls (--snp): PrintSNPCall over the tracks in HBM ----
+    def snp_calls(self, pval=0.001, monop=False):
+        """gm_snp_calls: the rows the reference marks 'Y' (p below --snp_pval), ascending position, as SNP_DTYPE records"""
+        cap = 4096
+        while True:
+            out = np.zeros(cap, SNP_DTYPE); got = u64()
+            rc = lib().gm_snp_calls(self.h, pval, int(monop), out.ctypes.data, cap, C.byref(got), None)
+            if rc == GM_E_CAPACITY:
+                cap = int(got.value)
+                continue
+            _chk(rc)
+            return out[:got.value]
+
+    def dev_snp_stat(self, counts, monop=False):
+        """is_snp on [n, 5] float counts: (p-value f8, first maximum i1, second maximum i1 or -1, diploid u1)"""
+        counts = np.ascontiguousarray(counts, np.float32).reshape(-1, 5)
+        n = len(counts)
+        p = np.zeros(n, np.float64); p1 = np.zeros(n, np.int8); p2 = np.zeros(n, np.int8); dip = np.zeros(n, np.uint8)
+        _chk(lib().gm_dev_snp_stat(self.h, counts.ctypes.data, n, int(monop), p.ctypes.data, p1.ctypes.data, p2.ctypes.data, dip.ctypes.data))
+        return p, p1, p2, dip
+
+    def coverage_write_gmp_calls(self, path, pval=0.001, monop=False):
+        """gm_coverage_write_gmp_calls: --snp's .gmp with the likelihood-ratio column, straight from the tracks in HBM"""
+        _chk(lib().gm_coverage_write_gmp_calls(self.h, pval, int(monop), os.fsencode(path), 0))
 
 
 class Batch:

@@ -1914,7 +1914,8 @@ static inline char* put_long(char* w, long v) {
 
 // bins [0, nb) in slabs: host_threads() threads format one slice of a slab each (emit(k, w) appends the line of bin k, if it has
 // one), the pieces are written with pwrite() at their offsets by the same threads
-template <class Emit> static int write_track_text(const char* path, int append, uint64_t nb, size_t max_line, Emit&& emit) {
+// slab(lo, hi) runs once before the bins [lo, hi) of a slab are formatted (a writer that fetches its slab from HBM there); non-zero ends the file
+template <class Emit, class Slab> static int write_track_text(const char* path, int append, uint64_t nb, size_t max_line, Emit&& emit, Slab&& slab) {
     // no O_APPEND: on Linux pwrite() on an O_APPEND descriptor ignores its offset, and the slices below are written concurrently
     const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
     if (fd < 0) { gm_set_error(std::string("cannot write ") + path); return GM_E_IO; }
@@ -1926,6 +1927,7 @@ template <class Emit> static int write_track_text(const char* path, int append, 
     std::atomic<int> bad{ 0 };
     for (uint64_t s0 = 0; s0 < nb && !bad; s0 += per * T) {
         const unsigned parts = (unsigned)std::min<uint64_t>(T, (nb - s0 + per - 1) / per);
+        if (const int rc = slab(s0, std::min<uint64_t>(nb, s0 + per * T))) { ::close(fd); return rc; }
         auto format = [&](unsigned c) {
             const uint64_t lo = s0 + c * per, hi = std::min<uint64_t>(nb, lo + per);
             std::vector<char>& o = buf[c];
@@ -1956,6 +1958,10 @@ template <class Emit> static int write_track_text(const char* path, int append, 
     ::close(fd);
     if (bad) { gm_set_error(std::string("write failed: ") + path); return GM_E_IO; }
     return GM_OK;
+}
+
+template <class Emit> static int write_track_text(const char* path, int append, uint64_t nb, size_t max_line, Emit&& emit) {
+    return write_track_text(path, append, nb, max_line, emit, [](uint64_t, uint64_t) { return 0; });
 }
 
 extern "C" int gm_coverage_write_sgr(gm_index* ix, const float* bins, const char* path, int append) {
@@ -2008,7 +2014,7 @@ extern "C" int gm_coverage_write_gmp(gm_index* ix, const gm_params* p, const flo
     const uint64_t bs = ix->cov_bin_size, nb = ix->cov_bins;
     if (p->mode == GM_MODE_SNP) {
         // GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1090 up to the per-nucleotide columns: every position whose total is above MIN_PRINT,
-        // "%.5f" for all six numbers.  PrintSNPCall's likelihood-ratio columns need gsl_cdf_chisq_P (GSL): not written, the line ends here.
+        // "%.5f" for all six numbers.  The line ends here; gm_coverage_write_gmp_calls writes the same rows with PrintSNPCall's column behind them.
         const uint64_t nbk = (h.l_pac + bs - 1) / bs;
         size_t max_name = 0;
         for (const auto& c : h.contigs) max_name = std::max(max_name, c.name.size());
@@ -2048,4 +2054,122 @@ extern "C" int gm_coverage_write_gmp(gm_index* ix, const gm_params* p, const flo
         *w++ = '\n';
         return w;
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// --snp: the likelihood-ratio column (gm_snpcall.hip)
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(gm_snp_rec) == sizeof(GmDevSnpRec) && sizeof(gm_snp_rec) == 64 && offsetof(gm_snp_rec, chr_pos) == offsetof(GmDevSnpRec, chr_pos) &&
+              offsetof(gm_snp_rec, total) == offsetof(GmDevSnpRec, total) && offsetof(gm_snp_rec, nuc) == offsetof(GmDevSnpRec, nuc) &&
+              offsetof(gm_snp_rec, p_val) == offsetof(GmDevSnpRec, p_val) && offsetof(gm_snp_rec, ref) == offsetof(GmDevSnpRec, ref) &&
+              offsetof(gm_snp_rec, diploid) == offsetof(GmDevSnpRec, diploid), "gm_snp_rec layout");
+
+namespace {
+template <class B> struct Scoped : B { ~Scoped() { this->release(); } };       // a DevBuf / PinBuf that lives as long as one call
+
+// what the three entry points below ask of the tracks: bin size 1 (Driver.cpp:3207-3211 forces it with --snp), the five sums enabled
+int snp_tracks_ready(gm_index* ix) {
+    if (!ix->cov_bins || ix->cov_bin_size != 1) { gm_set_error("SNP calls need the coverage track with bin size 1 (gm_coverage_reset(ix, 1))"); return GM_E_ARG; }
+    if (!ix->host_only && !ix->nuc_on) { gm_set_error("SNP calls read the per-nucleotide tracks: call gm_coverage_enable_nuc first"); return GM_E_ARG; }
+    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    return GM_OK;
+}
+}  // namespace
+
+extern "C" int gm_snp_calls(gm_index* ix, float snp_pval, int monop, gm_snp_rec* out, uint64_t cap, uint64_t* n_out, void* stream) {
+    if (!ix || !n_out || (cap && !out)) return GM_E_ARG;
+    if (const int rc = snp_tracks_ready(ix)) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    hipStream_t st = S_(stream);
+    const uint64_t l_pac = ix->h.l_pac, bins = ix->cov_bins;
+    const uint64_t per = (uint64_t)std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 20)) * 16;       // positions per launch
+    const uint32_t groups = gmk_snp_call_groups(std::min(per, l_pac));
+    Scoped<DevBuf> d_code, d_pval, d_cnt, d_off, d_out;
+    if (d_code.ensure(per) || d_pval.ensure(per * 8) || d_cnt.ensure((size_t)groups * 4 + 4) || d_off.ensure(((size_t)groups + 1) * 8) ||
+        d_out.ensure((size_t)std::max<uint64_t>(cap, 1) * sizeof(GmDevSnpRec))) return GM_E_NOMEM;
+    unsigned long long total = 0;
+    for (uint64_t lo = 0; lo < l_pac; lo += per) {
+        const uint64_t n = std::min(per, l_pac - lo);
+        KCHK(gmk_snp_call(ix->d_cov.as<float>(), ix->d_nuc.as<float>(), bins, ix->dev, lo, n, snp_pval, monop ? 1 : 0, d_code.as<uint8_t>(), d_pval.as<double>(),
+                          d_cnt.as<uint32_t>(), st));
+        KCHK(gmk_snp_gather(ix->d_cov.as<float>(), ix->d_nuc.as<float>(), bins, ix->dev, lo, n, d_code.as<uint8_t>(), d_pval.as<double>(), d_cnt.as<uint32_t>(),
+                            d_off.as<unsigned long long>(), total, cap, d_out.as<GmDevSnpRec>(), st));
+        unsigned long long got = 0;
+        HIPCHK(hipMemcpyAsync(&got, d_off.as<unsigned long long>() + gmk_snp_call_groups(n), 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        total += got;
+    }
+    const uint64_t have = std::min<uint64_t>(total, cap);
+    if (have) HIPCHK(hipMemcpy(out, d_out.p, (size_t)have * sizeof(gm_snp_rec), hipMemcpyDeviceToHost));
+    *n_out = total;
+    if (total > cap) { gm_set_error("gm_snp_calls: out[] too small"); return GM_E_CAPACITY; }
+    return GM_OK;
+}
+
+extern "C" int gm_dev_snp_stat(gm_index* ix, const float* counts, uint32_t n, int monop, double* p_val, int8_t* pos1, int8_t* pos2, uint8_t* dip) {
+    if (!ix || !counts || !p_val || !pos1 || !pos2 || !dip) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (n == 0) return GM_OK;
+    HIPCHK(hipSetDevice(ix->device));
+    Scoped<DevBuf> d_in, d_p, d_1, d_2, d_d;
+    if (d_in.ensure((size_t)n * 20) || d_p.ensure((size_t)n * 8) || d_1.ensure(n) || d_2.ensure(n) || d_d.ensure(n)) return GM_E_NOMEM;
+    HIPCHK(hipMemcpy(d_in.p, counts, (size_t)n * 20, hipMemcpyHostToDevice));
+    KCHK(gmk_snp_stat(d_in.as<float>(), n, monop ? 1 : 0, d_p.as<double>(), d_1.as<int8_t>(), d_2.as<int8_t>(), d_d.as<uint8_t>(), nullptr));
+    HIPCHK(hipMemcpy(p_val, d_p.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pos1, d_1.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pos2, d_2.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dip, d_d.p, n, hipMemcpyDeviceToHost));
+    return GM_OK;
+}
+
+extern "C" int gm_coverage_write_gmp_calls(gm_index* ix, float snp_pval, int monop, const char* path, int append) {
+    // GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1009 with PrintSNPCall's column (:1011-1090).  A slab of the six tracks comes down from
+    // HBM together with k_snp_call's code byte and p-value per position; the first eight columns are gm_coverage_write_gmp's, byte for byte
+    if (!ix || !path) return GM_E_ARG;
+    if (const int rc = snp_tracks_ready(ix)) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    const GmHostIndex& h = ix->h;
+    const uint64_t bins = ix->cov_bins, nbk = h.l_pac;
+    const uint64_t slab_max = std::min<uint64_t>(nbk, (uint64_t)std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 20)) * host_threads());
+    Scoped<DevBuf> d_code, d_pval, d_cnt;
+    Scoped<PinBuf> h_f, h_code, h_pval;
+    if (d_code.ensure(slab_max) || d_pval.ensure(slab_max * 8) || d_cnt.ensure((size_t)gmk_snp_call_groups(slab_max) * 4 + 4) || h_f.ensure(slab_max * 24) ||
+        h_code.ensure(slab_max) || h_pval.ensure(slab_max * 8)) return GM_E_NOMEM;
+    uint64_t s_lo = 0, s_n = 0;
+    auto slab = [&](uint64_t lo, uint64_t hi) -> int {
+        s_lo = lo; s_n = hi - lo;
+        KCHK(gmk_snp_call(ix->d_cov.as<float>(), ix->d_nuc.as<float>(), bins, ix->dev, lo, s_n, snp_pval, monop ? 1 : 0, d_code.as<uint8_t>(), d_pval.as<double>(),
+                          d_cnt.as<uint32_t>(), nullptr));
+        HIPCHK(hipMemcpy(h_f.as<float>(), ix->d_cov.as<float>() + lo, s_n * 4, hipMemcpyDeviceToHost));
+        for (uint64_t q = 0; q < 5; ++q) HIPCHK(hipMemcpy(h_f.as<float>() + (q + 1) * s_n, ix->d_nuc.as<float>() + q * bins + lo, s_n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_code.p, d_code.p, s_n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_pval.p, d_pval.p, s_n * 8, hipMemcpyDeviceToHost));
+        return GM_OK;
+    };
+    size_t max_name = 0;
+    for (const auto& c : h.contigs) max_name = std::max(max_name, c.name.size());
+    std::vector<int> cur(host_threads(), 0);
+    return write_track_text(path, append, nbk, max_name + 208, [&](uint64_t count, char* w, unsigned c, bool first) -> char* {
+        int& i = cur[c];
+        if (first) i = (int)host_pos2rid(h, count);
+        while ((size_t)i + 1 < h.contigs.size() && count >= h.contigs[(size_t)i + 1].offset) ++i;
+        const uint64_t k = count - s_lo;
+        const float* f = h_f.as<float>();
+        if (!(f[k] > 0.001f)) return w;
+        const GmContig& cg = h.contigs[(size_t)i];
+        memcpy(w, cg.name.data(), cg.name.size()); w += cg.name.size();
+        *w++ = '\t'; w = put_long(w, (long)(count - cg.offset) + 1); *w++ = '\t';
+        w = put_fixed(w, f[k], 5);
+        for (uint64_t q = 1; q <= 5; ++q) { *w++ = '\t'; w = put_fixed(w, f[q * s_n + k], 5); }
+        const unsigned cd = h_code.as<uint8_t>()[k];
+        const unsigned at = (h.pac[count >> 2] >> ((~count & 3) << 1)) & 3, p1 = cd & 7u, dip = (cd >> 5) & 1u, r2 = (cd >> 3) & 3u;
+        *w++ = '\t'; *w++ = (cd & 0x40) ? 'Y' : 'N';
+        if (p1 != at || dip) {                                                // :1065-1085
+            *w++ = ':'; *w++ = "acgt"[at]; *w++ = '-'; *w++ = '>'; *w++ = "acgtn"[p1];
+            if (dip) { *w++ = '/'; *w++ = "acgtn"[r2 + (r2 >= p1 ? 1u : 0u)]; }
+            w += snprintf(w, 40, " p_val=%.2e", h_pval.as<double>()[k]);
+        }
+        *w++ = '\n';
+        return w;
+    }, slab);
 }

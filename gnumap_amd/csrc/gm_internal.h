@@ -137,6 +137,10 @@ struct GmDevPos { unsigned long long pos; uint8_t strand; uint8_t pad[7]; };
 struct GmDevSamRec { uint32_t read, pad0; unsigned long long pos; uint32_t contig, pad1; unsigned long long chr_pos; uint8_t strand; uint8_t pad2[3];
                      int32_t mapq; float a_score, post_prob; int32_t sim_matches; uint32_t cigar_off; };
 
+// gm_snp_rec (layout asserted in gm_api.cpp): a row of --snp's .gmp that carries a 'Y' call, written by k_snp_gather (gm_snpcall.hip)
+struct GmDevSnpRec { unsigned long long pos; uint32_t contig, pad0; unsigned long long chr_pos; float total, nuc[5]; double p_val; uint8_t ref, alt1, alt2, diploid;
+                     uint8_t pad1[4]; };
+
 // workspace of the grouping kernels (process_hits' unique map on the device); per-hit arrays share the CSR of hit_begin
 struct GmDevGroup {
     GmRawHit* sorted;               // accepted hits of a read in the reference's processing order
@@ -217,6 +221,14 @@ size_t gmk_pair_hmm_cells(uint32_t Lmax);            // doubles of scratch per w
 int gmk_pair_hmm(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, const GmCand* items, uint32_t n, double* scratch, uint32_t Lmax, float* hmm, void* stream);
 int gmk_snp_deposit(float* cov, float* nuc, uint64_t bins, uint32_t bin_size, const GmDevBatch& b, const GmDevMatch* matches, const GmDevPos* positions,
                     uint32_t m0, uint32_t count, const float* post, const float* hmm, uint32_t Lmax, void* stream);
+// gm_snpcall.hip: --snp's likelihood-ratio column (PrintSNPCall): code byte + p-value per position of [lo, lo + n), 'Y' rows per workgroup;
+// then the 'Y' rows in position order (off: workgroups + 1 words of scratch; off[workgroups] = their number, to be read back by the caller)
+uint32_t gmk_snp_call_groups(uint64_t n);
+int gmk_snp_call(const float* cov, const float* nuc, uint64_t bins, const GmDevIndex& ix, uint64_t lo, uint64_t n, float snp_pval, int monop, uint8_t* code, double* pval,
+                 uint32_t* ycnt, void* stream);
+int gmk_snp_gather(const float* cov, const float* nuc, uint64_t bins, const GmDevIndex& ix, uint64_t lo, uint64_t n, const uint8_t* code, const double* pval,
+                   const uint32_t* ycnt, unsigned long long* off, unsigned long long base, unsigned long long cap, GmDevSnpRec* out, void* stream);
+int gmk_snp_stat(const float* counts, uint32_t n, int monop, double* pval, int8_t* pos1, int8_t* pos2, uint8_t* dip, void* stream);
 int gmk_compact(const GmDevBatch& b, void* stream);
 int gmk_scan_hits(const GmDevBatch& b, void* stream);
 int gmk_scatter(const GmDevBatch& b, uint32_t grid, void* stream);

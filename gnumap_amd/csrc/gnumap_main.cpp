@@ -46,6 +46,8 @@ struct Options {
     int workers = 3;            // host threads (and gm_batch objects) per GPU (measured: 2 -> 9.6, 3 -> 11.4, 4 -> 11.0 M reads/s)
     int fmt_threads = 0;        // SAM formatter threads per block (0 = min(8, cores))
     int threads = 1;            // -c: accepted for compatibility (the GPU replaces the pthread pool)
+    float snp_pval = 0.001f;    // --snp_pval: gSNP_PVAL inc/const_define.h:33
+    bool snp_monop = false, snp_calls = false;      // --snp_monop: gSNP_MONOP; --snp_calls: <out>.gmp with PrintSNPCall's ninth column
 };
 
 static void usage(int rc, const char* msg) {
@@ -67,7 +69,11 @@ static void usage(int rc, const char* msg) {
             "  -S, --subst_file=STRING      5 x 4 substitution matrix file (rows a c g t n; scores are then used unscaled)\n"
             "  -c, --num_proc=INT           accepted for compatibility (the GPU path ignores it)\n"
             "  -b, --bs_seq / --b2 / -d, --a_to_g   bisulfite / A-to-G scoring\n"
-            "      --snp                    pair-HMM per-nucleotide deposit (SNPScoredSeq); <out>.gmp without the likelihood-ratio columns\n"
+            "      --snp                    pair-HMM per-nucleotide deposit (SNPScoredSeq); <out>.gmp with eight columns (no SNP call)\n"
+            "      --snp_calls              with --snp: append the reference's ninth column, the likelihood-ratio SNP call\n"
+            "                               (N, [YN]:r->x p_val=.., [YN]:r->x/y p_val=..); not yet the default of --snp\n"
+            "      --snp_pval=DOUBLE        P-Value cutoff for calling SNPs (default: 0.001); changes the ninth column only\n"
+            "      --snp_monop              monoploid SNP calling; changes the ninth column only\n"
             "      --no_nw                  use k-mer hit counts instead of Needleman-Wunsch alignments\n"
             "      --fast, --print_all_sam, --illumina, --up_strand, --down_strand, --bin_size=INT\n"
             "  MI355X options: --gpus=N  --batch=N (blocks of exactly N reads)  --chunk_reads=N  --workers=N  --fmt_threads=N  --locate=sampled|full\n");
@@ -105,6 +111,11 @@ static void parse_args(int argc, char** argv, Options& o) {
             else if (!strcmp(s, "b2")) o.p.mode = GM_MODE_BS2;
             else if (!strcmp(s, "a_to_g")) o.p.mode = GM_MODE_ATOG;
             else if (!strcmp(s, "snp")) o.p.mode = GM_MODE_SNP;             // Driver.cpp:3207-3211: gSNP, bin size 1
+            else if (starts(s, "snp_pval=")) {                                   // Driver.cpp:3030, 3200: "%f" into the float gSNP_PVAL
+                if (sscanf(s + 9, "%f", &o.snp_pval) < 1) { fprintf(stderr, "Error: could not read --snp_pval in: %s\n", a); exit(1); }
+            }
+            else if (!strcmp(s, "snp_monop")) o.snp_monop = true;
+            else if (!strcmp(s, "snp_calls")) o.snp_calls = true;
             else if (!strcmp(s, "fast")) o.p.fast = 1;
             else if (starts(s, "bin_size=")) o.p.bin_size = atoi(s + 9);
             else if (starts(s, "jump=")) o.p.jump = atoi(s + 5);
@@ -786,16 +797,20 @@ int main(int argc, char** argv) {
     auto t_cov0 = std::chrono::steady_clock::now();
     // coverage: all-reduce over the GPUs, then PrintFinalSGR / PrintFinalBisulfite
     if (gm_coverage_allreduce(gpu_ix.data(), o.gpus) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
-    PinVec<float> cov; cov.ensure(gm_coverage_bins(gpu_ix[0]));                         // page-locked: the 1.5 GB of a human track come down at link rate
-    if (gm_coverage_download(gpu_ix[0], cov.data()) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
-    if (o.p.mode == GM_MODE_NORMAL) {                                  // GenomeBwt::PrintFinal src/GenomeBwt.cpp:915-926
-        if (gm_coverage_write_sgr(gpu_ix[0], cov.data(), (o.output + ".sgr").c_str(), 0) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+    if (o.p.mode == GM_MODE_SNP && o.snp_calls) {                      // PrintFinalSNP with PrintSNPCall's column: the tracks are read where they are, slab by slab
+        if (gm_coverage_write_gmp_calls(gpu_ix[0], o.snp_pval, o.snp_monop, (o.output + ".gmp").c_str(), 0) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
     } else {
-        std::vector<float> nuc(5 * (size_t)gm_coverage_bins(gpu_ix[0]));
-        if (gm_coverage_download_nuc(gpu_ix[0], nuc.data()) != GM_OK ||
-            gm_coverage_write_gmp(gpu_ix[0], &o.p, cov.data(), nuc.data(), (o.output + ".gmp").c_str(), 0) != GM_OK) {
-            fprintf(stderr, "ERROR: %s\n", gm_last_error());
-            return 1;
+        PinVec<float> cov; cov.ensure(gm_coverage_bins(gpu_ix[0]));                     // page-locked: the 1.5 GB of a human track come down at link rate
+        if (gm_coverage_download(gpu_ix[0], cov.data()) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+        if (o.p.mode == GM_MODE_NORMAL) {                              // GenomeBwt::PrintFinal src/GenomeBwt.cpp:915-926
+            if (gm_coverage_write_sgr(gpu_ix[0], cov.data(), (o.output + ".sgr").c_str(), 0) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+        } else {
+            std::vector<float> nuc(5 * (size_t)gm_coverage_bins(gpu_ix[0]));
+            if (gm_coverage_download_nuc(gpu_ix[0], nuc.data()) != GM_OK ||
+                gm_coverage_write_gmp(gpu_ix[0], &o.p, cov.data(), nuc.data(), (o.output + ".gmp").c_str(), 0) != GM_OK) {
+                fprintf(stderr, "ERROR: %s\n", gm_last_error());
+                return 1;
+            }
         }
     }
     uint64_t n_reads = 0, n_matched = 0, n_records = 0;

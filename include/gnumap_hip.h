@@ -277,8 +277,33 @@ int gm_coverage_enable_nuc(gm_index*);
 void* gm_coverage_nuc_device_ptr(gm_index*);
 int gm_coverage_download_nuc(gm_index*, float* host /* 5 x bins */);
 int gm_coverage_write_gmp(gm_index*, const gm_params*, const float* host_bins, const float* host_nuc, const char* path, int append);
-/* (GM_MODE_SNP: PrintFinalSNP src/GenomeBwt.cpp:930-1090 - every position above 0.001: contig, position, %.5f total, five %.5f sums.  The
- * likelihood-ratio columns PrintSNPCall appends are NOT written: they need GSL's gsl_cdf_chisq_P, outside this hot path.) */
+/* (GM_MODE_SNP: PrintFinalSNP src/GenomeBwt.cpp:930-1009 - every position above 0.001: contig, position, %.5f total, five %.5f sums.  This
+ * writer stops there, eight columns; gm_coverage_write_gmp_calls below writes the same rows with PrintSNPCall's ninth column.) */
+
+/* ---- SNP calls (--snp): GenomeBwt::PrintSNPCall src/GenomeBwt.cpp:1011-1090 with is_snp :875-901, LRT :739-753, dipLRT :758-873 ----
+ * One device pass (k_snp_call) over the total track and the five per-nucleotide tracks in HBM.  The reference's one GSL function,
+ * gsl_cdf_chisq_P(x, 1 | 2), is evaluated in closed form - erf(sqrt(x/2)), 1 - exp(-x/2), 0 for x <= 0 - and the p-value as 1 - P in
+ * fp64 like the reference's.  All three need bin size 1 and gm_coverage_enable_nuc (GM_E_ARG otherwise).  snp_pval is the reference's
+ * --snp_pval (gSNP_PVAL, a float, default 0.001), monop its --snp_monop (LRT instead of dipLRT).
+ * Two departures, where the reference has no defined answer: a forced-monoploid position (first / second sum above 3, or no second)
+ * is never diploid and carries pval1 (the reference reads one float before its array there); and the likelihood ratios are kept as
+ * logarithms, so totals above ~440, where the reference's pow() underflows to 0 / 0, still give a finite p-value. */
+typedef struct {
+    uint64_t pos;           /* 0-based on the concatenated reference */
+    uint32_t contig;        /* contig index */
+    uint64_t chr_pos;       /* 1-based within the contig, as the .gmp prints it */
+    float total, nuc[5];    /* the row's six numbers: total, a c g t n */
+    double p_val;
+    uint8_t ref, alt1, alt2, diploid;   /* 0..4 = a c g t n; alt2 = 255 unless diploid */
+} gm_snp_rec;
+/* the rows PrintSNPCall marks 'Y', ascending position.  GM_E_CAPACITY when there are more than cap: *n_out has the number required */
+int gm_snp_calls(gm_index*, float snp_pval, int monop, gm_snp_rec* out, uint64_t cap, uint64_t* n_out, void* hip_stream);
+/* is_snp (src/GenomeBwt.cpp:875-901) on caller-supplied counts (unit level, parity tests): n x 5 floats -> p-value, first maximum,
+ * second maximum (-1 where dipLRT drops it or with monop), diploid */
+int gm_dev_snp_stat(gm_index*, const float* counts, uint32_t n, int monop, double* p_val, int8_t* pos1, int8_t* pos2, uint8_t* dip);
+/* PrintFinalSNP (src/GenomeBwt.cpp:930-1009) with its ninth column: N, [YN]:r->x p_val=%.2e or [YN]:r->x/y p_val=%.2e.  The tracks are read
+ * from HBM slab by slab (GM_TRACK_SLICE positions per host thread); no host copy of them is needed */
+int gm_coverage_write_gmp_calls(gm_index*, float snp_pval, int monop, const char* path, int append);
 
 #ifdef __cplusplus
 }
