@@ -63,6 +63,14 @@ class gm_sam_out(C.Structure):
     _fields_ = [("recs", C.c_void_p), ("recs_cap", u64), ("n_recs", u64), ("cigar_pool", C.c_void_p), ("cigar_cap", u64), ("cigar_len", u64)]
 
 
+class gm_read_text(C.Structure):
+    _fields_ = [("names", C.c_void_p), ("name_off", C.c_void_p), ("qual_tail", C.c_void_p), ("qual_tail_off", C.c_void_p)]
+
+
+class gm_sam_text(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_cap", u64), ("text_len", u64), ("n_recs", u64), ("row_off", C.c_void_p), ("row_cap", u64)]
+
+
 class gm_counters(C.Structure):
     _fields_ = [(n, u64) for n in ("reads", "kmers_searched", "occ_calls", "occ_blocks", "seeds_used", "sa_hits", "lf_steps", "candidates",
                                    "nw_cells", "accepted", "vote_retries", "table_lookups")]
@@ -84,7 +92,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_index_contig_offset", "gm_index_window", "gm_params_default", "gm_params_finalize", "gm_params_load_subst", "gm_batch_create", "gm_batch_destroy",
            "gm_batch_upload", "gm_map_batch_device", "gm_batch_counters", "gm_batch_path", "gm_batch_set_profiling", "gm_batch_kernel_times", "gm_kernel_name",
            "gm_batch_raw_hits", "gm_stream_create", "gm_stream_destroy", "gm_host_alloc", "gm_host_free", "gm_map_batch", "gm_output_batch",
-           "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait",
+           "gm_output_batch_text", "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait", "gm_dev_fmt_g6",
            "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
            "gm_coverage_device_ptr", "gm_coverage_add", "gm_coverage_download", "gm_coverage_allreduce", "gm_coverage_write_sgr", "gm_coverage_enable_nuc", "gm_coverage_nuc_device_ptr",
            "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls"]
@@ -137,6 +145,9 @@ def load_library():
     L.gm_host_free.argtypes = [C.c_void_p]; L.gm_host_free.restype = None
     L.gm_map_batch.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_reads), C.POINTER(gm_hits), C.c_void_p]
     L.gm_output_batch.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_reads), C.POINTER(gm_hits), C.POINTER(gm_sam_out), C.c_void_p]
+    L.gm_output_batch_text.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_reads), C.POINTER(gm_read_text), C.POINTER(gm_hits),
+                                       C.POINTER(gm_sam_text), C.c_void_p]
+    L.gm_dev_fmt_g6.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_sa_interval.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
     L.gm_dev_nw_score.argtypes = [C.c_void_p, C.POINTER(gm_params), C.POINTER(gm_reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -293,6 +304,14 @@ class Index:
         out = np.zeros((len(read_idx), B.shape[1], 5), np.float32)
         _chk(lib().gm_dev_pair_hmm(self.h, C.byref(params.c), C.byref(r), read_idx.ctypes.data, strand.ctypes.data, pos.ctypes.data, len(read_idx), out.ctypes.data))
         return out
+
+    def dev_fmt_g6(self, values):
+        """gm_dev_fmt_g6: printf("%g") of every value as the device prints XA / XP; a list of bytes (b"" = outside the domain)"""
+        v = np.ascontiguousarray(values, np.float64); n = len(v)
+        out = np.zeros((n, 16), np.uint8); ln = np.zeros(n, np.uint8)
+        _chk(lib().gm_dev_fmt_g6(self.h, v.ctypes.data, n, out.ctypes.data, ln.ctypes.data))
+        raw = out.tobytes()
+        return [raw[16 * i:16 * i + int(ln[i])] for i in range(n)]
 
     # ---- coverage ----
     def coverage_reset(self, bin_size):
@@ -456,6 +475,45 @@ class Batch:
         raw = pool.tobytes()
         cigars = [raw[o:raw.index(b"\0", o)] for o in recs["cigar_off"]]
         return recs, cigars
+
+    def output_text(self, params, res, names, qual_tails=None, stream=None, text_cap=None):
+        """gm_output_batch_text on the result of map(): (SAM rows as bytes, row offsets [n_recs + 1]).  names: one bytes per read (what
+        follows '@'); qual_tails: None, or one bytes per read (what a quality line holds beyond the length of its sequence).
+        text_cap: first capacity to try (None: a guess; the call is repeated with the size GM_E_CAPACITY reports)."""
+        rt, keep = _pack_read_text([bytes(x) for x in names], None if qual_tails is None else [bytes(x) for x in qual_tails], self.n)
+        stride = res["_reads"].stride
+        tcap = int(text_cap) if text_cap is not None else self.n * (2 * stride + 160) + 1024
+        rcap = 2 * self.n + 64
+        self.text_calls = 0
+        while True:
+            text = np.zeros(max(tcap, 1), np.uint8); row_off = np.zeros(rcap, np.uint64)
+            st = gm_sam_text()
+            st.text = text.ctypes.data; st.text_cap = tcap; st.row_off = row_off.ctypes.data; st.row_cap = rcap
+            rc = lib().gm_output_batch_text(self.index.h, C.byref(params.c), self.h, C.byref(res["_reads"]), C.byref(rt), C.byref(res["_struct"]), C.byref(st), stream)
+            self.text_calls += 1
+            if rc == GM_E_CAPACITY:
+                tcap, rcap = max(tcap, int(st.text_cap)), max(rcap, int(st.row_cap))
+                continue
+            _chk(rc)
+            break
+        del keep
+        return text[:st.text_len].tobytes(), row_off[:st.n_recs + 1].copy()
+
+
+def _pack_read_text(names, qual_tails, n):
+    """(gm_read_text, the arrays it points into) from lists of bytes"""
+    if len(names) != n or (qual_tails is not None and len(qual_tails) != n):
+        raise ValueError("one name (and one quality tail) per read")
+    pool = np.frombuffer(b"".join(names) + b"\0", np.uint8).copy()
+    off = np.zeros(n + 1, np.uint64); off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+    rt = gm_read_text(); rt.names = pool.ctypes.data; rt.name_off = off.ctypes.data
+    keep = [pool, off]
+    if qual_tails is not None:
+        tp = np.frombuffer(b"".join(qual_tails) + b"\0", np.uint8).copy()
+        to = np.zeros(n + 1, np.uint64); to[1:] = np.cumsum([len(x) for x in qual_tails], dtype=np.uint64)
+        rt.qual_tail = tp.ctypes.data; rt.qual_tail_off = to.ctypes.data
+        keep += [tp, to]
+    return rt, keep
 
 
 def pinned_empty(shape, dtype):

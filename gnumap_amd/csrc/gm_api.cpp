@@ -108,6 +108,8 @@ struct gm_index {
     bool host_only = false;
     bool full_sa = false;
     DevBuf d_bwt, d_sa, d_full, d_pac, d_contig, d_cov, d_ptab, d_planes, d_nuc;
+    DevBuf d_cnames, d_cname_off;           // contig names back to back + n_seqs + 1 offsets: what k_out_text_rows prints (uploaded by the first gm_output_batch_text)
+    bool cnames_on = false;
     bool nuc_on = false;
     GmDevIndex dev{};
     uint64_t cov_bins = 0;
@@ -134,7 +136,8 @@ struct gm_batch {
         g_sorted, g_ord, g_lead, g_krank, g_khash, g_nmatch, g_mbegin, g_multi, g_big, g_bigdone, g_sk0, g_sk1, g_si0, g_si1, g_matches, g_mhit, g_positions, scan_tmp,
         o_small, o_posmatch, o_post, o_mapq, o_emit, o_reccnt, o_cigcnt, o_cigall, o_recoff, o_cigoff, o_recs, o_pool, o_codes,
         pair_fb, pair_list,             // k_vote_pair: the reads it leaves to k_vote_bucket (one byte each), their list + its counter
-        snp_scratch, snp_hmm;           // --snp: forward matrices of a chunk of kept sequences, their 5 floats per window position
+        snp_scratch, snp_hmm,           // --snp: forward matrices of a chunk of kept sequences, their 5 floats per window position
+        t_names, t_nameoff, t_qtail, t_qtailoff, t_slots, t_rowlen, t_rowoff, t_text, t_bad;     // gm_output_batch_text: the block's names, tails and row offsets, the text
     PinBuf h_top, h_hbegin, h_ord, h_post, h_mapq, h_emit, h_mhit, h_stat;      // h_stat: the small status words a phase reads back (page-locked: one short DMA)
     std::vector<double> h_exp;          // exp(score) of every accepted hit of the last gm_map_batch (reused by gm_output_batch)
     uint64_t cache_hits = 0, cache_matches = 0;
@@ -497,7 +500,7 @@ extern "C" void gm_index_close(gm_index* ix) {
     if (!ix->host_only && ix->device >= 0) {
         (void)hipSetDevice(ix->device);
         ix->d_bwt.release(); ix->d_sa.release(); ix->d_full.release(); ix->d_pac.release(); ix->d_contig.release();
-        ix->d_cov.release(); ix->d_ptab.release(); ix->d_planes.release(); ix->d_nuc.release();
+        ix->d_cov.release(); ix->d_ptab.release(); ix->d_planes.release(); ix->d_nuc.release(); ix->d_cnames.release(); ix->d_cname_off.release();
         for (auto& kv : ix->ptabs) kv.second.release();
         for (auto& kv : ix->kmer_tabs) kv.second.release();
         for (auto& kv : ix->kmer_ctabs) kv.second.release();
@@ -582,7 +585,8 @@ extern "C" void gm_batch_destroy(gm_batch* b) {
                       &b->tb_len, &b->band_moves, &b->pack,
                       &b->g_sorted, &b->g_ord, &b->g_lead, &b->g_krank, &b->g_khash, &b->g_nmatch, &b->g_mbegin, &b->g_multi, &b->g_big, &b->g_bigdone, &b->g_sk0, &b->g_sk1, &b->g_si0, &b->g_si1, &b->g_matches, &b->g_mhit, &b->g_positions,
                       &b->scan_tmp, &b->o_small, &b->o_posmatch, &b->o_post, &b->o_mapq, &b->o_emit, &b->o_reccnt, &b->o_cigcnt, &b->o_cigall, &b->o_recoff, &b->o_cigoff,
-                      &b->o_recs, &b->o_pool, &b->o_codes, &b->snp_scratch, &b->snp_hmm, &b->pair_fb, &b->pair_list };
+                      &b->o_recs, &b->o_pool, &b->o_codes, &b->snp_scratch, &b->snp_hmm, &b->pair_fb, &b->pair_list,
+                      &b->t_names, &b->t_nameoff, &b->t_qtail, &b->t_qtailoff, &b->t_slots, &b->t_rowlen, &b->t_rowoff, &b->t_text, &b->t_bad };
     for (DevBuf* d : all) d->release();
     PinBuf* pins[] = { &b->h_top, &b->h_hbegin, &b->h_ord, &b->h_post, &b->h_mapq, &b->h_emit, &b->h_mhit, &b->h_stat };
     for (PinBuf* d : pins) d->release();
@@ -1459,10 +1463,21 @@ extern "C" int gm_map_batch(gm_index* ix, const gm_params* p, gm_batch* b, const
 // MAPQ = round(-10 log10(1 - p)): glibc exp / log / round).  Device: traceback of every kept sequence, run-length CIGAR text, SAM
 // rows, coverage deposit (+ the per-nucleotide track of -b / -d).  Nothing per read is done on the host beyond that pass.
 // ------------------------------------------------------------------------------------------------
-extern "C" int gm_output_batch(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_hits* hits, gm_sam_out* out, void* stream) {
-    if (!ix || !p || !b || !reads || !hits || !out) return GM_E_ARG;
+// `out` (records + CIGAR pool to the host: gm_output_batch) or `rt` + `tout` (finished SAM text: gm_output_batch_text), never both
+static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_hits* hits, gm_sam_out* out, const gm_read_text* rt,
+                             gm_sam_text* tout, void* stream) {
     if (hits->n != b->n || reads->n != b->n) { gm_set_error("hits / reads do not belong to the batch"); return GM_E_ARG; }
-    PhaseClock pc("gm_output_batch");
+    PhaseClock pc(tout ? "gm_output_batch_text" : "gm_output_batch");
+    gm_sam_out no_host_records{};              // text form: the records and the CIGAR pool stay in HBM
+    if (!out) out = &no_host_records;
+    if (tout) {
+        tout->text_len = 0; tout->n_recs = 0;
+        if (tout->row_off && tout->row_cap) tout->row_off[0] = 0;
+        const uint32_t n = hits->n;
+        bool asc = rt->names && rt->name_off && (rt->qual_tail != nullptr) == (rt->qual_tail_off != nullptr);
+        for (uint32_t i = 0; asc && i < n; ++i) asc = rt->name_off[i] <= rt->name_off[i + 1] && (!rt->qual_tail_off || rt->qual_tail_off[i] <= rt->qual_tail_off[i + 1]);
+        if (!asc) { gm_set_error("gm_read_text: names / name_off missing, qual_tail without qual_tail_off (or the reverse), or offsets that do not ascend"); return GM_E_ARG; }
+    }
     HIPCHK(hipSetDevice(ix->device));
     hipStream_t st = S_(stream);
     GmDevParams dp;
@@ -1579,7 +1594,7 @@ extern "C" int gm_output_batch(gm_index* ix, const gm_params* p, gm_batch* b, co
     pc.lap("traceback+count");
     // capacity first: a call that is going to be repeated with larger buffers must not deposit coverage twice
     out->n_recs = n_recs; out->cigar_len = cig_len;
-    if (n_recs > out->recs_cap || cig_len > out->cigar_cap) {
+    if (!tout && (n_recs > out->recs_cap || cig_len > out->cigar_cap)) {
         out->recs_cap = n_recs; out->cigar_cap = cig_len;
         gm_set_error("output buffers too small");
         return GM_E_CAPACITY;
@@ -1590,8 +1605,74 @@ extern "C" int gm_output_batch(gm_index* ix, const gm_params* p, gm_batch* b, co
         KCHK(gmk_out_write(ix->dev, b->dev, d_m, d_p, n_m, b->o_emit.as<uint8_t>(), b->o_mapq.as<int32_t>(), b->o_post.as<float>(), b->tb_ops.as<unsigned long long>(),
                            ops_words, b->tb_len.as<uint16_t>(), p->nw, b->o_recoff.as<uint64_t>(), b->o_cigoff.as<uint64_t>(),
                            b->o_recs.as<GmDevSamRec>(), b->o_pool.as<char>(), st));
-        HIPCHK(hipMemcpyAsync(out->recs, b->o_recs.p, (size_t)n_recs * sizeof(gm_sam_rec), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(out->cigar_pool, b->o_pool.p, (size_t)cig_len, hipMemcpyDeviceToHost, st));
+        if (!tout) {
+            HIPCHK(hipMemcpyAsync(out->recs, b->o_recs.p, (size_t)n_recs * sizeof(gm_sam_rec), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(out->cigar_pool, b->o_pool.p, (size_t)cig_len, hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (tout) {
+        // ---- SAM text: tails + row lengths, their scan, then - once the caller's buffer is known to hold them - the rows ----
+        tout->n_recs = n_recs;
+        if (n_recs) {
+            const uint32_t n_seqs = (uint32_t)ix->h.contigs.size();
+            {   // contig names, once per index
+                std::lock_guard<std::mutex> lk(ix->mu);
+                if (!ix->cnames_on) {
+                    std::string all; std::vector<uint32_t> off(n_seqs + 1, 0);
+                    for (uint32_t i = 0; i < n_seqs; ++i) { off[i] = (uint32_t)all.size(); all += ix->h.contigs[i].name; }
+                    off[n_seqs] = (uint32_t)all.size();
+                    if (ix->d_cnames.ensure(all.size() + 16) || ix->d_cname_off.ensure(off.size() * 4)) return GM_E_NOMEM;
+                    HIPCHK(hipMemcpy(ix->d_cnames.p, all.data(), all.size(), hipMemcpyHostToDevice));
+                    HIPCHK(hipMemcpy(ix->d_cname_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+                    ix->cnames_on = true;
+                }
+            }
+            const uint64_t name_bytes = rt->name_off[n] - rt->name_off[0], tail_bytes = rt->qual_tail_off ? rt->qual_tail_off[n] - rt->qual_tail_off[0] : 0;
+            if (b->t_names.ensure((size_t)name_bytes + 16) || b->t_nameoff.ensure(((size_t)n + 1) * 8) || b->t_slots.ensure((size_t)n_recs * 64) ||
+                b->t_rowlen.ensure((size_t)n_recs * 4) || b->t_rowoff.ensure(((size_t)n_recs + 1) * 8) || b->t_bad.ensure(8) ||
+                b->scan_tmp.ensure(((size_t)n_recs / 1024 + 8) * 8) ||
+                (rt->qual_tail_off && (b->t_qtail.ensure((size_t)tail_bytes + 16) || b->t_qtailoff.ensure(((size_t)n + 1) * 8)))) return GM_E_NOMEM;
+            // the offsets are used as they are: the kernels index names - name_off[0] so that a caller may pass a window of a larger pool
+            if (name_bytes) HIPCHK(hipMemcpyAsync(b->t_names.p, rt->names + rt->name_off[0], (size_t)name_bytes, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(b->t_nameoff.p, rt->name_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+            if (rt->qual_tail_off) {
+                if (tail_bytes) HIPCHK(hipMemcpyAsync(b->t_qtail.p, rt->qual_tail + rt->qual_tail_off[0], (size_t)tail_bytes, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(b->t_qtailoff.p, rt->qual_tail_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+            }
+            HIPCHK(hipMemsetAsync(b->t_bad.p, 0xFF, 8, st));
+            GmDevText t{};
+            t.recs = b->o_recs.as<GmDevSamRec>(); t.n_recs = n_recs; t.pool = b->o_pool.as<char>();
+            t.names = b->t_names.as<char>() - rt->name_off[0]; t.name_off = b->t_nameoff.as<uint64_t>();
+            t.qtail = rt->qual_tail_off ? b->t_qtail.as<char>() - rt->qual_tail_off[0] : nullptr; t.qtail_off = rt->qual_tail_off ? b->t_qtailoff.as<uint64_t>() : nullptr;
+            t.cnames = ix->d_cnames.as<char>(); t.cname_off = ix->d_cname_off.as<uint32_t>();
+            t.slots = b->t_slots.as<uint8_t>(); t.row_len = b->t_rowlen.as<uint32_t>(); t.row_off = b->t_rowoff.as<uint64_t>();
+            t.inv_adjust = 1.0 / p->adjust; t.bad = b->t_bad.as<unsigned long long>();
+            KCHK(gmk_out_text_sizes(b->dev, t, st));
+            KCHK(gmk_scan_u32(t.row_len, n_recs, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
+            uint64_t text_len = 0; unsigned long long bad = ~0ull;
+            HIPCHK(hipMemcpyAsync(&text_len, b->t_rowoff.as<uint64_t>() + n_recs, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&bad, b->t_bad.p, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            pc.lap("text sizes");
+            if (bad != ~0ull) {
+                gm_set_error("SAM record " + std::to_string(bad) + ": XA or XP is outside the range the device prints exactly (2^-200 <= |v| < 2^200)");
+                return GM_E_UNSUPPORTED;
+            }
+            tout->text_len = text_len;
+            // capacity first, as above: nothing has been deposited yet, the repeated call deposits once
+            const bool rows_fit = !tout->row_off || tout->row_cap >= n_recs + 1;
+            if (text_len > tout->text_cap || !rows_fit) {
+                tout->text_cap = text_len;
+                if (tout->row_off) tout->row_cap = n_recs + 1;
+                gm_set_error("output buffers too small");
+                return GM_E_CAPACITY;
+            }
+            if (b->t_text.ensure((size_t)text_len + 16)) return GM_E_NOMEM;
+            t.text = b->t_text.as<char>();
+            KCHK(gmk_out_text_rows(b->dev, t, st));
+            HIPCHK(hipMemcpyAsync(tout->text, b->t_text.p, (size_t)text_len, hipMemcpyDeviceToHost, st));
+            if (tout->row_off) HIPCHK(hipMemcpyAsync(tout->row_off, b->t_rowoff.p, ((size_t)n_recs + 1) * 8, hipMemcpyDeviceToHost, st));
+        }
     }
     if (snp && ix->cov_bins && n_p) {
         // SNPScoredSeq::score: no traceback in the deposit - the pair HMM of every kept sequence against its window, chunk by chunk (a
@@ -1614,6 +1695,49 @@ extern "C" int gm_output_batch(gm_index* ix, const gm_params* p, gm_batch* b, co
     HIPCHK(hipStreamSynchronize(st));
     pc.lap("records+coverage");
     return GM_OK;
+}
+
+extern "C" int gm_output_batch(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_hits* hits, gm_sam_out* out, void* stream) {
+    if (!ix || !p || !b || !reads || !hits || !out) return GM_E_ARG;
+    return output_batch_impl(ix, p, b, reads, hits, out, nullptr, nullptr, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// gm_output_batch_text = gm_output_batch with a different ending: the SAM rows leave as finished text (src/Driver.cpp:2146-2217,
+// ScoredSeq::get_SAM inc/ScoredSeq.h:293-404, reverse_comp / reverse_CIGAR inc/SequenceOperations.h:56-123), written by
+// k_out_text_sizes / k_out_text_rows (gm_output.hip) from the records and the CIGAR pool where k_out_write left them.
+// ------------------------------------------------------------------------------------------------
+extern "C" int gm_output_batch_text(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_read_text* rt, const gm_hits* hits, gm_sam_text* out,
+                                    void* stream) {
+    if (!ix) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!p || !b || !reads || !hits || !out) return GM_E_ARG;
+    if (!rt) { gm_set_error("gm_output_batch_text: gm_read_text is NULL"); return GM_E_ARG; }
+    if (!out->text && out->text_cap) { gm_set_error("gm_sam_text: text is NULL"); return GM_E_ARG; }
+    return output_batch_impl(ix, p, b, reads, hits, nullptr, rt, out, stream);
+}
+
+// gm_put_g6_hd (gm_fmt_dev.h) on the device, one lane per value: out[i * 16 ..] holds len[i] characters (0 = outside its domain)
+extern "C" int gm_dev_fmt_g6(gm_index* ix, const double* v, uint32_t n, char* out, uint8_t* len) {
+    if (!ix || (n && (!v || !out || !len))) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (n == 0) return GM_OK;
+    HIPCHK(hipSetDevice(ix->device));
+    DevBuf dv, dout, dlen;
+    int rc = GM_OK;
+    if (dv.ensure((size_t)n * 8) || dout.ensure((size_t)n * 16) || dlen.ensure(n)) rc = GM_E_NOMEM;
+    auto run = [&]() -> int {
+        HIPCHK(hipMemcpy(dv.p, v, (size_t)n * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(dout.p, 0, (size_t)n * 16));
+        KCHK(gmk_fmt_g6(dv.as<double>(), n, dout.as<char>(), dlen.as<uint8_t>(), nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(len, dlen.p, n, hipMemcpyDeviceToHost));
+        return GM_OK;
+    };
+    if (rc == GM_OK) rc = run();
+    dv.release(); dout.release(); dlen.release();
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------

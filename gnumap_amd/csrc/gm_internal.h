@@ -137,6 +137,22 @@ struct GmDevPos { unsigned long long pos; uint8_t strand; uint8_t pad[7]; };
 struct GmDevSamRec { uint32_t read, pad0; unsigned long long pos; uint32_t contig, pad1; unsigned long long chr_pos; uint8_t strand; uint8_t pad2[3];
                      int32_t mapq; float a_score, post_prob; int32_t sim_matches; uint32_t cigar_off; };
 
+// what the SAM text kernels (k_out_text_*, gm_output.hip) read and write besides the block itself
+struct GmDevText {
+    const GmDevSamRec* recs; unsigned long long n_recs;
+    const char* pool;                               // CIGAR pool of k_out_write (NUL-terminated, forward orientation)
+    const char* names; const uint64_t* name_off;    // gm_read_text::names / name_off of the block, in HBM
+    const char* qtail; const uint64_t* qtail_off;   // gm_read_text::qual_tail / qual_tail_off, or null
+    const char* cnames; const uint32_t* cname_off;  // contig names back to back, n_seqs + 1 offsets (uploaded once per index)
+    // 64 bytes per record: [0, 56) the numeric tail "XA:f:..\tXP:f:..\tX0:i:..\n", [56] u16 CIGAR length in the pool, [58] u16 CIGAR
+    // length in the row (a reversed CIGAR drops trailing digits without an operation), [60] u8 length of the tail
+    uint8_t* slots;
+    uint32_t* row_len; const uint64_t* row_off;     // bytes of every row; their exclusive scan (n_recs + 1)
+    char* text;
+    double inv_adjust;                              // 1.0 / gADJUST: XA is printed rescaled
+    unsigned long long* bad;                        // smallest record whose XA / XP lies outside gm_put_g6_hd's domain (~0: none)
+};
+
 // gm_snp_rec (layout asserted in gm_api.cpp): a row of --snp's .gmp that carries a 'Y' call, written by k_snp_gather (gm_snpcall.hip)
 struct GmDevSnpRec { unsigned long long pos; uint32_t contig, pad0; unsigned long long chr_pos; float total, nuc[5]; double p_val; uint8_t ref, alt1, alt2, diploid;
                      uint8_t pad1[4]; };
@@ -251,6 +267,10 @@ int gmk_out_codes(const GmDevBatch& b, const GmDevParams& p, const GmDevMatch* m
 int gmk_out_deposit(float* cov, uint64_t bins, uint32_t bin_size, const GmDevMatch* matches, const GmDevPos* positions, const uint32_t* pos_match,
                     uint64_t n_p, const uint16_t* ops_len, const float* post, uint32_t max_span, float* nuc, const uint8_t* codes, uint32_t codes_stride,
                     void* stream);
+// SAM rows as text (gm_output_batch_text): tails + row lengths, then - after the scan of the lengths - the rows themselves
+int gmk_out_text_sizes(const GmDevBatch& b, const GmDevText& t, void* stream);
+int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream);
+int gmk_fmt_g6(const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len, void* stream);
 int gmk_coverage_add(float* cov, uint64_t bins, uint32_t bin_size, const uint64_t* pos, const uint32_t* span, const float* w,
                      uint32_t n, uint32_t max_span, float* nuc, const uint8_t* codes, const uint64_t* code_off, void* stream);
 }

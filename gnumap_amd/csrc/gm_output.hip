@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "gm_internal.h"
+#include "gm_fmt_dev.h"
 
 namespace {
 
@@ -641,6 +642,172 @@ __global__ void __launch_bounds__(256) k_out_deposit(float* cov, uint64_t bins, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// SAM rows as text (src/Driver.cpp:2146-2217, ScoredSeq::get_SAM inc/ScoredSeq.h:293-404): what the host driver's format_sam writes,
+// byte for byte.  Row = name \t flag \t contig \t chr_pos \t mapq \t cigar \t*\t0\t0\t seq \t qual \t XA:f:%g \t XP:f:%g \t X0:i:%d \n
+// ------------------------------------------------------------------------------------------------
+#define GO_TAIL_MAX 56u
+#define GO_NAME_MAX 1023u                                  // MAX_NAME_SZ - 1, inc/const_include.h:46
+
+__device__ __forceinline__ uint32_t go_digits64(unsigned long long v) { uint32_t d = 1; while (v >= 10ull) { v /= 10ull; ++d; } return d; }
+__device__ __forceinline__ uint32_t go_int_chars(int32_t v) { return v < 0 ? 1u + go_digits64((unsigned long long)(-(long long)v)) : go_digits64((unsigned long long)v); }
+__device__ __forceinline__ char* go_put_u64(char* w, unsigned long long v) {
+    const uint32_t d = go_digits64(v);
+    for (uint32_t q = d; q > 0; --q) { w[q - 1] = (char)('0' + (uint32_t)(v % 10ull)); v /= 10ull; }
+    return w + d;
+}
+__device__ __forceinline__ char* go_put_int(char* w, int32_t v) {
+    if (v < 0) { *w++ = '-'; return go_put_u64(w, (unsigned long long)(-(long long)v)); }
+    return go_put_u64(w, (unsigned long long)v);
+}
+__device__ __forceinline__ bool go_cigar_digit(char c) { return c >= 48 && c <= 58; }      // ':' counts as a digit, SequenceOperations.h:109-123
+// reverse_comp's table (SequenceOperations.h:56-96): a<->t, c<->g in both cases, '-' stays, everything else 'n'
+__device__ __forceinline__ char go_comp_char(char c) {
+    const char lo = (char)(c | 0x20);
+    const char up = (char)(c == lo ? 0 : 0x20);            // subtracted again for an upper-case letter
+    switch (lo) {
+        case 'a': return (char)('t' - up); case 't': return (char)('a' - up);
+        case 'c': return (char)('g' - up); case 'g': return (char)('c' - up);
+        default: return c == '-' ? '-' : 'n';
+    }
+}
+
+// one lane per record: the numeric tail into the record's slot (through LDS, so that the slots leave as whole 16-byte stores) and
+// the length of the row
+__global__ void __launch_bounds__(256) k_out_text_sizes(GmDevBatch b, GmDevText t) {
+    __shared__ __attribute__((aligned(16))) char s_slot[256][64];
+    const unsigned long long k0 = (unsigned long long)blockIdx.x * 256ull, k = k0 + threadIdx.x;
+    if (k < t.n_recs) {
+        const GmDevSamRec r = t.recs[k];
+        char* const s = s_slot[threadIdx.x];
+        char* w = s;
+        bool ok = true;
+        w[0] = 'X'; w[1] = 'A'; w[2] = ':'; w[3] = 'f'; w[4] = ':'; w += 5;
+        {   // (double)(float)a_score * (1.0 / gADJUST), as format_sam computes it
+            char* e = gm_put_g6_hd(w, (double)r.a_score * t.inv_adjust);
+            ok &= e != w; w = e;
+        }
+        w[0] = '\t'; w[1] = 'X'; w[2] = 'P'; w[3] = ':'; w[4] = 'f'; w[5] = ':'; w += 6;
+        if (r.post_prob == 1.0f) *w++ = '1';
+        else { char* e = gm_put_g6_hd(w, (double)r.post_prob); ok &= e != w; w = e; }
+        w[0] = '\t'; w[1] = 'X'; w[2] = '0'; w[3] = ':'; w[4] = 'i'; w[5] = ':'; w += 6;
+        w = go_put_int(w, r.sim_matches);
+        *w++ = '\n';
+        const uint32_t tail = (uint32_t)(w - s);            // <= 5 + 13 + 6 + 13 + 6 + 11 + 1 = 55
+        if (!ok) atomicMin(t.bad, k);
+        // CIGAR: length in the pool, length in the row
+        const char* cg = t.pool + r.cigar_off;
+        uint32_t gl = 0, last_op = 0;
+        for (char c; gl < 0xFFFFu && (c = cg[gl]) != 0; ++gl) if (!go_cigar_digit(c)) last_op = gl + 1;
+        const uint32_t gout = r.strand ? last_op : gl;
+        s[56] = (char)(gl & 255u); s[57] = (char)(gl >> 8); s[58] = (char)(gout & 255u); s[59] = (char)(gout >> 8); s[60] = (char)tail;
+        const uint32_t rd = r.read;
+        unsigned long long nl = t.name_off[rd + 1] - t.name_off[rd];
+        if (nl > GO_NAME_MAX) nl = GO_NAME_MAX;
+        const uint32_t cl = t.cname_off[r.contig + 1] - t.cname_off[r.contig];
+        const uint32_t L = b.len[rd];
+        const uint32_t QL = L + (t.qtail_off ? (uint32_t)(t.qtail_off[rd + 1] - t.qtail_off[rd]) : 0u);
+        t.row_len[k] = (uint32_t)nl + (r.strand ? 4u : 3u) + cl + 1u + go_digits64(r.chr_pos) + 1u + go_int_chars(r.mapq) + 1u + gout + 7u + L + 1u + QL + 1u + tail;
+    }
+    __syncthreads();
+    // the block's slots are one contiguous stretch of HBM: 16 bytes per lane and step
+    const unsigned long long left = t.n_recs - k0;
+    const uint32_t chunks = (uint32_t)(left < 256ull ? left : 256ull) * 4u;
+    const uint4* src = reinterpret_cast<const uint4*>(&s_slot[0][0]);
+    uint4* dst = reinterpret_cast<uint4*>(t.slots + k0 * 64ull);
+    for (uint32_t q = threadIdx.x; q < chunks; q += 256u) dst[q] = src[q];
+}
+
+// one wavefront per row, four rows per workgroup and step; the grid is one resident round
+__global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t) {
+    __shared__ char s_head[4][64];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    char* const hd = s_head[wv];
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 4ull; base < t.n_recs; base += (unsigned long long)gridDim.x * 4ull) {
+        const unsigned long long k = base + wv;
+        const bool live = k < t.n_recs;
+        GmDevSamRec r = {};
+        if (live) {
+            r = t.recs[k];
+            if (lane == 0) {                                  // the short head: [0, 4) "\t<flag>\t", [4, ..) "\t<chr_pos>\t<mapq>\t", [48, 55) the constant columns
+                char* w = hd;
+                *w++ = '\t';
+                if (r.strand) { *w++ = '1'; *w++ = '6'; } else *w++ = '0';
+                *w++ = '\t';
+                hd[62] = (char)(w - hd);
+                w = hd + 4;
+                *w++ = '\t'; w = go_put_u64(w, r.chr_pos); *w++ = '\t'; w = go_put_int(w, r.mapq); *w++ = '\t';      // <= 1 + 20 + 1 + 11 + 1 = 34
+                hd[63] = (char)(w - (hd + 4));
+                hd[48] = '\t'; hd[49] = '*'; hd[50] = '\t'; hd[51] = '0'; hd[52] = '\t'; hd[53] = '0'; hd[54] = '\t';
+            }
+        }
+        __syncthreads();
+        if (live) {
+            const unsigned long long end = t.row_off[k + 1];
+            unsigned long long o = t.row_off[k];
+            char* const out = t.text;
+            const uint8_t* slot = t.slots + k * 64ull;
+            const uint32_t gl = (uint32_t)slot[56] | ((uint32_t)slot[57] << 8), gout = (uint32_t)slot[58] | ((uint32_t)slot[59] << 8), tail = slot[60];
+            const uint32_t rd = r.read, L = b.len[rd];
+            const unsigned long long n0 = t.name_off[rd];
+            unsigned long long nl64 = t.name_off[rd + 1] - n0;
+            const uint32_t nl = nl64 > GO_NAME_MAX ? GO_NAME_MAX : (uint32_t)nl64;
+            const uint32_t c0 = t.cname_off[r.contig], cl = t.cname_off[r.contig + 1] - c0;
+            const unsigned long long q0 = t.qtail_off ? t.qtail_off[rd] : 0ull;
+            const uint32_t TL = t.qtail_off ? (uint32_t)(t.qtail_off[rd + 1] - q0) : 0u, QL = L + TL;
+            const uint32_t h1 = (uint8_t)hd[62], h2 = (uint8_t)hd[63];
+            const bool neg = r.strand != 0;
+            // every store stays inside the row the scan gave this record, whatever the lengths say
+            for (uint32_t i = lane; i < nl; i += 64u) if (o + i < end) out[o + i] = t.names[n0 + i];
+            o += nl;
+            for (uint32_t i = lane; i < h1; i += 64u) if (o + i < end) out[o + i] = hd[i];
+            o += h1;
+            for (uint32_t i = lane; i < cl; i += 64u) if (o + i < end) out[o + i] = t.cnames[c0 + i];
+            o += cl;
+            for (uint32_t i = lane; i < h2; i += 64u) if (o + i < end) out[o + i] = hd[4 + i];
+            o += h2;
+            const char* cg = t.pool + r.cigar_off;
+            if (!neg) { for (uint32_t i = lane; i < gl; i += 64u) if (o + i < end) out[o + i] = cg[i]; }
+            else {
+                // reverse_cigar: the tokens (digits + operation) in reverse order; byte i of token [ts, te] goes behind the tokens that
+                // follow it: (gout - (te + 1)) + (i - ts).  Digits after the last operation belong to no token and are dropped.
+                for (uint32_t i = lane; i < gout; i += 64u) {
+                    uint32_t te = i; while (te + 1u < gout && go_cigar_digit(cg[te])) ++te;
+                    uint32_t ts = i; while (ts > 0 && go_cigar_digit(cg[ts - 1u])) --ts;
+                    const uint32_t d = (gout - (te + 1u)) + (i - ts);
+                    if (o + d < end) out[o + d] = cg[i];
+                }
+            }
+            o += gout;
+            for (uint32_t i = lane; i < 7u; i += 64u) if (o + i < end) out[o + i] = hd[48 + i];
+            o += 7u;
+            const uint8_t* bs = b.bases + (size_t)rd * b.stride; const uint8_t* qs = b.quals + (size_t)rd * b.stride;
+            if (!neg) { for (uint32_t i = lane; i < L; i += 64u) if (o + i < end) out[o + i] = (char)bs[i]; }
+            else { for (uint32_t i = lane; i < L; i += 64u) if (o + i < end) out[o + i] = go_comp_char((char)bs[L - 1u - i]); }
+            o += L;
+            if (lane == 0 && o < end) out[o] = '\t';
+            o += 1u;
+            for (uint32_t i = lane; i < QL; i += 64u) {
+                const uint32_t si = neg ? QL - 1u - i : i;          // the whole quality line is reversed, its tail included
+                const char c = si < L ? (char)qs[si] : t.qtail[q0 + (si - L)];
+                if (o + i < end) out[o + i] = c;
+            }
+            o += QL;
+            if (lane == 0 && o < end) out[o] = '\t';
+            o += 1u;
+            for (uint32_t i = lane; i < tail; i += 64u) if (o + i < end) out[o + i] = (char)slot[i];
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) k_fmt_g6(const double* v, uint32_t n, char* out, uint8_t* len) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    char* w = out + (size_t)i * 16;
+    len[i] = (uint8_t)(gm_put_g6_hd(w, v[i]) - w);
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -703,5 +870,28 @@ int gmk_out_deposit(float* cov, uint64_t bins, uint32_t bin_size, const GmDevMat
     const uint64_t total = n_p * bins_per_place;
     hipLaunchKernelGGL(k_out_deposit, dim3(cdiv(total, 256)), dim3(256), 0, S_(stream), cov, bins, bin_size, matches, positions, pos_match, n_p, ops_len,
                        post, bins_per_place, nuc, codes, codes_stride);
+    return (int)hipGetLastError();
+}
+
+int gmk_out_text_sizes(const GmDevBatch& b, const GmDevText& t, void* stream) {
+    if (t.n_recs == 0) return 0;
+    hipLaunchKernelGGL(k_out_text_sizes, dim3(cdiv(t.n_recs, 256)), dim3(256), 0, S_(stream), b, t);
+    return (int)hipGetLastError();
+}
+
+int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream) {
+    if (t.n_recs == 0) return 0;
+    // one resident round: as many workgroups of 4 waves as the device holds at once
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_out_text_rows, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((t.n_recs + 3) / 4, (uint64_t)cus * (uint64_t)per_cu);
+    hipLaunchKernelGGL(k_out_text_rows, dim3(grid), dim3(256), 0, S_(stream), b, t);
+    return (int)hipGetLastError();
+}
+
+int gmk_fmt_g6(const double* v, uint32_t n, char* out, uint8_t* len, void* stream) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_fmt_g6, dim3(cdiv(n, 256)), dim3(256), 0, S_(stream), v, n, out, len);
     return (int)hipGetLastError();
 }

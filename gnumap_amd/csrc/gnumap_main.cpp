@@ -6,6 +6,9 @@
 // I/O at rate: the FASTQ file is memory-mapped and cut into blocks by one scanner thread (memchr only, no
 // copies); per GPU `--workers` host threads (default 3, each with its own gm_batch and HIP stream) pack a block, run the
 // two batch calls and hand the records to formatter threads; SAM text is written in block order by one writer thread.
+// --sam_text=device: the library formats the rows on the GPU (gm_output_batch_text) and the formatter stage is skipped.
+// --sam_shards=K: the rows go to K files by input position, each with its own descriptor and writer; their concatenation in
+// order is the single-file SAM.
 // The number of blocks in flight is bounded by a fixed pool of Block objects.
 // Multi-GPU (--gpus N): one index replica per GPU, blocks dealt to whichever worker is free, coverage tracks combined
 // with one RCCL all-reduce (gm_coverage_allreduce).
@@ -48,6 +51,8 @@ struct Options {
     int threads = 1;            // -c: accepted for compatibility (the GPU replaces the pthread pool)
     float snp_pval = 0.001f;    // --snp_pval: gSNP_PVAL inc/const_define.h:33
     bool snp_monop = false, snp_calls = false;      // --snp_monop: gSNP_MONOP; --snp_calls: <out>.gmp with PrintSNPCall's ninth column
+    bool sam_text_device = false;   // --sam_text=device: SAM rows formatted on the GPU (gm_output_batch_text); host = format_sam below
+    int sam_shards = 1;             // --sam_shards=K: <out>.0.sam .. <out>.<K-1>.sam by input position instead of one <out>.sam
 };
 
 static void usage(int rc, const char* msg) {
@@ -76,7 +81,12 @@ static void usage(int rc, const char* msg) {
             "      --snp_monop              monoploid SNP calling; changes the ninth column only\n"
             "      --no_nw                  use k-mer hit counts instead of Needleman-Wunsch alignments\n"
             "      --fast, --print_all_sam, --illumina, --up_strand, --down_strand, --bin_size=INT\n"
-            "  MI355X options: --gpus=N  --batch=N (blocks of exactly N reads)  --chunk_reads=N  --workers=N  --fmt_threads=N  --locate=sampled|full\n");
+            "  MI355X options: --gpus=N  --batch=N (blocks of exactly N reads)  --chunk_reads=N  --workers=N  --fmt_threads=N  --locate=sampled|full\n"
+            "      --sam_text=host|device   where the SAM rows become text: host formatter threads (default) or the GPU\n"
+            "                               (gm_output_batch_text; same bytes, no formatter stage)\n"
+            "      --sam_shards=K           1 .. 64 (default 1 = <out>.sam): write <out>.0.sam .. <out>.<K-1>.sam, a block going to the\n"
+            "                               shard of its position in the input, header lines in shard 0 only;\n"
+            "                               cat <out>.0.sam .. <out>.<K-1>.sam is the single-file SAM\n");
     exit(rc);
 }
 
@@ -129,6 +139,17 @@ static void parse_args(int argc, char** argv, Options& o) {
             else if (starts(s, "workers=")) o.workers = atoi(s + 8);
             else if (starts(s, "fmt_threads=")) o.fmt_threads = atoi(s + 12);
             else if (starts(s, "locate=")) o.locate_sampled = !strcmp(s + 7, "sampled");
+            else if (starts(s, "sam_text=")) {
+                if (!strcmp(s + 9, "device")) o.sam_text_device = true;
+                else if (!strcmp(s + 9, "host")) o.sam_text_device = false;
+                else { fprintf(stderr, "Error: --sam_text takes host or device, not: %s\n", s + 9); exit(1); }
+            }
+            else if (starts(s, "sam_shards=")) {
+                char* end = nullptr;
+                const long k = strtol(s + 11, &end, 10);
+                if (end == s + 11 || *end || k < 1 || k > 64) { fprintf(stderr, "Error: --sam_shards takes 1 .. 64, not: %s\n", s + 11); exit(1); }
+                o.sam_shards = (int)k;
+            }
             else if (!strcmp(s, "help")) usage(0, "");
             else { fprintf(stderr, "No matching arg in: %s\n", a); exit(1); }
             continue;
@@ -215,6 +236,18 @@ struct TextBuf {
     }
 };
 
+// --sam_text=device: the page-locked buffers gm_output_batch_text writes a block's rows into.  A worker takes one when its block reaches
+// the output call, the writer gives it back once the rows are in the file: a handful are in use at a time, far fewer than there are
+// Block objects (page-locking 80 MB costs tens of milliseconds, and a short run pays that for every buffer it ever touches).
+struct TextPool {
+    std::mutex mu; std::vector<std::unique_ptr<PinVec<char>>> idle;
+    PinVec<char>* get() {
+        { std::lock_guard<std::mutex> lk(mu); if (!idle.empty()) { PinVec<char>* p = idle.back().release(); idle.pop_back(); return p; } }
+        return new PinVec<char>();
+    }
+    void put(PinVec<char>* p) { if (p) { std::lock_guard<std::mutex> lk(mu); idle.emplace_back(p); } }
+};
+
 // ---- blocks ------------------------------------------------------------------------------------------------------
 struct Block {
     uint64_t index = 0;
@@ -232,6 +265,10 @@ struct Block {
     bool malformed = false;                 // chunk mode: a malformed record ended this block; the rest of the input is read again in file order with the reference's recovery
     int illumina = 0;                       // --illumina still in force when this block starts (the fallback is sticky, SeqReader.cpp:1171-1180)
     std::vector<TextBuf> text;              // SAM text, one piece per formatter thread
+    // --sam_text=device: what gm_output_batch_text reads of the block besides bases and qualities, and the text it returns (page-locked)
+    PinVec<char> names_pool, qtail_pool; PinVec<uint64_t> name_off, qtail_off; bool has_qtail = false;
+    PinVec<char>* dtext = nullptr; uint64_t dtext_len = 0;      // from the TextPool, while the block holds rows that are not written yet
+    size_t first_byte = 0;                  // where the block starts in the FASTQ text: decides its shard (--sam_shards)
     bool failed = false;
 };
 
@@ -414,10 +451,29 @@ template <class F> static void run_slices(uint32_t n, int threads, uint32_t grai
     for (auto& x : th) x.join();
 }
 
-static void pack_block(Block& b, int threads) {          // rows of `stride` bytes, zero padded, as gm_reads wants them
+// with_text: also the names (cut to what a row prints of them) and the rare quality tails, back to back, for gm_read_text
+static void pack_block(Block& b, int threads, bool with_text) {          // rows of `stride` bytes, zero padded, as gm_reads wants them
     const size_t bytes = (size_t)b.n * b.stride;
     b.bases.ensure(bytes); b.qbuf.ensure(bytes); b.plen.ensure(b.n);
     memcpy(b.plen.data(), b.len.data(), (size_t)b.n * 2);
+    if (with_text) {
+        b.name_off.ensure((size_t)b.n + 1); b.qtail_off.ensure((size_t)b.n + 1);
+        uint64_t no = 0, qo = 0;
+        for (uint32_t i = 0; i < b.n; ++i) {
+            b.name_off[i] = no; b.qtail_off[i] = qo;
+            no += std::min<uint32_t>(b.name_len[i], MAX_NAME_SZ - 1);
+            qo += b.qual_len[i] > b.len[i] ? b.qual_len[i] - b.len[i] : 0u;
+        }
+        b.name_off[b.n] = no; b.qtail_off[b.n] = qo;
+        b.has_qtail = qo != 0;
+        b.names_pool.ensure((size_t)no + 1); b.qtail_pool.ensure((size_t)qo + 1);
+        run_slices(b.n, threads, 8192, [&](int, uint32_t lo, uint32_t hi) {
+            for (uint32_t i = lo; i < hi; ++i) {
+                memcpy(&b.names_pool[(size_t)b.name_off[i]], b.name[i], (size_t)(b.name_off[i + 1] - b.name_off[i]));
+                if (b.qtail_off[i + 1] > b.qtail_off[i]) memcpy(&b.qtail_pool[(size_t)b.qtail_off[i]], b.qual[i] + b.len[i], (size_t)(b.qtail_off[i + 1] - b.qtail_off[i]));
+            }
+        });
+    }
     run_slices(b.n, threads, 8192, [&](int, uint32_t lo, uint32_t hi) {
         for (uint32_t i = lo; i < hi; ++i) {
             uint8_t* pb = &b.bases[(size_t)i * b.stride]; uint8_t* pq = &b.qbuf[(size_t)i * b.stride];
@@ -509,6 +565,7 @@ struct Worker {
     gm_index* ix = nullptr;
     gm_batch* batch = nullptr;
     void* stream = nullptr;                 // this worker's own HIP stream: its device work overlaps the other workers'
+    TextPool* text_pool = nullptr;
     PinVec<int8_t> status; PinVec<float> self_score; PinVec<double> top, den; PinVec<uint64_t> mbegin;
     PinVec<gm_match> matches; PinVec<gm_pos> positions;
     uint64_t n_reads = 0, n_matched = 0, n_records = 0;
@@ -521,7 +578,7 @@ static int process_block(Worker& w, const Options& o, Block& b) {
     const uint32_t n = b.n;
     gm_params bp = o.p; bp.illumina = b.illumina;
     auto c0 = std::chrono::steady_clock::now();
-    pack_block(b, 4);
+    pack_block(b, 4, o.sam_text_device);
     gm_reads reads; reads.n = n; reads.stride = b.stride; reads.bases = b.bases.data(); reads.quals = b.qbuf.data(); reads.len = b.plen.data();
     w.status.ensure(n); w.self_score.ensure(n); w.top.ensure(n); w.den.ensure(n); w.mbegin.ensure((size_t)n + 1);
     w.matches.ensure(2 * (size_t)n + 64); w.positions.ensure(2 * (size_t)n + 64);
@@ -539,6 +596,26 @@ static int process_block(Worker& w, const Options& o, Block& b) {
         break;
     }
     auto c2 = std::chrono::steady_clock::now();
+    if (o.sam_text_device) {                                // the rows come back as text: no records, no CIGAR pool on the host
+        gm_read_text rt; rt.names = b.names_pool.data(); rt.name_off = b.name_off.data();
+        rt.qual_tail = b.has_qtail ? b.qtail_pool.data() : nullptr; rt.qual_tail_off = b.has_qtail ? b.qtail_off.data() : nullptr;
+        if (!b.dtext) b.dtext = w.text_pool->get();
+        b.dtext->ensure(((size_t)n + (size_t)n / 16) * (2 * (size_t)b.maxlen + 64) + (size_t)b.name_off[n] + 4096);
+        gm_sam_text st;
+        for (;;) {
+            st.text = b.dtext->data(); st.text_cap = b.dtext->size(); st.text_len = 0; st.n_recs = 0; st.row_off = nullptr; st.row_cap = 0;
+            int rc = gm_output_batch_text(w.ix, &bp, w.batch, &reads, &rt, &hits, &st, w.stream);
+            if (rc == GM_E_CAPACITY) { b.dtext->ensure((size_t)st.text_cap + 64); continue; }
+            if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
+            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch_text: %s\n", gm_last_error()); return rc; }
+            break;
+        }
+        b.n_recs = st.n_recs; b.dtext_len = st.text_len; b.gpu = w.gpu;
+        w.t_pack += std::chrono::duration<double>(c1 - c0).count(); w.t_map += std::chrono::duration<double>(c2 - c1).count(); w.t_out += secs_since(c2);
+        w.n_reads += n; w.n_records += st.n_recs;
+        for (uint32_t i = 0; i < n; ++i) w.n_matched += (w.status[i] == GM_READ_OK || w.status[i] == GM_READ_TOO_MANY);
+        return GM_OK;
+    }
     b.recs.ensure((size_t)n + (size_t)n / 4 + 64);
     b.pool.ensure(8 * (size_t)n + 1024);
     gm_sam_out so;
@@ -564,7 +641,7 @@ static int process_block_split(Worker& w, const Options& o, Block& b, int depth)
     if (rc != GM_E_BATCH_TOO_LARGE || b.n < 2 || depth > 20) return rc;
     const uint32_t half = b.n / 2;
     uint64_t total = 0; size_t pool_len = 0;
-    std::vector<gm_sam_rec> recs; std::vector<char> pool;
+    std::vector<gm_sam_rec> recs; std::vector<char> pool, text;
     for (int part = 0; part < 2; ++part) {
         const uint32_t lo = part ? half : 0, hi = part ? b.n : half;
         Block c;
@@ -577,12 +654,24 @@ static int process_block_split(Worker& w, const Options& o, Block& b, int depth)
                 for (uint32_t t = 0; t < b.len[i]; ++t) if ((signed char)b.qual[i][t] < 64) { c.illumina = 0; break; }      // (the reference's quality characters are signed chars)
         }
         rc = process_block_split(w, o, c, depth + 1);
-        if (rc != GM_OK) return rc;
+        if (rc != GM_OK) { w.text_pool->put(c.dtext); return rc; }
+        if (o.sam_text_device) {                            // rows are text already: the halves' text, one behind the other
+            if (c.dtext) { text.insert(text.end(), c.dtext->data(), c.dtext->data() + c.dtext_len); w.text_pool->put(c.dtext); c.dtext = nullptr; }
+            total += c.n_recs;
+            continue;
+        }
         for (uint64_t k = 0; k < c.n_recs; ++k) { gm_sam_rec r = c.recs[k]; r.read += lo; r.cigar_off += (uint32_t)pool_len; recs.push_back(r); }
         size_t used = 0;
         for (uint64_t k = 0; k < c.n_recs; ++k) used = std::max<size_t>(used, c.recs[k].cigar_off + strlen(c.pool.data() + c.recs[k].cigar_off) + 1);
         pool.insert(pool.end(), c.pool.data(), c.pool.data() + used);
         pool_len += used; total += c.n_recs;
+    }
+    if (o.sam_text_device) {
+        if (!b.dtext) b.dtext = w.text_pool->get();
+        b.dtext->ensure(text.size() + 1);
+        if (!text.empty()) memcpy(b.dtext->data(), text.data(), text.size());
+        b.dtext_len = text.size(); b.n_recs = total; b.gpu = w.gpu;
+        return GM_OK;
     }
     b.recs.ensure(recs.size() + 1); b.pool.ensure(pool.size() + 1);
     if (!recs.empty()) memcpy(b.recs.data(), recs.data(), recs.size() * sizeof(gm_sam_rec));
@@ -607,12 +696,13 @@ int main(int argc, char** argv) {
     for (int g = 0; g < o.gpus; ++g)                                   // k-mer tables / records for these parameters: part of staging the index
         if (gm_index_prepare(gpu_ix[(size_t)g], &o.p) != GM_OK) { fprintf(stderr, "ERROR: GPU %d: %s\n", g, gm_last_error()); return 1; }
     std::vector<Worker> workers((size_t)o.gpus * (size_t)o.workers);
+    TextPool text_pool;
     for (int g = 0; g < o.gpus; ++g) {
         if (gm_coverage_reset(gpu_ix[(size_t)g], (uint32_t)o.p.bin_size) != GM_OK ||
             (o.p.mode != GM_MODE_NORMAL && gm_coverage_enable_nuc(gpu_ix[(size_t)g]) != GM_OK)) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
         for (int k = 0; k < o.workers; ++k) {
             Worker& w = workers[(size_t)g * (size_t)o.workers + (size_t)k];
-            w.gpu = g; w.ix = gpu_ix[(size_t)g];
+            w.gpu = g; w.ix = gpu_ix[(size_t)g]; w.text_pool = &text_pool;
             if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
         }
     }
@@ -622,8 +712,16 @@ int main(int argc, char** argv) {
     if (o.verbose > 0)
         fprintf(stderr, "gnumap-mi355x: genome %s (%lu bp, %u contigs), %s locate, %d GPU(s), index %.1f MB in HBM\n", o.genome.c_str(),
                 (unsigned long)info.l_pac, info.n_seqs, info.full_sa ? "full-SA" : "sampled-SA", o.gpus, info.hbm_bytes / 1e6);
-    const int ofd = ::open((o.output + ".sam").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (ofd < 0) { fprintf(stderr, "ERROR: cannot write %s.sam\n", o.output.c_str()); return 1; }
+    // one <out>.sam, or --sam_shards=K files <out>.<k>.sam: every shard has its own descriptor and offset counter (no two share an inode)
+    const int K = o.sam_shards;
+    std::vector<int> ofds((size_t)K, -1);
+    std::vector<uint64_t> file_offs((size_t)K, 0);
+    for (int k = 0; k < K; ++k) {
+        const std::string fn = K == 1 ? o.output + ".sam" : o.output + "." + std::to_string(k) + ".sam";
+        ofds[(size_t)k] = ::open(fn.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (ofds[(size_t)k] < 0) { fprintf(stderr, "ERROR: cannot write %s\n", fn.c_str()); return 1; }
+    }
+    const int ofd = ofds[0];                                             // the header lines go to the first (or only) file
     auto write_all = [&](const char* p, size_t n) {
         while (n) { ssize_t k = ::write(ofd, p, n); if (k <= 0) return false; p += k; n -= (size_t)k; }
         return true;
@@ -643,12 +741,12 @@ int main(int argc, char** argv) {
     if (!fq.open(o.reads)) { fprintf(stderr, "ERROR: cannot open %s\n", o.reads.c_str()); return 1; }
     std::atomic<int> failed{ 0 };
     double t_scan = 0, t_fmt = 0, t_write = 0;
-    uint64_t file_off = 0;
-    { struct stat hs; if (fstat(ofd, &hs) == 0) file_off = (uint64_t)lseek(ofd, 0, SEEK_CUR); }
-    auto pwrite_all = [&](const char* p, size_t n, uint64_t off) {
-        while (n) { ssize_t k = ::pwrite(ofd, p, n, (off_t)off); if (k <= 0) return false; p += k; n -= (size_t)k; off += (uint64_t)k; }
+    { struct stat hs; if (fstat(ofd, &hs) == 0) file_offs[0] = (uint64_t)lseek(ofd, 0, SEEK_CUR); }
+    auto pwrite_all = [&](int fd, const char* p, size_t n, uint64_t off) {
+        while (n) { ssize_t k = ::pwrite(fd, p, n, (off_t)off); if (k <= 0) return false; p += k; n -= (size_t)k; off += (uint64_t)k; }
         return true;
     };
+    std::mutex tw_mu;                                                    // t_write is summed by several writers with --sam_shards
     // (Tried in round 4: the pieces copied in through shared mappings of the file's byte ranges instead - no inode write lock, which is
     // what holds buffered pwrite()s to ONE file to the rate of one thread, 8.4-8.8 GB/s whatever the number of writers.  4 x SLOWER on the
     // GPU box's file system: 2.1 M first-touch page faults of a growing file cost more than the copies.  The write calls stay.)
@@ -676,6 +774,7 @@ int main(int argc, char** argv) {
                 auto s0 = std::chrono::steady_clock::now();
                 b->lazy = false; b->malformed = false;
                 bool too_long = false;
+                b->first_byte = fq.at;
                 const bool more = chunks ? fq.next_chunk(*b, o.batch) : fq.next(*b, o.batch, &too_long);
                 t_scan += secs_since(s0);
                 if (too_long) failed = 1;
@@ -737,6 +836,7 @@ int main(int argc, char** argv) {
                     const int T = o.fmt_threads;
                     if ((int)b->text.size() < T) b->text.resize((size_t)T);
                     for (auto& s : b->text) s.clear();
+                    if (!o.sam_text_device)                  // (device: the block's text is there already, b->dtext)
                     run_slices(nr, T, 4096, [&](int s, uint32_t lo, uint32_t hi) {
                         TextBuf& out = b->text[(size_t)s];
                         out.room((size_t)(hi - lo) * 320);
@@ -748,8 +848,35 @@ int main(int argc, char** argv) {
                 }
                 if (--live_fmt == 0) { { std::lock_guard<std::mutex> lk(wr_mu); fmt_done = true; } wr_cv.notify_all(); }
             });
-        // the writer only hands out file offsets in block order; the text pieces of a block (one per formatter slice) are written by
-        // pwrite() from a few threads at once (a single write() stream tops out at ~8 GB/s of page-cache copies)
+        // the writer only hands out file offsets in block order; the text pieces of a block (one per formatter slice, or cuts of the
+        // device's text) are written by pwrite() from a few threads at once (a single write() stream tops out at ~8 GB/s of page-cache
+        // copies).  --sam_shards=K: a block belongs to the shard of its first byte in the input, which only grows with the block index,
+        // so blocks keep their order inside a shard; the writer then only assigns (shard, offsets) and the shard's own writer thread does
+        // the writing, side by side with the other shards'.
+        struct Piece { const char* p; size_t n; uint64_t off; };
+        struct WriteJob { Block* b; int shard; std::vector<Piece> pieces; };
+        auto write_job = [&](WriteJob& j) {
+            auto w0 = std::chrono::steady_clock::now();
+            const int fd = ofds[(size_t)j.shard];
+            const int nt = (int)std::min<size_t>(8, j.pieces.size());
+            std::atomic<size_t> nextp{ 0 }; std::atomic<int> bad{ 0 };
+            auto job = [&] { for (size_t k; (k = nextp++) < j.pieces.size();) if (j.pieces[k].n && !pwrite_all(fd, j.pieces[k].p, j.pieces[k].n, j.pieces[k].off)) bad = 1; };
+            std::vector<std::thread> ws;
+            for (int t = 1; t < nt; ++t) ws.emplace_back(job);
+            job();
+            for (auto& x : ws) x.join();
+            if (bad) { fprintf(stderr, "ERROR: write failed\n"); failed = 1; }
+            { std::lock_guard<std::mutex> lk(tw_mu); t_write += secs_since(w0); }
+        };
+        auto release = [&](Block* b) { text_pool.put(b->dtext); b->dtext = nullptr; free_q.push(b); };       // the rows are written (or there are none)
+        std::vector<std::unique_ptr<Queue<WriteJob*>>> shard_q;
+        std::vector<std::thread> shard_th;
+        if (K > 1)
+            for (int k = 0; k < K; ++k) {
+                shard_q.emplace_back(new Queue<WriteJob*>());
+                Queue<WriteJob*>* q = shard_q.back().get();
+                shard_th.emplace_back([&, q] { WriteJob* j; while (q->pop(j)) { write_job(*j); release(j->b); delete j; } });
+            }
         std::thread writer([&] {
             uint64_t next = 0;
             for (;;) {
@@ -760,23 +887,22 @@ int main(int argc, char** argv) {
                     if (ready.empty() || ready.begin()->first != next) break;
                     b = ready.begin()->second; ready.erase(ready.begin());
                 }
-                auto w0 = std::chrono::steady_clock::now();
-                if (!b->failed && b->n_recs) {
-                    std::vector<uint64_t> offs(b->text.size());
-                    for (size_t k = 0; k < b->text.size(); ++k) { offs[k] = file_off; file_off += b->text[k].size(); }
-                    const int nt = (int)std::min<size_t>(8, b->text.size());
-                    std::atomic<size_t> nextp{ 0 }; std::atomic<int> bad{ 0 };
-                    auto job = [&] { for (size_t k; (k = nextp++) < b->text.size();) if (!b->text[k].empty() && !pwrite_all(b->text[k].data(), b->text[k].size(), offs[k])) bad = 1; };
-                    std::vector<std::thread> ws;
-                    for (int t = 1; t < nt; ++t) ws.emplace_back(job);
-                    job();
-                    for (auto& x : ws) x.join();
-                    if (bad) { fprintf(stderr, "ERROR: write failed\n"); failed = 1; }
-                }
-                t_write += secs_since(w0);
                 ++next;
-                free_q.push(b);
+                if (b->failed || !b->n_recs) { release(b); continue; }
+                WriteJob* j = new WriteJob();
+                j->b = b;
+                j->shard = K == 1 || fq.size == 0 ? 0 : (int)std::min<unsigned __int128>((unsigned __int128)(K - 1), (unsigned __int128)b->first_byte * (unsigned)K / fq.size);
+                uint64_t& off = file_offs[(size_t)j->shard];
+                if (o.sam_text_device) {
+                    const size_t cut = std::max<size_t>((size_t)1 << 22, ((size_t)b->dtext_len + 7) / 8);
+                    for (size_t at = 0; at < b->dtext_len; at += cut) { const size_t n = std::min<size_t>(cut, (size_t)b->dtext_len - at); j->pieces.push_back({ b->dtext->data() + at, n, off }); off += n; }
+                } else
+                    for (size_t k = 0; k < b->text.size(); ++k) { j->pieces.push_back({ b->text[k].data(), b->text[k].size(), off }); off += b->text[k].size(); }
+                if (K == 1) { write_job(*j); delete j; release(b); }
+                else shard_q[(size_t)j->shard]->push(j);
             }
+            for (auto& q : shard_q) q->close();
+            for (auto& x : shard_th) x.join();
             free_q.close();
         });
         scanner.join();
@@ -791,7 +917,7 @@ int main(int argc, char** argv) {
         fq.at = bad_at; fq.done = false;
         run_pass(false);
     }
-    ::close(ofd);
+    for (int fd : ofds) ::close(fd);
     if (failed) return 1;
     const double t_pipe = secs_since(t_pipe0);
     auto t_cov0 = std::chrono::steady_clock::now();
@@ -824,6 +950,10 @@ int main(int argc, char** argv) {
     for (auto ix : gpu_ix) gm_index_close(ix);
     double secs = secs_since(t0);
     if (o.verbose > 0) {
+        if (o.sam_text_device)                               // no formatter stage: the rows were text when they left the library
+            fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, pack %.2f, gm_map_batch %.2f, gm_output_batch_text %.2f, write %.2f\n",
+                    t_index, t_scan, t_pack, t_map, t_out, t_write);
+        else
         fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, pack %.2f, gm_map_batch %.2f, gm_output_batch %.2f, SAM format %.2f, write %.2f\n",
                 t_index, t_scan, t_pack, t_map, t_out, t_fmt, t_write);
         fprintf(stderr, "wall seconds: index %.2f, FASTQ->SAM pipeline %.2f (%.3f M reads/s), coverage all-reduce + track file %.2f\n", t_index, t_pipe,

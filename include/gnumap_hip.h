@@ -19,6 +19,9 @@
  *                                    src/NormalScoredSeq.cpp:24-76, ScoredSeq::get_SAM inc/ScoredSeq.h:293-404,
  *                                    bin_seq::get_align_score_w_traceback inc/bin_seq.h:175, GenomeBwt::AddScore
  *                                    src/GenomeBwt.cpp:483-490
+ *   gm_output_batch_text             the same block loop, ending in the SAM rows as text: the print loop of
+ *                                    parallel_thread_run src/Driver.cpp:2146-2217, ScoredSeq::get_SAM inc/ScoredSeq.h:293-404,
+ *                                    reverse_comp / reverse_CIGAR inc/SequenceOperations.h:56-123
  *   gm_coverage_*                    amount_genome, PrintFinalSGR src/GenomeBwt.cpp:1212-1273; the MPI
  *                                    Allreduce of the track src/Driver.cpp:1660-1672 (-> RCCL)
  *
@@ -155,6 +158,22 @@ typedef struct {
     char* cigar_pool;  uint64_t cigar_cap, cigar_len;    /* caller-owned */
 } gm_sam_out;
 
+/* what a SAM row prints of a read besides its bases and qualities */
+typedef struct {
+    const char* names;              /* the names back to back, no terminators: exactly the bytes after '@' */
+    const uint64_t* name_off;       /* n+1 offsets into names */
+    const char* qual_tail;          /* NULL, or: bytes the row prints after the len[i] quality characters of read i (a quality
+                                       line longer than its sequence line, SeqReader.cpp:1091) */
+    const uint64_t* qual_tail_off;  /* n+1, NULL with qual_tail */
+} gm_read_text;
+
+/* finished SAM rows, one '\n'-terminated line per record, in gm_output_batch's record order */
+typedef struct {
+    char* text;  uint64_t text_cap, text_len;   /* caller-owned (page-locked for link rate) */
+    uint64_t n_recs;
+    uint64_t* row_off;  uint64_t row_cap;       /* optional (NULL / 0): n_recs+1 row offsets */
+} gm_sam_text;
+
 /* kernel-side work counters of the last gm_map_batch on a batch (algorithmic-bytes accounting) */
 typedef struct {
     uint64_t reads, kmers_searched, occ_calls, occ_blocks, seeds_used, sa_hits, lf_steps, candidates, nw_cells, accepted, vote_retries,
@@ -239,6 +258,16 @@ void gm_host_free(void*);
 int gm_map_batch(gm_index*, const gm_params*, gm_batch*, const gm_reads*, gm_hits* out, void* hip_stream);
 int gm_output_batch(gm_index*, const gm_params*, gm_batch*, const gm_reads*, const gm_hits*, gm_sam_out* out, void* hip_stream);
 
+/* gm_output_batch with a different ending: same host fp64 pass, same traceback, same coverage / per-nucleotide / SNP deposit - call
+ * one or the other for a block, never both - then the rows are formatted on the device (name cut to 1023 bytes, flag 0 / 16, contig,
+ * position, MAPQ, CIGAR - reversed token by token on the minus strand -, reverse-complemented sequence, reversed qualities, exact
+ * "%g" of XA / XP, X0) and come back as ONE buffer a host can fwrite: byte for byte what the reference program prints for these
+ * records.  GM_E_CAPACITY: text_cap (and row_cap) hold the required sizes and NOTHING has been deposited yet - repeat the call.
+ * GM_E_ARG: gm_read_text NULL or its offsets do not ascend.  GM_E_UNSUPPORTED: an XA / XP outside 2^-200 <= |v| < 2^200 (not reachable
+ * with finite fp32 scores and the reference's adjust values); gm_last_error() names the record.  There is no enqueue form. */
+int gm_output_batch_text(gm_index*, const gm_params*, gm_batch*, const gm_reads*, const gm_read_text*, const gm_hits*, gm_sam_text* out,
+                         void* hip_stream);
+
 /* enqueue / wait forms: the call is queued on the batch's own service thread and runs there exactly as the synchronous form would;
  * the caller goes on (with another batch).  Calls queued on one batch run in order - gm_output_batch_enqueue may be queued right
  * behind the gm_map_batch_enqueue whose gm_hits it reads - and after a failing call the rest of the batch's queue is skipped.
@@ -257,6 +286,10 @@ int gm_dev_nw_score(gm_index*, const gm_params*, const gm_reads*, const uint32_t
 int gm_dev_traceback(gm_index*, const gm_params*, const gm_reads*, const uint32_t* read_idx, const uint8_t* strand,
                      const uint64_t* pos, uint32_t n, char* ops /* n x ops_stride, 'M','I','D', NUL padded */,
                      uint32_t ops_stride, uint16_t* ops_len);
+
+/* printf("%g") as the device prints XA / XP (gm_fmt_dev.h): out[16 i ..] holds len[i] characters, no terminator; len[i] = 0 for a
+ * value outside the function's domain (0, -0, inf, nan, 2^-200 <= |v| < 2^200) */
+int gm_dev_fmt_g6(gm_index*, const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len);
 
 /* bin_seq::pairHMM (src/bin_seq.cpp:60-244) of read read_idx[k] in the orientation of strand[k] against the window at pos[k]:
  * out[k][max_len][5] floats (a, c, g, t, n per window position), max_len = gm_reads.stride */

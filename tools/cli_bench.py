@@ -4,7 +4,7 @@ reference; the numbers quoted in DESIGN.md for SURVEY §8 row (f2).  Usage:
     python tools/cli_bench.py [--mbp 100] [--reads 2000000] [--args "-a 0.9"] [--dir /tmp/gm_cli]
 Writes the FASTA / FASTQ with numpy (substitution-only reads, 50 % reverse strand), builds the index through the binary on
 its first run, then times a second run (index already on disk)."""
-import argparse, os, subprocess, sys, time
+import argparse, glob, os, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -55,16 +55,21 @@ def main():
     out = os.path.join(a.dir, "out")
     env = dict(os.environ)
     runs = [("index+map", a.args), ("map", a.args)] + [("map " + x.strip(), a.args + " " + x.strip()) for x in a.sweep.split(";") if x.strip()]
+    def shard_files():                                           # <out>.<k>.sam of a --sam_shards=K run
+        return [f for f in glob.glob(glob.escape(out) + ".*.sam") if f[len(out) + 1:-4].isdigit()]
+
+    sam_bytes = 0
     for run, args in runs:
-        for ext in (".sam", ".sgr", ".gmp"):                     # a fresh output file each time (overwriting 8 GB of page cache is a different test)
-            if os.path.exists(out + ext):
-                os.remove(out + ext)
+        for f in [out + ext for ext in (".sam", ".sgr", ".gmp")] + shard_files():     # fresh output files each time (overwriting 8 GB of page cache is a different test)
+            if os.path.exists(f):
+                os.remove(f)
         t0 = time.time()
         r = subprocess.run([exe, "-g", fa, "-o", out, "-v", "1"] + args.split() + [fq], capture_output=True, text=True, env=env)
         dt = time.time() - t0
         print(f"--- {run}: {dt:.2f} s wall, {n / dt / 1e6:.3f} M reads/s end to end (rc {r.returncode})")
         print("\n".join(l for l in r.stderr[-3000:].splitlines() if not l.startswith("[gm_")))
-    print("SAM bytes", os.path.getsize(out + ".sam"), "FASTQ bytes", os.path.getsize(fq))
+        sam_bytes = sum(os.path.getsize(f) for f in ([out + ".sam"] if os.path.exists(out + ".sam") else []) + shard_files())
+    print("SAM bytes", sam_bytes, "FASTQ bytes", os.path.getsize(fq))
 
 
 if __name__ == "__main__":
