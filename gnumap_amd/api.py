@@ -95,7 +95,8 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_output_batch_text", "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait", "gm_dev_fmt_g6",
            "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
            "gm_coverage_device_ptr", "gm_coverage_add", "gm_coverage_download", "gm_coverage_allreduce", "gm_coverage_write_sgr", "gm_coverage_enable_nuc", "gm_coverage_nuc_device_ptr",
-           "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls"]
+           "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls",
+           "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim"]
 
 
 def library_path():
@@ -168,6 +169,10 @@ def load_library():
     L.gm_snp_calls.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
     L.gm_dev_snp_stat.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gm_coverage_write_gmp_calls.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_char_p, C.c_int]
+    L.gm_batch_set_adaptor.argtypes = [C.c_void_p, C.c_char_p]
+    L.gm_batch_trimmed_len.argtypes = [C.c_void_p, C.c_void_p]
+    L.gm_batch_adaptor_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(u64)]
+    L.gm_dev_adaptor_trim.argtypes = [C.c_void_p, C.POINTER(gm_reads), C.c_char_p, C.c_void_p]
     _LIB = L
     return L
 
@@ -305,6 +310,14 @@ class Index:
         _chk(lib().gm_dev_pair_hmm(self.h, C.byref(params.c), C.byref(r), read_idx.ctypes.data, strand.ctypes.data, pos.ctypes.data, len(read_idx), out.ctypes.data))
         return out
 
+    def adaptor_trim(self, B, Ln, adaptor):
+        """gm_dev_adaptor_trim: the length every read of B[n, stride] keeps with -A `adaptor` (SeqReader::FixReads2), uint16[n]"""
+        B = np.ascontiguousarray(B, np.uint8); Ln = np.ascontiguousarray(Ln, np.uint16)
+        r = _reads_struct(B, B, Ln)
+        out = np.zeros(len(Ln), np.uint16)
+        _chk(lib().gm_dev_adaptor_trim(self.h, C.byref(r), None if adaptor is None else bytes(adaptor), out.ctypes.data))
+        return out
+
     def dev_fmt_g6(self, values):
         """gm_dev_fmt_g6: printf("%g") of every value as the device prints XA / XP; a list of bytes (b"" = outside the domain)"""
         v = np.ascontiguousarray(values, np.float64); n = len(v)
@@ -393,6 +406,22 @@ class Batch:
             self.destroy()
         except Exception:
             pass
+
+    def set_adaptor(self, adaptor):
+        """-A: trim this adaptor (bytes) from the reads of every block uploaded from now on; None or b"" clears it"""
+        _chk(lib().gm_batch_set_adaptor(self.h, None if adaptor is None else bytes(adaptor)))
+
+    def trimmed_len(self):
+        """the lengths the kernels used for the block uploaded last (what the adaptor trim kept; the uploaded lengths without one)"""
+        out = np.zeros(self.n, np.uint16)
+        _chk(lib().gm_batch_trimmed_len(self.h, out.ctypes.data))
+        return out
+
+    def adaptor_time(self):
+        """(ms, launches) of k_adaptor_trim since the last call, while set_profiling is on"""
+        ms = C.c_double(); ln = u64()
+        _chk(lib().gm_batch_adaptor_time(self.h, C.byref(ms), C.byref(ln)))
+        return float(ms.value), int(ln.value)
 
     def upload(self, params, B, Q, Ln, stream=None):
         self._keep = (B, Q, Ln)

@@ -137,7 +137,10 @@ struct gm_batch {
         o_small, o_posmatch, o_post, o_mapq, o_emit, o_reccnt, o_cigcnt, o_cigall, o_recoff, o_cigoff, o_recs, o_pool, o_codes,
         pair_fb, pair_list,             // k_vote_pair: the reads it leaves to k_vote_bucket (one byte each), their list + its counter
         snp_scratch, snp_hmm,           // --snp: forward matrices of a chunk of kept sequences, their 5 floats per window position
-        t_names, t_nameoff, t_qtail, t_qtailoff, t_slots, t_rowlen, t_rowoff, t_text, t_bad;     // gm_output_batch_text: the block's names, tails and row offsets, the text
+        t_names, t_nameoff, t_qtail, t_qtailoff, t_slots, t_rowlen, t_rowoff, t_text, t_bad,     // gm_output_batch_text: the block's names, tails and row offsets, the text
+        full_len, d_adaptor;            // -A: the lengths as uploaded (`len` then holds what k_adaptor_trim keeps), the adaptor's characters
+    std::string adaptor;                // gm_batch_set_adaptor; empty = none (no launch, no copy, no wait in gm_batch_upload)
+    bool adaptor_dirty = false;         // d_adaptor does not hold `adaptor` yet
     PinBuf h_top, h_hbegin, h_ord, h_post, h_mapq, h_emit, h_mhit, h_stat;      // h_stat: the small status words a phase reads back (page-locked: one short DMA)
     std::vector<double> h_exp;          // exp(score) of every accepted hit of the last gm_map_batch (reused by gm_output_batch)
     uint64_t cache_hits = 0, cache_matches = 0;
@@ -162,7 +165,8 @@ struct gm_batch {
     bool mapped = false;
     unsigned long long counters_host[GMK_N] = { 0 };
     GmDevBatch dev{};
-    std::vector<uint16_t> len_host;
+    std::vector<uint16_t> len_host;     // the lengths `len` holds in HBM: as uploaded, or with an adaptor set what k_adaptor_trim kept
+    double adaptor_ms = 0; uint64_t adaptor_launches = 0;      // k_adaptor_trim while profiling is on (gm_batch_adaptor_time)
     // sub-batch pipeline (gm_map_batch_device on large batches): streams + per-stream retry tables + host counter sums
     static const int NS = 3;
     hipStream_t sub_streams[NS] = { nullptr, nullptr, nullptr };
@@ -586,7 +590,7 @@ extern "C" void gm_batch_destroy(gm_batch* b) {
                       &b->g_sorted, &b->g_ord, &b->g_lead, &b->g_krank, &b->g_khash, &b->g_nmatch, &b->g_mbegin, &b->g_multi, &b->g_big, &b->g_bigdone, &b->g_sk0, &b->g_sk1, &b->g_si0, &b->g_si1, &b->g_matches, &b->g_mhit, &b->g_positions,
                       &b->scan_tmp, &b->o_small, &b->o_posmatch, &b->o_post, &b->o_mapq, &b->o_emit, &b->o_reccnt, &b->o_cigcnt, &b->o_cigall, &b->o_recoff, &b->o_cigoff,
                       &b->o_recs, &b->o_pool, &b->o_codes, &b->snp_scratch, &b->snp_hmm, &b->pair_fb, &b->pair_list,
-                      &b->t_names, &b->t_nameoff, &b->t_qtail, &b->t_qtailoff, &b->t_slots, &b->t_rowlen, &b->t_rowoff, &b->t_text, &b->t_bad };
+                      &b->t_names, &b->t_nameoff, &b->t_qtail, &b->t_qtailoff, &b->t_slots, &b->t_rowlen, &b->t_rowoff, &b->t_text, &b->t_bad, &b->full_len, &b->d_adaptor };
     for (DevBuf* d : all) d->release();
     PinBuf* pins[] = { &b->h_top, &b->h_hbegin, &b->h_ord, &b->h_post, &b->h_mapq, &b->h_emit, &b->h_mhit, &b->h_stat };
     for (PinBuf* d : pins) d->release();
@@ -650,26 +654,99 @@ extern "C" int gm_batch_upload(gm_batch* b, const gm_params* p, const gm_reads* 
         b->len_max = std::max<uint32_t>(b->len_max, r->len[i]);
         b->len_min = std::min<uint32_t>(b->len_min, r->len[i]);
     }
+    const bool trim = !b->adaptor.empty() && r->n != 0;
+    if (bytes) {
+        HIPCHK(hipMemcpyAsync(b->bases.p, r->bases, bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b->quals.p, r->quals, bytes, hipMemcpyHostToDevice, st));
+        if (!trim) HIPCHK(hipMemcpyAsync(b->len.p, r->len, (size_t)r->n * 2, hipMemcpyHostToDevice, st));
+    }
+    if (trim) {
+        // -A (SeqReader.cpp:1146-1150): the lengths as uploaded stay in full_len (SEQ / QUAL of a SAM row are the whole lines, :1264-1265),
+        // `len` - what every kernel downstream reads - takes what FixReads2 keeps, and the host's copy follows: one small wait per upload
+        if (b->full_len.ensure((size_t)r->n * 2 + 16) || b->d_adaptor.ensure(GM_ADAPTOR_MAX)) return GM_E_NOMEM;
+        if (b->adaptor_dirty) { HIPCHK(hipMemcpyAsync(b->d_adaptor.p, b->adaptor.data(), b->adaptor.size(), hipMemcpyHostToDevice, st)); b->adaptor_dirty = false; }
+        HIPCHK(hipMemcpyAsync(b->full_len.p, r->len, (size_t)r->n * 2, hipMemcpyHostToDevice, st));
+        hipEvent_t ea = nullptr, ee = nullptr;
+        if (b->profiling) { if (hipEventCreate(&ea) != hipSuccess || hipEventCreate(&ee) != hipSuccess) { if (ea) (void)hipEventDestroy(ea); ea = ee = nullptr; } }
+        if (ea) (void)hipEventRecord(ea, st);
+        const int krc = gmk_adaptor_trim(b->bases.as<uint8_t>(), r->stride, b->full_len.as<uint16_t>(), r->n, b->d_adaptor.as<uint8_t>(), (uint32_t)b->adaptor.size(),
+                                         b->len.as<uint16_t>(), st);
+        if (ea) (void)hipEventRecord(ee, st);
+        hipError_t e1 = krc ? (hipError_t)krc : hipMemcpyAsync(b->len_host.data(), b->len.p, (size_t)r->n * 2, hipMemcpyDeviceToHost, st);
+        if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+        if (ea) { float ms = 0.0f; if (e1 == hipSuccess && hipEventElapsedTime(&ms, ea, ee) == hipSuccess) { b->adaptor_ms += ms; ++b->adaptor_launches; } (void)hipEventDestroy(ea); (void)hipEventDestroy(ee); }
+        if (e1 != hipSuccess) { gm_set_error(std::string("k_adaptor_trim: ") + hipGetErrorString(e1)); return GM_E_HIP; }
+        b->len_max = 0; b->len_min = 0xFFFFFFFFu;                 // a block whose reads all keep one length takes the one-length DP / prep kernels
+        for (uint32_t i = 0; i < r->n; ++i) { b->len_max = std::max<uint32_t>(b->len_max, b->len_host[i]); b->len_min = std::min<uint32_t>(b->len_min, b->len_host[i]); }
+    }
     // --illumina with automatic fallback (SeqReader.cpp:1171-1180): reads before the first one that shows a
-    // quality below '@' keep Phred+64, that read and all later ones use Phred+33
+    // quality below '@' keep Phred+64, that read and all later ones use Phred+33 (with -A only the kept characters are looked at, :1152)
     b->illumina_until = 0;
     if (p->illumina) {
         uint32_t until = r->n;
         for (uint32_t i = 0; i < r->n && until == r->n; ++i) {
             const uint8_t* q = r->quals + (size_t)i * r->stride;
-            for (uint32_t t = 0; t < r->len[i]; ++t) if ((int8_t)q[t] < 64) { until = i; break; }      // `int Q = (int)fastq[i]` (SeqReader.cpp:1155): a signed char
+            for (uint32_t t = 0; t < b->len_host[i]; ++t) if ((int8_t)q[t] < 64) { until = i; break; }      // `int Q = (int)fastq[i]` (SeqReader.cpp:1155): a signed char
         }
         b->illumina_until = until;
-    }
-    if (bytes) {
-        HIPCHK(hipMemcpyAsync(b->bases.p, r->bases, bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(b->quals.p, r->quals, bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(b->len.p, r->len, (size_t)r->n * 2, hipMemcpyHostToDevice, st));
     }
     int rc = ensure_batch_buffers(b, p);
     if (rc) return rc;
     fill_dev_batch(b);
     return GM_OK;
+}
+
+// -A / --adaptor (Driver.cpp:2793-2798: the string exactly as given).  Takes effect with the next upload; NULL or "" clears it.
+extern "C" int gm_batch_set_adaptor(gm_batch* b, const char* adaptor) {
+    if (!b) { gm_set_error("gm_batch_set_adaptor: batch is NULL"); return GM_E_ARG; }
+    const size_t n = adaptor ? strlen(adaptor) : 0;
+    if (n > GM_ADAPTOR_MAX) { gm_set_error("gm_batch_set_adaptor: an adaptor of at most 256 characters"); return GM_E_ARG; }
+    b->adaptor.assign(adaptor ? adaptor : "", n);
+    b->adaptor_dirty = n != 0;
+    return GM_OK;
+}
+
+extern "C" int gm_batch_trimmed_len(gm_batch* b, uint16_t* out) {
+    if (!b || (b->n && !out)) return GM_E_ARG;
+    if (b->len_host.size() < b->n) { gm_set_error("gm_batch_trimmed_len: no block uploaded"); return GM_E_ARG; }
+    if (b->n) memcpy(out, b->len_host.data(), (size_t)b->n * 2);
+    return GM_OK;
+}
+
+extern "C" int gm_batch_adaptor_time(gm_batch* b, double* ms, uint64_t* launches) {
+    if (!b || !ms || !launches) return GM_E_ARG;
+    *ms = b->adaptor_ms; *launches = b->adaptor_launches;
+    b->adaptor_ms = 0; b->adaptor_launches = 0;
+    return GM_OK;
+}
+
+// k_adaptor_trim on a caller's block (unit level, parity tests): out_len[i] = what FixReads2 keeps of read i; only bases and len are read
+extern "C" int gm_dev_adaptor_trim(gm_index* ix, const gm_reads* reads, const char* adaptor, uint16_t* out_len) {
+    if (!ix || !reads || (reads->n && (!reads->bases || !reads->len || !out_len))) return GM_E_ARG;
+    const size_t a_len = adaptor ? strlen(adaptor) : 0;
+    if (a_len > GM_ADAPTOR_MAX) { gm_set_error("gm_dev_adaptor_trim: an adaptor of at most 256 characters"); return GM_E_ARG; }
+    if (reads->stride % 8 != 0 || reads->stride > 2048) { gm_set_error("gm_reads.stride must be a multiple of 8, at most 2048"); return GM_E_ARG; }
+    for (uint32_t i = 0; i < reads->n; ++i) if (reads->len[i] > reads->stride) { gm_set_error("read longer than stride"); return GM_E_ARG; }
+    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (reads->n == 0) return GM_OK;
+    if (a_len == 0) { memcpy(out_len, reads->len, (size_t)reads->n * 2); return GM_OK; }      // no adaptor: every read keeps its length
+    HIPCHK(hipSetDevice(ix->device));
+    DevBuf db, dl, da, dout;
+    const size_t bytes = (size_t)reads->n * reads->stride;
+    int rc = GM_OK;
+    if (db.ensure(bytes + 16) || dl.ensure((size_t)reads->n * 2) || da.ensure(GM_ADAPTOR_MAX) || dout.ensure((size_t)reads->n * 2)) rc = GM_E_NOMEM;
+    auto run = [&]() -> int {
+        if (bytes) HIPCHK(hipMemcpy(db.p, reads->bases, bytes, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dl.p, reads->len, (size_t)reads->n * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(da.p, adaptor, a_len, hipMemcpyHostToDevice));
+        KCHK(gmk_adaptor_trim(db.as<uint8_t>(), reads->stride, dl.as<uint16_t>(), reads->n, da.as<uint8_t>(), (uint32_t)a_len, dout.as<uint16_t>(), nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(out_len, dout.p, (size_t)reads->n * 2, hipMemcpyDeviceToHost));
+        return GM_OK;
+    };
+    if (rc == GM_OK) rc = run();
+    db.release(); dl.release(); da.release(); dout.release();
+    return rc;
 }
 
 // Large batches in full-SA mode: the batch is cut into sub-batches that go through prep -> seed -> vote -> NW on NS
@@ -746,7 +823,7 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
         HIPCHK(hipMemsetAsync(view[i].shard_cnt, 0, shard_bytes, ss));
         HIPCHK(hipMemsetAsync(view[i].rs_overflow, 0, 2 * (size_t)view[i].n, ss));
         { KTimer t(b, GM_K_PREP, ss); KCHK(gmk_prep(ix->dev, dp, view[i], ss)); }
-        { KTimer t(b, GM_K_SEED, ss); KCHK(gmk_seed(ix->dev, dp, view[i], ss)); }
+        { KTimer t(b, GM_K_SEED, ss); KCHK(gmk_seed(ix->dev, dp, view[i], ss, b->adaptor.empty() ? nullptr : b->full_len.as<uint16_t>() + view[i].read_base)); }
         { KTimer t(b, GM_K_VOTE, ss); KCHK(gmk_vote(ix->dev, dp, view[i], 1, dense, slots_hint, ss)); }
         if (i + 1 >= (uint32_t)gm_batch::NS) { int rc = finish(next_finish++); if (rc) return rc; }
     }
@@ -846,6 +923,8 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
         const uint32_t max_reg = (lastmax + (uint32_t)p->jump - 1) / (uint32_t)p->jump;
         use_bucket = dp.bucket && use_full && dp.kmer_tab && dp.kmer_T == dp.bucket_T && dp.bucket_T == p->mer && p->min_seed_hits >= 2 && max_reg <= 32 && b->max_seeds <= 34 && !gm_opt("GM_VOTE_KERNEL") &&
                      !gm_opt("GM_VOTE") && gm_opt_ll("GM_PIPELINE", 0) == 0 && !(dp.dbg & 128) && fused_env != 0;
+        // -A: the minus strand's k-mers come from another stretch of the row than its DP (see k_seed): only k_seed knows that form
+        if (!b->adaptor.empty()) { dp.fused = 0; use_bucket = false; }
         if (use_bucket) { dp.fused = 1; bucket_reg = max_reg; } else dp.bucket = nullptr;
         // ... two reads per wavefront (gm_pair.hip) where a strand has at most 16 seeds; GM_VOTE_PAIR=0: one read per wavefront always
         use_pair = use_bucket && !dp.bucket_ctx && max_reg <= 16 && !(p->nw && p->fast) && !gm_opt_is("GM_VOTE_PAIR", "0") && !(dp.dbg & (64 | 256 | 512 | 1024 | 2048));       // (GM_DBG 4096 .. 32768: timing experiments of k_vote_pair)
@@ -883,7 +962,7 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     fill_dev_batch(b);
     HIPCHK(hipMemsetAsync(b->counters.p, 0, GMK_N * 8, st));
     { KTimer t(b, GM_K_PREP, st); KCHK(gmk_prep(ix->dev, dp, b->dev, st)); }
-    if (!dp.fused) { KTimer t(b, GM_K_SEED, st); KCHK(gmk_seed(ix->dev, dp, b->dev, st)); }
+    if (!dp.fused) { KTimer t(b, GM_K_SEED, st); KCHK(gmk_seed(ix->dev, dp, b->dev, st, b->adaptor.empty() ? nullptr : b->full_len.as<uint16_t>())); }
     unsigned long long ctr[GMK_N];
     if (!use_full) {
         // faithful mode: locate every SA hit by LF walks into coords[] first (exact size from the seed kernel)
@@ -1538,6 +1617,7 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
     // length of every sequence's CIGAR text and finds the longest aligned length
     KCHK(gmk_traceback(ix->dev, dp, b->dev, b->tb_items.as<GmCand>(), n_m, b->tb_ops.as<unsigned long long>(), ops_words, b->tb_len.as<uint16_t>(),
                        nullptr, b->o_cigall.as<uint32_t>(), b->o_small.as<uint32_t>(), st));
+    if (!p->nw && !b->adaptor.empty()) KCHK(gmk_adaptor_cigar_room(d_m, n_m, b->full_len.as<uint16_t>(), std::min<uint32_t>(n, b->n), b->o_cigall.as<uint32_t>(), st));
     pc.lap("enqueue");
     // ---- host pass: ScoredSeq::get_SAM :300-309, is_greater :223-228, Driver.cpp:672-701 ----
     if (b->h_post.ensure((size_t)n_m * 4) || b->h_mapq.ensure((size_t)n_m * 4) || b->h_emit.ensure(n_m)) return GM_E_NOMEM;
@@ -1602,7 +1682,9 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
     if (cig_len > 0xFFFFFFFFull) { gm_set_error("CIGAR pool beyond 4 GB in one batch; map the block in smaller pieces"); return GM_E_BATCH_TOO_LARGE; }
     if (b->o_recs.ensure((size_t)(n_recs + 1) * sizeof(GmDevSamRec)) || b->o_pool.ensure((size_t)cig_len + 16)) return GM_E_NOMEM;
     if (n_recs) {
-        KCHK(gmk_out_write(ix->dev, b->dev, d_m, d_p, n_m, b->o_emit.as<uint8_t>(), b->o_mapq.as<int32_t>(), b->o_post.as<float>(), b->tb_ops.as<unsigned long long>(),
+        GmDevBatch wb = b->dev;                      // (k_out_write reads the lengths for --no_nw's "<L>M" only: consensus.size(), the whole line with -A, ScoredSeq.h:365)
+        if (!b->adaptor.empty()) wb.len = b->full_len.as<uint16_t>();
+        KCHK(gmk_out_write(ix->dev, wb, d_m, d_p, n_m, b->o_emit.as<uint8_t>(), b->o_mapq.as<int32_t>(), b->o_post.as<float>(), b->tb_ops.as<unsigned long long>(),
                            ops_words, b->tb_len.as<uint16_t>(), p->nw, b->o_recoff.as<uint64_t>(), b->o_cigoff.as<uint64_t>(),
                            b->o_recs.as<GmDevSamRec>(), b->o_pool.as<char>(), st));
         if (!tout) {
@@ -1647,6 +1729,7 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
             t.cnames = ix->d_cnames.as<char>(); t.cname_off = ix->d_cname_off.as<uint32_t>();
             t.slots = b->t_slots.as<uint8_t>(); t.row_len = b->t_rowlen.as<uint32_t>(); t.row_off = b->t_rowoff.as<uint64_t>();
             t.inv_adjust = 1.0 / p->adjust; t.bad = b->t_bad.as<unsigned long long>();
+            t.seq_len = b->adaptor.empty() ? b->dev.len : b->full_len.as<uint16_t>();
             KCHK(gmk_out_text_sizes(b->dev, t, st));
             KCHK(gmk_scan_u32(t.row_len, n_recs, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
             uint64_t text_len = 0; unsigned long long bad = ~0ull;

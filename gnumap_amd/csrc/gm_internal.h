@@ -55,6 +55,7 @@ struct GmSeed { uint32_t k, l, pos; };
 // EVERY read x strand: one 1 KB stretch per wavefront instead of 16 bytes out of every 64), slots 1 .. 3 behind them
 #define GM_FIXED_AT(b, rs, idx) (((size_t)(rs) >> 6) * (64 * GM_FIXED_C) + ((idx) == 0 ? ((size_t)(rs) & 63) : 64 + ((size_t)(rs) & 63) * (GM_FIXED_C - 1) + (size_t)(idx) - 1))
 #define GM_GROUP_BIG 64          // accepted hits per read above which grouping takes the hash-set + sort path
+#define GM_ADAPTOR_MAX 256       // longest -A / --adaptor sequence gm_batch_set_adaptor takes (k_adaptor_trim keeps it in LDS)
 #define GM_NSHARD 1024
 #define GM_SHARD_STRIDE 32
 
@@ -151,6 +152,7 @@ struct GmDevText {
     char* text;
     double inv_adjust;                              // 1.0 / gADJUST: XA is printed rescaled
     unsigned long long* bad;                        // smallest record whose XA / XP lies outside gm_put_g6_hd's domain (~0: none)
+    const uint16_t* seq_len;                        // characters of SEQ / QUAL a row prints: the block's lengths as uploaded (with -A the whole line, not the kept part)
 };
 
 // gm_snp_rec (layout asserted in gm_api.cpp): a row of --snp's .gmp that carries a 'Y' call, written by k_snp_gather (gm_snpcall.hip)
@@ -192,7 +194,8 @@ int gmk_build_kmer_compact(const uint2* tab, uint4* ctab, int T, void* stream);
 int gmk_extend_kmer_table(const GmDevIndex& ix, const uint2* prev, uint2* next, int T, void* stream);
 int gmk_prep(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, void* stream);
 int gmk_prep_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, void* stream);      // gm_prep.hip (stride <= 152)
-int gmk_seed(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, void* stream);
+// full_len != null (-A): the lengths as uploaded, b.len being what the adaptor trim kept: the minus strand's k-mers come from the END of the line
+int gmk_seed(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, void* stream, const uint16_t* full_len = nullptr);
 int gmk_scan_entries(const GmDevBatch& b, void* stream);
 int gmk_locate_sampled(const GmDevIndex& ix, const GmDevBatch& b, unsigned long long n_entries /* SA hits of the block = entries of coords[] */, void* stream);
 int gmk_vote(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, int use_full_sa, int dense, int slots_hint, void* stream);
@@ -271,6 +274,9 @@ int gmk_out_deposit(float* cov, uint64_t bins, uint32_t bin_size, const GmDevMat
 int gmk_out_text_sizes(const GmDevBatch& b, const GmDevText& t, void* stream);
 int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream);
 int gmk_fmt_g6(const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len, void* stream);
+// gm_adaptor.hip: -A / --adaptor (SeqReader::FixReads2): out_len[r] = the length read r keeps; len = the lengths as uploaded, stride a multiple of 8
+int gmk_adaptor_cigar_room(const GmDevMatch* matches, uint32_t n_m, const uint16_t* full_len, uint32_t n, uint32_t* cig_all, void* stream);      // --no_nw with -A: room for "<whole length>M"
+int gmk_adaptor_trim(const uint8_t* bases, uint32_t stride, const uint16_t* len, uint32_t n, const uint8_t* adaptor, uint32_t a_len, uint16_t* out_len, void* stream);
 int gmk_coverage_add(float* cov, uint64_t bins, uint32_t bin_size, const uint64_t* pos, const uint32_t* span, const float* w,
                      uint32_t n, uint32_t max_span, float* nuc, const uint8_t* codes, const uint64_t* code_off, void* stream);
 }

@@ -296,7 +296,11 @@ __global__ void __launch_bounds__(256) k_prep(GmDevIndex ix, GmDevParams p, GmDe
 // ------------------------------------------------------------------------------------------------
 // seed: one lane per read x strand walks the read exactly like align_sequence does
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256, 8) k_seed(GmDevIndex ix, GmDevParams p, GmDevBatch b, uint32_t TR) {
+// ADAPT (-A): the reference walks the minus strand over the reverse complement of the WHOLE sequence line (Driver.cpp:352-355 hands
+// set_top_matches Read::seq, :538 reverses it) but only over Read::length = the kept characters of it: the minus strand's k-mers are
+// those of the last b.len[r] characters of the line, not of the first - full_len[r] - b.len[r] bytes further into the row
+template <bool ADAPT>
+__global__ void __launch_bounds__(256, 8) k_seed(GmDevIndex ix, GmDevParams p, GmDevBatch b, uint32_t TR, const uint16_t* full_len) {
     // the TR reads of a tile (2 lanes per read: + and - strand; TR = 128 unless long reads leave less room in LDS: gmk_seed) are
     // staged into LDS with coalesced 16-byte loads
     extern __shared__ __attribute__((aligned(16))) unsigned char s_reads[];
@@ -328,6 +332,7 @@ __global__ void __launch_bounds__(256, 8) k_seed(GmDevIndex ix, GmDevParams p, G
         if (on) {
             uint32_t L = b.len[r];
             const unsigned char* rb = s_reads + (size_t)(r - r0) * b.stride;
+            if (ADAPT && strand) { const uint32_t lf = full_len[r]; rb += lf > L && lf <= b.stride ? lf - L : 0u; }
             gm_seed_walk(ix, p, rb, L, strand, b.seeds + (size_t)rs * b.max_seeds, b.max_seeds, nk, nocc, nblk, ntab, nseed, nent);
         }
         b.n_seeds[rs] = (uint16_t)(nseed < b.max_seeds ? nseed : b.max_seeds);
@@ -2682,7 +2687,7 @@ __global__ void __launch_bounds__(256, NCH > 0 ? (LDSR ? 2 : NCH <= 13 ? 4 : 3) 
             // source register whole): picking a cell's value among the row's four is three byte-permutes, no compares
             uint32_t S1[7], S2[7];
             auto set_col = [&](int d, uint32_t code) { S1[d] = 0x03020100u + (code & 1u) * 0x04040404u; S2[d] = 0x03020100u + (code >> 1) * 0x04040404u; };
-            uint32_t wword_lo = 0, wword_hi = 0; int wbase = -1;          // 16-base words [wbase*16, +16) and the next one
+            uint32_t wword_lo = 0, wword_hi = 0; int wbase = -2;          // 16-base words [wbase*16, +16) and the next one (-2: nothing loaded yet - word 0 is neither it nor its successor)
             auto wcode = [&](int j) -> uint32_t {                          // 2-bit code of the reference at window offset j
                 uint32_t g = c.b + (uint32_t)j;
                 int wi16 = (int)(g >> 4);
@@ -3089,7 +3094,7 @@ __global__ void __launch_bounds__(NT) k_traceback_lane(GmDevIndex ix, GmDevParam
             const uint8_t* rb = b.bases + (size_t)r * b.stride;
             const uint8_t* rq = b.quals + (size_t)r * b.stride;
             const int Li = (int)L;
-            uint32_t wword_lo = 0, wword_hi = 0; int wbase = -1;
+            uint32_t wword_lo = 0, wword_hi = 0; int wbase = -2;          // (-2, not -1: a window that starts in the reference's first 16 bases must load word 0)
             auto wcode = [&](int j) -> uint32_t {                        // 2-bit code of the reference at window offset j
                 uint32_t g = c.b + (uint32_t)j;
                 int wi16 = (int)(g >> 4);
@@ -3304,7 +3309,7 @@ int gmk_prep(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, vo
     return (int)hipGetLastError();
 }
 
-int gmk_seed(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, void* stream) {
+int gmk_seed(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, void* stream, const uint16_t* full_len) {
     if (b.n == 0) return 0;
     // (measured: a grid of exactly the resident workgroups is slower here, 8.7 against 7.6 ms at 10 M reads)
     const uint32_t seed_grid = (uint32_t)gm_opt_ll("GM_SEED_GRID", 256 * 12);
@@ -3312,7 +3317,8 @@ int gmk_seed(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, vo
     uint32_t TR = 128;
     while (TR > 32 && (size_t)TR * b.stride > 64u * 1024u) TR -= 32;
     if ((size_t)TR * b.stride > 64u * 1024u) return (int)hipErrorInvalidValue;     // stride > 2048: gm_batch_upload refuses it
-    hipLaunchKernelGGL(k_seed, dim3((uint32_t)std::min<uint64_t>(cdiv(b.n, TR), seed_grid)), dim3(256), (size_t)TR * b.stride, S_(stream), ix, p, b, TR);
+    if (full_len) hipLaunchKernelGGL(k_seed<true>, dim3((uint32_t)std::min<uint64_t>(cdiv(b.n, TR), seed_grid)), dim3(256), (size_t)TR * b.stride, S_(stream), ix, p, b, TR, full_len);
+    else hipLaunchKernelGGL(k_seed<false>, dim3((uint32_t)std::min<uint64_t>(cdiv(b.n, TR), seed_grid)), dim3(256), (size_t)TR * b.stride, S_(stream), ix, p, b, TR, full_len);
     return (int)hipGetLastError();
 }
 

@@ -704,7 +704,7 @@ __global__ void __launch_bounds__(256) k_out_text_sizes(GmDevBatch b, GmDevText 
         unsigned long long nl = t.name_off[rd + 1] - t.name_off[rd];
         if (nl > GO_NAME_MAX) nl = GO_NAME_MAX;
         const uint32_t cl = t.cname_off[r.contig + 1] - t.cname_off[r.contig];
-        const uint32_t L = b.len[rd];
+        const uint32_t L = t.seq_len[rd];
         const uint32_t QL = L + (t.qtail_off ? (uint32_t)(t.qtail_off[rd + 1] - t.qtail_off[rd]) : 0u);
         t.row_len[k] = (uint32_t)nl + (r.strand ? 4u : 3u) + cl + 1u + go_digits64(r.chr_pos) + 1u + go_int_chars(r.mapq) + 1u + gout + 7u + L + 1u + QL + 1u + tail;
     }
@@ -747,7 +747,7 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
             char* const out = t.text;
             const uint8_t* slot = t.slots + k * 64ull;
             const uint32_t gl = (uint32_t)slot[56] | ((uint32_t)slot[57] << 8), gout = (uint32_t)slot[58] | ((uint32_t)slot[59] << 8), tail = slot[60];
-            const uint32_t rd = r.read, L = b.len[rd];
+            const uint32_t rd = r.read, L = t.seq_len[rd];
             const unsigned long long n0 = t.name_off[rd];
             unsigned long long nl64 = t.name_off[rd + 1] - n0;
             const uint32_t nl = nl64 > GO_NAME_MAX ? GO_NAME_MAX : (uint32_t)nl64;

@@ -42,6 +42,7 @@
 
 struct Options {
     std::string genome, output = "gnumap_out", reads, subst;
+    std::string adaptor;        // -A / --adaptor: trimmed from the 3' end of every read on the device (gm_batch_set_adaptor); empty = none
     gm_params p;
     int gpus = 1, locate_sampled = 0, verbose = 1;
     uint32_t batch = 262144;
@@ -72,6 +73,11 @@ static void usage(int rc, const char* msg) {
             "  -u X                         Only match sequences to one position (like the reference, -u swallows the next word)\n"
             "  -G, --gap_penalty=DOUBLE     Gap penalty (default: -4)\n"
             "  -S, --subst_file=STRING      5 x 4 substitution matrix file (rows a c g t n; scores are then used unscaled)\n"
+            "  -A, --adaptor=STRING         Adaptor sequence to trim from the 3' end of every read (SeqReader::FixReads2, on the GPU):\n"
+            "                               a read is cut at the first offset where 85%% of the compared characters equal the adaptor's,\n"
+            "                               else loses its last 4 bases; SEQ and QUAL of a row stay whole.  At most 256 characters.\n"
+            "                               -A takes the string as given and is pinned to the reference program's output;\n"
+            "                               --adaptor=STRING is -A of the lower-cased string (the reference reads an unterminated buffer there)\n"
             "  -c, --num_proc=INT           accepted for compatibility (the GPU path ignores it)\n"
             "  -b, --bs_seq / --b2 / -d, --a_to_g   bisulfite / A-to-G scoring\n"
             "      --snp                    pair-HMM per-nucleotide deposit (SNPScoredSeq); <out>.gmp with eight columns (no SNP call)\n"
@@ -114,6 +120,7 @@ static void parse_args(int argc, char** argv, Options& o) {
             else if (starts(s, "max_kmer=")) o.p.max_kmer_hits = (uint32_t)atoi(s + 9);
             else if (starts(s, "gap_penalty=")) o.p.gap = (float)atof(s + 12);
             else if (starts(s, "subst_file=")) o.subst = s + 11;
+            else if (starts(s, "adaptor=")) { o.adaptor = s + 8; for (char& ch : o.adaptor) ch = (char)tolower((unsigned char)ch); }     // Driver.cpp:3160-3163
             else if (starts(s, "max_gap=")) o.p.max_gap = atoi(s + 8);
             else if (!strcmp(s, "unique")) o.p.unique_only = 1;
             else if (!strcmp(s, "print_all_sam")) o.p.print_all_sam = 1;
@@ -182,7 +189,8 @@ static void parse_args(int argc, char** argv, Options& o) {
             case 'j': o.p.jump = atoi(v); break;
             case 'k': o.p.min_seed_hits = atoi(v); break;
             case 'S': o.subst = v; break;
-            case 'l': case 'B': case 's': case 'A': fprintf(stderr, "option -%c is outside the hot path of this build\n", c); exit(1);
+            case 'A': o.adaptor = v; break;                                     // Driver.cpp:2792-2798: exactly as given
+            case 'l': case 'B': case 's': fprintf(stderr, "option -%c is outside the hot path of this build\n", c); exit(1);
             case '?': usage(0, "");
             default: fprintf(stderr, "Irregular Parameter in: %s\n", a); exit(1);
         }
@@ -194,6 +202,7 @@ static void parse_args(int argc, char** argv, Options& o) {
     if (o.p.mode == GM_MODE_ATOG && !o.p.pos_strand) o.p.mode = GM_MODE_ATOG2;
     if (gm_params_finalize(&o.p) != GM_OK) { fprintf(stderr, "%s\n", gm_last_error()); exit(1); }
     if (!o.subst.empty() && gm_params_load_subst(&o.p, o.subst.c_str()) != GM_OK) { fprintf(stderr, "ERROR: \n\t%s\n", gm_last_error()); exit(1); }
+    if (o.adaptor.size() > 256) { fprintf(stderr, "Error: -A/--adaptor takes at most 256 characters\n"); exit(1); }
     if (o.gpus < 1) o.gpus = 1;
     if (o.batch < 1) o.batch = 1;
     if (o.workers < 1) o.workers = 1;
@@ -256,6 +265,7 @@ struct Block {
     std::vector<const char*> name, seq, qual;
     std::vector<uint32_t> name_len, qual_len;
     std::vector<uint16_t> len;
+    std::vector<uint16_t> kept;             // -A with --illumina: what the adaptor trim keeps of every read (the fallback scan sees only that); else empty
     // packed for gm_reads (page-locked)
     PinVec<uint8_t> bases, qbuf; PinVec<uint16_t> plen;
     // results of the two batch calls (page-locked)
@@ -649,9 +659,10 @@ static int process_block_split(Worker& w, const Options& o, Block& b, int depth)
         c.name.assign(b.name.begin() + lo, b.name.begin() + hi); c.seq.assign(b.seq.begin() + lo, b.seq.begin() + hi);
         c.qual.assign(b.qual.begin() + lo, b.qual.begin() + hi); c.name_len.assign(b.name_len.begin() + lo, b.name_len.begin() + hi);
         c.qual_len.assign(b.qual_len.begin() + lo, b.qual_len.begin() + hi); c.len.assign(b.len.begin() + lo, b.len.begin() + hi);
+        if (!b.kept.empty()) c.kept.assign(b.kept.begin() + lo, b.kept.begin() + hi);
         if (part && b.illumina) {                           // the fallback may have happened inside the first half
             for (uint32_t i = 0; i < half && c.illumina; ++i)
-                for (uint32_t t = 0; t < b.len[i]; ++t) if ((signed char)b.qual[i][t] < 64) { c.illumina = 0; break; }      // (the reference's quality characters are signed chars)
+                for (uint32_t t = 0; t < (b.kept.empty() ? b.len[i] : b.kept[i]); ++t) if ((signed char)b.qual[i][t] < 64) { c.illumina = 0; break; }      // (the reference's quality characters are signed chars)
         }
         rc = process_block_split(w, o, c, depth + 1);
         if (rc != GM_OK) { w.text_pool->put(c.dtext); return rc; }
@@ -703,7 +714,8 @@ int main(int argc, char** argv) {
         for (int k = 0; k < o.workers; ++k) {
             Worker& w = workers[(size_t)g * (size_t)o.workers + (size_t)k];
             w.gpu = g; w.ix = gpu_ix[(size_t)g]; w.text_pool = &text_pool;
-            if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+            if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK ||
+                gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
         }
     }
     gm_index_info info;
@@ -712,6 +724,7 @@ int main(int argc, char** argv) {
     if (o.verbose > 0)
         fprintf(stderr, "gnumap-mi355x: genome %s (%lu bp, %u contigs), %s locate, %d GPU(s), index %.1f MB in HBM\n", o.genome.c_str(),
                 (unsigned long)info.l_pac, info.n_seqs, info.full_sa ? "full-SA" : "sampled-SA", o.gpus, info.hbm_bytes / 1e6);
+    if (o.verbose > 0 && !o.adaptor.empty()) fprintf(stderr, "\tUsing Adaptor Sequence: %s\n", o.adaptor.c_str());      // Driver.cpp:1231-1233
     // one <out>.sam, or --sam_shards=K files <out>.<k>.sam: every shard has its own descriptor and offset counter (no two share an inode)
     const int K = o.sam_shards;
     std::vector<int> ofds((size_t)K, -1);
@@ -781,9 +794,17 @@ int main(int argc, char** argv) {
                 if (!more || failed) { free_q.push(b); break; }
                 b->index = idx++; b->failed = false;
                 b->illumina = ill_state;
+                b->kept.clear();
+                if (ill_state && !o.adaptor.empty()) {      // -A: the fallback scan sees only the characters the trim keeps (SeqReader.cpp:1152)
+                    std::vector<uint8_t> rows((size_t)b->n * b->stride, 0);
+                    for (uint32_t i = 0; i < b->n; ++i) memcpy(&rows[(size_t)i * b->stride], b->seq[i], b->len[i]);
+                    gm_reads rr; rr.n = b->n; rr.stride = b->stride; rr.bases = rows.data(); rr.quals = nullptr; rr.len = b->len.data();
+                    b->kept.resize(b->n);
+                    if (gm_dev_adaptor_trim(gpu_ix[0], &rr, o.adaptor.c_str(), b->kept.data()) != GM_OK) { fprintf(stderr, "ERROR: gm_dev_adaptor_trim: %s\n", gm_last_error()); failed = 1; free_q.push(b); break; }
+                }
                 if (ill_state)                              // gILLUMINA is cleared for the rest of the run by the first quality below '@'
                     for (uint32_t i = 0; i < b->n && ill_state; ++i)
-                        for (uint32_t t = 0; t < b->len[i]; ++t) if ((signed char)b->qual[i][t] < 64) { ill_state = 0; break; }
+                        for (uint32_t t = 0; t < (b->kept.empty() ? b->len[i] : b->kept[i]); ++t) if ((signed char)b->qual[i][t] < 64) { ill_state = 0; break; }
                 map_q.push(b);
             }
             map_q.close();

@@ -22,6 +22,7 @@
  *   gm_output_batch_text             the same block loop, ending in the SAM rows as text: the print loop of
  *                                    parallel_thread_run src/Driver.cpp:2146-2217, ScoredSeq::get_SAM inc/ScoredSeq.h:293-404,
  *                                    reverse_comp / reverse_CIGAR inc/SequenceOperations.h:56-123
+ *   gm_batch_set_adaptor             -A: SeqReader::FixReads2 / Compare            src/SeqReader.cpp:1146-1150, 1294-1305, 1356-1372
  *   gm_coverage_*                    amount_genome, PrintFinalSGR src/GenomeBwt.cpp:1212-1273; the MPI
  *                                    Allreduce of the track src/Driver.cpp:1660-1672 (-> RCCL)
  *
@@ -225,6 +226,22 @@ int gm_params_load_subst(gm_params*, const char* path);
 int gm_batch_create(gm_index*, uint32_t max_reads /* <= 16 000 000 */, uint32_t max_len /* <= 2048 */, gm_batch** out);
 void gm_batch_destroy(gm_batch*);
 int gm_batch_upload(gm_batch*, const gm_params*, const gm_reads*, void* hip_stream);       /* host -> HBM */
+/* -A / --adaptor: trim adaptor sequence from the 3' end of every read of the blocks uploaded from now on.  Replaces the
+ * `if(g_adaptor) J=FixReads2(sequence)` of SeqReader::get_more_fastq (src/SeqReader.cpp:1146-1150) with FixReads2 (:1356-1372) and
+ * Compare (:1294-1305), as one device kernel (k_adaptor_trim) behind the copies of gm_batch_upload / gm_map_batch: a read keeps its
+ * first J characters, J = the smallest offset in [0, len - 4) where `(float)same / compared >= 0.85f` over min(|adaptor|, len - offset)
+ * raw, case-sensitive characters, or len - 4 when there is none (a read without any adaptor loses four bases: FixReads2 has no
+ * gMIN_CHOPPED_BASES guard).  Status, self score, -q, seeds, DP, CIGAR, coverage and the --illumina fallback scan see J characters;
+ * SEQ and QUAL of a SAM row stay the whole lines (:1264-1265): gm_output_batch_text prints gm_reads.len characters.  The string is
+ * used exactly as given (Driver.cpp:2793-2798), at most 256 characters (GM_E_ARG beyond); NULL or "" clears it.  Departure, where
+ * the reference's unsigned bound wraps: a read of fewer than 4 bases keeps 0.  Cost: one launch and one small read-back per upload,
+ * only while an adaptor is set. */
+int gm_batch_set_adaptor(gm_batch*, const char* adaptor);
+/* the lengths the kernels used for the block uploaded last (Read::length = J, SeqReader.cpp:1260): n values; gm_reads.len without an adaptor */
+int gm_batch_trimmed_len(gm_batch*, uint16_t* out);
+/* device time of k_adaptor_trim since the last call, measured with HIP events while gm_batch_set_profiling is on (it is not one of
+ * the GM_K_* kernels of gm_map_batch_device: it runs inside the upload) */
+int gm_batch_adaptor_time(gm_batch*, double* ms, uint64_t* launches);
 /* the hot path proper, everything resident in HBM: prep -> seed -> locate+vote -> NW -> hit compaction.
  * Asynchronous on hip_stream except for one 16-byte size read-back used to size the workspace. */
 int gm_map_batch_device(gm_index*, const gm_params*, gm_batch*, void* hip_stream);
@@ -286,6 +303,10 @@ int gm_dev_nw_score(gm_index*, const gm_params*, const gm_reads*, const uint32_t
 int gm_dev_traceback(gm_index*, const gm_params*, const gm_reads*, const uint32_t* read_idx, const uint8_t* strand,
                      const uint64_t* pos, uint32_t n, char* ops /* n x ops_stride, 'M','I','D', NUL padded */,
                      uint32_t ops_stride, uint16_t* ops_len);
+
+/* SeqReader::FixReads2 / Compare (src/SeqReader.cpp:1356-1372, 1294-1305) of every read of the block against `adaptor`, on the device:
+ * out_len[i] = the length read i keeps (see gm_batch_set_adaptor).  Only gm_reads.bases / len are read; NULL or "" copies len */
+int gm_dev_adaptor_trim(gm_index*, const gm_reads*, const char* adaptor, uint16_t* out_len);
 
 /* printf("%g") as the device prints XA / XP (gm_fmt_dev.h): out[16 i ..] holds len[i] characters, no terminator; len[i] = 0 for a
  * value outside the function's domain (0, -0, inf, nan, 2^-200 <= |v| < 2^200) */
