@@ -96,7 +96,8 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
            "gm_coverage_device_ptr", "gm_coverage_add", "gm_coverage_download", "gm_coverage_allreduce", "gm_coverage_write_sgr", "gm_coverage_enable_nuc", "gm_coverage_nuc_device_ptr",
            "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls",
-           "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim"]
+           "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim",
+           "gm_batch_set_read_format", "gm_index_set_probe_format"]
 
 
 def library_path():
@@ -173,6 +174,8 @@ def load_library():
     L.gm_batch_trimmed_len.argtypes = [C.c_void_p, C.c_void_p]
     L.gm_batch_adaptor_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(u64)]
     L.gm_dev_adaptor_trim.argtypes = [C.c_void_p, C.POINTER(gm_reads), C.c_char_p, C.c_void_p]
+    L.gm_batch_set_read_format.argtypes = [C.c_void_p, C.c_int]
+    L.gm_index_set_probe_format.argtypes = [C.c_void_p, C.c_int]
     _LIB = L
     return L
 
@@ -224,22 +227,27 @@ class Params:
         return getattr(self.c, k)
 
 
-def pack_reads(seqs, quals, stride=None):
-    """list of bytes -> (bases[n,stride] u8, quals[n,stride] u8, len[n] u16)"""
+def pack_reads(seqs, quals=None, stride=None):
+    """list of bytes -> (bases[n,stride] u8, quals[n,stride] u8, len[n] u16); quals=None (FASTA reads): the second array is None"""
     n = len(seqs)
     mx = max([len(s) for s in seqs] + [1])
     stride = stride or ((mx + 7) // 8) * 8
-    B = np.zeros((n, stride), np.uint8); Q = np.zeros((n, stride), np.uint8); Ln = np.zeros(n, np.uint16)
-    for i, (s, q) in enumerate(zip(seqs, quals)):
-        B[i, :len(s)] = np.frombuffer(s, np.uint8); Q[i, :len(s)] = np.frombuffer(q[:len(s)], np.uint8); Ln[i] = len(s)
+    B = np.zeros((n, stride), np.uint8); Q = None if quals is None else np.zeros((n, stride), np.uint8); Ln = np.zeros(n, np.uint16)
+    for i, s in enumerate(seqs):
+        B[i, :len(s)] = np.frombuffer(s, np.uint8); Ln[i] = len(s)
+        if quals is not None:
+            Q[i, :len(s)] = np.frombuffer(quals[i][:len(s)], np.uint8)
     return B, Q, Ln
 
 
 def _reads_struct(B, Q, Ln):
     r = gm_reads()
     r.n = B.shape[0]; r.stride = B.shape[1] if B.ndim == 2 else 0
-    r.bases = B.ctypes.data; r.quals = Q.ctypes.data; r.len = Ln.ctypes.data
+    r.bases = B.ctypes.data; r.quals = None if Q is None else Q.ctypes.data; r.len = Ln.ctypes.data
     return r
+
+
+GM_READS_FASTQ, GM_READS_FASTA = 0, 1
 
 
 class Index:
@@ -285,21 +293,29 @@ class Index:
         _chk(lib().gm_dev_locate(self.h, ranks.ctypes.data, len(ranks), int(use_full_sa), out.ctypes.data))
         return out
 
-    def dev_nw_score(self, params, B, Q, Ln, read_idx, strand, pos):
+    def _probe(self, fasta, call):
+        """run a unit probe with its gm_reads read as FASTA (Q is then not read) or FASTQ; the index goes back to FASTQ probes"""
+        _chk(lib().gm_index_set_probe_format(self.h, GM_READS_FASTA if fasta else GM_READS_FASTQ))
+        try:
+            _chk(call())
+        finally:
+            lib().gm_index_set_probe_format(self.h, GM_READS_FASTQ)
+
+    def dev_nw_score(self, params, B, Q, Ln, read_idx, strand, pos, fasta=False):
         r = _reads_struct(B, Q, Ln)
         read_idx = np.ascontiguousarray(read_idx, np.uint32); strand = np.ascontiguousarray(strand, np.uint8); pos = np.ascontiguousarray(pos, np.uint64)
         n = len(read_idx); score = np.zeros(n, np.float32); valid = np.zeros(n, np.uint8)
-        _chk(lib().gm_dev_nw_score(self.h, C.byref(params.c), C.byref(r), read_idx.ctypes.data, strand.ctypes.data, pos.ctypes.data, n,
-                                   score.ctypes.data, valid.ctypes.data))
+        self._probe(fasta, lambda: lib().gm_dev_nw_score(self.h, C.byref(params.c), C.byref(r), read_idx.ctypes.data, strand.ctypes.data, pos.ctypes.data, n,
+                                                         score.ctypes.data, valid.ctypes.data))
         return score, valid
 
-    def dev_traceback(self, params, B, Q, Ln, read_idx, strand, pos):
+    def dev_traceback(self, params, B, Q, Ln, read_idx, strand, pos, fasta=False):
         r = _reads_struct(B, Q, Ln)
         read_idx = np.ascontiguousarray(read_idx, np.uint32); strand = np.ascontiguousarray(strand, np.uint8); pos = np.ascontiguousarray(pos, np.uint64)
         n = len(read_idx); stride = 2 * B.shape[1] + 16
         ops = np.zeros((n, stride), np.uint8); ln = np.zeros(n, np.uint16)
-        _chk(lib().gm_dev_traceback(self.h, C.byref(params.c), C.byref(r), read_idx.ctypes.data, strand.ctypes.data, pos.ctypes.data, n,
-                                    ops.ctypes.data, stride, ln.ctypes.data))
+        self._probe(fasta, lambda: lib().gm_dev_traceback(self.h, C.byref(params.c), C.byref(r), read_idx.ctypes.data, strand.ctypes.data, pos.ctypes.data, n,
+                                                          ops.ctypes.data, stride, ln.ctypes.data))
         return [ops[i, :ln[i]].tobytes() for i in range(n)]
 
     def dev_pair_hmm(self, params, B, Q, Ln, read_idx, strand, pos):
@@ -423,9 +439,11 @@ class Batch:
         _chk(lib().gm_batch_adaptor_time(self.h, C.byref(ms), C.byref(ln)))
         return float(ms.value), int(ln.value)
 
-    def upload(self, params, B, Q, Ln, stream=None):
+    def upload(self, params, B, Q, Ln, stream=None, fasta=False):
+        """fasta=True: B holds the letters of FASTA reads (gm_batch_set_read_format), Q is not read (None will do)"""
         self._keep = (B, Q, Ln)
         r = _reads_struct(B, Q, Ln)
+        _chk(lib().gm_batch_set_read_format(self.h, GM_READS_FASTA if fasta else GM_READS_FASTQ))
         _chk(lib().gm_batch_upload(self.h, C.byref(params.c), C.byref(r), stream))
         self.n = B.shape[0]
 
@@ -463,11 +481,13 @@ class Batch:
             _chk(rc)
             return out[:got.value], status, self_score, top
 
-    def map(self, params, B, Q, Ln, stream=None):
-        """gm_map_batch: returns dict(status, self_score, top_score, denominator, match_begin, matches, positions)"""
+    def map(self, params, B, Q, Ln, stream=None, fasta=False):
+        """gm_map_batch: returns dict(status, self_score, top_score, denominator, match_begin, matches, positions).
+        fasta=True: B holds the letters of FASTA reads (gm_batch_set_read_format), Q is not read (None will do)"""
         n = B.shape[0]
         self._keep = (B, Q, Ln); self.n = n
         r = _reads_struct(B, Q, Ln)
+        _chk(lib().gm_batch_set_read_format(self.h, GM_READS_FASTA if fasta else GM_READS_FASTQ))
         status = np.zeros(n, np.int8); self_score = np.zeros(n, np.float32); top = np.zeros(n, np.float64); den = np.zeros(n, np.float64)
         mbegin = np.zeros(n + 1, np.uint64)
         mcap, pcap = 4 * n + 64, 8 * n + 64

@@ -121,6 +121,7 @@ struct gm_index {
     std::map<int, DevBuf> buckets;          // k-mer -> positions records (128 B per code; gm_bucket.hip), per T; empty DevBuf = tried, no room
     std::mutex mu;
     uint64_t hbm_bytes = 0;
+    int probe_format = GM_READS_FASTQ;      // gm_index_set_probe_format: how the unit probes read their gm_reads
 };
 
 struct gm_batch {
@@ -140,6 +141,8 @@ struct gm_batch {
         t_names, t_nameoff, t_qtail, t_qtailoff, t_slots, t_rowlen, t_rowoff, t_text, t_bad,     // gm_output_batch_text: the block's names, tails and row offsets, the text
         full_len, d_adaptor;            // -A: the lengths as uploaded (`len` then holds what k_adaptor_trim keeps), the adaptor's characters
     std::string adaptor;                // gm_batch_set_adaptor; empty = none (no launch, no copy, no wait in gm_batch_upload)
+    int read_format = GM_READS_FASTQ;   // gm_batch_set_read_format: the blocks uploaded from now on
+    bool fasta = false;                 // the block that is resident was uploaded as FASTA (GmDevBatch::fasta)
     bool adaptor_dirty = false;         // d_adaptor does not hold `adaptor` yet
     PinBuf h_top, h_hbegin, h_ord, h_post, h_mapq, h_emit, h_mhit, h_stat;      // h_stat: the small status words a phase reads back (page-locked: one short DMA)
     std::vector<double> h_exp;          // exp(score) of every accepted hit of the last gm_map_batch (reused by gm_output_batch)
@@ -273,6 +276,25 @@ extern "C" int gm_params_load_subst(gm_params* p, const char* path) {
 
 // Q -> (p, (1-p)/3) in fp32 exactly as SeqReader::get_more_fastq computes them (fp64 libm, then one cast):
 // Q2Prb_std src/SeqReader.cpp:623-627, Q2Prb_ill :618-622.  Negative p is stored as NaN.
+// the FASTA rows of SeqReader::get_more_fasta (src/SeqReader.cpp:875-979, cast to float at :996) as (p, q) by base mask: a row holds the
+// fp64 constant 1.0, 0.5, 1.0 / 3.0 or 0.25 at the 1, 2, 3 or 4 bases of its mask and 0.0 elsewhere.  Mask 0 (no IUPAC letter) is all zero.
+static void build_fasta_lut(float* lut /* 16 x 2 */) {
+    static const double by_count[5] = { 0.0, 1.0, 0.5, 1.0 / 3.0, 0.25 };
+    for (int m = 0; m < 16; ++m) { lut[2 * m] = (float)by_count[__builtin_popcount(m)]; lut[2 * m + 1] = (float)0.0; }
+}
+// str2qual (inc/SequenceOperations.h:193-217) of a FASTA row whose largest entry is pmax: the quality character a SAM row prints there
+static char fasta_qual_char(float pmax) {
+    const double MAX_PRB = 0.9999;
+    if (pmax > MAX_PRB) return (char)((-10 * log(1 - MAX_PRB) / log(10.)) + 33);
+    return (char)((-10 * log(1 - pmax) / log(10)) + 33);
+}
+// ... for the rows with 1, 2, 3, 4 bases in their mask, in bytes 0 .. 3 (GmDevText::fa_qual)
+static uint32_t fasta_qual_word() {
+    float l[32]; build_fasta_lut(l);
+    return (uint32_t)(uint8_t)fasta_qual_char(l[2 * 1]) | ((uint32_t)(uint8_t)fasta_qual_char(l[2 * 3]) << 8) | ((uint32_t)(uint8_t)fasta_qual_char(l[2 * 7]) << 16) |
+           ((uint32_t)(uint8_t)fasta_qual_char(l[2 * 15]) << 24);
+}
+
 static void build_lut(float* lut /* 512 x 2 */) {
     for (int which = 0; which < 2; ++which)
         for (int ch = 0; ch < 256; ++ch) {
@@ -289,9 +311,10 @@ static void build_lut(float* lut /* 512 x 2 */) {
 
 // want_bucket: the caller may use the bucket table of gm_bucket.hip (gm_map_batch_device): built on first use when it applies
 static int sync_params(gm_index* ix, const gm_params* p, GmDevParams& dp, hipStream_t st, bool want_bucket = false) {
-    std::vector<float> tab(256 * 4 + 512 * 2);
+    std::vector<float> tab(256 * 4 + GM_LUT_ENTRIES * 2);
     memcpy(tab.data(), p->S, sizeof(float) * 1024);
     build_lut(tab.data() + 1024);
+    build_fasta_lut(tab.data() + 1024 + 2 * GM_LUT_FASTA);
     // parameter tables are kept per CONTENT and never overwritten: batches of one index may run concurrently with different
     // gm_params (e.g. --illumina switched off from some block on) without one call rewriting what another call's kernels read
     const float* d_tab = nullptr;
@@ -620,7 +643,7 @@ static int ensure_batch_buffers(gm_batch* b, const gm_params* p) {
 
 static void fill_dev_batch(gm_batch* b) {
     GmDevBatch& d = b->dev;
-    d.n = b->n; d.stride = b->stride; d.max_seeds = b->max_seeds; d.illumina_until = b->illumina_until; d.read_base = 0;
+    d.n = b->n; d.stride = b->stride; d.max_seeds = b->max_seeds; d.illumina_until = b->illumina_until; d.read_base = 0; d.fasta = b->fasta ? 1u : 0u;
     d.bases = b->bases.as<uint8_t>(); d.quals = b->quals.as<uint8_t>(); d.len = b->len.as<uint16_t>();
     d.status = b->status.as<int8_t>(); d.self_score = b->self_score.as<float>(); d.min_score = b->min_score.as<double>();
     d.top_score = b->top_score.as<float>(); d.seeds = b->seeds.as<GmSeed>(); d.n_seeds = b->n_seeds.as<uint16_t>();
@@ -642,11 +665,15 @@ extern "C" int gm_batch_upload(gm_batch* b, const gm_params* p, const gm_reads* 
     if (!b || !p || !r || !p->finalized) return GM_E_ARG;
     if (r->n > b->max_reads || r->stride > 2048) { gm_set_error("batch larger than gm_batch_create allowed, or reads longer than 2048 bases"); return GM_E_ARG; }
     if (r->stride % 8 != 0) { gm_set_error("gm_reads.stride must be a multiple of 8"); return GM_E_ARG; }
+    const bool fasta = b->read_format == GM_READS_FASTA;
+    if (fasta && !b->adaptor.empty()) { gm_set_error("a FASTA block with an adaptor set: the reference trims FASTA reads with the PWM-based FixReads, which is not built (gm_batch_set_adaptor(NULL) first)"); return GM_E_UNSUPPORTED; }
+    if (r->n && (!r->bases || !r->len || (!fasta && !r->quals))) { gm_set_error("gm_reads: bases, len" + std::string(fasta ? "" : ", quals") + " must not be NULL"); return GM_E_ARG; }
     HIPCHK(hipSetDevice(b->ix->device));
     hipStream_t st = S_(stream);
     b->n = r->n; b->stride = r->stride; b->mapped = false; b->cache_hits = b->cache_matches = 0; b->resume_ptr = nullptr; b->stamp = 0;
+    b->fasta = fasta;
     size_t bytes = (size_t)r->n * r->stride;
-    if (b->bases.ensure(bytes + 16) || b->quals.ensure(bytes + 16) || b->len.ensure((size_t)r->n * 2 + 16)) return GM_E_NOMEM;
+    if (b->bases.ensure(bytes + 16) || (!fasta && b->quals.ensure(bytes + 16)) || b->len.ensure((size_t)r->n * 2 + 16)) return GM_E_NOMEM;
     b->len_host.assign(r->len, r->len + r->n);
     b->len_max = 0; b->len_min = r->n ? 0xFFFFFFFFu : 0u;
     for (uint32_t i = 0; i < r->n; ++i) {
@@ -657,7 +684,7 @@ extern "C" int gm_batch_upload(gm_batch* b, const gm_params* p, const gm_reads* 
     const bool trim = !b->adaptor.empty() && r->n != 0;
     if (bytes) {
         HIPCHK(hipMemcpyAsync(b->bases.p, r->bases, bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(b->quals.p, r->quals, bytes, hipMemcpyHostToDevice, st));
+        if (!fasta) HIPCHK(hipMemcpyAsync(b->quals.p, r->quals, bytes, hipMemcpyHostToDevice, st));      // (a FASTA block is its letters: half the bytes)
         if (!trim) HIPCHK(hipMemcpyAsync(b->len.p, r->len, (size_t)r->n * 2, hipMemcpyHostToDevice, st));
     }
     if (trim) {
@@ -682,7 +709,7 @@ extern "C" int gm_batch_upload(gm_batch* b, const gm_params* p, const gm_reads* 
     // --illumina with automatic fallback (SeqReader.cpp:1171-1180): reads before the first one that shows a
     // quality below '@' keep Phred+64, that read and all later ones use Phred+33 (with -A only the kept characters are looked at, :1152)
     b->illumina_until = 0;
-    if (p->illumina) {
+    if (p->illumina && !fasta) {                                   // (--illumina is accepted and ignored for FASTA, as in the reference)
         uint32_t until = r->n;
         for (uint32_t i = 0; i < r->n && until == r->n; ++i) {
             const uint8_t* q = r->quals + (size_t)i * r->stride;
@@ -704,6 +731,34 @@ extern "C" int gm_batch_set_adaptor(gm_batch* b, const char* adaptor) {
     b->adaptor.assign(adaptor ? adaptor : "", n);
     b->adaptor_dirty = n != 0;
     return GM_OK;
+}
+
+// which of SeqReader::find_type's formats (src/SeqReader.cpp:175-244) the blocks uploaded from now on are in
+extern "C" int gm_batch_set_read_format(gm_batch* b, int format) {
+    if (!b) { gm_set_error("gm_batch_set_read_format: batch is NULL"); return GM_E_ARG; }
+    if (format != GM_READS_FASTQ && format != GM_READS_FASTA) { gm_set_error("gm_batch_set_read_format: GM_READS_FASTQ or GM_READS_FASTA"); return GM_E_ARG; }
+    b->read_format = format;
+    return GM_OK;
+}
+
+extern "C" int gm_index_set_probe_format(gm_index* ix, int format) {
+    if (!ix) { gm_set_error("gm_index_set_probe_format: index is NULL"); return GM_E_ARG; }
+    if (format != GM_READS_FASTQ && format != GM_READS_FASTA) { gm_set_error("gm_index_set_probe_format: GM_READS_FASTQ or GM_READS_FASTA"); return GM_E_ARG; }
+    ix->probe_format = format;
+    return GM_OK;
+}
+
+// a kernel form that only an A/B switch selects and that was not taught FASTA blocks: the DP score kernel k_nw.  Such a block with the
+// switch set is refused, by name.  (GM_PREP=tile and GM_TRACEBACK=group are no such forms: k_prep and k_traceback are what blocks with
+// rows beyond 152 / 511 bytes take, FASTA included.)
+// Every way into gmk_nw passes here first: gm_map_batch_device (before its pipelined and its single-pass form) and gm_dev_nw_score;
+// gmk_nw itself fails the launch for a FASTA block in the wave form, should a new caller forget.
+static int fasta_forced_form(const gm_batch* b) {
+    if (!b->fasta) return GM_OK;
+    const char* sw = gm_opt_is("GM_NW", "wave") ? "GM_NW=wave" : nullptr;
+    if (!sw) return GM_OK;
+    gm_set_error(std::string("a FASTA block with ") + sw + ": that kernel form takes FASTQ blocks only (unset the switch)");
+    return GM_E_UNSUPPORTED;
 }
 
 extern "C" int gm_batch_trimmed_len(gm_batch* b, uint16_t* out) {
@@ -793,7 +848,7 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
         HIPCHK(hipMemcpyAsync(ctr, view[i].counters, sizeof ctr, hipMemcpyDeviceToHost, ss));
         HIPCHK(hipMemcpyAsync(shard_host.data(), view[i].shard_cnt, shard_bytes, hipMemcpyDeviceToHost, ss));
         HIPCHK(hipStreamSynchronize(ss));
-        if (ctr[GMK_BAD_QUAL]) { gm_set_error("Invalid Fastq Character? (negative base probability)"); return GM_E_BAD_QUAL; }
+        if (ctr[GMK_BAD_QUAL] && !b->fasta) { gm_set_error("Invalid Fastq Character? (negative base probability)"); return GM_E_BAD_QUAL; }
         auto tally = [&](uint64_t& total, uint32_t& mx) { total = 0; mx = 0; for (int q = 0; q < GM_NSHARD; ++q) { uint32_t c = shard_host[(size_t)q * GM_SHARD_STRIDE]; total += c; mx = std::max(mx, c); } };
         uint64_t total; uint32_t mx;
         tally(total, mx);
@@ -810,7 +865,7 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
         }
         if (mx > region) { overflow = true; return GM_OK; }
         ncand[i] = (uint32_t)total;
-        { KTimer t(b, GM_K_NW, ss); KCHK(gmk_nw(ix->dev, dp, view[i], ncand[i], (b->len_min == b->len_max && !ctr[GMK_HIGH_QUAL]) ? b->len_max : 0u, gm_qual_lo(ctr), gm_qual_hi(ctr), ss)); }
+        { KTimer t(b, GM_K_NW, ss); KCHK(gmk_nw(ix->dev, dp, view[i], ncand[i], (b->len_min == b->len_max && (b->fasta || !ctr[GMK_HIGH_QUAL])) ? b->len_max : 0u, gm_qual_lo(ctr), gm_qual_hi(ctr), ss)); }
         return GM_OK;
     };
     uint32_t next_finish = 0;
@@ -861,6 +916,7 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     int rc = sync_params(ix, p, dp, st, true);
     if (rc) return rc;
     b->mapped = false;
+    if ((rc = fasta_forced_form(b)) != GM_OK) return rc;
     if (b->n == 0) { b->n_cands = 0; b->n_raw = 0; b->mapped = true; memset(b->counters_host, 0, sizeof b->counters_host); return GM_OK; }
     const int use_full = ix->full_sa ? 1 : 0;
     // which vote kernel: expected SA hits per seed ~ reference length / 4^mer (capped by -h), expected seeds per strand from the
@@ -956,7 +1012,7 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
                  : use_bucket ? (bucket_reg <= 8 ? "k_vote_bucket<2>" : bucket_reg <= 16 ? "k_vote_bucket<4>" : bucket_reg <= 24 ? "k_vote_bucket<6>" : "k_vote_bucket<8>")
                             : dense == 0 ? "sparse" : dense == 3 ? "k_vote_block" : dense == 2 ? (slots_pp ? "k_vote_slots_pp<64>" : "k_vote_slots<64>") : slots_hint == 0 ? "k_vote_tiny" : slots_hint < 0 ? "k_vote_tiny2" : slots_pp ? "k_vote_slots_pp" : "k_vote_slots",
                  use_full ? "full-SA" : "sampled-SA");
-        b->path = buf;
+        b->path = std::string("reads=") + (b->fasta ? "fasta " : "fastq ") + buf;
         GM_TRACE("path: %s", buf);
     }
     fill_dev_batch(b);
@@ -1087,7 +1143,7 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
                             "filter2 %.0f, table %.0f, emit %.0f\n", ctr[GMK_DBG8], ctr[GMK_DBG0] / ns, ctr[GMK_DBG1] / ns, ctr[GMK_DBG2] / ns, ctr[GMK_DBG3] / ns, ctr[GMK_DBG4] / ns,
                     ctr[GMK_DBG5] / ns, ctr[GMK_DBG6] / ns, ctr[GMK_DBG7] / ns);
         }
-        if (ctr[GMK_BAD_QUAL]) { gm_set_error("Invalid Fastq Character? (negative base probability)"); return GM_E_BAD_QUAL; }
+        if (ctr[GMK_BAD_QUAL] && !b->fasta) { gm_set_error("Invalid Fastq Character? (negative base probability)"); return GM_E_BAD_QUAL; }
         uint32_t n_retry = small[1];
         if (n_retry && mx <= b->dev.cand_region) {
             size_t slots = (size_t)ctr[GMK_HEAVY_SLOTS];
@@ -1153,7 +1209,7 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     if (b->raw_hits.ensure(b->raw_cap * sizeof(GmRawHit))) return GM_E_NOMEM;
     fill_dev_batch(b);
     // one read length in the block and no quality character above 127 (k_prep counted them): the DP kernel with the rows in DP order
-    const uint32_t nw_rows_len = (b->len_min == b->len_max && ctr[GMK_HIGH_QUAL] == 0) ? b->len_max : 0u;
+    const uint32_t nw_rows_len = (b->len_min == b->len_max && (b->fasta || ctr[GMK_HIGH_QUAL] == 0)) ? b->len_max : 0u;      // (a FASTA block has no quality characters)
     b->path += std::string(" nw=") + gmk_nw_form(dp, b->dev, b->n_cands, nw_rows_len, gm_qual_lo(ctr), gm_qual_hi(ctr));
     { KTimer t(b, GM_K_NW, st); KCHK(gmk_nw(ix->dev, dp, b->dev, b->n_cands, nw_rows_len, gm_qual_lo(ctr), gm_qual_hi(ctr), st)); }
     { KTimer t(b, GM_K_COMPACT, st); KCHK(gmk_compact(b->dev, st)); }
@@ -1556,6 +1612,8 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
         bool asc = rt->names && rt->name_off && (rt->qual_tail != nullptr) == (rt->qual_tail_off != nullptr);
         for (uint32_t i = 0; asc && i < n; ++i) asc = rt->name_off[i] <= rt->name_off[i + 1] && (!rt->qual_tail_off || rt->qual_tail_off[i] <= rt->qual_tail_off[i + 1]);
         if (!asc) { gm_set_error("gm_read_text: names / name_off missing, qual_tail without qual_tail_off (or the reverse), or offsets that do not ascend"); return GM_E_ARG; }
+        // a FASTA record has no quality line: QUAL is str2qual's string, one character per base, and nothing can follow it
+        if (b->fasta && rt->qual_tail_off) { gm_set_error("gm_read_text: qual_tail / qual_tail_off must be NULL for a FASTA block (its QUAL is synthesised, one character per base)"); return GM_E_ARG; }
     }
     HIPCHK(hipSetDevice(ix->device));
     hipStream_t st = S_(stream);
@@ -1594,6 +1652,7 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
     }
     const uint32_t ops_words = gm_ops_words(b->stride), codes_stride = 32u * ops_words;
     const bool snp = p->mode == GM_MODE_SNP;
+    if (snp && b->fasta) { gm_set_error("GM_MODE_SNP with a FASTA block: the pair HMM of --snp takes FASTQ blocks only"); return GM_E_UNSUPPORTED; }
     if (snp && !ix->nuc_on) { gm_set_error("GM_MODE_SNP deposits into the per-nucleotide tracks: call gm_coverage_enable_nuc first"); return GM_E_ARG; }
     const bool nuc = p->mode != GM_MODE_NORMAL && !snp && ix->nuc_on;
     if (b->g_matches.ensure((size_t)n_m * sizeof(GmDevMatch)) || b->g_positions.ensure((size_t)(n_p + 1) * sizeof(GmDevPos)) ||
@@ -1730,6 +1789,7 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
             t.slots = b->t_slots.as<uint8_t>(); t.row_len = b->t_rowlen.as<uint32_t>(); t.row_off = b->t_rowoff.as<uint64_t>();
             t.inv_adjust = 1.0 / p->adjust; t.bad = b->t_bad.as<unsigned long long>();
             t.seq_len = b->adaptor.empty() ? b->dev.len : b->full_len.as<uint16_t>();
+            t.fa_qual = fasta_qual_word();
             KCHK(gmk_out_text_sizes(b->dev, t, st));
             KCHK(gmk_scan_u32(t.row_len, n_recs, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
             uint64_t text_len = 0; unsigned long long bad = ~0ull;
@@ -1931,11 +1991,13 @@ extern "C" int gm_dev_locate(gm_index* ix, const uint64_t* ranks, uint32_t n, in
     return GM_OK;
 }
 
-static int unit_batch(gm_index* ix, const gm_params* p, const gm_reads* reads, gm_batch** bo, GmDevParams& dp) {
+static int unit_batch(gm_index* ix, const gm_params* p, const gm_reads* reads, gm_batch** bo, GmDevParams& dp, bool nw_probe = false) {
     gm_batch* b = nullptr;
     int rc = gm_batch_create(ix, reads->n ? reads->n : 1, reads->stride ? reads->stride : 1, &b);
     if (rc) return rc;
+    b->read_format = ix->probe_format;                   // gm_index_set_probe_format
     rc = gm_batch_upload(b, p, reads, nullptr);
+    if (!rc && nw_probe) rc = fasta_forced_form(b);            // (the DP score kernel runs for gm_dev_nw_score only)
     if (!rc) rc = sync_params(ix, p, dp, nullptr);
     if (!rc) {
         if (hipMemsetAsync(b->counters.p, 0, GMK_N * 8, nullptr) != hipSuccess || hipMemsetAsync(b->small.p, 0, 64, nullptr) != hipSuccess ||
@@ -1952,7 +2014,7 @@ extern "C" int gm_dev_nw_score(gm_index* ix, const gm_params* p, const gm_reads*
     if (ix->host_only) return GM_E_NO_DEVICE;
     HIPCHK(hipSetDevice(ix->device));
     gm_batch* b; GmDevParams dp;
-    int rc = unit_batch(ix, p, reads, &b, dp);
+    int rc = unit_batch(ix, p, reads, &b, dp, true);
     if (rc) return rc;
     std::vector<GmCand> c(n);
     for (uint32_t i = 0; i < n; ++i) {
@@ -1968,9 +2030,9 @@ extern "C" int gm_dev_nw_score(gm_index* ix, const gm_params* p, const gm_reads*
         if (hipMemset(b->shards.p, 0, (size_t)GM_NSHARD * GM_SHARD_STRIDE * 4) != hipSuccess) { rc = GM_E_HIP; break; }
         if (hipMemcpy(b->shards.p, &n, 4, hipMemcpyHostToDevice) != hipSuccess) { rc = GM_E_HIP; break; }
         uint32_t rows_len = (b->len_min == b->len_max) ? b->len_max : 0u;          // (no k_prep here: the quality characters are looked at on the host)
-        for (size_t q = 0; q < (size_t)reads->n * reads->stride && rows_len; ++q) if (reads->quals[q] >= 128) rows_len = 0;
+        for (size_t q = 0; q < (size_t)reads->n * reads->stride && rows_len && !b->fasta; ++q) if (reads->quals[q] >= 128) rows_len = 0;
         uint32_t qlo = 255, qhi = 0;
-        for (uint32_t r = 0; r < reads->n; ++r)
+        for (uint32_t r = 0; r < reads->n && !b->fasta; ++r)
             for (uint32_t i = 0; i < reads->len[r] && i < reads->stride; ++i) { const uint32_t qc = reads->quals[(size_t)r * reads->stride + i]; qlo = std::min(qlo, qc); qhi = std::max(qhi, qc); }
         if (gmk_nw(ix->dev, dp, b->dev, n, rows_len, qlo, qhi, nullptr)) { rc = GM_E_HIP; break; }
         if (n && hipMemcpy(c.data(), b->cands.p, (size_t)n * sizeof(GmCand), hipMemcpyDeviceToHost) != hipSuccess) { rc = GM_E_HIP; break; }
@@ -2021,6 +2083,7 @@ extern "C" int gm_dev_pair_hmm(gm_index* ix, const gm_params* p, const gm_reads*
     if (ix->host_only) return GM_E_NO_DEVICE;
     HIPCHK(hipSetDevice(ix->device));
     gm_batch* b; GmDevParams dp;
+    if (ix->probe_format == GM_READS_FASTA) { gm_set_error("gm_dev_pair_hmm: the pair HMM of --snp takes FASTQ reads only"); return GM_E_UNSUPPORTED; }
     int rc = unit_batch(ix, p, reads, &b, dp);
     if (rc) return rc;
     std::vector<GmCand> c(n);

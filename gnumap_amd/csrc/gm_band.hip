@@ -20,14 +20,14 @@ namespace {
 
 __device__ __forceinline__ uint32_t gb_nt4(uint32_t ch) { uint32_t u = ch & 0xDFu; return u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : u == 'T' ? 3u : 4u; }
 
-__device__ __forceinline__ float gb_get_val(uint32_t code, float p, float q, const float* s) {     // get_val src/bin_seq.cpp:975-987, no FMA
-    float r0 = code == 0 ? p : q, r1 = code == 1 ? p : q, r2 = code == 2 ? p : q, r3 = code == 3 ? p : q;
+__device__ __forceinline__ float gb_get_val_mask(uint32_t mask, float p, float q, const float* s) {     // get_val src/bin_seq.cpp:975-987, no FMA; row k = mask bit k ? p : q
+    float r0 = (mask & 1u) ? p : q, r1 = (mask & 2u) ? p : q, r2 = (mask & 4u) ? p : q, r3 = (mask & 8u) ? p : q;
     float a = __fadd_rn(__fmul_rn(r0, s[0]), __fmul_rn(r1, s[1]));
     a = __fadd_rn(a, __fmul_rn(r2, s[2]));
     a = __fadd_rn(a, __fmul_rn(r3, s[3]));
     return a;
 }
-
+__device__ __forceinline__ float gb_get_val(uint32_t code, float p, float q, const float* s) { return gb_get_val_mask(code < 4u ? 1u << code : 0u, p, q, s); }
 __device__ __forceinline__ uint32_t gb_pos2rid(const uint32_t* coff, uint32_t n_seqs, uint32_t pos) {
     uint32_t lo = 0, hi = n_seqs - 1;
     while (lo < hi) { uint32_t mid = (lo + hi + 1) >> 1; if (pos >= coff[mid]) lo = mid; else hi = mid - 1; }
@@ -44,7 +44,16 @@ __device__ __forceinline__ uint32_t gb_ref(const uint8_t* pac, uint32_t g) { ret
 // PWM row i of the read in strand orientation against the four reference bases (reverse_comp_cpy SequenceOperations.h:149-161)
 __device__ __forceinline__ void gb_row(const GmDevBatch& b, const float2* lut, const float (*sg)[4], uint32_t r, uint32_t L, uint32_t strand, uint32_t i, float* v4) {
     const uint32_t src = strand ? L - 1u - i : i;
-    const uint32_t ch = b.bases[(size_t)r * b.stride + src], qc = b.quals[(size_t)r * b.stride + src];
+    const uint32_t ch = b.bases[(size_t)r * b.stride + src];
+    if (b.fasta) {                                      // the letter's row (get_more_fasta): base mask, (p, q) by mask; `lut` is the caller's FASTA table
+        uint32_t mask = gm_iupac_mask(ch);
+        if (strand) mask = gm_mask_rc(mask);
+        const float2 pq = lut[mask];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) v4[g] = gb_get_val_mask(mask, pq.x, pq.y, sg[g]);
+        return;
+    }
+    const uint32_t qc = b.quals[(size_t)r * b.stride + src];
     uint32_t code = gb_nt4(ch);
     if (strand && code < 4) code = 3 - code;
     const float2 pq = lut[qc];
@@ -85,7 +94,7 @@ __global__ void __launch_bounds__(GB_NT) k_nw_band(GmDevIndex ix, GmDevParams p,
         const bool ok = gb_window_ok(ix, c.b, L);
         float result = 0.0f;
         if (ok && p.nw) {
-            const float2* lut = p.lut + ((r < b.illumina_until) ? 256 : 0);
+            const float2* lut = p.lut + (b.fasta ? GM_LUT_FASTA : (r < b.illumina_until) ? 256u : 0u);
             const int end = (int)L;
             int cur = 0;                                                    // s_row[cur] = row i + 1 while row i is computed into s_row[cur ^ 1]
             // row `end`: nm[end][j] = gGAP * (end - j) for the last G + 2 columns (bin_seq.cpp:805-808); offset = j - i + G + 1
@@ -148,7 +157,7 @@ __global__ void __launch_bounds__(GB_NT) k_traceback_band(GmDevIndex ix, GmDevPa
         uint16_t outlen = 0;
         uint32_t ctext = 1;                                                 // "*" when there is no path
         if (ok) {
-            const float2* lut = p.lut + ((r < b.illumina_until) ? 256 : 0);
+            const float2* lut = p.lut + (b.fasta ? GM_LUT_FASTA : (r < b.illumina_until) ? 256u : 0u);
             const int N = (int)L;
             int cur = 0;
             // row 0: nm[0][j] = gGAP * j ('L') for j <= G + 1 (bin_seq.cpp:503-511); offset = j - i + G + 1

@@ -117,14 +117,27 @@ __device__ __forceinline__ uint32_t gm_locate_walk(const GmDevIndex& ix, uint32_
     return sa + ix.sa_samples[k >> ix.sa_shift];
 }
 
-// bin_seq::get_val src/bin_seq.cpp:975-987 with the PWM row given as (called base, p, q)
-__device__ __forceinline__ float gm_get_val(uint32_t code, float p, float q, const float* s) {
-    float r0 = code == 0 ? p : q, r1 = code == 1 ? p : q, r2 = code == 2 ? p : q, r3 = code == 3 ? p : q;
+// A PWM row as (4-bit base mask, p, q): r_k = mask bit k ? p : q (bit 0 = A .. bit 3 = T).  A FASTQ position is the one-hot mask of its
+// called base (0 for N and every other character) with (p, q) from the quality LUT; a FASTA position is its IUPAC letter's mask
+// (get_more_fasta, SeqReader.cpp:884-950) with (p, q) = lut[GM_LUT_FASTA + mask].  The minus strand reads reverse_comp_cpy's row
+// (SequenceOperations.h:149-161): A<->T, C<->G = the mask's four bits in reverse order.
+// (gm_mask_rc, gm_code_mask, gm_iupac_mask: gm_internal.h - gm_band.hip and gm_output.hip use them too)
+// the mask of read character ch of a FASTQ (fasta = 0) or FASTA block, in the orientation of `strand`
+__device__ __forceinline__ uint32_t gm_row_mask(uint32_t fasta, uint32_t ch, uint32_t strand) {
+    const uint32_t m = fasta ? gm_iupac_mask(ch) : gm_code_mask(gm_nt4(ch));
+    return strand ? gm_mask_rc(m) : m;
+}
+
+// bin_seq::get_val src/bin_seq.cpp:975-987 with the PWM row given as (base mask, p, q): ((r0 s0 + r1 s1) + r2 s2) + r3 s3, fp32, no contraction
+__device__ __forceinline__ float gm_get_val_mask(uint32_t mask, float p, float q, const float* s) {
+    float r0 = (mask & 1u) ? p : q, r1 = (mask & 2u) ? p : q, r2 = (mask & 4u) ? p : q, r3 = (mask & 8u) ? p : q;
     float a = __fadd_rn(__fmul_rn(r0, s[0]), __fmul_rn(r1, s[1]));
     a = __fadd_rn(a, __fmul_rn(r2, s[2]));
     a = __fadd_rn(a, __fmul_rn(r3, s[3]));
     return a;
 }
+// ... as (called base 0 .. 3 or 4 = none, p, q)
+__device__ __forceinline__ float gm_get_val(uint32_t code, float p, float q, const float* s) { return gm_get_val_mask(gm_code_mask(code), p, q, s); }
 
 // bin_seq::max_flt src/bin_seq.cpp:1013-1026
 __device__ __forceinline__ float gm_max3(float a, float b, float c) {

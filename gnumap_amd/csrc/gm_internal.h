@@ -42,13 +42,32 @@ struct GmDevParams {
     const uint2* kmer_tab;          // SA interval of every kmer_T-mer (suffix of the seed k-mer), or null: {k,l}; empty = {0xFFFFFFFF, depth}
     int kmer_T;
     const uint4* kmer_ctab;         // compact form of kmer_tab, 16 B per 8 consecutive codes: {first SA rank, 8 x u8 hit counts (2 words), escape flag}; null = not built
-    const float2* lut;              // [0..255] Phred+33, [256..511] Phred+64: (p, (1-p)/3) as fp32; p = NaN when negative
+    const float2* lut;              // [0..255] Phred+33, [256..511] Phred+64: (p, (1-p)/3) as fp32; p = NaN when negative;
+                                    // [512..527] FASTA blocks: (in-mask, out-of-mask) probability of a row by its 4-bit base mask (GM_LUT_FASTA)
     const uint4* bucket;            // direct-addressed k-mer -> positions table (gm_bucket.hip): 128 bytes per mer-mer code, or null
     uint32_t bucket_ecap, bucket_ovcap;   // k_vote_bucket votes itself on a strand with at most this many SA hits / seeds beyond 28 hits; more -> list kernel
     int bucket_T, bucket_ctx;       // the table's k-mer length; 1 = context records: seeds of bucket_T + 1 .. bucket_T + 5 characters (k_build_bucket_ctx)
 };
 
+#define GM_LUT_FASTA 512u         // GmDevParams::lut: where the 16 (p, q) pairs of the FASTA rows start
+#define GM_LUT_ENTRIES 528u
+
 struct GmSeed { uint32_t k, l, pos; };
+
+#if defined(__HIPCC__)
+// base masks of PWM rows (bit 0 = A .. bit 3 = T), for every kernel translation unit; see gm_get_val_mask (gm_device.h)
+__device__ __forceinline__ uint32_t gm_mask_rc(uint32_t m) { return ((m & 1u) << 3) | ((m & 2u) << 1) | ((m & 4u) >> 1) | ((m & 8u) >> 3); }
+__device__ __forceinline__ uint32_t gm_code_mask(uint32_t code) { return code < 4u ? 1u << code : 0u; }
+// letters a .. z (either case) -> mask, 4 bits each: a 1, b 14, c 2, d 13, g 4, h 11, k 12, m 3, n 15, r 5, s 6, t 8, v 7, w 9, y 10;
+// every other byte 0 (the host refuses such a file; here it is a row of four q)
+__device__ __forceinline__ uint32_t gm_iupac_mask(uint32_t ch) {
+    const uint32_t l = (ch | 0x20u) - 'a';                          // 0 .. 25 for a letter
+    const unsigned long long lo = 0x00F30C00B400D2E1ull;            // a .. p (a = bits 0..3)
+    const unsigned long long hi = 0x0000000A09708650ull;            // q .. z (q = bits 0..3)
+    const uint32_t m = l < 16u ? (uint32_t)(lo >> (4u * l)) : (uint32_t)(hi >> (4u * (l & 15u)));
+    return (l < 26u && (ch & 0xC0u) == 0x40u) ? (m & 15u) : 0u;
+}
+#endif
 
 #define GM_FIXED_C 4
 // own candidate slots of read x strand rs, in blocks of 64 read x strands: the 64 slots 0 side by side (what k_cand_gather reads of
@@ -85,6 +104,8 @@ enum {
 struct GmDevBatch {
     uint32_t n, stride, max_seeds, illumina_until;
     uint32_t read_base;             // index of read 0 of this (sub-)batch in the caller's batch (raw hits carry absolute indices)
+    uint32_t fasta;                 // 1 = a FASTA block (gm_batch_set_read_format): `bases` holds the file's letters, a position's PWM row is its
+                                    // IUPAC letter's (get_more_fasta, SeqReader.cpp:875-979: base mask + lut[GM_LUT_FASTA + mask]); `quals` is not read
     const uint8_t* bases;
     const uint8_t* quals;
     const uint16_t* len;
@@ -153,6 +174,7 @@ struct GmDevText {
     double inv_adjust;                              // 1.0 / gADJUST: XA is printed rescaled
     unsigned long long* bad;                        // smallest record whose XA / XP lies outside gm_put_g6_hd's domain (~0: none)
     const uint16_t* seq_len;                        // characters of SEQ / QUAL a row prints: the block's lengths as uploaded (with -A the whole line, not the kept part)
+    uint32_t fa_qual;                               // FASTA blocks: str2qual's character of a row with 1, 2, 3, 4 bases in its mask, in bytes 0 .. 3
 };
 
 // gm_snp_rec (layout asserted in gm_api.cpp): a row of --snp's .gmp that carries a 'Y' call, written by k_snp_gather (gm_snpcall.hip)

@@ -174,11 +174,14 @@ __global__ void __launch_bounds__(256) k_prep(GmDevIndex ix, GmDevParams p, GmDe
     }
     for (int e = threadIdx.x; e < 2 * 9 * 128; e += 256) {
         const int tab = e / (9 * 128), cl = (e / 128) % 9, qc = e & 127;
-        const int ch = cl < 8 ? "ACGTacgt"[cl] : 'N';
-        const float2 pq = p.lut[tab * 256 + qc];
+        // FASTA block: one term per raw character (S's row of it dotted with the letter's PWM row), looked up with the character in the
+        // quality's place - see k_prep_rows
+        const int ch = b.fasta ? (cl < 8 ? "ACGTacgt"[cl] : qc) : (cl < 8 ? "ACGTacgt"[cl] : 'N');
+        const uint32_t mask = b.fasta ? gm_iupac_mask((uint32_t)ch) : gm_code_mask(gm_nt4((uint32_t)ch));
+        const float2 pq = b.fasta ? p.lut[GM_LUT_FASTA + mask] : p.lut[tab * 256 + qc];
         const float4 sv = S4[ch];
         const float sarr[4] = { sv.x, sv.y, sv.z, sv.w };
-        s_term[tab][cl][qc] = gm_get_val(gm_nt4((uint32_t)ch), pq.x, pq.y, sarr);
+        s_term[tab][cl][qc] = gm_get_val_mask(mask, pq.x, pq.y, sarr);
     }
     // a lane walking its own row with 8-byte loads pulls a whole 128-byte line per load and finds it evicted by the next one
     // (measured: 13 x the useful HBM traffic).  So the 256 reads of a tile are staged into LDS with coalesced 16-byte loads.
@@ -197,6 +200,7 @@ __global__ void __launch_bounds__(256) k_prep(GmDevIndex ix, GmDevParams p, GmDe
     __syncthreads();                                 // the previous tile (and the tables) are done with
 #pragma unroll
     for (int which = 0; which < 2 && staged; ++which) {
+        if (which && b.fasta) break;                 // (a FASTA block has no quality rows)
         const unsigned char* src = (which ? b.quals : b.bases) + (size_t)r0 * b.stride;
         unsigned char* dst = which ? s_q : s_b;
         if ((((size_t)src) & 15) == 0) {
@@ -213,11 +217,11 @@ __global__ void __launch_bounds__(256) k_prep(GmDevIndex ix, GmDevParams p, GmDe
     if (threadIdx.x < TR && r < b.n) {
         uint32_t L = b.len[r];
         const uint8_t* rb = staged ? s_b + (size_t)threadIdx.x * b.stride : b.bases + (size_t)r * b.stride;
-        const uint8_t* rq = staged ? s_q + (size_t)threadIdx.x * b.stride : b.quals + (size_t)r * b.stride;
+        const uint8_t* rq = b.fasta ? rb : staged ? s_q + (size_t)threadIdx.x * b.stride : b.quals + (size_t)r * b.stride;      // (FASTA: the letters stand in the qualities' place)
         const int tab = (r < b.illumina_until) ? 1 : 0;
         const float2* lut = p.lut + tab * 256;
         const float (*term)[128] = s_term[tab];
-        const bool uni = s_other_uniform != 0;
+        const bool uni = b.fasta || s_other_uniform != 0;
         int8_t st = 0;
         float self = 0.0f;
         double mn;
@@ -233,7 +237,7 @@ __global__ void __launch_bounds__(256) k_prep(GmDevIndex ix, GmDevParams p, GmDe
             for (uint32_t t = 0; t < 8; ++t) {
                 if (i0 + t < L) {
                     uint32_t ch = ((t < 4 ? bw.x : bw.y) >> ((t & 3) * 8)) & 255u;
-                    uint32_t qc = ((t < 4 ? qw.x : qw.y) >> ((t & 3) * 8)) & 255u;
+                    uint32_t qc = ((t < 4 ? qw.x : qw.y) >> ((t & 3) * 8)) & (b.fasta ? 127u : 255u);
                     const uint32_t cl = s_cls[ch];
                     if (prow) { pk |= (cl & 3u) << (((i0 & 8u) + t) << 1); any_n |= cl >> 3; }
                     float v;
@@ -2504,7 +2508,7 @@ __device__ __forceinline__ GmNwLds gm_nw_lds(unsigned char* raw, uint32_t Lp, ui
 __device__ __forceinline__ void gm_stage(const GmDevIndex& ix, const GmDevBatch& b, uint16_t* rows, uint8_t* win,
                                          uint32_t r, uint32_t strand, uint32_t L, uint32_t b0, int d) {
     const uint8_t* rb = b.bases + (size_t)r * b.stride;
-    const uint8_t* rq = b.quals + (size_t)r * b.stride;
+    const uint8_t* rq = b.fasta ? rb : b.quals + (size_t)r * b.stride;    // (FASTA: no quality rows)
     for (uint32_t o = (uint32_t)d * 8; o < L; o += 64) {                  // rows are 8-byte aligned
         const uint2 bw = *reinterpret_cast<const uint2*>(rb + o);
         const uint2 qw = *reinterpret_cast<const uint2*>(rq + o);
@@ -2514,9 +2518,9 @@ __device__ __forceinline__ void gm_stage(const GmDevIndex& ix, const GmDevBatch&
             if (src < L) {
                 uint32_t ch = ((t < 4 ? bw.x : bw.y) >> ((t & 3) * 8)) & 255u;
                 uint32_t qc = ((t < 4 ? qw.x : qw.y) >> ((t & 3) * 8)) & 255u;
-                uint32_t code = gm_nt4(ch);
-                if (strand && code < 4) code = 3 - code;
-                rows[strand ? L - 1 - src : src] = (uint16_t)((code << 8) | qc);   // reverse_comp_cpy SequenceOperations.h:149-161
+                // the row as (base mask, index of its (p, q) in the staged LUT): the quality character, or for a FASTA block the mask itself
+                const uint32_t mask = gm_row_mask(b.fasta, ch, strand);             // reverse_comp_cpy SequenceOperations.h:149-161
+                rows[strand ? L - 1 - src : src] = (uint16_t)((mask << 8) | (b.fasta ? mask : qc));
             }
         }
     }
@@ -2581,7 +2585,7 @@ __global__ void __launch_bounds__(256) k_nw(GmDevIndex ix, GmDevParams p, GmDevB
             if (icur >= imin) {
                 uint32_t row = rows[icur];
                 float2 pq = lut[row & 255u];
-                vcur = gm_get_val(row >> 8, pq.x, pq.y, S.sg + 4 * win[icur + delta]);
+                vcur = gm_get_val_mask(row >> 8, pq.x, pq.y, S.sg + 4 * win[icur + delta]);
             }
             for (int s = 2 * Lw - 2; s >= 0; --s) {
                 float a = gm_from_prev_lane(own);         // diagonal delta-1, cell (i+1, j)
@@ -2599,7 +2603,7 @@ __global__ void __launch_bounds__(256) k_nw(GmDevIndex ix, GmDevParams p, GmDevB
                     if (icur >= imin) {
                         uint32_t row = rows[icur];
                         float2 pq = lut[row & 255u];
-                        vcur = gm_get_val(row >> 8, pq.x, pq.y, S.sg + 4 * win[icur + delta]);
+                        vcur = gm_get_val_mask(row >> 8, pq.x, pq.y, S.sg + 4 * win[icur + delta]);
                     }
                 }
             }
@@ -2649,10 +2653,10 @@ __global__ void __launch_bounds__(256) k_nw(GmDevIndex ix, GmDevParams p, GmDevB
 template <int NCH, bool LDSR>
 __global__ void __launch_bounds__(256, NCH > 0 ? (LDSR ? 2 : NCH <= 13 ? 4 : 3) : GM_NW_OCC) k_nw_lane(GmDevIndex ix, GmDevParams p, GmDevBatch b) {
     extern __shared__ __attribute__((aligned(16))) uint2 s_rows[];          // LDSR: [2][NCH][256] bases, then qualities
-    __shared__ float2 s_lut[512];
+    __shared__ float2 s_lut[GM_LUT_ENTRIES];
     __shared__ uint32_t s_coff[GM_NW_NCOFF];
     __shared__ uint32_t s_pre[GM_NSHARD + 4];
-    for (int q = threadIdx.x; q < 512; q += 256) s_lut[q] = p.lut[q];
+    for (int q = threadIdx.x; q < (int)GM_LUT_ENTRIES; q += 256) s_lut[q] = p.lut[q];
     const bool lds_coff = ix.n_seqs + 1 <= GM_NW_NCOFF;
     if (lds_coff) for (uint32_t q = threadIdx.x; q <= ix.n_seqs; q += 256) s_coff[q] = ix.contig_off[q];
     const uint32_t* coff = lds_coff ? s_coff : ix.contig_off;
@@ -2674,9 +2678,10 @@ __global__ void __launch_bounds__(256, NCH > 0 ? (LDSR ? 2 : NCH <= 13 ? 4 : 3) 
         const bool ok = gm_window_ok(ix, coff, c.b, L);
         float result = 0.0f;
         if (ok && p.nw) {
-            const float2* lut = s_lut + ((r < b.illumina_until) ? 256 : 0);
+            // FASTA block: a row is (base mask of its letter, lut[GM_LUT_FASTA + mask]); there are no quality rows (the loads below fetch the letters twice)
+            const float2* lut = s_lut + (b.fasta ? GM_LUT_FASTA : (r < b.illumina_until) ? 256u : 0u);
             const uint8_t* rb = b.bases + (size_t)r * b.stride;
-            const uint8_t* rq = b.quals + (size_t)r * b.stride;
+            const uint8_t* rq = b.fasta ? rb : b.quals + (size_t)r * b.stride;
             const int Li = (int)L;
             // band row of i+1: P[d] = nm[i+1][i+1+delta], delta = d-3.  Row L: gGAP * (L - j) for j <= L (bin_seq.cpp:805-808)
             float P[7];
@@ -2771,12 +2776,11 @@ __global__ void __launch_bounds__(256, NCH > 0 ? (LDSR ? 2 : NCH <= 13 ? 4 : 3) 
                 const uint32_t sh = (uint32_t)(src & 3) << 3;
                 const uint32_t ch = (((src & 4) ? bw.y : bw.x) >> sh) & 255u;
                 const uint32_t qc = (((src & 4) ? qw.y : qw.x) >> sh) & 255u;
-                uint32_t code = gm_nt4(ch);
-                if (strand && code < 4) code = 3 - code;
-                const float2 pq = lut[qc];
+                const uint32_t mask = gm_row_mask(b.fasta, ch, strand);
+                const float2 pq = lut[b.fasta ? mask : qc];
                 float v4[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) v4[g] = gm_get_val(code, pq.x, pq.y, sg[g]);
+                for (int g = 0; g < 4; ++g) v4[g] = gm_get_val_mask(mask, pq.x, pq.y, sg[g]);
                 const float lastcol = EDGE ? __fmul_rn(gap, (float)(unsigned)(Li - i)) : 0.0f;      // nm[i][L] = gGAP * (L - i)
 #pragma unroll
                 for (int d = 6; d >= 0; --d) {
@@ -2920,7 +2924,7 @@ __global__ void __launch_bounds__(256) k_traceback(GmDevIndex ix, GmDevParams p,
     const uint32_t G = blockDim.x >> 3;
     GmNwLds S = gm_nw_lds(s_raw, Lp, G);
     uint32_t* mv_all = reinterpret_cast<uint32_t*>(s_raw + GM_NW_HDR + (size_t)G * Lp * 3);   // G groups x 7 x mvw words
-    for (int q = threadIdx.x; q < 512; q += blockDim.x) S.lut[q] = p.lut[q];
+    for (int q = threadIdx.x; q < 512; q += blockDim.x) S.lut[q] = p.lut[b.fasta ? GM_LUT_FASTA + (q & 15) : q];      // (FASTA: the 16 rows by mask)
     if (threadIdx.x < 16) S.sg[threadIdx.x] = p.S256[(size_t)("acgt"[threadIdx.x >> 2]) * 4 + (threadIdx.x & 3)];
     const bool lds_coff = ix.n_seqs + 1 <= GM_NW_NCOFF;
     if (lds_coff) for (uint32_t q = threadIdx.x; q <= ix.n_seqs; q += blockDim.x) S.coff[q] = ix.contig_off[q];
@@ -2944,7 +2948,7 @@ __global__ void __launch_bounds__(256) k_traceback(GmDevIndex ix, GmDevParams p,
         if (ok) gm_stage(ix, b, rows, win, r, strand, L, c.b, d);
         if (d < 7) for (uint32_t q = 0; q < mvw; ++q) mv[q] = 0;
         __syncthreads();
-        const float2* lut = S.lut + ((r < b.illumina_until) ? 256 : 0);
+        const float2* lut = S.lut + ((!b.fasta && r < b.illumina_until) ? 256 : 0);
         int absd = delta < 0 ? -delta : delta;
         float own = __fmul_rn(gap, (float)absd);          // first row / column: gGAP * t (bin_seq.cpp:503-511)
         int Lw = (int)L;
@@ -2958,7 +2962,7 @@ __global__ void __launch_bounds__(256) k_traceback(GmDevIndex ix, GmDevParams p,
         if (icur <= imax) {
             uint32_t row = rows[icur - 1];
             float2 pq = lut[row & 255u];
-            vcur = gm_get_val(row >> 8, pq.x, pq.y, S.sg + 4 * win[icur + delta - 1]);
+            vcur = gm_get_val_mask(row >> 8, pq.x, pq.y, S.sg + 4 * win[icur + delta - 1]);
         }
         for (int s = 2; s <= 2 * Lw; ++s) {
             float u_nb = gm_from_next_lane(own);          // diagonal delta+1, cell (i-1, j)
@@ -2979,7 +2983,7 @@ __global__ void __launch_bounds__(256) k_traceback(GmDevIndex ix, GmDevParams p,
                 if (icur <= imax) {
                     uint32_t row = rows[icur - 1];
                     float2 pq = lut[row & 255u];
-                    vcur = gm_get_val(row >> 8, pq.x, pq.y, S.sg + 4 * win[icur + delta - 1]);
+                    vcur = gm_get_val_mask(row >> 8, pq.x, pq.y, S.sg + 4 * win[icur + delta - 1]);
                 }
             }
         }
@@ -3089,10 +3093,10 @@ __global__ void __launch_bounds__(NT) k_traceback_lane(GmDevIndex ix, GmDevParam
         uint32_t ctext = 1;                                              // "*" when there is no path
         if (ok) {
             const uint32_t tab = (r < b.illumina_until) ? 1u : 0u;
-            const float2* lut = p.lut + tab * 256u;
+            const float2* lut = p.lut + (b.fasta ? GM_LUT_FASTA : tab * 256u);       // FASTA block: (p, q) by the letter's base mask, always the direct form
             const float4* const vtab = s_val + (tab < ntab ? tab : 0u) * GM_TBV_ENTRIES;
             const uint8_t* rb = b.bases + (size_t)r * b.stride;
-            const uint8_t* rq = b.quals + (size_t)r * b.stride;
+            const uint8_t* rq = b.fasta ? rb : b.quals + (size_t)r * b.stride;
             const int Li = (int)L;
             uint32_t wword_lo = 0, wword_hi = 0; int wbase = -2;          // (-2, not -1: a window that starts in the reference's first 16 bases must load word 0)
             auto wcode = [&](int j) -> uint32_t {                        // 2-bit code of the reference at window offset j
@@ -3130,13 +3134,14 @@ __global__ void __launch_bounds__(NT) k_traceback_lane(GmDevIndex ix, GmDevParam
                 uint32_t code = gm_nt4(ch);
                 if (strand && code < 4) code = 3 - code;
                 float v4[4];
-                if (tab < ntab && qc - 32u < 96u) {
+                if (!b.fasta && tab < ntab && qc - 32u < 96u) {
                     const float4 t4 = vtab[code * 96u + qc - 32u];
                     v4[0] = t4.x; v4[1] = t4.y; v4[2] = t4.z; v4[3] = t4.w;
-                } else {                                                 // a character outside the table (or no table): the direct form
-                    const float2 pq = lut[qc];
+                } else {                                                 // a character outside the table (or no table, or a FASTA block): the direct form
+                    const uint32_t mask = b.fasta ? gm_row_mask(1u, ch, strand) : gm_code_mask(code);
+                    const float2 pq = lut[b.fasta ? mask : qc];
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) v4[g] = gm_get_val(code, pq.x, pq.y, sg[g]);
+                    for (int g = 0; g < 4; ++g) v4[g] = gm_get_val_mask(mask, pq.x, pq.y, sg[g]);
                 }
                 uint32_t mrow = 0;
 #pragma unroll
@@ -3301,11 +3306,12 @@ int gmk_prep(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, vo
     // rows of up to 152 bytes: the form with the row in registers (gm_prep.hip); GM_PREP=tile keeps the LDS-tile form for A/B runs
     if (b.stride <= 152 && !gm_opt_is("GM_PREP", "tile")) return gmk_prep_rows(ix, p, b, stream);
     // reads per LDS tile: 48 KB for bases + quals, whole waves; rows too long for at least one wave per tile are read directly
-    uint32_t tr = (uint32_t)(49152 / (2 * (size_t)b.stride));
+    const size_t rows = b.fasta ? 1 : 2;                     // (a FASTA block has no quality rows to stage)
+    uint32_t tr = (uint32_t)(49152 / (rows * (size_t)b.stride));
     tr = tr >= 256 ? 256 : (tr / 64) * 64;
     const uint32_t per = tr ? tr : 256;
-    const uint32_t pg = resident_grid(k_prep, 256, (size_t)2 * tr * b.stride, 256 * 3);
-    hipLaunchKernelGGL(k_prep, dim3((uint32_t)std::min<uint64_t>(cdiv(b.n, per), pg)), dim3(256), (size_t)2 * tr * b.stride, S_(stream), ix, p, b, tr);
+    const uint32_t pg = resident_grid(k_prep, 256, rows * tr * b.stride, 256 * 3);
+    hipLaunchKernelGGL(k_prep, dim3((uint32_t)std::min<uint64_t>(cdiv(b.n, per), pg)), dim3(256), rows * tr * b.stride, S_(stream), ix, p, b, tr);
     return (int)hipGetLastError();
 }
 
@@ -3487,6 +3493,7 @@ int gmk_nw(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint
     if (b.n == 0) return 0;
     if (p.max_gap != 3) return gmk_nw_band(ix, p, b, n_cands, p.max_gap, stream);
     const bool wave_form = gm_opt_is("GM_NW", "wave");
+    if (wave_form && b.fasta) return (int)hipErrorInvalidValue;      // k_nw reads FASTQ rows only (the callers refuse this by name: fasta_forced_form)
     if (nw_rows_ok(p, b, rows_len)) return gmk_nw_rows(ix, p, b, n_cands, rows_len, qual_lo, qual_hi, stream);
     if (!wave_form) {
         // ~4 candidates per lane: fewer, larger workgroups leave a long tail (measured at 17 M candidates: 2048 workgroups 6.1 ms,
@@ -3565,7 +3572,7 @@ int gmk_traceback(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& 
     uint32_t Lp = lp_of(b.stride);
     const bool group_form = gm_opt_is("GM_TRACEBACK", "group");   // GM_TRACEBACK=group: the 8-lane form for every length (tests)
     if (!group_form && Lp <= 511) {              // lane form: one lane per item, move rows in LDS
-        uint32_t ntab = gm_opt_is("GM_TRACEBACK", "direct") ? 0u : (b.illumina_until ? 2u : 1u);      // value tables in LDS (direct: none, A/B runs)
+        uint32_t ntab = (gm_opt_is("GM_TRACEBACK", "direct") || b.fasta) ? 0u : (b.illumina_until ? 2u : 1u);      // value tables in LDS (direct: none, A/B runs; FASTA blocks: none)
         if (Lp <= 255) {
             const size_t mv_bytes = ((size_t)(Lp + 1) * 128 * 2 + 15) & ~(size_t)15;
             if (mv_bytes + (size_t)ntab * GM_TBV_ENTRIES * 16 > 65536) ntab = 0;          // (the default dynamic-LDS limit: long rows go without the table)

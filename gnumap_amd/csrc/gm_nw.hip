@@ -25,6 +25,9 @@
 //   * the first 8 and the last 9 .. 16 rows (which touch row L, column L or column -1) run a generic row; the rows between them test nothing.
 // The host launches it only for blocks it has checked: one read length L (24 <= L <= 8 NCH), no quality character above 127, -M 3; the
 // pair form only with the block's quality range, inside which every quality character of the block lies.
+// FASTA blocks (GmDevBatch::fasta): a position's row is its IUPAC letter's, (base mask, p, q) with (p, q) a function of the mask - the
+// class axis is the 16 masks (the minus strand's class = the mask with its bits reversed), the quality axis ONE entry: the quality rows
+// are neither loaded nor multiplied in (their words stay 0), and the whole pair table is 16 records (2.1 KB), the cells table 256 bytes.
 #include <hip/hip_runtime.h>
 #include "gm_device.h"
 
@@ -36,16 +39,18 @@ static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s);
 #define GM_NWR_PAIR_SKEW 8u                 // bytes of skew after each 128-byte pair record (GM_NW_PAIR_SKEW): record r starts 34 r dwords in
 
 // PAIRS: qlo = the block's smallest quality character, nq = the number of characters in its range, rs = bytes per pair record
-template <int NCH, bool PAIRS>
+// FA: a FASTA block (its own instantiation: the FASTQ kernels keep their instructions)
+template <int NCH, bool PAIRS, bool FA>
 __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex ix, GmDevParams p, GmDevBatch b, const uint32_t L, const uint32_t ntab,
                                                                     const uint32_t qlo, const uint32_t nq, const uint32_t rs) {
+    constexpr uint32_t ncls = FA ? 16u : 5u;                                    // class records per quality character (FA: one per base mask)
     constexpr int NHW = (8 * NCH + 3) / 16 + 1;                                // 16-column words of the window stream
     // cells: [ntab][128 quality characters][8 classes] float4 {val(a), val(c), val(g), val(t)};
     // PAIRS: [ntab][nq quality characters][5 classes] 16 x float2 {val(x), val(y)}, records rs bytes apart
     extern __shared__ __attribute__((aligned(16))) unsigned char s_tab[];
     // [phred table][strand][read character] -> byte offset of its class record (+ its table's; PAIRS: - qlo x the quality stride, mod 2^32)
     __shared__ std::conditional_t<PAIRS, uint32_t, uint16_t> s_cls[2][2][256];
-    const uint32_t qstride = PAIRS ? 5u * rs : GM_NWR_QSTRIDE, tabb = PAIRS ? nq * qstride : GM_NWR_TAB_BYTES;
+    const uint32_t qstride = PAIRS ? ncls * rs : GM_NWR_QSTRIDE, tabb = PAIRS ? nq * qstride : GM_NWR_TAB_BYTES;      // ncls: 5, FASTA 16
     __shared__ uint32_t s_coff[GM_NWR_NCOFF];
     __shared__ uint32_t s_pre[GM_NSHARD + 4];
     {
@@ -55,16 +60,26 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
 #pragma unroll
             for (int k = 0; k < 4; ++k) sg[g][k] = p.S256[(size_t)("acgt"[g]) * 4 + k];     // windows are lowercase acgt (GetString)
         if (PAIRS) {
-            for (uint32_t e = threadIdx.x; e < ntab * nq * 80u; e += 256) {     // 16 entries of 5 class records per quality character
-                const uint32_t n = e & 15u, rec = e >> 4, tq = rec / 5u, code = rec - 5u * tq;        // class 4: any character outside ACGTacgt
+            for (uint32_t e = threadIdx.x; e < ntab * nq * ncls * 16u; e += 256) {     // 16 entries of ncls class records per quality character
+                const uint32_t n = e & 15u, rec = e >> 4, tq = rec / ncls, code = rec - ncls * tq;    // class 4: any character outside ACGTacgt
                 const uint32_t tab = tq / nq, qi = tq - tab * nq;
-                const float2 pq = p.lut[tab * 256u + qlo + qi];
+                const uint32_t mask = FA ? code : gm_code_mask(code);                            // (FASTA: the class IS the base mask)
+                const float2 pq = FA ? p.lut[GM_LUT_FASTA + mask] : p.lut[tab * 256u + qlo + qi];
                 float v[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) v[g] = gm_get_val(code, pq.x, pq.y, sg[g]);
+                for (int g = 0; g < 4; ++g) v[g] = gm_get_val_mask(mask, pq.x, pq.y, sg[g]);
                 const uint32_t x = n >> 2, y = n & 3u;
                 const float2 o = make_float2(x == 0 ? v[0] : x == 1 ? v[1] : x == 2 ? v[2] : v[3], y == 0 ? v[0] : y == 1 ? v[1] : y == 2 ? v[2] : v[3]);
                 *reinterpret_cast<float2*>(s_tab + tab * tabb + qi * qstride + code * rs + 8u * n) = o;
+            }
+        } else if (FA) {
+            if (threadIdx.x < 16u) {                                              // one record per base mask, at "quality" 0
+                const uint32_t mask = threadIdx.x;
+                const float2 pq = p.lut[GM_LUT_FASTA + mask];
+                float4 v;
+                v.x = gm_get_val_mask(mask, pq.x, pq.y, sg[0]); v.y = gm_get_val_mask(mask, pq.x, pq.y, sg[1]);
+                v.z = gm_get_val_mask(mask, pq.x, pq.y, sg[2]); v.w = gm_get_val_mask(mask, pq.x, pq.y, sg[3]);
+                *reinterpret_cast<float4*>(s_tab + mask * 16u) = v;
             }
         } else {
             for (uint32_t e = threadIdx.x; e < ntab * 1024u; e += 256) {
@@ -82,7 +97,7 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
         for (uint32_t tab = 0; tab < 2; ++tab)
 #pragma unroll
             for (uint32_t st = 0; st < 2; ++st) {                                 // the reverse strand reads the complemented PWM row (reverse_comp_cpy)
-                const uint32_t cl = (code < 4u && st) ? 3u - code : code;
+                const uint32_t cl = FA ? gm_row_mask(1u, ch, st) : (code < 4u && st) ? 3u - code : code;
                 const uint32_t tb = (tab < ntab ? tab : 0u) * tabb;
                 s_cls[tab][st][ch] = PAIRS ? tb + cl * rs - qlo * qstride : tb + cl * 16u;
             }
@@ -119,8 +134,9 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
                     if (k < nchunk) {
                         const int fo = Li - 8 - 8 * k;
                         const uint32_t off = strand ? (uint32_t)(8 * k) : (uint32_t)(fo > 0 ? fo : 0);
-                        uint2 tb, tq;
-                        __builtin_memcpy(&tb, rb + off, 8); __builtin_memcpy(&tq, rq + off, 8);
+                        uint2 tb, tq = make_uint2(0u, 0u);
+                        __builtin_memcpy(&tb, rb + off, 8);
+                        if (!FA) __builtin_memcpy(&tq, rq + off, 8);
                         uint2 ob = make_uint2(__builtin_amdgcn_perm(tb.y, tb.x, selx), __builtin_amdgcn_perm(tb.y, tb.x, sely));
                         uint2 oq = make_uint2(__builtin_amdgcn_perm(tq.y, tq.x, selx), __builtin_amdgcn_perm(tq.y, tq.x, sely));
                         if (k == nchunk - 1 && sh != 0u) {                      // the last word of a reversed row was loaded from offset 0: its elements sit sh bytes up
@@ -319,46 +335,55 @@ static uint32_t nw_pair_rs() {
 static size_t nw_pair_lds(uint32_t ntab, uint32_t qlo, uint32_t qhi) {
     return (qlo <= qhi && qhi < 128u) ? (size_t)ntab * (qhi - qlo + 1u) * 5u * nw_pair_rs() : 0;
 }
+#define GM_NWR_FASTA_CELLS_BYTES 256u       // FASTA blocks, cells form: 16 mask records of 16 bytes
+
+// workgroups per CU: the pair form (lds bytes of table) holds at least as many as the cells form
+template <bool FA>
+static bool nw_pairs_fit(bool narrow, size_t lds_cells, size_t lds) {
+    int per_cells = 0, per_pairs = 0;
+    hipError_t e0, e1;
+    if (narrow) {
+        e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cells, k_nw_rows<13, false, FA>, 256, lds_cells);
+        e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_pairs, k_nw_rows<13, true, FA>, 256, lds);
+    } else {
+        e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cells, k_nw_rows<19, false, FA>, 256, lds_cells);
+        e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_pairs, k_nw_rows<19, true, FA>, 256, lds);
+    }
+    return e0 == hipSuccess && e1 == hipSuccess && per_pairs > 0 && per_pairs >= per_cells;
+}
 
 // the pair table unless it would leave fewer workgroups per CU than the cells table (wide quality ranges, two tables), or GM_NW_CELLS=b32
 bool gmk_nw_rows_pairs(const GmDevBatch& b, uint32_t L, uint32_t qlo, uint32_t qhi) {
     if (gm_opt_is("GM_NW_CELLS", "b32")) return false;
     const uint32_t ntab = b.illumina_until ? 2u : 1u;
-    const size_t lds = nw_pair_lds(ntab, qlo, qhi);
+    const size_t lds = b.fasta ? (size_t)16u * nw_pair_rs() : nw_pair_lds(ntab, qlo, qhi);
+    const size_t lds_cells = b.fasta ? (size_t)GM_NWR_FASTA_CELLS_BYTES : (size_t)ntab * GM_NWR_TAB_BYTES;
     if (!lds) return false;
-    int per_cells = 0, per_pairs = 0;
-    const bool narrow = L <= 104;
-    hipError_t e0, e1;
-    if (narrow) {
-        e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cells, k_nw_rows<13, false>, 256, (size_t)ntab * GM_NWR_TAB_BYTES);
-        e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_pairs, k_nw_rows<13, true>, 256, lds);
-    } else {
-        e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cells, k_nw_rows<19, false>, 256, (size_t)ntab * GM_NWR_TAB_BYTES);
-        e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_pairs, k_nw_rows<19, true>, 256, lds);
-    }
-    return e0 == hipSuccess && e1 == hipSuccess && per_pairs > 0 && per_pairs >= per_cells;
+    return b.fasta ? nw_pairs_fit<true>(L <= 104, lds_cells, lds) : nw_pairs_fit<false>(L <= 104, lds_cells, lds);
 }
 
 // L = the one read length of the block; [qlo, qhi] = the range of its quality characters (all below 128); illumina = some reads of the
 // block use the Phred+64 table (both tables are then resident)
 int gmk_nw_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t L, uint32_t qlo, uint32_t qhi, void* stream) {
     if (b.n == 0) return 0;
-    const uint32_t ntab = b.illumina_until ? 2u : 1u;
+    const uint32_t ntab = (b.illumina_until && !b.fasta) ? 2u : 1u;
     const bool pairs = gmk_nw_rows_pairs(b, L, qlo, qhi);
-    const size_t lds = pairs ? nw_pair_lds(ntab, qlo, qhi) : (size_t)ntab * GM_NWR_TAB_BYTES;
-    const uint32_t nq = pairs ? qhi - qlo + 1u : 0u, q0 = pairs ? qlo : 0u;
+    const size_t lds = b.fasta ? (pairs ? (size_t)16u * nw_pair_rs() : (size_t)GM_NWR_FASTA_CELLS_BYTES) : pairs ? nw_pair_lds(ntab, qlo, qhi) : (size_t)ntab * GM_NWR_TAB_BYTES;
+    const uint32_t nq = b.fasta ? 1u : pairs ? qhi - qlo + 1u : 0u, q0 = (pairs && !b.fasta) ? qlo : 0u;
     // the workgroups stride over the candidates: one resident round of them (4 per CU for <13> with one table; fewer with two tables or
     // for <19>).  The earlier grid of n_cands / 1024 workgroups (10 449 at 10.7 M candidates) left its last round a fifth full and
     // built the value table 10 times per CU: 2.04 -> 1.85 ms
     const uint32_t nw_fixed = (uint32_t)gm_opt_ll("GM_NW_GRID", 0);
     const bool narrow = L <= 104;
-#define GM_NWR_LAUNCH(N, PR, FB)                                                                                                        \
-    hipLaunchKernelGGL((k_nw_rows<N, PR>), dim3(nw_fixed ? nw_fixed : resident_grid(k_nw_rows<N, PR>, 256, lds, FB)), dim3(256), lds, \
+#define GM_NWR_LAUNCH_(N, PR, FA, FB)                                                                                                          \
+    hipLaunchKernelGGL((k_nw_rows<N, PR, FA>), dim3(nw_fixed ? nw_fixed : resident_grid(k_nw_rows<N, PR, FA>, 256, lds, FB)), dim3(256), lds, \
                        S_(stream), ix, p, b, L, ntab, q0, nq, nw_pair_rs())
+#define GM_NWR_LAUNCH(N, PR, FB) do { if (b.fasta) GM_NWR_LAUNCH_(N, PR, true, FB); else GM_NWR_LAUNCH_(N, PR, false, FB); } while (0)
     if (narrow && pairs) GM_NWR_LAUNCH(13, true, 1024u);
     else if (narrow) GM_NWR_LAUNCH(13, false, 1024u);
     else if (pairs) GM_NWR_LAUNCH(19, true, 768u);
     else GM_NWR_LAUNCH(19, false, 768u);
+#undef GM_NWR_LAUNCH_
 #undef GM_NWR_LAUNCH
     return (int)hipGetLastError();
 }

@@ -565,14 +565,22 @@ __global__ void __launch_bounds__(256) k_out_write(GmDevIndex ix, GmDevBatch b, 
 // orientation of the match's first strand (ScoredSeq.h:57-103 max_char, bin_seq.cpp:578-698 incl. the consense[i] quirk at :607)
 __device__ __forceinline__ uint32_t go_cons_code(const GmDevBatch& b, const float2* lut, uint32_t r, uint32_t L, uint32_t first_strand, uint32_t i) {
     const uint32_t src = first_strand ? L - 1u - i : i;
-    const uint8_t ch = b.bases[(size_t)r * b.stride + src], q = b.quals[(size_t)r * b.stride + src];
-    const float2 pq = lut[q];
-    int code;
-    switch (ch) { case 'a': case 'A': code = 0; break; case 'c': case 'C': code = 1; break; case 'g': case 'G': code = 2; break;
-                  case 't': case 'T': code = 3; break; default: code = 4; }
-    if (first_strand && code < 4) code = 3 - code;
-    float c[4] = { pq.y, pq.y, pq.y, pq.y };
-    if (code < 4) c[code] = pq.x;
+    const uint8_t ch = b.bases[(size_t)r * b.stride + src];
+    float c[4];
+    if (b.fasta) {                                      // the letter's row (get_more_fasta): `lut` is the FASTA table, (p, q) by base mask
+        uint32_t mask = gm_iupac_mask(ch);
+        if (first_strand) mask = gm_mask_rc(mask);
+        const float2 pq = lut[mask];
+        for (int k = 0; k < 4; ++k) c[k] = ((mask >> k) & 1u) ? pq.x : pq.y;
+    } else {
+        const float2 pq = lut[b.quals[(size_t)r * b.stride + src]];
+        int code;
+        switch (ch) { case 'a': case 'A': code = 0; break; case 'c': case 'C': code = 1; break; case 'g': case 'G': code = 2; break;
+                      case 't': case 'T': code = 3; break; default: code = 4; }
+        if (first_strand && code < 4) code = 3 - code;
+        c[0] = c[1] = c[2] = c[3] = pq.y;
+        if (code < 4) c[code] = pq.x;
+    }
     if (c[0] == c[1] && c[0] == c[2] && c[0] == c[3]) return 4;        // 'n'
     if (c[0] >= c[1]) { if (c[0] >= c[2]) return c[0] >= c[3] ? 0u : 3u; return c[2] >= c[3] ? 2u : 3u; }
     if (c[1] >= c[2]) return c[1] >= c[3] ? 1u : 3u;
@@ -585,7 +593,7 @@ __global__ void __launch_bounds__(256) k_out_codes(GmDevBatch b, GmDevParams p, 
     if (m >= n_m) return;
     const GmDevMatch mm = matches[m];
     const uint32_t r = mm.read - b.read_base, L = b.len[r];
-    const float2* lut = p.lut + ((r < b.illumina_until) ? 256 : 0);
+    const float2* lut = p.lut + (b.fasta ? GM_LUT_FASTA : (r < b.illumina_until) ? 256u : 0u);
     const unsigned long long* op = ops + (size_t)m * ops_words;
     uint8_t* out = codes + (size_t)m * codes_stride;
     const uint32_t n_op = ops_len[m];
@@ -788,7 +796,9 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
             o += 1u;
             for (uint32_t i = lane; i < QL; i += 64u) {
                 const uint32_t si = neg ? QL - 1u - i : i;          // the whole quality line is reversed, its tail included
-                const char c = si < L ? (char)qs[si] : t.qtail[q0 + (si - L)];
+                // FASTA block: str2qual's character (SequenceOperations.h:193-217) of the letter's row, by the number of bases in its mask
+                const char c = b.fasta ? (char)(t.fa_qual >> (8u * (((uint32_t)__popc(gm_iupac_mask(bs[si < L ? si : 0u])) - 1u) & 3u)))
+                               : si < L ? (char)qs[si] : t.qtail[q0 + (si - L)];
                 if (o + i < end) out[o + i] = c;
             }
             o += QL;

@@ -42,14 +42,18 @@ __global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p,
     }
     for (int e = threadIdx.x; e < 2 * 9 * 128; e += 256) {
         const int tab = e / (9 * 128), cl = (e / 128) % 9, qc = e & 127;
-        const int ch = cl < 8 ? "ACGTacgt"[cl] : 'N';
-        const float2 pq = p.lut[tab * 256 + qc];
+        // FASTA block: the term of a position depends on its raw character alone - S's row of that character (case-sensitive: Read::seq
+        // is the file's text) dotted with the letter's PWM row.  The kernel looks it up with the character in the quality's place:
+        // class 8 holds one term per character, the classes of ACGTacgt their one term at every index
+        const int ch = b.fasta ? (cl < 8 ? "ACGTacgt"[cl] : qc) : (cl < 8 ? "ACGTacgt"[cl] : 'N');
+        const uint32_t mask = b.fasta ? gm_iupac_mask((uint32_t)ch) : gm_code_mask(gm_nt4((uint32_t)ch));
+        const float2 pq = b.fasta ? p.lut[GM_LUT_FASTA + mask] : p.lut[tab * 256 + qc];
         const float4 sv = S4[ch];
         const float sarr[4] = { sv.x, sv.y, sv.z, sv.w };
-        s_term[tab][cl][qc] = gm_get_val(gm_nt4((uint32_t)ch), pq.x, pq.y, sarr);
+        s_term[tab][cl][qc] = gm_get_val_mask(mask, pq.x, pq.y, sarr);
     }
     __syncthreads();
-    const bool uni = s_other_uniform != 0;
+    const bool uni = b.fasta || s_other_uniform != 0;        // (FASTA: class 8 has every character's own term)
     const uint32_t pw = b.pack ? b.pack_words : 0u;
     uint32_t* const myrow = s_rows + (size_t)threadIdx.x * pw;
     unsigned long long bad = 0, high = 0;
@@ -69,7 +73,16 @@ __global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p,
             for (int k = 0; k < NCH; k += 2) {
                 RB[k] = make_uint2(0u, 0u); RQ[k] = make_uint2(0u, 0u);
                 if (k + 1 < NCH) { RB[k + 1] = make_uint2(0u, 0u); RQ[k + 1] = make_uint2(0u, 0u); }
-                if (k + 1 < NCH && (uint32_t)(8 * k + 8) < L) {
+                if (b.fasta) {                            // no quality rows: the letters (7 bits) stand in their place
+                    if (k + 1 < NCH && (uint32_t)(8 * k + 8) < L) {
+                        uint4 tb;
+                        __builtin_memcpy(&tb, rb + 8 * k, 16);
+                        RB[k] = make_uint2(tb.x, tb.y);
+                        if (k + 1 < NCH) RB[k + 1] = make_uint2(tb.z, tb.w);
+                    } else if ((uint32_t)(8 * k) < L) RB[k] = *reinterpret_cast<const uint2*>(rb + 8 * k);
+                    RQ[k] = make_uint2(RB[k].x & 0x7F7F7F7Fu, RB[k].y & 0x7F7F7F7Fu);
+                    if (k + 1 < NCH) RQ[k + 1] = make_uint2(RB[k + 1].x & 0x7F7F7F7Fu, RB[k + 1].y & 0x7F7F7F7Fu);
+                } else if (k + 1 < NCH && (uint32_t)(8 * k + 8) < L) {
                     uint4 tb, tq;
                     __builtin_memcpy(&tb, rb + 8 * k, 16); __builtin_memcpy(&tq, rq + 8 * k, 16);
                     RB[k] = make_uint2(tb.x, tb.y); RQ[k] = make_uint2(tq.x, tq.y);

@@ -1,7 +1,7 @@
 // gnumap_main.cpp — the C++ host driver: keeps the reference's command line (src/Driver.cpp:172-250, 2658-3251),
 // SAM format (src/Driver.cpp:2146-2217, 2317-2329) and .sgr output (src/GenomeBwt.cpp:1212-1273), and drives the hot
 // path through the C ABI of libgnumap_hip.so only.  Per batch it mirrors parallel_thread_run (src/Driver.cpp:2303-2407):
-//     parse FASTQ block -> gm_map_batch (= loop over set_top_matches) -> gm_output_batch (= loop over create_match_output)
+//     parse FASTQ (or FASTA) block -> gm_map_batch (= loop over set_top_matches) -> gm_output_batch (= loop over create_match_output)
 //     -> SAM text.
 // I/O at rate: the FASTQ file is memory-mapped and cut into blocks by one scanner thread (memchr only, no
 // copies); per GPU `--workers` host threads (default 3, each with its own gm_batch and HIP stream) pack a block, run the
@@ -23,6 +23,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
+#include <cctype>
 #include <fstream>
 #include <iostream>
 #include <map>
@@ -54,12 +56,15 @@ struct Options {
     bool snp_monop = false, snp_calls = false;      // --snp_monop: gSNP_MONOP; --snp_calls: <out>.gmp with PrintSNPCall's ninth column
     bool sam_text_device = false;   // --sam_text=device: SAM rows formatted on the GPU (gm_output_batch_text); host = format_sam below
     int sam_shards = 1;             // --sam_shards=K: <out>.0.sam .. <out>.<K-1>.sam by input position instead of one <out>.sam
+    bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
 
 static void usage(int rc, const char* msg) {
     if (msg && *msg) fprintf(stderr, "%s\n", msg);
     fprintf(stderr,
             "Usage: gnumap [options] <file_to_parse>\n"
+            "  <file_to_parse>              FASTQ (first byte '@') or FASTA (first byte '>': the 15 IUPAC letters in either case, sequence\n"
+            "                               lines joined, the whole header line is the name); -A and --snp take FASTQ only\n"
             "  -g, --genome=STRING          Genome .fa file\n"
             "  -o, --output=STRING          Output file prefix (<out>.sam, <out>.sgr)\n"
             "  -a, --align_score=DOUBLE     Limit for sequence alignment (default: 0.9)\n"
@@ -265,6 +270,7 @@ struct Block {
     std::vector<const char*> name, seq, qual;
     std::vector<uint32_t> name_len, qual_len;
     std::vector<uint16_t> len;
+    std::vector<char> fa_text;              // FASTA: the joined sequence lines of the records that span several, and the QUAL strings the rows print (seq / qual point here)
     std::vector<uint16_t> kept;             // -A with --illumina: what the adaptor trim keeps of every read (the fallback scan sees only that); else empty
     // packed for gm_reads (page-locked)
     PinVec<uint8_t> bases, qbuf; PinVec<uint16_t> plen;
@@ -359,6 +365,56 @@ struct FastqScanner {
         b.stride = std::max<uint32_t>(8, (b.maxlen + 7u) & ~7u);
         return b.n > 0;
     }
+    // FASTA (SeqReader::get_more_fasta src/SeqReader.cpp:813-1018): a record runs from one '>' line to the next, the name is the whole
+    // header line after '>', the sequence lines are joined.  base[cur, limit) starts at a '>' (the whole input was checked by
+    // fasta_check before anything was mapped).  QUAL is str2qual's string (fasta_qual): the host formatter prints it from the block.
+    static bool parse_range_fasta(const char* base, size_t& cur, size_t limit, Block& b, uint32_t max_reads, bool* too_long, const char* qual_of) {
+        b.n = 0; b.maxlen = 0;
+        b.name.clear(); b.seq.clear(); b.qual.clear(); b.name_len.clear(); b.qual_len.clear(); b.len.clear(); b.fa_text.clear();
+        std::vector<size_t> seq_at, qual_at;                 // offsets into fa_text (npos: a one-line sequence, printed from the mapping)
+        std::vector<const char*> one_line;
+        const size_t npos = ~(size_t)0;
+        while (b.n < max_reads && cur < limit) {
+            const char* hd = base + cur;
+            const char* e = (const char*)memchr(hd, '\n', limit - cur);
+            const size_t hl = e ? (size_t)(e - hd) : limit - cur;
+            cur = e ? (size_t)(e - base) + 1 : limit;
+            // sequence lines up to the next header
+            const char* first = nullptr; size_t first_len = 0, total = 0; int lines = 0; size_t joined_at = npos;
+            while (cur < limit && base[cur] != '>') {
+                const char* l = base + cur;
+                const char* le = (const char*)memchr(l, '\n', limit - cur);
+                const size_t ll = le ? (size_t)(le - l) : limit - cur;
+                cur = le ? (size_t)(le - base) + 1 : limit;
+                if (ll == 0) continue;
+                if (lines == 0) { first = l; first_len = ll; }
+                else {
+                    if (lines == 1) { joined_at = b.fa_text.size(); b.fa_text.insert(b.fa_text.end(), first, first + first_len); }
+                    b.fa_text.insert(b.fa_text.end(), l, l + ll);
+                }
+                total += ll; ++lines;
+            }
+            if (total > 2048) { fprintf(stderr, "ERROR: read %.*s is longer than 2048 bases\n", (int)std::min<size_t>(hl, 200), hd); *too_long = true; break; }
+            b.name.push_back(hd + 1); b.name_len.push_back((uint32_t)(hl - 1));
+            one_line.push_back(first ? first : hd); seq_at.push_back(joined_at);
+            b.len.push_back((uint16_t)total); b.qual_len.push_back((uint32_t)total);
+            b.maxlen = std::max<uint32_t>(b.maxlen, (uint32_t)total);
+            ++b.n;
+        }
+        // the QUAL strings behind the joined sequences, then the views (fa_text does not move any more)
+        qual_at.resize(b.n);
+        for (uint32_t i = 0; i < b.n; ++i) { qual_at[i] = b.fa_text.size(); b.fa_text.resize(b.fa_text.size() + b.len[i]); }
+        b.seq.resize(b.n); b.qual.resize(b.n);
+        for (uint32_t i = 0; i < b.n; ++i) {
+            b.seq[i] = seq_at[i] == npos ? one_line[i] : b.fa_text.data() + seq_at[i];
+            char* q = b.fa_text.data() + qual_at[i];
+            for (uint32_t t = 0; t < b.len[i]; ++t) q[t] = qual_of[(unsigned char)b.seq[i][t]];
+            b.qual[i] = q;
+        }
+        b.stride = std::max<uint32_t>(8, (b.maxlen + 7u) & ~7u);
+        return b.n > 0;
+    }
+    bool fasta = false; const char* fasta_qual = nullptr;    // set by main() for a FASTA input
     // File order, with the recovery of SeqReader::get_more_fastq (src/SeqReader.cpp:1060-1150): four lines are read; while the first does
     // not start with '@' or the third not with '+', the lines are shifted up by one and one more is read; a quality line shorter than
     // its sequence makes the reader take the next four lines instead.  The lines come from std::getline on an ifstream, whose end-of-input
@@ -414,6 +470,11 @@ struct FastqScanner {
     }
     bool next(Block& b, uint32_t max_reads, bool* too_long) {    // file-order mode: blocks of exactly max_reads reads
         if (done) return false;
+        if (fasta) {
+            const bool got = parse_range_fasta(base, at, size, b, max_reads, too_long, fasta_qual);
+            if (at >= size || *too_long) done = true;
+            return got;
+        }
         return parse_resync(b, max_reads, too_long);
     }
     // chunk mode: the start of the first record at or after `off` (a line starting with '@' whose next-but-one line starts with
@@ -423,6 +484,12 @@ struct FastqScanner {
         if (off >= size) return size;
         const char* e = (const char*)memchr(base + off - 1, '\n', size - off + 1);      // the line containing off-1 ends here
         size_t p = e ? (size_t)(e - base) + 1 : size;
+        while (fasta && p < size) {                          // FASTA: the next line that starts with '>'
+            if (base[p] == '>') return p;
+            const char* l1 = (const char*)memchr(base + p, '\n', size - p);
+            if (!l1) return size;
+            p = (size_t)(l1 - base) + 1;
+        }
         while (p < size) {
             const char* l1 = (const char*)memchr(base + p, '\n', size - p);
             if (!l1) return size;
@@ -439,6 +506,7 @@ struct FastqScanner {
         if (!chunk_bytes) {                                  // record size from the first records of the file
             size_t p = 0; uint32_t recs = 0;
             while (recs < 4000 && p < size) { const char* e = (const char*)memchr(base + p, '\n', size - p); if (!e) break; p = (size_t)(e - base) + 1; ++recs; }
+            if (fasta) { uint32_t hd = 0; for (size_t q = 0; q < p; ++q) hd += base[q] == '>' && (q == 0 || base[q - 1] == '\n'); recs = 4 * std::max<uint32_t>(hd, 1u); }
             const double per_rec = recs >= 4 ? (double)p / (recs / 4) : 256.0;
             chunk_bytes = (size_t)std::max(4096.0, per_rec * target_reads);
         }
@@ -462,9 +530,11 @@ template <class F> static void run_slices(uint32_t n, int threads, uint32_t grai
 }
 
 // with_text: also the names (cut to what a row prints of them) and the rare quality tails, back to back, for gm_read_text
-static void pack_block(Block& b, int threads, bool with_text) {          // rows of `stride` bytes, zero padded, as gm_reads wants them
+// fasta: the letters only (gm_reads.quals is not read for a FASTA block)
+static void pack_block(Block& b, int threads, bool with_text, bool fasta) {          // rows of `stride` bytes, zero padded, as gm_reads wants them
     const size_t bytes = (size_t)b.n * b.stride;
-    b.bases.ensure(bytes); b.qbuf.ensure(bytes); b.plen.ensure(b.n);
+    b.bases.ensure(bytes); if (!fasta) b.qbuf.ensure(bytes);
+    b.plen.ensure(b.n);
     memcpy(b.plen.data(), b.len.data(), (size_t)b.n * 2);
     if (with_text) {
         b.name_off.ensure((size_t)b.n + 1); b.qtail_off.ensure((size_t)b.n + 1);
@@ -486,9 +556,11 @@ static void pack_block(Block& b, int threads, bool with_text) {          // rows
     }
     run_slices(b.n, threads, 8192, [&](int, uint32_t lo, uint32_t hi) {
         for (uint32_t i = lo; i < hi; ++i) {
-            uint8_t* pb = &b.bases[(size_t)i * b.stride]; uint8_t* pq = &b.qbuf[(size_t)i * b.stride];
+            uint8_t* pb = &b.bases[(size_t)i * b.stride];
             const uint32_t L = b.len[i];
             memcpy(pb, b.seq[i], L); memset(pb + L, 0, b.stride - L);
+            if (fasta) continue;
+            uint8_t* pq = &b.qbuf[(size_t)i * b.stride];
             memcpy(pq, b.qual[i], L); memset(pq + L, 0, b.stride - L);
         }
     });
@@ -569,6 +641,61 @@ static void format_sam(TextBuf& out, const gm_index* ix, const gm_params& p, con
     out.len += (size_t)(w - w0);
 }
 
+// ---- FASTA reads --------------------------------------------------------------------------------------------------
+// bases in the row of a sequence character (get_more_fasta src/SeqReader.cpp:884-950), 0 = not one of the 15 letters
+static int fasta_row_bases(unsigned char c) {
+    switch (tolower(c)) {
+        case 'a': case 'c': case 'g': case 't': return 1;
+        case 'r': case 'y': case 'k': case 'm': case 's': case 'w': return 2;
+        case 'b': case 'd': case 'h': case 'v': return 3;
+        case 'n': return 4;
+        default: return 0;
+    }
+}
+// str2qual (inc/SequenceOperations.h:193-217): the QUAL character of every letter, from the largest entry of its row
+static void fasta_qual_table(char* t /* 256 */) {
+    static const double share[5] = { 0.0, 1.0, 0.5, 1.0 / 3.0, 0.25 };
+    const double MAX_PRB = 0.9999;
+    for (int c = 0; c < 256; ++c) {
+        const float pmax = (float)share[fasta_row_bases((unsigned char)c)];
+        t[c] = pmax > MAX_PRB ? (char)((-10 * log(1 - MAX_PRB) / log(10.)) + 33) : (char)((-10 * log(1 - pmax) / log(10)) + 33);
+    }
+}
+// The whole input, once, before anything is mapped: every record has a sequence of the 15 letters.  The reference skips CR, space, VT and
+// FF inside a sequence when it builds the rows but keeps them in the text it prints and seeds from, so rows and text fall out of step
+// there; this driver refuses such a file instead.  Blank lines inside a record are skipped, here and in
+// parse_range_fasta (the reference appends their nothing).  One serial pass at memory rate: a table look-up per byte.
+static bool fasta_check(const char* base, size_t size, const char* fn) {
+    size_t at = 0, rec = 0, hd_at = 0, seq_len = 0;
+    bool letter[256];
+    for (int c = 0; c < 256; ++c) letter[c] = fasta_row_bases((unsigned char)c) != 0;
+    auto name = [&](size_t h) { const char* e = (const char*)memchr(base + h, '\n', size - h); return std::string(base + h, std::min<size_t>(e ? (size_t)(e - (base + h)) : size - h, 200)); };
+    while (at < size) {
+        const char* l = base + at;
+        const char* e = (const char*)memchr(l, '\n', size - at);
+        const size_t ll = e ? (size_t)(e - l) : size - at;
+        if (ll && l[0] == '>') {
+            if (rec && !seq_len) { fprintf(stderr, "ERROR: %s: FASTA record %s has no sequence\n", fn, name(hd_at).c_str()); return false; }
+            ++rec; hd_at = at; seq_len = 0;
+        } else {
+            for (size_t k = 0; k < ll; ++k) {
+                const unsigned char c = (unsigned char)l[k];
+                if (letter[c]) continue;
+                if (c == '\r' || c == ' ' || c == 11 || c == 12)
+                    fprintf(stderr, "ERROR: %s: FASTA record %s: white space (CR, space, VT or FF) inside a sequence line is not supported\n", fn, name(hd_at).c_str());
+                else
+                    fprintf(stderr, "ERROR: %s: FASTA record %s: sequence character '%c' (%d) at position %zu is not one of the 15 letters acgtnrykmswbdhv\n", fn,
+                            name(hd_at).c_str(), c >= 32 && c < 127 ? c : '?', (int)c, seq_len + k);
+                return false;
+            }
+            seq_len += ll;
+        }
+        at = e ? (size_t)(e - base) + 1 : size;
+    }
+    if (rec && !seq_len) { fprintf(stderr, "ERROR: %s: FASTA record %s has no sequence\n", fn, name(hd_at).c_str()); return false; }
+    return true;
+}
+
 // ---- per worker: the two batch calls ---------------------------------------------------------------------------------
 struct Worker {
     int gpu = 0;
@@ -588,8 +715,8 @@ static int process_block(Worker& w, const Options& o, Block& b) {
     const uint32_t n = b.n;
     gm_params bp = o.p; bp.illumina = b.illumina;
     auto c0 = std::chrono::steady_clock::now();
-    pack_block(b, 4, o.sam_text_device);
-    gm_reads reads; reads.n = n; reads.stride = b.stride; reads.bases = b.bases.data(); reads.quals = b.qbuf.data(); reads.len = b.plen.data();
+    pack_block(b, 4, o.sam_text_device, o.fasta);
+    gm_reads reads; reads.n = n; reads.stride = b.stride; reads.bases = b.bases.data(); reads.quals = o.fasta ? nullptr : b.qbuf.data(); reads.len = b.plen.data();
     w.status.ensure(n); w.self_score.ensure(n); w.top.ensure(n); w.den.ensure(n); w.mbegin.ensure((size_t)n + 1);
     w.matches.ensure(2 * (size_t)n + 64); w.positions.ensure(2 * (size_t)n + 64);
     gm_hits hits{};
@@ -697,6 +824,28 @@ int main(int argc, char** argv) {
     std::string cl;
     for (int i = 0; i < argc; ++i) { cl += argv[i]; cl += " "; }      // Driver.cpp:1032-1039
     auto t0 = std::chrono::steady_clock::now();
+    // the read file's format from its first byte, as SeqReader::find_type (src/SeqReader.cpp:175-244) - and what a FASTA input rules out -
+    // before the device is opened
+    FastqScanner fq;
+    char fasta_qual[256];
+    const bool reads_open = fq.open(o.reads);
+    if (reads_open && fq.size) {
+        if (fq.base[0] == '>') {
+            o.fasta = true;
+            if (!o.adaptor.empty()) {
+                fprintf(stderr, "ERROR: -A/--adaptor with FASTA reads is not supported (the reference trims FASTA reads with the PWM-based FixReads, a different rule); use FASTQ reads\n");
+                return 1;
+            }
+            if (o.p.mode == GM_MODE_SNP) { fprintf(stderr, "ERROR: --snp with FASTA reads is not supported; use FASTQ reads\n"); return 1; }
+            if (!fasta_check(fq.base, fq.size, o.reads.c_str())) return 1;
+            o.p.illumina = 0;                                  // accepted and ignored, as in the reference
+            fasta_qual_table(fasta_qual);
+            fq.fasta = true; fq.fasta_qual = fasta_qual;
+        } else if (fq.base[0] != '@') {
+            fprintf(stderr, "ERROR: %s starts with neither '@' (FASTQ) nor '>' (FASTA): the _prb.txt and _int.txt read formats are not supported\n", o.reads.c_str());
+            return 1;
+        }
+    }
     const int flags = GM_INDEX_BUILD | (o.locate_sampled ? 0 : GM_INDEX_FULL_SA);
     std::vector<gm_index*> gpu_ix((size_t)o.gpus, nullptr);
     {   // build once if missing, then one replica per GPU
@@ -715,7 +864,8 @@ int main(int argc, char** argv) {
             Worker& w = workers[(size_t)g * (size_t)o.workers + (size_t)k];
             w.gpu = g; w.ix = gpu_ix[(size_t)g]; w.text_pool = &text_pool;
             if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK ||
-                gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+                gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK ||
+                gm_batch_set_read_format(w.batch, o.fasta ? GM_READS_FASTA : GM_READS_FASTQ) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
         }
     }
     gm_index_info info;
@@ -750,8 +900,7 @@ int main(int argc, char** argv) {
     }
 
     auto t_pipe0 = std::chrono::steady_clock::now();
-    FastqScanner fq;
-    if (!fq.open(o.reads)) { fprintf(stderr, "ERROR: cannot open %s\n", o.reads.c_str()); return 1; }
+    if (!reads_open) { fprintf(stderr, "ERROR: cannot open %s\n", o.reads.c_str()); return 1; }
     std::atomic<int> failed{ 0 };
     double t_scan = 0, t_fmt = 0, t_write = 0;
     { struct stat hs; if (fstat(ofd, &hs) == 0) file_offs[0] = (uint64_t)lseek(ofd, 0, SEEK_CUR); }
@@ -819,7 +968,8 @@ int main(int argc, char** argv) {
                     if (b->lazy) {                              // chunk mode: this worker cuts its byte range into records
                         auto s0 = std::chrono::steady_clock::now();
                         size_t cur = b->text_lo, bad_at = npos; bool stop = false, too_long = false;
-                        FastqScanner::parse_range(fq.base, cur, b->text_hi, *b, 16000000u, &stop, &bad_at, &too_long);
+                        if (o.fasta) FastqScanner::parse_range_fasta(fq.base, cur, b->text_hi, *b, 16000000u, &too_long, fq.fasta_qual);
+                        else FastqScanner::parse_range(fq.base, cur, b->text_hi, *b, 16000000u, &stop, &bad_at, &too_long);
                         if (too_long) failed = 1;
                         w.t_scan += secs_since(s0);
                         bool drop;

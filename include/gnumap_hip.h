@@ -102,12 +102,13 @@ typedef struct {
     int finalized;
 } gm_params;
 
-/* a block of reads exactly as they stand in the FASTQ file; caller-owned host memory */
+/* a block of reads exactly as they stand in the FASTQ (or, gm_batch_set_read_format, FASTA) file; caller-owned host memory */
 typedef struct {
     uint32_t n;                 /* number of reads */
     uint32_t stride;            /* bytes between consecutive reads in bases[] / quals[] (>= longest read, multiple of 8) */
-    const uint8_t* bases;       /* n x stride, FASTQ sequence characters verbatim (any case, N allowed) */
-    const uint8_t* quals;       /* n x stride, raw FASTQ quality characters */
+    const uint8_t* bases;       /* n x stride, FASTQ sequence characters verbatim (any case, N allowed); FASTA: the sequence lines of a
+                                   record joined, the 15 IUPAC letters in either case */
+    const uint8_t* quals;       /* n x stride, raw FASTQ quality characters; not read for a FASTA block (may be NULL) */
     const uint16_t* len;        /* n read lengths */
 } gm_reads;
 
@@ -237,6 +238,23 @@ int gm_batch_upload(gm_batch*, const gm_params*, const gm_reads*, void* hip_stre
  * the reference's unsigned bound wraps: a read of fewer than 4 bases keeps 0.  Cost: one launch and one small read-back per upload,
  * only while an adaptor is set. */
 int gm_batch_set_adaptor(gm_batch*, const char* adaptor);
+/* The read file's format, as SeqReader::find_type (src/SeqReader.cpp:175-244) tells it from the first byte: '@' FASTQ, '>' FASTA (the
+ * reference's _prb.txt / _int.txt formats are not built).  Holds for the blocks uploaded from now on - gm_batch_upload, gm_map_batch(_device /
+ * _enqueue) - and for what gm_output_batch(_text / _enqueue) does with them.  A FASTA block is its letters only: gm_reads.quals is not
+ * read and not copied (half the upload).  A position's PWM row is get_more_fasta's (src/SeqReader.cpp:875-979, cast to float at :996):
+ * a c g t one 1.0; r y k m s w two 0.5; b d h v three (float)(1.0 / 3.0); n four 0.25; everything else 0.0 - on the device a 4-bit base mask
+ * with an in-mask and an out-of-mask probability, the mask's bits reversed for reverse_comp_cpy's row on the minus strand, every value
+ * ((r0 s0 + r1 s1) + r2 s2) + r3 s3 in fp32 like bin_seq::get_val.  The self score takes S's row of the RAW character (Read::seq is the
+ * file's text, GetConsensus Driver.cpp:352-364: 'K' and 'k' are different rows).  Every letter outside ACGTacgt ends a seed k-mer like
+ * N.  SEQ of a row is the letters (reverse_comp on the minus strand: every letter outside ACGTacgt becomes 'n'), QUAL is str2qual's
+ * string (inc/SequenceOperations.h:193-217), one character per position from the row's largest entry.  gm_params.illumina is ignored.
+ * The caller checks the letters: a byte that is none of the 15 gives an all-zero row.  gm_output_batch_text: gm_read_text.qual_tail must be
+ * NULL for a FASTA block (GM_E_ARG otherwise): there is no quality line a tail could come from.
+ * GM_E_UNSUPPORTED for a FASTA block with an adaptor set (the reference's FixReads for FASTA is a different, PWM-based trim), with
+ * GM_MODE_SNP, or with the switch that forces the one kernel form which takes FASTQ only (GM_NW=wave, the DP score kernel k_nw):
+ * gm_last_error() names it. */
+enum { GM_READS_FASTQ = 0, GM_READS_FASTA = 1 };
+int gm_batch_set_read_format(gm_batch*, int format);
 /* the lengths the kernels used for the block uploaded last (Read::length = J, SeqReader.cpp:1260): n values; gm_reads.len without an adaptor */
 int gm_batch_trimmed_len(gm_batch*, uint16_t* out);
 /* device time of k_adaptor_trim since the last call, measured with HIP events while gm_batch_set_profiling is on (it is not one of
@@ -251,8 +269,9 @@ int gm_batch_counters(gm_batch*, gm_counters* out);
 int gm_batch_set_profiling(gm_batch*, int on);
 int gm_batch_kernel_times(gm_batch*, double* ms /* GM_K_COUNT */, uint64_t* launches /* GM_K_COUNT */);
 const char* gm_kernel_name(int which);
-/* which seed lookup / vote kernel / locate form the last gm_map_batch_device on this batch chose, e.g.
- * "seeds=bucket-table (in the vote kernel) vote=k_vote_bucket<4> locate=full-SA" (valid until the next call on the batch) */
+/* the block's read format and which seed lookup / vote kernel / locate form / DP kernel the last gm_map_batch_device on this batch chose,
+ * e.g. "reads=fastq seeds=bucket-table (in the vote kernel) vote=k_vote_bucket<4> locate=full-SA nw=k_nw_rows/pairs" (valid until the
+ * next call on the batch) */
 const char* gm_batch_path(gm_batch*);
 /* raw device results (accepted candidates), for tests and for callers that post-process themselves */
 typedef struct { uint32_t read; uint32_t pos; float score; uint16_t step; uint8_t strand; uint8_t pad; } gm_raw_hit;
@@ -303,6 +322,10 @@ int gm_dev_nw_score(gm_index*, const gm_params*, const gm_reads*, const uint32_t
 int gm_dev_traceback(gm_index*, const gm_params*, const gm_reads*, const uint32_t* read_idx, const uint8_t* strand,
                      const uint64_t* pos, uint32_t n, char* ops /* n x ops_stride, 'M','I','D', NUL padded */,
                      uint32_t ops_stride, uint16_t* ops_len);
+
+/* the format in which the unit probes above (and gm_dev_pair_hmm, which refuses FASTA) read their gm_reads from now on: GM_READS_FASTQ
+ * (default) or GM_READS_FASTA - see gm_batch_set_read_format.  Per index, not thread-safe against probes running at the same time */
+int gm_index_set_probe_format(gm_index*, int format);
 
 /* SeqReader::FixReads2 / Compare (src/SeqReader.cpp:1356-1372, 1294-1305) of every read of the block against `adaptor`, on the device:
  * out_len[i] = the length read i keeps (see gm_batch_set_adaptor).  Only gm_reads.bases / len are read; NULL or "" copies len */
