@@ -1007,11 +1007,17 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
         char buf[224];
         const int pp_env = (int)gm_opt_ll("GM_SLOTS_PIPE", -1);                                               // (gmk_vote's condition for the pipelined form of k_vote_slots)
         const bool slots_pp = use_full && !gm_opt("GM_VOTE_KERNEL") && (pp_env < 0 ? dense == 2 : pp_env != 0) && !(dp.dbg & 64);
-        snprintf(buf, sizeof buf, "seeds=%s vote=%s locate=%s", use_bucket ? "bucket-table (in the vote kernel)" : dp.fused ? "k-mer table (in the vote kernel)" : "k_seed",
+        // gmk_vote's own branches: more than 64 seeds per strand leave the one-workgroup kernels for the ordered k_vote, GM_VOTE_KERNEL picks
+        // the dense form whatever `dense` says, GM_VOTE_SPARSE=0 runs k_vote_fast for every read x strand
+        const char* kenv = gm_opt("GM_VOTE_KERNEL"); if (kenv && !*kenv) kenv = nullptr;
+        const bool wg_form = dense != 0 && b->max_seeds <= 64;
+        const bool slots_form = wg_form && (kenv ? !strcmp(kenv, "slots") : dense <= 2);
+        snprintf(buf, sizeof buf, "seeds=%s vote=%s locate=%s cands=%s", use_bucket ? "bucket-table (in the vote kernel)" : dp.fused ? "k-mer table (in the vote kernel)" : "k_seed",
                  use_pair ? (bucket_reg <= 8 ? "k_vote_pair<4> + k_vote_bucket<2>" : bucket_reg <= 14 ? "k_vote_pair<7> + k_vote_bucket<4>" : "k_vote_pair<8> + k_vote_bucket<4>")
                  : use_bucket ? (bucket_reg <= 8 ? "k_vote_bucket<2>" : bucket_reg <= 16 ? "k_vote_bucket<4>" : bucket_reg <= 24 ? "k_vote_bucket<6>" : "k_vote_bucket<8>")
-                            : dense == 0 ? "sparse" : dense == 3 ? "k_vote_block" : dense == 2 ? (slots_pp ? "k_vote_slots_pp<64>" : "k_vote_slots<64>") : slots_hint == 0 ? "k_vote_tiny" : slots_hint < 0 ? "k_vote_tiny2" : slots_pp ? "k_vote_slots_pp" : "k_vote_slots",
-                 use_full ? "full-SA" : "sampled-SA");
+                            : !wg_form ? (b->max_seeds > 64 ? "k_vote" : gm_opt_is("GM_VOTE_SPARSE", "0") ? "k_vote_fast" : "sparse") : !slots_form ? "k_vote_block"
+                            : dense == 2 ? (slots_pp ? "k_vote_slots_pp<64>" : "k_vote_slots<64>") : slots_hint == 0 ? "k_vote_tiny" : slots_hint < 0 ? "k_vote_tiny2" : slots_pp ? "k_vote_slots_pp" : "k_vote_slots",
+                 use_full ? "full-SA" : "sampled-SA", b->use_fixed ? "own-slots" : "shards");
         b->path = std::string("reads=") + (b->fasta ? "fasta " : "fastq ") + buf;
         GM_TRACE("path: %s", buf);
     }
@@ -2034,6 +2040,7 @@ extern "C" int gm_dev_nw_score(gm_index* ix, const gm_params* p, const gm_reads*
         uint32_t qlo = 255, qhi = 0;
         for (uint32_t r = 0; r < reads->n && !b->fasta; ++r)
             for (uint32_t i = 0; i < reads->len[r] && i < reads->stride; ++i) { const uint32_t qc = reads->quals[(size_t)r * reads->stride + i]; qlo = std::min(qlo, qc); qhi = std::max(qhi, qc); }
+        GM_TRACE("dev_nw_score: %u probes, nw=%s", n, gmk_nw_form(dp, b->dev, n, rows_len, qlo, qhi));
         if (gmk_nw(ix->dev, dp, b->dev, n, rows_len, qlo, qhi, nullptr)) { rc = GM_E_HIP; break; }
         if (n && hipMemcpy(c.data(), b->cands.p, (size_t)n * sizeof(GmCand), hipMemcpyDeviceToHost) != hipSuccess) { rc = GM_E_HIP; break; }
     } while (0);
@@ -2063,6 +2070,7 @@ extern "C" int gm_dev_traceback(gm_index* ix, const gm_params* p, const gm_reads
         if (n && hipMemcpy(b->tb_items.p, c.data(), (size_t)n * sizeof(GmCand), hipMemcpyHostToDevice) != hipSuccess) { rc = GM_E_HIP; break; }
         if (n && hipMemset(b->tb_ops.p, 0, (size_t)n * ow * 8) != hipSuccess) { rc = GM_E_HIP; break; }
         if (p->max_gap != 3) { if (b->band_moves.ensure(gm_band_moves_words(n, b->stride) * 8)) { rc = GM_E_NOMEM; break; } fill_dev_batch(b); }
+        GM_TRACE("dev_traceback: %u probes, traceback=%s", n, gmk_traceback_form(dp, b->dev));
         if (gmk_traceback(ix->dev, dp, b->dev, b->tb_items.as<GmCand>(), n, b->tb_ops.as<unsigned long long>(), ow, b->tb_len.as<uint16_t>(), nullptr, nullptr, nullptr, nullptr)) { rc = GM_E_HIP; break; }
         if (n && hipMemcpy(packed.data(), b->tb_ops.p, (size_t)n * ow * 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = GM_E_HIP; break; }
         if (n && hipMemcpy(ops_len, b->tb_len.p, (size_t)n * 2, hipMemcpyDeviceToHost) != hipSuccess) { rc = GM_E_HIP; break; }

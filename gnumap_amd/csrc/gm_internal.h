@@ -277,6 +277,7 @@ int gmk_sa_interval(const GmDevIndex& ix, const uint8_t* kmers, uint32_t n, uint
 int gmk_locate(const GmDevIndex& ix, const uint32_t* ranks, uint32_t n, int use_full_sa, uint32_t* out, void* stream);
 // traceback operations: 2 bits each (0 M, 1 I, 2 D), operation k in 64-bit word k / 32 at bits 2 (k % 32); ops_words words per item
 inline uint32_t gm_ops_words(uint32_t stride) { return (2u * ((stride + 7u) & ~7u) + 8u + 31u) / 32u; }
+const char* gmk_traceback_form(const GmDevParams& p, const GmDevBatch& b);      // the kernel gmk_traceback launches for this block
 int gmk_traceback(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, const GmCand* items, uint32_t n,
                   unsigned long long* ops, uint32_t ops_words, uint16_t* ops_len, const uint8_t* emit, uint32_t* cig_cnt, uint32_t* max_span, void* stream);
 int gmk_scan_u32(const uint32_t* in, uint64_t n, uint64_t* out, unsigned long long* tmp, void* stream);

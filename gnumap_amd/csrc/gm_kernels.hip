@@ -3483,10 +3483,15 @@ static bool nw_rows_ok(const GmDevParams& p, const GmDevBatch& b, uint32_t rows_
     return p.max_gap == 3 && p.nw && !gm_opt_is("GM_NW", "wave") && !gm_opt_is("GM_NW", "lane") && rows_len >= 24 && rows_len <= 152 && rows_len <= b.stride;
 }
 const char* gmk_nw_form(const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, uint32_t qual_lo, uint32_t qual_hi) {
-    (void)n_cands;
     if (p.max_gap != 3) return "k_nw_band";
     if (nw_rows_ok(p, b, rows_len)) return gmk_nw_rows_pairs(b, rows_len, qual_lo, qual_hi) ? "k_nw_rows/pairs" : "k_nw_rows/cells";
-    return gm_opt_is("GM_NW", "wave") ? "k_nw" : "k_nw_lane";
+    if (gm_opt_is("GM_NW", "wave")) return "k_nw";
+    // (gmk_nw's choice among the forms of k_nw_lane; keep in step with it)
+    const int rows_in_regs = (int)gm_opt_ll("GM_NW_ROWS", 1);
+    const bool sparse = rows_in_regs && n_cands < 2.5 * b.n;
+    if (sparse && b.stride <= 104) return rows_in_regs == 2 ? "k_nw_lane<13,lds>" : "k_nw_lane<13>";
+    if (sparse && b.stride <= 152) return rows_in_regs == 2 ? "k_nw_lane<19,lds>" : "k_nw_lane<19>";
+    return "k_nw_lane<0>";
 }
 
 int gmk_nw(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, uint32_t qual_lo, uint32_t qual_hi, void* stream) {
@@ -3596,6 +3601,18 @@ int gmk_traceback(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& 
     uint32_t grid = cdiv(n, G); if (grid > 8192) grid = 8192;
     hipLaunchKernelGGL(k_traceback, dim3(grid), dim3(threads), lds, S_(stream), ix, p, b, items, n, ops, ops_words, ops_len, Lp, mvw, emit, cig_cnt, max_span);
     return (int)hipGetLastError();
+}
+
+// which kernel gmk_traceback launches for this block (keep in step with it): what the unit probe's trace line names
+const char* gmk_traceback_form(const GmDevParams& p, const GmDevBatch& b) {
+    if (p.max_gap != 3) return "k_traceback_band";
+    const uint32_t Lp = lp_of(b.stride);
+    if (gm_opt_is("GM_TRACEBACK", "group") || Lp > 511) return "k_traceback";
+    uint32_t ntab = (gm_opt_is("GM_TRACEBACK", "direct") || b.fasta) ? 0u : (b.illumina_until ? 2u : 1u);
+    const size_t mv_bytes = ((size_t)(Lp + 1) * (Lp <= 255 ? 128 : 64) * 2 + 15) & ~(size_t)15;
+    if (mv_bytes + (size_t)ntab * GM_TBV_ENTRIES * 16 > 65536) ntab = 0;
+    if (Lp <= 255) return ntab ? "k_traceback_lane<128>/table" : "k_traceback_lane<128>/direct";
+    return ntab ? "k_traceback_lane<64>/table" : "k_traceback_lane<64>/direct";
 }
 
 int gmk_coverage_add(float* cov, uint64_t bins, uint32_t bin_size, const uint64_t* pos, const uint32_t* span, const float* w,

@@ -184,3 +184,72 @@ def test_cli_maps_a_too_large_block_in_halves(mode, tmp_path):
     assert "".join(l for l in open(out + ".sam") if not l.startswith("@PG")) == ref_text(mode, "sam")
     ext = "sgr" if "sgr" in m["tracks"] else "gmp"
     compare_tracks(open(out + "." + ext).read(), ref_text(mode, ext), 3 if ext == "sgr" else 8)
+
+
+# ------------------------------------------------------------------ the edges of the reference (tests/golden/make_edge_fixtures.py)
+import edge_fixture as ef                                                  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def edge_fa(tmp_path_factory):
+    return ef.build_index(tmp_path_factory)
+
+
+def _edge_track_has_every_contig_edge(text, edge_fa):
+    """what stands in for compare_tracks' `len(b) > 100` on this small genome: in the bin-size-1 mode the reference's track has a row
+    for the first and for the last position of every contig, so the rows compared include the ones this fixture is about"""
+    rows = {(f[0], int(f[1])) for f in (l.split("\t") for l in text.splitlines())}
+    ann = open(edge_fa + ".gnumap.ann").read().split("\n")
+    contigs = [(ann[i].split()[1], int(ann[i + 1].split()[1])) for i in range(1, len(ann) - 1, 2)]
+    assert len(contigs) == 3
+    for name, n in contigs:
+        assert (name, 1) in rows and (name, n) in rows, name
+
+
+def _edge_compare_tracks(mine, ref, ncol):
+    """compare_tracks without its size guard (the edge genome's tracks have fewer than 100 rows at bin size 8): same tolerance"""
+    a, b = track(mine, ncol), track(ref, ncol)
+    assert len(b) > 50
+    for k in set(a) ^ set(b):
+        assert (a.get(k) or b.get(k))[0] < 2e-3, k
+    for k in set(a) & set(b):
+        for x, y in zip(a[k], b[k]):
+            assert abs(x - y) <= 1e-4 * max(1.0, abs(y)) + 2e-5, (k, x, y)
+
+
+EDGE_VARIANTS = {"full_sa": [], "bucket": [], "sampled_sa": ["--locate=sampled"], "batch64": ["--batch=64", "--workers=2"], "sam_text_device": ["--sam_text=device"]}
+
+
+@pytest.mark.parametrize("variant", list(EDGE_VARIANTS))
+@pytest.mark.parametrize("mode", sorted(ef.MANIFEST))
+def test_cli_on_the_edge_genome_equals_reference_program(mode, variant, edge_fa, tmp_path):
+    """the reference's argv on edge.fa / edge.fq: reads at and across every contig start and end, seeds that clamp to window start 0,
+    contigs that begin inside a 16-base word; SAM byte-identical, tracks up to the order of the fp32 atomic adds"""
+    m = ef.MANIFEST[mode]
+    env = dict(os.environ)
+    if variant == "bucket":
+        mer, jump, k = _seed_flags(m["argv"])
+        longest = 150 if m["fastq"] == "edge_mixed.fq" else 100
+        max_reg = (longest - mer + jump - 1) // jump
+        if k < 2:
+            pytest.skip("k_vote_bucket needs -k >= 2")
+        assert max_reg <= 32
+        env.update(GM_SEED_BUCKET="1", GM_TRACE="1", GM_KMER_TABLE=str(mer))
+    out = str(tmp_path / "mine")
+    r = subprocess.run([EXE, "-g", edge_fa, "-o", out, "-a", "0.9"] + m["argv"] + EDGE_VARIANTS[variant] + [os.path.join(GOLDEN, m["fastq"])],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    if variant == "bucket":                                     # at most 16 seeds per strand: two reads per wavefront, else one
+        assert ("k_vote_pair<" if max_reg <= 16 else "k_vote_bucket<") in r.stderr, r.stderr[-1500:]
+    sam = "".join(l for l in open(out + ".sam") if not l.startswith("@PG"))
+    ref = ef.ref_text(mode, "sam").decode()
+    if sam != ref:
+        a, b = sam.splitlines(), ref.splitlines()
+        first = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+        pytest.fail(f"{mode}: {len(a)} vs {len(b)} lines, first difference at line {first}:\n  mine {a[first] if first < len(a) else None}\n  ref  {b[first] if first < len(b) else None}")
+    ext = "sgr" if "sgr" in m["tracks"] else "gmp"
+    assert not os.path.exists(out + (".gmp" if ext == "sgr" else ".sgr"))
+    ref_track = ef.ref_text(mode, ext).decode()
+    if mode == "bin1":
+        _edge_track_has_every_contig_edge(ref_track, edge_fa)
+    _edge_compare_tracks(open(out + "." + ext).read(), ref_track, 3 if ext == "sgr" else 8)
