@@ -27,6 +27,10 @@ class gm_index_info(C.Structure):
                 ("sa_intv", C.c_uint32), ("n_seqs", C.c_uint32), ("device_id", C.c_int), ("full_sa", C.c_int), ("hbm_bytes", u64)]
 
 
+class gm_track_text_stats(C.Structure):
+    _fields_ = [("rows", u64), ("bytes", u64), ("slabs", u64), ("host_slabs", u64), ("launches", u64), ("kernel_ms", C.c_double)]
+
+
 class gm_params(C.Structure):
     _fields_ = [("mer", C.c_int), ("jump", C.c_int), ("min_seed_hits", C.c_int), ("max_kmer_hits", C.c_uint32), ("max_matches", C.c_uint32),
                 ("max_gap", C.c_int), ("nw", C.c_int), ("fast", C.c_int), ("unique_only", C.c_int), ("pos_strand", C.c_int), ("neg_strand", C.c_int),
@@ -96,6 +100,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
            "gm_coverage_device_ptr", "gm_coverage_add", "gm_coverage_download", "gm_coverage_allreduce", "gm_coverage_write_sgr", "gm_coverage_enable_nuc", "gm_coverage_nuc_device_ptr",
            "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls",
+           "gm_coverage_write_sgr_device", "gm_coverage_write_gmp_device", "gm_coverage_text", "gm_coverage_text_stats",
            "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim",
            "gm_batch_set_read_format", "gm_index_set_probe_format"]
 
@@ -170,6 +175,10 @@ def load_library():
     L.gm_snp_calls.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
     L.gm_dev_snp_stat.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gm_coverage_write_gmp_calls.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_char_p, C.c_int]
+    L.gm_coverage_write_sgr_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.gm_coverage_write_gmp_device.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_char_p, C.c_int]
+    L.gm_coverage_text.argtypes = [C.c_void_p, C.POINTER(gm_params), u64, u64, C.c_void_p, u64, C.POINTER(u64)]
+    L.gm_coverage_text_stats.argtypes = [C.c_void_p, C.POINTER(gm_track_text_stats)]
     L.gm_batch_set_adaptor.argtypes = [C.c_void_p, C.c_char_p]
     L.gm_batch_trimmed_len.argtypes = [C.c_void_p, C.c_void_p]
     L.gm_batch_adaptor_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(u64)]
@@ -403,6 +412,35 @@ class Index:
     def coverage_write_gmp_calls(self, path, pval=0.001, monop=False):
         """gm_coverage_write_gmp_calls: --snp's .gmp with the likelihood-ratio column, straight from the tracks in HBM"""
         _chk(lib().gm_coverage_write_gmp_calls(self.h, pval, int(monop), os.fsencode(path), 0))
+
+    # ---- track files formatted on the device (k_track_sizes / k_track_rows) ----
+    def coverage_text(self, params=None, lo=0, hi=None):
+        """gm_coverage_text: the rows of bins [lo, hi) as bytes; params None or normal mode = .sgr rows, else the .gmp rows of its mode"""
+        hi = self.coverage_bins() if hi is None else hi
+        p = C.byref(getattr(params, "c", params)) if params is not None else None      # a Params or a gm_params
+        cap = 1 << 16
+        while True:
+            buf = C.create_string_buffer(cap); got = u64()
+            rc = lib().gm_coverage_text(self.h, p, lo, hi, buf, cap, C.byref(got))
+            if rc == GM_E_CAPACITY:
+                cap = int(got.value)
+                continue
+            _chk(rc)
+            return buf.raw[:got.value]
+
+    def coverage_write_sgr_device(self, path, append=False):
+        """gm_coverage_write_sgr_device: <out>.sgr from the track in HBM, the bytes of coverage_write_sgr"""
+        _chk(lib().gm_coverage_write_sgr_device(self.h, os.fsencode(path), int(append)))
+
+    def coverage_write_gmp_device(self, params, path, append=False):
+        """gm_coverage_write_gmp_device: the eight-column <out>.gmp of -b / --b2 / -d / --snp from the tracks in HBM"""
+        _chk(lib().gm_coverage_write_gmp_device(self.h, C.byref(getattr(params, "c", params)), os.fsencode(path), int(append)))
+
+    def coverage_text_stats(self):
+        """rows, bytes, slabs, host_slabs, launches, kernel_ms of the last of the three calls above"""
+        st = gm_track_text_stats()
+        _chk(lib().gm_coverage_text_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in gm_track_text_stats._fields_}
 
 
 class Batch:

@@ -122,6 +122,7 @@ struct gm_index {
     std::mutex mu;
     uint64_t hbm_bytes = 0;
     int probe_format = GM_READS_FASTQ;      // gm_index_set_probe_format: how the unit probes read their gm_reads
+    gm_track_text_stats tt_stats{};         // of the last gm_coverage_write_*_device / gm_coverage_text
 };
 
 struct gm_batch {
@@ -553,6 +554,21 @@ extern "C" uint64_t gm_index_contig_offset(const gm_index* ix, uint32_t i) {
     if (!ix) return 0;
     if (i >= ix->h.contigs.size()) return ix->h.l_pac;
     return ix->h.contigs[i].offset;
+}
+
+// contig names back to back + n_seqs + 1 offsets in HBM, once per index: what k_out_text_rows and k_track_rows print
+static int index_cnames(gm_index* ix) {
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->cnames_on) return GM_OK;
+    const uint32_t n_seqs = (uint32_t)ix->h.contigs.size();
+    std::string all; std::vector<uint32_t> off(n_seqs + 1, 0);
+    for (uint32_t i = 0; i < n_seqs; ++i) { off[i] = (uint32_t)all.size(); all += ix->h.contigs[i].name; }
+    off[n_seqs] = (uint32_t)all.size();
+    if (ix->d_cnames.ensure(all.size() + 16) || ix->d_cname_off.ensure(off.size() * 4)) return GM_E_NOMEM;
+    HIPCHK(hipMemcpy(ix->d_cnames.p, all.data(), all.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ix->d_cname_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    ix->cnames_on = true;
+    return GM_OK;
 }
 
 static uint32_t host_pos2rid(const GmHostIndex& h, uint64_t pos) {      // bns_pos2rid src/bntseq.c:349-363
@@ -1761,19 +1777,7 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
         // ---- SAM text: tails + row lengths, their scan, then - once the caller's buffer is known to hold them - the rows ----
         tout->n_recs = n_recs;
         if (n_recs) {
-            const uint32_t n_seqs = (uint32_t)ix->h.contigs.size();
-            {   // contig names, once per index
-                std::lock_guard<std::mutex> lk(ix->mu);
-                if (!ix->cnames_on) {
-                    std::string all; std::vector<uint32_t> off(n_seqs + 1, 0);
-                    for (uint32_t i = 0; i < n_seqs; ++i) { off[i] = (uint32_t)all.size(); all += ix->h.contigs[i].name; }
-                    off[n_seqs] = (uint32_t)all.size();
-                    if (ix->d_cnames.ensure(all.size() + 16) || ix->d_cname_off.ensure(off.size() * 4)) return GM_E_NOMEM;
-                    HIPCHK(hipMemcpy(ix->d_cnames.p, all.data(), all.size(), hipMemcpyHostToDevice));
-                    HIPCHK(hipMemcpy(ix->d_cname_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-                    ix->cnames_on = true;
-                }
-            }
+            if (const int rc = index_cnames(ix)) return rc;                // contig names, once per index
             const uint64_t name_bytes = rt->name_off[n] - rt->name_off[0], tail_bytes = rt->qual_tail_off ? rt->qual_tail_off[n] - rt->qual_tail_off[0] : 0;
             if (b->t_names.ensure((size_t)name_bytes + 16) || b->t_nameoff.ensure(((size_t)n + 1) * 8) || b->t_slots.ensure((size_t)n_recs * 64) ||
                 b->t_rowlen.ensure((size_t)n_recs * 4) || b->t_rowoff.ensure(((size_t)n_recs + 1) * 8) || b->t_bad.ensure(8) ||
@@ -2242,29 +2246,49 @@ template <class Emit> static int write_track_text(const char* path, int append, 
     return write_track_text(path, append, nb, max_line, emit, [](uint64_t, uint64_t) { return 0; });
 }
 
+// one row of a track file: the emitter of every writer below.  bins[k - base] is bin k, nuc[q * nuc_stride + k - base] its sum q (a writer
+// that holds one slab of the tracks passes the slab's first bin as base); i = the caller's contig cursor, looked up at the first bin of a run
+struct TrackEmit {
+    const GmHostIndex& h; uint64_t bs; int kind; char want;               // kind: GM_TRACK_*; want: the reference base of GM_TRACK_BASE
+    const float* bins; const float* nuc; uint64_t nuc_stride, base;
+    char* operator()(uint64_t k, char* w, int& i, bool first) const {
+        // the reference walks `count` over the concatenated coordinate in steps of bin_size without resetting it per contig,
+        // so bin k is printed under the contig that holds k * bin_size
+        const uint64_t count = k * bs;
+        if (first) i = (int)host_pos2rid(h, count);
+        while ((size_t)i + 1 < h.contigs.size() && count >= h.contigs[(size_t)i + 1].offset) ++i;
+        const float total = bins[k - base];
+        if (kind == GM_TRACK_SGR) { if (!((double)total > 0.001)) return w; }       // MIN_PRINT, GenomeBwt.cpp:928
+        else if (kind == GM_TRACK_SNP) { if (!(total > 0.001f)) return w; }
+        else {
+            const char at = "acgt"[(h.pac[count >> 2] >> ((~count & 3) << 1)) & 3];
+            if (at != want || !(total > 0.0f)) return w;
+        }
+        const GmContig& cg = h.contigs[(size_t)i];
+        memcpy(w, cg.name.data(), cg.name.size()); w += cg.name.size();
+        *w++ = '\t'; w = put_long(w, (long)(count - cg.offset) + 1); *w++ = '\t';
+        w = put_fixed(w, total, kind == GM_TRACK_BASE ? 6 : 5);                     // "%f" of the total in the base-filtered .gmp
+        if (kind != GM_TRACK_SGR) for (int q = 0; q < 5; ++q) { *w++ = '\t'; w = put_fixed(w, nuc[(uint64_t)q * nuc_stride + k - base], 5); }
+        *w++ = '\n';
+        return w;
+    }
+};
+static size_t max_contig_name(const GmHostIndex& h) {
+    size_t m = 0;
+    for (const auto& c : h.contigs) m = std::max(m, c.name.size());
+    return m;
+}
+static char gmp_want(int mode) { return mode == GM_MODE_BS ? 'c' : mode == GM_MODE_BS2 ? 'g' : mode == GM_MODE_ATOG ? 'a' : 't'; }
+
 extern "C" int gm_coverage_write_sgr(gm_index* ix, const float* bins, const char* path, int append) {
     // GenomeBwt::PrintFinalSGR src/GenomeBwt.cpp:1212-1273: bins run over the CONCATENATED coordinate
     if (!ix || !bins || !path || !ix->cov_bin_size) return GM_E_ARG;
     const GmHostIndex& h = ix->h;
     const uint64_t bs = ix->cov_bin_size;
-    // the reference walks `count` over the concatenated coordinate in steps of bin_size without resetting it per contig,
-    // so bin k is printed under the contig that holds k * bin_size
     const uint64_t nb = (h.l_pac + bs - 1) / bs;
-    size_t max_name = 0;
-    for (const auto& c : h.contigs) max_name = std::max(max_name, c.name.size());
     std::vector<int> cur(host_threads(), 0);
-    return write_track_text(path, append, nb, max_name + 48, [&](uint64_t k, char* w, unsigned c, bool first) -> char* {
-        int& i = cur[c];
-        const uint64_t count = k * bs;
-        if (first) i = (int)host_pos2rid(h, count);
-        while ((size_t)i + 1 < h.contigs.size() && count >= h.contigs[(size_t)i + 1].offset) ++i;
-        if (!((double)bins[k] > 0.001)) return w;       // MIN_PRINT, GenomeBwt.cpp:928
-        const GmContig& cg = h.contigs[(size_t)i];
-        memcpy(w, cg.name.data(), cg.name.size()); w += cg.name.size();
-        *w++ = '\t'; w = put_long(w, (long)(count - cg.offset) + 1); *w++ = '\t';
-        w = put_fixed(w, bins[k], 5); *w++ = '\n';
-        return w;
-    });
+    const TrackEmit e{ h, bs, GM_TRACK_SGR, 0, bins, nullptr, 0, 0 };
+    return write_track_text(path, append, nb, max_contig_name(h) + 48, [&](uint64_t k, char* w, unsigned c, bool first) -> char* { return e(k, w, cur[c], first); });
 }
 
 extern "C" int gm_coverage_enable_nuc(gm_index* ix) {
@@ -2290,48 +2314,12 @@ extern "C" int gm_coverage_write_gmp(gm_index* ix, const gm_params* p, const flo
     if (!ix || !p || !bins || !nuc || !path || !ix->cov_bin_size || p->mode == GM_MODE_NORMAL) return GM_E_ARG;
     const GmHostIndex& h = ix->h;
     const uint64_t bs = ix->cov_bin_size, nb = ix->cov_bins;
-    if (p->mode == GM_MODE_SNP) {
-        // GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1090 up to the per-nucleotide columns: every position whose total is above MIN_PRINT,
-        // "%.5f" for all six numbers.  The line ends here; gm_coverage_write_gmp_calls writes the same rows with PrintSNPCall's column behind them.
-        const uint64_t nbk = (h.l_pac + bs - 1) / bs;
-        size_t max_name = 0;
-        for (const auto& c : h.contigs) max_name = std::max(max_name, c.name.size());
-        std::vector<int> cur(host_threads(), 0);
-        return write_track_text(path, append, nbk, max_name + 160, [&](uint64_t k, char* w, unsigned c, bool first) -> char* {
-            int& i = cur[c];
-            const uint64_t count = k * bs;
-            if (first) i = (int)host_pos2rid(h, count);
-            while ((size_t)i + 1 < h.contigs.size() && count >= h.contigs[(size_t)i + 1].offset) ++i;
-            if (!(bins[k] > 0.001f)) return w;
-            const GmContig& cg = h.contigs[(size_t)i];
-            memcpy(w, cg.name.data(), cg.name.size()); w += cg.name.size();
-            *w++ = '\t'; w = put_long(w, (long)(count - cg.offset) + 1); *w++ = '\t';
-            w = put_fixed(w, bins[k], 5);
-            for (int q = 0; q < 5; ++q) { *w++ = '\t'; w = put_fixed(w, nuc[(uint64_t)q * nb + k], 5); }
-            *w++ = '\n';
-            return w;
-        });
-    }
-    const char want = p->mode == GM_MODE_BS ? 'c' : p->mode == GM_MODE_BS2 ? 'g' : p->mode == GM_MODE_ATOG ? 'a' : 't';
     const uint64_t nbk = (h.l_pac + bs - 1) / bs;
-    size_t max_name = 0;
-    for (const auto& c : h.contigs) max_name = std::max(max_name, c.name.size());
     std::vector<int> cur(host_threads(), 0);
-    return write_track_text(path, append, nbk, max_name + 160, [&](uint64_t k, char* w, unsigned c, bool first) -> char* {
-        int& i = cur[c];
-        const uint64_t count = k * bs;
-        if (first) i = (int)host_pos2rid(h, count);
-        while ((size_t)i + 1 < h.contigs.size() && count >= h.contigs[(size_t)i + 1].offset) ++i;
-        const char at = "acgt"[(h.pac[count >> 2] >> ((~count & 3) << 1)) & 3];
-        if (at != want || !(bins[k] > 0.0f)) return w;
-        const GmContig& cg = h.contigs[(size_t)i];
-        memcpy(w, cg.name.data(), cg.name.size()); w += cg.name.size();
-        *w++ = '\t'; w = put_long(w, (long)(count - cg.offset) + 1); *w++ = '\t';
-        w = put_fixed(w, bins[k], 6);                                         // "%f"
-        for (int q = 0; q < 5; ++q) { *w++ = '\t'; w = put_fixed(w, nuc[(uint64_t)q * nb + k], 5); }
-        *w++ = '\n';
-        return w;
-    });
+    // GM_MODE_SNP: GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1090 up to the per-nucleotide columns: every position whose total is above MIN_PRINT,
+    // "%.5f" for all six numbers.  The line ends here; gm_coverage_write_gmp_calls writes the same rows with PrintSNPCall's column behind them.
+    const TrackEmit e{ h, bs, p->mode == GM_MODE_SNP ? GM_TRACK_SNP : GM_TRACK_BASE, gmp_want(p->mode), bins, nuc, nb, 0 };
+    return write_track_text(path, append, nbk, max_contig_name(h) + 160, [&](uint64_t k, char* w, unsigned c, bool first) -> char* { return e(k, w, cur[c], first); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2450,4 +2438,181 @@ extern "C" int gm_coverage_write_gmp_calls(gm_index* ix, float snp_pval, int mon
         *w++ = '\n';
         return w;
     }, slab);
+}
+
+// ------------------------------------------------------------------------------------------------
+// track files formatted on the device (gm_tracktext.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct ScopedEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~ScopedEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+// where the text goes: a file at a running offset, or the first cap bytes into the caller's buffer; `total` counts everything
+struct TrackSink {
+    int fd = -1; uint64_t file_off = 0;
+    char* mem = nullptr; uint64_t cap = 0;
+    uint64_t total = 0;
+    uint64_t room() const { return fd >= 0 ? ~0ull : (cap > total ? cap - total : 0); }
+    bool put(const char* q, uint64_t n) {                    // host text
+        if (fd >= 0) {
+            uint64_t at = file_off, left = n;
+            while (left) { const ssize_t k = ::pwrite(fd, q, (size_t)left, (off_t)at); if (k <= 0) return false; q += k; left -= (uint64_t)k; at += (uint64_t)k; }
+            file_off += n;
+        } else if (const uint64_t m = std::min(n, room())) memcpy(mem + total, q, (size_t)m);
+        total += n;
+        return true;
+    }
+};
+
+// bins [lo, hi) as rows: per slab of GM_TRACK_SLICE bins the sizes pass and its scan, the 32 bytes of `meta` read back, a text buffer of
+// exactly that size, the rows pass, and the text down in pieces of 32 MB through two page-locked buffers (the copy of one piece runs
+// while the one before it is written).  A slab whose meta says that a printed value needs snprintf is formatted here from its own tracks.
+int track_text_run(gm_index* ix, const char* call, int kind, char want, uint64_t lo, uint64_t hi, TrackSink& out) {
+    HIPCHK(hipSetDevice(ix->device));
+    if (const int rc = index_cnames(ix)) return rc;
+    const GmHostIndex& h = ix->h;
+    const uint64_t bs = ix->cov_bin_size, bins = ix->cov_bins, nbk = (h.l_pac + bs - 1) / bs;      // the files print the bins that start below l_pac
+    hi = std::min(hi, nbk); lo = std::min(lo, hi);
+    const uint64_t per = (uint64_t)std::min<long long>(std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 24)), 1ll << 26);      // bins per slab
+    const size_t piece = (size_t)32 << 20;
+    gm_track_text_stats st{};
+    ix->tt_stats = st;
+    const uint32_t tiles_max = gmk_track_tiles(std::min(per, hi - lo));
+    Scoped<DevBuf> d_len, d_off, d_meta, d_text;
+    Scoped<PinBuf> h_meta, h_txt[2];
+    ScopedEvents ev;
+    if (d_len.ensure((size_t)tiles_max * 4 + 4) || d_off.ensure(((size_t)tiles_max + 1) * 8) || d_meta.ensure(TT_META_N * 8) || h_meta.ensure(TT_META_N * 8)) return GM_E_NOMEM;
+    HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
+    GmDevTrack t{};
+    t.cov = ix->d_cov.as<float>(); t.nuc = kind == GM_TRACK_SGR ? nullptr : ix->d_nuc.as<float>(); t.nuc_stride = bins;
+    t.pac = ix->dev.pac; t.contig_off = ix->dev.contig_off; t.n_seqs = ix->dev.n_seqs;
+    t.cnames = ix->d_cnames.as<char>(); t.cname_off = ix->d_cname_off.as<uint32_t>();
+    t.bin_size = (uint32_t)bs; t.kind = (uint32_t)kind; t.want = want == 'a' ? 0u : want == 'c' ? 1u : want == 'g' ? 2u : 3u;
+    t.tile_len = d_len.as<uint32_t>(); t.tile_off = d_off.as<unsigned long long>(); t.meta = d_meta.as<unsigned long long>();
+    const hipStream_t s = nullptr;
+    const unsigned long long* meta = h_meta.as<unsigned long long>();
+    const size_t max_line = max_contig_name(h) + 160;
+    std::vector<float> hf; std::vector<char> hbuf;          // a host-formatted slab's tracks and text
+    auto fail_io = [&]() { gm_set_error(std::string(call) + ": write failed"); return GM_E_IO; };
+    for (uint64_t s0 = lo; s0 < hi; s0 += per) {
+        const uint64_t n = std::min(per, hi - s0);
+        float ms = 0;
+        t.lo = s0; t.n = n; t.text = nullptr;
+        HIPCHK(hipMemsetAsync(d_meta.p, 0, TT_META_N * 8, s));
+        HIPCHK(hipEventRecord(ev.a, s));
+        KCHK(gmk_track_sizes(t, s));
+        HIPCHK(hipEventRecord(ev.b, s));
+        HIPCHK(hipMemcpyAsync(h_meta.p, d_meta.p, TT_META_N * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
+        st.kernel_ms += ms; st.launches += 2; ++st.slabs;
+        const uint64_t bytes = meta[TT_META_BYTES];
+        if (meta[TT_META_HOST]) {                            // the host emitters, from this slab's tracks only
+            ++st.host_slabs;
+            const int cols = kind == GM_TRACK_SGR ? 1 : 6;
+            hf.resize((size_t)n * cols);
+            HIPCHK(hipMemcpy(hf.data(), t.cov + s0, n * 4, hipMemcpyDeviceToHost));
+            for (int q = 1; q < cols; ++q) HIPCHK(hipMemcpy(hf.data() + (size_t)q * n, t.nuc + (uint64_t)(q - 1) * bins + s0, n * 4, hipMemcpyDeviceToHost));
+            const TrackEmit e{ h, bs, kind, want, hf.data(), hf.data() + n, n, s0 };
+            int cur = 0;
+            for (uint64_t k0 = s0; k0 < s0 + n; k0 += 65536) {
+                const uint64_t k1 = std::min(s0 + n, k0 + 65536);
+                hbuf.resize((size_t)(k1 - k0) * max_line);
+                char* w = hbuf.data();
+                for (uint64_t k = k0; k < k1; ++k) { char* const w2 = e(k, w, cur, k == k0); st.rows += w2 != w; w = w2; }
+                if (!out.put(hbuf.data(), (uint64_t)(w - hbuf.data()))) return fail_io();
+            }
+            continue;
+        }
+        st.rows += meta[TT_META_ROWS];
+        const uint64_t need = std::min(bytes, out.room());   // what has to come down
+        if (need) {
+            if (d_text.ensure((size_t)bytes + 16)) return GM_E_NOMEM;
+            t.text = d_text.as<char>();
+            HIPCHK(hipEventRecord(ev.a, s));
+            KCHK(gmk_track_rows(t, s));
+            HIPCHK(hipEventRecord(ev.b, s));
+            ++st.launches;
+            if (out.fd < 0) HIPCHK(hipMemcpy(out.mem + out.total, t.text, (size_t)need, hipMemcpyDeviceToHost));
+            else {
+                const char* prev = nullptr; size_t prev_n = 0; int c = 0;
+                for (uint64_t done = 0; done < bytes; c ^= 1) {
+                    const size_t m = (size_t)std::min<uint64_t>(piece, bytes - done);
+                    if (h_txt[c].ensure(m)) return GM_E_NOMEM;
+                    HIPCHK(hipMemcpyAsync(h_txt[c].p, t.text + done, m, hipMemcpyDeviceToHost, s));
+                    if (prev && !out.put(prev, prev_n)) return fail_io();
+                    HIPCHK(hipStreamSynchronize(s));
+                    prev = h_txt[c].as<char>(); prev_n = m; done += m;
+                }
+                if (prev && !out.put(prev, prev_n)) return fail_io();
+                out.total -= bytes;                          // counted below
+            }
+            HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
+            st.kernel_ms += ms;
+        }
+        out.total += bytes;
+    }
+    st.bytes = out.total;
+    ix->tt_stats = st;
+    return GM_OK;
+}
+
+// the checks the three entry points share; kind / want from the mode
+int track_text_args(gm_index* ix, const gm_params* p, const char* call, int& kind, char& want) {
+    if (!ix->cov_bins || !ix->cov_bin_size) { gm_set_error(std::string(call) + ": no coverage track (gm_coverage_reset)"); return GM_E_ARG; }
+    const int mode = p ? p->mode : GM_MODE_NORMAL;
+    kind = mode == GM_MODE_NORMAL ? GM_TRACK_SGR : mode == GM_MODE_SNP ? GM_TRACK_SNP : GM_TRACK_BASE;
+    want = gmp_want(mode);
+    if (ix->host_only) { gm_set_error(std::string(call) + ": no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (kind != GM_TRACK_SGR && !ix->nuc_on) { gm_set_error(std::string(call) + ": the .gmp rows read the per-nucleotide tracks: call gm_coverage_enable_nuc first"); return GM_E_ARG; }
+    return GM_OK;
+}
+
+int track_text_file(gm_index* ix, const gm_params* p, const char* call, const char* path, int append) {
+    int kind; char want;
+    if (const int rc = track_text_args(ix, p, call, kind, want)) return rc;
+    // no O_APPEND: pwrite() on such a descriptor ignores its offset (see write_track_text)
+    const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
+    if (fd < 0) { gm_set_error(std::string(call) + ": cannot write " + path); return GM_E_IO; }
+    TrackSink out;
+    out.fd = fd; out.file_off = append ? (uint64_t)lseek(fd, 0, SEEK_END) : 0;
+    const int rc = track_text_run(ix, call, kind, want, 0, ix->cov_bins, out);
+    ::close(fd);
+    return rc;
+}
+}  // namespace
+
+extern "C" int gm_coverage_write_sgr_device(gm_index* ix, const char* path, int append) {
+    // GenomeBwt::PrintFinalSGR src/GenomeBwt.cpp:1212-1273, from the track in HBM
+    if (!ix || !path) { gm_set_error("gm_coverage_write_sgr_device: null argument"); return GM_E_ARG; }
+    return track_text_file(ix, nullptr, "gm_coverage_write_sgr_device", path, append);
+}
+
+extern "C" int gm_coverage_write_gmp_device(gm_index* ix, const gm_params* p, const char* path, int append) {
+    // GenomeBwt::PrintFinalBisulfite src/GenomeBwt.cpp:1092-1210, PrintFinalSNP :930-1009 (eight columns), from the tracks in HBM
+    if (!ix || !p || !path) { gm_set_error("gm_coverage_write_gmp_device: null argument"); return GM_E_ARG; }
+    if (p->mode == GM_MODE_NORMAL) { gm_set_error("gm_coverage_write_gmp_device: GM_MODE_NORMAL writes an .sgr (gm_coverage_write_sgr_device)"); return GM_E_ARG; }
+    return track_text_file(ix, p, "gm_coverage_write_gmp_device", path, append);
+}
+
+extern "C" int gm_coverage_text(gm_index* ix, const gm_params* p, uint64_t bin_lo, uint64_t bin_hi, char* text, uint64_t cap, uint64_t* n_out) {
+    if (!ix || !n_out || (cap && !text)) { gm_set_error("gm_coverage_text: null argument"); return GM_E_ARG; }
+    int kind; char want;
+    if (!ix->cov_bins || !ix->cov_bin_size) { gm_set_error("gm_coverage_text: no coverage track (gm_coverage_reset)"); return GM_E_ARG; }
+    if (bin_lo > bin_hi || bin_hi > ix->cov_bins) { gm_set_error("gm_coverage_text: bins [bin_lo, bin_hi) are not a range of the track"); return GM_E_ARG; }
+    if (const int rc = track_text_args(ix, p, "gm_coverage_text", kind, want)) return rc;
+    TrackSink out;
+    out.mem = text; out.cap = cap;
+    if (const int rc = track_text_run(ix, "gm_coverage_text", kind, want, bin_lo, bin_hi, out)) return rc;
+    *n_out = out.total;
+    if (out.total > cap) { gm_set_error("gm_coverage_text: text[] too small"); return GM_E_CAPACITY; }
+    return GM_OK;
+}
+
+extern "C" int gm_coverage_text_stats(gm_index* ix, gm_track_text_stats* out) {
+    if (!ix || !out) return GM_E_ARG;
+    *out = ix->tt_stats;
+    return GM_OK;
 }

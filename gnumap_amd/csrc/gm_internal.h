@@ -181,6 +181,20 @@ struct GmDevText {
 struct GmDevSnpRec { unsigned long long pos; uint32_t contig, pad0; unsigned long long chr_pos; float total, nuc[5]; double p_val; uint8_t ref, alt1, alt2, diploid;
                      uint8_t pad1[4]; };
 
+// what the track text kernels (k_track_sizes / k_track_rows, gm_tracktext.hip) read and write: bins [lo, lo + n) of the coverage track
+enum { GM_TRACK_SGR = 0, GM_TRACK_SNP = 1, GM_TRACK_BASE = 2 };     // .sgr; --snp's .gmp; the .gmp of -b / --b2 / -d (rows of one reference base)
+enum { TT_META_BYTES = 0, TT_META_ROWS = 1, TT_META_HOST = 2, TT_META_N = 4 };
+struct GmDevTrack {
+    const float* cov; const float* nuc; uint64_t nuc_stride;         // nuc: a c g t n tracks nuc_stride floats apart, or null (.sgr)
+    const uint8_t* pac; const uint32_t* contig_off; uint32_t n_seqs;
+    const char* cnames; const uint32_t* cname_off;                   // contig names back to back, n_seqs + 1 offsets
+    uint64_t lo, n;
+    uint32_t bin_size, kind, want;                                   // GM_TRACK_*; want: 2-bit code of the reference base of GM_TRACK_BASE
+    uint32_t* tile_len; unsigned long long* tile_off;                // bytes of text per tile of 256 bins; their exclusive scan (tiles + 1)
+    unsigned long long* meta;                                        // TT_META_*: bytes and rows of the slab, 1 = a value only the host can print (zeroed by the caller)
+    char* text;                                                      // 16-byte aligned
+};
+
 // workspace of the grouping kernels (process_hits' unique map on the device); per-hit arrays share the CSR of hit_begin
 struct GmDevGroup {
     GmRawHit* sorted;               // accepted hits of a read in the reference's processing order
@@ -270,6 +284,10 @@ int gmk_snp_call(const float* cov, const float* nuc, uint64_t bins, const GmDevI
 int gmk_snp_gather(const float* cov, const float* nuc, uint64_t bins, const GmDevIndex& ix, uint64_t lo, uint64_t n, const uint8_t* code, const double* pval,
                    const uint32_t* ycnt, unsigned long long* off, unsigned long long base, unsigned long long cap, GmDevSnpRec* out, void* stream);
 int gmk_snp_stat(const float* counts, uint32_t n, int monop, double* pval, int8_t* pos1, int8_t* pos2, uint8_t* dip, void* stream);
+// gm_tracktext.hip: .sgr / .gmp rows as text.  Sizes + their scan (meta is read back by the caller), then the rows into text[0, meta[TT_META_BYTES])
+uint32_t gmk_track_tiles(uint64_t n);
+int gmk_track_sizes(const GmDevTrack& t, void* stream);
+int gmk_track_rows(const GmDevTrack& t, void* stream);
 int gmk_compact(const GmDevBatch& b, void* stream);
 int gmk_scan_hits(const GmDevBatch& b, void* stream);
 int gmk_scatter(const GmDevBatch& b, uint32_t grid, void* stream);

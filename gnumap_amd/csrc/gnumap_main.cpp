@@ -55,6 +55,7 @@ struct Options {
     float snp_pval = 0.001f;    // --snp_pval: gSNP_PVAL inc/const_define.h:33
     bool snp_monop = false, snp_calls = false;      // --snp_monop: gSNP_MONOP; --snp_calls: <out>.gmp with PrintSNPCall's ninth column
     bool sam_text_device = false;   // --sam_text=device: SAM rows formatted on the GPU (gm_output_batch_text); host = format_sam below
+    bool track_text_device = false; // --track_text=device: <out>.sgr / <out>.gmp formatted on the GPU (gm_coverage_write_*_device); host = the whole tracks come down
     int sam_shards = 1;             // --sam_shards=K: <out>.0.sam .. <out>.<K-1>.sam by input position instead of one <out>.sam
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
@@ -95,6 +96,8 @@ static void usage(int rc, const char* msg) {
             "  MI355X options: --gpus=N  --batch=N (blocks of exactly N reads)  --chunk_reads=N  --workers=N  --fmt_threads=N  --locate=sampled|full\n"
             "      --sam_text=host|device   where the SAM rows become text: host formatter threads (default) or the GPU\n"
             "                               (gm_output_batch_text; same bytes, no formatter stage)\n"
+            "      --track_text=host|device where <out>.sgr / the eight-column <out>.gmp become text: host threads over a host copy of the\n"
+            "                               tracks (default) or the GPU (same bytes; only the text crosses the link, no whole-genome host array)\n"
             "      --sam_shards=K           1 .. 64 (default 1 = <out>.sam): write <out>.0.sam .. <out>.<K-1>.sam, a block going to the\n"
             "                               shard of its position in the input, header lines in shard 0 only;\n"
             "                               cat <out>.0.sam .. <out>.<K-1>.sam is the single-file SAM\n");
@@ -155,6 +158,11 @@ static void parse_args(int argc, char** argv, Options& o) {
                 if (!strcmp(s + 9, "device")) o.sam_text_device = true;
                 else if (!strcmp(s + 9, "host")) o.sam_text_device = false;
                 else { fprintf(stderr, "Error: --sam_text takes host or device, not: %s\n", s + 9); exit(1); }
+            }
+            else if (starts(s, "track_text=")) {
+                if (!strcmp(s + 11, "device")) o.track_text_device = true;
+                else if (!strcmp(s + 11, "host")) o.track_text_device = false;
+                else { fprintf(stderr, "Error: --track_text takes host or device, not: %s\n", s + 11); exit(1); }
             }
             else if (starts(s, "sam_shards=")) {
                 char* end = nullptr;
@@ -1096,6 +1104,14 @@ int main(int argc, char** argv) {
     if (gm_coverage_allreduce(gpu_ix.data(), o.gpus) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
     if (o.p.mode == GM_MODE_SNP && o.snp_calls) {                      // PrintFinalSNP with PrintSNPCall's column: the tracks are read where they are, slab by slab
         if (gm_coverage_write_gmp_calls(gpu_ix[0], o.snp_pval, o.snp_monop, (o.output + ".gmp").c_str(), 0) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+    } else if (o.track_text_device) {                                  // GPU 0 formats the rows where the tracks are: no host copy of a track
+        const int rc = o.p.mode == GM_MODE_NORMAL ? gm_coverage_write_sgr_device(gpu_ix[0], (o.output + ".sgr").c_str(), 0)
+                                                  : gm_coverage_write_gmp_device(gpu_ix[0], &o.p, (o.output + ".gmp").c_str(), 0);
+        if (rc != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+        gm_track_text_stats ts;
+        if (o.verbose > 0 && gm_coverage_text_stats(gpu_ix[0], &ts) == GM_OK)
+            fprintf(stderr, "track text on the device: %lu rows, %lu bytes, %lu slabs (%lu formatted by the host), %lu launches, %.2f ms in kernels\n", (unsigned long)ts.rows,
+                    (unsigned long)ts.bytes, (unsigned long)ts.slabs, (unsigned long)ts.host_slabs, (unsigned long)ts.launches, ts.kernel_ms);
     } else {
         PinVec<float> cov; cov.ensure(gm_coverage_bins(gpu_ix[0]));                     // page-locked: the 1.5 GB of a human track come down at link rate
         if (gm_coverage_download(gpu_ix[0], cov.data()) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }

@@ -382,6 +382,27 @@ int gm_dev_snp_stat(gm_index*, const float* counts, uint32_t n, int monop, doubl
  * from HBM slab by slab (GM_TRACK_SLICE positions per host thread); no host copy of them is needed */
 int gm_coverage_write_gmp_calls(gm_index*, float snp_pval, int monop, const char* path, int append);
 
+/* ---- track files formatted on the device (k_track_sizes / k_track_rows, gm_tracktext.hip) ----
+ * The same files as gm_coverage_write_sgr / gm_coverage_write_gmp, byte for byte, without a host copy of the tracks: the rows are
+ * formatted where the tracks live, slab by slab (GM_TRACK_SLICE bins per slab, default 2^24), and only their text crosses the link,
+ * into page-locked buffers that go to the file with pwrite at a running offset.  A slab in which a printed value lies outside
+ * [0, 1e9) - negative, NaN, inf: what the host writers hand to snprintf - is formatted by the host emitters from that slab's tracks
+ * (gm_track_text_stats.host_slabs counts them), so the file is the host writer's file whatever the tracks hold.
+ * GM_E_NO_DEVICE on a host-only index; GM_E_ARG without a coverage track, for bin_lo > bin_hi or bin_hi > gm_coverage_bins, and for
+ * gm_coverage_write_gmp_device in GM_MODE_NORMAL or without gm_coverage_enable_nuc; gm_last_error() names the call. */
+typedef struct { uint64_t rows, bytes, slabs, host_slabs, launches; double kernel_ms; } gm_track_text_stats;
+/* GenomeBwt::PrintFinalSGR src/GenomeBwt.cpp:1212-1273 */
+int gm_coverage_write_sgr_device(gm_index*, const char* path, int append);
+/* GenomeBwt::PrintFinalBisulfite src/GenomeBwt.cpp:1092-1210 (GM_MODE_BS, BS2, ATOG, ATOG2) and PrintFinalSNP :930-1009 without
+ * PrintSNPCall's column (GM_MODE_SNP: eight columns) */
+int gm_coverage_write_gmp_device(gm_index*, const gm_params*, const char* path, int append);
+/* the rows of bins [bin_lo, bin_hi) as text in host memory: p NULL or GM_MODE_NORMAL = .sgr rows, else the .gmp rows of p->mode (bins
+ * past the last one the files print have no row).  *n_out = the bytes needed; GM_E_CAPACITY when that exceeds cap, text[0, cap)
+ * then holds the first cap bytes (the protocol of gm_snp_calls) */
+int gm_coverage_text(gm_index*, const gm_params* p, uint64_t bin_lo, uint64_t bin_hi, char* text, uint64_t cap, uint64_t* n_out);
+/* of the last of the three calls above on this index: kernel_ms is the device time of the launches (hipEvent), launches their number */
+int gm_coverage_text_stats(gm_index*, gm_track_text_stats*);
+
 #ifdef __cplusplus
 }
 #endif

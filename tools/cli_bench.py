@@ -64,10 +64,15 @@ def main():
             if os.path.exists(f):
                 os.remove(f)
         t0 = time.time()
-        r = subprocess.run([exe, "-g", fa, "-o", out, "-v", "1"] + args.split() + [fq], capture_output=True, text=True, env=env)
-        dt = time.time() - t0
-        print(f"--- {run}: {dt:.2f} s wall, {n / dt / 1e6:.3f} M reads/s end to end (rc {r.returncode})")
-        print("\n".join(l for l in r.stderr[-3000:].splitlines() if not l.startswith("[gm_")))
+        with open(out + ".stderr", "w+") as log:                  # os.wait4: this child's own peak resident set
+            child = subprocess.Popen([exe, "-g", fa, "-o", out, "-v", "1"] + args.split() + [fq], stdout=subprocess.DEVNULL, stderr=log, env=env)
+            _, status, usage = os.wait4(child.pid, 0)
+            child.returncode = os.waitstatus_to_exitcode(status)
+            dt = time.time() - t0
+            log.seek(0); err = log.read()
+        print(f"--- {run}: {dt:.2f} s wall, {n / dt / 1e6:.3f} M reads/s end to end (rc {child.returncode}), peak resident host memory {usage.ru_maxrss / 1048576:.2f} GB")
+        print("\n".join(l for l in err[-3000:].splitlines() if not l.startswith("[gm_")))
+        print("track files:", ", ".join(f"{ext} {os.path.getsize(out + ext)} bytes" for ext in (".sgr", ".gmp") if os.path.exists(out + ext)))
         sam_bytes = sum(os.path.getsize(f) for f in ([out + ".sam"] if os.path.exists(out + ".sam") else []) + shard_files())
     print("SAM bytes", sam_bytes, "FASTQ bytes", os.path.getsize(fq))
 
