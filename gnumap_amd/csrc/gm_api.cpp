@@ -881,7 +881,7 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
         }
         if (mx > region) { overflow = true; return GM_OK; }
         ncand[i] = (uint32_t)total;
-        { KTimer t(b, GM_K_NW, ss); KCHK(gmk_nw(ix->dev, dp, view[i], ncand[i], (b->len_min == b->len_max && (b->fasta || !ctr[GMK_HIGH_QUAL])) ? b->len_max : 0u, gm_qual_lo(ctr), gm_qual_hi(ctr), ss)); }
+        { KTimer t(b, GM_K_NW, ss); KCHK(gmk_nw(ix->dev, dp, view[i], ncand[i], (b->len_min == b->len_max && (b->fasta || !ctr[GMK_HIGH_QUAL])) ? b->len_max : 0u, gm_qual_lo(ctr), gm_qual_hi(ctr), small[1] != 0, ss)); }
         return GM_OK;
     };
     uint32_t next_finish = 0;
@@ -1118,6 +1118,9 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
         return GM_OK;
     };
     auto read_shards = read_status;
+    // of the last attempt: k_nw_rows loads rs_overflow bytes only when this is set.  The bytes are written by the vote kernels next to
+    // n_retry alone; the heavy path does not write them and is included only to stay on the safe side
+    bool any_superseded = false;
     for (int attempt = 0;; ++attempt) {
         HIPCHK(hipMemsetAsync(b->small.p, 0, 64, st));
         HIPCHK(hipMemsetAsync(b->shards.p, 0, (size_t)GM_NSHARD * GM_SHARD_STRIDE * 4, st));
@@ -1167,6 +1170,7 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
         }
         if (ctr[GMK_BAD_QUAL] && !b->fasta) { gm_set_error("Invalid Fastq Character? (negative base probability)"); return GM_E_BAD_QUAL; }
         uint32_t n_retry = small[1];
+        any_superseded = n_retry != 0 || !heavy.empty();
         if (n_retry && mx <= b->dev.cand_region) {
             size_t slots = (size_t)ctr[GMK_HEAVY_SLOTS];
             const size_t budget = (size_t)gm_opt_ll("GM_RETRY_BUDGET", 1ll << 28);   // table slots per launch (2 GB of keys + counts; the switch is for tests)
@@ -1233,7 +1237,7 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     // one read length in the block and no quality character above 127 (k_prep counted them): the DP kernel with the rows in DP order
     const uint32_t nw_rows_len = (b->len_min == b->len_max && (b->fasta || ctr[GMK_HIGH_QUAL] == 0)) ? b->len_max : 0u;      // (a FASTA block has no quality characters)
     b->path += std::string(" nw=") + gmk_nw_form(dp, b->dev, b->n_cands, nw_rows_len, gm_qual_lo(ctr), gm_qual_hi(ctr));
-    { KTimer t(b, GM_K_NW, st); KCHK(gmk_nw(ix->dev, dp, b->dev, b->n_cands, nw_rows_len, gm_qual_lo(ctr), gm_qual_hi(ctr), st)); }
+    { KTimer t(b, GM_K_NW, st); KCHK(gmk_nw(ix->dev, dp, b->dev, b->n_cands, nw_rows_len, gm_qual_lo(ctr), gm_qual_hi(ctr), any_superseded, st)); }
     { KTimer t(b, GM_K_COMPACT, st); KCHK(gmk_compact(b->dev, st)); }
     if (gm_trace_on()) { HIPCHK(hipStreamSynchronize(st)); GM_TRACE("NW + compaction done"); }
     b->mapped = true;
@@ -2040,12 +2044,12 @@ extern "C" int gm_dev_nw_score(gm_index* ix, const gm_params* p, const gm_reads*
         if (hipMemset(b->shards.p, 0, (size_t)GM_NSHARD * GM_SHARD_STRIDE * 4) != hipSuccess) { rc = GM_E_HIP; break; }
         if (hipMemcpy(b->shards.p, &n, 4, hipMemcpyHostToDevice) != hipSuccess) { rc = GM_E_HIP; break; }
         uint32_t rows_len = (b->len_min == b->len_max) ? b->len_max : 0u;          // (no k_prep here: the quality characters are looked at on the host)
-        for (size_t q = 0; q < (size_t)reads->n * reads->stride && rows_len && !b->fasta; ++q) if (reads->quals[q] >= 128) rows_len = 0;
-        uint32_t qlo = 255, qhi = 0;
+        uint32_t qlo = 255, qhi = 0;                                                // (of the reads' own characters, as k_prep counts them: a row's padding is not data)
         for (uint32_t r = 0; r < reads->n && !b->fasta; ++r)
             for (uint32_t i = 0; i < reads->len[r] && i < reads->stride; ++i) { const uint32_t qc = reads->quals[(size_t)r * reads->stride + i]; qlo = std::min(qlo, qc); qhi = std::max(qhi, qc); }
+        if (qhi >= 128) rows_len = 0;
         GM_TRACE("dev_nw_score: %u probes, nw=%s", n, gmk_nw_form(dp, b->dev, n, rows_len, qlo, qhi));
-        if (gmk_nw(ix->dev, dp, b->dev, n, rows_len, qlo, qhi, nullptr)) { rc = GM_E_HIP; break; }
+        if (gmk_nw(ix->dev, dp, b->dev, n, rows_len, qlo, qhi, false, nullptr)) { rc = GM_E_HIP; break; }
         if (n && hipMemcpy(c.data(), b->cands.p, (size_t)n * sizeof(GmCand), hipMemcpyDeviceToHost) != hipSuccess) { rc = GM_E_HIP; break; }
     } while (0);
     gm_batch_destroy(b);

@@ -256,10 +256,10 @@ int gmk_heavy_chunk(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch
 int gmk_vote_retry(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, int use_full_sa, uint32_t j0, uint32_t n_retry, void* stream);
 // rows_len != 0: every read of the block has this length and no quality character is above 127 -> k_nw_rows (gm_nw.hip) may take it
 // [qual_lo, qual_hi] = the range of the block's quality characters (k_prep's GMK_QUAL_MIN / GMK_QUAL_MAX): the size of k_nw_rows' pair table
-int gmk_nw(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, uint32_t qual_lo, uint32_t qual_hi, void* stream);
+int gmk_nw(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, uint32_t qual_lo, uint32_t qual_hi, bool any_superseded, void* stream);
 // which DP kernel gmk_nw launches for these arguments (k_nw_rows/pairs or k_nw_rows/cells for the two forms of k_nw_rows)
 const char* gmk_nw_form(const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, uint32_t qual_lo, uint32_t qual_hi);
-int gmk_nw_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t L, uint32_t qual_lo, uint32_t qual_hi, void* stream);
+int gmk_nw_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t L, uint32_t qual_lo, uint32_t qual_hi, bool any_superseded, void* stream);
 bool gmk_nw_rows_pairs(const GmDevBatch& b, uint32_t L, uint32_t qual_lo, uint32_t qual_hi);     // k_nw_rows takes its pair table (gm_nw.hip)
 inline uint32_t gm_qual_lo(const unsigned long long* ctr) { return 255u - (uint32_t)ctr[GMK_QUAL_MIN]; }
 inline uint32_t gm_qual_hi(const unsigned long long* ctr) { return (uint32_t)ctr[GMK_QUAL_MAX]; }

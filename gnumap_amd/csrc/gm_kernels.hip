@@ -3494,12 +3494,12 @@ const char* gmk_nw_form(const GmDevParams& p, const GmDevBatch& b, uint32_t n_ca
     return "k_nw_lane<0>";
 }
 
-int gmk_nw(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, uint32_t qual_lo, uint32_t qual_hi, void* stream) {
+int gmk_nw(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t rows_len, uint32_t qual_lo, uint32_t qual_hi, bool any_superseded, void* stream) {
     if (b.n == 0) return 0;
     if (p.max_gap != 3) return gmk_nw_band(ix, p, b, n_cands, p.max_gap, stream);
     const bool wave_form = gm_opt_is("GM_NW", "wave");
     if (wave_form && b.fasta) return (int)hipErrorInvalidValue;      // k_nw reads FASTQ rows only (the callers refuse this by name: fasta_forced_form)
-    if (nw_rows_ok(p, b, rows_len)) return gmk_nw_rows(ix, p, b, n_cands, rows_len, qual_lo, qual_hi, stream);
+    if (nw_rows_ok(p, b, rows_len)) return gmk_nw_rows(ix, p, b, n_cands, rows_len, qual_lo, qual_hi, any_superseded, stream);
     if (!wave_form) {
         // ~4 candidates per lane: fewer, larger workgroups leave a long tail (measured at 17 M candidates: 2048 workgroups 6.1 ms,
         // 16384 5.6 ms), more, smaller ones pay their set-up (LDS tables, shard prefix) too often (2 M candidates: 0.77 against 1.02 ms)

@@ -28,6 +28,28 @@
 // FASTA blocks (GmDevBatch::fasta): a position's row is its IUPAC letter's, (base mask, p, q) with (p, q) a function of the mask - the
 // class axis is the 16 masks (the minus strand's class = the mask with its bits reversed), the quality axis ONE entry: the quality rows
 // are neither loaded nor multiplied in (their words stay 0), and the whole pair table is 16 records (2.1 KB), the cells table 256 bytes.
+//
+// THE LOAD GROUP.  A candidate costs two dependent memory trips: its 16-byte record, then everything the record's fields address,
+// requested back to back with no branch and no wait between two loads (the first form went chunk by chunk, one basic block and one
+// round trip each: 13 row trips behind the record and the rs_overflow byte, then the window words, then min_score - DESIGN.md section 4):
+//   * the read row as NP = (NCH + 1) / 2 pieces of 16 bytes per array (7 for <13>, 10 for <19>), two 8-row chunks each.  Reverse strand:
+//     piece m at row offset 16 m.  Forward strand: the row backwards, piece m at L - 16 - 16 m (any byte alignment), byte-reversed as
+//     a whole by the v_perm that also splits it into its chunks.  One selector serves both strands;
+//   * a row of an ODD number of chunks ends in a piece with one live chunk.  That piece is loaded one chunk lower (reverse strand: at
+//     16 m - 8; forward strand: at 0, where the clamp puts it anyway), so that on both strands the live chunk arrives in the piece's
+//     upper half and is moved down after the loads; the forward strand's is then shifted by the sh bytes the row falls short of
+//     its last chunk.  An EVEN row's last piece on the forward strand starts sh bytes before the row: loaded at 0, both chunks
+//     funnel-shifted down by sh bytes.  These fix-ups sit behind the loads, under wave-uniform conditions;
+//   * clamps instead of predicates: a piece offset lies in [0, stride - 16], so a piece beyond the row's chunks (L < 8 NCH) loads
+//     inside the row and is zeroed by its selector, and nothing is read past the row - the last row of the block ends where the
+//     uploaded data does.  Needs stride >= 16 and, for the odd row's 16 m - 8, at least two chunks: the launcher admits 24 <= L <= stride;
+//   * the packed window as NWL 16-byte loads (2 / 3) of ASCENDING words ending at word n0 = (begin + L - 1) / 16, n0 clamped to
+//     the reference's last word (candidates whose window is refused afterwards load too) and the first word clamped to word 0.  A
+//     window within the reference's first NWW - 1 words therefore arrives too low in its registers: its words are moved up by the
+//     difference (a rare, divergent branch behind the loads), word 0 filling in, which feeds only columns j < 0;
+//   * min_score[r], which the epilogue compares with; and, only when the host says that the retry kernel ran for this launch (sup:
+//     rs_overflow is written nowhere else), the flagged candidate's rs_overflow byte, as the last load of the group.
+// Only then come the tests: window inside one contig, superseded.  The epilogue writes {step, flags, pad, score} as one 8-byte store.
 #include <hip/hip_runtime.h>
 #include "gm_device.h"
 
@@ -40,11 +62,14 @@ static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 // PAIRS: qlo = the block's smallest quality character, nq = the number of characters in its range, rs = bytes per pair record
 // FA: a FASTA block (its own instantiation: the FASTQ kernels keep their instructions)
+// sup: the host saw the retry kernel (or the heavy path) run for this launch: only then is a flagged candidate's rs_overflow byte loaded
 template <int NCH, bool PAIRS, bool FA>
 __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex ix, GmDevParams p, GmDevBatch b, const uint32_t L, const uint32_t ntab,
-                                                                    const uint32_t qlo, const uint32_t nq, const uint32_t rs) {
+                                                                    const uint32_t qlo, const uint32_t nq, const uint32_t rs, const uint32_t sup) {
     constexpr uint32_t ncls = FA ? 16u : 5u;                                    // class records per quality character (FA: one per base mask)
     constexpr int NHW = (8 * NCH + 3) / 16 + 1;                                // 16-column words of the window stream
+    constexpr int NP = (NCH + 1) / 2;                                          // 16-byte pieces of a read row (two chunks each)
+    constexpr int NWL = (NHW + 4) / 4, NWW = 4 * NWL;                          // 16-byte loads / words of the packed window (NHW + 1 are used)
     // cells: [ntab][128 quality characters][8 classes] float4 {val(a), val(c), val(g), val(t)};
     // PAIRS: [ntab][nq quality characters][5 classes] 16 x float2 {val(x), val(y)}, records rs bytes apart
     extern __shared__ __attribute__((aligned(16))) unsigned char s_tab[];
@@ -112,40 +137,98 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
     const int Li = (int)L;
     const int nchunk = (Li + 7) >> 3;
     const uint32_t sh = (uint32_t)(8 * nchunk - Li);            // bytes the reversed row of a forward-strand read is shifted down by
-    unsigned long long cells = 0, accepted = 0;
+    const int m_last = (nchunk - 1) >> 1;                       // the piece that holds the row's last chunk
+    const bool odd = (nchunk & 1) != 0;                         // .. alone: it is loaded one chunk lower, so that both strands find that chunk in its upper half
+    // a piece never reaches past its row.  Preconditions (nw_rows_ok: 24 <= L <= stride, stride a multiple of 8): omax >= 8, and the odd
+    // row's last piece, loaded at 16 m_last - 8 = 8 nchunk - 16, starts at 8 or beyond and ends inside the row
+    const int omax = (int)b.stride - 16;
+    const uint32_t nlast = (ix.l_pac - 1u) >> 4;                // the last word of the packed reference that holds a base
+    // cells inside the band of one candidate (counter only)
+    unsigned long long band_cells = 0;
+    if (Li >= 7) band_cells = (unsigned long long)(7 * Li - 12);
+    else for (int i = 0; i < Li; ++i) { int lo = i - 3 < 0 ? 0 : i - 3, hi = i + 3 >= Li ? Li - 1 : i + 3; band_cells += (unsigned long long)(hi - lo + 1); }
+    uint32_t scored = 0, accepted = 0;                          // this lane's candidates: a grid-stride share of fewer than 2^32
     for (uint32_t wi = blockIdx.x * 256 + threadIdx.x; wi < n_cands; wi += gridDim.x * 256) {
         const size_t ci = gm_cand_slot(b, s_pre, wi);
-        GmCand c = b.cands[ci];
+        GmCand c;
+        uint32_t c_hi;                                          // step | flags << 16 | pad << 24: the word the epilogue writes back
+        {
+            uint4 cw;
+            __builtin_memcpy(&cw, &b.cands[ci], 16);
+            c.rs = cw.x; c.b = cw.y; c_hi = cw.z;
+            c.step = (uint16_t)c_hi; c.flags = (uint8_t)(c_hi >> 16);
+        }
         const uint32_t r = c.rs >> 1, strand = c.rs & 1;
-        if ((c.flags & 4) && b.rs_overflow[c.rs]) continue;                 // superseded by the retry kernel
+        // ---- the load group: everything the candidate's fields address is requested here, back to back - no branch and no wait between
+        //      two loads, every address clamped into its allocation instead of predicated.  What is tested (superseded, window inside a
+        //      contig) is tested afterwards.  (No overlap is claimed for those tests: coff is an LDS-or-global pointer, its reads are flat
+        //      loads, and the first one waits for the whole group) ----
+        // the read row in 16-byte pieces, in DP order (element t belongs to DP row i = L - 1 - t).  Reverse strand: t = the read's own
+        // index (complemented through s_cls), piece m at 16 m; forward strand: the read backwards, piece m at L - 16 - 16 m, or at 0 when
+        // that is before the row (the last piece: put right after the loads).  Pieces beyond the row load inside it and are zeroed
+        uint4 TB[NP], TQ[NP];
+        {
+            unsigned long long row = (unsigned long long)r * b.stride;
+            asm("" : "+v"(row));                                            // (the product alone: with a base folded in, both bases wait in vector registers)
+            const uint8_t* rb = b.bases + row;
+            const uint8_t* rq = b.quals + row;
+            uint32_t fwd = strand - 1u;                                     // all ones on the forward strand
+            asm("" : "+v"(fwd));                                            // (kept a mask: as a select, the 14 offsets would wait in vector registers)
+#pragma unroll
+            for (int m = 0; m < NP; ++m) {
+                const int orv = 16 * m - ((odd && m == m_last) ? 8 : 0), ofw = Li - 16 - 16 * m;
+                const uint32_t orc = (uint32_t)(orv < omax ? orv : omax), ofc = (uint32_t)(ofw > 0 ? ofw : 0);        // (wave-uniform)
+                const uint32_t off = orc + (fwd & (ofc - orc));             // (an AND and an add on scalars: a select would keep both in registers)
+                __builtin_memcpy(&TB[m], rb + off, 16);
+                if (!FA) __builtin_memcpy(&TQ[m], rq + off, 16);
+                else TQ[m] = make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+        // the packed window as ascending words ending at word n0 (clamped to the reference's last word for windows that are refused
+        // below, and to word 0 at its start)
+        const uint32_t g0 = c.b + L - 1u, n0 = g0 >> 4;
+        const uint32_t n0c = n0 < nlast ? n0 : nlast;
+        uint32_t A[NWW];
+        {
+            const uint32_t* wp = pac32 + (n0c >= (uint32_t)(NWW - 1) ? n0c - (uint32_t)(NWW - 1) : 0u);
+#pragma unroll
+            for (int q = 0; q < NWL; ++q) {
+                uint4 t;
+                __builtin_memcpy(&t, wp + 4 * q, 16);
+                A[4 * q] = t.x; A[4 * q + 1] = t.y; A[4 * q + 2] = t.z; A[4 * q + 3] = t.w;
+            }
+        }
+        const double min_score = b.min_score[r];
+        uint32_t superseded = 0u;
+        if (sup && (c.flags & 4)) superseded = b.rs_overflow[c.rs];         // (the last load of the group)
         const bool ok = gm_window_ok(ix, coff, c.b, L);
+        if (superseded) continue;                                           // the retry kernel made this read x strand's candidates again
         float result = 0.0f;
         if (ok && p.nw) {
-            // ---- the read in DP order: element t belongs to DP row i = L - 1 - t.  Reverse strand: t = the read's own index (complemented
-            //      through s_cls); forward strand: the read backwards ----
+            // ---- the pieces into chunks: reverse strand as loaded, forward strand byte-reversed (piece and all) ----
             uint2 XB[NCH], XQ[NCH];
             {
-                const uint8_t* rb = b.bases + (size_t)r * b.stride;
-                const uint8_t* rq = b.quals + (size_t)r * b.stride;
-                const uint32_t selx = strand ? 0x03020100u : 0x04050607u, sely = strand ? 0x07060504u : 0x00010203u;
+                const uint32_t selx = strand ? 0x03020100u : 0x04050607u;
+                const uint32_t s8 = strand ? 0u : 8u * sh;                  // the forward strand's last piece was loaded from offset 0: its elements sit sh bytes up
 #pragma unroll
-                for (int k = 0; k < NCH; ++k) {
-                    XB[k] = make_uint2(0u, 0u); XQ[k] = make_uint2(0u, 0u);
-                    if (k < nchunk) {
-                        const int fo = Li - 8 - 8 * k;
-                        const uint32_t off = strand ? (uint32_t)(8 * k) : (uint32_t)(fo > 0 ? fo : 0);
-                        uint2 tb, tq = make_uint2(0u, 0u);
-                        __builtin_memcpy(&tb, rb + off, 8);
-                        if (!FA) __builtin_memcpy(&tq, rq + off, 8);
-                        uint2 ob = make_uint2(__builtin_amdgcn_perm(tb.y, tb.x, selx), __builtin_amdgcn_perm(tb.y, tb.x, sely));
-                        uint2 oq = make_uint2(__builtin_amdgcn_perm(tq.y, tq.x, selx), __builtin_amdgcn_perm(tq.y, tq.x, sely));
-                        if (k == nchunk - 1 && sh != 0u) {                      // the last word of a reversed row was loaded from offset 0: its elements sit sh bytes up
-                            const uint32_t s8 = strand ? 0u : 8u * sh;
-                            const unsigned long long wb = (((unsigned long long)ob.y << 32) | ob.x) >> s8, wq = (((unsigned long long)oq.y << 32) | oq.x) >> s8;
-                            ob = make_uint2((uint32_t)wb, (uint32_t)(wb >> 32)); oq = make_uint2((uint32_t)wq, (uint32_t)(wq >> 32));
+                for (int m = 0; m < NP; ++m) {
+                    const uint32_t sel = m <= m_last ? selx : 0x0C0C0C0Cu;   // (selector 0x0C: a zero byte)
+                    uint2 lo[2], hi[2];
+#pragma unroll
+                    for (int a = 0; a < (FA ? 1 : 2); ++a) {
+                        const uint4 t = a ? TQ[m] : TB[m];
+                        lo[a] = make_uint2(__builtin_amdgcn_perm(t.w, t.x, sel), __builtin_amdgcn_perm(t.z, t.y, sel));
+                        hi[a] = make_uint2(__builtin_amdgcn_perm(t.y, t.z, sel), __builtin_amdgcn_perm(t.x, t.w, sel));
+                        if (m == m_last && (odd || sh != 0u)) {
+                            const unsigned long long l64 = ((unsigned long long)lo[a].y << 32) | lo[a].x, h64 = ((unsigned long long)hi[a].y << 32) | hi[a].x;
+                            // odd: the one chunk of the piece came in the upper half.  Even: both halves move down by sh bytes
+                            const unsigned long long nl = odd ? h64 >> s8 : (l64 >> s8) | ((h64 << 1) << (63u - s8)), nh = odd ? 0ull : h64 >> s8;
+                            lo[a] = make_uint2((uint32_t)nl, (uint32_t)(nl >> 32)); hi[a] = make_uint2((uint32_t)nh, (uint32_t)(nh >> 32));
                         }
-                        XB[k] = ob; XQ[k] = oq;
                     }
+                    if (FA) { lo[1] = make_uint2(0u, 0u); hi[1] = make_uint2(0u, 0u); }
+                    XB[2 * m] = lo[0]; XQ[2 * m] = lo[1];
+                    if (2 * m + 1 < NCH) { XB[2 * m + 1] = hi[0]; XQ[2 * m + 1] = hi[1]; }
                 }
             }
             // ---- the window in DP order: H[u] = w[L - 1 - u], 2 bits each, 16 per word, u ascending from bit 0.  The reference packs 4
@@ -153,14 +236,21 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
             //      so descending positions are ascending bits and the stream is the words n0, n0 - 1, .. funnel-shifted by 30 - 2 (g0 & 15) ----
             uint32_t HW[NHW];
             {
-                const uint32_t g0 = c.b + L - 1u, n0 = g0 >> 4, s = 30u - 2u * (g0 & 15u);
+                if (n0c < (uint32_t)(NWW - 1)) {
+                    // the loads started at word 0 instead of n0 - (NWW - 1): the words move up by the difference, word 0 filling in
+                    // (below the reference's start only columns j < 0 are fed)
+                    const uint32_t up = (uint32_t)(NWW - 1) - n0c;
+#pragma unroll
+                    for (int bit = 1; bit < NWW; bit <<= 1) {
+                        const bool mv = (up & (uint32_t)bit) != 0u;
+#pragma unroll
+                        for (int q = NWW - 1; q >= 0; --q) A[q] = mv ? A[q >= bit ? q - bit : 0] : A[q];
+                    }
+                }
+                const uint32_t s = 30u - 2u * (g0 & 15u);
                 uint32_t W[NHW + 1];
 #pragma unroll
-                for (int j = 0; j <= NHW; ++j) {
-                    const uint32_t idx = n0 >= (uint32_t)j ? n0 - (uint32_t)j : 0u;          // below the reference's start only columns j < 0 are fed
-                    const uint32_t x = pac32[idx];
-                    W[j] = __builtin_amdgcn_perm(x, x, 0x00010203u);
-                }
+                for (int j = 0; j <= NHW; ++j) W[j] = __builtin_amdgcn_perm(A[NWW - 1 - j], A[NWW - 1 - j], 0x00010203u);
 #pragma unroll
                 for (int m = 0; m < NHW; ++m) HW[m] = __builtin_amdgcn_alignbit(W[m + 1], W[m], s);
             }
@@ -302,9 +392,7 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
             } else {
                 for (int k = 0; k < nchunk; ++k) tail_rows(k, 8 * k, (8 * k + 8 < Li) ? 8 * k + 8 : Li, std::true_type{});
             }
-            // cells inside the band (counter only)
-            if (Li >= 7) cells += (unsigned long long)(7 * Li - 12);
-            else for (int i = 0; i < Li; ++i) { int lo = i - 3 < 0 ? 0 : i - 3, hi = i + 3 >= Li ? Li - 1 : i + 3; cells += (unsigned long long)(hi - lo + 1); }
+            ++scored;
             result = P[3];                                                      // nm[0][0]
         } else if (!p.nw) {
             result = (float)c.step;                                             // --no_nw: the score is the vote count (:70-76)
@@ -313,17 +401,18 @@ __global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 3) k_nw_rows(GmDevIndex i
         if (ok) {
             fl |= GMC_VALID;
             if (result > 0.0f) atomicMax(reinterpret_cast<int*>(&b.top_score[r]), __float_as_int(result));   // top_align_score (:95-98)
-            if ((double)result >= b.min_score[r]) {                            // :102
+            if ((double)result >= min_score) {                                 // :102
                 fl |= GMC_ACCEPT;
                 atomicAdd(&b.hit_count[r], 1u);
                 ++accepted;
             }
         }
-        b.cands[ci].score = result;
-        b.cands[ci].flags = fl;
+        // {step, flags, pad, score}: the record's upper 8 bytes, one store
+        const uint2 out = make_uint2((c_hi & 0xFF00FFFFu) | ((uint32_t)fl << 16), __float_as_uint(result));
+        __builtin_memcpy(reinterpret_cast<unsigned char*>(&b.cands[ci]) + 8, &out, 8);
     }
-    gm_count(b, GMK_NW_CELLS, cells);
-    gm_count(b, GMK_ACCEPTED, accepted);
+    gm_count(b, GMK_NW_CELLS, (unsigned long long)scored * band_cells);
+    gm_count(b, GMK_ACCEPTED, (unsigned long long)accepted);
 }
 
 // bytes per pair record: 128 + a skew of 0 .. 64 bytes in steps of 8 (the entries stay 8-byte aligned for ds_read_b64)
@@ -363,8 +452,9 @@ bool gmk_nw_rows_pairs(const GmDevBatch& b, uint32_t L, uint32_t qlo, uint32_t q
 }
 
 // L = the one read length of the block; [qlo, qhi] = the range of its quality characters (all below 128); illumina = some reads of the
-// block use the Phred+64 table (both tables are then resident)
-int gmk_nw_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t L, uint32_t qlo, uint32_t qhi, void* stream) {
+// block use the Phred+64 table (both tables are then resident); any_superseded = the retry kernel or the heavy path ran for this launch (a
+// candidate's rs_overflow byte is read only then)
+int gmk_nw_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, uint32_t L, uint32_t qlo, uint32_t qhi, bool any_superseded, void* stream) {
     if (b.n == 0) return 0;
     const uint32_t ntab = (b.illumina_until && !b.fasta) ? 2u : 1u;
     const bool pairs = gmk_nw_rows_pairs(b, L, qlo, qhi);
@@ -377,7 +467,7 @@ int gmk_nw_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b,
     const bool narrow = L <= 104;
 #define GM_NWR_LAUNCH_(N, PR, FA, FB)                                                                                                          \
     hipLaunchKernelGGL((k_nw_rows<N, PR, FA>), dim3(nw_fixed ? nw_fixed : resident_grid(k_nw_rows<N, PR, FA>, 256, lds, FB)), dim3(256), lds, \
-                       S_(stream), ix, p, b, L, ntab, q0, nq, nw_pair_rs())
+                       S_(stream), ix, p, b, L, ntab, q0, nq, nw_pair_rs(), any_superseded ? 1u : 0u)
 #define GM_NWR_LAUNCH(N, PR, FB) do { if (b.fasta) GM_NWR_LAUNCH_(N, PR, true, FB); else GM_NWR_LAUNCH_(N, PR, false, FB); } while (0)
     if (narrow && pairs) GM_NWR_LAUNCH(13, true, 1024u);
     else if (narrow) GM_NWR_LAUNCH(13, false, 1024u);
