@@ -96,11 +96,12 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_index_contig_offset", "gm_index_window", "gm_params_default", "gm_params_finalize", "gm_params_load_subst", "gm_batch_create", "gm_batch_destroy",
            "gm_batch_upload", "gm_map_batch_device", "gm_batch_counters", "gm_batch_path", "gm_batch_set_profiling", "gm_batch_kernel_times", "gm_kernel_name",
            "gm_batch_raw_hits", "gm_stream_create", "gm_stream_destroy", "gm_host_alloc", "gm_host_free", "gm_map_batch", "gm_output_batch",
-           "gm_output_batch_text", "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait", "gm_dev_fmt_g6",
+           "gm_output_batch_text", "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait", "gm_dev_fmt_g6", "gm_dev_fmt_e2",
            "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
            "gm_coverage_device_ptr", "gm_coverage_add", "gm_coverage_download", "gm_coverage_allreduce", "gm_coverage_write_sgr", "gm_coverage_enable_nuc", "gm_coverage_nuc_device_ptr",
            "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls",
            "gm_coverage_write_sgr_device", "gm_coverage_write_gmp_device", "gm_coverage_text", "gm_coverage_text_stats",
+           "gm_coverage_write_gmp_calls_device", "gm_coverage_calls_text", "gm_coverage_write_vcf",
            "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim",
            "gm_batch_set_read_format", "gm_index_set_probe_format"]
 
@@ -155,6 +156,7 @@ def load_library():
     L.gm_output_batch_text.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_reads), C.POINTER(gm_read_text), C.POINTER(gm_hits),
                                        C.POINTER(gm_sam_text), C.c_void_p]
     L.gm_dev_fmt_g6.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.gm_dev_fmt_e2.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_sa_interval.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
     L.gm_dev_nw_score.argtypes = [C.c_void_p, C.POINTER(gm_params), C.POINTER(gm_reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -179,6 +181,9 @@ def load_library():
     L.gm_coverage_write_gmp_device.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_char_p, C.c_int]
     L.gm_coverage_text.argtypes = [C.c_void_p, C.POINTER(gm_params), u64, u64, C.c_void_p, u64, C.POINTER(u64)]
     L.gm_coverage_text_stats.argtypes = [C.c_void_p, C.POINTER(gm_track_text_stats)]
+    L.gm_coverage_write_gmp_calls_device.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_char_p, C.c_int]
+    L.gm_coverage_calls_text.argtypes = [C.c_void_p, C.c_float, C.c_int, u64, u64, C.c_void_p, u64, C.POINTER(u64)]
+    L.gm_coverage_write_vcf.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_char_p, C.c_int]
     L.gm_batch_set_adaptor.argtypes = [C.c_void_p, C.c_char_p]
     L.gm_batch_trimmed_len.argtypes = [C.c_void_p, C.c_void_p]
     L.gm_batch_adaptor_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(u64)]
@@ -351,6 +356,14 @@ class Index:
         raw = out.tobytes()
         return [raw[16 * i:16 * i + int(ln[i])] for i in range(n)]
 
+    def dev_fmt_e2(self, values):
+        """gm_dev_fmt_e2: printf("%.2e") of every value as the device prints the ninth .gmp column's p-value; b"" = outside the domain"""
+        v = np.ascontiguousarray(values, np.float64); n = len(v)
+        out = np.zeros((n, 16), np.uint8); ln = np.zeros(n, np.uint8)
+        _chk(lib().gm_dev_fmt_e2(self.h, v.ctypes.data, n, out.ctypes.data, ln.ctypes.data))
+        raw = out.tobytes()
+        return [raw[16 * i:16 * i + int(ln[i])] for i in range(n)]
+
     # ---- coverage ----
     def coverage_reset(self, bin_size):
         _chk(lib().gm_coverage_reset(self.h, bin_size))
@@ -436,8 +449,29 @@ class Index:
         """gm_coverage_write_gmp_device: the eight-column <out>.gmp of -b / --b2 / -d / --snp from the tracks in HBM"""
         _chk(lib().gm_coverage_write_gmp_device(self.h, C.byref(getattr(params, "c", params)), os.fsencode(path), int(append)))
 
+    def coverage_write_gmp_calls_device(self, path, pval=0.001, monop=False, append=False):
+        """gm_coverage_write_gmp_calls_device: the nine-column <out>.gmp of --snp --snp_calls formatted on the device, the bytes of coverage_write_gmp_calls"""
+        _chk(lib().gm_coverage_write_gmp_calls_device(self.h, pval, int(monop), os.fsencode(path), int(append)))
+
+    def coverage_calls_text(self, pval=0.001, monop=False, lo=0, hi=None):
+        """gm_coverage_calls_text: the nine-column rows of the positions [lo, hi) as bytes"""
+        hi = self.coverage_bins() if hi is None else hi
+        cap = 1 << 16
+        while True:
+            buf = C.create_string_buffer(cap); got = u64()
+            rc = lib().gm_coverage_calls_text(self.h, pval, int(monop), lo, hi, buf, cap, C.byref(got))
+            if rc == GM_E_CAPACITY:
+                cap = int(got.value)
+                continue
+            _chk(rc)
+            return buf.raw[:got.value]
+
+    def coverage_write_vcf(self, path, pval=0.001, monop=False, append=False):
+        """gm_coverage_write_vcf: <out>.vcf, one row per record of snp_calls (Genome::PrintFinalVCF); the header unless appending"""
+        _chk(lib().gm_coverage_write_vcf(self.h, pval, int(monop), os.fsencode(path), int(append)))
+
     def coverage_text_stats(self):
-        """rows, bytes, slabs, host_slabs, launches, kernel_ms of the last of the three calls above"""
+        """rows, bytes, slabs, host_slabs, launches, kernel_ms of the last device track writer / coverage_text / coverage_calls_text"""
         st = gm_track_text_stats()
         _chk(lib().gm_coverage_text_stats(self.h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in gm_track_text_stats._fields_}

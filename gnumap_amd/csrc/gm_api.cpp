@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <ctime>
 #include <chrono>
 #include <map>
 #include <memory>
@@ -122,7 +123,7 @@ struct gm_index {
     std::mutex mu;
     uint64_t hbm_bytes = 0;
     int probe_format = GM_READS_FASTQ;      // gm_index_set_probe_format: how the unit probes read their gm_reads
-    gm_track_text_stats tt_stats{};         // of the last gm_coverage_write_*_device / gm_coverage_text
+    gm_track_text_stats tt_stats{};         // of the last gm_coverage_write_*_device / gm_coverage_text / gm_coverage_calls_text
 };
 
 struct gm_batch {
@@ -1875,7 +1876,7 @@ extern "C" int gm_output_batch_text(gm_index* ix, const gm_params* p, gm_batch* 
 }
 
 // gm_put_g6_hd (gm_fmt_dev.h) on the device, one lane per value: out[i * 16 ..] holds len[i] characters (0 = outside its domain)
-extern "C" int gm_dev_fmt_g6(gm_index* ix, const double* v, uint32_t n, char* out, uint8_t* len) {
+static int dev_fmt_probe(gm_index* ix, const double* v, uint32_t n, char* out, uint8_t* len, int (*kernel)(const double*, uint32_t, char*, uint8_t*, void*)) {
     if (!ix || (n && (!v || !out || !len))) return GM_E_ARG;
     if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
     if (n == 0) return GM_OK;
@@ -1886,7 +1887,7 @@ extern "C" int gm_dev_fmt_g6(gm_index* ix, const double* v, uint32_t n, char* ou
     auto run = [&]() -> int {
         HIPCHK(hipMemcpy(dv.p, v, (size_t)n * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemset(dout.p, 0, (size_t)n * 16));
-        KCHK(gmk_fmt_g6(dv.as<double>(), n, dout.as<char>(), dlen.as<uint8_t>(), nullptr));
+        KCHK(kernel(dv.as<double>(), n, dout.as<char>(), dlen.as<uint8_t>(), nullptr));
         HIPCHK(hipDeviceSynchronize());
         HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(len, dlen.p, n, hipMemcpyDeviceToHost));
@@ -1896,6 +1897,9 @@ extern "C" int gm_dev_fmt_g6(gm_index* ix, const double* v, uint32_t n, char* ou
     dv.release(); dout.release(); dlen.release();
     return rc;
 }
+extern "C" int gm_dev_fmt_g6(gm_index* ix, const double* v, uint32_t n, char* out, uint8_t* len) { return dev_fmt_probe(ix, v, n, out, len, gmk_fmt_g6); }
+// gm_put_e2_hd the same way: "%.2e" as k_track_rows prints the p-value of --snp's ninth column
+extern "C" int gm_dev_fmt_e2(gm_index* ix, const double* v, uint32_t n, char* out, uint8_t* len) { return dev_fmt_probe(ix, v, n, out, len, gmk_fmt_e2); }
 
 // ------------------------------------------------------------------------------------------------
 // enqueue / wait forms of the two batch calls: a caller thread hands a block to the batch's service thread and goes on with the next
@@ -2346,19 +2350,18 @@ int snp_tracks_ready(gm_index* ix) {
 }
 }  // namespace
 
-extern "C" int gm_snp_calls(gm_index* ix, float snp_pval, int monop, gm_snp_rec* out, uint64_t cap, uint64_t* n_out, void* stream) {
-    if (!ix || !n_out || (cap && !out)) return GM_E_ARG;
-    if (const int rc = snp_tracks_ready(ix)) return rc;
+// the 'Y' rows of the positions [p_lo, p_hi) (clamped to the reference): gm_snp_calls is the whole range, gm_coverage_write_vcf fetches in pieces
+static int snp_calls_range(gm_index* ix, float snp_pval, int monop, uint64_t p_lo, uint64_t p_hi, gm_snp_rec* out, uint64_t cap, uint64_t* n_out, void* stream) {
     HIPCHK(hipSetDevice(ix->device));
     hipStream_t st = S_(stream);
-    const uint64_t l_pac = ix->h.l_pac, bins = ix->cov_bins;
+    const uint64_t l_pac = std::min<uint64_t>(ix->h.l_pac, p_hi), bins = ix->cov_bins;
     const uint64_t per = (uint64_t)std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 20)) * 16;       // positions per launch
     const uint32_t groups = gmk_snp_call_groups(std::min(per, l_pac));
     Scoped<DevBuf> d_code, d_pval, d_cnt, d_off, d_out;
     if (d_code.ensure(per) || d_pval.ensure(per * 8) || d_cnt.ensure((size_t)groups * 4 + 4) || d_off.ensure(((size_t)groups + 1) * 8) ||
         d_out.ensure((size_t)std::max<uint64_t>(cap, 1) * sizeof(GmDevSnpRec))) return GM_E_NOMEM;
     unsigned long long total = 0;
-    for (uint64_t lo = 0; lo < l_pac; lo += per) {
+    for (uint64_t lo = p_lo; lo < l_pac; lo += per) {
         const uint64_t n = std::min(per, l_pac - lo);
         KCHK(gmk_snp_call(ix->d_cov.as<float>(), ix->d_nuc.as<float>(), bins, ix->dev, lo, n, snp_pval, monop ? 1 : 0, d_code.as<uint8_t>(), d_pval.as<double>(),
                           d_cnt.as<uint32_t>(), st));
@@ -2376,6 +2379,12 @@ extern "C" int gm_snp_calls(gm_index* ix, float snp_pval, int monop, gm_snp_rec*
     return GM_OK;
 }
 
+extern "C" int gm_snp_calls(gm_index* ix, float snp_pval, int monop, gm_snp_rec* out, uint64_t cap, uint64_t* n_out, void* stream) {
+    if (!ix || !n_out || (cap && !out)) return GM_E_ARG;
+    if (const int rc = snp_tracks_ready(ix)) return rc;
+    return snp_calls_range(ix, snp_pval, monop, 0, ~0ull, out, cap, n_out, stream);
+}
+
 extern "C" int gm_dev_snp_stat(gm_index* ix, const float* counts, uint32_t n, int monop, double* p_val, int8_t* pos1, int8_t* pos2, uint8_t* dip) {
     if (!ix || !counts || !p_val || !pos1 || !pos2 || !dip) return GM_E_ARG;
     if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
@@ -2391,6 +2400,36 @@ extern "C" int gm_dev_snp_stat(gm_index* ix, const float* counts, uint32_t n, in
     HIPCHK(hipMemcpy(dip, d_d.p, n, hipMemcpyDeviceToHost));
     return GM_OK;
 }
+
+namespace {
+// one row of the nine-column .gmp: GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1009 with PrintSNPCall's column (:1011-1090) from k_snp_call's
+// code byte.  The caller holds one slab of n positions from `base` on: f[q * n + count - base] = the total (q = 0) and the five sums,
+// code / pval the same positions' calls; i = the caller's contig cursor, looked up at the first position of a run
+struct CallsEmit {
+    const GmHostIndex& h; const float* f; const uint8_t* code; const double* pval; uint64_t base, n;
+    char* operator()(uint64_t count, char* w, int& i, bool first) const {
+        if (first) i = (int)host_pos2rid(h, count);
+        while ((size_t)i + 1 < h.contigs.size() && count >= h.contigs[(size_t)i + 1].offset) ++i;
+        const uint64_t k = count - base;
+        if (!(f[k] > 0.001f)) return w;
+        const GmContig& cg = h.contigs[(size_t)i];
+        memcpy(w, cg.name.data(), cg.name.size()); w += cg.name.size();
+        *w++ = '\t'; w = put_long(w, (long)(count - cg.offset) + 1); *w++ = '\t';
+        w = put_fixed(w, f[k], 5);
+        for (uint64_t q = 1; q <= 5; ++q) { *w++ = '\t'; w = put_fixed(w, f[q * n + k], 5); }
+        const unsigned cd = code[k];
+        const unsigned at = (h.pac[count >> 2] >> ((~count & 3) << 1)) & 3, p1 = cd & 7u, dip = (cd >> 5) & 1u, r2 = (cd >> 3) & 3u;
+        *w++ = '\t'; *w++ = (cd & 0x40) ? 'Y' : 'N';
+        if (p1 != at || dip) {                                                // :1065-1085
+            *w++ = ':'; *w++ = "acgt"[at]; *w++ = '-'; *w++ = '>'; *w++ = "acgtn"[p1];
+            if (dip) { *w++ = '/'; *w++ = "acgtn"[r2 + (r2 >= p1 ? 1u : 0u)]; }
+            w += snprintf(w, 40, " p_val=%.2e", pval[k]);
+        }
+        *w++ = '\n';
+        return w;
+    }
+};
+}  // namespace
 
 extern "C" int gm_coverage_write_gmp_calls(gm_index* ix, float snp_pval, int monop, const char* path, int append) {
     // GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1009 with PrintSNPCall's column (:1011-1090).  A slab of the six tracks comes down from
@@ -2416,31 +2455,10 @@ extern "C" int gm_coverage_write_gmp_calls(gm_index* ix, float snp_pval, int mon
         HIPCHK(hipMemcpy(h_pval.p, d_pval.p, s_n * 8, hipMemcpyDeviceToHost));
         return GM_OK;
     };
-    size_t max_name = 0;
-    for (const auto& c : h.contigs) max_name = std::max(max_name, c.name.size());
     std::vector<int> cur(host_threads(), 0);
-    return write_track_text(path, append, nbk, max_name + 208, [&](uint64_t count, char* w, unsigned c, bool first) -> char* {
-        int& i = cur[c];
-        if (first) i = (int)host_pos2rid(h, count);
-        while ((size_t)i + 1 < h.contigs.size() && count >= h.contigs[(size_t)i + 1].offset) ++i;
-        const uint64_t k = count - s_lo;
-        const float* f = h_f.as<float>();
-        if (!(f[k] > 0.001f)) return w;
-        const GmContig& cg = h.contigs[(size_t)i];
-        memcpy(w, cg.name.data(), cg.name.size()); w += cg.name.size();
-        *w++ = '\t'; w = put_long(w, (long)(count - cg.offset) + 1); *w++ = '\t';
-        w = put_fixed(w, f[k], 5);
-        for (uint64_t q = 1; q <= 5; ++q) { *w++ = '\t'; w = put_fixed(w, f[q * s_n + k], 5); }
-        const unsigned cd = h_code.as<uint8_t>()[k];
-        const unsigned at = (h.pac[count >> 2] >> ((~count & 3) << 1)) & 3, p1 = cd & 7u, dip = (cd >> 5) & 1u, r2 = (cd >> 3) & 3u;
-        *w++ = '\t'; *w++ = (cd & 0x40) ? 'Y' : 'N';
-        if (p1 != at || dip) {                                                // :1065-1085
-            *w++ = ':'; *w++ = "acgt"[at]; *w++ = '-'; *w++ = '>'; *w++ = "acgtn"[p1];
-            if (dip) { *w++ = '/'; *w++ = "acgtn"[r2 + (r2 >= p1 ? 1u : 0u)]; }
-            w += snprintf(w, 40, " p_val=%.2e", h_pval.as<double>()[k]);
-        }
-        *w++ = '\n';
-        return w;
+    return write_track_text(path, append, nbk, max_contig_name(h) + 208, [&](uint64_t count, char* w, unsigned c, bool first) -> char* {
+        const CallsEmit e{ h, h_f.as<float>(), h_code.as<uint8_t>(), h_pval.as<double>(), s_lo, s_n };
+        return e(count, w, cur[c], first);
     }, slab);
 }
 
@@ -2473,7 +2491,10 @@ struct TrackSink {
 // bins [lo, hi) as rows: per slab of GM_TRACK_SLICE bins the sizes pass and its scan, the 32 bytes of `meta` read back, a text buffer of
 // exactly that size, the rows pass, and the text down in pieces of 32 MB through two page-locked buffers (the copy of one piece runs
 // while the one before it is written).  A slab whose meta says that a printed value needs snprintf is formatted here from its own tracks.
-int track_text_run(gm_index* ix, const char* call, int kind, char want, uint64_t lo, uint64_t hi, TrackSink& out) {
+// GM_TRACK_CALLS (the nine-column .gmp): k_snp_call runs first on every slab and its code bytes / p-values stay in HBM for the two passes.
+// GM_TRACK_CALLS: k_snp_call with `calls` settings fills the slab's code bytes and p-values before the sizes pass
+struct TrackCalls { float snp_pval; int monop; };
+int track_text_run(gm_index* ix, const char* call, int kind, char want, uint64_t lo, uint64_t hi, TrackSink& out, const TrackCalls* calls = nullptr) {
     HIPCHK(hipSetDevice(ix->device));
     if (const int rc = index_cnames(ix)) return rc;
     const GmHostIndex& h = ix->h;
@@ -2484,10 +2505,14 @@ int track_text_run(gm_index* ix, const char* call, int kind, char want, uint64_t
     gm_track_text_stats st{};
     ix->tt_stats = st;
     const uint32_t tiles_max = gmk_track_tiles(std::min(per, hi - lo));
-    Scoped<DevBuf> d_len, d_off, d_meta, d_text;
+    Scoped<DevBuf> d_len, d_off, d_meta, d_text, d_code, d_pval, d_cnt;
     Scoped<PinBuf> h_meta, h_txt[2];
     ScopedEvents ev;
     if (d_len.ensure((size_t)tiles_max * 4 + 4) || d_off.ensure(((size_t)tiles_max + 1) * 8) || d_meta.ensure(TT_META_N * 8) || h_meta.ensure(TT_META_N * 8)) return GM_E_NOMEM;
+    const bool nine = kind == GM_TRACK_CALLS;
+    if (nine && !calls) return GM_E_ARG;
+    const uint64_t slab_max = std::min(per, hi - lo);
+    if (nine && slab_max && (d_code.ensure(slab_max) || d_pval.ensure(slab_max * 8) || d_cnt.ensure((size_t)gmk_snp_call_groups(slab_max) * 4 + 4))) return GM_E_NOMEM;
     HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
     GmDevTrack t{};
     t.cov = ix->d_cov.as<float>(); t.nuc = kind == GM_TRACK_SGR ? nullptr : ix->d_nuc.as<float>(); t.nuc_stride = bins;
@@ -2495,39 +2520,53 @@ int track_text_run(gm_index* ix, const char* call, int kind, char want, uint64_t
     t.cnames = ix->d_cnames.as<char>(); t.cname_off = ix->d_cname_off.as<uint32_t>();
     t.bin_size = (uint32_t)bs; t.kind = (uint32_t)kind; t.want = want == 'a' ? 0u : want == 'c' ? 1u : want == 'g' ? 2u : 3u;
     t.tile_len = d_len.as<uint32_t>(); t.tile_off = d_off.as<unsigned long long>(); t.meta = d_meta.as<unsigned long long>();
+    t.code = d_code.as<uint8_t>(); t.pval = d_pval.as<double>();
     const hipStream_t s = nullptr;
     const unsigned long long* meta = h_meta.as<unsigned long long>();
-    const size_t max_line = max_contig_name(h) + 160;
+    const size_t max_line = max_contig_name(h) + (nine ? 208 : 160);
     std::vector<float> hf; std::vector<char> hbuf;          // a host-formatted slab's tracks and text
+    std::vector<uint8_t> hcode; std::vector<double> hpval;  // and, for the nine-column file, its calls
     auto fail_io = [&]() { gm_set_error(std::string(call) + ": write failed"); return GM_E_IO; };
+    // the host emitters, from this slab's tracks only
+    auto host_slab = [&](uint64_t s0, uint64_t n) -> int {
+        ++st.host_slabs;
+        const int cols = kind == GM_TRACK_SGR ? 1 : 6;
+        hf.resize((size_t)n * cols);
+        HIPCHK(hipMemcpy(hf.data(), t.cov + s0, n * 4, hipMemcpyDeviceToHost));
+        for (int q = 1; q < cols; ++q) HIPCHK(hipMemcpy(hf.data() + (size_t)q * n, t.nuc + (uint64_t)(q - 1) * bins + s0, n * 4, hipMemcpyDeviceToHost));
+        if (nine) {
+            hcode.resize((size_t)n); hpval.resize((size_t)n);
+            HIPCHK(hipMemcpy(hcode.data(), t.code, n, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hpval.data(), t.pval, n * 8, hipMemcpyDeviceToHost));
+        }
+        const TrackEmit e{ h, bs, kind, want, hf.data(), hf.data() + n, n, s0 };
+        const CallsEmit e9{ h, hf.data(), hcode.data(), hpval.data(), s0, n };
+        int cur = 0;
+        for (uint64_t k0 = s0; k0 < s0 + n; k0 += 65536) {
+            const uint64_t k1 = std::min(s0 + n, k0 + 65536);
+            hbuf.resize((size_t)(k1 - k0) * max_line);
+            char* w = hbuf.data();
+            for (uint64_t k = k0; k < k1; ++k) { char* const w2 = nine ? e9(k, w, cur, k == k0) : e(k, w, cur, k == k0); st.rows += w2 != w; w = w2; }
+            if (!out.put(hbuf.data(), (uint64_t)(w - hbuf.data()))) return fail_io();
+        }
+        return GM_OK;
+    };
     for (uint64_t s0 = lo; s0 < hi; s0 += per) {
         const uint64_t n = std::min(per, hi - s0);
         float ms = 0;
         t.lo = s0; t.n = n; t.text = nullptr;
         HIPCHK(hipMemsetAsync(d_meta.p, 0, TT_META_N * 8, s));
         HIPCHK(hipEventRecord(ev.a, s));
+        if (nine) KCHK(gmk_snp_call(t.cov, t.nuc, bins, ix->dev, s0, n, calls->snp_pval, calls->monop ? 1 : 0, d_code.as<uint8_t>(), d_pval.as<double>(), d_cnt.as<uint32_t>(), s));
         KCHK(gmk_track_sizes(t, s));
         HIPCHK(hipEventRecord(ev.b, s));
         HIPCHK(hipMemcpyAsync(h_meta.p, d_meta.p, TT_META_N * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
-        st.kernel_ms += ms; st.launches += 2; ++st.slabs;
+        st.kernel_ms += ms; st.launches += nine ? 3 : 2; ++st.slabs;
         const uint64_t bytes = meta[TT_META_BYTES];
-        if (meta[TT_META_HOST]) {                            // the host emitters, from this slab's tracks only
-            ++st.host_slabs;
-            const int cols = kind == GM_TRACK_SGR ? 1 : 6;
-            hf.resize((size_t)n * cols);
-            HIPCHK(hipMemcpy(hf.data(), t.cov + s0, n * 4, hipMemcpyDeviceToHost));
-            for (int q = 1; q < cols; ++q) HIPCHK(hipMemcpy(hf.data() + (size_t)q * n, t.nuc + (uint64_t)(q - 1) * bins + s0, n * 4, hipMemcpyDeviceToHost));
-            const TrackEmit e{ h, bs, kind, want, hf.data(), hf.data() + n, n, s0 };
-            int cur = 0;
-            for (uint64_t k0 = s0; k0 < s0 + n; k0 += 65536) {
-                const uint64_t k1 = std::min(s0 + n, k0 + 65536);
-                hbuf.resize((size_t)(k1 - k0) * max_line);
-                char* w = hbuf.data();
-                for (uint64_t k = k0; k < k1; ++k) { char* const w2 = e(k, w, cur, k == k0); st.rows += w2 != w; w = w2; }
-                if (!out.put(hbuf.data(), (uint64_t)(w - hbuf.data()))) return fail_io();
-            }
+        if (meta[TT_META_HOST]) {
+            if (const int rc = host_slab(s0, n)) return rc;
             continue;
         }
         st.rows += meta[TT_META_ROWS];
@@ -2539,6 +2578,15 @@ int track_text_run(gm_index* ix, const char* call, int kind, char want, uint64_t
             KCHK(gmk_track_rows(t, s));
             HIPCHK(hipEventRecord(ev.b, s));
             ++st.launches;
+            if (nine) {                                      // k_track_rows<true> flags a p-value that gm_put_e2_hd refused inside its domain
+                HIPCHK(hipMemcpyAsync(h_meta.p, d_meta.p, TT_META_N * 8, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                if (meta[TT_META_HOST]) {
+                    st.rows -= meta[TT_META_ROWS];           // host_slab counts them
+                    if (const int rc = host_slab(s0, n)) return rc;
+                    continue;
+                }
+            }
             if (out.fd < 0) HIPCHK(hipMemcpy(out.mem + out.total, t.text, (size_t)need, hipMemcpyDeviceToHost));
             else {
                 const char* prev = nullptr; size_t prev_n = 0; int c = 0;
@@ -2612,6 +2660,94 @@ extern "C" int gm_coverage_text(gm_index* ix, const gm_params* p, uint64_t bin_l
     if (const int rc = track_text_run(ix, "gm_coverage_text", kind, want, bin_lo, bin_hi, out)) return rc;
     *n_out = out.total;
     if (out.total > cap) { gm_set_error("gm_coverage_text: text[] too small"); return GM_E_CAPACITY; }
+    return GM_OK;
+}
+
+namespace {
+// snp_tracks_ready under the caller's name: bin size 1, the five sums, a device
+int calls_text_ready(gm_index* ix, const char* call) {
+    if (!ix->cov_bins || ix->cov_bin_size != 1) { gm_set_error(std::string(call) + ": SNP calls need the coverage track with bin size 1 (gm_coverage_reset(ix, 1))"); return GM_E_ARG; }
+    if (!ix->host_only && !ix->nuc_on) { gm_set_error(std::string(call) + ": SNP calls read the per-nucleotide tracks: call gm_coverage_enable_nuc first"); return GM_E_ARG; }
+    if (ix->host_only) { gm_set_error(std::string(call) + ": no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    return GM_OK;
+}
+}  // namespace
+
+extern "C" int gm_coverage_write_gmp_calls_device(gm_index* ix, float snp_pval, int monop, const char* path, int append) {
+    // the file of gm_coverage_write_gmp_calls from the tracks in HBM: k_snp_call, then k_track_sizes<true> / k_track_rows<true> per slab
+    const char* const call = "gm_coverage_write_gmp_calls_device";
+    if (!ix || !path) { gm_set_error(std::string(call) + ": null argument"); return GM_E_ARG; }
+    if (const int rc = calls_text_ready(ix, call)) return rc;
+    const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
+    if (fd < 0) { gm_set_error(std::string(call) + ": cannot write " + path); return GM_E_IO; }
+    TrackSink out;
+    out.fd = fd; out.file_off = append ? (uint64_t)lseek(fd, 0, SEEK_END) : 0;
+    const TrackCalls calls{ snp_pval, monop };
+    const int rc = track_text_run(ix, call, GM_TRACK_CALLS, 0, 0, ix->cov_bins, out, &calls);
+    ::close(fd);
+    return rc;
+}
+
+extern "C" int gm_coverage_calls_text(gm_index* ix, float snp_pval, int monop, uint64_t bin_lo, uint64_t bin_hi, char* text, uint64_t cap, uint64_t* n_out) {
+    const char* const call = "gm_coverage_calls_text";
+    if (!ix || !n_out || (cap && !text)) { gm_set_error(std::string(call) + ": null argument"); return GM_E_ARG; }
+    if (!ix->cov_bins || !ix->cov_bin_size) { gm_set_error(std::string(call) + ": no coverage track (gm_coverage_reset)"); return GM_E_ARG; }
+    if (bin_lo > bin_hi || bin_hi > ix->cov_bins) { gm_set_error(std::string(call) + ": bins [bin_lo, bin_hi) are not a range of the track"); return GM_E_ARG; }
+    if (const int rc = calls_text_ready(ix, call)) return rc;
+    TrackSink out;
+    out.mem = text; out.cap = cap;
+    const TrackCalls calls{ snp_pval, monop };
+    if (const int rc = track_text_run(ix, call, GM_TRACK_CALLS, 0, bin_lo, bin_hi, out, &calls)) return rc;
+    *n_out = out.total;
+    if (out.total > cap) { gm_set_error(std::string(call) + ": text[] too small"); return GM_E_CAPACITY; }
+    return GM_OK;
+}
+
+extern "C" int gm_coverage_write_vcf(gm_index* ix, float snp_pval, int monop, const char* path, int append) {
+    // Genome::PrintFinalVCF src/Genome.cpp:1142-1245 over gm_snp_calls' records.  The rows are few (one per called SNP), so they are
+    // formatted here: a count pass, then the records of one stretch of positions at a time
+    const char* const call = "gm_coverage_write_vcf";
+    if (!ix || !path) { gm_set_error(std::string(call) + ": null argument"); return GM_E_ARG; }
+    if (const int rc = calls_text_ready(ix, call)) return rc;
+    uint64_t total = 0;
+    int rc = snp_calls_range(ix, snp_pval, monop, 0, ~0ull, nullptr, 0, &total, nullptr);
+    if (rc != GM_OK && rc != GM_E_CAPACITY) return rc;
+    FILE* f = fopen(path, append ? "a" : "w");
+    if (!f) { gm_set_error(std::string(call) + ": cannot write " + path); return GM_E_IO; }
+    if (!append) {
+        char date[16] = "";
+        const time_t now = time(nullptr);
+        struct tm tmv;
+        if (localtime_r(&now, &tmv)) strftime(date, sizeof date, "%Y%m%d", &tmv);
+        fprintf(f, "##fileformat=VCFv4.0\n##fileDate=%s\n##source=%s\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n", date, gm_version());
+    }
+    const GmHostIndex& h = ix->h;
+    const uint64_t step = (uint64_t)std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 20)) * 16;     // snp_calls_range's positions per launch
+    std::vector<gm_snp_rec> recs((size_t)std::min<uint64_t>(std::max<uint64_t>(total, 1), 1u << 16));
+    unsigned long long id = 0;
+    for (uint64_t lo = 0; total && lo < h.l_pac; lo += step) {
+        uint64_t got = 0;
+        rc = snp_calls_range(ix, snp_pval, monop, lo, lo + step, recs.data(), recs.size(), &got, nullptr);
+        if (rc == GM_E_CAPACITY) {                           // a denser stretch: once more with room for it
+            recs.resize((size_t)got);
+            rc = snp_calls_range(ix, snp_pval, monop, lo, lo + step, recs.data(), recs.size(), &got, nullptr);
+        }
+        if (rc != GM_OK) { fclose(f); return rc; }
+        auto base = [](unsigned b) { return b < 5u ? b : 4u; };
+        for (uint64_t r = 0; r < got; ++r) {
+            const gm_snp_rec& c = recs[(size_t)r];
+            const unsigned a1 = base(c.alt1), a2 = base(c.alt2);
+            const char* name = h.contigs[c.contig].name.c_str();
+            if (c.diploid)
+                fprintf(f, "%s\t%llu\tsnp%llu\t%c\t%c%c\t.\t.\tDiploid;pval=%.5f;coverage=%.5f;ratio=%.2f\n", name, (unsigned long long)c.chr_pos, id++, "acgtn"[base(c.ref)],
+                        "acgtn"[a1], "acgtn"[a2], c.p_val, c.total, c.nuc[a2] / c.nuc[a1]);
+            else
+                fprintf(f, "%s\t%llu\tsnp%llu\t%c\t%c\t.\t.\tMonoploid;pval=%.5f;coverage=%.5f\n", name, (unsigned long long)c.chr_pos, id++, "acgtn"[base(c.ref)], "acgtn"[a1], c.p_val,
+                        c.total);
+        }
+    }
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) { gm_set_error(std::string(call) + ": write failed: " + path); return GM_E_IO; }
     return GM_OK;
 }
 

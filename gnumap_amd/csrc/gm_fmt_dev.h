@@ -1,15 +1,16 @@
-// gm_fmt_dev.h — exact printf("%g") that compiles for the host and for the device: the XA / XP columns of a SAM row
-// (src/Driver.cpp:2196-2205) written by k_out_text_sizes (gm_output.hip).  No library calls, no division of wide integers.
+// gm_fmt_dev.h — exact printf("%g") and printf("%.2e") that compile for the host and for the device: the XA / XP columns of a SAM row
+// (src/Driver.cpp:2196-2205) written by k_out_text_sizes (gm_output.hip), and the p-value of --snp's ninth .gmp column
+// (PrintSNPCall src/GenomeBwt.cpp:1011-1090) written by k_track_rows (gm_tracktext.hip).  No library calls, no division of wide integers.
 //
-// Domain: 0, -0, inf, nan and every double with 2^-200 <= |v| < 2^200 (every float, denormals included, times any sensible
-// 1 / adjust).  Outside it gm_put_g6_hd writes nothing and returns its argument: a caller sees length 0 and refuses the record
-// instead of printing a wrong digit.
+// Domain of gm_put_g6_hd: 0, -0, inf, nan and every double with 2^-200 <= |v| < 2^200 (every float, denormals included, times any
+// sensible 1 / adjust); of gm_put_e2_hd: +0.0 and 2^-200 <= v < 2^200 (a p-value).  Outside it they write nothing and return their
+// argument: a caller sees length 0 and refuses the record (or hands the slab to the host) instead of printing a wrong digit.
 //
-// Scheme: v = m * 2^e2 with a 53-bit m.  For a decimal exponent E, N = floor(v / 10^(E-5)) is estimated in double (one rounding of
-// v, one of the power: off by one at most), then pinned with 256-bit integers: A / B = v / 10^(E-5) with A, B products of m, a power
-// of five (table) and a power of two (shift), N B <= A < (N+1) B.  100000 <= N < 1000000 says that E was right; the remainder
-// A - N B against B / 2 gives round-half-even on the exact binary value, as printf rounds.  Largest integer that occurs:
-// m * 5^68 < 2^211.
+// Scheme, for D significant digits (6 and 3): v = m * 2^e2 with a 53-bit m.  For a decimal exponent E, N = floor(v / 10^(E-D+1)) is
+// estimated in double (one rounding of v, one of the power: off by one at most), then pinned with 256-bit integers:
+// A / B = v / 10^(E-D+1) with A, B products of m, a power of five (table) and a power of two (shift), N B <= A < (N+1) B.
+// 10^(D-1) <= N < 10^D says that E was right; the remainder A - N B against B / 2 gives round-half-even on the exact binary value, as
+// printf rounds.  Largest integer that occurs: m * 5^68 < 2^211.
 #pragma once
 #include <stdint.h>
 
@@ -74,9 +75,12 @@ GM_FMT_HD static inline char* gm_put_digits(char* w, uint32_t v, int count) {
     return w + count;
 }
 
-// "%g" of v; returns the end of the text, or w itself (nothing written) outside the domain
-GM_FMT_HD static inline char* gm_put_g6_hd(char* w, double v) {
-static const uint64_t t5[69][3] = {
+// the D leading decimal digits (D = 6: "%g", D = 3: "%.2e") of av = m * 2^e2, 2^-200 <= av < 2^200 with the biased exponent be:
+// 10^(D-1) <= N < 10^D, its first digit at 10^E, rounded half-even on the exact binary value.  false: refused (the estimate was not
+// within a few units, or a product would leave 256 bits); the callers then write nothing.
+template <int D> GM_FMT_HD static inline bool gm_fmt_digits_hd(double av, int be, uint64_t m, int e2, uint32_t& N_out, int& E_out) {
+    static_assert(D == 6 || D == 3, "the bounds below are worked out for these two");
+    static const uint64_t t5[69][3] = {
         { 0x0000000000000001ull, 0x0000000000000000ull, 0x0000000000000000ull }, { 0x0000000000000005ull, 0x0000000000000000ull, 0x0000000000000000ull },
         { 0x0000000000000019ull, 0x0000000000000000ull, 0x0000000000000000ull }, { 0x000000000000007dull, 0x0000000000000000ull, 0x0000000000000000ull },
         { 0x0000000000000271ull, 0x0000000000000000ull, 0x0000000000000000ull }, { 0x0000000000000c35ull, 0x0000000000000000ull, 0x0000000000000000ull },
@@ -122,6 +126,46 @@ static const uint64_t t5[69][3] = {
         1e50, 1e51, 1e52, 1e53, 1e54, 1e55, 1e56, 1e57, 1e58, 1e59,
         1e60, 1e61, 1e62, 1e63, 1e64, 1e65, 1e66, 1e67, 1e68,
     };
+    int E = ((be - 1023) * 1233) >> 12;                      // floor(log10 |v|) to within two: N below says which way it is off
+    constexpr uint64_t lo = D == 6 ? 100000ull : 100ull, hi = lo * 10ull;
+    constexpr double xlo = D == 6 ? 1e3 : 1.0, xhi = D == 6 ? 1e9 : 1e6;     // E off by two either way still lands inside
+    uint32_t N = 0;
+    bool found = false;
+    for (int tries = 0; tries < 5 && !found; ++tries) {
+        const int j = E - (D - 1), aj = j < 0 ? -j : j;
+        if (aj > 68) return false;
+        // the estimate first: xlo <= x < xhi also says that nothing below leaves 256 bits (A 2^s < 2^30 B, B 2^-s <= A)
+        const double x = j < 0 ? av * p10[aj] : av / p10[aj];
+        if (!(x < xhi)) { ++E; continue; }
+        if (!(x >= xlo)) { --E; continue; }
+        gm_u256 P5; P5.w0 = t5[aj][0]; P5.w1 = t5[aj][1]; P5.w2 = t5[aj][2]; P5.w3 = 0;
+        gm_u256 A, B;
+        if (j < 0) { A = gm_u256_mul64(P5, m); B.w0 = 1; B.w1 = B.w2 = B.w3 = 0; }
+        else { A.w0 = m; A.w1 = A.w2 = A.w3 = 0; B = P5; }
+        const int s = e2 - j;                                // v / 10^j = A / B * 2^s
+        if (s > 250 || s < -250) return false;
+        if (s >= 0) A = gm_u256_shl(A, (unsigned)s); else B = gm_u256_shl(B, (unsigned)-s);
+        uint64_t n = (uint64_t)x;
+        gm_u256 NB = gm_u256_mul64(B, n);
+        for (int k = 0; k < 4 && gm_u256_cmp(NB, A) > 0; ++k) { --n; NB = gm_u256_sub(NB, B); }
+        if (gm_u256_cmp(NB, A) > 0) return false;
+        gm_u256 R = gm_u256_sub(A, NB);
+        for (int k = 0; k < 4 && gm_u256_cmp(R, B) >= 0; ++k) { ++n; R = gm_u256_sub(R, B); }
+        if (gm_u256_cmp(R, B) >= 0) return false;            // the estimate was not within a few units: refuse, never guess
+        if (n < lo) { --E; continue; }
+        if (n >= hi) { ++E; continue; }
+        const int c = gm_u256_cmp(gm_u256_shl(R, 1), B);     // remainder against one half
+        if (c > 0 || (c == 0 && (n & 1ull))) ++n;
+        if (n == hi) { n = lo; ++E; }                        // the rounding carried into one digit more
+        N = (uint32_t)n;
+        found = true;
+    }
+    N_out = N; E_out = E;
+    return found;
+}
+
+// "%g" of v; returns the end of the text, or w itself (nothing written) outside the domain
+GM_FMT_HD static inline char* gm_put_g6_hd(char* w, double v) {
     char* const w0 = w;
     uint64_t bits;
     __builtin_memcpy(&bits, &v, 8);
@@ -140,39 +184,8 @@ static const uint64_t t5[69][3] = {
     const uint64_t abits = bits & ~(1ull << 63);
     double av;
     __builtin_memcpy(&av, &abits, 8);
-    int E = ((be - 1023) * 1233) >> 12;                      // floor(log10 |v|) to within two: N below says which way it is off
-    uint32_t N = 0;
-    bool found = false;
-    for (int tries = 0; tries < 5 && !found; ++tries) {
-        const int j = E - 5, aj = j < 0 ? -j : j;
-        if (aj > 68) return w0;
-        // the estimate first: 1e3 <= x < 1e9 also says that nothing below leaves 256 bits (A 2^s < 2^30 B, B 2^-s <= A / 1000)
-        const double x = j < 0 ? av * p10[aj] : av / p10[aj];
-        if (!(x < 1e9)) { ++E; continue; }
-        if (!(x >= 1e3)) { --E; continue; }
-        gm_u256 P5; P5.w0 = t5[aj][0]; P5.w1 = t5[aj][1]; P5.w2 = t5[aj][2]; P5.w3 = 0;
-        gm_u256 A, B;
-        if (j < 0) { A = gm_u256_mul64(P5, m); B.w0 = 1; B.w1 = B.w2 = B.w3 = 0; }
-        else { A.w0 = m; A.w1 = A.w2 = A.w3 = 0; B = P5; }
-        const int s = e2 - j;                                // v / 10^j = A / B * 2^s
-        if (s > 250 || s < -250) return w0;
-        if (s >= 0) A = gm_u256_shl(A, (unsigned)s); else B = gm_u256_shl(B, (unsigned)-s);
-        uint64_t n = (uint64_t)x;
-        gm_u256 NB = gm_u256_mul64(B, n);
-        for (int k = 0; k < 4 && gm_u256_cmp(NB, A) > 0; ++k) { --n; NB = gm_u256_sub(NB, B); }
-        if (gm_u256_cmp(NB, A) > 0) return w0;
-        gm_u256 R = gm_u256_sub(A, NB);
-        for (int k = 0; k < 4 && gm_u256_cmp(R, B) >= 0; ++k) { ++n; R = gm_u256_sub(R, B); }
-        if (gm_u256_cmp(R, B) >= 0) return w0;               // the estimate was not within a few units: refuse, never guess
-        if (n < 100000ull) { --E; continue; }
-        if (n >= 1000000ull) { ++E; continue; }
-        const int c = gm_u256_cmp(gm_u256_shl(R, 1), B);     // remainder against one half
-        if (c > 0 || (c == 0 && (n & 1ull))) ++n;
-        if (n == 1000000ull) { n = 100000ull; ++E; }         // the rounding carried into a seventh digit
-        N = (uint32_t)n;
-        found = true;
-    }
-    if (!found) return w0;
+    uint32_t N; int E;
+    if (!gm_fmt_digits_hd<6>(av, be, m, e2, N, E)) return w0;
     int nd = 6;
     while (nd > 1 && N % 10u == 0) { N /= 10u; --nd; }       // trailing zeros go (no '#' flag); N now has nd digits, the first at 10^E
     if (neg) *w++ = '-';
@@ -201,4 +214,21 @@ static const uint64_t t5[69][3] = {
         w = gm_put_digits(w, N, nd);
     }
     return w;
+}
+
+// "%.2e" of v, always the 8 characters d.dde[+-]dd; returns the end of the text, or w itself (nothing written) outside the domain:
+// +0.0 and positive doubles with 2^-200 <= v < 2^200 (decimal exponents -61 .. 60).  The p-value of --snp's ninth column.
+GM_FMT_HD static inline char* gm_put_e2_hd(char* w, double v) {
+    uint64_t bits;
+    __builtin_memcpy(&bits, &v, 8);
+    uint32_t N = 0; int E = 0;                               // +0.0: 0.00e+00
+    if (bits) {
+        const int be = (int)((bits >> 52) & 0x7FFu);
+        if ((bits >> 63) || be < 1023 - 200 || be >= 1023 + 200) return w;       // negative, -0.0, nan, inf, denormal, out of range
+        if (!gm_fmt_digits_hd<3>(v, be, (bits & ((1ull << 52) - 1)) | (1ull << 52), be - 1075, N, E)) return w;
+    }
+    const uint32_t ae = (uint32_t)(E < 0 ? -E : E);          // <= 61
+    w[0] = (char)('0' + N / 100u); w[1] = '.'; w[2] = (char)('0' + N / 10u % 10u); w[3] = (char)('0' + N % 10u);
+    w[4] = 'e'; w[5] = E < 0 ? '-' : '+'; w[6] = (char)('0' + ae / 10u); w[7] = (char)('0' + ae % 10u);
+    return w + 8;
 }

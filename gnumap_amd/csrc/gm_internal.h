@@ -182,7 +182,8 @@ struct GmDevSnpRec { unsigned long long pos; uint32_t contig, pad0; unsigned lon
                      uint8_t pad1[4]; };
 
 // what the track text kernels (k_track_sizes / k_track_rows, gm_tracktext.hip) read and write: bins [lo, lo + n) of the coverage track
-enum { GM_TRACK_SGR = 0, GM_TRACK_SNP = 1, GM_TRACK_BASE = 2 };     // .sgr; --snp's .gmp; the .gmp of -b / --b2 / -d (rows of one reference base)
+enum { GM_TRACK_SGR = 0, GM_TRACK_SNP = 1, GM_TRACK_BASE = 2,       // .sgr; --snp's .gmp; the .gmp of -b / --b2 / -d (rows of one reference base)
+       GM_TRACK_CALLS = 3 };                                        // --snp's .gmp with PrintSNPCall's ninth column (bin size 1)
 enum { TT_META_BYTES = 0, TT_META_ROWS = 1, TT_META_HOST = 2, TT_META_N = 4 };
 struct GmDevTrack {
     const float* cov; const float* nuc; uint64_t nuc_stride;         // nuc: a c g t n tracks nuc_stride floats apart, or null (.sgr)
@@ -193,6 +194,7 @@ struct GmDevTrack {
     uint32_t* tile_len; unsigned long long* tile_off;                // bytes of text per tile of 256 bins; their exclusive scan (tiles + 1)
     unsigned long long* meta;                                        // TT_META_*: bytes and rows of the slab, 1 = a value only the host can print (zeroed by the caller)
     char* text;                                                      // 16-byte aligned
+    const uint8_t* code; const double* pval;                         // GM_TRACK_CALLS: k_snp_call's code byte and p-value of bin lo + i at [i]
 };
 
 // workspace of the grouping kernels (process_hits' unique map on the device); per-hit arrays share the CSR of hit_begin
@@ -284,10 +286,11 @@ int gmk_snp_call(const float* cov, const float* nuc, uint64_t bins, const GmDevI
 int gmk_snp_gather(const float* cov, const float* nuc, uint64_t bins, const GmDevIndex& ix, uint64_t lo, uint64_t n, const uint8_t* code, const double* pval,
                    const uint32_t* ycnt, unsigned long long* off, unsigned long long base, unsigned long long cap, GmDevSnpRec* out, void* stream);
 int gmk_snp_stat(const float* counts, uint32_t n, int monop, double* pval, int8_t* pos1, int8_t* pos2, uint8_t* dip, void* stream);
-// gm_tracktext.hip: .sgr / .gmp rows as text.  Sizes + their scan (meta is read back by the caller), then the rows into text[0, meta[TT_META_BYTES])
+// gm_tracktext.hip: .sgr / .gmp rows as text (GM_TRACK_CALLS: t.code / t.pval filled by gmk_snp_call for the same bins first).  Sizes + their scan (meta is read back by the caller), then the rows into text[0, meta[TT_META_BYTES])
 uint32_t gmk_track_tiles(uint64_t n);
 int gmk_track_sizes(const GmDevTrack& t, void* stream);
 int gmk_track_rows(const GmDevTrack& t, void* stream);
+int gmk_fmt_e2(const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len, void* stream);      // gm_put_e2_hd per value
 int gmk_compact(const GmDevBatch& b, void* stream);
 int gmk_scan_hits(const GmDevBatch& b, void* stream);
 int gmk_scatter(const GmDevBatch& b, uint32_t grid, void* stream);

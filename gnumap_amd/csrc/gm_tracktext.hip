@@ -1,6 +1,7 @@
 // gm_tracktext.hip — the per-position files as text, formatted where the tracks live: <out>.sgr (GenomeBwt::PrintFinalSGR
-// src/GenomeBwt.cpp:1212-1273) and the eight-column <out>.gmp (PrintFinalBisulfite :1092-1210, PrintFinalSNP :930-1009 without
-// PrintSNPCall's column).  The contract is the bytes of the host writers of gm_api.cpp (gm_coverage_write_sgr / _gmp):
+// src/GenomeBwt.cpp:1212-1273), the eight-column <out>.gmp (PrintFinalBisulfite :1092-1210, PrintFinalSNP :930-1009 without
+// PrintSNPCall's column) and the nine-column one with it.  The contract is the bytes of the host writers of gm_api.cpp
+// (gm_coverage_write_sgr / _gmp / _gmp_calls):
 //
 //   bin k, count = k * bin_size, contig = the last one whose offset is <= count (bins run over the CONCATENATED coordinate)
 //   .sgr          a row iff (double)bins[k] > 0.001            name \t count-off+1 \t %.5f \n
@@ -14,6 +15,16 @@
 // value (negative, NaN, inf, >= 1e9) is snprintf's on the host: a launch that meets one in a row it would print only FLAGS its slab
 // (meta[TT_META_HOST]) and the library formats that slab with the host emitters.  Nothing here imitates snprintf.
 //
+// GM_TRACK_CALLS is the nine-column .gmp of --snp --snp_calls (gm_coverage_write_gmp_calls): the GM_TRACK_SNP rows with PrintSNPCall's
+// column (src/GenomeBwt.cpp:1011-1090) in front of the newline, built from k_snp_call's code byte and p-value of the slab (t.code / t.pval,
+// written by gmk_snp_call before the sizes pass):
+//   \tN                          the first allele is the reference base and the call is not diploid            2 bytes
+//   \t[YN]:r->x p_val=d.dde[+-]dd                                                                              22 bytes
+//   \t[YN]:r->x/y p_val=d.dde[+-]dd   a diploid call                                                           24 bytes
+// The length follows from the code byte alone, so the sizes pass never formats a p-value: it only asks whether gm_put_e2_hd (gm_fmt_dev.h,
+// exact "%.2e" for +0.0 and 2^-200 <= p < 2^200) can print it, and flags the slab otherwise.  The calls path is a second instantiation of
+// the two kernels (k_track_sizes<true> / k_track_rows<true>): the other kinds' kernels carry none of it and keep their registers.
+//
 // Two passes over a slab of bins, one lane per bin, tiles of TT_WG consecutive bins:
 //   k_track_sizes   length of every row, summed per tile; rows counted; out-of-domain values flagged
 //   k_track_scan    exclusive scan of the tile sums by one workgroup (kernel boundaries order the passes: nothing waits for another
@@ -24,6 +35,7 @@
 //                   length is copied from HBM through as many windows as it takes.
 #include <hip/hip_runtime.h>
 #include "gm_internal.h"
+#include "gm_fmt_dev.h"
 
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -35,7 +47,8 @@ struct TtRow {
     uint32_t c0, cl;                // its contig's name in cnames
     uint32_t pos;                   // 1-based position in the contig
     float v[6];                     // the total and, in a .gmp, a c g t n
-    bool bad;                       // a printed value outside put_fixed's own domain
+    bool bad;                       // a printed value outside put_fixed's own domain (or a p-value outside gm_put_e2_hd's)
+    uint32_t call;                  // GM_TRACK_CALLS: k_snp_call's code byte, the reference base in bits 8-9
 };
 
 __device__ __forceinline__ uint32_t tt_digits(uint32_t v) {
@@ -62,27 +75,40 @@ __device__ __forceinline__ uint32_t tt_contig_search(const uint32_t* off, uint32
     return a;
 }
 
+// bytes of the ninth column of a row with the code byte cd at a position whose reference base is ref
+__device__ __forceinline__ uint32_t tt_call_len(uint32_t cd, uint32_t ref) {
+    const uint32_t p1 = cd & 7u, dip = (cd >> 5) & 1u;
+    return (p1 != ref || dip) ? (dip ? 24u : 22u) : 2u;
+}
+// gm_put_e2_hd's domain, from the bits alone
+__device__ __forceinline__ bool tt_e2_in_domain(double p) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(p);
+    const uint32_t be = (uint32_t)(bits >> 52);             // with the sign: a negative value is >= 2048
+    return bits == 0ull || (be >= 1023u - 200u && be < 1023u + 200u);
+}
+
 // what lane i of the slab prints; `contig` = the contig of the tile's first bin (the lanes walk on from it)
-__device__ __forceinline__ TtRow tt_row(const GmDevTrack& t, uint64_t i, uint32_t contig) {
+template <bool CALLS> __device__ __forceinline__ TtRow tt_row(const GmDevTrack& t, uint64_t i, uint32_t contig) {
     TtRow r;
-    r.len = 0; r.c0 = 0; r.cl = 0; r.pos = 0; r.bad = false;
+    r.len = 0; r.c0 = 0; r.cl = 0; r.pos = 0; r.bad = false; r.call = 0;
+    const uint32_t kind = CALLS ? (uint32_t)GM_TRACK_SNP : t.kind;            // the calls file: --snp's rows, one column more
     for (int q = 0; q < 6; ++q) r.v[q] = 0.0f;
     if (i >= t.n) return r;
     const uint64_t k = t.lo + i, count = k * (uint64_t)t.bin_size;
     const float total = t.cov[k];
     bool print;
-    if (t.kind == GM_TRACK_SGR) print = (double)total > 0.001;
-    else if (t.kind == GM_TRACK_SNP) print = total > 0.001f;
+    if (kind == GM_TRACK_SGR) print = (double)total > 0.001;
+    else if (kind == GM_TRACK_SNP) print = total > 0.001f;
     else print = ((uint32_t)(t.pac[count >> 2] >> ((~count & 3u) << 1)) & 3u) == t.want && total > 0.0f;
     if (!print) return r;
     while (contig + 1u < t.n_seqs && count >= (uint64_t)t.contig_off[contig + 1u]) ++contig;
     r.c0 = t.cname_off[contig]; r.cl = t.cname_off[contig + 1u] - r.c0;
     r.pos = (uint32_t)(count - (uint64_t)t.contig_off[contig]) + 1u;
     r.v[0] = total;
-    const bool six = t.kind == GM_TRACK_BASE;                                 // "%f" of the total there
+    const bool six = kind == GM_TRACK_BASE;                                   // "%f" of the total there
     r.bad = !tt_in_domain(total);
     uint32_t len = r.cl + 1u + tt_digits(r.pos) + 1u + tt_fixed_len(total, six) + 1u;
-    if (t.kind != GM_TRACK_SGR) {
+    if (kind != GM_TRACK_SGR) {
         for (int q = 0; q < 5; ++q) {
             const float x = t.nuc[(uint64_t)q * t.nuc_stride + k];
             r.v[q + 1] = x;
@@ -90,9 +116,19 @@ __device__ __forceinline__ TtRow tt_row(const GmDevTrack& t, uint64_t i, uint32_
             len += 1u + tt_fixed_len(x, false);
         }
     }
+    if (CALLS) {
+        const uint32_t cd = t.code[i], ref = (uint32_t)(t.pac[count >> 2] >> ((~count & 3u) << 1)) & 3u;
+        const uint32_t col = tt_call_len(cd, ref);
+        if (col > 2u) r.bad |= !tt_e2_in_domain(t.pval[i]);
+        r.call = cd | (ref << 8);
+        len += col;
+    }
     r.len = len;
     return r;
 }
+
+// "acgtn"[b] without a table in memory
+__device__ __forceinline__ char tt_letter(uint32_t b) { return b == 0u ? 'a' : b == 1u ? 'c' : b == 2u ? 'g' : b == 3u ? 't' : 'n'; }
 
 // sum over the workgroup (every lane gets it) and the exclusive prefix of the lane
 __device__ __forceinline__ uint32_t tt_block_scan(uint32_t v, uint32_t* s_wave, uint32_t& total) {
@@ -107,7 +143,7 @@ __device__ __forceinline__ uint32_t tt_block_scan(uint32_t v, uint32_t* s_wave, 
     return before + inc - v;
 }
 
-__global__ void __launch_bounds__(TT_WG) k_track_sizes(GmDevTrack t) {
+template <bool CALLS> __global__ void __launch_bounds__(TT_WG) k_track_sizes(GmDevTrack t) {
     __shared__ uint32_t s_wave[TT_WG / 64u];
     __shared__ uint32_t s_contig, s_rows, s_bad;
     if (threadIdx.x == 0) {
@@ -115,7 +151,7 @@ __global__ void __launch_bounds__(TT_WG) k_track_sizes(GmDevTrack t) {
         s_rows = 0; s_bad = 0;
     }
     __syncthreads();
-    const TtRow r = tt_row(t, (uint64_t)blockIdx.x * TT_WG + threadIdx.x, s_contig);
+    const TtRow r = tt_row<CALLS>(t, (uint64_t)blockIdx.x * TT_WG + threadIdx.x, s_contig);
     const unsigned long long rows = __ballot(r.len != 0u), bad = __ballot(r.bad);
     if ((threadIdx.x & 63u) == 0u) { if (rows) atomicAdd(&s_rows, (uint32_t)__popcll(rows)); if (bad) s_bad = 1u; }
     uint32_t total;
@@ -166,19 +202,30 @@ struct TtWin {
     }
 };
 
-__global__ void __launch_bounds__(TT_WG) k_track_rows(GmDevTrack t) {
+template <bool CALLS> __global__ void __launch_bounds__(TT_WG) k_track_rows(GmDevTrack t) {
     __shared__ __attribute__((aligned(16))) char s_txt[TT_WIN];
     __shared__ uint32_t s_wave[TT_WG / 64u];
     __shared__ uint32_t s_contig;
     if (threadIdx.x == 0) s_contig = tt_contig_search(t.contig_off, t.n_seqs, (t.lo + (uint64_t)blockIdx.x * TT_WG) * (uint64_t)t.bin_size);
     __syncthreads();
-    const TtRow r = tt_row(t, (uint64_t)blockIdx.x * TT_WG + threadIdx.x, s_contig);
+    // the ninth column's p-value first, once for all windows, while nothing else is live.  The sizes pass let only values of
+    // gm_put_e2_hd's domain through; should it refuse one all the same, the slab is flagged now and the host formats it after all
+    char e2[8] = { '?', '?', '?', '?', '?', '?', '?', '?' };
+    if (CALLS) {
+        const uint64_t i = (uint64_t)blockIdx.x * TT_WG + threadIdx.x;
+        if (i < t.n && t.cov[t.lo + i] > 0.001f) {
+            const uint64_t count = t.lo + i;
+            if (tt_call_len(t.code[i], (uint32_t)(t.pac[count >> 2] >> ((~count & 3u) << 1)) & 3u) > 2u && gm_put_e2_hd(e2, t.pval[i]) == e2) t.meta[TT_META_HOST] = 1ull;
+        }
+    }
+    const TtRow r = tt_row<CALLS>(t, (uint64_t)blockIdx.x * TT_WG + threadIdx.x, s_contig);
     uint32_t tile_len;
     const uint32_t r0 = tt_block_scan(r.len, s_wave, tile_len);              // where the lane's row starts in the tile's text
     // every store stays inside the range the scan gave this tile, whatever the lengths say
     const unsigned long long T0 = t.tile_off[blockIdx.x], room = t.tile_off[blockIdx.x + 1u] - T0;
     if ((unsigned long long)tile_len > room) tile_len = (uint32_t)room;
-    const bool six = t.kind == GM_TRACK_BASE;
+    const bool six = !CALLS && t.kind == GM_TRACK_BASE;
+    const uint32_t call_len = CALLS && r.len ? tt_call_len(r.call & 0xFFu, r.call >> 8) : 0u;
     for (uint32_t w0 = 0; w0 < tile_len;) {
         const unsigned long long g = T0 + w0;                                // the window's first byte in the output
         const uint32_t a = (uint32_t)(g & 15ull);                            // LDS byte i <-> output byte g - a + i: the same alignment on both sides
@@ -194,7 +241,19 @@ __global__ void __launch_bounds__(TT_WG) k_track_rows(GmDevTrack t) {
             w.digits(at + dp, r.pos, dp); at += dp;
             w.put(at, '\t'); ++at;
             at = w.fixed(at, r.v[0], six);
-            if (t.kind != GM_TRACK_SGR) for (int q = 1; q < 6; ++q) { w.put(at, '\t'); at = w.fixed(at + 1u, r.v[q], false); }
+            if (CALLS || t.kind != GM_TRACK_SGR) for (int q = 1; q < 6; ++q) { w.put(at, '\t'); at = w.fixed(at + 1u, r.v[q], false); }
+            if (CALLS) {                                                     // the host emitter of gm_coverage_write_gmp_calls, byte for byte
+                const uint32_t cd = r.call & 0xFFu, ref = r.call >> 8, p1 = cd & 7u, r2 = (cd >> 3) & 3u;
+                w.put(at, '\t'); w.put(at + 1u, (cd & 0x40u) ? 'Y' : 'N'); at += 2u;
+                if (call_len > 2u) {
+                    w.put(at, ':'); w.put(at + 1u, tt_letter(ref)); w.put(at + 2u, '-'); w.put(at + 3u, '>'); w.put(at + 4u, tt_letter(p1)); at += 5u;
+                    if (call_len == 24u) { w.put(at, '/'); w.put(at + 1u, tt_letter(r2 + (r2 >= p1 ? 1u : 0u))); at += 2u; }
+                    w.put(at, ' '); w.put(at + 1u, 'p'); w.put(at + 2u, '_'); w.put(at + 3u, 'v'); w.put(at + 4u, 'a'); w.put(at + 5u, 'l'); w.put(at + 6u, '='); at += 7u;
+#pragma unroll
+                    for (uint32_t j = 0; j < 8u; ++j) w.put(at + j, e2[j]);
+                    at += 8u;
+                }
+            }
             w.put(at, '\n');
         }
         __syncthreads();
@@ -215,13 +274,29 @@ uint32_t gmk_track_tiles(uint64_t n) { return (uint32_t)((n + TT_WG - 1) / TT_WG
 int gmk_track_sizes(const GmDevTrack& t, void* stream) {
     if (t.n == 0) return 0;
     const uint32_t nt = gmk_track_tiles(t.n);
-    hipLaunchKernelGGL(k_track_sizes, dim3(nt), dim3(TT_WG), 0, S_(stream), t);
+    if (t.kind == GM_TRACK_CALLS) hipLaunchKernelGGL(k_track_sizes<true>, dim3(nt), dim3(TT_WG), 0, S_(stream), t);
+    else hipLaunchKernelGGL(k_track_sizes<false>, dim3(nt), dim3(TT_WG), 0, S_(stream), t);
     hipLaunchKernelGGL(k_track_scan, dim3(1), dim3(1024), 0, S_(stream), t.tile_len, nt, t.tile_off, t.meta);
     return (int)hipGetLastError();
 }
 
 int gmk_track_rows(const GmDevTrack& t, void* stream) {
     if (t.n == 0) return 0;
-    hipLaunchKernelGGL(k_track_rows, dim3(gmk_track_tiles(t.n)), dim3(TT_WG), 0, S_(stream), t);
+    if (t.kind == GM_TRACK_CALLS) hipLaunchKernelGGL(k_track_rows<true>, dim3(gmk_track_tiles(t.n)), dim3(TT_WG), 0, S_(stream), t);
+    else hipLaunchKernelGGL(k_track_rows<false>, dim3(gmk_track_tiles(t.n)), dim3(TT_WG), 0, S_(stream), t);
+    return (int)hipGetLastError();
+}
+
+// gm_put_e2_hd on the device, one lane per value (gm_dev_fmt_e2)
+__global__ void __launch_bounds__(256) k_fmt_e2(const double* v, uint32_t n, char* out, uint8_t* len) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    char* w = out + (size_t)i * 16;
+    len[i] = (uint8_t)(gm_put_e2_hd(w, v[i]) - w);
+}
+
+int gmk_fmt_e2(const double* v, uint32_t n, char* out, uint8_t* len, void* stream) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_fmt_e2, dim3((n + 255u) / 256u), dim3(256), 0, S_(stream), v, n, out, len);
     return (int)hipGetLastError();
 }

@@ -55,6 +55,7 @@ struct Options {
     float snp_pval = 0.001f;    // --snp_pval: gSNP_PVAL inc/const_define.h:33
     bool snp_monop = false, snp_calls = false;      // --snp_monop: gSNP_MONOP; --snp_calls: <out>.gmp with PrintSNPCall's ninth column
     bool sam_text_device = false;   // --sam_text=device: SAM rows formatted on the GPU (gm_output_batch_text); host = format_sam below
+    bool vcf = false;               // --vcf: with --snp, <out>.vcf beside <out>.gmp (gm_coverage_write_vcf)
     bool track_text_device = false; // --track_text=device: <out>.sgr / <out>.gmp formatted on the GPU (gm_coverage_write_*_device); host = the whole tracks come down
     int sam_shards = 1;             // --sam_shards=K: <out>.0.sam .. <out>.<K-1>.sam by input position instead of one <out>.sam
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
@@ -91,13 +92,15 @@ static void usage(int rc, const char* msg) {
             "                               (N, [YN]:r->x p_val=.., [YN]:r->x/y p_val=..); not yet the default of --snp\n"
             "      --snp_pval=DOUBLE        P-Value cutoff for calling SNPs (default: 0.001); changes the ninth column only\n"
             "      --snp_monop              monoploid SNP calling; changes the ninth column only\n"
+            "      --vcf                    with --snp: also write <out>.vcf (VCFv4.0), one row per position the ninth column marks 'Y',\n"
+            "                               under --snp_pval / --snp_monop; <out>.gmp is written exactly as without the flag\n"
             "      --no_nw                  use k-mer hit counts instead of Needleman-Wunsch alignments\n"
             "      --fast, --print_all_sam, --illumina, --up_strand, --down_strand, --bin_size=INT\n"
             "  MI355X options: --gpus=N  --batch=N (blocks of exactly N reads)  --chunk_reads=N  --workers=N  --fmt_threads=N  --locate=sampled|full\n"
             "      --sam_text=host|device   where the SAM rows become text: host formatter threads (default) or the GPU\n"
             "                               (gm_output_batch_text; same bytes, no formatter stage)\n"
-            "      --track_text=host|device where <out>.sgr / the eight-column <out>.gmp become text: host threads over a host copy of the\n"
-            "                               tracks (default) or the GPU (same bytes; only the text crosses the link, no whole-genome host array)\n"
+            "      --track_text=host|device where <out>.sgr / <out>.gmp (eight columns, or nine with --snp_calls) become text: host threads\n"
+            "                               (default) or the GPU (same bytes; only the text crosses the link, no whole-genome host array)\n"
             "      --sam_shards=K           1 .. 64 (default 1 = <out>.sam): write <out>.0.sam .. <out>.<K-1>.sam, a block going to the\n"
             "                               shard of its position in the input, header lines in shard 0 only;\n"
             "                               cat <out>.0.sam .. <out>.<K-1>.sam is the single-file SAM\n");
@@ -141,6 +144,7 @@ static void parse_args(int argc, char** argv, Options& o) {
             }
             else if (!strcmp(s, "snp_monop")) o.snp_monop = true;
             else if (!strcmp(s, "snp_calls")) o.snp_calls = true;
+            else if (!strcmp(s, "vcf")) o.vcf = true;                            // Driver.cpp: gVCF
             else if (!strcmp(s, "fast")) o.p.fast = 1;
             else if (starts(s, "bin_size=")) o.p.bin_size = atoi(s + 9);
             else if (starts(s, "jump=")) o.p.jump = atoi(s + 5);
@@ -215,6 +219,7 @@ static void parse_args(int argc, char** argv, Options& o) {
     if (o.p.mode == GM_MODE_ATOG && !o.p.pos_strand) o.p.mode = GM_MODE_ATOG2;
     if (gm_params_finalize(&o.p) != GM_OK) { fprintf(stderr, "%s\n", gm_last_error()); exit(1); }
     if (!o.subst.empty() && gm_params_load_subst(&o.p, o.subst.c_str()) != GM_OK) { fprintf(stderr, "ERROR: \n\t%s\n", gm_last_error()); exit(1); }
+    if (o.vcf && o.p.mode != GM_MODE_SNP) { fprintf(stderr, "Error: --vcf writes the SNP calls of --snp: give --snp with --vcf\n"); exit(1); }
     if (o.adaptor.size() > 256) { fprintf(stderr, "Error: -A/--adaptor takes at most 256 characters\n"); exit(1); }
     if (o.gpus < 1) o.gpus = 1;
     if (o.batch < 1) o.batch = 1;
@@ -1102,11 +1107,12 @@ int main(int argc, char** argv) {
     auto t_cov0 = std::chrono::steady_clock::now();
     // coverage: all-reduce over the GPUs, then PrintFinalSGR / PrintFinalBisulfite
     if (gm_coverage_allreduce(gpu_ix.data(), o.gpus) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
-    if (o.p.mode == GM_MODE_SNP && o.snp_calls) {                      // PrintFinalSNP with PrintSNPCall's column: the tracks are read where they are, slab by slab
+    if (o.p.mode == GM_MODE_SNP && o.snp_calls && !o.track_text_device) {      // PrintFinalSNP with PrintSNPCall's column: the tracks are read where they are, slab by slab
         if (gm_coverage_write_gmp_calls(gpu_ix[0], o.snp_pval, o.snp_monop, (o.output + ".gmp").c_str(), 0) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
     } else if (o.track_text_device) {                                  // GPU 0 formats the rows where the tracks are: no host copy of a track
         const int rc = o.p.mode == GM_MODE_NORMAL ? gm_coverage_write_sgr_device(gpu_ix[0], (o.output + ".sgr").c_str(), 0)
-                                                  : gm_coverage_write_gmp_device(gpu_ix[0], &o.p, (o.output + ".gmp").c_str(), 0);
+                       : o.p.mode == GM_MODE_SNP && o.snp_calls ? gm_coverage_write_gmp_calls_device(gpu_ix[0], o.snp_pval, o.snp_monop, (o.output + ".gmp").c_str(), 0)
+                                                                : gm_coverage_write_gmp_device(gpu_ix[0], &o.p, (o.output + ".gmp").c_str(), 0);
         if (rc != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
         gm_track_text_stats ts;
         if (o.verbose > 0 && gm_coverage_text_stats(gpu_ix[0], &ts) == GM_OK)
@@ -1126,6 +1132,8 @@ int main(int argc, char** argv) {
             }
         }
     }
+    // Genome::PrintFinalVCF src/Genome.cpp:1142-1245 beside the .gmp (the reference's compiled GenomeBwt accepts --vcf and writes no file)
+    if (o.vcf && gm_coverage_write_vcf(gpu_ix[0], o.snp_pval, o.snp_monop, (o.output + ".vcf").c_str(), 0) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
     uint64_t n_reads = 0, n_matched = 0, n_records = 0;
     double t_pack = 0, t_map = 0, t_out = 0;
     for (auto& w : workers) {

@@ -334,6 +334,9 @@ int gm_dev_adaptor_trim(gm_index*, const gm_reads*, const char* adaptor, uint16_
 /* printf("%g") as the device prints XA / XP (gm_fmt_dev.h): out[16 i ..] holds len[i] characters, no terminator; len[i] = 0 for a
  * value outside the function's domain (0, -0, inf, nan, 2^-200 <= |v| < 2^200) */
 int gm_dev_fmt_g6(gm_index*, const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len);
+/* printf("%.2e") as the device prints the p-value of --snp's ninth .gmp column (gm_put_e2_hd), same contract: always 8 characters
+ * on its domain (+0.0, 2^-200 <= v < 2^200), len[i] = 0 outside it (negative, -0.0, nan, inf, anything else) */
+int gm_dev_fmt_e2(gm_index*, const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len);
 
 /* bin_seq::pairHMM (src/bin_seq.cpp:60-244) of read read_idx[k] in the orientation of strand[k] against the window at pos[k]:
  * out[k][max_len][5] floats (a, c, g, t, n per window position), max_len = gm_reads.stride */
@@ -400,8 +403,26 @@ int gm_coverage_write_gmp_device(gm_index*, const gm_params*, const char* path, 
  * past the last one the files print have no row).  *n_out = the bytes needed; GM_E_CAPACITY when that exceeds cap, text[0, cap)
  * then holds the first cap bytes (the protocol of gm_snp_calls) */
 int gm_coverage_text(gm_index*, const gm_params* p, uint64_t bin_lo, uint64_t bin_hi, char* text, uint64_t cap, uint64_t* n_out);
-/* of the last of the three calls above on this index: kernel_ms is the device time of the launches (hipEvent), launches their number */
+/* the file of gm_coverage_write_gmp_calls (nine columns), byte for byte, formatted on the device: per slab k_snp_call writes the code
+ * byte and the p-value of every position into HBM, then the track text kernels' calls variant prints the rows with the ninth column,
+ * the p-value with an exact "%.2e" (gm_put_e2_hd).  A slab with a printed count outside [0, 1e9) or a printed p-value outside that
+ * function's domain is formatted by the host emitter.  gm_coverage_calls_text: the rows of the positions [bin_lo, bin_hi), protocol
+ * and argument errors of gm_coverage_text.  Both need bin size 1 and gm_coverage_enable_nuc like gm_snp_calls (GM_E_ARG otherwise). */
+int gm_coverage_write_gmp_calls_device(gm_index*, float snp_pval, int monop, const char* path, int append);
+int gm_coverage_calls_text(gm_index*, float snp_pval, int monop, uint64_t bin_lo, uint64_t bin_hi, char* text, uint64_t cap, uint64_t* n_out);
+/* of the last of the five calls above on this index: kernel_ms is the device time of the launches (hipEvent), launches their number
+ * (four per slab with the ninth column: k_snp_call, sizes, scan, rows) */
 int gm_coverage_text_stats(gm_index*, gm_track_text_stats*);
+
+/* ---- <out>.vcf (--vcf): Genome::PrintFinalVCF src/Genome.cpp:1142-1245 over the records of gm_snp_calls ----
+ * Header, unless appending: ##fileformat=VCFv4.0, ##fileDate=YYYYMMDD (local date), ##source=<gm_version()>, the #CHROM line.  One row
+ * per record in ascending position, IDs snp0, snp1, ... counting the rows of this call, letters acgtn:
+ *   contig \t pos \t snpN \t ref \t xy \t . \t . \t Diploid;pval=%.5f;coverage=%.5f;ratio=%.2f      ratio = nuc[y] / nuc[x] in float
+ *   contig \t pos \t snpN \t ref \t x  \t . \t . \t Monoploid;pval=%.5f;coverage=%.5f
+ * Formatted on the host (the rows are sparse): a count pass, then the records of one stretch of positions at a time.  Two departures:
+ * the date is one well-formed line (the reference prints ctime()'s text with its newline), and a row needs a total above 0.001 like
+ * the .gmp's 'Y' rows, not above 0, so both files name the same positions.  Needs bin size 1 and gm_coverage_enable_nuc. */
+int gm_coverage_write_vcf(gm_index*, float snp_pval, int monop, const char* path, int append);
 
 #ifdef __cplusplus
 }

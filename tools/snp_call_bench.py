@@ -4,6 +4,8 @@ filled on the device (about --depth x coverage at every position, 0.5 % errors, 
 
   * three runs each of the eight-column path (gm_coverage_download + gm_coverage_download_nuc + gm_coverage_write_gmp) and of
     gm_coverage_write_gmp_calls on the same tracks: wall seconds, bytes written;
+  * the same number of runs of gm_coverage_write_gmp_calls_device (the nine-column file formatted on the device), alternating with the
+    host writer: wall seconds, kernel_ms of gm_coverage_text_stats, and whether the two files are the same bytes;
   * gm_snp_calls: wall seconds, records.
 
     python3 tools/snp_call_bench.py --mbp 25
@@ -23,6 +25,18 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def same_file(a, b, piece=64 << 20):
+    if os.path.getsize(a) != os.path.getsize(b):
+        return False
+    with open(a, "rb") as fa, open(b, "rb") as fb:
+        while True:
+            x = fa.read(piece)
+            if x != fb.read(piece):
+                return False
+            if not x:
+                return True
 
 
 def main():
@@ -69,7 +83,8 @@ def main():
     if not a.calls_only:
         p5 = g.Params(mode=5)
         out = os.path.join(work, "t.gmp")
-        eight, nine = [], []
+        eight, nine, nine_dev, nine_dev_kernel_ms = [], [], [], []
+        out_dev = os.path.join(work, "t_dev.gmp")
         for _ in range(a.runs):
             t0 = time.time()
             h_cov = ix.coverage_download(); h_nuc = ix.coverage_download_nuc()
@@ -79,7 +94,13 @@ def main():
             t0 = time.time()
             ix.coverage_write_gmp_calls(out)
             nine.append(round(time.time() - t0, 3)); res["nine_column_bytes"] = os.path.getsize(out)
-        os.remove(out)
+            t0 = time.time()
+            ix.coverage_write_gmp_calls_device(out_dev)
+            nine_dev.append(round(time.time() - t0, 3)); st = ix.coverage_text_stats()
+            nine_dev_kernel_ms.append(round(st["kernel_ms"], 3)); res["nine_column_device_stats"] = {k: st[k] for k in ("rows", "bytes", "slabs", "host_slabs", "launches")}
+        res["nine_column_device_same_bytes"] = same_file(out, out_dev)
+        os.remove(out); os.remove(out_dev)
+        res["nine_column_write_gmp_calls_device_s"] = nine_dev; res["nine_column_device_kernel_ms"] = nine_dev_kernel_ms
         res["eight_column_download_and_write_s"] = eight; res["nine_column_write_gmp_calls_s"] = nine
     ix.close()
     for f in os.listdir(work):
