@@ -1839,6 +1839,7 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
         const uint32_t chunk = (uint32_t)std::min<long long>(std::max<long long>(64, gm_opt_ll("GM_SNP_CHUNK", 16384)), n_m) / 64u * 64u + 64u;
         const size_t cells = gmk_pair_hmm_cells(Lmax);
         if (b->snp_scratch.ensure((size_t)((chunk + 63) / 64) * cells * 8) || b->snp_hmm.ensure((size_t)chunk * Lmax * 5 * 4)) return GM_E_NOMEM;
+        GM_TRACE("snp deposit: %u kept sequences, chunks of %u: %u chunk%s", n_m, chunk, (n_m + chunk - 1) / chunk, (n_m + chunk - 1) / chunk == 1 ? "" : "s");
         for (uint32_t m0 = 0; m0 < n_m; m0 += chunk) {
             const uint32_t cnt = std::min<uint32_t>(chunk, n_m - m0);
             KCHK(gmk_pair_hmm(ix->dev, dp, b->dev, b->tb_items.as<GmCand>() + m0, cnt, b->snp_scratch.as<double>(), Lmax, b->snp_hmm.as<float>(), st));
