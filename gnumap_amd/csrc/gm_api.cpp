@@ -3,23 +3,17 @@
 // (unique-sequence map, denominator, posterior, MAPQ: src/Driver.cpp:432-753, inc/align_seq2_raw.cpp:102-165,
 // inc/ScoredSeq.h:293-404).  There is NO CPU fallback for the device work: without a usable gfx950 device every
 // compute entry point fails with GM_E_NO_DEVICE.
-#include "gm_host.h"
+#include "gm_lib.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <ctime>
 #include <chrono>
-#include <map>
-#include <memory>
-#include <mutex>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
 #include <functional>
-#include <set>
 #include <thread>
-#include <fcntl.h>
 #include <unistd.h>
 
 static thread_local std::string g_err;
@@ -47,84 +41,6 @@ static double gm_trace_ms() { static const auto t0 = std::chrono::steady_clock::
 void gm_set_error(const std::string& s) { g_err = s; }
 extern "C" const char* gm_last_error(void) { return g_err.c_str(); }
 extern "C" const char* gm_version(void) { return "gnumap-mi355x 0.2 (gfx950)"; }
-
-#define HIPCHK(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess) {                                                                               \
-            gm_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                                  \
-            return GM_E_HIP;                                                                                  \
-        }                                                                                                     \
-    } while (0)
-#define KCHK(expr)                                                                                            \
-    do {                                                                                                      \
-        int e_ = (expr);                                                                                      \
-        if (e_ != 0) {                                                                                        \
-            gm_set_error(std::string(#expr) + ": " + hipGetErrorString((hipError_t)e_));                      \
-            return GM_E_HIP;                                                                                  \
-        }                                                                                                     \
-    } while (0)
-
-namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return GM_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { gm_set_error(std::string("hipMalloc: ") + hipGetErrorString(e)); p = nullptr; return GM_E_NOMEM; }
-        cap = want;
-        return GM_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-struct PinBuf {                              // page-locked host staging: device <-> host copies at link rate, no zero fill
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return GM_OK;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) { gm_set_error(std::string("hipHostMalloc: ") + hipGetErrorString(e)); p = nullptr; return GM_E_NOMEM; }
-        cap = want;
-        return GM_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-}  // namespace
-
-struct gm_index {
-    GmHostIndex h;
-    int device = -1;
-    bool host_only = false;
-    bool full_sa = false;
-    DevBuf d_bwt, d_sa, d_full, d_pac, d_contig, d_cov, d_ptab, d_planes, d_nuc;
-    DevBuf d_cnames, d_cname_off;           // contig names back to back + n_seqs + 1 offsets: what k_out_text_rows prints (uploaded by the first gm_output_batch_text)
-    bool cnames_on = false;
-    bool nuc_on = false;
-    GmDevIndex dev{};
-    uint64_t cov_bins = 0;
-    uint32_t cov_bin_size = 0;
-    // parameter tables resident in HBM: S256 (256x4 floats) + lut (512 float2)
-    std::map<std::vector<float>, DevBuf> ptabs;   // by content
-    std::map<int, DevBuf> kmer_tabs;        // memoised backward search of the last T characters of a seed, per T
-    std::map<int, DevBuf> kmer_ctabs;       // its compact form (16 B per 8 codes), per T
-    std::map<int, DevBuf> buckets;          // k-mer -> positions records (128 B per code; gm_bucket.hip), per T; empty DevBuf = tried, no room
-    std::mutex mu;
-    uint64_t hbm_bytes = 0;
-    int probe_format = GM_READS_FASTQ;      // gm_index_set_probe_format: how the unit probes read their gm_reads
-    gm_track_text_stats tt_stats{};         // of the last gm_coverage_write_*_device / gm_coverage_text / gm_coverage_calls_text
-};
 
 struct gm_batch {
     gm_index* ix = nullptr;
@@ -558,7 +474,7 @@ extern "C" uint64_t gm_index_contig_offset(const gm_index* ix, uint32_t i) {
 }
 
 // contig names back to back + n_seqs + 1 offsets in HBM, once per index: what k_out_text_rows and k_track_rows print
-static int index_cnames(gm_index* ix) {
+int index_cnames(gm_index* ix) {
     std::lock_guard<std::mutex> lk(ix->mu);
     if (ix->cnames_on) return GM_OK;
     const uint32_t n_seqs = (uint32_t)ix->h.contigs.size();
@@ -572,7 +488,7 @@ static int index_cnames(gm_index* ix) {
     return GM_OK;
 }
 
-static uint32_t host_pos2rid(const GmHostIndex& h, uint64_t pos) {      // bns_pos2rid src/bntseq.c:349-363
+uint32_t host_pos2rid(const GmHostIndex& h, uint64_t pos) {      // bns_pos2rid src/bntseq.c:349-363
     uint32_t lo = 0, hi = (uint32_t)h.contigs.size() - 1;
     while (lo < hi) {
         uint32_t mid = (lo + hi + 1) >> 1;
@@ -1341,7 +1257,7 @@ extern "C" int gm_batch_raw_hits(gm_batch* b, gm_raw_hit* out, uint64_t cap, uin
 
 // host-side bookkeeping that is independent per item: cut into contiguous chunks, one host thread each (GM_HOST_THREADS; used by
 // the track writers: threads made per call) ...
-static unsigned host_threads() {
+unsigned host_threads() {
     static const unsigned n = [] {
         const char* e = getenv("GM_HOST_THREADS");               // sizes thread pools once per process
         unsigned v = e ? (unsigned)atoi(e) : std::min(16u, std::thread::hardware_concurrency());
@@ -2123,637 +2039,5 @@ extern "C" int gm_dev_pair_hmm(gm_index* ix, const gm_params* p, const gm_reads*
     } while (0);
     gm_batch_destroy(b);
     if (rc) { gm_set_error("gm_dev_pair_hmm: HIP failure"); return rc; }
-    return GM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// coverage track
-// ------------------------------------------------------------------------------------------------
-extern "C" int gm_coverage_reset(gm_index* ix, uint32_t bin_size) {
-    if (!ix || bin_size == 0) return GM_E_ARG;
-    if (ix->host_only) {                                // no track in HBM: only the geometry the text writers need (CPU-side tests of gm_coverage_write_*)
-        ix->cov_bins = ix->h.l_pac / bin_size + 64; ix->cov_bin_size = bin_size;
-        return GM_OK;
-    }
-    HIPCHK(hipSetDevice(ix->device));
-    uint64_t bins = ix->h.l_pac / bin_size + 64;        // the reference allocates l_pac/gGEN_SIZE floats and writes a little past it
-    if (ix->d_cov.ensure(bins * 4)) return GM_E_NOMEM;
-    HIPCHK(hipMemset(ix->d_cov.p, 0, bins * 4));
-    ix->cov_bins = bins; ix->cov_bin_size = bin_size;
-    return GM_OK;
-}
-
-extern "C" uint64_t gm_coverage_bins(const gm_index* ix) { return ix ? ix->cov_bins : 0; }
-extern "C" void* gm_coverage_device_ptr(gm_index* ix) { return ix ? ix->d_cov.p : nullptr; }
-
-extern "C" int gm_coverage_add(gm_index* ix, const uint64_t* pos, const uint32_t* span, const float* w, uint32_t n, void* stream) {
-    if (!ix || !pos || !span || !w) return GM_E_ARG;
-    if (!ix->cov_bins) { gm_set_error("coverage track not initialised (gm_coverage_reset)"); return GM_E_ARG; }
-    HIPCHK(hipSetDevice(ix->device));
-    if (n == 0) return GM_OK;
-    DevBuf dp_, ds_, dw_;
-    if (dp_.ensure((size_t)n * 8) || ds_.ensure((size_t)n * 4) || dw_.ensure((size_t)n * 4)) return GM_E_NOMEM;
-    uint32_t max_span = 0;
-    for (uint32_t i = 0; i < n; ++i) max_span = std::max(max_span, span[i]);
-    int rc = GM_OK;
-    hipStream_t st = S_(stream);
-    do {
-        if (hipMemcpyAsync(dp_.p, pos, (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess) { rc = GM_E_HIP; break; }
-        if (hipMemcpyAsync(ds_.p, span, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = GM_E_HIP; break; }
-        if (hipMemcpyAsync(dw_.p, w, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = GM_E_HIP; break; }
-        if (gmk_coverage_add(ix->d_cov.as<float>(), ix->cov_bins, ix->cov_bin_size, dp_.as<uint64_t>(), ds_.as<uint32_t>(), dw_.as<float>(), n, max_span, nullptr, nullptr, nullptr, st)) { rc = GM_E_HIP; break; }
-        if (hipStreamSynchronize(st) != hipSuccess) { rc = GM_E_HIP; break; }
-    } while (0);
-    dp_.release(); ds_.release(); dw_.release();
-    if (rc) gm_set_error("gm_coverage_add: HIP failure");
-    return rc;
-}
-
-extern "C" int gm_coverage_download(gm_index* ix, float* host) {
-    if (!ix || !host || !ix->cov_bins) return GM_E_ARG;
-    HIPCHK(hipSetDevice(ix->device));
-    HIPCHK(hipMemcpy(host, ix->d_cov.p, ix->cov_bins * 4, hipMemcpyDeviceToHost));
-    return GM_OK;
-}
-
-enum { MAX_SGR_LINE = 1200 };
-
-// ---- track text at memory speed ------------------------------------------------------------------------------------------------------
-// printf("%.Nf") of a float bin, N = 5 or 6, without printf: a float has 24 significant bits, so value x 10^N is exact in a double for
-// every value below 2^53 / 10^N x 2^-17 (far beyond any coverage), and rint() of an exact number in the default rounding mode is the
-// correctly rounded decimal glibc's printf prints (ties to even included).  Larger or non-finite values take snprintf.
-static inline char* put_fixed(char* w, float v, int decimals) {
-    const double scale = decimals == 5 ? 100000.0 : 1000000.0;
-    if (!(v >= 0.0f) || !(v < 1.0e9f)) return w + snprintf(w, 64, decimals == 5 ? "%.5f" : "%f", v);
-    const uint64_t q = (uint64_t)rint((double)v * scale);
-    const uint64_t ip = q / (uint64_t)scale; uint32_t fp = (uint32_t)(q % (uint64_t)scale);
-    char tmp[24]; int k = 0;
-    uint64_t t = ip;
-    do { tmp[k++] = (char)('0' + t % 10); t /= 10; } while (t);
-    while (k) *w++ = tmp[--k];
-    *w++ = '.';
-    for (int d = decimals - 1; d >= 0; --d) { w[d] = (char)('0' + fp % 10); fp /= 10; }
-    return w + decimals;
-}
-static inline char* put_long(char* w, long v) {
-    if (v < 0) { *w++ = '-'; v = -v; }
-    char tmp[24]; int k = 0;
-    do { tmp[k++] = (char)('0' + v % 10); v /= 10; } while (v);
-    while (k) *w++ = tmp[--k];
-    return w;
-}
-
-// bins [0, nb) in slabs: host_threads() threads format one slice of a slab each (emit(k, w) appends the line of bin k, if it has
-// one), the pieces are written with pwrite() at their offsets by the same threads
-// slab(lo, hi) runs once before the bins [lo, hi) of a slab are formatted (a writer that fetches its slab from HBM there); non-zero ends the file
-template <class Emit, class Slab> static int write_track_text(const char* path, int append, uint64_t nb, size_t max_line, Emit&& emit, Slab&& slab) {
-    // no O_APPEND: on Linux pwrite() on an O_APPEND descriptor ignores its offset, and the slices below are written concurrently
-    const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
-    if (fd < 0) { gm_set_error(std::string("cannot write ") + path); return GM_E_IO; }
-    uint64_t file_off = append ? (uint64_t)lseek(fd, 0, SEEK_END) : 0;
-    const unsigned T = host_threads();
-    const uint64_t per = (uint64_t)std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 20));      // bins per slice (the option: tests with several slices on a small index)
-    std::vector<std::vector<char>> buf(T);
-    std::vector<size_t> used(T);
-    std::atomic<int> bad{ 0 };
-    for (uint64_t s0 = 0; s0 < nb && !bad; s0 += per * T) {
-        const unsigned parts = (unsigned)std::min<uint64_t>(T, (nb - s0 + per - 1) / per);
-        if (const int rc = slab(s0, std::min<uint64_t>(nb, s0 + per * T))) { ::close(fd); return rc; }
-        auto format = [&](unsigned c) {
-            const uint64_t lo = s0 + c * per, hi = std::min<uint64_t>(nb, lo + per);
-            std::vector<char>& o = buf[c];
-            if (o.size() < (size_t)(hi - lo) * max_line) o.resize((size_t)(hi - lo) * max_line);
-            char* w = o.data();
-            for (uint64_t k = lo; k < hi; ++k) w = emit(k, w, c, k == lo);
-            used[c] = (size_t)(w - o.data());
-        };
-        {
-            std::vector<std::thread> th;
-            for (unsigned c = 1; c < parts; ++c) th.emplace_back(format, c);
-            format(0);
-            for (auto& x : th) x.join();
-        }
-        std::vector<uint64_t> off(parts);
-        for (unsigned c = 0; c < parts; ++c) { off[c] = file_off; file_off += used[c]; }
-        auto put = [&](unsigned c) {
-            const char* q = buf[c].data(); size_t n = used[c]; uint64_t at = off[c];
-            while (n) { const ssize_t k = ::pwrite(fd, q, n, (off_t)at); if (k <= 0) { bad = 1; return; } q += k; n -= (size_t)k; at += (uint64_t)k; }
-        };
-        {
-            std::vector<std::thread> th;
-            for (unsigned c = 1; c < parts; ++c) th.emplace_back(put, c);
-            put(0);
-            for (auto& x : th) x.join();
-        }
-    }
-    ::close(fd);
-    if (bad) { gm_set_error(std::string("write failed: ") + path); return GM_E_IO; }
-    return GM_OK;
-}
-
-template <class Emit> static int write_track_text(const char* path, int append, uint64_t nb, size_t max_line, Emit&& emit) {
-    return write_track_text(path, append, nb, max_line, emit, [](uint64_t, uint64_t) { return 0; });
-}
-
-// one row of a track file: the emitter of every writer below.  bins[k - base] is bin k, nuc[q * nuc_stride + k - base] its sum q (a writer
-// that holds one slab of the tracks passes the slab's first bin as base); i = the caller's contig cursor, looked up at the first bin of a run
-struct TrackEmit {
-    const GmHostIndex& h; uint64_t bs; int kind; char want;               // kind: GM_TRACK_*; want: the reference base of GM_TRACK_BASE
-    const float* bins; const float* nuc; uint64_t nuc_stride, base;
-    char* operator()(uint64_t k, char* w, int& i, bool first) const {
-        // the reference walks `count` over the concatenated coordinate in steps of bin_size without resetting it per contig,
-        // so bin k is printed under the contig that holds k * bin_size
-        const uint64_t count = k * bs;
-        if (first) i = (int)host_pos2rid(h, count);
-        while ((size_t)i + 1 < h.contigs.size() && count >= h.contigs[(size_t)i + 1].offset) ++i;
-        const float total = bins[k - base];
-        if (kind == GM_TRACK_SGR) { if (!((double)total > 0.001)) return w; }       // MIN_PRINT, GenomeBwt.cpp:928
-        else if (kind == GM_TRACK_SNP) { if (!(total > 0.001f)) return w; }
-        else {
-            const char at = "acgt"[(h.pac[count >> 2] >> ((~count & 3) << 1)) & 3];
-            if (at != want || !(total > 0.0f)) return w;
-        }
-        const GmContig& cg = h.contigs[(size_t)i];
-        memcpy(w, cg.name.data(), cg.name.size()); w += cg.name.size();
-        *w++ = '\t'; w = put_long(w, (long)(count - cg.offset) + 1); *w++ = '\t';
-        w = put_fixed(w, total, kind == GM_TRACK_BASE ? 6 : 5);                     // "%f" of the total in the base-filtered .gmp
-        if (kind != GM_TRACK_SGR) for (int q = 0; q < 5; ++q) { *w++ = '\t'; w = put_fixed(w, nuc[(uint64_t)q * nuc_stride + k - base], 5); }
-        *w++ = '\n';
-        return w;
-    }
-};
-static size_t max_contig_name(const GmHostIndex& h) {
-    size_t m = 0;
-    for (const auto& c : h.contigs) m = std::max(m, c.name.size());
-    return m;
-}
-static char gmp_want(int mode) { return mode == GM_MODE_BS ? 'c' : mode == GM_MODE_BS2 ? 'g' : mode == GM_MODE_ATOG ? 'a' : 't'; }
-
-extern "C" int gm_coverage_write_sgr(gm_index* ix, const float* bins, const char* path, int append) {
-    // GenomeBwt::PrintFinalSGR src/GenomeBwt.cpp:1212-1273: bins run over the CONCATENATED coordinate
-    if (!ix || !bins || !path || !ix->cov_bin_size) return GM_E_ARG;
-    const GmHostIndex& h = ix->h;
-    const uint64_t bs = ix->cov_bin_size;
-    const uint64_t nb = (h.l_pac + bs - 1) / bs;
-    std::vector<int> cur(host_threads(), 0);
-    const TrackEmit e{ h, bs, GM_TRACK_SGR, 0, bins, nullptr, 0, 0 };
-    return write_track_text(path, append, nb, max_contig_name(h) + 48, [&](uint64_t k, char* w, unsigned c, bool first) -> char* { return e(k, w, cur[c], first); });
-}
-
-extern "C" int gm_coverage_enable_nuc(gm_index* ix) {
-    if (!ix || !ix->cov_bins) { gm_set_error("gm_coverage_reset first"); return GM_E_ARG; }
-    HIPCHK(hipSetDevice(ix->device));
-    if (ix->d_nuc.ensure(5 * ix->cov_bins * 4)) return GM_E_NOMEM;
-    HIPCHK(hipMemset(ix->d_nuc.p, 0, 5 * ix->cov_bins * 4));
-    ix->nuc_on = true;
-    return GM_OK;
-}
-
-extern "C" void* gm_coverage_nuc_device_ptr(gm_index* ix) { return ix && ix->nuc_on ? ix->d_nuc.p : nullptr; }
-
-extern "C" int gm_coverage_download_nuc(gm_index* ix, float* host) {
-    if (!ix || !host || !ix->nuc_on) return GM_E_ARG;
-    HIPCHK(hipSetDevice(ix->device));
-    HIPCHK(hipMemcpy(host, ix->d_nuc.p, 5 * ix->cov_bins * 4, hipMemcpyDeviceToHost));
-    return GM_OK;
-}
-
-extern "C" int gm_coverage_write_gmp(gm_index* ix, const gm_params* p, const float* bins, const float* nuc, const char* path, int append) {
-    // GenomeBwt::PrintFinalBisulfite src/GenomeBwt.cpp:1092-1210
-    if (!ix || !p || !bins || !nuc || !path || !ix->cov_bin_size || p->mode == GM_MODE_NORMAL) return GM_E_ARG;
-    const GmHostIndex& h = ix->h;
-    const uint64_t bs = ix->cov_bin_size, nb = ix->cov_bins;
-    const uint64_t nbk = (h.l_pac + bs - 1) / bs;
-    std::vector<int> cur(host_threads(), 0);
-    // GM_MODE_SNP: GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1090 up to the per-nucleotide columns: every position whose total is above MIN_PRINT,
-    // "%.5f" for all six numbers.  The line ends here; gm_coverage_write_gmp_calls writes the same rows with PrintSNPCall's column behind them.
-    const TrackEmit e{ h, bs, p->mode == GM_MODE_SNP ? GM_TRACK_SNP : GM_TRACK_BASE, gmp_want(p->mode), bins, nuc, nb, 0 };
-    return write_track_text(path, append, nbk, max_contig_name(h) + 160, [&](uint64_t k, char* w, unsigned c, bool first) -> char* { return e(k, w, cur[c], first); });
-}
-
-// ------------------------------------------------------------------------------------------------
-// --snp: the likelihood-ratio column (gm_snpcall.hip)
-// ------------------------------------------------------------------------------------------------
-static_assert(sizeof(gm_snp_rec) == sizeof(GmDevSnpRec) && sizeof(gm_snp_rec) == 64 && offsetof(gm_snp_rec, chr_pos) == offsetof(GmDevSnpRec, chr_pos) &&
-              offsetof(gm_snp_rec, total) == offsetof(GmDevSnpRec, total) && offsetof(gm_snp_rec, nuc) == offsetof(GmDevSnpRec, nuc) &&
-              offsetof(gm_snp_rec, p_val) == offsetof(GmDevSnpRec, p_val) && offsetof(gm_snp_rec, ref) == offsetof(GmDevSnpRec, ref) &&
-              offsetof(gm_snp_rec, diploid) == offsetof(GmDevSnpRec, diploid), "gm_snp_rec layout");
-
-namespace {
-template <class B> struct Scoped : B { ~Scoped() { this->release(); } };       // a DevBuf / PinBuf that lives as long as one call
-
-// what the three entry points below ask of the tracks: bin size 1 (Driver.cpp:3207-3211 forces it with --snp), the five sums enabled
-int snp_tracks_ready(gm_index* ix) {
-    if (!ix->cov_bins || ix->cov_bin_size != 1) { gm_set_error("SNP calls need the coverage track with bin size 1 (gm_coverage_reset(ix, 1))"); return GM_E_ARG; }
-    if (!ix->host_only && !ix->nuc_on) { gm_set_error("SNP calls read the per-nucleotide tracks: call gm_coverage_enable_nuc first"); return GM_E_ARG; }
-    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    return GM_OK;
-}
-}  // namespace
-
-// the 'Y' rows of the positions [p_lo, p_hi) (clamped to the reference): gm_snp_calls is the whole range, gm_coverage_write_vcf fetches in pieces
-static int snp_calls_range(gm_index* ix, float snp_pval, int monop, uint64_t p_lo, uint64_t p_hi, gm_snp_rec* out, uint64_t cap, uint64_t* n_out, void* stream) {
-    HIPCHK(hipSetDevice(ix->device));
-    hipStream_t st = S_(stream);
-    const uint64_t l_pac = std::min<uint64_t>(ix->h.l_pac, p_hi), bins = ix->cov_bins;
-    const uint64_t per = (uint64_t)std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 20)) * 16;       // positions per launch
-    const uint32_t groups = gmk_snp_call_groups(std::min(per, l_pac));
-    Scoped<DevBuf> d_code, d_pval, d_cnt, d_off, d_out;
-    if (d_code.ensure(per) || d_pval.ensure(per * 8) || d_cnt.ensure((size_t)groups * 4 + 4) || d_off.ensure(((size_t)groups + 1) * 8) ||
-        d_out.ensure((size_t)std::max<uint64_t>(cap, 1) * sizeof(GmDevSnpRec))) return GM_E_NOMEM;
-    unsigned long long total = 0;
-    for (uint64_t lo = p_lo; lo < l_pac; lo += per) {
-        const uint64_t n = std::min(per, l_pac - lo);
-        KCHK(gmk_snp_call(ix->d_cov.as<float>(), ix->d_nuc.as<float>(), bins, ix->dev, lo, n, snp_pval, monop ? 1 : 0, d_code.as<uint8_t>(), d_pval.as<double>(),
-                          d_cnt.as<uint32_t>(), st));
-        KCHK(gmk_snp_gather(ix->d_cov.as<float>(), ix->d_nuc.as<float>(), bins, ix->dev, lo, n, d_code.as<uint8_t>(), d_pval.as<double>(), d_cnt.as<uint32_t>(),
-                            d_off.as<unsigned long long>(), total, cap, d_out.as<GmDevSnpRec>(), st));
-        unsigned long long got = 0;
-        HIPCHK(hipMemcpyAsync(&got, d_off.as<unsigned long long>() + gmk_snp_call_groups(n), 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        total += got;
-    }
-    const uint64_t have = std::min<uint64_t>(total, cap);
-    if (have) HIPCHK(hipMemcpy(out, d_out.p, (size_t)have * sizeof(gm_snp_rec), hipMemcpyDeviceToHost));
-    *n_out = total;
-    if (total > cap) { gm_set_error("gm_snp_calls: out[] too small"); return GM_E_CAPACITY; }
-    return GM_OK;
-}
-
-extern "C" int gm_snp_calls(gm_index* ix, float snp_pval, int monop, gm_snp_rec* out, uint64_t cap, uint64_t* n_out, void* stream) {
-    if (!ix || !n_out || (cap && !out)) return GM_E_ARG;
-    if (const int rc = snp_tracks_ready(ix)) return rc;
-    return snp_calls_range(ix, snp_pval, monop, 0, ~0ull, out, cap, n_out, stream);
-}
-
-extern "C" int gm_dev_snp_stat(gm_index* ix, const float* counts, uint32_t n, int monop, double* p_val, int8_t* pos1, int8_t* pos2, uint8_t* dip) {
-    if (!ix || !counts || !p_val || !pos1 || !pos2 || !dip) return GM_E_ARG;
-    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    if (n == 0) return GM_OK;
-    HIPCHK(hipSetDevice(ix->device));
-    Scoped<DevBuf> d_in, d_p, d_1, d_2, d_d;
-    if (d_in.ensure((size_t)n * 20) || d_p.ensure((size_t)n * 8) || d_1.ensure(n) || d_2.ensure(n) || d_d.ensure(n)) return GM_E_NOMEM;
-    HIPCHK(hipMemcpy(d_in.p, counts, (size_t)n * 20, hipMemcpyHostToDevice));
-    KCHK(gmk_snp_stat(d_in.as<float>(), n, monop ? 1 : 0, d_p.as<double>(), d_1.as<int8_t>(), d_2.as<int8_t>(), d_d.as<uint8_t>(), nullptr));
-    HIPCHK(hipMemcpy(p_val, d_p.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(pos1, d_1.p, n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(pos2, d_2.p, n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(dip, d_d.p, n, hipMemcpyDeviceToHost));
-    return GM_OK;
-}
-
-namespace {
-// one row of the nine-column .gmp: GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1009 with PrintSNPCall's column (:1011-1090) from k_snp_call's
-// code byte.  The caller holds one slab of n positions from `base` on: f[q * n + count - base] = the total (q = 0) and the five sums,
-// code / pval the same positions' calls; i = the caller's contig cursor, looked up at the first position of a run
-struct CallsEmit {
-    const GmHostIndex& h; const float* f; const uint8_t* code; const double* pval; uint64_t base, n;
-    char* operator()(uint64_t count, char* w, int& i, bool first) const {
-        if (first) i = (int)host_pos2rid(h, count);
-        while ((size_t)i + 1 < h.contigs.size() && count >= h.contigs[(size_t)i + 1].offset) ++i;
-        const uint64_t k = count - base;
-        if (!(f[k] > 0.001f)) return w;
-        const GmContig& cg = h.contigs[(size_t)i];
-        memcpy(w, cg.name.data(), cg.name.size()); w += cg.name.size();
-        *w++ = '\t'; w = put_long(w, (long)(count - cg.offset) + 1); *w++ = '\t';
-        w = put_fixed(w, f[k], 5);
-        for (uint64_t q = 1; q <= 5; ++q) { *w++ = '\t'; w = put_fixed(w, f[q * n + k], 5); }
-        const unsigned cd = code[k];
-        const unsigned at = (h.pac[count >> 2] >> ((~count & 3) << 1)) & 3, p1 = cd & 7u, dip = (cd >> 5) & 1u, r2 = (cd >> 3) & 3u;
-        *w++ = '\t'; *w++ = (cd & 0x40) ? 'Y' : 'N';
-        if (p1 != at || dip) {                                                // :1065-1085
-            *w++ = ':'; *w++ = "acgt"[at]; *w++ = '-'; *w++ = '>'; *w++ = "acgtn"[p1];
-            if (dip) { *w++ = '/'; *w++ = "acgtn"[r2 + (r2 >= p1 ? 1u : 0u)]; }
-            w += snprintf(w, 40, " p_val=%.2e", pval[k]);
-        }
-        *w++ = '\n';
-        return w;
-    }
-};
-}  // namespace
-
-extern "C" int gm_coverage_write_gmp_calls(gm_index* ix, float snp_pval, int monop, const char* path, int append) {
-    // GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1009 with PrintSNPCall's column (:1011-1090).  A slab of the six tracks comes down from
-    // HBM together with k_snp_call's code byte and p-value per position; the first eight columns are gm_coverage_write_gmp's, byte for byte
-    if (!ix || !path) return GM_E_ARG;
-    if (const int rc = snp_tracks_ready(ix)) return rc;
-    HIPCHK(hipSetDevice(ix->device));
-    const GmHostIndex& h = ix->h;
-    const uint64_t bins = ix->cov_bins, nbk = h.l_pac;
-    const uint64_t slab_max = std::min<uint64_t>(nbk, (uint64_t)std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 20)) * host_threads());
-    Scoped<DevBuf> d_code, d_pval, d_cnt;
-    Scoped<PinBuf> h_f, h_code, h_pval;
-    if (d_code.ensure(slab_max) || d_pval.ensure(slab_max * 8) || d_cnt.ensure((size_t)gmk_snp_call_groups(slab_max) * 4 + 4) || h_f.ensure(slab_max * 24) ||
-        h_code.ensure(slab_max) || h_pval.ensure(slab_max * 8)) return GM_E_NOMEM;
-    uint64_t s_lo = 0, s_n = 0;
-    auto slab = [&](uint64_t lo, uint64_t hi) -> int {
-        s_lo = lo; s_n = hi - lo;
-        KCHK(gmk_snp_call(ix->d_cov.as<float>(), ix->d_nuc.as<float>(), bins, ix->dev, lo, s_n, snp_pval, monop ? 1 : 0, d_code.as<uint8_t>(), d_pval.as<double>(),
-                          d_cnt.as<uint32_t>(), nullptr));
-        HIPCHK(hipMemcpy(h_f.as<float>(), ix->d_cov.as<float>() + lo, s_n * 4, hipMemcpyDeviceToHost));
-        for (uint64_t q = 0; q < 5; ++q) HIPCHK(hipMemcpy(h_f.as<float>() + (q + 1) * s_n, ix->d_nuc.as<float>() + q * bins + lo, s_n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(h_code.p, d_code.p, s_n, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(h_pval.p, d_pval.p, s_n * 8, hipMemcpyDeviceToHost));
-        return GM_OK;
-    };
-    std::vector<int> cur(host_threads(), 0);
-    return write_track_text(path, append, nbk, max_contig_name(h) + 208, [&](uint64_t count, char* w, unsigned c, bool first) -> char* {
-        const CallsEmit e{ h, h_f.as<float>(), h_code.as<uint8_t>(), h_pval.as<double>(), s_lo, s_n };
-        return e(count, w, cur[c], first);
-    }, slab);
-}
-
-// ------------------------------------------------------------------------------------------------
-// track files formatted on the device (gm_tracktext.hip)
-// ------------------------------------------------------------------------------------------------
-namespace {
-struct ScopedEvents {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~ScopedEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-// where the text goes: a file at a running offset, or the first cap bytes into the caller's buffer; `total` counts everything
-struct TrackSink {
-    int fd = -1; uint64_t file_off = 0;
-    char* mem = nullptr; uint64_t cap = 0;
-    uint64_t total = 0;
-    uint64_t room() const { return fd >= 0 ? ~0ull : (cap > total ? cap - total : 0); }
-    bool put(const char* q, uint64_t n) {                    // host text
-        if (fd >= 0) {
-            uint64_t at = file_off, left = n;
-            while (left) { const ssize_t k = ::pwrite(fd, q, (size_t)left, (off_t)at); if (k <= 0) return false; q += k; left -= (uint64_t)k; at += (uint64_t)k; }
-            file_off += n;
-        } else if (const uint64_t m = std::min(n, room())) memcpy(mem + total, q, (size_t)m);
-        total += n;
-        return true;
-    }
-};
-
-// bins [lo, hi) as rows: per slab of GM_TRACK_SLICE bins the sizes pass and its scan, the 32 bytes of `meta` read back, a text buffer of
-// exactly that size, the rows pass, and the text down in pieces of 32 MB through two page-locked buffers (the copy of one piece runs
-// while the one before it is written).  A slab whose meta says that a printed value needs snprintf is formatted here from its own tracks.
-// GM_TRACK_CALLS (the nine-column .gmp): k_snp_call runs first on every slab and its code bytes / p-values stay in HBM for the two passes.
-// GM_TRACK_CALLS: k_snp_call with `calls` settings fills the slab's code bytes and p-values before the sizes pass
-struct TrackCalls { float snp_pval; int monop; };
-int track_text_run(gm_index* ix, const char* call, int kind, char want, uint64_t lo, uint64_t hi, TrackSink& out, const TrackCalls* calls = nullptr) {
-    HIPCHK(hipSetDevice(ix->device));
-    if (const int rc = index_cnames(ix)) return rc;
-    const GmHostIndex& h = ix->h;
-    const uint64_t bs = ix->cov_bin_size, bins = ix->cov_bins, nbk = (h.l_pac + bs - 1) / bs;      // the files print the bins that start below l_pac
-    hi = std::min(hi, nbk); lo = std::min(lo, hi);
-    const uint64_t per = (uint64_t)std::min<long long>(std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 24)), 1ll << 26);      // bins per slab
-    const size_t piece = (size_t)32 << 20;
-    gm_track_text_stats st{};
-    ix->tt_stats = st;
-    const uint32_t tiles_max = gmk_track_tiles(std::min(per, hi - lo));
-    Scoped<DevBuf> d_len, d_off, d_meta, d_text, d_code, d_pval, d_cnt;
-    Scoped<PinBuf> h_meta, h_txt[2];
-    ScopedEvents ev;
-    if (d_len.ensure((size_t)tiles_max * 4 + 4) || d_off.ensure(((size_t)tiles_max + 1) * 8) || d_meta.ensure(TT_META_N * 8) || h_meta.ensure(TT_META_N * 8)) return GM_E_NOMEM;
-    const bool nine = kind == GM_TRACK_CALLS;
-    if (nine && !calls) return GM_E_ARG;
-    const uint64_t slab_max = std::min(per, hi - lo);
-    if (nine && slab_max && (d_code.ensure(slab_max) || d_pval.ensure(slab_max * 8) || d_cnt.ensure((size_t)gmk_snp_call_groups(slab_max) * 4 + 4))) return GM_E_NOMEM;
-    HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
-    GmDevTrack t{};
-    t.cov = ix->d_cov.as<float>(); t.nuc = kind == GM_TRACK_SGR ? nullptr : ix->d_nuc.as<float>(); t.nuc_stride = bins;
-    t.pac = ix->dev.pac; t.contig_off = ix->dev.contig_off; t.n_seqs = ix->dev.n_seqs;
-    t.cnames = ix->d_cnames.as<char>(); t.cname_off = ix->d_cname_off.as<uint32_t>();
-    t.bin_size = (uint32_t)bs; t.kind = (uint32_t)kind; t.want = want == 'a' ? 0u : want == 'c' ? 1u : want == 'g' ? 2u : 3u;
-    t.tile_len = d_len.as<uint32_t>(); t.tile_off = d_off.as<unsigned long long>(); t.meta = d_meta.as<unsigned long long>();
-    t.code = d_code.as<uint8_t>(); t.pval = d_pval.as<double>();
-    const hipStream_t s = nullptr;
-    const unsigned long long* meta = h_meta.as<unsigned long long>();
-    const size_t max_line = max_contig_name(h) + (nine ? 208 : 160);
-    std::vector<float> hf; std::vector<char> hbuf;          // a host-formatted slab's tracks and text
-    std::vector<uint8_t> hcode; std::vector<double> hpval;  // and, for the nine-column file, its calls
-    auto fail_io = [&]() { gm_set_error(std::string(call) + ": write failed"); return GM_E_IO; };
-    // the host emitters, from this slab's tracks only
-    auto host_slab = [&](uint64_t s0, uint64_t n) -> int {
-        ++st.host_slabs;
-        const int cols = kind == GM_TRACK_SGR ? 1 : 6;
-        hf.resize((size_t)n * cols);
-        HIPCHK(hipMemcpy(hf.data(), t.cov + s0, n * 4, hipMemcpyDeviceToHost));
-        for (int q = 1; q < cols; ++q) HIPCHK(hipMemcpy(hf.data() + (size_t)q * n, t.nuc + (uint64_t)(q - 1) * bins + s0, n * 4, hipMemcpyDeviceToHost));
-        if (nine) {
-            hcode.resize((size_t)n); hpval.resize((size_t)n);
-            HIPCHK(hipMemcpy(hcode.data(), t.code, n, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(hpval.data(), t.pval, n * 8, hipMemcpyDeviceToHost));
-        }
-        const TrackEmit e{ h, bs, kind, want, hf.data(), hf.data() + n, n, s0 };
-        const CallsEmit e9{ h, hf.data(), hcode.data(), hpval.data(), s0, n };
-        int cur = 0;
-        for (uint64_t k0 = s0; k0 < s0 + n; k0 += 65536) {
-            const uint64_t k1 = std::min(s0 + n, k0 + 65536);
-            hbuf.resize((size_t)(k1 - k0) * max_line);
-            char* w = hbuf.data();
-            for (uint64_t k = k0; k < k1; ++k) { char* const w2 = nine ? e9(k, w, cur, k == k0) : e(k, w, cur, k == k0); st.rows += w2 != w; w = w2; }
-            if (!out.put(hbuf.data(), (uint64_t)(w - hbuf.data()))) return fail_io();
-        }
-        return GM_OK;
-    };
-    for (uint64_t s0 = lo; s0 < hi; s0 += per) {
-        const uint64_t n = std::min(per, hi - s0);
-        float ms = 0;
-        t.lo = s0; t.n = n; t.text = nullptr;
-        HIPCHK(hipMemsetAsync(d_meta.p, 0, TT_META_N * 8, s));
-        HIPCHK(hipEventRecord(ev.a, s));
-        if (nine) KCHK(gmk_snp_call(t.cov, t.nuc, bins, ix->dev, s0, n, calls->snp_pval, calls->monop ? 1 : 0, d_code.as<uint8_t>(), d_pval.as<double>(), d_cnt.as<uint32_t>(), s));
-        KCHK(gmk_track_sizes(t, s));
-        HIPCHK(hipEventRecord(ev.b, s));
-        HIPCHK(hipMemcpyAsync(h_meta.p, d_meta.p, TT_META_N * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
-        st.kernel_ms += ms; st.launches += nine ? 3 : 2; ++st.slabs;
-        const uint64_t bytes = meta[TT_META_BYTES];
-        if (meta[TT_META_HOST]) {
-            if (const int rc = host_slab(s0, n)) return rc;
-            continue;
-        }
-        st.rows += meta[TT_META_ROWS];
-        const uint64_t need = std::min(bytes, out.room());   // what has to come down
-        if (need) {
-            if (d_text.ensure((size_t)bytes + 16)) return GM_E_NOMEM;
-            t.text = d_text.as<char>();
-            HIPCHK(hipEventRecord(ev.a, s));
-            KCHK(gmk_track_rows(t, s));
-            HIPCHK(hipEventRecord(ev.b, s));
-            ++st.launches;
-            if (nine) {                                      // k_track_rows<true> flags a p-value that gm_put_e2_hd refused inside its domain
-                HIPCHK(hipMemcpyAsync(h_meta.p, d_meta.p, TT_META_N * 8, hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-                if (meta[TT_META_HOST]) {
-                    st.rows -= meta[TT_META_ROWS];           // host_slab counts them
-                    if (const int rc = host_slab(s0, n)) return rc;
-                    continue;
-                }
-            }
-            if (out.fd < 0) HIPCHK(hipMemcpy(out.mem + out.total, t.text, (size_t)need, hipMemcpyDeviceToHost));
-            else {
-                const char* prev = nullptr; size_t prev_n = 0; int c = 0;
-                for (uint64_t done = 0; done < bytes; c ^= 1) {
-                    const size_t m = (size_t)std::min<uint64_t>(piece, bytes - done);
-                    if (h_txt[c].ensure(m)) return GM_E_NOMEM;
-                    HIPCHK(hipMemcpyAsync(h_txt[c].p, t.text + done, m, hipMemcpyDeviceToHost, s));
-                    if (prev && !out.put(prev, prev_n)) return fail_io();
-                    HIPCHK(hipStreamSynchronize(s));
-                    prev = h_txt[c].as<char>(); prev_n = m; done += m;
-                }
-                if (prev && !out.put(prev, prev_n)) return fail_io();
-                out.total -= bytes;                          // counted below
-            }
-            HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
-            st.kernel_ms += ms;
-        }
-        out.total += bytes;
-    }
-    st.bytes = out.total;
-    ix->tt_stats = st;
-    return GM_OK;
-}
-
-// the checks the three entry points share; kind / want from the mode
-int track_text_args(gm_index* ix, const gm_params* p, const char* call, int& kind, char& want) {
-    if (!ix->cov_bins || !ix->cov_bin_size) { gm_set_error(std::string(call) + ": no coverage track (gm_coverage_reset)"); return GM_E_ARG; }
-    const int mode = p ? p->mode : GM_MODE_NORMAL;
-    kind = mode == GM_MODE_NORMAL ? GM_TRACK_SGR : mode == GM_MODE_SNP ? GM_TRACK_SNP : GM_TRACK_BASE;
-    want = gmp_want(mode);
-    if (ix->host_only) { gm_set_error(std::string(call) + ": no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    if (kind != GM_TRACK_SGR && !ix->nuc_on) { gm_set_error(std::string(call) + ": the .gmp rows read the per-nucleotide tracks: call gm_coverage_enable_nuc first"); return GM_E_ARG; }
-    return GM_OK;
-}
-
-int track_text_file(gm_index* ix, const gm_params* p, const char* call, const char* path, int append) {
-    int kind; char want;
-    if (const int rc = track_text_args(ix, p, call, kind, want)) return rc;
-    // no O_APPEND: pwrite() on such a descriptor ignores its offset (see write_track_text)
-    const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
-    if (fd < 0) { gm_set_error(std::string(call) + ": cannot write " + path); return GM_E_IO; }
-    TrackSink out;
-    out.fd = fd; out.file_off = append ? (uint64_t)lseek(fd, 0, SEEK_END) : 0;
-    const int rc = track_text_run(ix, call, kind, want, 0, ix->cov_bins, out);
-    ::close(fd);
-    return rc;
-}
-}  // namespace
-
-extern "C" int gm_coverage_write_sgr_device(gm_index* ix, const char* path, int append) {
-    // GenomeBwt::PrintFinalSGR src/GenomeBwt.cpp:1212-1273, from the track in HBM
-    if (!ix || !path) { gm_set_error("gm_coverage_write_sgr_device: null argument"); return GM_E_ARG; }
-    return track_text_file(ix, nullptr, "gm_coverage_write_sgr_device", path, append);
-}
-
-extern "C" int gm_coverage_write_gmp_device(gm_index* ix, const gm_params* p, const char* path, int append) {
-    // GenomeBwt::PrintFinalBisulfite src/GenomeBwt.cpp:1092-1210, PrintFinalSNP :930-1009 (eight columns), from the tracks in HBM
-    if (!ix || !p || !path) { gm_set_error("gm_coverage_write_gmp_device: null argument"); return GM_E_ARG; }
-    if (p->mode == GM_MODE_NORMAL) { gm_set_error("gm_coverage_write_gmp_device: GM_MODE_NORMAL writes an .sgr (gm_coverage_write_sgr_device)"); return GM_E_ARG; }
-    return track_text_file(ix, p, "gm_coverage_write_gmp_device", path, append);
-}
-
-extern "C" int gm_coverage_text(gm_index* ix, const gm_params* p, uint64_t bin_lo, uint64_t bin_hi, char* text, uint64_t cap, uint64_t* n_out) {
-    if (!ix || !n_out || (cap && !text)) { gm_set_error("gm_coverage_text: null argument"); return GM_E_ARG; }
-    int kind; char want;
-    if (!ix->cov_bins || !ix->cov_bin_size) { gm_set_error("gm_coverage_text: no coverage track (gm_coverage_reset)"); return GM_E_ARG; }
-    if (bin_lo > bin_hi || bin_hi > ix->cov_bins) { gm_set_error("gm_coverage_text: bins [bin_lo, bin_hi) are not a range of the track"); return GM_E_ARG; }
-    if (const int rc = track_text_args(ix, p, "gm_coverage_text", kind, want)) return rc;
-    TrackSink out;
-    out.mem = text; out.cap = cap;
-    if (const int rc = track_text_run(ix, "gm_coverage_text", kind, want, bin_lo, bin_hi, out)) return rc;
-    *n_out = out.total;
-    if (out.total > cap) { gm_set_error("gm_coverage_text: text[] too small"); return GM_E_CAPACITY; }
-    return GM_OK;
-}
-
-namespace {
-// snp_tracks_ready under the caller's name: bin size 1, the five sums, a device
-int calls_text_ready(gm_index* ix, const char* call) {
-    if (!ix->cov_bins || ix->cov_bin_size != 1) { gm_set_error(std::string(call) + ": SNP calls need the coverage track with bin size 1 (gm_coverage_reset(ix, 1))"); return GM_E_ARG; }
-    if (!ix->host_only && !ix->nuc_on) { gm_set_error(std::string(call) + ": SNP calls read the per-nucleotide tracks: call gm_coverage_enable_nuc first"); return GM_E_ARG; }
-    if (ix->host_only) { gm_set_error(std::string(call) + ": no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    return GM_OK;
-}
-}  // namespace
-
-extern "C" int gm_coverage_write_gmp_calls_device(gm_index* ix, float snp_pval, int monop, const char* path, int append) {
-    // the file of gm_coverage_write_gmp_calls from the tracks in HBM: k_snp_call, then k_track_sizes<true> / k_track_rows<true> per slab
-    const char* const call = "gm_coverage_write_gmp_calls_device";
-    if (!ix || !path) { gm_set_error(std::string(call) + ": null argument"); return GM_E_ARG; }
-    if (const int rc = calls_text_ready(ix, call)) return rc;
-    const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
-    if (fd < 0) { gm_set_error(std::string(call) + ": cannot write " + path); return GM_E_IO; }
-    TrackSink out;
-    out.fd = fd; out.file_off = append ? (uint64_t)lseek(fd, 0, SEEK_END) : 0;
-    const TrackCalls calls{ snp_pval, monop };
-    const int rc = track_text_run(ix, call, GM_TRACK_CALLS, 0, 0, ix->cov_bins, out, &calls);
-    ::close(fd);
-    return rc;
-}
-
-extern "C" int gm_coverage_calls_text(gm_index* ix, float snp_pval, int monop, uint64_t bin_lo, uint64_t bin_hi, char* text, uint64_t cap, uint64_t* n_out) {
-    const char* const call = "gm_coverage_calls_text";
-    if (!ix || !n_out || (cap && !text)) { gm_set_error(std::string(call) + ": null argument"); return GM_E_ARG; }
-    if (!ix->cov_bins || !ix->cov_bin_size) { gm_set_error(std::string(call) + ": no coverage track (gm_coverage_reset)"); return GM_E_ARG; }
-    if (bin_lo > bin_hi || bin_hi > ix->cov_bins) { gm_set_error(std::string(call) + ": bins [bin_lo, bin_hi) are not a range of the track"); return GM_E_ARG; }
-    if (const int rc = calls_text_ready(ix, call)) return rc;
-    TrackSink out;
-    out.mem = text; out.cap = cap;
-    const TrackCalls calls{ snp_pval, monop };
-    if (const int rc = track_text_run(ix, call, GM_TRACK_CALLS, 0, bin_lo, bin_hi, out, &calls)) return rc;
-    *n_out = out.total;
-    if (out.total > cap) { gm_set_error(std::string(call) + ": text[] too small"); return GM_E_CAPACITY; }
-    return GM_OK;
-}
-
-extern "C" int gm_coverage_write_vcf(gm_index* ix, float snp_pval, int monop, const char* path, int append) {
-    // Genome::PrintFinalVCF src/Genome.cpp:1142-1245 over gm_snp_calls' records.  The rows are few (one per called SNP), so they are
-    // formatted here: a count pass, then the records of one stretch of positions at a time
-    const char* const call = "gm_coverage_write_vcf";
-    if (!ix || !path) { gm_set_error(std::string(call) + ": null argument"); return GM_E_ARG; }
-    if (const int rc = calls_text_ready(ix, call)) return rc;
-    uint64_t total = 0;
-    int rc = snp_calls_range(ix, snp_pval, monop, 0, ~0ull, nullptr, 0, &total, nullptr);
-    if (rc != GM_OK && rc != GM_E_CAPACITY) return rc;
-    FILE* f = fopen(path, append ? "a" : "w");
-    if (!f) { gm_set_error(std::string(call) + ": cannot write " + path); return GM_E_IO; }
-    if (!append) {
-        char date[16] = "";
-        const time_t now = time(nullptr);
-        struct tm tmv;
-        if (localtime_r(&now, &tmv)) strftime(date, sizeof date, "%Y%m%d", &tmv);
-        fprintf(f, "##fileformat=VCFv4.0\n##fileDate=%s\n##source=%s\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n", date, gm_version());
-    }
-    const GmHostIndex& h = ix->h;
-    const uint64_t step = (uint64_t)std::max<long long>(1, gm_opt_ll("GM_TRACK_SLICE", 1ll << 20)) * 16;     // snp_calls_range's positions per launch
-    std::vector<gm_snp_rec> recs((size_t)std::min<uint64_t>(std::max<uint64_t>(total, 1), 1u << 16));
-    unsigned long long id = 0;
-    for (uint64_t lo = 0; total && lo < h.l_pac; lo += step) {
-        uint64_t got = 0;
-        rc = snp_calls_range(ix, snp_pval, monop, lo, lo + step, recs.data(), recs.size(), &got, nullptr);
-        if (rc == GM_E_CAPACITY) {                           // a denser stretch: once more with room for it
-            recs.resize((size_t)got);
-            rc = snp_calls_range(ix, snp_pval, monop, lo, lo + step, recs.data(), recs.size(), &got, nullptr);
-        }
-        if (rc != GM_OK) { fclose(f); return rc; }
-        auto base = [](unsigned b) { return b < 5u ? b : 4u; };
-        for (uint64_t r = 0; r < got; ++r) {
-            const gm_snp_rec& c = recs[(size_t)r];
-            const unsigned a1 = base(c.alt1), a2 = base(c.alt2);
-            const char* name = h.contigs[c.contig].name.c_str();
-            if (c.diploid)
-                fprintf(f, "%s\t%llu\tsnp%llu\t%c\t%c%c\t.\t.\tDiploid;pval=%.5f;coverage=%.5f;ratio=%.2f\n", name, (unsigned long long)c.chr_pos, id++, "acgtn"[base(c.ref)],
-                        "acgtn"[a1], "acgtn"[a2], c.p_val, c.total, c.nuc[a2] / c.nuc[a1]);
-            else
-                fprintf(f, "%s\t%llu\tsnp%llu\t%c\t%c\t.\t.\tMonoploid;pval=%.5f;coverage=%.5f\n", name, (unsigned long long)c.chr_pos, id++, "acgtn"[base(c.ref)], "acgtn"[a1], c.p_val,
-                        c.total);
-        }
-    }
-    const bool bad = ferror(f) != 0;
-    if (fclose(f) != 0 || bad) { gm_set_error(std::string(call) + ": write failed: " + path); return GM_E_IO; }
-    return GM_OK;
-}
-
-extern "C" int gm_coverage_text_stats(gm_index* ix, gm_track_text_stats* out) {
-    if (!ix || !out) return GM_E_ARG;
-    *out = ix->tt_stats;
     return GM_OK;
 }

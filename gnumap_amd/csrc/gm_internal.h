@@ -177,7 +177,7 @@ struct GmDevText {
     uint32_t fa_qual;                               // FASTA blocks: str2qual's character of a row with 1, 2, 3, 4 bases in its mask, in bytes 0 .. 3
 };
 
-// gm_snp_rec (layout asserted in gm_api.cpp): a row of --snp's .gmp that carries a 'Y' call, written by k_snp_gather (gm_snpcall.hip)
+// gm_snp_rec (layout asserted in gm_tracks.cpp): a row of --snp's .gmp that carries a 'Y' call, written by k_snp_gather (gm_snpcall.hip)
 struct GmDevSnpRec { unsigned long long pos; uint32_t contig, pad0; unsigned long long chr_pos; float total, nuc[5]; double p_val; uint8_t ref, alt1, alt2, diploid;
                      uint8_t pad1[4]; };
 

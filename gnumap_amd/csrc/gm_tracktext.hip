@@ -1,6 +1,6 @@
 // gm_tracktext.hip — the per-position files as text, formatted where the tracks live: <out>.sgr (GenomeBwt::PrintFinalSGR
 // src/GenomeBwt.cpp:1212-1273), the eight-column <out>.gmp (PrintFinalBisulfite :1092-1210, PrintFinalSNP :930-1009 without
-// PrintSNPCall's column) and the nine-column one with it.  The contract is the bytes of the host writers of gm_api.cpp
+// PrintSNPCall's column) and the nine-column one with it.  The contract is the bytes of the host writers of gm_tracks.cpp
 // (gm_coverage_write_sgr / _gmp / _gmp_calls):
 //
 //   bin k, count = k * bin_size, contig = the last one whose offset is <= count (bins run over the CONCATENATED coordinate)
@@ -9,7 +9,7 @@
 //   .gmp  others  a row iff the reference base at count is the mode's and bins[k] > 0.0f
 //                                                              name \t pos \t %f    5 x (\t %.5f)  \n
 //
-// Numbers: put_fixed (gm_api.cpp) is the specification.  For 0 <= v < 1e9 the digits are rint((double)v * 10^N); the product of a
+// Numbers: put_fixed (gm_tracks.cpp) is the specification.  For 0 <= v < 1e9 the digits are rint((double)v * 10^N); the product of a
 // 24-bit float and 10^5 or 10^6 is exact in a double and rint rounds to nearest even on the device as on the host, so the digits are
 // the host's bit for bit (the library is built with -ffp-contract=off).  -0.0f takes that path too and prints as 0.  Every other
 // value (negative, NaN, inf, >= 1e9) is snprintf's on the host: a launch that meets one in a row it would print only FLAGS its slab

@@ -6,11 +6,13 @@ gm_coverage_write_gmp_calls, which tests/test_gpu_snp_call.py pins to the refere
   1. gm_dev_fmt_e2 against Python's "%.2e";
   2. device writer == host writer, byte for byte, three call settings x three slab sizes, on tracks that hold every column shape on both
      sides of every contig boundary, at position 0 and at l_pac - 1, the print threshold from both sides, p = 0 and p = 1 (flat counts
-     give p = 1 under --snp_monop; the diploid test turns them into a diploid call of small p), and a non-zero tail past l_pac;
+     give p = 1 under --snp_monop; the diploid test turns them into a diploid call of small p), and a non-zero tail past l_pac; the host
+     writer against itself in several slabs and appending;
   3. one tile whose text needs two LDS windows;
   4. gm_coverage_calls_text on ranges, and its capacity protocol;
   5. a NaN and a negative count in printed rows: their slabs, and no other, are formatted by the host;
-  6. the VCF against a Python formatter over gm_snp_calls' records and against the 'Y' rows of the .gmp;
+  6. the VCF against a Python formatter over gm_snp_calls' records and against the 'Y' rows of the .gmp; in many launches, appended, and
+     with a stretch of more records than its first buffer holds;
   7. the driver with --snp --snp_calls --vcf --track_text=device against the reference program's nine-column file.
 
 Every count of 2, 3 and 4 lies in [0, 1e9) and every p-value in gm_put_e2_hd's domain: there host_slabs must be 0 - a host-formatted
@@ -189,6 +191,23 @@ def test_device_writer_equals_the_host_writer(world, tmp_path, monop, pval):
     assert _with_slice(4096, lambda: (world.device_file(out, pval, monop), world.device_file(out, pval, monop, append=True))[1]) == 2 * want
 
 
+@pytest.mark.parametrize("monop,pval", SETTINGS[:2], ids=IDS[:2])
+def test_host_writer_in_several_slabs_and_appending(world, tmp_path, monop, pval):
+    """gm_coverage_write_gmp_calls itself: the text does not depend on how many slabs of the tracks it brings down (512 positions per host
+    thread, 16 threads unless GM_HOST_THREADS says otherwise: more than 30 slabs), and appending writes behind what is there"""
+    world.upload(world.cov, world.nuc)
+    want = world.host_file(str(tmp_path / "host.gmp"), pval, monop)                # the text test_device_writer_equals_the_host_writer holds the device writer to
+    assert want.count(b"\n") > 6000 and world.l_pac > 30 * 512 * 16
+    out = str(tmp_path / "slabs.gmp")
+    write = lambda append: g.lib().gm_coverage_write_gmp_calls(world.ix.h, pval, int(monop), out.encode(), append)
+
+    def run():
+        assert write(0) == 0
+        assert open(out, "rb").read() == want
+        assert write(1) == 0
+        assert open(out, "rb").read() == 2 * want
+    _with_slice(512, run)
+
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------------------
 def test_a_tile_of_two_lds_windows(world, tmp_path):
     rng = np.random.default_rng(23)
@@ -325,6 +344,38 @@ def test_vcf(world, tmp_path, monop, pval):
     only = open(out, "rb").read()
     assert HEADER.fullmatch(only)
 
+
+def test_vcf_in_many_launches_and_a_stretch_beyond_the_first_buffer(world, tmp_path):
+    """gm_coverage_write_vcf fetches its records one stretch of 16 x GM_TRACK_SLICE positions at a time, into a buffer of at most 65 536
+    records at first.  GM_TRACK_SLICE=64: stretches of 1024 positions, 274 of them, each a call of its own with a launch of its own, a new
+    file and appending.  The default (2^20): ONE stretch, the whole reference; with 70 000 substituted positions in a row it holds more
+    than 70 000 records, which is more than the first buffer: the fetch is repeated with room for them ("once more with room for it")."""
+    pval, monop = 0.001, False
+    cov, nuc = world.cov.copy(), world.nuc.copy()
+    ks = np.arange(100000, 170000)                                  # across the boundaries it meets; every base read as another one, 50 times
+    assert world.l_pac > ks[-1] and world.l_pac <= 16 << 20
+    nuc[:, ks] = 0; nuc[(world.ref[ks] + 1) % 4, ks] = 50.0; cov[ks] = 50.0
+    world.upload(cov, nuc)
+    ix = world.ix
+    calls = ix.snp_calls(pval, monop)
+    dense = int(((calls["pos"] >= ks[0]) & (calls["pos"] <= ks[-1])).sum())
+    assert dense == len(ks) == 70000 > 1 << 16 and len(calls) > dense                # every one of them is called, and others besides
+    body = _vcf_rows(calls, world.contigs)
+    assert b"\tDiploid;" in body and b"\tMonoploid;" in body
+    out = str(tmp_path / "o.vcf")
+
+    def many():
+        ix.coverage_write_vcf(out, pval, monop)
+        text = open(out, "rb").read()
+        ix.coverage_write_vcf(out, pval, monop, append=True)
+        return text, open(out, "rb").read()
+    text, twice = _with_slice(64, many)
+    m = HEADER.match(text)
+    assert m and text[m.end():] == body
+    assert twice == text + body                                     # one header, the records twice
+    ix.coverage_write_vcf(out, pval, monop)                         # one stretch of len(calls) > 65 536 records
+    one = open(out, "rb").read()
+    assert HEADER.match(one) and one[HEADER.match(one).end():] == body
 
 # ---- 7 ---------------------------------------------------------------------------------------------------------------------------------
 def test_cli_snp_calls_vcf_with_track_text_device(tmp_path, syn_fa):

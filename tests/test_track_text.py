@@ -75,3 +75,43 @@ def test_sgr_and_gmp_text_equal_printf(syn_fa, tmp_path):
         want.append("%s\t%d\t%f\t%.5f\t%.5f\t%.5f\t%.5f\t%.5f\n" % ((contigs[i][0], k - contigs[i][1] + 1, float(bins[k])) + tuple(float(nuc[q * nb + k]) for q in range(5))))
     assert open(out).read() == "".join(want) and len(want) > 10000
     L.gm_index_close(h)
+
+
+def test_snp_gmp_text_equal_printf(syn_fa, tmp_path):
+    """--snp's eight-column .gmp (GenomeBwt::PrintFinalSNP src/GenomeBwt.cpp:930-1009 without the call column): bin size 1, a row iff the
+    fp32 total is above fp32 0.001, six "%.5f" columns; the same text from several slices, and behind what is there when appending"""
+    L = g.lib()
+    h = C.c_void_p()
+    assert L.gm_index_open(os.fsencode(syn_fa), 0, api.GM_INDEX_HOST_ONLY, C.byref(h)) == 0
+    L.gm_coverage_write_gmp.argtypes = [C.c_void_p, C.POINTER(api.gm_params), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    L.gm_coverage_bins.restype = C.c_uint64; L.gm_coverage_bins.argtypes = [C.c_void_p]
+    contigs = [(L.gm_index_contig_name(h, i).decode(), L.gm_index_contig_offset(h, i)) for i in range(3)]
+    l_pac = L.gm_index_contig_offset(h, 3)
+    rng = np.random.default_rng(5)
+    p = g.Params(mode=5)
+    assert L.gm_coverage_reset(h, 1) == 0
+    nb = L.gm_coverage_bins(h)
+    bins = _values(nb, rng); nuc = _values(5 * nb, rng)
+    offs = np.array([off for _, off in contigs])
+    want = []
+    for k in range(l_pac):
+        if not np.float32(bins[k]) > np.float32(0.001):
+            continue
+        i = int(np.searchsorted(offs, k, side="right")) - 1
+        want.append("%s\t%d\t%.5f\t%.5f\t%.5f\t%.5f\t%.5f\t%.5f\n" % ((contigs[i][0], k - contigs[i][1] + 1, float(bins[k])) + tuple(float(nuc[q * nb + k]) for q in range(5))))
+    want = "".join(want)
+    # the threshold from both sides and a contig boundary are among the rows
+    assert want.count("\n") > 10000 and (bins[:l_pac] == np.float32(0.001)).any() and len({l.split("\t")[0] for l in want.splitlines()}) == 3
+    out = str(tmp_path / "snp.gmp")
+    write = lambda append: L.gm_coverage_write_gmp(h, C.byref(p.c), bins.ctypes.data, nuc.ctypes.data, out.encode(), append)
+    assert write(0) == 0
+    assert open(out).read() == want
+    assert L.gm_set_option(b"GM_TRACK_SLICE", b"4096") == 0
+    try:
+        assert write(0) == 0
+        assert open(out).read() == want
+    finally:
+        assert L.gm_set_option(b"GM_TRACK_SLICE", None) == 0
+    assert write(1) == 0
+    assert open(out).read() == 2 * want
+    L.gm_index_close(h)
