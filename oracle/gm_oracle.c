@@ -584,7 +584,7 @@ static int process_hits(const gmo_index* ix, const gmo_params* p, gmo_result* r,
                 memmove(r->hits + at + 1, r->hits + at, sizeof(gmo_hit) * (size_t)(r->n_hits - at));
                 h = &r->hits[at];
                 memset(h, 0, sizeof *h);
-                h->key = strdup(key); h->seq = strdup(w); h->score = sc; h->first_strand = strand;
+                h->key = strdup(key); h->seq = strdup(w); h->score = sc; h->first_strand = strand; h->first_pos = b;
                 hit_add_spot(h, b, strand);
                 r->n_hits++;
                 r->denominator += exp(sc);

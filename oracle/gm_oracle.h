@@ -64,6 +64,7 @@ typedef struct {
     double score;               /* align score of the FIRST hit */
     int first_strand;
     gmo_pos* pos; int n_pos, cap_pos;   /* ordered set of (pos,strand) */
+    uint64_t first_pos;         /* window start of the FIRST hit (with first_strand: the place that made the key) */
 } gmo_hit;
 
 typedef struct {

@@ -159,7 +159,7 @@ class GmoPos(C.Structure):
 
 class GmoHit(C.Structure):
     _fields_ = [("key", C.c_char_p), ("seq", C.c_char_p), ("score", C.c_double), ("first_strand", C.c_int),
-                ("pos", C.POINTER(GmoPos)), ("n_pos", C.c_int), ("cap_pos", C.c_int)]
+                ("pos", C.POINTER(GmoPos)), ("n_pos", C.c_int), ("cap_pos", C.c_int), ("first_pos", u64)]
 
 
 class GmoResult(C.Structure):
@@ -280,7 +280,7 @@ class OracleLib:
         hits = []
         for i in range(r.n_hits):
             h = r.hits[i]
-            hits.append(dict(key=h.key, seq=h.seq, score=h.score, first_strand=h.first_strand,
+            hits.append(dict(key=h.key, seq=h.seq, score=h.score, first_strand=h.first_strand, first_pos=h.first_pos,
                              pos=[(h.pos[j].pos, h.pos[j].strand) for j in range(h.n_pos)]))
         out = dict(status=r.status, self_score=r.self_score, min_score=r.min_score, top_score=r.top_score,
                    denominator=r.denominator, hits=hits,

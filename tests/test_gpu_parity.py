@@ -541,8 +541,10 @@ def test_every_kernel_variant_matches_oracle(env, cfg, syn_fa, oracle, oix, syn_
 
 @pytest.mark.parametrize("cfg", ["default", "no_nw", "T2", "unique", "unique_no_nw", "k1", "m6_j2", "bs", "a07_q50"])
 def test_big_grouping_path_matches_oracle(cfg, syn_fa, oracle, oix, syn_reads, tmp_path):
-    """GM_GROUP_BIG_MIN=1 sends every read with >= 2 accepted hits through the hash-set + wave-radix-sort grouping (k_group_big /
-    k_group_write_big: the path of reads with thousands of repeat copies), incl. its -T / -u exits and the hand-back cases"""
+    """GM_GROUP_BIG_MIN=1 sends every read of syn.fq with >= 2 accepted hits through the hash-set + wave-radix-sort grouping (k_group_big /
+    k_group_write_big) in nine configurations, -T 2 and -u among them.  These reads have 2 or 3 hits (the period-8 stretch: many, in
+    about eight keys): one sort pass, a set that stays almost empty, and no assertion that a read was handed back to the all-pairs kernel.
+    The path at 65 .. 3001 hits, the set's limit and the three hand-backs by their counts: tests/test_gpu_repeat_groups.py"""
     _run_variant(dict(GM_GROUP_BIG_MIN="1"), cfg, syn_fa, oracle, oix, syn_reads, tmp_path)
 
 
