@@ -75,6 +75,19 @@ class gm_sam_text(C.Structure):
     _fields_ = [("text", C.c_void_p), ("text_cap", u64), ("text_len", u64), ("n_recs", u64), ("row_off", C.c_void_p), ("row_cap", u64)]
 
 
+class gm_text_info(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("max_len", C.c_uint32), ("stride", C.c_uint32), ("status", C.c_int32), ("bad_at", u64)]
+
+
+class gm_text_rec(C.Structure):
+    _fields_ = [("name_off", C.c_uint32), ("seq_off", C.c_uint32), ("qual_off", C.c_uint32), ("name_len", C.c_uint32), ("seq_len", C.c_uint32),
+                ("qual_len", C.c_uint32)]
+
+
+GM_TEXT_OK, GM_TEXT_MALFORMED, GM_TEXT_TOO_LONG = 0, 1, 2
+TEXT_REC_DTYPE = np.dtype([("name_off", "<u4"), ("seq_off", "<u4"), ("qual_off", "<u4"), ("name_len", "<u4"), ("seq_len", "<u4"), ("qual_len", "<u4")])
+
+
 class gm_counters(C.Structure):
     _fields_ = [(n, u64) for n in ("reads", "kmers_searched", "occ_calls", "occ_blocks", "seeds_used", "sa_hits", "lf_steps", "candidates",
                                    "nw_cells", "accepted", "vote_retries", "table_lookups")]
@@ -103,7 +116,8 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_coverage_write_sgr_device", "gm_coverage_write_gmp_device", "gm_coverage_text", "gm_coverage_text_stats",
            "gm_coverage_write_gmp_calls_device", "gm_coverage_calls_text", "gm_coverage_write_vcf",
            "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim",
-           "gm_batch_set_read_format", "gm_index_set_probe_format"]
+           "gm_batch_set_read_format", "gm_index_set_probe_format",
+           "gm_batch_upload_text", "gm_map_batch_text", "gm_output_batch_text_resident", "gm_dev_fastq_rows", "gm_dev_fastq_tile_bytes"]
 
 
 def library_path():
@@ -190,6 +204,11 @@ def load_library():
     L.gm_dev_adaptor_trim.argtypes = [C.c_void_p, C.POINTER(gm_reads), C.c_char_p, C.c_void_p]
     L.gm_batch_set_read_format.argtypes = [C.c_void_p, C.c_int]
     L.gm_index_set_probe_format.argtypes = [C.c_void_p, C.c_int]
+    L.gm_batch_upload_text.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, u64, C.POINTER(gm_text_info), C.c_void_p, u64, C.c_void_p]
+    L.gm_map_batch_text.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_hits), C.c_void_p]
+    L.gm_output_batch_text_resident.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_hits), C.POINTER(gm_sam_text), C.c_void_p]
+    L.gm_dev_fastq_rows.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(gm_text_info), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u64]
+    L.gm_dev_fastq_tile_bytes.argtypes = []; L.gm_dev_fastq_tile_bytes.restype = C.c_uint32
     _LIB = L
     return L
 
@@ -347,6 +366,21 @@ class Index:
         out = np.zeros(len(Ln), np.uint16)
         _chk(lib().gm_dev_adaptor_trim(self.h, C.byref(r), None if adaptor is None else bytes(adaptor), out.ctypes.data))
         return out
+
+    def dev_fastq_rows(self, text):
+        """gm_dev_fastq_rows: FASTQ text cut into rows on the device.  dict(n, max_len, stride, status, bad_at, recs[n] TEXT_REC_DTYPE,
+        bases[n, stride], quals[n, stride], len[n]): the block in front of the first record that ends it"""
+        text = bytes(text)
+        buf = np.frombuffer(text + b"\0", np.uint8)
+        info = gm_text_info()
+        rc = lib().gm_dev_fastq_rows(self.h, buf.ctypes.data, len(text), C.byref(info), None, None, None, None, 0)      # sizes the buffers
+        if rc != GM_E_CAPACITY:
+            _chk(rc)
+        n, stride = int(info.n), int(info.stride)
+        recs = np.zeros(n, TEXT_REC_DTYPE); B = np.zeros((n, stride), np.uint8); Q = np.zeros((n, stride), np.uint8); Ln = np.zeros(n, np.uint16)
+        if n:
+            _chk(lib().gm_dev_fastq_rows(self.h, buf.ctypes.data, len(text), C.byref(info), recs.ctypes.data, B.ctypes.data, Q.ctypes.data, Ln.ctypes.data, n))
+        return dict(n=n, max_len=int(info.max_len), stride=stride, status=int(info.status), bad_at=int(info.bad_at), recs=recs, bases=B, quals=Q, len=Ln)
 
     def dev_fmt_g6(self, values):
         """gm_dev_fmt_g6: printf("%g") of every value as the device prints XA / XP; a list of bytes (b"" = outside the domain)"""
@@ -518,6 +552,70 @@ class Batch:
         _chk(lib().gm_batch_set_read_format(self.h, GM_READS_FASTA if fasta else GM_READS_FASTQ))
         _chk(lib().gm_batch_upload(self.h, C.byref(params.c), C.byref(r), stream))
         self.n = B.shape[0]
+
+    def upload_text(self, params, text, stream=None, want_recs=True):
+        """gm_batch_upload_text: FASTQ text as it stands in the file -> the batch resident as upload() of the rows cut from it would leave
+        it.  Returns dict(n, max_len, stride, status, bad_at, recs): recs is the gm_text_rec table (TEXT_REC_DTYPE), None without want_recs"""
+        text = bytes(text)
+        buf = np.frombuffer(text + b"\0", np.uint8)
+        _chk(lib().gm_batch_set_read_format(self.h, GM_READS_FASTQ))
+        info = gm_text_info()
+        cap = max(len(text) // 64, 64)
+        while True:
+            recs = np.zeros(cap, TEXT_REC_DTYPE) if want_recs else None
+            rc = lib().gm_batch_upload_text(self.h, C.byref(params.c), buf.ctypes.data, len(text), C.byref(info), recs.ctypes.data if want_recs else None, cap, stream)
+            if rc == GM_E_CAPACITY:
+                cap = int(info.n)
+                continue
+            _chk(rc)
+            break
+        self.n = int(info.n); self.stride = int(info.stride); self._keep = None
+        return dict(n=self.n, max_len=int(info.max_len), stride=self.stride, status=int(info.status), bad_at=int(info.bad_at),
+                    recs=recs[:self.n] if want_recs else None)
+
+    def map_text(self, params, stream=None, mcap=None, pcap=None):
+        """gm_map_batch_text: map() for the block upload_text left resident; the same dict.  mcap / pcap: first capacities to try (the call
+        is repeated with the sizes GM_E_CAPACITY reports; self.map_calls counts the calls)"""
+        n = self.n
+        status = np.zeros(n, np.int8); self_score = np.zeros(n, np.float32); top = np.zeros(n, np.float64); den = np.zeros(n, np.float64)
+        mbegin = np.zeros(n + 1, np.uint64)
+        mcap = 4 * n + 64 if mcap is None else int(mcap); pcap = 8 * n + 64 if pcap is None else int(pcap)
+        r = gm_reads(); r.n = n; r.stride = self.stride
+        self.map_calls = 0
+        while True:
+            matches = np.zeros(max(mcap, 1), MATCH_DTYPE); positions = np.zeros(max(pcap, 1), POS_DTYPE)
+            h = gm_hits()
+            h.n = n; h.status = status.ctypes.data; h.self_score = self_score.ctypes.data; h.top_score = top.ctypes.data
+            h.denominator = den.ctypes.data; h.match_begin = mbegin.ctypes.data
+            h.matches = matches.ctypes.data; h.matches_cap = mcap; h.positions = positions.ctypes.data; h.positions_cap = pcap
+            rc = lib().gm_map_batch_text(self.index.h, C.byref(params.c), self.h, C.byref(h), stream)
+            self.map_calls += 1
+            if rc == GM_E_CAPACITY:
+                mcap, pcap = int(h.matches_cap), int(h.positions_cap)
+                continue
+            _chk(rc)
+            break
+        return dict(status=status, self_score=self_score, top_score=top, denominator=den, match_begin=mbegin,
+                    matches=matches[:int(mbegin[n])], positions=positions, _struct=h, _reads=r)
+
+    def output_text_resident(self, params, res, stream=None, text_cap=None):
+        """gm_output_batch_text_resident on the result of map_text(): (SAM rows as bytes, row offsets [n_recs + 1]); names and quality tails
+        are the ones upload_text left on the device.  text_cap as in output_text"""
+        tcap = int(text_cap) if text_cap is not None else self.n * (2 * self.stride + 160) + 1024
+        rcap = 2 * self.n + 64
+        self.text_calls = 0
+        while True:
+            text = np.zeros(max(tcap, 1), np.uint8); row_off = np.zeros(rcap, np.uint64)
+            st = gm_sam_text()
+            st.text = text.ctypes.data; st.text_cap = tcap; st.row_off = row_off.ctypes.data; st.row_cap = rcap
+            rc = lib().gm_output_batch_text_resident(self.index.h, C.byref(params.c), self.h, C.byref(res["_struct"]), C.byref(st), stream)
+            self.text_calls += 1
+            if rc == GM_E_CAPACITY:
+                tcap, rcap = max(tcap, int(st.text_cap)), max(rcap, int(st.row_cap))
+                continue
+            _chk(rc)
+            break
+        return text[:st.text_len].tobytes(), row_off[:st.n_recs + 1].copy()
 
     def map_device(self, params, stream=None):
         _chk(lib().gm_map_batch_device(self.index.h, C.byref(params.c), self.h, stream))

@@ -57,7 +57,12 @@ struct gm_batch {
         pair_fb, pair_list,             // k_vote_pair: the reads it leaves to k_vote_bucket (one byte each), their list + its counter
         snp_scratch, snp_hmm,           // --snp: forward matrices of a chunk of kept sequences, their 5 floats per window position
         t_names, t_nameoff, t_qtail, t_qtailoff, t_slots, t_rowlen, t_rowoff, t_text, t_bad,     // gm_output_batch_text: the block's names, tails and row offsets, the text
-        full_len, d_adaptor;            // -A: the lengths as uploaded (`len` then holds what k_adaptor_trim keeps), the adaptor's characters
+        full_len, d_adaptor,            // -A: the lengths as uploaded (`len` then holds what k_adaptor_trim keeps), the adaptor's characters
+        rt_text, rt_tilecnt, rt_tileoff, rt_lineat, rt_lsum, rt_lin, rt_recs, rt_nlen, rt_tlen, rt_meta;      // gm_batch_upload_text: the FASTQ text and what k_rt_* make of it
+    bool text_block = false;            // the block that is resident was cut from text by gm_batch_upload_text: t_names / t_qtail hold its names and tails
+    bool text_pools = false;            // ... and still do (gm_output_batch_text with a caller's gm_read_text overwrites them)
+    uint64_t text_name_bytes = 0, text_tail_bytes = 0;
+    PinBuf h_rt;                        // its read-backs
     std::string adaptor;                // gm_batch_set_adaptor; empty = none (no launch, no copy, no wait in gm_batch_upload)
     int read_format = GM_READS_FASTQ;   // gm_batch_set_read_format: the blocks uploaded from now on
     bool fasta = false;                 // the block that is resident was uploaded as FASTA (GmDevBatch::fasta)
@@ -546,9 +551,10 @@ extern "C" void gm_batch_destroy(gm_batch* b) {
                       &b->g_sorted, &b->g_ord, &b->g_lead, &b->g_krank, &b->g_khash, &b->g_nmatch, &b->g_mbegin, &b->g_multi, &b->g_big, &b->g_bigdone, &b->g_sk0, &b->g_sk1, &b->g_si0, &b->g_si1, &b->g_matches, &b->g_mhit, &b->g_positions,
                       &b->scan_tmp, &b->o_small, &b->o_posmatch, &b->o_post, &b->o_mapq, &b->o_emit, &b->o_reccnt, &b->o_cigcnt, &b->o_cigall, &b->o_recoff, &b->o_cigoff,
                       &b->o_recs, &b->o_pool, &b->o_codes, &b->snp_scratch, &b->snp_hmm, &b->pair_fb, &b->pair_list,
-                      &b->t_names, &b->t_nameoff, &b->t_qtail, &b->t_qtailoff, &b->t_slots, &b->t_rowlen, &b->t_rowoff, &b->t_text, &b->t_bad, &b->full_len, &b->d_adaptor };
+                      &b->t_names, &b->t_nameoff, &b->t_qtail, &b->t_qtailoff, &b->t_slots, &b->t_rowlen, &b->t_rowoff, &b->t_text, &b->t_bad, &b->full_len, &b->d_adaptor,
+                      &b->rt_text, &b->rt_tilecnt, &b->rt_tileoff, &b->rt_lineat, &b->rt_lsum, &b->rt_lin, &b->rt_recs, &b->rt_nlen, &b->rt_tlen, &b->rt_meta };
     for (DevBuf* d : all) d->release();
-    PinBuf* pins[] = { &b->h_top, &b->h_hbegin, &b->h_ord, &b->h_post, &b->h_mapq, &b->h_emit, &b->h_mhit, &b->h_stat };
+    PinBuf* pins[] = { &b->h_top, &b->h_hbegin, &b->h_ord, &b->h_post, &b->h_mapq, &b->h_emit, &b->h_mhit, &b->h_stat, &b->h_rt };
     for (PinBuf* d : pins) d->release();
     for (int i = 0; i < gm_batch::NS; ++i) { if (b->sub_streams[i]) (void)hipStreamDestroy(b->sub_streams[i]); b->sub_gk[i].release(); b->sub_gv[i].release(); }
     if (b->sub_ready) (void)hipEventDestroy(b->sub_ready);
@@ -604,7 +610,7 @@ extern "C" int gm_batch_upload(gm_batch* b, const gm_params* p, const gm_reads* 
     HIPCHK(hipSetDevice(b->ix->device));
     hipStream_t st = S_(stream);
     b->n = r->n; b->stride = r->stride; b->mapped = false; b->cache_hits = b->cache_matches = 0; b->resume_ptr = nullptr; b->stamp = 0;
-    b->fasta = fasta;
+    b->fasta = fasta; b->text_block = b->text_pools = false;
     size_t bytes = (size_t)r->n * r->stride;
     if (b->bases.ensure(bytes + 16) || (!fasta && b->quals.ensure(bytes + 16)) || b->len.ensure((size_t)r->n * 2 + 16)) return GM_E_NOMEM;
     b->len_host.assign(r->len, r->len + r->n);
@@ -653,6 +659,122 @@ extern "C" int gm_batch_upload(gm_batch* b, const gm_params* p, const gm_reads* 
     int rc = ensure_batch_buffers(b, p);
     if (rc) return rc;
     fill_dev_batch(b);
+    return GM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// gm_batch_upload_text = gm_batch_upload for reads that are still FASTQ text: the text goes up as it stands and the kernels of
+// gm_readtext.hip cut it into the rows, lengths, names and quality tails the other kernels read.  Two small waits: the number of
+// lines (sizes the line and record tables), then n / longest read / first bad record / byte sums together with the lengths (size the
+// rows and the pools).  With -A or --illumina one more, for what the trim kept and the fallback index.
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(gm_text_rec) == sizeof(GmDevTextRec) && offsetof(gm_text_rec, name_off) == offsetof(GmDevTextRec, name_off) &&
+              offsetof(gm_text_rec, seq_off) == offsetof(GmDevTextRec, seq_off) && offsetof(gm_text_rec, qual_off) == offsetof(GmDevTextRec, qual_off) &&
+              offsetof(gm_text_rec, name_len) == offsetof(GmDevTextRec, name_len) && offsetof(gm_text_rec, seq_len) == offsetof(GmDevTextRec, seq_len) &&
+              offsetof(gm_text_rec, qual_len) == offsetof(GmDevTextRec, qual_len), "gm_text_rec layout");
+
+extern "C" int gm_batch_upload_text(gm_batch* b, const gm_params* p, const char* text, uint64_t bytes, gm_text_info* info, gm_text_rec* recs, uint64_t recs_cap,
+                                    void* stream) {
+    if (!b) { gm_set_error("gm_batch_upload_text: batch is NULL"); return GM_E_ARG; }
+    if (b->ix->host_only) { gm_set_error("gm_batch_upload_text: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!p || !p->finalized || !info || (bytes && !text)) { gm_set_error("gm_batch_upload_text: params (finalized), info and text must not be NULL"); return GM_E_ARG; }
+    memset(info, 0, sizeof *info);
+    if (b->read_format == GM_READS_FASTA) { gm_set_error("gm_batch_upload_text: the batch is set to GM_READS_FASTA; FASTQ text only"); return GM_E_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(b->ix->device));
+    hipStream_t st = S_(stream);
+    // until the end of this call nothing is resident
+    b->n = 0; b->mapped = false; b->cache_hits = b->cache_matches = 0; b->resume_ptr = nullptr; b->stamp = 0; b->fasta = false;
+    b->text_block = b->text_pools = false; b->text_name_bytes = b->text_tail_bytes = 0; b->len_host.clear(); b->len_max = b->len_min = 0; b->illumina_until = 0;
+    if (bytes >= (1ull << 32)) {
+        gm_set_error("gm_batch_upload_text: " + std::to_string(bytes) + " bytes of text; the limit is bytes < 2^32 per call (offsets are 32 bits): cut the text at a record start");
+        return GM_E_ARG;
+    }
+    const bool adaptor = !b->adaptor.empty();
+    uint32_t n = 0, maxlen = 0, minlen = 0;
+    GmDevReadText t{};
+    if (bytes) {
+        if (b->h_rt.ensure((RT_META_N_WORDS + 2) * 8)) return GM_E_NOMEM;
+        unsigned long long* const hm = b->h_rt.as<unsigned long long>();
+        t.n_tiles = gmk_readtext_tiles(bytes);
+        if (b->rt_text.ensure((size_t)bytes + 64) || b->rt_tilecnt.ensure((size_t)t.n_tiles * 4) || b->rt_tileoff.ensure(((size_t)t.n_tiles + 1) * 4) ||
+            b->rt_meta.ensure(RT_META_N_WORDS * 8)) return GM_E_NOMEM;
+        t.text = b->rt_text.as<uint8_t>(); t.bytes = bytes; t.tile_cnt = b->rt_tilecnt.as<uint32_t>(); t.tile_off = b->rt_tileoff.as<uint32_t>();
+        t.meta = b->rt_meta.as<unsigned long long>();
+        for (int i = 0; i < RT_META_N_WORDS; ++i) hm[i] = 0ull;
+        hm[RT_META_BAD] = ~0ull; hm[RT_META_MINLEN] = ~0ull;
+        HIPCHK(hipMemcpyAsync(b->rt_meta.p, hm, RT_META_N_WORDS * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b->rt_text.p, text, (size_t)bytes, hipMemcpyHostToDevice, st));
+        KCHK(gmk_readtext_count(t, st));
+        HIPCHK(hipMemcpyAsync(&hm[RT_META_N_WORDS], t.meta + RT_META_LINES, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const unsigned long long lines = hm[RT_META_N_WORDS];
+        if (lines == 0 || lines > bytes) { gm_set_error("internal: gm_batch_upload_text counted " + std::to_string(lines) + " lines in " + std::to_string(bytes) + " bytes"); return GM_E_HIP; }
+        t.n_lines = (uint32_t)lines; t.n_ltiles = gmk_readtext_line_tiles(lines); t.rec_cap = (uint32_t)(lines / 4 + 1);
+        DevBuf& len_as_read = adaptor ? b->full_len : b->len;       // with -A the lengths as they stand in the text go to full_len, as in gm_batch_upload
+        if (b->rt_lineat.ensure((size_t)lines * 4) || b->rt_lsum.ensure((size_t)t.n_ltiles * 32) || b->rt_lin.ensure((size_t)t.n_ltiles * 8) ||
+            b->rt_recs.ensure((size_t)t.rec_cap * sizeof(GmDevTextRec)) || len_as_read.ensure((size_t)t.rec_cap * 2 + 16) ||
+            b->rt_nlen.ensure((size_t)t.rec_cap * 4) || b->rt_tlen.ensure((size_t)t.rec_cap * 4)) return GM_E_NOMEM;
+        t.line_at = b->rt_lineat.as<uint32_t>(); t.ltile_sum = b->rt_lsum.as<uint32_t>(); t.ltile_in = b->rt_lin.as<uint32_t>();
+        t.recs = b->rt_recs.as<GmDevTextRec>(); t.len = len_as_read.as<uint16_t>(); t.name_len = b->rt_nlen.as<uint32_t>(); t.tail_len = b->rt_tlen.as<uint32_t>();
+        KCHK(gmk_readtext_records(t, st));
+        b->len_host.resize(t.rec_cap);
+        HIPCHK(hipMemcpyAsync(hm, t.meta, RT_META_N_WORDS * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(b->len_host.data(), t.len, (size_t)t.rec_cap * 2, hipMemcpyDeviceToHost, st));     // n is not known yet: the table's bound, n x 2 bytes for a well-formed text
+        HIPCHK(hipStreamSynchronize(st));
+        const unsigned long long all = hm[RT_META_RECS], nn = hm[RT_META_N];
+        if (nn > all || all > t.rec_cap) { b->len_host.clear(); gm_set_error("internal: gm_batch_upload_text found more records than four lines each allow"); return GM_E_HIP; }
+        n = (uint32_t)nn;
+        info->n = n;
+        if (nn < all) { info->status = (hm[RT_META_BAD] & 3ull) == RT_BAD_LONG ? GM_TEXT_TOO_LONG : GM_TEXT_MALFORMED; info->bad_at = hm[RT_META_BAD_AT]; }
+        if (n) { maxlen = (uint32_t)hm[RT_META_MAXLEN]; minlen = (uint32_t)hm[RT_META_MINLEN]; }
+        b->text_name_bytes = hm[RT_META_NAME_BYTES]; b->text_tail_bytes = hm[RT_META_TAIL_BYTES];
+        b->len_host.resize(n);
+    }
+    info->max_len = maxlen; info->stride = std::max<uint32_t>(8u, (maxlen + 7u) & ~7u);
+    if (n > b->max_reads) {
+        b->len_host.clear();
+        gm_set_error("gm_batch_upload_text: " + std::to_string(n) + " records in the text; the limit is gm_batch_create's max_reads = " + std::to_string(b->max_reads));
+        return GM_E_ARG;
+    }
+    if (recs && n > recs_cap) { b->len_host.clear(); gm_set_error("gm_batch_upload_text: recs has room for fewer records than the text holds"); return GM_E_CAPACITY; }
+    const uint32_t stride = info->stride;
+    if (n) {
+        const size_t row_bytes = (size_t)n * stride;
+        unsigned long long* const hm = b->h_rt.as<unsigned long long>();
+        if (b->bases.ensure(row_bytes + 16) || b->quals.ensure(row_bytes + 16) || b->len.ensure((size_t)n * 2 + 16) || b->t_names.ensure((size_t)b->text_name_bytes + 16) ||
+            b->t_nameoff.ensure(((size_t)n + 1) * 8) || b->t_qtail.ensure((size_t)b->text_tail_bytes + 16) || b->t_qtailoff.ensure(((size_t)n + 1) * 8) ||
+            b->scan_tmp.ensure(((size_t)n / 1024 + 8) * 8)) return GM_E_NOMEM;
+        KCHK(gmk_scan_u32(t.name_len, n, b->t_nameoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
+        KCHK(gmk_scan_u32(t.tail_len, n, b->t_qtailoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
+        KCHK(gmk_readtext_rows(t, n, stride, b->bases.as<uint8_t>(), b->quals.as<uint8_t>(), st));
+        KCHK(gmk_readtext_names(t, n, b->t_names.as<char>(), b->t_nameoff.as<uint64_t>(), b->t_qtail.as<char>(), b->t_qtailoff.as<uint64_t>(), st));
+        if (recs) HIPCHK(hipMemcpyAsync(recs, t.recs, (size_t)n * sizeof(gm_text_rec), hipMemcpyDeviceToHost, st));
+        if (adaptor) {                                             // as gm_batch_upload: `len` takes what FixReads2 keeps, the host's copy follows
+            if (b->d_adaptor.ensure(GM_ADAPTOR_MAX)) return GM_E_NOMEM;
+            if (b->adaptor_dirty) { HIPCHK(hipMemcpyAsync(b->d_adaptor.p, b->adaptor.data(), b->adaptor.size(), hipMemcpyHostToDevice, st)); b->adaptor_dirty = false; }
+            KCHK(gmk_adaptor_trim(b->bases.as<uint8_t>(), stride, b->full_len.as<uint16_t>(), n, b->d_adaptor.as<uint8_t>(), (uint32_t)b->adaptor.size(), b->len.as<uint16_t>(), st));
+            HIPCHK(hipMemcpyAsync(b->len_host.data(), b->len.p, (size_t)n * 2, hipMemcpyDeviceToHost, st));
+        }
+        uint32_t* const h_until = reinterpret_cast<uint32_t*>(&hm[RT_META_N_WORDS + 1]);
+        uint32_t* const d_until = reinterpret_cast<uint32_t*>(t.meta + RT_META_N_WORDS - 1);
+        if (p->illumina) {                                         // the smallest read with a quality below '@' in what is kept of it (SeqReader.cpp:1152-1180)
+            *h_until = n;
+            HIPCHK(hipMemcpyAsync(d_until, h_until, 4, hipMemcpyHostToDevice, st));
+            KCHK(gmk_readtext_illumina(b->quals.as<uint8_t>(), stride, b->len.as<uint16_t>(), n, d_until, st));
+            HIPCHK(hipMemcpyAsync(h_until, d_until, 4, hipMemcpyDeviceToHost, st));
+        }
+        if (recs || adaptor || p->illumina) HIPCHK(hipStreamSynchronize(st));
+        if (p->illumina) b->illumina_until = *h_until;
+        if (adaptor) {
+            maxlen = 0; minlen = 0xFFFFFFFFu;
+            for (uint32_t i = 0; i < n; ++i) { maxlen = std::max<uint32_t>(maxlen, b->len_host[i]); minlen = std::min<uint32_t>(minlen, b->len_host[i]); }
+        }
+    }
+    b->n = n; b->stride = stride; b->len_max = maxlen; b->len_min = minlen;
+    const int rc = ensure_batch_buffers(b, p);
+    if (rc) { b->n = 0; b->len_host.clear(); return rc; }
+    fill_dev_batch(b);
+    b->text_block = b->text_pools = true;
     return GM_OK;
 }
 
@@ -1411,6 +1533,8 @@ static_assert(sizeof(gm_sam_rec) == sizeof(GmDevSamRec) && offsetof(gm_sam_rec, 
 // gm_pos records in HBM.  Host: ONE flat fp64 pass, denominator += exp(score) in the reference's order (glibc exp, the
 // order-dependent part that has to stay bit-identical to the CPU program).
 // ------------------------------------------------------------------------------------------------
+static int map_batch_rest(gm_index* ix, const gm_params* p, gm_batch* b, gm_hits* out, hipStream_t st, bool resume, const void* resume_key, PhaseClock& pc);
+
 extern "C" int gm_map_batch(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, gm_hits* out, void* stream) {
     if (!ix || !p || !b || !reads || !out) return GM_E_ARG;
     out->stamp = 0;                                            // every return path that does not leave a resident result leaves "none"
@@ -1432,6 +1556,35 @@ extern "C" int gm_map_batch(gm_index* ix, const gm_params* p, gm_batch* b, const
         rc = gm_map_batch_device(ix, p, b, stream);
         if (rc) return rc;
     } else HIPCHK(hipSetDevice(ix->device));
+    return map_batch_rest(ix, p, b, out, st, resume, (const void*)reads->bases, pc);
+}
+
+// gm_map_batch for the block gm_batch_upload_text left resident.  The resume after GM_E_CAPACITY is keyed on the batch holding that text
+// block (there is no gm_reads whose pointer could name it): the key is the address of the batch's own flag, which no caller's
+// gm_reads.bases can be
+extern "C" int gm_map_batch_text(gm_index* ix, const gm_params* p, gm_batch* b, gm_hits* out, void* stream) {
+    if (!ix) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("gm_map_batch_text: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!p || !b || !out) return GM_E_ARG;
+    out->stamp = 0;
+    if (!b->text_block) { gm_set_error("gm_map_batch_text: the batch holds no block from gm_batch_upload_text"); return GM_E_ARG; }
+    PhaseClock pc("gm_map_batch_text");
+    {
+        const uint32_t test_max = (uint32_t)gm_opt_ll("GM_TEST_MAX_BLOCK", 0);
+        if (test_max && b->n > test_max) { gm_set_error("GM_TEST_MAX_BLOCK: block treated as too large"); return GM_E_BATCH_TOO_LARGE; }
+    }
+    const void* const key = (const void*)&b->text_block;
+    const bool resume = b->resume_ptr == key;
+    b->resume_ptr = nullptr;
+    if (!resume) {
+        const int rc = gm_map_batch_device(ix, p, b, stream);
+        if (rc) return rc;
+    } else HIPCHK(hipSetDevice(ix->device));
+    return map_batch_rest(ix, p, b, out, S_(stream), resume, key, pc);
+}
+
+// everything of gm_map_batch behind the upload and the mapping kernels: grouping, the copies to the host, the fp64 pass
+static int map_batch_rest(gm_index* ix, const gm_params* p, gm_batch* b, gm_hits* out, hipStream_t st, bool resume, const void* resume_key, PhaseClock& pc) {
     const uint32_t n = b->n;
     out->n = n;
     if (n == 0) { out->match_begin[0] = 0; return GM_OK; }
@@ -1486,7 +1639,7 @@ extern "C" int gm_map_batch(gm_index* ix, const gm_params* p, gm_batch* b, const
     if (n_m > out->matches_cap || n_hits > out->positions_cap) {
         out->matches_cap = n_m; out->positions_cap = n_hits;
         gm_set_error("output buffers too small");
-        b->resume_ptr = (const void*)reads->bases;               // the repeated call only copies
+        b->resume_ptr = resume_key;                              // the repeated call only copies
         return GM_E_CAPACITY;
     }
     if (n_m) HIPCHK(hipMemcpyAsync(out->matches, g.matches, (size_t)n_m * sizeof(gm_match), hipMemcpyDeviceToHost, st));
@@ -1542,8 +1695,10 @@ extern "C" int gm_map_batch(gm_index* ix, const gm_params* p, gm_batch* b, const
 // rows, coverage deposit (+ the per-nucleotide track of -b / -d).  Nothing per read is done on the host beyond that pass.
 // ------------------------------------------------------------------------------------------------
 // `out` (records + CIGAR pool to the host: gm_output_batch) or `rt` + `tout` (finished SAM text: gm_output_batch_text), never both
+// rt == null with tout: names and tails are the ones gm_batch_upload_text left in t_names / t_qtail (gm_output_batch_text_resident)
 static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_hits* hits, gm_sam_out* out, const gm_read_text* rt,
                              gm_sam_text* tout, void* stream) {
+    const bool pools = tout && !rt;
     if (hits->n != b->n || reads->n != b->n) { gm_set_error("hits / reads do not belong to the batch"); return GM_E_ARG; }
     PhaseClock pc(tout ? "gm_output_batch_text" : "gm_output_batch");
     gm_sam_out no_host_records{};              // text form: the records and the CIGAR pool stay in HBM
@@ -1552,11 +1707,11 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
         tout->text_len = 0; tout->n_recs = 0;
         if (tout->row_off && tout->row_cap) tout->row_off[0] = 0;
         const uint32_t n = hits->n;
-        bool asc = rt->names && rt->name_off && (rt->qual_tail != nullptr) == (rt->qual_tail_off != nullptr);
-        for (uint32_t i = 0; asc && i < n; ++i) asc = rt->name_off[i] <= rt->name_off[i + 1] && (!rt->qual_tail_off || rt->qual_tail_off[i] <= rt->qual_tail_off[i + 1]);
+        bool asc = pools || (rt->names && rt->name_off && (rt->qual_tail != nullptr) == (rt->qual_tail_off != nullptr));
+        for (uint32_t i = 0; !pools && asc && i < n; ++i) asc = rt->name_off[i] <= rt->name_off[i + 1] && (!rt->qual_tail_off || rt->qual_tail_off[i] <= rt->qual_tail_off[i + 1]);
         if (!asc) { gm_set_error("gm_read_text: names / name_off missing, qual_tail without qual_tail_off (or the reverse), or offsets that do not ascend"); return GM_E_ARG; }
         // a FASTA record has no quality line: QUAL is str2qual's string, one character per base, and nothing can follow it
-        if (b->fasta && rt->qual_tail_off) { gm_set_error("gm_read_text: qual_tail / qual_tail_off must be NULL for a FASTA block (its QUAL is synthesised, one character per base)"); return GM_E_ARG; }
+        if (!pools && b->fasta && rt->qual_tail_off) { gm_set_error("gm_read_text: qual_tail / qual_tail_off must be NULL for a FASTA block (its QUAL is synthesised, one character per base)"); return GM_E_ARG; }
     }
     HIPCHK(hipSetDevice(ix->device));
     hipStream_t st = S_(stream);
@@ -1699,23 +1854,27 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
         tout->n_recs = n_recs;
         if (n_recs) {
             if (const int rc = index_cnames(ix)) return rc;                // contig names, once per index
-            const uint64_t name_bytes = rt->name_off[n] - rt->name_off[0], tail_bytes = rt->qual_tail_off ? rt->qual_tail_off[n] - rt->qual_tail_off[0] : 0;
-            if (b->t_names.ensure((size_t)name_bytes + 16) || b->t_nameoff.ensure(((size_t)n + 1) * 8) || b->t_slots.ensure((size_t)n_recs * 64) ||
+            // the pools of a text block start at offset 0 and are in place; a block without a quality tail passes none, as a caller would
+            const bool tails = pools ? b->text_tail_bytes != 0 : rt->qual_tail_off != nullptr;
+            const uint64_t name0 = pools ? 0 : rt->name_off[0], tail0 = pools || !tails ? 0 : rt->qual_tail_off[0];
+            const uint64_t name_bytes = pools ? 0 : rt->name_off[n] - name0, tail_bytes = pools || !tails ? 0 : rt->qual_tail_off[n] - tail0;
+            if ((!pools && (b->t_names.ensure((size_t)name_bytes + 16) || b->t_nameoff.ensure(((size_t)n + 1) * 8))) || b->t_slots.ensure((size_t)n_recs * 64) ||
                 b->t_rowlen.ensure((size_t)n_recs * 4) || b->t_rowoff.ensure(((size_t)n_recs + 1) * 8) || b->t_bad.ensure(8) ||
                 b->scan_tmp.ensure(((size_t)n_recs / 1024 + 8) * 8) ||
-                (rt->qual_tail_off && (b->t_qtail.ensure((size_t)tail_bytes + 16) || b->t_qtailoff.ensure(((size_t)n + 1) * 8)))) return GM_E_NOMEM;
+                (!pools && tails && (b->t_qtail.ensure((size_t)tail_bytes + 16) || b->t_qtailoff.ensure(((size_t)n + 1) * 8)))) return GM_E_NOMEM;
+            if (!pools) b->text_pools = false;                             // the caller's names take the place of the parse's
             // the offsets are used as they are: the kernels index names - name_off[0] so that a caller may pass a window of a larger pool
             if (name_bytes) HIPCHK(hipMemcpyAsync(b->t_names.p, rt->names + rt->name_off[0], (size_t)name_bytes, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(b->t_nameoff.p, rt->name_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-            if (rt->qual_tail_off) {
+            if (!pools) HIPCHK(hipMemcpyAsync(b->t_nameoff.p, rt->name_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+            if (!pools && tails) {
                 if (tail_bytes) HIPCHK(hipMemcpyAsync(b->t_qtail.p, rt->qual_tail + rt->qual_tail_off[0], (size_t)tail_bytes, hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(b->t_qtailoff.p, rt->qual_tail_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
             }
             HIPCHK(hipMemsetAsync(b->t_bad.p, 0xFF, 8, st));
             GmDevText t{};
             t.recs = b->o_recs.as<GmDevSamRec>(); t.n_recs = n_recs; t.pool = b->o_pool.as<char>();
-            t.names = b->t_names.as<char>() - rt->name_off[0]; t.name_off = b->t_nameoff.as<uint64_t>();
-            t.qtail = rt->qual_tail_off ? b->t_qtail.as<char>() - rt->qual_tail_off[0] : nullptr; t.qtail_off = rt->qual_tail_off ? b->t_qtailoff.as<uint64_t>() : nullptr;
+            t.names = b->t_names.as<char>() - name0; t.name_off = b->t_nameoff.as<uint64_t>();
+            t.qtail = tails ? b->t_qtail.as<char>() - tail0 : nullptr; t.qtail_off = tails ? b->t_qtailoff.as<uint64_t>() : nullptr;
             t.cnames = ix->d_cnames.as<char>(); t.cname_off = ix->d_cname_off.as<uint32_t>();
             t.slots = b->t_slots.as<uint8_t>(); t.row_len = b->t_rowlen.as<uint32_t>(); t.row_off = b->t_rowoff.as<uint64_t>();
             t.inv_adjust = 1.0 / p->adjust; t.bad = b->t_bad.as<unsigned long long>();
@@ -1791,6 +1950,52 @@ extern "C" int gm_output_batch_text(gm_index* ix, const gm_params* p, gm_batch* 
     if (!out->text && out->text_cap) { gm_set_error("gm_sam_text: text is NULL"); return GM_E_ARG; }
     return output_batch_impl(ix, p, b, reads, hits, nullptr, rt, out, stream);
 }
+
+extern "C" int gm_output_batch_text_resident(gm_index* ix, const gm_params* p, gm_batch* b, const gm_hits* hits, gm_sam_text* out, void* stream) {
+    if (!ix) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("gm_output_batch_text_resident: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!p || !b || !hits || !out) return GM_E_ARG;
+    if (!b->text_block || !b->text_pools) { gm_set_error("gm_output_batch_text_resident: the batch holds no names from gm_batch_upload_text"); return GM_E_ARG; }
+    if (!out->text && out->text_cap) { gm_set_error("gm_sam_text: text is NULL"); return GM_E_ARG; }
+    gm_reads reads{};
+    reads.n = b->n; reads.stride = b->stride;
+    return output_batch_impl(ix, p, b, &reads, hits, nullptr, nullptr, out, stream);
+}
+
+// gm_batch_upload_text on a batch of its own, the rows brought back (unit level, parity tests)
+extern "C" int gm_dev_fastq_rows(gm_index* ix, const char* text, uint64_t bytes, gm_text_info* info, gm_text_rec* recs, uint8_t* bases, uint8_t* quals, uint16_t* len,
+                                 uint64_t rows_cap) {
+    if (!ix) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("gm_dev_fastq_rows: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!info || (bytes && !text)) return GM_E_ARG;
+    gm_params p;
+    gm_params_default(&p);
+    int rc = gm_params_finalize(&p);
+    if (rc) return rc;
+    gm_batch* b = nullptr;
+    rc = gm_batch_create(ix, 16000000u, 2048, &b);
+    if (rc) return rc;
+    auto run = [&]() -> int {
+        int r = gm_batch_upload_text(b, &p, text, bytes, info, nullptr, 0, nullptr);
+        if (r) return r;
+        const uint32_t n = b->n;
+        if (n > rows_cap) { gm_set_error("gm_dev_fastq_rows: room for fewer reads than the text holds"); return GM_E_CAPACITY; }
+        if (n == 0) return GM_OK;
+        const size_t row_bytes = (size_t)n * b->stride;
+        if (recs) HIPCHK(hipMemcpy(recs, b->rt_recs.p, (size_t)n * sizeof(gm_text_rec), hipMemcpyDeviceToHost));
+        if (bases) HIPCHK(hipMemcpy(bases, b->bases.p, row_bytes, hipMemcpyDeviceToHost));
+        if (quals) HIPCHK(hipMemcpy(quals, b->quals.p, row_bytes, hipMemcpyDeviceToHost));
+        if (len) memcpy(len, b->len_host.data(), (size_t)n * 2);
+        return GM_OK;
+    };
+    rc = run();
+    const std::string err = gm_last_error();
+    gm_batch_destroy(b);
+    if (rc) gm_set_error(err);
+    return rc;
+}
+
+extern "C" uint32_t gm_dev_fastq_tile_bytes(void) { return gmk_readtext_tile_bytes(); }
 
 // gm_put_g6_hd (gm_fmt_dev.h) on the device, one lane per value: out[i * 16 ..] holds len[i] characters (0 = outside its domain)
 static int dev_fmt_probe(gm_index* ix, const double* v, uint32_t n, char* out, uint8_t* len, int (*kernel)(const double*, uint32_t, char*, uint8_t*, void*)) {

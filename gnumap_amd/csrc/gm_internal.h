@@ -197,6 +197,28 @@ struct GmDevTrack {
     const uint8_t* code; const double* pval;                         // GM_TRACK_CALLS: k_snp_call's code byte and p-value of bin lo + i at [i]
 };
 
+// gm_text_rec (layout asserted in gm_api.cpp): where the name (behind '@'), the sequence line and the quality line of a read lie in the text
+struct GmDevTextRec { uint32_t name_off, seq_off, qual_off, name_len, seq_len, qual_len; };
+// what the FASTQ text kernels (k_rt_*, gm_readtext.hip) read and write
+enum { RT_META_LINES = 0,           // lines of the text
+       RT_META_END,                 // where the last line ends
+       RT_META_RECS,                // records the text starts, good or not
+       RT_META_BAD,                 // (index << 2 | RT_BAD_*) of the first record that ends the block; ~0: none (set by the caller)
+       RT_META_N, RT_META_BAD_AT,   // records of the block; offset of the name line of the record that ended it
+       RT_META_MAXLEN, RT_META_MINLEN,      // over the block's reads (MINLEN set to ~0 by the caller)
+       RT_META_NAME_BYTES, RT_META_TAIL_BYTES,
+       RT_META_N_WORDS = 16 };
+enum { RT_BAD_FORM = 0, RT_BAD_LONG = 1 };
+struct GmDevReadText {
+    const uint8_t* text; uint64_t bytes;                             // 16-byte aligned, at least 16 readable bytes behind `bytes`; bytes < 2^32
+    uint32_t* tile_cnt; uint32_t* tile_off; uint32_t n_tiles;        // newlines that start a line, per tile of text; their exclusive scan (n_tiles + 1)
+    uint32_t* line_at; uint32_t n_lines;                             // line starts (known to the host after k_rt_scan)
+    uint32_t* ltile_sum; uint32_t* ltile_in; uint32_t n_ltiles;      // per tile of lines: {map, records started when entered in phase 0 .. 3, -, -, -}; {phase entered in, records in front}
+    GmDevTextRec* recs; uint32_t rec_cap;                            // n_lines / 4 + 1: every record but the last takes four lines
+    uint16_t* len; uint32_t* name_len; uint32_t* tail_len;           // of the block's reads: sequence length, name bytes a row prints, quality bytes behind the sequence's length
+    unsigned long long* meta;                                        // RT_META_*
+};
+
 // workspace of the grouping kernels (process_hits' unique map on the device); per-hit arrays share the CSR of hit_begin
 struct GmDevGroup {
     GmRawHit* sorted;               // accepted hits of a read in the reference's processing order
@@ -321,6 +343,16 @@ int gmk_fmt_g6(const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len
 // gm_adaptor.hip: -A / --adaptor (SeqReader::FixReads2): out_len[r] = the length read r keeps; len = the lengths as uploaded, stride a multiple of 8
 int gmk_adaptor_cigar_room(const GmDevMatch* matches, uint32_t n_m, const uint16_t* full_len, uint32_t n, uint32_t* cig_all, void* stream);      // --no_nw with -A: room for "<whole length>M"
 int gmk_adaptor_trim(const uint8_t* bases, uint32_t stride, const uint16_t* len, uint32_t n, const uint8_t* adaptor, uint32_t a_len, uint16_t* out_len, void* stream);
+// gm_readtext.hip: FASTQ text -> rows.  count: newlines per tile + their scan (meta[RT_META_LINES] is read back by the caller); records: line
+// starts, phases, the record table, the block's n / lengths / byte sums (t.n_lines, t.n_ltiles, t.rec_cap set from that read-back)
+uint32_t gmk_readtext_tile_bytes();
+uint32_t gmk_readtext_tiles(uint64_t bytes);
+uint32_t gmk_readtext_line_tiles(uint64_t lines);
+int gmk_readtext_count(const GmDevReadText& t, void* stream);
+int gmk_readtext_records(const GmDevReadText& t, void* stream);
+int gmk_readtext_rows(const GmDevReadText& t, uint32_t n, uint32_t stride, uint8_t* bases, uint8_t* quals, void* stream);
+int gmk_readtext_names(const GmDevReadText& t, uint32_t n, char* names, const uint64_t* name_off, char* tails, const uint64_t* tail_off, void* stream);
+int gmk_readtext_illumina(const uint8_t* quals, uint32_t stride, const uint16_t* len, uint32_t n, uint32_t* until /* set to n by the caller */, void* stream);
 int gmk_coverage_add(float* cov, uint64_t bins, uint32_t bin_size, const uint64_t* pos, const uint32_t* span, const float* w,
                      uint32_t n, uint32_t max_span, float* nuc, const uint8_t* codes, const uint64_t* code_off, void* stream);
 }

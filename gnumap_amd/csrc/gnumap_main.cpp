@@ -7,6 +7,8 @@
 // copies); per GPU `--workers` host threads (default 3, each with its own gm_batch and HIP stream) pack a block, run the
 // two batch calls and hand the records to formatter threads; SAM text is written in block order by one writer thread.
 // --sam_text=device: the library formats the rows on the GPU (gm_output_batch_text) and the formatter stage is skipped.
+// --read_text=device: a worker copies its block's byte range into a page-locked buffer and the library cuts it into reads on the GPU
+// (gm_batch_upload_text); parse_range and pack_block do not run for that block.
 // --sam_shards=K: the rows go to K files by input position, each with its own descriptor and writer; their concatenation in
 // order is the single-file SAM.
 // The number of blocks in flight is bounded by a fixed pool of Block objects.
@@ -58,6 +60,7 @@ struct Options {
     bool vcf = false;               // --vcf: with --snp, <out>.vcf beside <out>.gmp (gm_coverage_write_vcf)
     bool track_text_device = false; // --track_text=device: <out>.sgr / <out>.gmp formatted on the GPU (gm_coverage_write_*_device); host = the whole tracks come down
     int sam_shards = 1;             // --sam_shards=K: <out>.0.sam .. <out>.<K-1>.sam by input position instead of one <out>.sam
+    bool read_text_device = false;  // --read_text=device: chunk-mode blocks go up as FASTQ text and are cut into reads on the GPU (gm_batch_upload_text); host = parse_range + pack_block
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
 
@@ -97,6 +100,9 @@ static void usage(int rc, const char* msg) {
             "      --no_nw                  use k-mer hit counts instead of Needleman-Wunsch alignments\n"
             "      --fast, --print_all_sam, --illumina, --up_strand, --down_strand, --bin_size=INT\n"
             "  MI355X options: --gpus=N  --batch=N (blocks of exactly N reads)  --chunk_reads=N  --workers=N  --fmt_threads=N  --locate=sampled|full\n"
+            "      --read_text=host|device  where a block of FASTQ text becomes read rows: host threads (default) or the GPU (the text is\n"
+            "                               uploaded as it stands; same bytes out).  FASTQ only; blocks of --batch=N and --illumina runs and\n"
+            "                               what follows a malformed record are cut by the host either way\n"
             "      --sam_text=host|device   where the SAM rows become text: host formatter threads (default) or the GPU\n"
             "                               (gm_output_batch_text; same bytes, no formatter stage)\n"
             "      --track_text=host|device where <out>.sgr / <out>.gmp (eight columns, or nine with --snp_calls) become text: host threads\n"
@@ -162,6 +168,11 @@ static void parse_args(int argc, char** argv, Options& o) {
                 if (!strcmp(s + 9, "device")) o.sam_text_device = true;
                 else if (!strcmp(s + 9, "host")) o.sam_text_device = false;
                 else { fprintf(stderr, "Error: --sam_text takes host or device, not: %s\n", s + 9); exit(1); }
+            }
+            else if (starts(s, "read_text=")) {
+                if (!strcmp(s + 10, "device")) o.read_text_device = true;
+                else if (!strcmp(s + 10, "host")) o.read_text_device = false;
+                else { fprintf(stderr, "Error: --read_text takes host or device, not: %s\n", s + 10); exit(1); }
             }
             else if (starts(s, "track_text=")) {
                 if (!strcmp(s + 11, "device")) o.track_text_device = true;
@@ -298,6 +309,9 @@ struct Block {
     PinVec<char> names_pool, qtail_pool; PinVec<uint64_t> name_off, qtail_off; bool has_qtail = false;
     PinVec<char>* dtext = nullptr; uint64_t dtext_len = 0;      // from the TextPool, while the block holds rows that are not written yet
     size_t first_byte = 0;                  // where the block starts in the FASTQ text: decides its shard (--sam_shards)
+    // --read_text=device: the block was cut on the GPU (gm_batch_upload_text) and is resident in its worker's batch; trecs = where its reads lie in
+    // the text from text_lo on (page-locked; only filled for the host formatter)
+    bool text_dev = false; PinVec<gm_text_rec> trecs;
     bool failed = false;
 };
 
@@ -720,9 +734,106 @@ struct Worker {
     PinVec<gm_match> matches; PinVec<gm_pos> positions;
     uint64_t n_reads = 0, n_matched = 0, n_records = 0;
     double t_pack = 0, t_map = 0, t_out = 0, t_scan = 0;
+    TextPool* stage_pool = nullptr;         // --read_text=device: page-locked buffers a block's FASTQ text is copied into for the upload
 };
 
 static double secs_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+// --read_text=device, before the gate: the block's byte range goes up as it stands and the GPU cuts it (gm_batch_upload_text).  What the host
+// parser would have reported comes back: the records in front of the first malformed (or too long) one, and where that one starts
+static int upload_text_block(Worker& w, const Options& o, const char* base, Block& b, bool* stop, size_t* bad_at, bool* too_long) {
+    const size_t bytes = b.text_hi - b.text_lo;
+    auto c0 = std::chrono::steady_clock::now();
+    PinVec<char>* stage = w.stage_pool->get();
+    stage->ensure(bytes + 1);
+    memcpy(stage->data(), base + b.text_lo, bytes);
+    auto c1 = std::chrono::steady_clock::now();
+    const bool want_recs = !o.sam_text_device;          // the host formatter prints names, bases and qualities from the mapped file
+    if (want_recs) b.trecs.ensure(bytes / 128 + 64);
+    gm_text_info ti;
+    int rc;
+    for (;;) {
+        rc = gm_batch_upload_text(w.batch, &o.p, stage->data(), bytes, &ti, want_recs ? b.trecs.data() : nullptr, want_recs ? b.trecs.size() : 0, w.stream);
+        if (rc == GM_E_CAPACITY) { b.trecs.ensure((size_t)ti.n + 64); continue; }
+        break;
+    }
+    w.stage_pool->put(stage);
+    w.t_pack += std::chrono::duration<double>(c1 - c0).count(); w.t_map += secs_since(c1);
+    if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_batch_upload_text: %s\n", gm_last_error()); return rc; }
+    b.n = ti.n; b.maxlen = ti.max_len; b.stride = ti.stride; b.text_dev = true;
+    if (ti.status == GM_TEXT_MALFORMED) { *stop = true; *bad_at = b.text_lo + (size_t)ti.bad_at; }
+    if (ti.status == GM_TEXT_TOO_LONG) {
+        const char* nm = base + b.text_lo + (size_t)ti.bad_at;
+        const char* e = (const char*)memchr(nm, '\n', b.text_hi - (b.text_lo + (size_t)ti.bad_at));
+        const size_t nl = e ? (size_t)(e - nm) : b.text_hi - (b.text_lo + (size_t)ti.bad_at);
+        fprintf(stderr, "ERROR: read %.*s is longer than 2048 bases\n", (int)std::min<size_t>(nl, 200), nm);
+        *too_long = true;
+    }
+    return GM_OK;
+}
+
+// the block gm_batch_upload_text left resident: gm_map_batch_text, then the rows as text from the names the parse left in HBM, or the
+// records for the host formatter, which reads the block's names, bases and qualities in the mapped file through the gm_text_rec table
+static int process_text_block(Worker& w, const Options& o, const char* base, Block& b) {
+    const uint32_t n = b.n;
+    w.status.ensure(n); w.self_score.ensure(n); w.top.ensure(n); w.den.ensure(n); w.mbegin.ensure((size_t)n + 1);
+    w.matches.ensure(2 * (size_t)n + 64); w.positions.ensure(2 * (size_t)n + 64);
+    gm_hits hits{};
+    auto c1 = std::chrono::steady_clock::now();
+    for (;;) {
+        hits.n = n; hits.status = w.status.data(); hits.self_score = w.self_score.data(); hits.top_score = w.top.data();
+        hits.denominator = w.den.data(); hits.match_begin = w.mbegin.data();
+        hits.matches = w.matches.data(); hits.matches_cap = w.matches.size();
+        hits.positions = w.positions.data(); hits.positions_cap = w.positions.size();
+        int rc = gm_map_batch_text(w.ix, &o.p, w.batch, &hits, w.stream);
+        if (rc == GM_E_CAPACITY) { w.matches.ensure(hits.matches_cap + 64); w.positions.ensure(hits.positions_cap + 64); continue; }
+        if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is mapped in halves (%s)\n", n, gm_last_error()); return rc; }
+        if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_map_batch_text: %s\n", gm_last_error()); return rc; }
+        break;
+    }
+    auto c2 = std::chrono::steady_clock::now();
+    uint64_t n_recs = 0;
+    if (o.sam_text_device) {
+        if (!b.dtext) b.dtext = w.text_pool->get();
+        b.dtext->ensure(((size_t)n + (size_t)n / 16) * (2 * (size_t)b.maxlen + 64) + (b.text_hi - b.text_lo) + 4096);
+        gm_sam_text st;
+        for (;;) {
+            st.text = b.dtext->data(); st.text_cap = b.dtext->size(); st.text_len = 0; st.n_recs = 0; st.row_off = nullptr; st.row_cap = 0;
+            int rc = gm_output_batch_text_resident(w.ix, &o.p, w.batch, &hits, &st, w.stream);
+            if (rc == GM_E_CAPACITY) { b.dtext->ensure((size_t)st.text_cap + 64); continue; }
+            if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
+            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch_text_resident: %s\n", gm_last_error()); return rc; }
+            break;
+        }
+        n_recs = st.n_recs; b.dtext_len = st.text_len;
+    } else {
+        const char* t0 = base + b.text_lo;
+        b.name.resize(n); b.seq.resize(n); b.qual.resize(n); b.name_len.resize(n); b.qual_len.resize(n); b.len.resize(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            const gm_text_rec& r = b.trecs[i];
+            b.name[i] = t0 + r.name_off; b.seq[i] = t0 + r.seq_off; b.qual[i] = t0 + r.qual_off;
+            b.name_len[i] = r.name_len; b.qual_len[i] = r.qual_len; b.len[i] = (uint16_t)r.seq_len;
+        }
+        gm_reads reads{}; reads.n = n; reads.stride = b.stride;
+        b.recs.ensure((size_t)n + (size_t)n / 4 + 64);
+        b.pool.ensure(8 * (size_t)n + 1024);
+        gm_sam_out so;
+        for (;;) {
+            so.recs = b.recs.data(); so.recs_cap = b.recs.size(); so.cigar_pool = b.pool.data(); so.cigar_cap = b.pool.size();
+            int rc = gm_output_batch(w.ix, &o.p, w.batch, &reads, &hits, &so, w.stream);
+            if (rc == GM_E_CAPACITY) { b.recs.ensure(so.recs_cap + 64); b.pool.ensure(so.cigar_cap + 64); continue; }
+            if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
+            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch: %s\n", gm_last_error()); return rc; }
+            break;
+        }
+        n_recs = so.n_recs;
+    }
+    b.n_recs = n_recs; b.gpu = w.gpu;
+    w.t_map += std::chrono::duration<double>(c2 - c1).count(); w.t_out += secs_since(c2);
+    w.n_reads += n; w.n_records += n_recs;
+    for (uint32_t i = 0; i < n; ++i) w.n_matched += (w.status[i] == GM_READ_OK || w.status[i] == GM_READ_TOO_MANY);
+    return GM_OK;
+}
 
 static int process_block(Worker& w, const Options& o, Block& b) {
     const uint32_t n = b.n;
@@ -786,9 +897,16 @@ static int process_block(Worker& w, const Options& o, Block& b) {
 
 // a block whose intermediate lists outgrow one launch (GM_E_BATCH_TOO_LARGE: e.g. > 2^31 candidates on a repeat-rich reference
 // without -h) is mapped as two halves, recursively; the halves' records are put back together in read order
-static int process_block_split(Worker& w, const Options& o, Block& b, int depth) {
-    int rc = process_block(w, o, b);
+static int process_block_split(Worker& w, const Options& o, const char* base, Block& b, int depth) {
+    int rc = b.text_dev ? process_text_block(w, o, base, b) : process_block(w, o, b);
     if (rc != GM_E_BATCH_TOO_LARGE || b.n < 2 || depth > 20) return rc;
+    if (b.text_dev) {                                       // a text block that is too large: the host parser cuts the same records, and the halves go the host's way
+        size_t cur = b.text_lo, bad_at = 0; bool stop = false, too_long = false;
+        const uint32_t n_dev = b.n;
+        FastqScanner::parse_range(base, cur, b.text_hi, b, n_dev, &stop, &bad_at, &too_long);
+        b.text_dev = false;
+        if (b.n != n_dev) { fprintf(stderr, "ERROR: the host parser finds %u reads where the device found %u\n", b.n, n_dev); return GM_E_ARG; }
+    }
     const uint32_t half = b.n / 2;
     uint64_t total = 0; size_t pool_len = 0;
     std::vector<gm_sam_rec> recs; std::vector<char> pool, text;
@@ -804,7 +922,7 @@ static int process_block_split(Worker& w, const Options& o, Block& b, int depth)
             for (uint32_t i = 0; i < half && c.illumina; ++i)
                 for (uint32_t t = 0; t < (b.kept.empty() ? b.len[i] : b.kept[i]); ++t) if ((signed char)b.qual[i][t] < 64) { c.illumina = 0; break; }      // (the reference's quality characters are signed chars)
         }
-        rc = process_block_split(w, o, c, depth + 1);
+        rc = process_block_split(w, o, base, c, depth + 1);
         if (rc != GM_OK) { w.text_pool->put(c.dtext); return rc; }
         if (o.sam_text_device) {                            // rows are text already: the halves' text, one behind the other
             if (c.dtext) { text.insert(text.end(), c.dtext->data(), c.dtext->data() + c.dtext_len); w.text_pool->put(c.dtext); c.dtext = nullptr; }
@@ -850,6 +968,7 @@ int main(int argc, char** argv) {
                 return 1;
             }
             if (o.p.mode == GM_MODE_SNP) { fprintf(stderr, "ERROR: --snp with FASTA reads is not supported; use FASTQ reads\n"); return 1; }
+            if (o.read_text_device) { fprintf(stderr, "ERROR: --read_text=device cuts FASTQ only; FASTA reads are cut by the host (--read_text=host)\n"); return 1; }
             if (!fasta_check(fq.base, fq.size, o.reads.c_str())) return 1;
             o.p.illumina = 0;                                  // accepted and ignored, as in the reference
             fasta_qual_table(fasta_qual);
@@ -869,13 +988,13 @@ int main(int argc, char** argv) {
     for (int g = 0; g < o.gpus; ++g)                                   // k-mer tables / records for these parameters: part of staging the index
         if (gm_index_prepare(gpu_ix[(size_t)g], &o.p) != GM_OK) { fprintf(stderr, "ERROR: GPU %d: %s\n", g, gm_last_error()); return 1; }
     std::vector<Worker> workers((size_t)o.gpus * (size_t)o.workers);
-    TextPool text_pool;
+    TextPool text_pool, stage_pool;
     for (int g = 0; g < o.gpus; ++g) {
         if (gm_coverage_reset(gpu_ix[(size_t)g], (uint32_t)o.p.bin_size) != GM_OK ||
             (o.p.mode != GM_MODE_NORMAL && gm_coverage_enable_nuc(gpu_ix[(size_t)g]) != GM_OK)) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
         for (int k = 0; k < o.workers; ++k) {
             Worker& w = workers[(size_t)g * (size_t)o.workers + (size_t)k];
-            w.gpu = g; w.ix = gpu_ix[(size_t)g]; w.text_pool = &text_pool;
+            w.gpu = g; w.ix = gpu_ix[(size_t)g]; w.text_pool = &text_pool; w.stage_pool = &stage_pool;
             if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK ||
                 gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK ||
                 gm_batch_set_read_format(w.batch, o.fasta ? GM_READS_FASTA : GM_READS_FASTQ) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
@@ -947,7 +1066,7 @@ int main(int argc, char** argv) {
             Block* b;
             while (!failed && stop_block.load() == ~0ull && free_q.pop(b)) {
                 auto s0 = std::chrono::steady_clock::now();
-                b->lazy = false; b->malformed = false;
+                b->lazy = false; b->malformed = false; b->text_dev = false;
                 bool too_long = false;
                 b->first_byte = fq.at;
                 const bool more = chunks ? fq.next_chunk(*b, o.batch) : fq.next(*b, o.batch, &too_long);
@@ -982,9 +1101,12 @@ int main(int argc, char** argv) {
                         auto s0 = std::chrono::steady_clock::now();
                         size_t cur = b->text_lo, bad_at = npos; bool stop = false, too_long = false;
                         if (o.fasta) FastqScanner::parse_range_fasta(fq.base, cur, b->text_hi, *b, 16000000u, &too_long, fq.fasta_qual);
+                        else if (o.read_text_device && b->text_hi - b->text_lo < ((size_t)1 << 32)) {
+                            if (upload_text_block(w, o, fq.base, *b, &stop, &bad_at, &too_long) != GM_OK) { failed = 1; b->n = 0; }
+                        }
                         else FastqScanner::parse_range(fq.base, cur, b->text_hi, *b, 16000000u, &stop, &bad_at, &too_long);
                         if (too_long) failed = 1;
-                        w.t_scan += secs_since(s0);
+                        if (!b->text_dev) w.t_scan += secs_since(s0);      // (a text block's staging and upload are booked by upload_text_block)
                         bool drop;
                         {
                             std::unique_lock<std::mutex> lk(gate.mu);
@@ -999,7 +1121,7 @@ int main(int argc, char** argv) {
                         if (drop) b->n = 0;
                     }
                     if (b->n == 0) { b->n_recs = 0; fmt_q.push(b); continue; }
-                    if (!failed && process_block_split(w, o, *b, 0) != GM_OK) { failed = 1; gate.cv.notify_all(); }
+                    if (!failed && process_block_split(w, o, fq.base, *b, 0) != GM_OK) { failed = 1; gate.cv.notify_all(); }
                     if (failed) { b->failed = true; b->n_recs = 0; }
                     fmt_q.push(b);
                 }
@@ -1144,13 +1266,16 @@ int main(int argc, char** argv) {
     const double t_cov = secs_since(t_cov0);
     for (auto ix : gpu_ix) gm_index_close(ix);
     double secs = secs_since(t0);
+    const bool text_blocks = o.read_text_device && !file_order;          // the chunk-mode blocks went up as text: name the path that ran
     if (o.verbose > 0) {
+        const char* const pack = text_blocks ? "stage" : "pack";       // copying the text into a page-locked buffer takes the place of cutting and packing it
+        const char* const map = text_blocks ? "gm_map_batch_text" : "gm_map_batch";      // (with the flag it includes gm_batch_upload_text, as gm_map_batch includes its upload)
         if (o.sam_text_device)                               // no formatter stage: the rows were text when they left the library
-            fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, pack %.2f, gm_map_batch %.2f, gm_output_batch_text %.2f, write %.2f\n",
-                    t_index, t_scan, t_pack, t_map, t_out, t_write);
+            fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, %s %.2f, %s %.2f, %s %.2f, write %.2f\n",
+                    t_index, t_scan, pack, t_pack, map, t_map, text_blocks ? "gm_output_batch_text_resident" : "gm_output_batch_text", t_out, t_write);
         else
-        fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, pack %.2f, gm_map_batch %.2f, gm_output_batch %.2f, SAM format %.2f, write %.2f\n",
-                t_index, t_scan, t_pack, t_map, t_out, t_fmt, t_write);
+        fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, %s %.2f, %s %.2f, gm_output_batch %.2f, SAM format %.2f, write %.2f\n",
+                t_index, t_scan, pack, t_pack, map, t_map, t_out, t_fmt, t_write);
         fprintf(stderr, "wall seconds: index %.2f, FASTQ->SAM pipeline %.2f (%.3f M reads/s), coverage all-reduce + track file %.2f\n", t_index, t_pipe,
                 n_reads / std::max(t_pipe, 1e-9) / 1e6, t_cov);
         fprintf(stderr, "Finished: %lu reads, %lu matched, %lu SAM records, %.2f s total (%.2f s after the index was resident)\n", (unsigned long)n_reads,

@@ -22,7 +22,9 @@
  *   gm_output_batch_text             the same block loop, ending in the SAM rows as text: the print loop of
  *                                    parallel_thread_run src/Driver.cpp:2146-2217, ScoredSeq::get_SAM inc/ScoredSeq.h:293-404,
  *                                    reverse_comp / reverse_CIGAR inc/SequenceOperations.h:56-123
- *   gm_batch_set_adaptor             -A: SeqReader::FixReads2 / Compare            src/SeqReader.cpp:1146-1150, 1294-1305, 1356-1372
+ *   gm_batch_upload_text             SeqReader::get_more_fastq src/SeqReader.cpp:1023-1292 for a byte range of well-formed records
+ *                                    (gm_map_batch_text / gm_output_batch_text_resident: the two calls above for that block)
+ *   gm_batch_set_adaptor             -A: SeqReader::FixReads2 / Compare           src/SeqReader.cpp:1146-1150, 1294-1305, 1356-1372
  *   gm_coverage_*                    amount_genome, PrintFinalSGR src/GenomeBwt.cpp:1212-1273; the MPI
  *                                    Allreduce of the track src/Driver.cpp:1660-1672 (-> RCCL)
  *
@@ -304,6 +306,35 @@ int gm_output_batch(gm_index*, const gm_params*, gm_batch*, const gm_reads*, con
 int gm_output_batch_text(gm_index*, const gm_params*, gm_batch*, const gm_reads*, const gm_read_text*, const gm_hits*, gm_sam_text* out,
                          void* hip_stream);
 
+/* ---- FASTQ text in: the reads cut into rows on the device ----
+ * gm_batch_upload_text takes a byte range of FASTQ text as it stands in the file, uploads it verbatim and leaves the batch resident
+ * exactly as gm_batch_upload would have with the rows a host had cut from it (n, stride, lengths, adaptor trim, --illumina fallback
+ * index).  The rule is the chunk mode of the driver's parser: a line starts at 0 and behind every '\n' that is not the last byte; blank
+ * lines are skipped before a name line only; a record is well-formed when its four lines exist, the name starts with '@', the plus
+ * line is non-empty and starts with '+' and the sequence is no longer than the quality line.  The first record that is not (status
+ * GM_TEXT_MALFORMED), or is but has more than 2048 bases (GM_TEXT_TOO_LONG), ends the block: n counts the records before it and bad_at
+ * is the offset of its name line.  stride = max(8, max_len rounded up to 8). */
+enum { GM_TEXT_OK = 0, GM_TEXT_MALFORMED = 1, GM_TEXT_TOO_LONG = 2 };
+typedef struct {
+    uint32_t n, max_len, stride;
+    int32_t status;             /* GM_TEXT_* */
+    uint64_t bad_at;            /* with a status other than GM_TEXT_OK */
+} gm_text_info;
+/* one read: offsets from the start of the text, lengths in bytes; the name without its '@' and uncut */
+typedef struct { uint32_t name_off, seq_off, qual_off, name_len, seq_len, qual_len; } gm_text_rec;
+/* recs: NULL, or room for recs_cap records; GM_E_CAPACITY (info->n = the number needed, nothing left resident) when n exceeds it.
+ * GM_E_UNSUPPORTED for a batch set to GM_READS_FASTA.  GM_E_ARG, nothing left resident, for bytes >= 2^32 and for more records than
+ * gm_batch_create's max_reads: gm_last_error() says which.  bytes == 0: n = 0.  `text` is read until the call returns (page-locked
+ * memory from gm_host_alloc is copied at link rate).  Synchronous on hip_stream; there is no enqueue form. */
+int gm_batch_upload_text(gm_batch*, const gm_params*, const char* text, uint64_t bytes, gm_text_info* info, gm_text_rec* recs, uint64_t recs_cap,
+                         void* hip_stream);
+/* gm_map_batch for the block gm_batch_upload_text left resident: everything behind the upload, GM_E_CAPACITY resume included (repeat
+ * the call with larger buffers).  GM_E_ARG when the batch holds no such block. */
+int gm_map_batch_text(gm_index*, const gm_params*, gm_batch*, gm_hits* out, void* hip_stream);
+/* gm_output_batch_text for that block: names and quality tails are the ones the parse left in HBM.  Same capacity-first contract.
+ * (gm_output_batch works on such a block too, with a gm_reads that carries its n and stride.) */
+int gm_output_batch_text_resident(gm_index*, const gm_params*, gm_batch*, const gm_hits*, gm_sam_text* out, void* hip_stream);
+
 /* enqueue / wait forms: the call is queued on the batch's own service thread and runs there exactly as the synchronous form would;
  * the caller goes on (with another batch).  Calls queued on one batch run in order - gm_output_batch_enqueue may be queued right
  * behind the gm_map_batch_enqueue whose gm_hits it reads - and after a failing call the rest of the batch's queue is skipped.
@@ -330,6 +361,15 @@ int gm_index_set_probe_format(gm_index*, int format);
 /* SeqReader::FixReads2 / Compare (src/SeqReader.cpp:1356-1372, 1294-1305) of every read of the block against `adaptor`, on the device:
  * out_len[i] = the length read i keeps (see gm_batch_set_adaptor).  Only gm_reads.bases / len are read; NULL or "" copies len */
 int gm_dev_adaptor_trim(gm_index*, const gm_reads*, const char* adaptor, uint16_t* out_len);
+
+/* gm_batch_upload_text's parse on a text of the caller's, the rows brought back: bases / quals take info->n rows of info->stride bytes
+ * (zero padded), len and recs info->n entries.  rows_cap = the reads the four buffers have room for (each row buffer rows_cap x
+ * info->stride bytes; 2048 is the largest stride): GM_E_CAPACITY with info filled in when n exceeds it, so a first call with
+ * rows_cap = 0 sizes the second.  Any of the four may be NULL. */
+int gm_dev_fastq_rows(gm_index*, const char* text, uint64_t bytes, gm_text_info* info, gm_text_rec* recs, uint8_t* bases, uint8_t* quals, uint16_t* len,
+                      uint64_t rows_cap);
+/* text bytes one workgroup of the line pass covers (a tile): lets a test put a line start on either side of a tile edge */
+uint32_t gm_dev_fastq_tile_bytes(void);
 
 /* printf("%g") as the device prints XA / XP (gm_fmt_dev.h): out[16 i ..] holds len[i] characters, no terminator; len[i] = 0 for a
  * value outside the function's domain (0, -0, inf, nan, 2^-200 <= |v| < 2^200) */
