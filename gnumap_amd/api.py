@@ -31,6 +31,11 @@ class gm_track_text_stats(C.Structure):
     _fields_ = [("rows", u64), ("bytes", u64), ("slabs", u64), ("host_slabs", u64), ("launches", u64), ("kernel_ms", C.c_double)]
 
 
+class gm_sam_sort_stats(C.Structure):
+    _fields_ = [("rows", u64), ("text_bytes", u64), ("pieces", u64), ("piece_bytes", u64), ("add_s", C.c_double), ("sort_s", C.c_double),
+                ("gather_ms", C.c_double), ("gather_bytes", u64), ("download_s", C.c_double)]
+
+
 class gm_params(C.Structure):
     _fields_ = [("mer", C.c_int), ("jump", C.c_int), ("min_seed_hits", C.c_int), ("max_kmer_hits", C.c_uint32), ("max_matches", C.c_uint32),
                 ("max_gap", C.c_int), ("nw", C.c_int), ("fast", C.c_int), ("unique_only", C.c_int), ("pos_strand", C.c_int), ("neg_strand", C.c_int),
@@ -117,7 +122,9 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_coverage_write_gmp_calls_device", "gm_coverage_calls_text", "gm_coverage_write_vcf",
            "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim",
            "gm_batch_set_read_format", "gm_index_set_probe_format",
-           "gm_batch_upload_text", "gm_map_batch_text", "gm_output_batch_text_resident", "gm_dev_fastq_rows", "gm_dev_fastq_tile_bytes"]
+           "gm_batch_upload_text", "gm_map_batch_text", "gm_output_batch_text_resident", "gm_dev_fastq_rows", "gm_dev_fastq_tile_bytes",
+           "gm_sam_sorter_create", "gm_sam_sorter_destroy", "gm_output_batch_sorted", "gm_output_batch_sorted_resident", "gm_sam_sorter_finish",
+           "gm_sam_sorter_read", "gm_sam_sorter_stats", "gm_sam_sorter_add_rows"]
 
 
 def library_path():
@@ -209,6 +216,15 @@ def load_library():
     L.gm_output_batch_text_resident.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_hits), C.POINTER(gm_sam_text), C.c_void_p]
     L.gm_dev_fastq_rows.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(gm_text_info), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u64]
     L.gm_dev_fastq_tile_bytes.argtypes = []; L.gm_dev_fastq_tile_bytes.restype = C.c_uint32
+    L.gm_sam_sorter_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.gm_sam_sorter_destroy.argtypes = [C.c_void_p]; L.gm_sam_sorter_destroy.restype = None
+    L.gm_output_batch_sorted.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_reads), C.POINTER(gm_read_text), C.POINTER(gm_hits),
+                                         C.c_void_p, u64, C.c_void_p]
+    L.gm_output_batch_sorted_resident.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_hits), C.c_void_p, u64, C.c_void_p]
+    L.gm_sam_sorter_finish.argtypes = [C.c_void_p, C.POINTER(u64), C.POINTER(u64), C.c_void_p]
+    L.gm_sam_sorter_read.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
+    L.gm_sam_sorter_add_rows.argtypes = [C.c_void_p, u64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_void_p]
+    L.gm_sam_sorter_stats.argtypes = [C.c_void_p, C.POINTER(gm_sam_sort_stats)]
     _LIB = L
     return L
 
@@ -717,6 +733,91 @@ class Batch:
             break
         del keep
         return text[:st.text_len].tobytes(), row_off[:st.n_recs + 1].copy()
+
+
+class SamSorter:
+    """gm_sam_sorter: the SAM rows of a run kept in HBM and read back in coordinate order.  The piece size of its arena is the
+    GM_SORT_PIECE switch as it stands when the object is made."""
+
+    def __init__(self, index):
+        self.index = index
+        self.h = C.c_void_p()
+        _chk(lib().gm_sam_sorter_create(index.h, C.byref(self.h)))
+
+    def destroy(self):
+        if self.h:
+            lib().gm_sam_sorter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def add_block(self, batch, params, res, seq, names=None, qual_tails=None, stream=None):
+        """the block `batch` was mapped with (res = map() or map_text()) under sequence number seq.  names (one bytes per read, and
+        qual_tails as in Batch.output_text): gm_output_batch_sorted; names None: gm_output_batch_sorted_resident, for a block of
+        upload_text() / map_text()"""
+        if names is None:
+            _chk(lib().gm_output_batch_sorted_resident(self.index.h, C.byref(params.c), batch.h, C.byref(res["_struct"]), self.h, int(seq), stream))
+            return
+        rt, keep = _pack_read_text([bytes(x) for x in names], None if qual_tails is None else [bytes(x) for x in qual_tails], batch.n)
+        _chk(lib().gm_output_batch_sorted(self.index.h, C.byref(params.c), batch.h, C.byref(res["_reads"]), C.byref(rt), C.byref(res["_struct"]), self.h,
+                                         int(seq), stream))
+        del keep
+
+    def add_rows(self, seq, rows, contig, chr_pos, stream=None):
+        """gm_sam_sorter_add_rows: rows (list of bytes, or one uint8 array with row_off as second element of a tuple) under the caller's
+        keys; contig >= the number of contigs gives the key of a row without a contig"""
+        if isinstance(rows, tuple):
+            text, off = rows
+        else:
+            text = np.frombuffer(b"".join(rows) + b"\0", np.uint8)
+            off = np.zeros(len(rows) + 1, np.uint64); off[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
+        off = np.ascontiguousarray(off, np.uint64)
+        c = np.ascontiguousarray(contig, np.uint32); q = np.ascontiguousarray(chr_pos, np.uint64)
+        n = len(off) - 1
+        assert len(c) == n and len(q) == n
+        _chk(lib().gm_sam_sorter_add_rows(self.h, int(seq), text.ctypes.data, off.ctypes.data, c.ctypes.data, q.ctypes.data, n, stream))
+
+    def finish(self, stream=None):
+        """sorts; (rows, text bytes)"""
+        n = u64(); b = u64()
+        _chk(lib().gm_sam_sorter_finish(self.h, C.byref(n), C.byref(b), stream))
+        return int(n.value), int(b.value)
+
+    def read(self, cap, stream=None):
+        """the next whole rows that fit in cap bytes (b"" = done).  GnumapError with code GM_E_CAPACITY and .needed = the next row's length
+        when that row alone is longer than cap"""
+        buf = np.zeros(max(int(cap), 1), np.uint8); got = u64()
+        rc = lib().gm_sam_sorter_read(self.h, buf.ctypes.data, int(cap), C.byref(got), stream)
+        if rc == GM_E_CAPACITY:
+            e = GnumapError(rc, lib().gm_last_error().decode())
+            e.needed = int(got.value)
+            raise e
+        _chk(rc)
+        return buf[:got.value].tobytes()
+
+    def text(self, cap=1 << 20):
+        """every slab that is left, joined"""
+        out = []
+        while True:
+            try:
+                t = self.read(cap)
+            except GnumapError as e:
+                if e.code != GM_E_CAPACITY:
+                    raise
+                cap = e.needed
+                continue
+            if not t:
+                return b"".join(out)
+            out.append(t)
+
+    def stats(self):
+        st = gm_sam_sort_stats()
+        _chk(lib().gm_sam_sorter_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in gm_sam_sort_stats._fields_}
 
 
 def _pack_read_text(names, qual_tails, n):

@@ -1696,8 +1696,9 @@ static int map_batch_rest(gm_index* ix, const gm_params* p, gm_batch* b, gm_hits
 // ------------------------------------------------------------------------------------------------
 // `out` (records + CIGAR pool to the host: gm_output_batch) or `rt` + `tout` (finished SAM text: gm_output_batch_text), never both
 // rt == null with tout: names and tails are the ones gm_batch_upload_text left in t_names / t_qtail (gm_output_batch_text_resident)
+// sorter (with tout): the text is not downloaded - it goes into the sorter's arena under sequence number seq (gm_output_batch_sorted)
 static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_hits* hits, gm_sam_out* out, const gm_read_text* rt,
-                             gm_sam_text* tout, void* stream) {
+                             gm_sam_text* tout, void* stream, gm_sam_sorter* sorter = nullptr, uint64_t seq = 0) {
     const bool pools = tout && !rt;
     if (hits->n != b->n || reads->n != b->n) { gm_set_error("hits / reads do not belong to the batch"); return GM_E_ARG; }
     PhaseClock pc(tout ? "gm_output_batch_text" : "gm_output_batch");
@@ -1723,6 +1724,10 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
     out->n_recs = 0; out->cigar_len = 0;
     if (n_m64 == 0) return GM_OK;
     if (n_m64 > 0x7FFFFFFFull) { gm_set_error("too many matches in one batch; map the block in smaller pieces"); return GM_E_BATCH_TOO_LARGE; }
+    {   // test switch: the output stage treats a block of more reads as too large, as the two limits of this function would
+        const uint32_t test_max = (uint32_t)gm_opt_ll("GM_TEST_MAX_OUT_BLOCK", 0);
+        if (test_max && n > test_max) { gm_set_error("GM_TEST_MAX_OUT_BLOCK: block treated as too large"); return GM_E_BATCH_TOO_LARGE; }
+    }
     const uint32_t n_m = (uint32_t)n_m64;
     // ---- device, part 1: everything that does not depend on the posteriors is enqueued BEFORE the host pass and runs under it ----
     // hits->stamp names this batch's resident result: its matches / positions are used where they are.  Otherwise `hits` may have been
@@ -1894,7 +1899,7 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
             tout->text_len = text_len;
             // capacity first, as above: nothing has been deposited yet, the repeated call deposits once
             const bool rows_fit = !tout->row_off || tout->row_cap >= n_recs + 1;
-            if (text_len > tout->text_cap || !rows_fit) {
+            if (!sorter && (text_len > tout->text_cap || !rows_fit)) {
                 tout->text_cap = text_len;
                 if (tout->row_off) tout->row_cap = n_recs + 1;
                 gm_set_error("output buffers too small");
@@ -1903,8 +1908,10 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
             if (b->t_text.ensure((size_t)text_len + 16)) return GM_E_NOMEM;
             t.text = b->t_text.as<char>();
             KCHK(gmk_out_text_rows(b->dev, t, st));
-            HIPCHK(hipMemcpyAsync(tout->text, b->t_text.p, (size_t)text_len, hipMemcpyDeviceToHost, st));
-            if (tout->row_off) HIPCHK(hipMemcpyAsync(tout->row_off, b->t_rowoff.p, ((size_t)n_recs + 1) * 8, hipMemcpyDeviceToHost, st));
+            // sorted: the rows stay in HBM (the arena grows before the deposit below: out of room, nothing of the block has been deposited)
+            if (sorter) { if (const int rc = gm_samsort_add(sorter, seq, t.recs, n_recs, t.text, t.row_off, text_len, st)) return rc; }
+            else HIPCHK(hipMemcpyAsync(tout->text, b->t_text.p, (size_t)text_len, hipMemcpyDeviceToHost, st));
+            if (!sorter && tout->row_off) HIPCHK(hipMemcpyAsync(tout->row_off, b->t_rowoff.p, ((size_t)n_recs + 1) * 8, hipMemcpyDeviceToHost, st));
         }
     }
     if (snp && ix->cov_bins && n_p) {
@@ -1960,6 +1967,34 @@ extern "C" int gm_output_batch_text_resident(gm_index* ix, const gm_params* p, g
     gm_reads reads{};
     reads.n = b->n; reads.stride = b->stride;
     return output_batch_impl(ix, p, b, &reads, hits, nullptr, nullptr, out, stream);
+}
+
+// gm_output_batch_text / _text_resident with the text kept in HBM: appended to the sorter's arena under `seq` (gm_samsort.hip)
+extern "C" int gm_output_batch_sorted(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_read_text* rt, const gm_hits* hits, gm_sam_sorter* sorter,
+                                      uint64_t seq, void* stream) {
+    if (!ix) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("gm_output_batch_sorted: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!p || !b || !reads || !hits || !sorter) return GM_E_ARG;
+    if (!rt) { gm_set_error("gm_output_batch_sorted: gm_read_text is NULL"); return GM_E_ARG; }
+    if (const int rc = gm_samsort_claim(sorter, ix, seq)) return rc;
+    gm_sam_text kept{};
+    const int rc = output_batch_impl(ix, p, b, reads, hits, nullptr, rt, &kept, stream, sorter, seq);
+    if (rc != GM_OK) gm_samsort_release(sorter, seq);             // (a no-op once rows of the block are in the arena)
+    return rc;
+}
+
+extern "C" int gm_output_batch_sorted_resident(gm_index* ix, const gm_params* p, gm_batch* b, const gm_hits* hits, gm_sam_sorter* sorter, uint64_t seq, void* stream) {
+    if (!ix) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("gm_output_batch_sorted_resident: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!p || !b || !hits || !sorter) return GM_E_ARG;
+    if (!b->text_block || !b->text_pools) { gm_set_error("gm_output_batch_sorted_resident: the batch holds no names from gm_batch_upload_text"); return GM_E_ARG; }
+    if (const int rc = gm_samsort_claim(sorter, ix, seq)) return rc;
+    gm_reads reads{};
+    reads.n = b->n; reads.stride = b->stride;
+    gm_sam_text kept{};
+    const int rc = output_batch_impl(ix, p, b, &reads, hits, nullptr, nullptr, &kept, stream, sorter, seq);
+    if (rc != GM_OK) gm_samsort_release(sorter, seq);
+    return rc;
 }
 
 // gm_batch_upload_text on a batch of its own, the rows brought back (unit level, parity tests)

@@ -84,3 +84,9 @@ struct gm_index {
 unsigned host_threads();                                        // these three: gm_api.cpp.  GM_HOST_THREADS, else min(16, hardware threads); read once per process
 uint32_t host_pos2rid(const GmHostIndex& h, uint64_t pos);      // the contig that holds a concatenated position
 int index_cnames(gm_index* ix);                                 // contig names + offsets into HBM (d_cnames / d_cname_off), once per index
+// gm_samsort.hip: what gm_output_batch_sorted (gm_api.cpp) does with a block besides gm_output_batch_text's work.  claim: the sequence number,
+// before anything of the block is computed (GM_E_ARG: used before, the sorter is finished or belongs to another index).  add: the rows
+// as k_out_text_rows left them in HBM - the records, n_rows + 1 offsets, the text - into the arena, on `stream` (GM_E_NOMEM, GM_E_UNSUPPORTED)
+int gm_samsort_claim(gm_sam_sorter* s, const gm_index* ix, uint64_t seq);
+void gm_samsort_release(gm_sam_sorter* s, uint64_t seq);     // the claim back, when the call failed before a row of the block was added
+int gm_samsort_add(gm_sam_sorter* s, uint64_t seq, const GmDevSamRec* recs, uint64_t n_rows, const char* d_text, const uint64_t* d_rowoff, uint64_t text_len, void* stream);

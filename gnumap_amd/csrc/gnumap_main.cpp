@@ -11,6 +11,8 @@
 // (gm_batch_upload_text); parse_range and pack_block do not run for that block.
 // --sam_shards=K: the rows go to K files by input position, each with its own descriptor and writer; their concatenation in
 // order is the single-file SAM.
+// --sam_sort=coordinate: the rows never leave HBM unsorted - every block's text goes into a gm_sam_sorter (gm_output_batch_sorted) under its
+// block index, and after the last block the rows come down in coordinate order, slab by slab, into the single <out>.sam.
 // The number of blocks in flight is bounded by a fixed pool of Block objects.
 // Multi-GPU (--gpus N): one index replica per GPU, blocks dealt to whichever worker is free, coverage tracks combined
 // with one RCCL all-reduce (gm_coverage_allreduce).
@@ -61,6 +63,8 @@ struct Options {
     bool track_text_device = false; // --track_text=device: <out>.sgr / <out>.gmp formatted on the GPU (gm_coverage_write_*_device); host = the whole tracks come down
     int sam_shards = 1;             // --sam_shards=K: <out>.0.sam .. <out>.<K-1>.sam by input position instead of one <out>.sam
     bool read_text_device = false;  // --read_text=device: chunk-mode blocks go up as FASTQ text and are cut into reads on the GPU (gm_batch_upload_text); host = parse_range + pack_block
+    bool sam_sort = false;          // --sam_sort=coordinate: the rows stay in HBM, are sorted there once and written in coordinate order (implies --sam_text=device)
+    bool sam_text_host_set = false; // an explicit --sam_text=host (refused with --sam_sort=coordinate)
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
 
@@ -109,7 +113,11 @@ static void usage(int rc, const char* msg) {
             "                               (default) or the GPU (same bytes; only the text crosses the link, no whole-genome host array)\n"
             "      --sam_shards=K           1 .. 64 (default 1 = <out>.sam): write <out>.0.sam .. <out>.<K-1>.sam, a block going to the\n"
             "                               shard of its position in the input, header lines in shard 0 only;\n"
-            "                               cat <out>.0.sam .. <out>.<K-1>.sam is the single-file SAM\n");
+            "                               cat <out>.0.sam .. <out>.<K-1>.sam is the single-file SAM\n"
+            "      --sam_sort=none|coordinate   none (default): rows in input order.  coordinate: the rows stay on the GPU until the input is\n"
+            "                               exhausted, are sorted there by (contig in @SQ order, position) - equal keys keep input order -\n"
+            "                               and written once, behind a first header line @HD VN:1.0 SO:coordinate.  Implies --sam_text=device;\n"
+            "                               one GPU, one <out>.sam (not with --sam_text=host, --sam_shards above 1 or --gpus above 1)\n");
     exit(rc);
 }
 
@@ -166,7 +174,7 @@ static void parse_args(int argc, char** argv, Options& o) {
             else if (starts(s, "locate=")) o.locate_sampled = !strcmp(s + 7, "sampled");
             else if (starts(s, "sam_text=")) {
                 if (!strcmp(s + 9, "device")) o.sam_text_device = true;
-                else if (!strcmp(s + 9, "host")) o.sam_text_device = false;
+                else if (!strcmp(s + 9, "host")) { o.sam_text_device = false; o.sam_text_host_set = true; }
                 else { fprintf(stderr, "Error: --sam_text takes host or device, not: %s\n", s + 9); exit(1); }
             }
             else if (starts(s, "read_text=")) {
@@ -178,6 +186,11 @@ static void parse_args(int argc, char** argv, Options& o) {
                 if (!strcmp(s + 11, "device")) o.track_text_device = true;
                 else if (!strcmp(s + 11, "host")) o.track_text_device = false;
                 else { fprintf(stderr, "Error: --track_text takes host or device, not: %s\n", s + 11); exit(1); }
+            }
+            else if (starts(s, "sam_sort=")) {
+                if (!strcmp(s + 9, "coordinate")) o.sam_sort = true;
+                else if (!strcmp(s + 9, "none")) o.sam_sort = false;
+                else { fprintf(stderr, "Error: --sam_sort takes none or coordinate, not: %s\n", s + 9); exit(1); }
             }
             else if (starts(s, "sam_shards=")) {
                 char* end = nullptr;
@@ -233,6 +246,12 @@ static void parse_args(int argc, char** argv, Options& o) {
     if (o.vcf && o.p.mode != GM_MODE_SNP) { fprintf(stderr, "Error: --vcf writes the SNP calls of --snp: give --snp with --vcf\n"); exit(1); }
     if (o.adaptor.size() > 256) { fprintf(stderr, "Error: -A/--adaptor takes at most 256 characters\n"); exit(1); }
     if (o.gpus < 1) o.gpus = 1;
+    if (o.sam_sort) {                                        // refused before a device is opened or a file is written
+        if (o.sam_text_host_set) { fprintf(stderr, "Error: --sam_sort=coordinate sorts the rows the GPU formats: it cannot be combined with --sam_text=host\n"); exit(1); }
+        if (o.sam_shards > 1) { fprintf(stderr, "Error: --sam_sort=coordinate writes one sorted <out>.sam: it cannot be combined with --sam_shards above 1\n"); exit(1); }
+        if (o.gpus > 1) { fprintf(stderr, "Error: --sam_sort=coordinate sorts on one GPU: it cannot be combined with --gpus above 1 (there is no cross-device merge)\n"); exit(1); }
+        o.sam_text_device = true;
+    }
     if (o.batch < 1) o.batch = 1;
     if (o.workers < 1) o.workers = 1;
     if (o.fmt_threads < 1) o.fmt_threads = (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
@@ -289,6 +308,7 @@ struct TextPool {
 // ---- blocks ------------------------------------------------------------------------------------------------------
 struct Block {
     uint64_t index = 0;
+    uint64_t sort_seq = 0;                  // --sam_sort: the block's sequence number in the sorter: (blocks before it in the run) << 21, the low bits order the halves of a split block
     uint32_t n = 0, maxlen = 0, stride = 8;
     // views into the memory-mapped FASTQ text (no per-read strings)
     std::vector<const char*> name, seq, qual;
@@ -734,6 +754,7 @@ struct Worker {
     PinVec<gm_match> matches; PinVec<gm_pos> positions;
     uint64_t n_reads = 0, n_matched = 0, n_records = 0;
     double t_pack = 0, t_map = 0, t_out = 0, t_scan = 0;
+    gm_sam_sorter* sorter = nullptr;        // --sam_sort=coordinate: where the blocks' rows go instead of a host buffer
     TextPool* stage_pool = nullptr;         // --read_text=device: page-locked buffers a block's FASTQ text is copied into for the upload
 };
 
@@ -793,7 +814,12 @@ static int process_text_block(Worker& w, const Options& o, const char* base, Blo
     }
     auto c2 = std::chrono::steady_clock::now();
     uint64_t n_recs = 0;
-    if (o.sam_text_device) {
+    if (o.sam_sort) {                                       // the rows stay in HBM; their number is known when the sorter finishes
+        int rc = gm_output_batch_sorted_resident(w.ix, &o.p, w.batch, &hits, w.sorter, b.sort_seq, w.stream);
+        if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
+        if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch_sorted_resident: %s\n", gm_last_error()); return rc; }
+        b.dtext_len = 0;
+    } else if (o.sam_text_device) {
         if (!b.dtext) b.dtext = w.text_pool->get();
         b.dtext->ensure(((size_t)n + (size_t)n / 16) * (2 * (size_t)b.maxlen + 64) + (b.text_hi - b.text_lo) + 4096);
         gm_sam_text st;
@@ -860,6 +886,16 @@ static int process_block(Worker& w, const Options& o, Block& b) {
     if (o.sam_text_device) {                                // the rows come back as text: no records, no CIGAR pool on the host
         gm_read_text rt; rt.names = b.names_pool.data(); rt.name_off = b.name_off.data();
         rt.qual_tail = b.has_qtail ? b.qtail_pool.data() : nullptr; rt.qual_tail_off = b.has_qtail ? b.qtail_off.data() : nullptr;
+        if (o.sam_sort) {
+            int rc = gm_output_batch_sorted(w.ix, &bp, w.batch, &reads, &rt, &hits, w.sorter, b.sort_seq, w.stream);
+            if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
+            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch_sorted: %s\n", gm_last_error()); return rc; }
+            b.n_recs = 0; b.dtext_len = 0; b.gpu = w.gpu;
+            w.t_pack += std::chrono::duration<double>(c1 - c0).count(); w.t_map += std::chrono::duration<double>(c2 - c1).count(); w.t_out += secs_since(c2);
+            w.n_reads += n;
+            for (uint32_t i = 0; i < n; ++i) w.n_matched += (w.status[i] == GM_READ_OK || w.status[i] == GM_READ_TOO_MANY);
+            return GM_OK;
+        }
         if (!b.dtext) b.dtext = w.text_pool->get();
         b.dtext->ensure(((size_t)n + (size_t)n / 16) * (2 * (size_t)b.maxlen + 64) + (size_t)b.name_off[n] + 4096);
         gm_sam_text st;
@@ -913,7 +949,7 @@ static int process_block_split(Worker& w, const Options& o, const char* base, Bl
     for (int part = 0; part < 2; ++part) {
         const uint32_t lo = part ? half : 0, hi = part ? b.n : half;
         Block c;
-        c.index = b.index; c.n = hi - lo; c.maxlen = b.maxlen; c.stride = b.stride; c.illumina = b.illumina;
+        c.index = b.index; c.sort_seq = b.sort_seq | (uint64_t)part << (20 - depth); c.n = hi - lo; c.maxlen = b.maxlen; c.stride = b.stride; c.illumina = b.illumina;
         c.name.assign(b.name.begin() + lo, b.name.begin() + hi); c.seq.assign(b.seq.begin() + lo, b.seq.begin() + hi);
         c.qual.assign(b.qual.begin() + lo, b.qual.begin() + hi); c.name_len.assign(b.name_len.begin() + lo, b.name_len.begin() + hi);
         c.qual_len.assign(b.qual_len.begin() + lo, b.qual_len.begin() + hi); c.len.assign(b.len.begin() + lo, b.len.begin() + hi);
@@ -935,6 +971,7 @@ static int process_block_split(Worker& w, const Options& o, const char* base, Bl
         pool.insert(pool.end(), c.pool.data(), c.pool.data() + used);
         pool_len += used; total += c.n_recs;
     }
+    if (o.sam_sort) { b.dtext_len = 0; b.n_recs = total; b.gpu = w.gpu; return GM_OK; }      // each half went into the sorter under its own sequence number
     if (o.sam_text_device) {
         if (!b.dtext) b.dtext = w.text_pool->get();
         b.dtext->ensure(text.size() + 1);
@@ -987,6 +1024,8 @@ int main(int argc, char** argv) {
     }
     for (int g = 0; g < o.gpus; ++g)                                   // k-mer tables / records for these parameters: part of staging the index
         if (gm_index_prepare(gpu_ix[(size_t)g], &o.p) != GM_OK) { fprintf(stderr, "ERROR: GPU %d: %s\n", g, gm_last_error()); return 1; }
+    gm_sam_sorter* sorter = nullptr;
+    if (o.sam_sort && gm_sam_sorter_create(gpu_ix[0], &sorter) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
     std::vector<Worker> workers((size_t)o.gpus * (size_t)o.workers);
     TextPool text_pool, stage_pool;
     for (int g = 0; g < o.gpus; ++g) {
@@ -994,7 +1033,7 @@ int main(int argc, char** argv) {
             (o.p.mode != GM_MODE_NORMAL && gm_coverage_enable_nuc(gpu_ix[(size_t)g]) != GM_OK)) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
         for (int k = 0; k < o.workers; ++k) {
             Worker& w = workers[(size_t)g * (size_t)o.workers + (size_t)k];
-            w.gpu = g; w.ix = gpu_ix[(size_t)g]; w.text_pool = &text_pool; w.stage_pool = &stage_pool;
+            w.gpu = g; w.ix = gpu_ix[(size_t)g]; w.text_pool = &text_pool; w.stage_pool = &stage_pool; w.sorter = sorter;
             if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK ||
                 gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK ||
                 gm_batch_set_read_format(w.batch, o.fasta ? GM_READS_FASTA : GM_READS_FASTQ) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
@@ -1023,6 +1062,7 @@ int main(int argc, char** argv) {
     };
     {
         std::ostringstream hd;
+        if (o.sam_sort) hd << "@HD\tVN:1.0\tSO:coordinate\n";
         for (uint32_t i = 0; i < info.n_seqs; ++i)                     // Driver.cpp:2322-2327
             hd << "@SQ\tSN:" << gm_index_contig_name(gpu_ix[0], i) << "\tLN:"
                << (gm_index_contig_offset(gpu_ix[0], i + 1) - gm_index_contig_offset(gpu_ix[0], i)) << "\n";
@@ -1045,6 +1085,7 @@ int main(int argc, char** argv) {
     // what holds buffered pwrite()s to ONE file to the rate of one thread, 8.4-8.8 GB/s whatever the number of writers.  4 x SLOWER on the
     // GPU box's file system: 2.1 M first-touch page faults of a growing file cost more than the copies.  The write calls stay.)
     const size_t npos = ~(size_t)0;
+    uint64_t seq_base = 0;                                               // --sam_sort: blocks handed out by the passes before this one
     // One pass of the pipeline over the FASTQ text from fq.at on.  chunks = byte ranges cut into records by the workers in parallel
     // (well-formed records only); returns where a malformed record starts (npos: none) - everything before it has been mapped and
     // written, nothing after it has touched the SAM file or the coverage track: a block is mapped only once every block before it is
@@ -1060,6 +1101,7 @@ int main(int argc, char** argv) {
         struct { std::mutex mu; std::condition_variable cv; uint64_t parsed = 0; std::set<uint64_t> done; uint64_t stop = ~0ull; size_t bad_at = ~(size_t)0; } gate;
         std::atomic<uint64_t> stop_block{ ~0ull };
 
+        uint64_t idx_end = 0;
         std::thread scanner([&] {
             uint64_t idx = 0;
             int ill_state = o.p.illumina;
@@ -1074,6 +1116,7 @@ int main(int argc, char** argv) {
                 if (too_long) failed = 1;
                 if (!more || failed) { free_q.push(b); break; }
                 b->index = idx++; b->failed = false;
+                b->sort_seq = (seq_base + b->index) << 21;
                 b->illumina = ill_state;
                 b->kept.clear();
                 if (ill_state && !o.adaptor.empty()) {      // -A: the fallback scan sees only the characters the trim keeps (SeqReader.cpp:1152)
@@ -1088,6 +1131,7 @@ int main(int argc, char** argv) {
                         for (uint32_t t = 0; t < (b->kept.empty() ? b->len[i] : b->kept[i]); ++t) if ((signed char)b->qual[i][t] < 64) { ill_state = 0; break; }
                 map_q.push(b);
             }
+            idx_end = idx;
             map_q.close();
         });
         std::vector<std::thread> wth;
@@ -1194,7 +1238,7 @@ int main(int argc, char** argv) {
                     b = ready.begin()->second; ready.erase(ready.begin());
                 }
                 ++next;
-                if (b->failed || !b->n_recs) { release(b); continue; }
+                if (b->failed || !b->n_recs || o.sam_sort) { release(b); continue; }      // (sorted: the rows are in the sorter)
                 WriteJob* j = new WriteJob();
                 j->b = b;
                 j->shard = K == 1 || fq.size == 0 ? 0 : (int)std::min<unsigned __int128>((unsigned __int128)(K - 1), (unsigned __int128)b->first_byte * (unsigned)K / fq.size);
@@ -1215,6 +1259,7 @@ int main(int argc, char** argv) {
         for (auto& x : wth) x.join();
         for (auto& x : fth) x.join();
         writer.join();
+        seq_base += idx_end;
         return gate.bad_at;
     };
     const bool file_order = o.batch_set || o.p.illumina;
@@ -1223,9 +1268,49 @@ int main(int argc, char** argv) {
         fq.at = bad_at; fq.done = false;
         run_pass(false);
     }
+    // --sam_sort=coordinate: sort once, then the rows come down slab by slab; a slab is written while the next one is gathered and downloaded
+    uint64_t sorted_rows = 0, sorted_bytes = 0;
+    if (o.sam_sort && !failed) {
+        if (gm_sam_sorter_finish(sorter, &sorted_rows, &sorted_bytes, workers[0].stream) != GM_OK) { fprintf(stderr, "ERROR: gm_sam_sorter_finish: %s\n", gm_last_error()); return 1; }
+        PinVec<char> slab[2];
+        const size_t slab_cap = (size_t)std::min<uint64_t>((uint64_t)64 << 20, std::max<uint64_t>(sorted_bytes, 1 << 16));
+        slab[0].ensure(slab_cap); slab[1].ensure(slab_cap);
+        std::thread wr; std::atomic<int> wr_bad{ 0 };
+        auto w0 = std::chrono::steady_clock::now();
+        size_t cap = slab_cap;                                           // what gm_sam_sorter_read may fill of either buffer
+        for (int k = 0;;) {                                              // k: the buffer the next slab goes into, while the other one is written
+            uint64_t got = 0;
+            int rc = gm_sam_sorter_read(sorter, slab[k].data(), cap, &got, workers[0].stream);
+            if (rc == GM_E_CAPACITY) {                                   // a row longer than a slab: both buffers grow to it, the same read again
+                if (wr.joinable()) wr.join();
+                cap = (size_t)got;
+                slab[0].ensure(cap); slab[1].ensure(cap);
+                continue;
+            }
+            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_sam_sorter_read: %s\n", gm_last_error()); failed = 1; break; }
+            if (wr.joinable()) wr.join();
+            if (!got || wr_bad) break;
+            const uint64_t off = file_offs[0];
+            file_offs[0] += got;
+            const char* p = slab[k].data();
+            wr = std::thread([&, p, got, off] { if (!pwrite_all(ofd, p, (size_t)got, off)) wr_bad = 1; });
+            k ^= 1;
+        }
+        if (wr.joinable()) wr.join();
+        if (wr_bad) { fprintf(stderr, "ERROR: write failed\n"); failed = 1; }
+        t_write += secs_since(w0);
+    }
     for (int fd : ofds) ::close(fd);
     if (failed) return 1;
     const double t_pipe = secs_since(t_pipe0);
+    if (o.sam_sort && o.verbose > 0) {
+        gm_sam_sort_stats ss;
+        if (gm_sam_sorter_stats(sorter, &ss) == GM_OK) {
+            fprintf(stderr, "sam sort on the device: %lu rows, %lu text bytes in %lu pieces of %lu bytes; seconds: arena appends %.3f, sort %.3f, gather %.3f, download %.3f\n",
+                    (unsigned long)ss.rows, (unsigned long)ss.text_bytes, (unsigned long)ss.pieces, (unsigned long)ss.piece_bytes, ss.add_s, ss.sort_s, ss.gather_ms / 1e3, ss.download_s);
+        }
+    }
+    gm_sam_sorter_destroy(sorter);
     auto t_cov0 = std::chrono::steady_clock::now();
     // coverage: all-reduce over the GPUs, then PrintFinalSGR / PrintFinalBisulfite
     if (gm_coverage_allreduce(gpu_ix.data(), o.gpus) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
@@ -1263,6 +1348,7 @@ int main(int argc, char** argv) {
         gm_batch_destroy(w.batch);
         gm_stream_destroy(w.ix, w.stream);
     }
+    if (o.sam_sort) n_records = sorted_rows;
     const double t_cov = secs_since(t_cov0);
     for (auto ix : gpu_ix) gm_index_close(ix);
     double secs = secs_since(t0);

@@ -335,6 +335,46 @@ int gm_map_batch_text(gm_index*, const gm_params*, gm_batch*, gm_hits* out, void
  * (gm_output_batch works on such a block too, with a gm_reads that carries its n and stride.) */
 int gm_output_batch_text_resident(gm_index*, const gm_params*, gm_batch*, const gm_hits*, gm_sam_text* out, void* hip_stream);
 
+/* ---- coordinate-sorted SAM: the rows stay in HBM until the input is exhausted (gm_samsort.hip) ----
+ * A gm_sam_sorter belongs to one index and its device.  gm_output_batch_sorted / _sorted_resident do for a block exactly what
+ * gm_output_batch_text / _text_resident do - fp64 pass, traceback, coverage / per-nucleotide / SNP deposit, the rows as text - but the
+ * text is not downloaded: it is appended device to device, on hip_stream, to the sorter's arena (pieces of GM_SORT_PIECE bytes, default
+ * 1 GiB, at least 64 KiB; a row never straddles two pieces) under the block's sequence number `seq`, with one key per row:
+ *     key = (uint64_t)contig << 32 | chr_pos        (~0 for a record without a contig: sorts last)
+ * gm_sam_sorter_finish orders the rows by key; equal keys keep input order: ascending seq, then gm_output_batch's record order within
+ * the block.  Blocks may be added in any order and from several threads at once (different batches, one sorter).  One stable radix sort
+ * of (key, 32-bit row ordinal) pairs over the key bits in use, a scan of the sorted rows' lengths, and gm_sam_sorter_read gathers the
+ * rows of one slab at a time in HBM (k_ss_gather) and downloads them.
+ * A call that fails before a row of its block is in the arena gives its seq back (GM_E_BATCH_TOO_LARGE: add the block in halves).
+ * GM_E_ARG: a seq used before, or an add after finish (nothing is deposited).  GM_E_NOMEM: the arena cannot grow - nothing of the block
+ * has been deposited; gm_last_error() gives the bytes the sorter holds and the bytes it asked for.  GM_E_UNSUPPORTED: more than
+ * 2^32 - 1 rows.  GM_E_NO_DEVICE on a host-only index. */
+typedef struct gm_sam_sorter gm_sam_sorter;
+typedef struct {
+    uint64_t rows, text_bytes, pieces, piece_bytes;     /* what the sorter holds */
+    double add_s;                   /* host seconds inside the arena appends (all threads) */
+    double sort_s;                  /* gm_sam_sorter_finish, host wall */
+    double gather_ms;               /* device time of k_ss_spans + k_ss_gather over all reads (HIP events) */
+    uint64_t gather_bytes;          /* bytes the gather kernel wrote */
+    double download_s;              /* host seconds in the device-to-host copies of the reads */
+} gm_sam_sort_stats;
+int gm_sam_sorter_create(gm_index*, gm_sam_sorter** out);
+void gm_sam_sorter_destroy(gm_sam_sorter*);
+int gm_output_batch_sorted(gm_index*, const gm_params*, gm_batch*, const gm_reads*, const gm_read_text*, const gm_hits*, gm_sam_sorter*, uint64_t seq,
+                           void* hip_stream);
+int gm_output_batch_sorted_resident(gm_index*, const gm_params*, gm_batch*, const gm_hits*, gm_sam_sorter*, uint64_t seq, void* hip_stream);
+/* sorts; zero rows is GM_OK with *n_rows = *text_bytes = 0.  A second call returns the same numbers.  A finish that fails (GM_E_NOMEM
+ * for the sort's buffers, GM_E_HIP) is remembered: every later finish and read returns its status, no block can be added */
+int gm_sam_sorter_finish(gm_sam_sorter*, uint64_t* n_rows, uint64_t* text_bytes, void* hip_stream);
+/* the next whole rows that fit in cap bytes, in sorted order; *n_out = 0: done.  GM_E_CAPACITY when the next row alone is longer than cap:
+ * *n_out = that row's length, nothing is consumed.  GM_E_ARG before finish.  One reader at a time */
+int gm_sam_sorter_read(gm_sam_sorter*, char* text, uint64_t cap, uint64_t* n_out, void* hip_stream);
+int gm_sam_sorter_stats(gm_sam_sorter*, gm_sam_sort_stats* out);
+/* unit level (parity tests, tools/sam_sort_bench.py): n_rows rows of the caller's - text[row_off[i], row_off[i + 1]) - under the caller's
+ * keys (contig >= the number of contigs: the key ~0), added as block `seq` exactly as the rows of gm_output_batch_sorted are */
+int gm_sam_sorter_add_rows(gm_sam_sorter*, uint64_t seq, const char* text, const uint64_t* row_off, const uint32_t* contig, const uint64_t* chr_pos,
+                           uint64_t n_rows, void* hip_stream);
+
 /* enqueue / wait forms: the call is queued on the batch's own service thread and runs there exactly as the synchronous form would;
  * the caller goes on (with another batch).  Calls queued on one batch run in order - gm_output_batch_enqueue may be queued right
  * behind the gm_map_batch_enqueue whose gm_hits it reads - and after a failing call the rest of the batch's queue is skipped.
