@@ -16,11 +16,12 @@
 // The number of blocks in flight is bounded by a fixed pool of Block objects.
 // Multi-GPU (--gpus N): one index replica per GPU, blocks dealt to whichever worker is free, coverage tracks combined
 // with one RCCL all-reduce (gm_coverage_allreduce).
+// Layout: process_block = the two batch calls of one block; Run = what lives for the whole run, main() = its steps in order; Pass = one pass
+// of the pipeline, its queues and the bodies of its scanner, worker, formatter and writer threads.
 #include "gnumap_hip.h"
 #include "gm_fmt.h"
 #include <algorithm>
 #include <atomic>
-#include <charconv>
 #include <condition_variable>
 #include <deque>
 #include <chrono>
@@ -29,8 +30,6 @@
 #include <cstring>
 #include <cmath>
 #include <cctype>
-#include <fstream>
-#include <iostream>
 #include <map>
 #include <memory>
 #include <set>
@@ -68,7 +67,7 @@ struct Options {
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
 
-static void usage(int rc, const char* msg) {
+[[noreturn]] static void usage(int rc, const char* msg) {
     if (msg && *msg) fprintf(stderr, "%s\n", msg);
     fprintf(stderr,
             "Usage: gnumap [options] <file_to_parse>\n"
@@ -122,6 +121,10 @@ static void usage(int rc, const char* msg) {
 }
 
 static bool starts(const char* s, const char* pre) { return strncmp(s, pre, strlen(pre)) == 0; }
+static bool on_device(const char* flag, const char* v) {        // the value of --sam_text, --read_text, --track_text
+    if (strcmp(v, "device") && strcmp(v, "host")) { fprintf(stderr, "Error: --%s takes host or device, not: %s\n", flag, v); exit(1); }
+    return !strcmp(v, "device");
+}
 
 static void parse_args(int argc, char** argv, Options& o) {
     gm_params_default(&o.p);
@@ -172,21 +175,9 @@ static void parse_args(int argc, char** argv, Options& o) {
             else if (starts(s, "workers=")) o.workers = atoi(s + 8);
             else if (starts(s, "fmt_threads=")) o.fmt_threads = atoi(s + 12);
             else if (starts(s, "locate=")) o.locate_sampled = !strcmp(s + 7, "sampled");
-            else if (starts(s, "sam_text=")) {
-                if (!strcmp(s + 9, "device")) o.sam_text_device = true;
-                else if (!strcmp(s + 9, "host")) { o.sam_text_device = false; o.sam_text_host_set = true; }
-                else { fprintf(stderr, "Error: --sam_text takes host or device, not: %s\n", s + 9); exit(1); }
-            }
-            else if (starts(s, "read_text=")) {
-                if (!strcmp(s + 10, "device")) o.read_text_device = true;
-                else if (!strcmp(s + 10, "host")) o.read_text_device = false;
-                else { fprintf(stderr, "Error: --read_text takes host or device, not: %s\n", s + 10); exit(1); }
-            }
-            else if (starts(s, "track_text=")) {
-                if (!strcmp(s + 11, "device")) o.track_text_device = true;
-                else if (!strcmp(s + 11, "host")) o.track_text_device = false;
-                else { fprintf(stderr, "Error: --track_text takes host or device, not: %s\n", s + 11); exit(1); }
-            }
+            else if (starts(s, "sam_text=")) { o.sam_text_device = on_device("sam_text", s + 9); if (!o.sam_text_device) o.sam_text_host_set = true; }
+            else if (starts(s, "read_text=")) o.read_text_device = on_device("read_text", s + 10);
+            else if (starts(s, "track_text=")) o.track_text_device = on_device("track_text", s + 11);
             else if (starts(s, "sam_sort=")) {
                 if (!strcmp(s + 9, "coordinate")) o.sam_sort = true;
                 else if (!strcmp(s + 9, "none")) o.sam_sort = false;
@@ -279,7 +270,6 @@ template <class T> struct PinVec {
 struct TextBuf {
     std::unique_ptr<char[]> p; size_t len = 0, cap = 0;
     void clear() { len = 0; }
-    bool empty() const { return len == 0; }
     size_t size() const { return len; }
     const char* data() const { return p.get(); }
     char* room(size_t extra) {                        // at least `extra` writable bytes at the end
@@ -322,8 +312,7 @@ struct Block {
     PinVec<gm_sam_rec> recs; PinVec<char> pool; uint64_t n_recs = 0;
     int gpu = 0;
     size_t text_lo = 0, text_hi = 0; bool lazy = false;   // chunk mode: the byte range of the FASTQ text a worker still has to cut into records
-    bool malformed = false;                 // chunk mode: a malformed record ended this block; the rest of the input is read again in file order with the reference's recovery
-    int illumina = 0;                       // --illumina still in force when this block starts (the fallback is sticky, SeqReader.cpp:1171-1180)
+    int illumina = 0;                      // --illumina still in force when this block starts (the fallback is sticky, SeqReader.cpp:1171-1180)
     std::vector<TextBuf> text;              // SAM text, one piece per formatter thread
     // --sam_text=device: what gm_output_batch_text reads of the block besides bases and qualities, and the text it returns (page-locked)
     PinVec<char> names_pool, qtail_pool; PinVec<uint64_t> name_off, qtail_off; bool has_qtail = false;
@@ -333,7 +322,25 @@ struct Block {
     // the text from text_lo on (page-locked; only filled for the host formatter)
     bool text_dev = false; PinVec<gm_text_rec> trecs;
     bool failed = false;
+    // what the three parsers share: no record, one more record (`head` = its name line with the '@' or '>'), the row stride behind the last
+    void reset() { n = 0; maxlen = 0; name.clear(); seq.clear(); qual.clear(); name_len.clear(); qual_len.clear(); len.clear(); fa_text.clear(); }
+    void append(const char* head, size_t head_len, const char* sq, size_t sl, const char* ql, size_t qll) {
+        name.push_back(head + 1); name_len.push_back((uint32_t)(head_len - 1));
+        seq.push_back(sq); len.push_back((uint16_t)sl); qual.push_back(ql); qual_len.push_back((uint32_t)qll);
+        maxlen = std::max<uint32_t>(maxlen, (uint32_t)sl); ++n;
+    }
+    bool finish() { stride = std::max<uint32_t>(8, (maxlen + 7u) & ~7u); return n > 0; }
+    // --illumina's fallback: a quality below '@' in what the adaptor trim keeps of the first `upto` reads (the reference's quality characters are signed chars)
+    bool has_quality_below_64(uint32_t upto) const {
+        for (uint32_t i = 0; i < upto; ++i)
+            for (uint32_t t = 0; t < (kept.empty() ? len[i] : kept[i]); ++t) if ((signed char)qual[i][t] < 64) return true;
+        return false;
+    }
 };
+
+static void report_too_long(const char* head, size_t head_len) {      // the kernels' limit, not the reference's
+    fprintf(stderr, "ERROR: read %.*s is longer than 2048 bases\n", (int)std::min<size_t>(head_len, 200), head);
+}
 
 template <class T> struct Queue {             // unbounded MPMC queue; the Block pool bounds what is in flight
     std::mutex mu; std::condition_variable cv; std::deque<T> q; bool closed = false;
@@ -369,22 +376,12 @@ struct FastqScanner {
         return true;
     }
     ~FastqScanner() { if (mapped) munmap((void*)base, size); if (fd >= 0) ::close(fd); }
-    // one line [p, p+len), without the newline; false at end of input
-    inline bool line(const char*& p, size_t& len) {
-        if (at >= size) return false;
-        const char* s = base + at;
-        const char* e = (const char*)memchr(s, '\n', size - at);
-        if (!e) { p = s; len = size - at; at = size; return true; }
-        p = s; len = (size_t)(e - s); at = (size_t)(e - base) + 1;
-        return true;
-    }
     // Chunk mode: cut base[cur, limit) into records until max_reads (thread-safe: no scanner state).  Only well-formed records are
     // taken here; at the first one that is not, `stop` is set and `bad_at` is where its name line starts: the driver then reads the rest
     // of the input again from there in file order (parse_resync), because what the reference does with a malformed record depends on
     // the lines that follow it.  `too_long` = a read longer than the kernels take (this implementation's limit, not the reference's).
     static bool parse_range(const char* base, size_t& cur, size_t limit, Block& b, uint32_t max_reads, bool* stop, size_t* bad_at, bool* too_long) {
-        b.n = 0; b.maxlen = 0;
-        b.name.clear(); b.seq.clear(); b.qual.clear(); b.name_len.clear(); b.qual_len.clear(); b.len.clear();
+        b.reset();
         auto line = [&](const char*& p, size_t& len) -> bool {       // one line without its newline; false at the end of the range
             if (cur >= limit) return false;
             const char* s0 = base + cur;
@@ -402,23 +399,17 @@ struct FastqScanner {
             const size_t rec_at = (size_t)(nm - base);
             const bool l2 = line(sq, sl), l3 = line(pl, pll), l4 = line(ql, qll);
             if (!l2 || !l3 || !l4 || nm[0] != '@' || pll == 0 || pl[0] != '+' || sl > qll) { *stop = true; *bad_at = rec_at; break; }
-            if (sl > 2048) { fprintf(stderr, "ERROR: read %.*s is longer than 2048 bases\n", (int)std::min<size_t>(nl, 200), nm); *too_long = true; break; }
-            b.name.push_back(nm + 1); b.name_len.push_back((uint32_t)(nl - 1));
-            b.seq.push_back(sq); b.len.push_back((uint16_t)sl);
-            b.qual.push_back(ql); b.qual_len.push_back((uint32_t)qll);
-            b.maxlen = std::max<uint32_t>(b.maxlen, (uint32_t)sl);
-            ++b.n;
+            if (sl > 2048) { report_too_long(nm, nl); *too_long = true; break; }
+            b.append(nm, nl, sq, sl, ql, qll);
         }
-        b.stride = std::max<uint32_t>(8, (b.maxlen + 7u) & ~7u);
-        return b.n > 0;
+        return b.finish();
     }
     // FASTA (SeqReader::get_more_fasta src/SeqReader.cpp:813-1018): a record runs from one '>' line to the next, the name is the whole
     // header line after '>', the sequence lines are joined.  base[cur, limit) starts at a '>' (the whole input was checked by
     // fasta_check before anything was mapped).  QUAL is str2qual's string (fasta_qual): the host formatter prints it from the block.
     static bool parse_range_fasta(const char* base, size_t& cur, size_t limit, Block& b, uint32_t max_reads, bool* too_long, const char* qual_of) {
-        b.n = 0; b.maxlen = 0;
-        b.name.clear(); b.seq.clear(); b.qual.clear(); b.name_len.clear(); b.qual_len.clear(); b.len.clear(); b.fa_text.clear();
-        std::vector<size_t> seq_at, qual_at;                 // offsets into fa_text (npos: a one-line sequence, printed from the mapping)
+        b.reset();
+        std::vector<size_t> seq_at, qual_at;                // offsets into fa_text (npos: a one-line sequence, printed from the mapping)
         std::vector<const char*> one_line;
         const size_t npos = ~(size_t)0;
         while (b.n < max_reads && cur < limit) {
@@ -441,25 +432,20 @@ struct FastqScanner {
                 }
                 total += ll; ++lines;
             }
-            if (total > 2048) { fprintf(stderr, "ERROR: read %.*s is longer than 2048 bases\n", (int)std::min<size_t>(hl, 200), hd); *too_long = true; break; }
-            b.name.push_back(hd + 1); b.name_len.push_back((uint32_t)(hl - 1));
+            if (total > 2048) { report_too_long(hd, hl); *too_long = true; break; }
+            b.append(hd, hl, nullptr, total, nullptr, total);      // (the views follow below)
             one_line.push_back(first ? first : hd); seq_at.push_back(joined_at);
-            b.len.push_back((uint16_t)total); b.qual_len.push_back((uint32_t)total);
-            b.maxlen = std::max<uint32_t>(b.maxlen, (uint32_t)total);
-            ++b.n;
         }
         // the QUAL strings behind the joined sequences, then the views (fa_text does not move any more)
         qual_at.resize(b.n);
         for (uint32_t i = 0; i < b.n; ++i) { qual_at[i] = b.fa_text.size(); b.fa_text.resize(b.fa_text.size() + b.len[i]); }
-        b.seq.resize(b.n); b.qual.resize(b.n);
         for (uint32_t i = 0; i < b.n; ++i) {
             b.seq[i] = seq_at[i] == npos ? one_line[i] : b.fa_text.data() + seq_at[i];
             char* q = b.fa_text.data() + qual_at[i];
             for (uint32_t t = 0; t < b.len[i]; ++t) q[t] = qual_of[(unsigned char)b.seq[i][t]];
             b.qual[i] = q;
         }
-        b.stride = std::max<uint32_t>(8, (b.maxlen + 7u) & ~7u);
-        return b.n > 0;
+        return b.finish();
     }
     bool fasta = false; const char* fasta_qual = nullptr;    // set by main() for a FASTA input
     // File order, with the recovery of SeqReader::get_more_fastq (src/SeqReader.cpp:1060-1150): four lines are read; while the first does
@@ -479,8 +465,7 @@ struct FastqScanner {
         if (e) { s.n = (size_t)(e - s0); at = (size_t)(e - base) + 1; } else { s.n = size - at; at = size; rs_eof = true; }
     }
     bool parse_resync(Block& b, uint32_t max_reads, bool* too_long) {
-        b.n = 0; b.maxlen = 0;
-        b.name.clear(); b.seq.clear(); b.qual.clear(); b.name_len.clear(); b.qual_len.clear(); b.len.clear();
+        b.reset();
         Line name, seq, plus, qual;
         while (b.n < max_reads) {
             if (rs_eof) { done = true; break; }                                               // :1061
@@ -505,15 +490,10 @@ struct FastqScanner {
                 }
             }
             if (done) break;
-            if (seq.n > 2048) { fprintf(stderr, "ERROR: read %.*s is longer than 2048 bases\n", (int)std::min<size_t>(name.n, 200), name.p); *too_long = true; done = true; break; }
-            b.name.push_back(name.p + 1); b.name_len.push_back((uint32_t)(name.n - 1));
-            b.seq.push_back(seq.p); b.len.push_back((uint16_t)seq.n);
-            b.qual.push_back(qual.p); b.qual_len.push_back((uint32_t)qual.n);
-            b.maxlen = std::max<uint32_t>(b.maxlen, (uint32_t)seq.n);
-            ++b.n;
+            if (seq.n > 2048) { report_too_long(name.p, name.n); *too_long = true; done = true; break; }
+            b.append(name.p, name.n, seq.p, seq.n, qual.p, qual.n);
         }
-        b.stride = std::max<uint32_t>(8, (b.maxlen + 7u) & ~7u);
-        return b.n > 0;
+        return b.finish();
     }
     bool next(Block& b, uint32_t max_reads, bool* too_long) {    // file-order mode: blocks of exactly max_reads reads
         if (done) return false;
@@ -638,8 +618,6 @@ static size_t reverse_cigar(const char* s, char* out) {  // SequenceOperations.h
     return used;
 }
 
-static inline char* put_u64(char* p, uint64_t v) { return gm_put_u64(p, v); }
-
 static const struct CompLut { char t[256]; CompLut() { for (int c = 0; c < 256; ++c) t[c] = comp_char((char)c); } } g_comp;
 
 // dst[0..n) = src[n-1..0], 8 bytes at a time
@@ -660,8 +638,8 @@ static void format_sam(TextBuf& out, const gm_index* ix, const gm_params& p, con
     memcpy(w, b.name[i], nl); w += nl;
     if (r.strand == GM_POS_STRAND) { memcpy(w, "\t0\t", 3); w += 3; } else { memcpy(w, "\t16\t", 4); w += 4; }
     memcpy(w, cn, cl); w += cl;
-    *w++ = '\t'; w = put_u64(w, r.chr_pos); *w++ = '\t';
-    if (r.mapq < 0) { *w++ = '-'; w = put_u64(w, (uint64_t)(-(int64_t)r.mapq)); } else w = put_u64(w, (uint64_t)r.mapq);
+    *w++ = '\t'; w = gm_put_u64(w, r.chr_pos); *w++ = '\t';
+    if (r.mapq < 0) { *w++ = '-'; w = gm_put_u64(w, (uint64_t)(-(int64_t)r.mapq)); } else w = gm_put_u64(w, (uint64_t)r.mapq);
     *w++ = '\t';
     if (r.strand == GM_POS_STRAND) {
         memcpy(w, cigar, gl); w += gl;
@@ -683,7 +661,7 @@ static void format_sam(TextBuf& out, const gm_index* ix, const gm_params& p, con
     memcpy(w, "\tXP:f:", 6); w += 6;
     if (r.post_prob == 1.0f) *w++ = '1'; else w = gm_put_g6(w, (double)(float)r.post_prob);
     memcpy(w, "\tX0:i:", 6); w += 6;
-    if (r.sim_matches < 0) { *w++ = '-'; w = put_u64(w, (uint64_t)(-(int64_t)r.sim_matches)); } else w = put_u64(w, (uint64_t)r.sim_matches);
+    if (r.sim_matches < 0) { *w++ = '-'; w = gm_put_u64(w, (uint64_t)(-(int64_t)r.sim_matches)); } else w = gm_put_u64(w, (uint64_t)r.sim_matches);
     *w++ = '\n';
     out.len += (size_t)(w - w0);
 }
@@ -744,6 +722,12 @@ static bool fasta_check(const char* base, size_t size, const char* fn) {
 }
 
 // ---- per worker: the two batch calls ---------------------------------------------------------------------------------
+using Clock = std::chrono::steady_clock;
+static double secs_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+static double secs_since(Clock::time_point t0) { return secs_between(t0, Clock::now()); }
+
+static int fail() { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+
 struct Worker {
     int gpu = 0;
     gm_index* ix = nullptr;
@@ -756,19 +740,28 @@ struct Worker {
     double t_pack = 0, t_map = 0, t_out = 0, t_scan = 0;
     gm_sam_sorter* sorter = nullptr;        // --sam_sort=coordinate: where the blocks' rows go instead of a host buffer
     TextPool* stage_pool = nullptr;         // --read_text=device: page-locked buffers a block's FASTQ text is copied into for the upload
+    // the result arrays of a block of n reads, and a gm_hits that points at them (filled again after a capacity retry has made them grow)
+    void ensure_hits(uint32_t n) {
+        status.ensure(n); self_score.ensure(n); top.ensure(n); den.ensure(n); mbegin.ensure((size_t)n + 1);
+        matches.ensure(2 * (size_t)n + 64); positions.ensure(2 * (size_t)n + 64);
+    }
+    void fill(gm_hits& h, uint32_t n) {
+        h.n = n; h.status = status.data(); h.self_score = self_score.data(); h.top_score = top.data();
+        h.denominator = den.data(); h.match_begin = mbegin.data();
+        h.matches = matches.data(); h.matches_cap = matches.size();
+        h.positions = positions.data(); h.positions_cap = positions.size();
+    }
 };
-
-static double secs_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 
 // --read_text=device, before the gate: the block's byte range goes up as it stands and the GPU cuts it (gm_batch_upload_text).  What the host
 // parser would have reported comes back: the records in front of the first malformed (or too long) one, and where that one starts
 static int upload_text_block(Worker& w, const Options& o, const char* base, Block& b, bool* stop, size_t* bad_at, bool* too_long) {
     const size_t bytes = b.text_hi - b.text_lo;
-    auto c0 = std::chrono::steady_clock::now();
+    auto c0 = Clock::now();
     PinVec<char>* stage = w.stage_pool->get();
     stage->ensure(bytes + 1);
     memcpy(stage->data(), base + b.text_lo, bytes);
-    auto c1 = std::chrono::steady_clock::now();
+    auto c1 = Clock::now();
     const bool want_recs = !o.sam_text_device;          // the host formatter prints names, bases and qualities from the mapped file
     if (want_recs) b.trecs.ensure(bytes / 128 + 64);
     gm_text_info ti;
@@ -779,154 +772,104 @@ static int upload_text_block(Worker& w, const Options& o, const char* base, Bloc
         break;
     }
     w.stage_pool->put(stage);
-    w.t_pack += std::chrono::duration<double>(c1 - c0).count(); w.t_map += secs_since(c1);
+    w.t_pack += secs_between(c0, c1); w.t_map += secs_since(c1);
     if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_batch_upload_text: %s\n", gm_last_error()); return rc; }
     b.n = ti.n; b.maxlen = ti.max_len; b.stride = ti.stride; b.text_dev = true;
     if (ti.status == GM_TEXT_MALFORMED) { *stop = true; *bad_at = b.text_lo + (size_t)ti.bad_at; }
     if (ti.status == GM_TEXT_TOO_LONG) {
         const char* nm = base + b.text_lo + (size_t)ti.bad_at;
         const char* e = (const char*)memchr(nm, '\n', b.text_hi - (b.text_lo + (size_t)ti.bad_at));
-        const size_t nl = e ? (size_t)(e - nm) : b.text_hi - (b.text_lo + (size_t)ti.bad_at);
-        fprintf(stderr, "ERROR: read %.*s is longer than 2048 bases\n", (int)std::min<size_t>(nl, 200), nm);
+        report_too_long(nm, e ? (size_t)(e - nm) : b.text_hi - (b.text_lo + (size_t)ti.bad_at));
         *too_long = true;
     }
     return GM_OK;
 }
 
-// the block gm_batch_upload_text left resident: gm_map_batch_text, then the rows as text from the names the parse left in HBM, or the
-// records for the host formatter, which reads the block's names, bases and qualities in the mapped file through the gm_text_rec table
-static int process_text_block(Worker& w, const Options& o, const char* base, Block& b) {
+// a batch call that did not return GM_OK: a block too large for one launch is no error (process_block_split takes it in halves)
+static int batch_call_failed(int rc, const char* call, bool output, uint32_t n) {
+    if (rc == GM_E_BATCH_TOO_LARGE)
+        fprintf(stderr, output ? "note: block of %u reads is written in halves (%s)\n" : "note: block of %u reads is mapped in halves (%s)\n", n, gm_last_error());
+    else fprintf(stderr, "ERROR: %s: %s\n", call, gm_last_error());
+    return rc;
+}
+
+// The two batch calls of one block.  A block the host cut (parse_range*, parse_resync) is packed into rows here; a block gm_batch_upload_text
+// left resident in the worker's batch (b.text_dev) has its rows and names in HBM already, and every call takes its _text / _resident form.
+// The rows go to the sorter, come back as text, or come back as records for the host formatter - which reads a resident block's names,
+// bases and qualities in the mapped file through the gm_text_rec table.
+static int process_block(Worker& w, const Options& o, const char* base, Block& b) {
     const uint32_t n = b.n;
-    w.status.ensure(n); w.self_score.ensure(n); w.top.ensure(n); w.den.ensure(n); w.mbegin.ensure((size_t)n + 1);
-    w.matches.ensure(2 * (size_t)n + 64); w.positions.ensure(2 * (size_t)n + 64);
-    gm_hits hits{};
-    auto c1 = std::chrono::steady_clock::now();
-    for (;;) {
-        hits.n = n; hits.status = w.status.data(); hits.self_score = w.self_score.data(); hits.top_score = w.top.data();
-        hits.denominator = w.den.data(); hits.match_begin = w.mbegin.data();
-        hits.matches = w.matches.data(); hits.matches_cap = w.matches.size();
-        hits.positions = w.positions.data(); hits.positions_cap = w.positions.size();
-        int rc = gm_map_batch_text(w.ix, &o.p, w.batch, &hits, w.stream);
-        if (rc == GM_E_CAPACITY) { w.matches.ensure(hits.matches_cap + 64); w.positions.ensure(hits.positions_cap + 64); continue; }
-        if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is mapped in halves (%s)\n", n, gm_last_error()); return rc; }
-        if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_map_batch_text: %s\n", gm_last_error()); return rc; }
-        break;
+    const bool resident = b.text_dev;
+    gm_params bp = o.p; bp.illumina = b.illumina;
+    auto c0 = Clock::now();
+    gm_reads reads{}; reads.n = n; reads.stride = b.stride;      // (all a call reads of it for a resident block)
+    gm_read_text rt{};
+    if (!resident) {
+        pack_block(b, 4, o.sam_text_device, o.fasta);
+        reads.bases = b.bases.data(); reads.quals = o.fasta ? nullptr : b.qbuf.data(); reads.len = b.plen.data();
+        if (o.sam_text_device) {
+            rt.names = b.names_pool.data(); rt.name_off = b.name_off.data();
+            rt.qual_tail = b.has_qtail ? b.qtail_pool.data() : nullptr; rt.qual_tail_off = b.has_qtail ? b.qtail_off.data() : nullptr;
+        }
     }
-    auto c2 = std::chrono::steady_clock::now();
-    uint64_t n_recs = 0;
+    w.ensure_hits(n);
+    gm_hits hits{};
+    auto c1 = Clock::now();
+    int rc;
+    for (;;) {
+        w.fill(hits, n);
+        rc = resident ? gm_map_batch_text(w.ix, &bp, w.batch, &hits, w.stream) : gm_map_batch(w.ix, &bp, w.batch, &reads, &hits, w.stream);
+        if (rc != GM_E_CAPACITY) break;
+        w.matches.ensure(hits.matches_cap + 64); w.positions.ensure(hits.positions_cap + 64);
+    }
+    if (rc != GM_OK) return batch_call_failed(rc, resident ? "gm_map_batch_text" : "gm_map_batch", false, n);
+    auto c2 = Clock::now();
+    uint64_t n_recs = 0, text_len = 0;
+    const char* call;
     if (o.sam_sort) {                                       // the rows stay in HBM; their number is known when the sorter finishes
-        int rc = gm_output_batch_sorted_resident(w.ix, &o.p, w.batch, &hits, w.sorter, b.sort_seq, w.stream);
-        if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
-        if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch_sorted_resident: %s\n", gm_last_error()); return rc; }
-        b.dtext_len = 0;
-    } else if (o.sam_text_device) {
+        call = resident ? "gm_output_batch_sorted_resident" : "gm_output_batch_sorted";
+        rc = resident ? gm_output_batch_sorted_resident(w.ix, &bp, w.batch, &hits, w.sorter, b.sort_seq, w.stream)
+                      : gm_output_batch_sorted(w.ix, &bp, w.batch, &reads, &rt, &hits, w.sorter, b.sort_seq, w.stream);
+    } else if (o.sam_text_device) {                         // the rows come back as text: no records, no CIGAR pool on the host
+        call = resident ? "gm_output_batch_text_resident" : "gm_output_batch_text";
         if (!b.dtext) b.dtext = w.text_pool->get();
-        b.dtext->ensure(((size_t)n + (size_t)n / 16) * (2 * (size_t)b.maxlen + 64) + (b.text_hi - b.text_lo) + 4096);
+        const size_t name_bytes = resident ? b.text_hi - b.text_lo : (size_t)b.name_off[n];
+        b.dtext->ensure(((size_t)n + (size_t)n / 16) * (2 * (size_t)b.maxlen + 64) + name_bytes + 4096);
         gm_sam_text st;
         for (;;) {
             st.text = b.dtext->data(); st.text_cap = b.dtext->size(); st.text_len = 0; st.n_recs = 0; st.row_off = nullptr; st.row_cap = 0;
-            int rc = gm_output_batch_text_resident(w.ix, &o.p, w.batch, &hits, &st, w.stream);
-            if (rc == GM_E_CAPACITY) { b.dtext->ensure((size_t)st.text_cap + 64); continue; }
-            if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
-            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch_text_resident: %s\n", gm_last_error()); return rc; }
-            break;
+            rc = resident ? gm_output_batch_text_resident(w.ix, &bp, w.batch, &hits, &st, w.stream)
+                          : gm_output_batch_text(w.ix, &bp, w.batch, &reads, &rt, &hits, &st, w.stream);
+            if (rc != GM_E_CAPACITY) break;
+            b.dtext->ensure((size_t)st.text_cap + 64);
         }
-        n_recs = st.n_recs; b.dtext_len = st.text_len;
+        n_recs = st.n_recs; text_len = st.text_len;
     } else {
-        const char* t0 = base + b.text_lo;
-        b.name.resize(n); b.seq.resize(n); b.qual.resize(n); b.name_len.resize(n); b.qual_len.resize(n); b.len.resize(n);
-        for (uint32_t i = 0; i < n; ++i) {
-            const gm_text_rec& r = b.trecs[i];
-            b.name[i] = t0 + r.name_off; b.seq[i] = t0 + r.seq_off; b.qual[i] = t0 + r.qual_off;
-            b.name_len[i] = r.name_len; b.qual_len[i] = r.qual_len; b.len[i] = (uint16_t)r.seq_len;
+        call = "gm_output_batch";
+        if (resident) {
+            const char* t0 = base + b.text_lo;
+            b.name.resize(n); b.seq.resize(n); b.qual.resize(n); b.name_len.resize(n); b.qual_len.resize(n); b.len.resize(n);
+            for (uint32_t i = 0; i < n; ++i) {
+                const gm_text_rec& r = b.trecs[i];
+                b.name[i] = t0 + r.name_off; b.seq[i] = t0 + r.seq_off; b.qual[i] = t0 + r.qual_off;
+                b.name_len[i] = r.name_len; b.qual_len[i] = r.qual_len; b.len[i] = (uint16_t)r.seq_len;
+            }
         }
-        gm_reads reads{}; reads.n = n; reads.stride = b.stride;
         b.recs.ensure((size_t)n + (size_t)n / 4 + 64);
         b.pool.ensure(8 * (size_t)n + 1024);
         gm_sam_out so;
         for (;;) {
             so.recs = b.recs.data(); so.recs_cap = b.recs.size(); so.cigar_pool = b.pool.data(); so.cigar_cap = b.pool.size();
-            int rc = gm_output_batch(w.ix, &o.p, w.batch, &reads, &hits, &so, w.stream);
-            if (rc == GM_E_CAPACITY) { b.recs.ensure(so.recs_cap + 64); b.pool.ensure(so.cigar_cap + 64); continue; }
-            if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
-            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch: %s\n", gm_last_error()); return rc; }
-            break;
+            rc = gm_output_batch(w.ix, &bp, w.batch, &reads, &hits, &so, w.stream);
+            if (rc != GM_E_CAPACITY) break;
+            b.recs.ensure(so.recs_cap + 64); b.pool.ensure(so.cigar_cap + 64);
         }
         n_recs = so.n_recs;
     }
-    b.n_recs = n_recs; b.gpu = w.gpu;
-    w.t_map += std::chrono::duration<double>(c2 - c1).count(); w.t_out += secs_since(c2);
-    w.n_reads += n; w.n_records += n_recs;
-    for (uint32_t i = 0; i < n; ++i) w.n_matched += (w.status[i] == GM_READ_OK || w.status[i] == GM_READ_TOO_MANY);
-    return GM_OK;
-}
-
-static int process_block(Worker& w, const Options& o, Block& b) {
-    const uint32_t n = b.n;
-    gm_params bp = o.p; bp.illumina = b.illumina;
-    auto c0 = std::chrono::steady_clock::now();
-    pack_block(b, 4, o.sam_text_device, o.fasta);
-    gm_reads reads; reads.n = n; reads.stride = b.stride; reads.bases = b.bases.data(); reads.quals = o.fasta ? nullptr : b.qbuf.data(); reads.len = b.plen.data();
-    w.status.ensure(n); w.self_score.ensure(n); w.top.ensure(n); w.den.ensure(n); w.mbegin.ensure((size_t)n + 1);
-    w.matches.ensure(2 * (size_t)n + 64); w.positions.ensure(2 * (size_t)n + 64);
-    gm_hits hits{};
-    auto c1 = std::chrono::steady_clock::now();
-    for (;;) {
-        hits.n = n; hits.status = w.status.data(); hits.self_score = w.self_score.data(); hits.top_score = w.top.data();
-        hits.denominator = w.den.data(); hits.match_begin = w.mbegin.data();
-        hits.matches = w.matches.data(); hits.matches_cap = w.matches.size();
-        hits.positions = w.positions.data(); hits.positions_cap = w.positions.size();
-        int rc = gm_map_batch(w.ix, &bp, w.batch, &reads, &hits, w.stream);
-        if (rc == GM_E_CAPACITY) { w.matches.ensure(hits.matches_cap + 64); w.positions.ensure(hits.positions_cap + 64); continue; }
-        if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is mapped in halves (%s)\n", n, gm_last_error()); return rc; }
-        if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_map_batch: %s\n", gm_last_error()); return rc; }
-        break;
-    }
-    auto c2 = std::chrono::steady_clock::now();
-    if (o.sam_text_device) {                                // the rows come back as text: no records, no CIGAR pool on the host
-        gm_read_text rt; rt.names = b.names_pool.data(); rt.name_off = b.name_off.data();
-        rt.qual_tail = b.has_qtail ? b.qtail_pool.data() : nullptr; rt.qual_tail_off = b.has_qtail ? b.qtail_off.data() : nullptr;
-        if (o.sam_sort) {
-            int rc = gm_output_batch_sorted(w.ix, &bp, w.batch, &reads, &rt, &hits, w.sorter, b.sort_seq, w.stream);
-            if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
-            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch_sorted: %s\n", gm_last_error()); return rc; }
-            b.n_recs = 0; b.dtext_len = 0; b.gpu = w.gpu;
-            w.t_pack += std::chrono::duration<double>(c1 - c0).count(); w.t_map += std::chrono::duration<double>(c2 - c1).count(); w.t_out += secs_since(c2);
-            w.n_reads += n;
-            for (uint32_t i = 0; i < n; ++i) w.n_matched += (w.status[i] == GM_READ_OK || w.status[i] == GM_READ_TOO_MANY);
-            return GM_OK;
-        }
-        if (!b.dtext) b.dtext = w.text_pool->get();
-        b.dtext->ensure(((size_t)n + (size_t)n / 16) * (2 * (size_t)b.maxlen + 64) + (size_t)b.name_off[n] + 4096);
-        gm_sam_text st;
-        for (;;) {
-            st.text = b.dtext->data(); st.text_cap = b.dtext->size(); st.text_len = 0; st.n_recs = 0; st.row_off = nullptr; st.row_cap = 0;
-            int rc = gm_output_batch_text(w.ix, &bp, w.batch, &reads, &rt, &hits, &st, w.stream);
-            if (rc == GM_E_CAPACITY) { b.dtext->ensure((size_t)st.text_cap + 64); continue; }
-            if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
-            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch_text: %s\n", gm_last_error()); return rc; }
-            break;
-        }
-        b.n_recs = st.n_recs; b.dtext_len = st.text_len; b.gpu = w.gpu;
-        w.t_pack += std::chrono::duration<double>(c1 - c0).count(); w.t_map += std::chrono::duration<double>(c2 - c1).count(); w.t_out += secs_since(c2);
-        w.n_reads += n; w.n_records += st.n_recs;
-        for (uint32_t i = 0; i < n; ++i) w.n_matched += (w.status[i] == GM_READ_OK || w.status[i] == GM_READ_TOO_MANY);
-        return GM_OK;
-    }
-    b.recs.ensure((size_t)n + (size_t)n / 4 + 64);
-    b.pool.ensure(8 * (size_t)n + 1024);
-    gm_sam_out so;
-    for (;;) {
-        so.recs = b.recs.data(); so.recs_cap = b.recs.size(); so.cigar_pool = b.pool.data(); so.cigar_cap = b.pool.size();
-        int rc = gm_output_batch(w.ix, &bp, w.batch, &reads, &hits, &so, w.stream);
-        if (rc == GM_E_CAPACITY) { b.recs.ensure(so.recs_cap + 64); b.pool.ensure(so.cigar_cap + 64); continue; }
-        if (rc == GM_E_BATCH_TOO_LARGE) { fprintf(stderr, "note: block of %u reads is written in halves (%s)\n", n, gm_last_error()); return rc; }
-        if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_output_batch: %s\n", gm_last_error()); return rc; }
-        break;
-    }
-    b.n_recs = so.n_recs; b.gpu = w.gpu;
-    w.t_pack += std::chrono::duration<double>(c1 - c0).count(); w.t_map += std::chrono::duration<double>(c2 - c1).count(); w.t_out += secs_since(c2);
-    w.n_reads += n; w.n_records += so.n_recs;
+    if (rc != GM_OK) return batch_call_failed(rc, call, true, n);        // (nothing is booked: the halves book themselves)
+    b.n_recs = n_recs; b.dtext_len = text_len; b.gpu = w.gpu;
+    w.t_pack += secs_between(c0, c1); w.t_map += secs_between(c1, c2); w.t_out += secs_since(c2);
+    w.n_reads += n; w.n_records += n_recs;                  // (sorted: no records here, main takes their number from the sorter)
     for (uint32_t i = 0; i < n; ++i) w.n_matched += (w.status[i] == GM_READ_OK || w.status[i] == GM_READ_TOO_MANY);
     return GM_OK;
 }
@@ -934,7 +877,7 @@ static int process_block(Worker& w, const Options& o, Block& b) {
 // a block whose intermediate lists outgrow one launch (GM_E_BATCH_TOO_LARGE: e.g. > 2^31 candidates on a repeat-rich reference
 // without -h) is mapped as two halves, recursively; the halves' records are put back together in read order
 static int process_block_split(Worker& w, const Options& o, const char* base, Block& b, int depth) {
-    int rc = b.text_dev ? process_text_block(w, o, base, b) : process_block(w, o, b);
+    int rc = process_block(w, o, base, b);
     if (rc != GM_E_BATCH_TOO_LARGE || b.n < 2 || depth > 20) return rc;
     if (b.text_dev) {                                       // a text block that is too large: the host parser cuts the same records, and the halves go the host's way
         size_t cur = b.text_lo, bad_at = 0; bool stop = false, too_long = false;
@@ -954,10 +897,7 @@ static int process_block_split(Worker& w, const Options& o, const char* base, Bl
         c.qual.assign(b.qual.begin() + lo, b.qual.begin() + hi); c.name_len.assign(b.name_len.begin() + lo, b.name_len.begin() + hi);
         c.qual_len.assign(b.qual_len.begin() + lo, b.qual_len.begin() + hi); c.len.assign(b.len.begin() + lo, b.len.begin() + hi);
         if (!b.kept.empty()) c.kept.assign(b.kept.begin() + lo, b.kept.begin() + hi);
-        if (part && b.illumina) {                           // the fallback may have happened inside the first half
-            for (uint32_t i = 0; i < half && c.illumina; ++i)
-                for (uint32_t t = 0; t < (b.kept.empty() ? b.len[i] : b.kept[i]); ++t) if ((signed char)b.qual[i][t] < 64) { c.illumina = 0; break; }      // (the reference's quality characters are signed chars)
-        }
+        if (part && b.illumina && b.has_quality_below_64(half)) c.illumina = 0;      // the fallback may have happened inside the first half
         rc = process_block_split(w, o, base, c, depth + 1);
         if (rc != GM_OK) { w.text_pool->put(c.dtext); return rc; }
         if (o.sam_text_device) {                            // rows are text already: the halves' text, one behind the other
@@ -971,401 +911,459 @@ static int process_block_split(Worker& w, const Options& o, const char* base, Bl
         pool.insert(pool.end(), c.pool.data(), c.pool.data() + used);
         pool_len += used; total += c.n_recs;
     }
-    if (o.sam_sort) { b.dtext_len = 0; b.n_recs = total; b.gpu = w.gpu; return GM_OK; }      // each half went into the sorter under its own sequence number
-    if (o.sam_text_device) {
+    if (o.sam_sort) b.dtext_len = 0;                        // each half went into the sorter under its own sequence number
+    else if (o.sam_text_device) {
         if (!b.dtext) b.dtext = w.text_pool->get();
         b.dtext->ensure(text.size() + 1);
         if (!text.empty()) memcpy(b.dtext->data(), text.data(), text.size());
-        b.dtext_len = text.size(); b.n_recs = total; b.gpu = w.gpu;
-        return GM_OK;
+        b.dtext_len = text.size();
+    } else {
+        b.recs.ensure(recs.size() + 1); b.pool.ensure(pool.size() + 1);
+        if (!recs.empty()) memcpy(b.recs.data(), recs.data(), recs.size() * sizeof(gm_sam_rec));
+        if (!pool.empty()) memcpy(b.pool.data(), pool.data(), pool.size());
     }
-    b.recs.ensure(recs.size() + 1); b.pool.ensure(pool.size() + 1);
-    if (!recs.empty()) memcpy(b.recs.data(), recs.data(), recs.size() * sizeof(gm_sam_rec));
-    if (!pool.empty()) memcpy(b.pool.data(), pool.data(), pool.size());
     b.n_recs = total; b.gpu = w.gpu;
     return GM_OK;
 }
 
-int main(int argc, char** argv) {
+// ---- the run: what lives from the first step of main() to the last ---------------------------------------------------------------------
+static const size_t NPOS = ~(size_t)0;
+
+struct Run {
     Options o;
-    parse_args(argc, argv, o);
-    std::string cl;
-    for (int i = 0; i < argc; ++i) { cl += argv[i]; cl += " "; }      // Driver.cpp:1032-1039
-    auto t0 = std::chrono::steady_clock::now();
-    // the read file's format from its first byte, as SeqReader::find_type (src/SeqReader.cpp:175-244) - and what a FASTA input rules out -
-    // before the device is opened
-    FastqScanner fq;
-    char fasta_qual[256];
-    const bool reads_open = fq.open(o.reads);
-    if (reads_open && fq.size) {
-        if (fq.base[0] == '>') {
-            o.fasta = true;
-            if (!o.adaptor.empty()) {
-                fprintf(stderr, "ERROR: -A/--adaptor with FASTA reads is not supported (the reference trims FASTA reads with the PWM-based FixReads, a different rule); use FASTQ reads\n");
-                return 1;
-            }
-            if (o.p.mode == GM_MODE_SNP) { fprintf(stderr, "ERROR: --snp with FASTA reads is not supported; use FASTQ reads\n"); return 1; }
-            if (o.read_text_device) { fprintf(stderr, "ERROR: --read_text=device cuts FASTQ only; FASTA reads are cut by the host (--read_text=host)\n"); return 1; }
-            if (!fasta_check(fq.base, fq.size, o.reads.c_str())) return 1;
-            o.p.illumina = 0;                                  // accepted and ignored, as in the reference
-            fasta_qual_table(fasta_qual);
-            fq.fasta = true; fq.fasta_qual = fasta_qual;
-        } else if (fq.base[0] != '@') {
-            fprintf(stderr, "ERROR: %s starts with neither '@' (FASTQ) nor '>' (FASTA): the _prb.txt and _int.txt read formats are not supported\n", o.reads.c_str());
+    std::string cl;                                 // the command line, for @PG (Driver.cpp:1032-1039)
+    Clock::time_point t0, t_pipe0;
+    FastqScanner fq; bool reads_open = false; char fasta_qual[256];
+    std::vector<gm_index*> gpu_ix; gm_index_info info;
+    std::vector<Worker> workers;
+    gm_sam_sorter* sorter = nullptr; uint64_t sorted_rows = 0;
+    TextPool text_pool, stage_pool;
+    // one <out>.sam, or --sam_shards=K files <out>.<k>.sam: every shard has its own descriptor and offset counter (no two share an inode)
+    std::vector<int> ofds; std::vector<uint64_t> file_offs;
+    std::atomic<int> failed{ 0 };
+    double t_index = 0, t_scan = 0, t_fmt = 0, t_write = 0;     // t_scan: the scanner thread's; t_fmt, t_write: summed under their locks
+    std::mutex fmt_mu, tw_mu;                       // (t_write is summed by several writers with --sam_shards)
+    uint64_t seq_base = 0;                          // --sam_sort: blocks handed out by the passes before this one
+    bool file_order() const { return o.batch_set || o.p.illumina; }
+};
+
+static bool write_all(int fd, const char* p, size_t n) {
+    while (n) { ssize_t k = ::write(fd, p, n); if (k <= 0) return false; p += k; n -= (size_t)k; }
+    return true;
+}
+static bool pwrite_all(int fd, const char* p, size_t n, uint64_t off) {
+    while (n) { ssize_t k = ::pwrite(fd, p, n, (off_t)off); if (k <= 0) return false; p += k; n -= (size_t)k; off += (uint64_t)k; }
+    return true;
+}
+
+// the read file's format from its first byte, as SeqReader::find_type (src/SeqReader.cpp:175-244) - and what a FASTA input rules out -
+// before the device is opened
+static int detect_read_format(Run& R) {
+    Options& o = R.o; FastqScanner& fq = R.fq;
+    R.reads_open = fq.open(o.reads);
+    if (!R.reads_open || !fq.size) return 0;
+    if (fq.base[0] == '>') {
+        o.fasta = true;
+        if (!o.adaptor.empty()) {
+            fprintf(stderr, "ERROR: -A/--adaptor with FASTA reads is not supported (the reference trims FASTA reads with the PWM-based FixReads, a different rule); use FASTQ reads\n");
             return 1;
         }
+        if (o.p.mode == GM_MODE_SNP) { fprintf(stderr, "ERROR: --snp with FASTA reads is not supported; use FASTQ reads\n"); return 1; }
+        if (o.read_text_device) { fprintf(stderr, "ERROR: --read_text=device cuts FASTQ only; FASTA reads are cut by the host (--read_text=host)\n"); return 1; }
+        if (!fasta_check(fq.base, fq.size, o.reads.c_str())) return 1;
+        o.p.illumina = 0;                                  // accepted and ignored, as in the reference
+        fasta_qual_table(R.fasta_qual);
+        fq.fasta = true; fq.fasta_qual = R.fasta_qual;
+    } else if (fq.base[0] != '@') {
+        fprintf(stderr, "ERROR: %s starts with neither '@' (FASTQ) nor '>' (FASTA): the _prb.txt and _int.txt read formats are not supported\n", o.reads.c_str());
+        return 1;
     }
+    return 0;
+}
+
+// the index (built once if missing, then one replica per GPU), the sorter, and per GPU `--workers` batches with a stream each
+static int open_devices(Run& R) {
+    const Options& o = R.o;
     const int flags = GM_INDEX_BUILD | (o.locate_sampled ? 0 : GM_INDEX_FULL_SA);
-    std::vector<gm_index*> gpu_ix((size_t)o.gpus, nullptr);
-    {   // build once if missing, then one replica per GPU
-        if (gm_index_open(o.genome.c_str(), 0, flags, &gpu_ix[0]) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
-        for (int g = 1; g < o.gpus; ++g)
-            if (gm_index_open(o.genome.c_str(), g, flags, &gpu_ix[(size_t)g]) != GM_OK) { fprintf(stderr, "ERROR: GPU %d: %s\n", g, gm_last_error()); return 1; }
-    }
+    R.gpu_ix.assign((size_t)o.gpus, nullptr);
+    if (gm_index_open(o.genome.c_str(), 0, flags, &R.gpu_ix[0]) != GM_OK) return fail();
+    for (int g = 1; g < o.gpus; ++g)
+        if (gm_index_open(o.genome.c_str(), g, flags, &R.gpu_ix[(size_t)g]) != GM_OK) { fprintf(stderr, "ERROR: GPU %d: %s\n", g, gm_last_error()); return 1; }
     for (int g = 0; g < o.gpus; ++g)                                   // k-mer tables / records for these parameters: part of staging the index
-        if (gm_index_prepare(gpu_ix[(size_t)g], &o.p) != GM_OK) { fprintf(stderr, "ERROR: GPU %d: %s\n", g, gm_last_error()); return 1; }
-    gm_sam_sorter* sorter = nullptr;
-    if (o.sam_sort && gm_sam_sorter_create(gpu_ix[0], &sorter) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
-    std::vector<Worker> workers((size_t)o.gpus * (size_t)o.workers);
-    TextPool text_pool, stage_pool;
+        if (gm_index_prepare(R.gpu_ix[(size_t)g], &o.p) != GM_OK) { fprintf(stderr, "ERROR: GPU %d: %s\n", g, gm_last_error()); return 1; }
+    if (o.sam_sort && gm_sam_sorter_create(R.gpu_ix[0], &R.sorter) != GM_OK) return fail();
+    R.workers = std::vector<Worker>((size_t)o.gpus * (size_t)o.workers);
     for (int g = 0; g < o.gpus; ++g) {
-        if (gm_coverage_reset(gpu_ix[(size_t)g], (uint32_t)o.p.bin_size) != GM_OK ||
-            (o.p.mode != GM_MODE_NORMAL && gm_coverage_enable_nuc(gpu_ix[(size_t)g]) != GM_OK)) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+        gm_index* ix = R.gpu_ix[(size_t)g];
+        if (gm_coverage_reset(ix, (uint32_t)o.p.bin_size) != GM_OK || (o.p.mode != GM_MODE_NORMAL && gm_coverage_enable_nuc(ix) != GM_OK)) return fail();
         for (int k = 0; k < o.workers; ++k) {
-            Worker& w = workers[(size_t)g * (size_t)o.workers + (size_t)k];
-            w.gpu = g; w.ix = gpu_ix[(size_t)g]; w.text_pool = &text_pool; w.stage_pool = &stage_pool; w.sorter = sorter;
+            Worker& w = R.workers[(size_t)g * (size_t)o.workers + (size_t)k];
+            w.gpu = g; w.ix = ix; w.text_pool = &R.text_pool; w.stage_pool = &R.stage_pool; w.sorter = R.sorter;
             if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK ||
                 gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK ||
-                gm_batch_set_read_format(w.batch, o.fasta ? GM_READS_FASTA : GM_READS_FASTQ) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+                gm_batch_set_read_format(w.batch, o.fasta ? GM_READS_FASTA : GM_READS_FASTQ) != GM_OK) return fail();
         }
     }
-    gm_index_info info;
-    gm_index_get_info(gpu_ix[0], &info);
-    const double t_index = secs_since(t0);
+    gm_index_get_info(R.gpu_ix[0], &R.info);
+    R.t_index = secs_since(R.t0);
     if (o.verbose > 0)
         fprintf(stderr, "gnumap-mi355x: genome %s (%lu bp, %u contigs), %s locate, %d GPU(s), index %.1f MB in HBM\n", o.genome.c_str(),
-                (unsigned long)info.l_pac, info.n_seqs, info.full_sa ? "full-SA" : "sampled-SA", o.gpus, info.hbm_bytes / 1e6);
+                (unsigned long)R.info.l_pac, R.info.n_seqs, R.info.full_sa ? "full-SA" : "sampled-SA", o.gpus, R.info.hbm_bytes / 1e6);
     if (o.verbose > 0 && !o.adaptor.empty()) fprintf(stderr, "\tUsing Adaptor Sequence: %s\n", o.adaptor.c_str());      // Driver.cpp:1231-1233
-    // one <out>.sam, or --sam_shards=K files <out>.<k>.sam: every shard has its own descriptor and offset counter (no two share an inode)
+    return 0;
+}
+
+// <out>.sam or the K shard files, and the header lines in the first (or only) one
+static int open_outputs(Run& R) {
+    const Options& o = R.o;
     const int K = o.sam_shards;
-    std::vector<int> ofds((size_t)K, -1);
-    std::vector<uint64_t> file_offs((size_t)K, 0);
+    R.ofds.assign((size_t)K, -1);
+    R.file_offs.assign((size_t)K, 0);
     for (int k = 0; k < K; ++k) {
         const std::string fn = K == 1 ? o.output + ".sam" : o.output + "." + std::to_string(k) + ".sam";
-        ofds[(size_t)k] = ::open(fn.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (ofds[(size_t)k] < 0) { fprintf(stderr, "ERROR: cannot write %s\n", fn.c_str()); return 1; }
+        R.ofds[(size_t)k] = ::open(fn.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (R.ofds[(size_t)k] < 0) { fprintf(stderr, "ERROR: cannot write %s\n", fn.c_str()); return 1; }
     }
-    const int ofd = ofds[0];                                             // the header lines go to the first (or only) file
-    auto write_all = [&](const char* p, size_t n) {
-        while (n) { ssize_t k = ::write(ofd, p, n); if (k <= 0) return false; p += k; n -= (size_t)k; }
-        return true;
-    };
-    {
-        std::ostringstream hd;
-        if (o.sam_sort) hd << "@HD\tVN:1.0\tSO:coordinate\n";
-        for (uint32_t i = 0; i < info.n_seqs; ++i)                     // Driver.cpp:2322-2327
-            hd << "@SQ\tSN:" << gm_index_contig_name(gpu_ix[0], i) << "\tLN:"
-               << (gm_index_contig_offset(gpu_ix[0], i + 1) - gm_index_contig_offset(gpu_ix[0], i)) << "\n";
-        hd << "@PG\tID:gnumap\tPN:gnumap\tVN:4.0.0 BETA\tCL:" << cl << "\n";
-        const std::string s = hd.str();
-        if (!write_all(s.data(), s.size())) { fprintf(stderr, "ERROR: write failed\n"); return 1; }
-    }
+    std::ostringstream hd;
+    if (o.sam_sort) hd << "@HD\tVN:1.0\tSO:coordinate\n";
+    for (uint32_t i = 0; i < R.info.n_seqs; ++i)                       // Driver.cpp:2322-2327
+        hd << "@SQ\tSN:" << gm_index_contig_name(R.gpu_ix[0], i) << "\tLN:"
+           << (gm_index_contig_offset(R.gpu_ix[0], i + 1) - gm_index_contig_offset(R.gpu_ix[0], i)) << "\n";
+    hd << "@PG\tID:gnumap\tPN:gnumap\tVN:4.0.0 BETA\tCL:" << R.cl << "\n";
+    const std::string s = hd.str();
+    if (!write_all(R.ofds[0], s.data(), s.size())) { fprintf(stderr, "ERROR: write failed\n"); return 1; }
+    return 0;
+}
 
-    auto t_pipe0 = std::chrono::steady_clock::now();
-    if (!reads_open) { fprintf(stderr, "ERROR: cannot open %s\n", o.reads.c_str()); return 1; }
-    std::atomic<int> failed{ 0 };
-    double t_scan = 0, t_fmt = 0, t_write = 0;
-    { struct stat hs; if (fstat(ofd, &hs) == 0) file_offs[0] = (uint64_t)lseek(ofd, 0, SEEK_CUR); }
-    auto pwrite_all = [&](int fd, const char* p, size_t n, uint64_t off) {
-        while (n) { ssize_t k = ::pwrite(fd, p, n, (off_t)off); if (k <= 0) return false; p += k; n -= (size_t)k; off += (uint64_t)k; }
-        return true;
-    };
-    std::mutex tw_mu;                                                    // t_write is summed by several writers with --sam_shards
-    // (Tried in round 4: the pieces copied in through shared mappings of the file's byte ranges instead - no inode write lock, which is
-    // what holds buffered pwrite()s to ONE file to the rate of one thread, 8.4-8.8 GB/s whatever the number of writers.  4 x SLOWER on the
-    // GPU box's file system: 2.1 M first-touch page faults of a growing file cost more than the copies.  The write calls stay.)
-    const size_t npos = ~(size_t)0;
-    uint64_t seq_base = 0;                                               // --sam_sort: blocks handed out by the passes before this one
-    // One pass of the pipeline over the FASTQ text from fq.at on.  chunks = byte ranges cut into records by the workers in parallel
-    // (well-formed records only); returns where a malformed record starts (npos: none) - everything before it has been mapped and
-    // written, nothing after it has touched the SAM file or the coverage track: a block is mapped only once every block before it is
-    // known to be well-formed.  !chunks = file order with the reference's recovery from malformed records (--batch=N, --illumina - its
-    // fallback is a property of the reads in file order -, and the rest of an input in which a malformed record was found).
-    auto run_pass = [&](const bool chunks) -> size_t {
-        const size_t n_blocks = workers.size() * 2 + 4;                    // blocks in flight
-        std::vector<Block> blocks(n_blocks);
-        Queue<Block*> free_q, map_q, fmt_q;
+// ---- one pass of the pipeline -----------------------------------------------------------------------------------------------------------
+// The gate of chunk mode: nothing of a block reaches the GPU before every block below it is known to be well-formed.
+struct ParseGate {
+    std::mutex mu; std::condition_variable cv;
+    uint64_t parsed = 0; std::set<uint64_t> done;          // `parsed` = every block below it has been cut into records
+    std::atomic<uint64_t> stop{ ~0ull }; size_t bad_at = NPOS;      // the first block with a malformed record, and where that record starts
+    bool stopped() const { return stop.load() != ~0ull; }  // (the scanner asks without the lock)
+    // Block `index` has been cut into records (`malformed`: up to a malformed record at `at`).  Returns once the block may go on (true) or is
+    // known to lie behind a malformed record (false: dropped, the next pass reads it again); a failed run lets everything through.
+    bool pass(uint64_t index, bool malformed, size_t at, const std::atomic<int>& failed) {
+        std::unique_lock<std::mutex> lk(mu);
+        if (malformed && index < stop) { stop = index; bad_at = at; }
+        done.insert(index);
+        while (done.count(parsed)) { done.erase(parsed); ++parsed; }
+        cv.notify_all();
+        cv.wait(lk, [&] { return parsed >= index || stop < index || failed.load(); });
+        return !(stop < index);
+    }
+};
+
+// The writer only hands out file offsets in block order; the text pieces of a block (one per formatter slice, or cuts of the
+// device's text) are written by pwrite() from a few threads at once (a single write() stream tops out at ~8 GB/s of page-cache
+// copies).  --sam_shards=K: a block belongs to the shard of its first byte in the input, which only grows with the block index,
+// so blocks keep their order inside a shard; the writer then only assigns (shard, offsets) and the shard's own writer thread does
+// the writing, side by side with the other shards'.
+// (Tried in round 4: the pieces copied in through shared mappings of the file's byte ranges instead - no inode write lock, which is
+// what holds buffered pwrite()s to ONE file to the rate of one thread, 8.4-8.8 GB/s whatever the number of writers.  4 x SLOWER on the
+// GPU box's file system: 2.1 M first-touch page faults of a growing file cost more than the copies.  The write calls stay.)
+struct Piece { const char* p; size_t n; uint64_t off; };
+struct WriteJob { Block* b; int shard; std::vector<Piece> pieces; };
+
+// One pass over the FASTQ text from fq.at on.  chunks = byte ranges cut into records by the workers in parallel (well-formed records
+// only); run() returns where a malformed record starts (NPOS: none) - everything before it has been mapped and written, nothing after it
+// has touched the SAM file or the coverage track.  !chunks = file order with the reference's recovery from malformed records (--batch=N,
+// --illumina - its fallback is a property of the reads in file order -, and the rest of an input in which a malformed record was found).
+// Members are grouped by the two stages they link; of the Run, a stage uses what its body names.
+struct Pass {
+    static const int N_FMT = 2;
+    Run& R; const Options& o; FastqScanner& fq; const bool chunks;
+    // the pool of blocks in flight: scanner <- writers
+    std::vector<Block> blocks; Queue<Block*> free_q;
+    // scanner -> workers (the gate: among the workers, and its stop flag back to the scanner)
+    Queue<Block*> map_q; ParseGate gate; uint64_t idx_end = 0;
+    // workers -> formatters
+    Queue<Block*> fmt_q; std::atomic<int> live_workers;
+    // formatters -> writer: blocks by index
+    std::mutex wr_mu; std::condition_variable wr_cv; std::map<uint64_t, Block*> ready; bool fmt_done = false; std::atomic<int> live_fmt{ N_FMT };
+    // writer -> shard writers (--sam_shards above 1)
+    std::vector<std::unique_ptr<Queue<WriteJob*>>> shard_q; std::vector<std::thread> shard_th;
+
+    Pass(Run& run, bool chunk_mode) : R(run), o(run.o), fq(run.fq), chunks(chunk_mode), blocks(run.workers.size() * 2 + 4), live_workers((int)run.workers.size()) {
         for (auto& b : blocks) free_q.push(&b);
-        std::mutex fmt_mu;
-        // the gate of chunk mode: `parsed` = every block below it has been cut into records; `stop` = first block with a malformed record
-        struct { std::mutex mu; std::condition_variable cv; uint64_t parsed = 0; std::set<uint64_t> done; uint64_t stop = ~0ull; size_t bad_at = ~(size_t)0; } gate;
-        std::atomic<uint64_t> stop_block{ ~0ull };
+    }
 
-        uint64_t idx_end = 0;
-        std::thread scanner([&] {
-            uint64_t idx = 0;
-            int ill_state = o.p.illumina;
-            Block* b;
-            while (!failed && stop_block.load() == ~0ull && free_q.pop(b)) {
-                auto s0 = std::chrono::steady_clock::now();
-                b->lazy = false; b->malformed = false; b->text_dev = false;
-                bool too_long = false;
-                b->first_byte = fq.at;
-                const bool more = chunks ? fq.next_chunk(*b, o.batch) : fq.next(*b, o.batch, &too_long);
-                t_scan += secs_since(s0);
-                if (too_long) failed = 1;
-                if (!more || failed) { free_q.push(b); break; }
-                b->index = idx++; b->failed = false;
-                b->sort_seq = (seq_base + b->index) << 21;
-                b->illumina = ill_state;
-                b->kept.clear();
-                if (ill_state && !o.adaptor.empty()) {      // -A: the fallback scan sees only the characters the trim keeps (SeqReader.cpp:1152)
-                    std::vector<uint8_t> rows((size_t)b->n * b->stride, 0);
-                    for (uint32_t i = 0; i < b->n; ++i) memcpy(&rows[(size_t)i * b->stride], b->seq[i], b->len[i]);
-                    gm_reads rr; rr.n = b->n; rr.stride = b->stride; rr.bases = rows.data(); rr.quals = nullptr; rr.len = b->len.data();
-                    b->kept.resize(b->n);
-                    if (gm_dev_adaptor_trim(gpu_ix[0], &rr, o.adaptor.c_str(), b->kept.data()) != GM_OK) { fprintf(stderr, "ERROR: gm_dev_adaptor_trim: %s\n", gm_last_error()); failed = 1; free_q.push(b); break; }
-                }
-                if (ill_state)                              // gILLUMINA is cleared for the rest of the run by the first quality below '@'
-                    for (uint32_t i = 0; i < b->n && ill_state; ++i)
-                        for (uint32_t t = 0; t < (b->kept.empty() ? b->len[i] : b->kept[i]); ++t) if ((signed char)b->qual[i][t] < 64) { ill_state = 0; break; }
-                map_q.push(b);
+    void scan() {
+        uint64_t idx = 0;
+        int ill_state = o.p.illumina;
+        Block* b;
+        while (!R.failed && !gate.stopped() && free_q.pop(b)) {
+            auto s0 = Clock::now();
+            b->lazy = false; b->text_dev = false;
+            bool too_long = false;
+            b->first_byte = fq.at;
+            const bool more = chunks ? fq.next_chunk(*b, o.batch) : fq.next(*b, o.batch, &too_long);
+            R.t_scan += secs_since(s0);
+            if (too_long) R.failed = 1;
+            if (!more || R.failed) { free_q.push(b); break; }
+            b->index = idx++; b->failed = false;
+            b->sort_seq = (R.seq_base + b->index) << 21;
+            b->illumina = ill_state;
+            b->kept.clear();
+            if (ill_state && !o.adaptor.empty()) {      // -A: the fallback scan sees only the characters the trim keeps (SeqReader.cpp:1152)
+                std::vector<uint8_t> rows((size_t)b->n * b->stride, 0);
+                for (uint32_t i = 0; i < b->n; ++i) memcpy(&rows[(size_t)i * b->stride], b->seq[i], b->len[i]);
+                gm_reads rr; rr.n = b->n; rr.stride = b->stride; rr.bases = rows.data(); rr.quals = nullptr; rr.len = b->len.data();
+                b->kept.resize(b->n);
+                const int rc = gm_dev_adaptor_trim(R.gpu_ix[0], &rr, o.adaptor.c_str(), b->kept.data());
+                if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_dev_adaptor_trim: %s\n", gm_last_error()); R.failed = 1; free_q.push(b); break; }
             }
-            idx_end = idx;
-            map_q.close();
-        });
-        std::vector<std::thread> wth;
-        std::atomic<int> live_workers{ (int)workers.size() };
-        for (size_t k = 0; k < workers.size(); ++k)
-            wth.emplace_back([&, k] {
-                Worker& w = workers[k];
-                Block* b;
-                while (map_q.pop(b)) {
-                    if (b->lazy) {                              // chunk mode: this worker cuts its byte range into records
-                        auto s0 = std::chrono::steady_clock::now();
-                        size_t cur = b->text_lo, bad_at = npos; bool stop = false, too_long = false;
-                        if (o.fasta) FastqScanner::parse_range_fasta(fq.base, cur, b->text_hi, *b, 16000000u, &too_long, fq.fasta_qual);
-                        else if (o.read_text_device && b->text_hi - b->text_lo < ((size_t)1 << 32)) {
-                            if (upload_text_block(w, o, fq.base, *b, &stop, &bad_at, &too_long) != GM_OK) { failed = 1; b->n = 0; }
-                        }
-                        else FastqScanner::parse_range(fq.base, cur, b->text_hi, *b, 16000000u, &stop, &bad_at, &too_long);
-                        if (too_long) failed = 1;
-                        if (!b->text_dev) w.t_scan += secs_since(s0);      // (a text block's staging and upload are booked by upload_text_block)
-                        bool drop;
-                        {
-                            std::unique_lock<std::mutex> lk(gate.mu);
-                            if (stop && b->index < gate.stop) { gate.stop = b->index; gate.bad_at = bad_at; stop_block = b->index; b->malformed = true; }
-                            gate.done.insert(b->index);
-                            while (gate.done.count(gate.parsed)) { gate.done.erase(gate.parsed); ++gate.parsed; }
-                            gate.cv.notify_all();
-                            // nothing of this block reaches the GPU before every block below it is known to be well-formed
-                            gate.cv.wait(lk, [&] { return gate.parsed >= b->index || gate.stop < b->index || failed.load(); });
-                            drop = gate.stop < b->index;
-                        }
-                        if (drop) b->n = 0;
-                    }
-                    if (b->n == 0) { b->n_recs = 0; fmt_q.push(b); continue; }
-                    if (!failed && process_block_split(w, o, fq.base, *b, 0) != GM_OK) { failed = 1; gate.cv.notify_all(); }
-                    if (failed) { b->failed = true; b->n_recs = 0; }
-                    fmt_q.push(b);
+            if (ill_state && b->has_quality_below_64(b->n)) ill_state = 0;      // gILLUMINA is cleared for the rest of the run by the first quality below '@'
+            map_q.push(b);
+        }
+        idx_end = idx;
+        map_q.close();
+    }
+
+    void work(Worker& w) {
+        Block* b;
+        while (map_q.pop(b)) {
+            if (b->lazy) {                              // chunk mode: this worker cuts its byte range into records
+                auto s0 = Clock::now();
+                size_t cur = b->text_lo, bad_at = NPOS; bool stop = false, too_long = false;
+                if (o.fasta) FastqScanner::parse_range_fasta(fq.base, cur, b->text_hi, *b, 16000000u, &too_long, fq.fasta_qual);
+                else if (o.read_text_device && b->text_hi - b->text_lo < ((size_t)1 << 32)) {
+                    if (upload_text_block(w, o, fq.base, *b, &stop, &bad_at, &too_long) != GM_OK) { R.failed = 1; b->n = 0; }
                 }
-                if (--live_workers == 0) fmt_q.close();
-            });
-        // formatters: a block is cut into slices of records, one string each; the writer emits blocks in index order
-        std::mutex wr_mu; std::condition_variable wr_cv; std::map<uint64_t, Block*> ready; bool fmt_done = false;
-        const int n_fmt = 2;
-        std::atomic<int> live_fmt{ n_fmt };
-        std::vector<std::thread> fth;
-        for (int f = 0; f < n_fmt; ++f)
-            fth.emplace_back([&] {
-                Block* b;
-                while (fmt_q.pop(b)) {
-                    auto f0 = std::chrono::steady_clock::now();
-                    const gm_index* ix = gpu_ix[(size_t)b->gpu];
-                    const uint32_t nr = (uint32_t)b->n_recs;
-                    const int T = o.fmt_threads;
-                    if ((int)b->text.size() < T) b->text.resize((size_t)T);
-                    for (auto& s : b->text) s.clear();
-                    if (!o.sam_text_device)                  // (device: the block's text is there already, b->dtext)
-                    run_slices(nr, T, 4096, [&](int s, uint32_t lo, uint32_t hi) {
-                        TextBuf& out = b->text[(size_t)s];
-                        out.room((size_t)(hi - lo) * 320);
-                        for (uint32_t k = lo; k < hi; ++k) { const gm_sam_rec& r = b->recs[k]; format_sam(out, ix, o.p, r, b->pool.data() + r.cigar_off, *b); }
-                    });
-                    { std::lock_guard<std::mutex> lk(fmt_mu); t_fmt += secs_since(f0); }
-                    { std::lock_guard<std::mutex> lk(wr_mu); ready[b->index] = b; }
-                    wr_cv.notify_all();
+                else FastqScanner::parse_range(fq.base, cur, b->text_hi, *b, 16000000u, &stop, &bad_at, &too_long);
+                if (too_long) R.failed = 1;
+                if (!b->text_dev) w.t_scan += secs_since(s0);      // (a text block's staging and upload are booked by upload_text_block)
+                if (!gate.pass(b->index, stop, bad_at, R.failed)) b->n = 0;
+            }
+            if (b->n == 0) { b->n_recs = 0; fmt_q.push(b); continue; }
+            if (!R.failed && process_block_split(w, o, fq.base, *b, 0) != GM_OK) { R.failed = 1; gate.cv.notify_all(); }
+            if (R.failed) { b->failed = true; b->n_recs = 0; }
+            fmt_q.push(b);
+        }
+        if (--live_workers == 0) fmt_q.close();
+    }
+
+    // formatters: a block is cut into slices of records, one string each; the writer emits blocks in index order
+    void format() {
+        Block* b;
+        while (fmt_q.pop(b)) {
+            auto f0 = Clock::now();
+            const gm_index* ix = R.gpu_ix[(size_t)b->gpu];
+            const uint32_t nr = (uint32_t)b->n_recs;
+            const int T = o.fmt_threads;
+            if ((int)b->text.size() < T) b->text.resize((size_t)T);
+            for (auto& s : b->text) s.clear();
+            if (!o.sam_text_device)                  // (device: the block's text is there already, b->dtext)
+                run_slices(nr, T, 4096, [&](int s, uint32_t lo, uint32_t hi) {
+                    TextBuf& out = b->text[(size_t)s];
+                    out.room((size_t)(hi - lo) * 320);
+                    for (uint32_t k = lo; k < hi; ++k) { const gm_sam_rec& r = b->recs[k]; format_sam(out, ix, o.p, r, b->pool.data() + r.cigar_off, *b); }
+                });
+            { std::lock_guard<std::mutex> lk(R.fmt_mu); R.t_fmt += secs_since(f0); }
+            { std::lock_guard<std::mutex> lk(wr_mu); ready[b->index] = b; }
+            wr_cv.notify_all();
+        }
+        if (--live_fmt == 0) { { std::lock_guard<std::mutex> lk(wr_mu); fmt_done = true; } wr_cv.notify_all(); }
+    }
+
+    void write_job(WriteJob& j) {
+        auto w0 = Clock::now();
+        const int fd = R.ofds[(size_t)j.shard];
+        const int nt = (int)std::min<size_t>(8, j.pieces.size());
+        std::atomic<size_t> nextp{ 0 }; std::atomic<int> bad{ 0 };
+        auto job = [&] { for (size_t k; (k = nextp++) < j.pieces.size();) if (j.pieces[k].n && !pwrite_all(fd, j.pieces[k].p, j.pieces[k].n, j.pieces[k].off)) bad = 1; };
+        std::vector<std::thread> ws;
+        for (int t = 1; t < nt; ++t) ws.emplace_back(job);
+        job();
+        for (auto& x : ws) x.join();
+        if (bad) { fprintf(stderr, "ERROR: write failed\n"); R.failed = 1; }
+        { std::lock_guard<std::mutex> lk(R.tw_mu); R.t_write += secs_since(w0); }
+    }
+    void release(Block* b) { R.text_pool.put(b->dtext); b->dtext = nullptr; free_q.push(b); }       // the rows are written (or there are none)
+    void shard_write(Queue<WriteJob*>* q) { WriteJob* j; while (q->pop(j)) { write_job(*j); release(j->b); delete j; } }
+
+    void write() {
+        const int K = o.sam_shards;
+        const size_t in_size = fq.size;
+        uint64_t next = 0;
+        for (;;) {
+            Block* b = nullptr;
+            {
+                std::unique_lock<std::mutex> lk(wr_mu);
+                wr_cv.wait(lk, [&] { return (!ready.empty() && ready.begin()->first == next) || (fmt_done && ready.empty()) || (fmt_done && R.failed); });
+                if (ready.empty() || ready.begin()->first != next) break;
+                b = ready.begin()->second; ready.erase(ready.begin());
+            }
+            ++next;
+            if (b->failed || !b->n_recs || o.sam_sort) { release(b); continue; }      // (sorted: the rows are in the sorter)
+            WriteJob* j = new WriteJob();
+            j->b = b;
+            j->shard = K == 1 || in_size == 0 ? 0 : (int)std::min<unsigned __int128>((unsigned __int128)(K - 1), (unsigned __int128)b->first_byte * (unsigned)K / in_size);
+            uint64_t& off = R.file_offs[(size_t)j->shard];
+            if (o.sam_text_device) {
+                const size_t cut = std::max<size_t>((size_t)1 << 22, ((size_t)b->dtext_len + 7) / 8);
+                for (size_t at = 0; at < b->dtext_len; at += cut) {
+                    const size_t n = std::min<size_t>(cut, (size_t)b->dtext_len - at);
+                    j->pieces.push_back({ b->dtext->data() + at, n, off }); off += n;
                 }
-                if (--live_fmt == 0) { { std::lock_guard<std::mutex> lk(wr_mu); fmt_done = true; } wr_cv.notify_all(); }
-            });
-        // the writer only hands out file offsets in block order; the text pieces of a block (one per formatter slice, or cuts of the
-        // device's text) are written by pwrite() from a few threads at once (a single write() stream tops out at ~8 GB/s of page-cache
-        // copies).  --sam_shards=K: a block belongs to the shard of its first byte in the input, which only grows with the block index,
-        // so blocks keep their order inside a shard; the writer then only assigns (shard, offsets) and the shard's own writer thread does
-        // the writing, side by side with the other shards'.
-        struct Piece { const char* p; size_t n; uint64_t off; };
-        struct WriteJob { Block* b; int shard; std::vector<Piece> pieces; };
-        auto write_job = [&](WriteJob& j) {
-            auto w0 = std::chrono::steady_clock::now();
-            const int fd = ofds[(size_t)j.shard];
-            const int nt = (int)std::min<size_t>(8, j.pieces.size());
-            std::atomic<size_t> nextp{ 0 }; std::atomic<int> bad{ 0 };
-            auto job = [&] { for (size_t k; (k = nextp++) < j.pieces.size();) if (j.pieces[k].n && !pwrite_all(fd, j.pieces[k].p, j.pieces[k].n, j.pieces[k].off)) bad = 1; };
-            std::vector<std::thread> ws;
-            for (int t = 1; t < nt; ++t) ws.emplace_back(job);
-            job();
-            for (auto& x : ws) x.join();
-            if (bad) { fprintf(stderr, "ERROR: write failed\n"); failed = 1; }
-            { std::lock_guard<std::mutex> lk(tw_mu); t_write += secs_since(w0); }
-        };
-        auto release = [&](Block* b) { text_pool.put(b->dtext); b->dtext = nullptr; free_q.push(b); };       // the rows are written (or there are none)
-        std::vector<std::unique_ptr<Queue<WriteJob*>>> shard_q;
-        std::vector<std::thread> shard_th;
-        if (K > 1)
-            for (int k = 0; k < K; ++k) {
+            } else
+                for (size_t k = 0; k < b->text.size(); ++k) { j->pieces.push_back({ b->text[k].data(), b->text[k].size(), off }); off += b->text[k].size(); }
+            if (K == 1) { write_job(*j); delete j; release(b); }
+            else shard_q[(size_t)j->shard]->push(j);
+        }
+        for (auto& q : shard_q) q->close();
+        for (auto& x : shard_th) x.join();
+        free_q.close();
+    }
+
+    size_t run() {
+        std::thread scanner(&Pass::scan, this);
+        std::vector<std::thread> wth, fth;
+        for (Worker& w : R.workers) wth.emplace_back(&Pass::work, this, std::ref(w));
+        for (int f = 0; f < N_FMT; ++f) fth.emplace_back(&Pass::format, this);
+        if (o.sam_shards > 1)
+            for (int k = 0; k < o.sam_shards; ++k) {
                 shard_q.emplace_back(new Queue<WriteJob*>());
-                Queue<WriteJob*>* q = shard_q.back().get();
-                shard_th.emplace_back([&, q] { WriteJob* j; while (q->pop(j)) { write_job(*j); release(j->b); delete j; } });
+                shard_th.emplace_back(&Pass::shard_write, this, shard_q.back().get());
             }
-        std::thread writer([&] {
-            uint64_t next = 0;
-            for (;;) {
-                Block* b = nullptr;
-                {
-                    std::unique_lock<std::mutex> lk(wr_mu);
-                    wr_cv.wait(lk, [&] { return (!ready.empty() && ready.begin()->first == next) || (fmt_done && ready.empty()) || (fmt_done && failed); });
-                    if (ready.empty() || ready.begin()->first != next) break;
-                    b = ready.begin()->second; ready.erase(ready.begin());
-                }
-                ++next;
-                if (b->failed || !b->n_recs || o.sam_sort) { release(b); continue; }      // (sorted: the rows are in the sorter)
-                WriteJob* j = new WriteJob();
-                j->b = b;
-                j->shard = K == 1 || fq.size == 0 ? 0 : (int)std::min<unsigned __int128>((unsigned __int128)(K - 1), (unsigned __int128)b->first_byte * (unsigned)K / fq.size);
-                uint64_t& off = file_offs[(size_t)j->shard];
-                if (o.sam_text_device) {
-                    const size_t cut = std::max<size_t>((size_t)1 << 22, ((size_t)b->dtext_len + 7) / 8);
-                    for (size_t at = 0; at < b->dtext_len; at += cut) { const size_t n = std::min<size_t>(cut, (size_t)b->dtext_len - at); j->pieces.push_back({ b->dtext->data() + at, n, off }); off += n; }
-                } else
-                    for (size_t k = 0; k < b->text.size(); ++k) { j->pieces.push_back({ b->text[k].data(), b->text[k].size(), off }); off += b->text[k].size(); }
-                if (K == 1) { write_job(*j); delete j; release(b); }
-                else shard_q[(size_t)j->shard]->push(j);
-            }
-            for (auto& q : shard_q) q->close();
-            for (auto& x : shard_th) x.join();
-            free_q.close();
-        });
+        std::thread writer(&Pass::write, this);
         scanner.join();
         for (auto& x : wth) x.join();
         for (auto& x : fth) x.join();
         writer.join();
-        seq_base += idx_end;
+        R.seq_base += idx_end;
         return gate.bad_at;
-    };
-    const bool file_order = o.batch_set || o.p.illumina;
-    const size_t bad_at = run_pass(!file_order);
-    if (!failed && bad_at != npos) {                   // a malformed record: the reference's recovery needs the lines in file order from there on
-        fq.at = bad_at; fq.done = false;
-        run_pass(false);
     }
-    // --sam_sort=coordinate: sort once, then the rows come down slab by slab; a slab is written while the next one is gathered and downloaded
-    uint64_t sorted_rows = 0, sorted_bytes = 0;
-    if (o.sam_sort && !failed) {
-        if (gm_sam_sorter_finish(sorter, &sorted_rows, &sorted_bytes, workers[0].stream) != GM_OK) { fprintf(stderr, "ERROR: gm_sam_sorter_finish: %s\n", gm_last_error()); return 1; }
-        PinVec<char> slab[2];
-        const size_t slab_cap = (size_t)std::min<uint64_t>((uint64_t)64 << 20, std::max<uint64_t>(sorted_bytes, 1 << 16));
-        slab[0].ensure(slab_cap); slab[1].ensure(slab_cap);
-        std::thread wr; std::atomic<int> wr_bad{ 0 };
-        auto w0 = std::chrono::steady_clock::now();
-        size_t cap = slab_cap;                                           // what gm_sam_sorter_read may fill of either buffer
-        for (int k = 0;;) {                                              // k: the buffer the next slab goes into, while the other one is written
-            uint64_t got = 0;
-            int rc = gm_sam_sorter_read(sorter, slab[k].data(), cap, &got, workers[0].stream);
-            if (rc == GM_E_CAPACITY) {                                   // a row longer than a slab: both buffers grow to it, the same read again
-                if (wr.joinable()) wr.join();
-                cap = (size_t)got;
-                slab[0].ensure(cap); slab[1].ensure(cap);
-                continue;
-            }
-            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_sam_sorter_read: %s\n", gm_last_error()); failed = 1; break; }
+};
+
+static size_t run_pass(Run& R, bool chunks) { return Pass(R, chunks).run(); }
+
+// --sam_sort=coordinate: sort once, then the rows come down slab by slab; a slab is written while the next one is gathered and downloaded
+static int drain_sorter(Run& R) {
+    uint64_t sorted_bytes = 0;
+    void* const stream = R.workers[0].stream;
+    if (gm_sam_sorter_finish(R.sorter, &R.sorted_rows, &sorted_bytes, stream) != GM_OK) { fprintf(stderr, "ERROR: gm_sam_sorter_finish: %s\n", gm_last_error()); return 1; }
+    PinVec<char> slab[2];
+    const size_t slab_cap = (size_t)std::min<uint64_t>((uint64_t)64 << 20, std::max<uint64_t>(sorted_bytes, 1 << 16));
+    slab[0].ensure(slab_cap); slab[1].ensure(slab_cap);
+    const int ofd = R.ofds[0];
+    std::thread wr; std::atomic<int> wr_bad{ 0 };
+    auto w0 = Clock::now();
+    size_t cap = slab_cap;                                           // what gm_sam_sorter_read may fill of either buffer
+    for (int k = 0;;) {                                              // k: the buffer the next slab goes into, while the other one is written
+        uint64_t got = 0;
+        int rc = gm_sam_sorter_read(R.sorter, slab[k].data(), cap, &got, stream);
+        if (rc == GM_E_CAPACITY) {                                   // a row longer than a slab: both buffers grow to it, the same read again
             if (wr.joinable()) wr.join();
-            if (!got || wr_bad) break;
-            const uint64_t off = file_offs[0];
-            file_offs[0] += got;
-            const char* p = slab[k].data();
-            wr = std::thread([&, p, got, off] { if (!pwrite_all(ofd, p, (size_t)got, off)) wr_bad = 1; });
-            k ^= 1;
+            cap = (size_t)got;
+            slab[0].ensure(cap); slab[1].ensure(cap);
+            continue;
         }
+        if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_sam_sorter_read: %s\n", gm_last_error()); R.failed = 1; break; }
         if (wr.joinable()) wr.join();
-        if (wr_bad) { fprintf(stderr, "ERROR: write failed\n"); failed = 1; }
-        t_write += secs_since(w0);
+        if (!got || wr_bad) break;
+        const uint64_t off = R.file_offs[0];
+        R.file_offs[0] += got;
+        const char* p = slab[k].data();
+        wr = std::thread([ofd, p, got, off, &wr_bad] { if (!pwrite_all(ofd, p, (size_t)got, off)) wr_bad = 1; });
+        k ^= 1;
     }
-    for (int fd : ofds) ::close(fd);
-    if (failed) return 1;
-    const double t_pipe = secs_since(t_pipe0);
-    if (o.sam_sort && o.verbose > 0) {
-        gm_sam_sort_stats ss;
-        if (gm_sam_sorter_stats(sorter, &ss) == GM_OK) {
-            fprintf(stderr, "sam sort on the device: %lu rows, %lu text bytes in %lu pieces of %lu bytes; seconds: arena appends %.3f, sort %.3f, gather %.3f, download %.3f\n",
-                    (unsigned long)ss.rows, (unsigned long)ss.text_bytes, (unsigned long)ss.pieces, (unsigned long)ss.piece_bytes, ss.add_s, ss.sort_s, ss.gather_ms / 1e3, ss.download_s);
-        }
-    }
-    gm_sam_sorter_destroy(sorter);
-    auto t_cov0 = std::chrono::steady_clock::now();
-    // coverage: all-reduce over the GPUs, then PrintFinalSGR / PrintFinalBisulfite
-    if (gm_coverage_allreduce(gpu_ix.data(), o.gpus) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+    if (wr.joinable()) wr.join();
+    if (wr_bad) { fprintf(stderr, "ERROR: write failed\n"); R.failed = 1; }
+    R.t_write += secs_since(w0);
+    return 0;
+}
+
+static void report_sorter(const Run& R) {
+    gm_sam_sort_stats ss;
+    if (gm_sam_sorter_stats(R.sorter, &ss) != GM_OK) return;
+    fprintf(stderr, "sam sort on the device: %lu rows, %lu text bytes in %lu pieces of %lu bytes; seconds: arena appends %.3f, sort %.3f, gather %.3f, download %.3f\n",
+            (unsigned long)ss.rows, (unsigned long)ss.text_bytes, (unsigned long)ss.pieces, (unsigned long)ss.piece_bytes, ss.add_s, ss.sort_s, ss.gather_ms / 1e3, ss.download_s);
+}
+
+// coverage: all-reduce over the GPUs, then PrintFinalSGR / PrintFinalBisulfite / PrintFinalSNP, and the .vcf beside a .gmp
+static int write_tracks(Run& R) {
+    const Options& o = R.o;
+    gm_index* const ix = R.gpu_ix[0];
+    const std::string sgr = o.output + ".sgr", gmp = o.output + ".gmp";
+    if (gm_coverage_allreduce(R.gpu_ix.data(), o.gpus) != GM_OK) return fail();
     if (o.p.mode == GM_MODE_SNP && o.snp_calls && !o.track_text_device) {      // PrintFinalSNP with PrintSNPCall's column: the tracks are read where they are, slab by slab
-        if (gm_coverage_write_gmp_calls(gpu_ix[0], o.snp_pval, o.snp_monop, (o.output + ".gmp").c_str(), 0) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+        if (gm_coverage_write_gmp_calls(ix, o.snp_pval, o.snp_monop, gmp.c_str(), 0) != GM_OK) return fail();
     } else if (o.track_text_device) {                                  // GPU 0 formats the rows where the tracks are: no host copy of a track
-        const int rc = o.p.mode == GM_MODE_NORMAL ? gm_coverage_write_sgr_device(gpu_ix[0], (o.output + ".sgr").c_str(), 0)
-                       : o.p.mode == GM_MODE_SNP && o.snp_calls ? gm_coverage_write_gmp_calls_device(gpu_ix[0], o.snp_pval, o.snp_monop, (o.output + ".gmp").c_str(), 0)
-                                                                : gm_coverage_write_gmp_device(gpu_ix[0], &o.p, (o.output + ".gmp").c_str(), 0);
-        if (rc != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+        const int rc = o.p.mode == GM_MODE_NORMAL ? gm_coverage_write_sgr_device(ix, sgr.c_str(), 0)
+                       : o.p.mode == GM_MODE_SNP && o.snp_calls ? gm_coverage_write_gmp_calls_device(ix, o.snp_pval, o.snp_monop, gmp.c_str(), 0)
+                                                                : gm_coverage_write_gmp_device(ix, &o.p, gmp.c_str(), 0);
+        if (rc != GM_OK) return fail();
         gm_track_text_stats ts;
-        if (o.verbose > 0 && gm_coverage_text_stats(gpu_ix[0], &ts) == GM_OK)
+        if (o.verbose > 0 && gm_coverage_text_stats(ix, &ts) == GM_OK)
             fprintf(stderr, "track text on the device: %lu rows, %lu bytes, %lu slabs (%lu formatted by the host), %lu launches, %.2f ms in kernels\n", (unsigned long)ts.rows,
                     (unsigned long)ts.bytes, (unsigned long)ts.slabs, (unsigned long)ts.host_slabs, (unsigned long)ts.launches, ts.kernel_ms);
     } else {
-        PinVec<float> cov; cov.ensure(gm_coverage_bins(gpu_ix[0]));                     // page-locked: the 1.5 GB of a human track come down at link rate
-        if (gm_coverage_download(gpu_ix[0], cov.data()) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+        PinVec<float> cov; cov.ensure(gm_coverage_bins(ix));                            // page-locked: the 1.5 GB of a human track come down at link rate
+        if (gm_coverage_download(ix, cov.data()) != GM_OK) return fail();
         if (o.p.mode == GM_MODE_NORMAL) {                              // GenomeBwt::PrintFinal src/GenomeBwt.cpp:915-926
-            if (gm_coverage_write_sgr(gpu_ix[0], cov.data(), (o.output + ".sgr").c_str(), 0) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
+            if (gm_coverage_write_sgr(ix, cov.data(), sgr.c_str(), 0) != GM_OK) return fail();
         } else {
-            std::vector<float> nuc(5 * (size_t)gm_coverage_bins(gpu_ix[0]));
-            if (gm_coverage_download_nuc(gpu_ix[0], nuc.data()) != GM_OK ||
-                gm_coverage_write_gmp(gpu_ix[0], &o.p, cov.data(), nuc.data(), (o.output + ".gmp").c_str(), 0) != GM_OK) {
-                fprintf(stderr, "ERROR: %s\n", gm_last_error());
-                return 1;
-            }
+            std::vector<float> nuc(5 * (size_t)gm_coverage_bins(ix));
+            if (gm_coverage_download_nuc(ix, nuc.data()) != GM_OK || gm_coverage_write_gmp(ix, &o.p, cov.data(), nuc.data(), gmp.c_str(), 0) != GM_OK) return fail();
         }
     }
     // Genome::PrintFinalVCF src/Genome.cpp:1142-1245 beside the .gmp (the reference's compiled GenomeBwt accepts --vcf and writes no file)
-    if (o.vcf && gm_coverage_write_vcf(gpu_ix[0], o.snp_pval, o.snp_monop, (o.output + ".vcf").c_str(), 0) != GM_OK) { fprintf(stderr, "ERROR: %s\n", gm_last_error()); return 1; }
-    uint64_t n_reads = 0, n_matched = 0, n_records = 0;
-    double t_pack = 0, t_map = 0, t_out = 0;
-    for (auto& w : workers) {
-        n_reads += w.n_reads; n_matched += w.n_matched; n_records += w.n_records; t_pack += w.t_pack; t_map += w.t_map; t_out += w.t_out; t_scan += w.t_scan;
-        gm_batch_destroy(w.batch);
-        gm_stream_destroy(w.ix, w.stream);
-    }
-    if (o.sam_sort) n_records = sorted_rows;
-    const double t_cov = secs_since(t_cov0);
-    for (auto ix : gpu_ix) gm_index_close(ix);
-    double secs = secs_since(t0);
-    const bool text_blocks = o.read_text_device && !file_order;          // the chunk-mode blocks went up as text: name the path that ran
-    if (o.verbose > 0) {
-        const char* const pack = text_blocks ? "stage" : "pack";       // copying the text into a page-locked buffer takes the place of cutting and packing it
-        const char* const map = text_blocks ? "gm_map_batch_text" : "gm_map_batch";      // (with the flag it includes gm_batch_upload_text, as gm_map_batch includes its upload)
-        if (o.sam_text_device)                               // no formatter stage: the rows were text when they left the library
-            fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, %s %.2f, %s %.2f, %s %.2f, write %.2f\n",
-                    t_index, t_scan, pack, t_pack, map, t_map, text_blocks ? "gm_output_batch_text_resident" : "gm_output_batch_text", t_out, t_write);
-        else
-        fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, %s %.2f, %s %.2f, gm_output_batch %.2f, SAM format %.2f, write %.2f\n",
-                t_index, t_scan, pack, t_pack, map, t_map, t_out, t_fmt, t_write);
-        fprintf(stderr, "wall seconds: index %.2f, FASTQ->SAM pipeline %.2f (%.3f M reads/s), coverage all-reduce + track file %.2f\n", t_index, t_pipe,
-                n_reads / std::max(t_pipe, 1e-9) / 1e6, t_cov);
-        fprintf(stderr, "Finished: %lu reads, %lu matched, %lu SAM records, %.2f s total (%.2f s after the index was resident)\n", (unsigned long)n_reads,
-                (unsigned long)n_matched, (unsigned long)n_records, secs, secs - t_index);
-    }
+    if (o.vcf && gm_coverage_write_vcf(ix, o.snp_pval, o.snp_monop, (o.output + ".vcf").c_str(), 0) != GM_OK) return fail();
     return 0;
 }
+
+static void report(const Run& R, double t_pipe, double t_cov, double secs) {
+    const Options& o = R.o;
+    struct { uint64_t n_reads = 0, n_matched = 0, n_records = 0; double t_pack = 0, t_map = 0, t_out = 0, t_scan = 0; } t;      // summed over the workers
+    for (const Worker& w : R.workers) {
+        t.n_reads += w.n_reads; t.n_matched += w.n_matched; t.n_records += w.n_records;
+        t.t_pack += w.t_pack; t.t_map += w.t_map; t.t_out += w.t_out; t.t_scan += w.t_scan;
+    }
+    if (o.sam_sort) t.n_records = R.sorted_rows;
+    const bool text_blocks = o.read_text_device && !R.file_order();      // the chunk-mode blocks went up as text: name the path that ran
+    const char* const pack = text_blocks ? "stage" : "pack";       // copying the text into a page-locked buffer takes the place of cutting and packing it
+    const char* const map = text_blocks ? "gm_map_batch_text" : "gm_map_batch";      // (with the flag it includes gm_batch_upload_text, as gm_map_batch includes its upload)
+    const double t_scan = R.t_scan + t.t_scan;
+    if (o.sam_text_device)                               // no formatter stage: the rows were text when they left the library
+        fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, %s %.2f, %s %.2f, %s %.2f, write %.2f\n",
+                R.t_index, t_scan, pack, t.t_pack, map, t.t_map, text_blocks ? "gm_output_batch_text_resident" : "gm_output_batch_text", t.t_out, R.t_write);
+    else
+        fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, %s %.2f, %s %.2f, gm_output_batch %.2f, SAM format %.2f, write %.2f\n",
+                R.t_index, t_scan, pack, t.t_pack, map, t.t_map, t.t_out, R.t_fmt, R.t_write);
+    fprintf(stderr, "wall seconds: index %.2f, FASTQ->SAM pipeline %.2f (%.3f M reads/s), coverage all-reduce + track file %.2f\n", R.t_index, t_pipe,
+            t.n_reads / std::max(t_pipe, 1e-9) / 1e6, t_cov);
+    fprintf(stderr, "Finished: %lu reads, %lu matched, %lu SAM records, %.2f s total (%.2f s after the index was resident)\n", (unsigned long)t.n_reads,
+            (unsigned long)t.n_matched, (unsigned long)t.n_records, secs, secs - R.t_index);
+}
+
+int main(int argc, char** argv) {
+    Run R;
+    parse_args(argc, argv, R.o);
+    for (int i = 0; i < argc; ++i) { R.cl += argv[i]; R.cl += " "; }
+    R.t0 = Clock::now();
+    if (detect_read_format(R) || open_devices(R) || open_outputs(R)) return 1;
+    R.t_pipe0 = Clock::now();
+    if (!R.reads_open) { fprintf(stderr, "ERROR: cannot open %s\n", R.o.reads.c_str()); return 1; }
+    { struct stat hs; if (fstat(R.ofds[0], &hs) == 0) R.file_offs[0] = (uint64_t)lseek(R.ofds[0], 0, SEEK_CUR); }
+    const size_t bad_at = run_pass(R, !R.file_order());
+    if (!R.failed && bad_at != NPOS) {                 // a malformed record: the reference's recovery needs the lines in file order from there on
+        R.fq.at = bad_at; R.fq.done = false;
+        run_pass(R, false);
+    }
+    if (R.o.sam_sort && !R.failed && drain_sorter(R)) return 1;
+    for (int fd : R.ofds) ::close(fd);
+    if (R.failed) return 1;
+    const double t_pipe = secs_since(R.t_pipe0);
+    if (R.o.sam_sort && R.o.verbose > 0) report_sorter(R);
+    gm_sam_sorter_destroy(R.sorter);
+    auto t_cov0 = Clock::now();
+    if (write_tracks(R)) return 1;
+    for (Worker& w : R.workers) { gm_batch_destroy(w.batch); gm_stream_destroy(w.ix, w.stream); }
+    const double t_cov = secs_since(t_cov0);
+    for (auto ix : R.gpu_ix) gm_index_close(ix);
+    if (R.o.verbose > 0) report(R, t_pipe, t_cov, secs_since(R.t0));
+    return 0;
+}
+

@@ -4,11 +4,12 @@ reference was run with, SAM text byte-identical including record order; .sgr / .
 import gzip
 import json
 import os
+import re
 import subprocess
 
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN, ROOT, read_fastq
 
 pytestmark = pytest.mark.gpu
 RUNS = os.path.join(GOLDEN, "ref_runs")
@@ -186,8 +187,77 @@ def test_cli_maps_a_too_large_block_in_halves(mode, tmp_path):
     compare_tracks(open(out + "." + ext).read(), ref_text(mode, ext), 3 if ext == "sgr" else 8)
 
 
+TEXT_PATHS = {"host": [], "sam_text_device": ["--sam_text=device"], "read_text_device": ["--read_text=device"],
+              "both_device": ["--read_text=device", "--sam_text=device"]}
+
+
+@pytest.mark.parametrize("path", list(TEXT_PATHS))
+@pytest.mark.parametrize("mode", ["default", "bs_all", "illumina"])
+def test_cli_writes_a_too_large_block_in_halves(mode, path, tmp_path):
+    """the OUTPUT call finds the block too large (GM_TEST_MAX_OUT_BLOCK stands in for its limits: 2^31 matches, a 4 GB CIGAR pool) after
+    the block was mapped whole: the halves' record arrays and CIGAR pools are merged, or their device text is put one behind the other,
+    and a block the GPU cut (--read_text=device) is cut again by the host first: same SAM, same tracks"""
+    m = MANIFEST[mode]
+    out = str(tmp_path / "mine")
+    r = subprocess.run([EXE, "-g", os.path.join(GOLDEN, "syn.fa"), "-o", out, "-a", "0.9"] + m["argv"] + TEXT_PATHS[path] + [os.path.join(GOLDEN, m["fastq"])],
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ, GM_TEST_MAX_OUT_BLOCK="60"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "written in halves" in r.stderr and "mapped in halves" not in r.stderr
+    assert "".join(l for l in open(out + ".sam") if not l.startswith("@PG")) == ref_text(mode, "sam")
+    ext = "sgr" if "sgr" in m["tracks"] else "gmp"
+    compare_tracks(open(out + "." + ext).read(), ref_text(mode, ext), 3 if ext == "sgr" else 8)
+
+
+HOST_LABELS = ["pack", "gm_map_batch", "gm_output_batch", "SAM format"]
+# (argv, environment, the stage labels between `scan` and `write`): a sorted run's rows are device text
+COUNT_PATHS = {
+    "host": ([], {}, HOST_LABELS),
+    "sam_text_device": (["--sam_text=device"], {}, ["pack", "gm_map_batch", "gm_output_batch_text"]),
+    "read_text_device": (["--read_text=device"], {}, ["stage", "gm_map_batch_text", "gm_output_batch", "SAM format"]),
+    "both_device": (["--read_text=device", "--sam_text=device"], {}, ["stage", "gm_map_batch_text", "gm_output_batch_text_resident"]),
+    "sorted": (["--sam_sort=coordinate"], {}, ["pack", "gm_map_batch", "gm_output_batch_text"]),
+    "batch64": (["--batch=64"], {}, HOST_LABELS),
+    "chunks37": (["--chunk_reads=37", "--workers=3"], {}, HOST_LABELS),
+    "halves": ([], {"GM_TEST_MAX_BLOCK": "60"}, HOST_LABELS),
+}
+
+
+def _run_and_count(extra, env, out):
+    """(reads, matched, records) of the `Finished:` line, the labels of the `stage seconds` line, the rows of the SAM file"""
+    m = MANIFEST["default"]
+    r = subprocess.run([EXE, "-g", os.path.join(GOLDEN, "syn.fa"), "-o", out, "-a", "0.9"] + m["argv"] + extra + [os.path.join(GOLDEN, m["fastq"])],
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
+    assert r.returncode == 0, r.stderr[-2000:]
+    fin = re.findall(r"^Finished: (\d+) reads, (\d+) matched, (\d+) SAM records,", r.stderr, re.M)
+    stage = [l for l in r.stderr.splitlines() if l.startswith("stage seconds (summed over threads): ")]
+    assert len(fin) == 1 and len(stage) == 1, r.stderr[-2000:]
+    labels = [x.rsplit(" ", 1)[0] for x in stage[0].split(": ", 1)[1].split(", ")]
+    rows = sum(1 for l in open(out + ".sam") if not l.startswith("@"))
+    return tuple(int(x) for x in fin[0]), labels, rows
+
+
+@pytest.fixture(scope="module")
+def plain_matched(tmp_path_factory):
+    (_, matched, _), _, _ = _run_and_count([], {}, str(tmp_path_factory.mktemp("plain") / "plain"))
+    return matched
+
+
+@pytest.mark.parametrize("path", list(COUNT_PATHS))
+def test_cli_counts_and_stage_labels_are_the_same_on_every_path(path, plain_matched, tmp_path):
+    """every path books a block's reads, matched reads and records once (a block mapped in halves through its halves, a sorted run's
+    records from the sorter), and the stage-seconds line names the calls that ran"""
+    extra, env, want_labels = COUNT_PATHS[path]
+    (reads, matched, records), labels, rows = _run_and_count(extra, env, str(tmp_path / "mine"))
+    n_fastq = len(read_fastq(os.path.join(GOLDEN, MANIFEST["default"]["fastq"])))
+    assert n_fastq > 500 and plain_matched > 100
+    assert reads == n_fastq
+    assert records == rows and rows > 100
+    assert matched == plain_matched
+    assert labels == ["index", "scan"] + want_labels + ["write"]
+
+
 # ------------------------------------------------------------------ the edges of the reference (tests/golden/make_edge_fixtures.py)
-import edge_fixture as ef                                                  # noqa: E402
+import edge_fixture as ef                                                 # noqa: E402
 
 
 @pytest.fixture(scope="module")
