@@ -11,6 +11,7 @@ GM_INDEX_FULL_SA, GM_INDEX_BUILD, GM_INDEX_HOST_ONLY = 1, 2, 4
 GM_READ_OK, GM_READ_TOO_MANY, GM_READ_NONE, GM_READ_TOO_SHORT, GM_READ_TOO_POOR = 0, 1, 2, -2, -3
 GM_E_CAPACITY = -5
 GM_E_BATCH_TOO_LARGE = -9
+GM_ROWS_TEXT, GM_ROWS_BAM = 0, 1
 
 u8p = C.POINTER(C.c_uint8)
 u64 = C.c_uint64
@@ -80,6 +81,10 @@ class gm_sam_text(C.Structure):
     _fields_ = [("text", C.c_void_p), ("text_cap", u64), ("text_len", u64), ("n_recs", u64), ("row_off", C.c_void_p), ("row_cap", u64)]
 
 
+class gm_bam_out(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("cap", u64), ("len", u64), ("raw_len", u64), ("n_recs", u64), ("level", C.c_int)]
+
+
 class gm_text_info(C.Structure):
     _fields_ = [("n", C.c_uint32), ("max_len", C.c_uint32), ("stride", C.c_uint32), ("status", C.c_int32), ("bad_at", u64)]
 
@@ -124,7 +129,9 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_batch_set_read_format", "gm_index_set_probe_format",
            "gm_batch_upload_text", "gm_map_batch_text", "gm_output_batch_text_resident", "gm_dev_fastq_rows", "gm_dev_fastq_tile_bytes",
            "gm_sam_sorter_create", "gm_sam_sorter_destroy", "gm_output_batch_sorted", "gm_output_batch_sorted_resident", "gm_sam_sorter_finish",
-           "gm_sam_sorter_read", "gm_sam_sorter_stats", "gm_sam_sorter_add_rows"]
+           "gm_sam_sorter_read", "gm_sam_sorter_stats", "gm_sam_sorter_add_rows",
+           "gm_bam_header", "gm_bgzf_compress", "gm_bgzf_eof", "gm_output_batch_bam", "gm_output_batch_bam_resident", "gm_sam_sorter_set_rows",
+           "gm_sam_sorter_read_bgzf", "gm_batch_bam_times"]
 
 
 def library_path():
@@ -225,6 +232,15 @@ def load_library():
     L.gm_sam_sorter_read.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
     L.gm_sam_sorter_add_rows.argtypes = [C.c_void_p, u64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_void_p]
     L.gm_sam_sorter_stats.argtypes = [C.c_void_p, C.POINTER(gm_sam_sort_stats)]
+    L.gm_bam_header.argtypes = [C.c_void_p, C.c_char_p, u64, C.c_void_p, u64, C.POINTER(u64)]
+    L.gm_bgzf_compress.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_int, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
+    L.gm_bgzf_eof.argtypes = [C.c_void_p]
+    L.gm_output_batch_bam.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_reads), C.POINTER(gm_read_text), C.POINTER(gm_hits),
+                                      C.POINTER(gm_bam_out), C.c_void_p]
+    L.gm_output_batch_bam_resident.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_hits), C.POINTER(gm_bam_out), C.c_void_p]
+    L.gm_sam_sorter_set_rows.argtypes = [C.c_void_p, C.c_int]
+    L.gm_batch_bam_times.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gm_sam_sorter_read_bgzf.argtypes = [C.c_void_p, C.c_int, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
     _LIB = L
     return L
 
@@ -397,6 +413,31 @@ class Index:
         if n:
             _chk(lib().gm_dev_fastq_rows(self.h, buf.ctypes.data, len(text), C.byref(info), recs.ctypes.data, B.ctypes.data, Q.ctypes.data, Ln.ctypes.data, n))
         return dict(n=n, max_len=int(info.max_len), stride=stride, status=int(info.status), bad_at=int(info.bad_at), recs=recs, bases=B, quals=Q, len=Ln)
+
+    def bam_header(self, sam_header=b""):
+        """gm_bam_header: the uncompressed bytes that open a BAM file with these header lines and this index's contigs (no device needed)"""
+        text = bytes(sam_header); need = u64()
+        rc = lib().gm_bam_header(self.h, text, len(text), None, 0, C.byref(need))
+        if rc != GM_E_CAPACITY:
+            _chk(rc)
+        buf = np.zeros(max(int(need.value), 1), np.uint8)
+        _chk(lib().gm_bam_header(self.h, text, len(text), buf.ctypes.data, int(need.value), C.byref(need)))
+        return buf[:need.value].tobytes()
+
+    def bgzf_compress(self, data, level=1, cap=None, stream=None):
+        """gm_bgzf_compress: whole BGZF blocks around `data`, deflated on the device.  cap: the output buffer's size (None: the worst case);
+        GnumapError with code GM_E_CAPACITY and .needed = the size when the blocks exceed it"""
+        src = np.frombuffer(bytes(data) + b"\0", np.uint8)
+        n = len(src) - 1
+        cap = n + 31 * ((n + 65279) // 65280) if cap is None else int(cap)
+        out = np.zeros(cap + 64, np.uint8); got = u64()
+        rc = lib().gm_bgzf_compress(self.h, src.ctypes.data, n, int(level), out.ctypes.data, cap, C.byref(got), stream)
+        if rc == GM_E_CAPACITY:
+            e = GnumapError(rc, lib().gm_last_error().decode())
+            e.needed = int(got.value); e.buffer = out
+            raise e
+        _chk(rc)
+        return out[:got.value].tobytes()
 
     def dev_fmt_g6(self, values):
         """gm_dev_fmt_g6: printf("%g") of every value as the device prints XA / XP; a list of bytes (b"" = outside the domain)"""
@@ -735,14 +776,66 @@ class Batch:
         return text[:st.text_len].tobytes(), row_off[:st.n_recs + 1].copy()
 
 
+    def _output_bam(self, call, level, bam_cap, stride):
+        cap = int(bam_cap) if bam_cap is not None else self.n * (2 * stride + 160) + 1024
+        self.bam_calls = 0
+        while True:
+            buf = np.zeros(max(cap, 1), np.uint8)
+            bo = gm_bam_out()
+            bo.data = buf.ctypes.data; bo.cap = cap; bo.level = int(level)
+            rc = call(bo)
+            self.bam_calls += 1
+            if rc == GM_E_CAPACITY:
+                cap = max(cap + 1, int(bo.cap))
+                continue
+            _chk(rc)
+            break
+        self.bam_raw_len, self.bam_n_recs = int(bo.raw_len), int(bo.n_recs)
+        return buf[:bo.len].tobytes()
+
+    def bam_times(self):
+        """gm_batch_bam_times (set_profiling first): dict(rows_ms, bgzf_ms, raw_bytes, bgzf_in, bgzf_out) since the last call"""
+        ms = np.zeros(2, np.float64); by = np.zeros(3, np.uint64)
+        _chk(lib().gm_batch_bam_times(self.h, ms.ctypes.data, by.ctypes.data))
+        return dict(rows_ms=float(ms[0]), bgzf_ms=float(ms[1]), raw_bytes=int(by[0]), bgzf_in=int(by[1]), bgzf_out=int(by[2]))
+
+    def output_bam(self, params, res, names, qual_tails=None, level=1, stream=None, bam_cap=None):
+        """gm_output_batch_bam on the result of map(): the block's BAM records as BGZF blocks (bytes).  names / qual_tails as in output_text;
+        bam_cap: first capacity to try.  self.bam_raw_len / self.bam_n_recs: bytes and number of the records"""
+        rt, keep = _pack_read_text([bytes(x) for x in names], None if qual_tails is None else [bytes(x) for x in qual_tails], self.n)
+        out = self._output_bam(lambda bo: lib().gm_output_batch_bam(self.index.h, C.byref(params.c), self.h, C.byref(res["_reads"]), C.byref(rt), C.byref(res["_struct"]),
+                                                                    C.byref(bo), stream), level, bam_cap, res["_reads"].stride)
+        del keep
+        return out
+
+    def output_bam_resident(self, params, res, level=1, stream=None, bam_cap=None):
+        """gm_output_batch_bam_resident on the result of map_text()"""
+        return self._output_bam(lambda bo: lib().gm_output_batch_bam_resident(self.index.h, C.byref(params.c), self.h, C.byref(res["_struct"]), C.byref(bo), stream),
+                                level, bam_cap, self.stride)
+
+
+def bgzf_eof():
+    """gm_bgzf_eof: the 28 bytes that end a BGZF file"""
+    buf = np.zeros(28, np.uint8)
+    _chk(lib().gm_bgzf_eof(buf.ctypes.data))
+    return buf.tobytes()
+
+
 class SamSorter:
     """gm_sam_sorter: the SAM rows of a run kept in HBM and read back in coordinate order.  The piece size of its arena is the
     GM_SORT_PIECE switch as it stands when the object is made."""
 
-    def __init__(self, index):
+    def __init__(self, index, rows="text"):
+        """rows: "text" (SAM rows) or "bam" (BAM records): what add_block puts into the arena"""
         self.index = index
         self.h = C.c_void_p()
         _chk(lib().gm_sam_sorter_create(index.h, C.byref(self.h)))
+        if rows != "text":
+            self.set_rows(rows)
+
+    def set_rows(self, rows):
+        """gm_sam_sorter_set_rows; before the first block"""
+        _chk(lib().gm_sam_sorter_set_rows(self.h, {"text": GM_ROWS_TEXT, "bam": GM_ROWS_BAM}[rows]))
 
     def destroy(self):
         if self.h:
@@ -792,6 +885,18 @@ class SamSorter:
         when that row alone is longer than cap"""
         buf = np.zeros(max(int(cap), 1), np.uint8); got = u64()
         rc = lib().gm_sam_sorter_read(self.h, buf.ctypes.data, int(cap), C.byref(got), stream)
+        if rc == GM_E_CAPACITY:
+            e = GnumapError(rc, lib().gm_last_error().decode())
+            e.needed = int(got.value)
+            raise e
+        _chk(rc)
+        return buf[:got.value].tobytes()
+
+    def read_bgzf(self, cap, level=1, stream=None):
+        """gm_sam_sorter_read_bgzf: the next whole rows whose BGZF form is sure to fit in cap bytes, as BGZF blocks (b"" = done).  GnumapError
+        with code GM_E_CAPACITY and .needed = the cap the next row needs when that row alone is too long"""
+        buf = np.zeros(max(int(cap), 1), np.uint8); got = u64()
+        rc = lib().gm_sam_sorter_read_bgzf(self.h, int(level), buf.ctypes.data, int(cap), C.byref(got), stream)
         if rc == GM_E_CAPACITY:
             e = GnumapError(rc, lib().gm_last_error().decode())
             e.needed = int(got.value)

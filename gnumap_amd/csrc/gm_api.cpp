@@ -57,8 +57,12 @@ struct gm_batch {
         pair_fb, pair_list,             // k_vote_pair: the reads it leaves to k_vote_bucket (one byte each), their list + its counter
         snp_scratch, snp_hmm,           // --snp: forward matrices of a chunk of kept sequences, their 5 floats per window position
         t_names, t_nameoff, t_qtail, t_qtailoff, t_slots, t_rowlen, t_rowoff, t_text, t_bad,     // gm_output_batch_text: the block's names, tails and row offsets, the text
+        t_bammeta,                      // gm_output_batch_bam: operations and bin of every record (k_bam_sizes)
         full_len, d_adaptor,            // -A: the lengths as uploaded (`len` then holds what k_adaptor_trim keeps), the adaptor's characters
         rt_text, rt_tilecnt, rt_tileoff, rt_lineat, rt_lsum, rt_lin, rt_recs, rt_nlen, rt_tlen, rt_meta;      // gm_batch_upload_text: the FASTQ text and what k_rt_* make of it
+    GmBgzfBufs bz;                      // gm_output_batch_bam: the BGZF blocks of the block's records
+    hipEvent_t bam_ev[4] = { nullptr, nullptr, nullptr, nullptr };      // while profiling is on: around k_bam_sizes and around k_bam_rows (gm_batch_bam_times)
+    double bam_rows_ms = 0; uint64_t bam_raw_bytes = 0;
     bool text_block = false;            // the block that is resident was cut from text by gm_batch_upload_text: t_names / t_qtail hold its names and tails
     bool text_pools = false;            // ... and still do (gm_output_batch_text with a caller's gm_read_text overwrites them)
     uint64_t text_name_bytes = 0, text_tail_bytes = 0;
@@ -551,9 +555,11 @@ extern "C" void gm_batch_destroy(gm_batch* b) {
                       &b->g_sorted, &b->g_ord, &b->g_lead, &b->g_krank, &b->g_khash, &b->g_nmatch, &b->g_mbegin, &b->g_multi, &b->g_big, &b->g_bigdone, &b->g_sk0, &b->g_sk1, &b->g_si0, &b->g_si1, &b->g_matches, &b->g_mhit, &b->g_positions,
                       &b->scan_tmp, &b->o_small, &b->o_posmatch, &b->o_post, &b->o_mapq, &b->o_emit, &b->o_reccnt, &b->o_cigcnt, &b->o_cigall, &b->o_recoff, &b->o_cigoff,
                       &b->o_recs, &b->o_pool, &b->o_codes, &b->snp_scratch, &b->snp_hmm, &b->pair_fb, &b->pair_list,
-                      &b->t_names, &b->t_nameoff, &b->t_qtail, &b->t_qtailoff, &b->t_slots, &b->t_rowlen, &b->t_rowoff, &b->t_text, &b->t_bad, &b->full_len, &b->d_adaptor,
+                      &b->t_names, &b->t_nameoff, &b->t_qtail, &b->t_qtailoff, &b->t_slots, &b->t_rowlen, &b->t_rowoff, &b->t_text, &b->t_bad, &b->t_bammeta, &b->full_len, &b->d_adaptor,
                       &b->rt_text, &b->rt_tilecnt, &b->rt_tileoff, &b->rt_lineat, &b->rt_lsum, &b->rt_lin, &b->rt_recs, &b->rt_nlen, &b->rt_tlen, &b->rt_meta };
     for (DevBuf* d : all) d->release();
+    b->bz.release();
+    for (auto e : b->bam_ev) if (e) (void)hipEventDestroy(e);
     PinBuf* pins[] = { &b->h_top, &b->h_hbegin, &b->h_ord, &b->h_post, &b->h_mapq, &b->h_emit, &b->h_mhit, &b->h_stat, &b->h_rt };
     for (PinBuf* d : pins) d->release();
     for (int i = 0; i < gm_batch::NS; ++i) { if (b->sub_streams[i]) (void)hipStreamDestroy(b->sub_streams[i]); b->sub_gk[i].release(); b->sub_gv[i].release(); }
@@ -1697,9 +1703,11 @@ static int map_batch_rest(gm_index* ix, const gm_params* p, gm_batch* b, gm_hits
 // `out` (records + CIGAR pool to the host: gm_output_batch) or `rt` + `tout` (finished SAM text: gm_output_batch_text), never both
 // rt == null with tout: names and tails are the ones gm_batch_upload_text left in t_names / t_qtail (gm_output_batch_text_resident)
 // sorter (with tout): the text is not downloaded - it goes into the sorter's arena under sequence number seq (gm_output_batch_sorted)
+// bout (with tout): the rows are BAM records and leave as BGZF blocks (gm_output_batch_bam); a sorter set to GM_ROWS_BAM keeps records too
 static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_hits* hits, gm_sam_out* out, const gm_read_text* rt,
-                             gm_sam_text* tout, void* stream, gm_sam_sorter* sorter = nullptr, uint64_t seq = 0) {
+                             gm_sam_text* tout, void* stream, gm_sam_sorter* sorter = nullptr, uint64_t seq = 0, gm_bam_out* bout = nullptr) {
     const bool pools = tout && !rt;
+    const bool bam = bout || (sorter && gm_samsort_rows(sorter) == GM_ROWS_BAM);      // the rows are BAM records, not text (gm_bam.hip)
     if (hits->n != b->n || reads->n != b->n) { gm_set_error("hits / reads do not belong to the batch"); return GM_E_ARG; }
     PhaseClock pc(tout ? "gm_output_batch_text" : "gm_output_batch");
     gm_sam_out no_host_records{};              // text form: the records and the CIGAR pool stay in HBM
@@ -1864,7 +1872,7 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
             const uint64_t name0 = pools ? 0 : rt->name_off[0], tail0 = pools || !tails ? 0 : rt->qual_tail_off[0];
             const uint64_t name_bytes = pools ? 0 : rt->name_off[n] - name0, tail_bytes = pools || !tails ? 0 : rt->qual_tail_off[n] - tail0;
             if ((!pools && (b->t_names.ensure((size_t)name_bytes + 16) || b->t_nameoff.ensure(((size_t)n + 1) * 8))) || b->t_slots.ensure((size_t)n_recs * 64) ||
-                b->t_rowlen.ensure((size_t)n_recs * 4) || b->t_rowoff.ensure(((size_t)n_recs + 1) * 8) || b->t_bad.ensure(8) ||
+                b->t_rowlen.ensure((size_t)n_recs * 4) || b->t_rowoff.ensure(((size_t)n_recs + 1) * 8) || b->t_bad.ensure(8) || (bam && b->t_bammeta.ensure((size_t)n_recs * 8)) ||
                 b->scan_tmp.ensure(((size_t)n_recs / 1024 + 8) * 8) ||
                 (!pools && tails && (b->t_qtail.ensure((size_t)tail_bytes + 16) || b->t_qtailoff.ensure(((size_t)n + 1) * 8)))) return GM_E_NOMEM;
             if (!pools) b->text_pools = false;                             // the caller's names take the place of the parse's
@@ -1886,6 +1894,10 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
             t.seq_len = b->adaptor.empty() ? b->dev.len : b->full_len.as<uint16_t>();
             t.fa_qual = fasta_qual_word();
             KCHK(gmk_out_text_sizes(b->dev, t, st));
+            const bool bam_timed = bam && b->profiling;
+            if (bam_timed) { for (auto& e : b->bam_ev) if (!e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(b->bam_ev[0], st)); }
+            if (bam) KCHK(gmk_bam_sizes(t, b->t_bammeta.as<uint32_t>(), st));      // the records' sizes take the place of the rows' lengths
+            if (bam_timed) HIPCHK(hipEventRecord(b->bam_ev[1], st));
             KCHK(gmk_scan_u32(t.row_len, n_recs, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
             uint64_t text_len = 0; unsigned long long bad = ~0ull;
             HIPCHK(hipMemcpyAsync(&text_len, b->t_rowoff.as<uint64_t>() + n_recs, 8, hipMemcpyDeviceToHost, st));
@@ -1899,7 +1911,7 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
             tout->text_len = text_len;
             // capacity first, as above: nothing has been deposited yet, the repeated call deposits once
             const bool rows_fit = !tout->row_off || tout->row_cap >= n_recs + 1;
-            if (!sorter && (text_len > tout->text_cap || !rows_fit)) {
+            if (!sorter && !bout && (text_len > tout->text_cap || !rows_fit)) {
                 tout->text_cap = text_len;
                 if (tout->row_off) tout->row_cap = n_recs + 1;
                 gm_set_error("output buffers too small");
@@ -1907,11 +1919,30 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
             }
             if (b->t_text.ensure((size_t)text_len + 16)) return GM_E_NOMEM;
             t.text = b->t_text.as<char>();
-            KCHK(gmk_out_text_rows(b->dev, t, st));
+            if (bam_timed) HIPCHK(hipEventRecord(b->bam_ev[2], st));
+            if (bam) KCHK(gmk_bam_rows(b->dev, t, b->t_bammeta.as<uint32_t>(), st));
+            else KCHK(gmk_out_text_rows(b->dev, t, st));
+            if (bam_timed) {
+                float ms_a = 0, ms_b = 0;
+                HIPCHK(hipEventRecord(b->bam_ev[3], st));
+                HIPCHK(hipStreamSynchronize(st));
+                HIPCHK(hipEventElapsedTime(&ms_a, b->bam_ev[0], b->bam_ev[1]));
+                HIPCHK(hipEventElapsedTime(&ms_b, b->bam_ev[2], b->bam_ev[3]));
+                b->bam_rows_ms += (double)ms_a + ms_b; b->bam_raw_bytes += text_len;
+            }
             // sorted: the rows stay in HBM (the arena grows before the deposit below: out of room, nothing of the block has been deposited)
             if (sorter) { if (const int rc = gm_samsort_add(sorter, seq, t.recs, n_recs, t.text, t.row_off, text_len, st)) return rc; }
+            else if (bout) {
+                // compressed where the records lie; capacity first, as above: the repeated call deposits once
+                uint64_t z_len = 0;
+                b->bz.timed = b->profiling;
+                if (const int rc = gm_bgzf_device(b->t_text.p, text_len, bout->level, b->bz, &z_len, st)) return rc;
+                bout->len = z_len; bout->raw_len = text_len; bout->n_recs = n_recs;
+                if (z_len > bout->cap) { bout->cap = z_len; bout->len = 0; gm_set_error("output buffers too small"); return GM_E_CAPACITY; }
+                HIPCHK(hipMemcpyAsync(bout->data, b->bz.out.p, (size_t)z_len, hipMemcpyDeviceToHost, st));
+            }
             else HIPCHK(hipMemcpyAsync(tout->text, b->t_text.p, (size_t)text_len, hipMemcpyDeviceToHost, st));
-            if (!sorter && tout->row_off) HIPCHK(hipMemcpyAsync(tout->row_off, b->t_rowoff.p, ((size_t)n_recs + 1) * 8, hipMemcpyDeviceToHost, st));
+            if (!sorter && !bout && tout->row_off) HIPCHK(hipMemcpyAsync(tout->row_off, b->t_rowoff.p, ((size_t)n_recs + 1) * 8, hipMemcpyDeviceToHost, st));
         }
     }
     if (snp && ix->cov_bins && n_p) {
@@ -1967,6 +1998,45 @@ extern "C" int gm_output_batch_text_resident(gm_index* ix, const gm_params* p, g
     gm_reads reads{};
     reads.n = b->n; reads.stride = b->stride;
     return output_batch_impl(ix, p, b, &reads, hits, nullptr, nullptr, out, stream);
+}
+
+// gm_output_batch_text / _text_resident with the rows as BAM records inside BGZF blocks (k_bam_sizes / k_bam_rows / k_bgzf_*, gm_bam.hip)
+static int bam_out_check(const char* who, gm_bam_out* out) {
+    out->len = 0; out->raw_len = 0; out->n_recs = 0;
+    if (out->level != 0 && out->level != 1) { gm_set_error(std::string(who) + ": gm_bam_out.level is 0 (stored) or 1 (Huffman), not " + std::to_string(out->level)); return GM_E_ARG; }
+    if (!out->data && out->cap) { gm_set_error(std::string(who) + ": gm_bam_out.data is NULL"); return GM_E_ARG; }
+    return GM_OK;
+}
+
+extern "C" int gm_output_batch_bam(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_read_text* rt, const gm_hits* hits, gm_bam_out* out,
+                                   void* stream) {
+    if (!ix) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("gm_output_batch_bam: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!p || !b || !reads || !hits || !out) return GM_E_ARG;
+    if (!rt) { gm_set_error("gm_output_batch_bam: gm_read_text is NULL"); return GM_E_ARG; }
+    if (const int rc = bam_out_check("gm_output_batch_bam", out)) return rc;
+    gm_sam_text kept{};
+    return output_batch_impl(ix, p, b, reads, hits, nullptr, rt, &kept, stream, nullptr, 0, out);
+}
+
+extern "C" int gm_output_batch_bam_resident(gm_index* ix, const gm_params* p, gm_batch* b, const gm_hits* hits, gm_bam_out* out, void* stream) {
+    if (!ix) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("gm_output_batch_bam_resident: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!p || !b || !hits || !out) return GM_E_ARG;
+    if (!b->text_block || !b->text_pools) { gm_set_error("gm_output_batch_bam_resident: the batch holds no names from gm_batch_upload_text"); return GM_E_ARG; }
+    if (const int rc = bam_out_check("gm_output_batch_bam_resident", out)) return rc;
+    gm_reads reads{};
+    reads.n = b->n; reads.stride = b->stride;
+    gm_sam_text kept{};
+    return output_batch_impl(ix, p, b, &reads, hits, nullptr, nullptr, &kept, stream, nullptr, 0, out);
+}
+
+extern "C" int gm_batch_bam_times(gm_batch* b, double* ms, uint64_t* bytes) {
+    if (!b || !ms || !bytes) return GM_E_ARG;
+    ms[0] = b->bam_rows_ms; ms[1] = b->bz.ms;
+    bytes[0] = b->bam_raw_bytes; bytes[1] = b->bz.in_bytes; bytes[2] = b->bz.out_bytes;
+    b->bam_rows_ms = 0; b->bam_raw_bytes = 0; b->bz.ms = 0; b->bz.in_bytes = 0; b->bz.out_bytes = 0;
+    return GM_OK;
 }
 
 // gm_output_batch_text / _text_resident with the text kept in HBM: appended to the sorter's arena under `seq` (gm_samsort.hip)

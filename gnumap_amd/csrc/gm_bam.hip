@@ -1,0 +1,497 @@
+// gm_bam.hip — BAM from the device: the records of a block in the binary layout of SAMv1 section 4.2, and BGZF (RFC 1952 members of at
+// most 64 KiB with the `BC` extra subfield, SAMv1 section 4.1) around any bytes, both written where the rows already are.
+//
+//   k_bam_sizes   one lane per record, after k_out_text_sizes (which has left the CIGAR lengths in the record's slot and has checked
+//                 XA / XP against the domain the text form prints): operations and reference length of the CIGAR field as the SAM row
+//                 prints it, reg2bin, the record's size
+//   k_bam_rows    one wavefront per record: the fixed 36 bytes and the three tags through LDS, then name, CIGAR, SEQ nibbles and QUAL
+//                 byte-wise; every store stays inside the span the scan gave the record
+//   k_bgzf_deflate  one workgroup per payload of at most 65280 bytes, held in LDS: CRC-32 by sub-chunks folded with
+//                 crc(A|B) = crc(A) * x^(8|B|) ^ crc(B), then a stored block (level 0) or one dynamic-Huffman block over literals
+//                 only (level 1) - histogram in LDS, a length-limited code built by one lane, all lanes emit through a prefix sum of
+//                 their bit counts - into the payload's worst-case slot
+//   k_bgzf_compact  after the scan of the blocks' sizes: the slots side by side, so that one contiguous run crosses the link
+//
+// A record is pinned to the SAM row k_out_text_rows prints for it.  One difference is the format's own: l_read_name is one byte, so
+// read_name holds the first 254 bytes of the name (the SAM row keeps up to 1023).
+// The output bytes are a function of the input bytes and the level alone: the only atomics are integer adds into the histogram and ORs
+// into words of the bit stream, whose results do not depend on the order in which they land.
+#include "gm_lib.h"
+#include <algorithm>
+#include <memory>
+
+namespace {
+
+constexpr uint32_t BZ_PAYLOAD = 65280;              // bytes of input per BGZF block
+constexpr uint32_t BZ_EXTRA = 31;                   // 18 header + 5 stored-block header + 8 trailer: the largest block is BZ_PAYLOAD + BZ_EXTRA
+constexpr uint32_t BZ_SLOT = 65312;                 // worst-case slot of a block, a multiple of 16
+constexpr uint32_t BZ_OUT_WORDS = (BZ_PAYLOAD + 16) / 4;
+constexpr uint32_t BZ_LDS = BZ_PAYLOAD + BZ_OUT_WORDS * 4;
+// BFINAL, BTYPE, HLIT = 257, HDIST = 1, HCLEN = 19; 19 code-length code lengths of 3 bits; 257 + 1 code lengths of 4 bits, not run-length coded
+constexpr uint32_t BZ_HDR_BITS = 3 + 5 + 5 + 4 + 19 * 3 + 258 * 4;
+constexpr uint32_t BZ_POLY = 0xEDB88320u;
+
+// a * b mod P over GF(2), operands and result bit-reflected as the CRC register is (x^0 = 0x80000000)
+__device__ __forceinline__ uint32_t bz_mul(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (uint32_t m = 0x80000000u; m; m >>= 1) {
+        if (a & m) p ^= b;
+        b = (b & 1u) ? (b >> 1) ^ BZ_POLY : b >> 1;
+    }
+    return p;
+}
+// x^(8k) mod P
+__device__ __forceinline__ uint32_t bz_xpow8(uint32_t k) {
+    uint32_t r = 0x80000000u, base = 0x00800000u;
+    for (; k; k >>= 1) { if (k & 1u) r = bz_mul(r, base); base = bz_mul(base, base); }
+    return r;
+}
+
+struct BzBits {                                     // one lane's writer into the block's bit stream (LSB first, RFC 1951 section 3.1.1)
+    uint32_t* out; uint32_t w, nb; unsigned long long acc;
+    __device__ __forceinline__ void start(uint32_t* o, uint32_t bit) { out = o; w = bit >> 5; nb = bit & 31u; acc = 0; }
+    __device__ __forceinline__ void put(uint32_t v, uint32_t n) {
+        acc |= (unsigned long long)v << nb; nb += n;
+        if (nb >= 32u) { atomicOr(&out[w], (uint32_t)acc); acc >>= 32; nb -= 32u; ++w; }
+    }
+    __device__ __forceinline__ void flush() { if (nb) atomicOr(&out[w], (uint32_t)acc); }
+};
+
+__global__ void __launch_bounds__(256) k_bgzf_deflate(const uint8_t* __restrict__ in, unsigned long long n, int level, uint8_t* __restrict__ slots,
+                                                      uint32_t* __restrict__ sizes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+    uint8_t* const s_in = s_dyn;
+    uint32_t* const s_out = reinterpret_cast<uint32_t*>(s_dyn + BZ_PAYLOAD);
+    __shared__ uint32_t s_tab[256], s_hist[257], s_code[257], s_wt[514], s_wave[4], s_misc[4];
+    __shared__ uint16_t s_par[514], s_ord[257];
+    __shared__ uint8_t s_dep[514];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const unsigned long long p0 = (unsigned long long)blockIdx.x * BZ_PAYLOAD;
+    if (p0 >= n) return;
+    const uint32_t len = (uint32_t)(n - p0 < BZ_PAYLOAD ? n - p0 : BZ_PAYLOAD);
+    const uint8_t* const src = in + p0;
+    // ---- the payload into LDS, the CRC table, an empty histogram and bit stream ----
+    if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
+        const uint32_t n16 = len >> 4;
+        for (uint32_t q = tid; q < n16; q += 256u) reinterpret_cast<uint4*>(s_in)[q] = reinterpret_cast<const uint4*>(src)[q];
+        for (uint32_t i = (n16 << 4) + tid; i < len; i += 256u) s_in[i] = src[i];
+    } else
+        for (uint32_t i = tid; i < len; i += 256u) s_in[i] = src[i];
+    {
+        uint32_t c = tid;
+        for (int k = 0; k < 8; ++k) c = (c & 1u) ? BZ_POLY ^ (c >> 1) : c >> 1;
+        s_tab[tid] = c;
+    }
+    for (uint32_t i = tid; i < 257u; i += 256u) s_hist[i] = i == 256u ? 1u : 0u;          // the end-of-block symbol occurs once
+    if (level == 1) for (uint32_t i = tid; i < BZ_OUT_WORDS; i += 256u) s_out[i] = 0;
+    __syncthreads();
+    // ---- a lane's sub-chunk: its CRC-32, its bytes into the histogram ----
+    const uint32_t chunk = (len + 255u) >> 8;
+    const uint32_t a = tid * chunk < len ? tid * chunk : len, e = a + chunk < len ? a + chunk : len;
+    uint32_t crc = 0xFFFFFFFFu;
+    for (uint32_t i = a; i < e; ++i) {
+        const uint32_t by = s_in[i];
+        crc = s_tab[(crc ^ by) & 255u] ^ (crc >> 8);
+        if (level == 1) atomicAdd(&s_hist[by], 1u);
+    }
+    crc ^= 0xFFFFFFFFu;                              // (an empty sub-chunk: 0)
+    uint32_t part = a < e ? bz_mul(bz_xpow8(len - e), crc) : 0u;
+    for (int off = 32; off; off >>= 1) part ^= __shfl_xor(part, off);
+    if (lane == 0) s_wave[wv] = part;
+    __syncthreads();
+    const uint32_t crc_all = s_wave[0] ^ s_wave[1] ^ s_wave[2] ^ s_wave[3];
+    __syncthreads();                                 // (s_wave is used again below)
+    bool huff = false;
+    uint32_t total_bits = 0;
+    if (level == 1) {
+        // ---- the symbols in use in ascending (count, symbol) order: every symbol finds its own rank ----
+        for (uint32_t s = tid; s < 257u; s += 256u) {
+            const uint32_t c = s_hist[s];
+            if (!c) continue;
+            uint32_t rank = 0;
+            for (uint32_t q = 0; q < 257u; ++q) { const uint32_t cq = s_hist[q]; rank += (cq && (cq < c || (cq == c && q < s))) ? 1u : 0u; }
+            s_ord[rank] = (uint16_t)s;
+        }
+        for (uint32_t s = tid; s < 257u; s += 256u) s_code[s] = 0;
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t m = 0;
+            for (uint32_t s = 0; s < 257u; ++s) m += s_hist[s] ? 1u : 0u;               // >= 2: a literal and the end of block
+            for (uint32_t i = 0; i < m; ++i) s_wt[i] = s_hist[s_ord[i]];
+            for (;;) {
+                // Huffman's algorithm on sorted leaves: leaves [0, m) and the nodes made so far [m, nn) are two ascending queues
+                uint32_t li = 0, ni = m, nn = m;
+                while (nn < 2u * m - 1u) {
+                    uint32_t pick[2];
+                    for (int k = 0; k < 2; ++k) pick[k] = (li < m && (ni >= nn || s_wt[li] <= s_wt[ni])) ? li++ : ni++;
+                    s_wt[nn] = s_wt[pick[0]] + s_wt[pick[1]];
+                    s_par[pick[0]] = s_par[pick[1]] = (uint16_t)nn;
+                    ++nn;
+                }
+                s_dep[2u * m - 2u] = 0;
+                uint32_t deepest = 0;
+                for (uint32_t i = 2u * m - 2u; i-- > 0;) {
+                    const uint32_t d = (uint32_t)s_dep[s_par[i]] + 1u;
+                    s_dep[i] = (uint8_t)(d < 255u ? d : 255u);
+                    if (i < m && d > deepest) deepest = d;
+                }
+                if (deepest <= 15u) break;
+                for (uint32_t i = 0; i < m; ++i) s_wt[i] = (s_wt[i] + 1u) >> 1;          // deeper than deflate allows: flatter counts (the order stays ascending), again
+            }
+            // canonical codes (RFC 1951 section 3.2.2), kept bit-reversed: Huffman codes enter the stream from their most significant bit
+            uint32_t cnt[16], next[16];
+            for (int k = 0; k < 16; ++k) cnt[k] = 0;
+            for (uint32_t i = 0; i < m; ++i) { ++cnt[s_dep[i]]; s_code[s_ord[i]] = (uint32_t)s_dep[i] << 16; }
+            uint32_t code = 0;
+            next[0] = 0;
+            for (int k = 1; k < 16; ++k) { code = (code + cnt[k - 1]) << 1; next[k] = code; }
+            unsigned long long bits = BZ_HDR_BITS;
+            for (uint32_t s = 0; s < 257u; ++s) {
+                const uint32_t l = s_code[s] >> 16;
+                if (!l) continue;
+                s_code[s] = (l << 16) | (__brev(next[l]++) >> (32u - l));
+                bits += (unsigned long long)s_hist[s] * l;
+            }
+            const bool use = (bits + 7u) / 8u < (unsigned long long)len + 5u;           // not smaller than stored: stored
+            s_misc[0] = use ? 1u : 0u; s_misc[1] = (uint32_t)bits;
+            if (use) {
+                BzBits w; w.start(s_out, 0);
+                w.put(1u, 1); w.put(2u, 2); w.put(0u, 5); w.put(0u, 5); w.put(15u, 4);
+                // code-length symbols 0 .. 15 take four bits each (their canonical code is their value), 16 .. 18 are not used;
+                // transmitted in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
+                for (int k = 0; k < 19; ++k) w.put(k < 3 ? 0u : 4u, 3);
+                for (uint32_t s = 0; s < 257u; ++s) w.put(__brev(s_code[s] >> 16) >> 28, 4);
+                w.put(__brev(1u) >> 28, 4);          // one distance code of length 1, never used
+                w.flush();
+            }
+        }
+        __syncthreads();
+        huff = s_misc[0] != 0; total_bits = s_misc[1];
+        if (huff) {
+            // ---- every lane's bit count, their prefix sum, and the lane's codes ORed into the stream behind the header ----
+            uint32_t nbits = 0;
+            for (uint32_t i = a; i < e; ++i) nbits += s_code[s_in[i]] >> 16;
+            uint32_t incl = nbits;
+            for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(incl, off); if ((int)lane >= off) incl += t; }
+            if (lane == 63u) s_wave[wv] = incl;
+            __syncthreads();
+            uint32_t before = 0;
+            for (uint32_t q = 0; q < wv; ++q) before += s_wave[q];
+            BzBits w; w.start(s_out, BZ_HDR_BITS + before + incl - nbits);
+            for (uint32_t i = a; i < e; ++i) { const uint32_t c = s_code[s_in[i]]; w.put(c & 0xFFFFu, c >> 16); }
+            w.flush();
+            if (tid == 0) { const uint32_t c = s_code[256]; BzBits z; z.start(s_out, total_bits - (c >> 16)); z.put(c & 0xFFFFu, c >> 16); z.flush(); }
+            __syncthreads();
+        }
+    }
+    // ---- the block into its slot: header, deflate stream, CRC-32, ISIZE ----
+    const uint32_t body = huff ? (total_bits + 7u) >> 3 : len + 5u;
+    const uint32_t bsize = 18u + body + 8u;
+    uint8_t* const o = slots + (size_t)blockIdx.x * BZ_SLOT;
+    if (tid < 18u) {
+        const uint32_t bs1 = bsize - 1u;
+        const uint8_t hd[18] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)(bs1 & 255u), (uint8_t)(bs1 >> 8) };
+        o[tid] = hd[tid];
+    }
+    if (huff) {
+        const uint8_t* const sb = reinterpret_cast<const uint8_t*>(s_out);
+        for (uint32_t i = tid; i < body; i += 256u) o[18u + i] = sb[i];
+    } else {
+        if (tid < 5u) {
+            const uint32_t nl = ~len & 0xFFFFu;
+            const uint8_t sh[5] = { 1, (uint8_t)(len & 255u), (uint8_t)(len >> 8), (uint8_t)(nl & 255u), (uint8_t)(nl >> 8) };
+            o[18u + tid] = sh[tid];
+        }
+        for (uint32_t i = tid; i < len; i += 256u) o[23u + i] = s_in[i];
+    }
+    if (tid < 8u) { const uint32_t v = tid < 4u ? crc_all : len; o[18u + body + tid] = (uint8_t)(v >> (8u * (tid & 3u))); }
+    if (tid == 0) sizes[blockIdx.x] = bsize;
+}
+
+__global__ void __launch_bounds__(256) k_bgzf_compact(const uint8_t* __restrict__ slots, const unsigned long long* __restrict__ off, uint8_t* __restrict__ out) {
+    const unsigned long long a = off[blockIdx.x];
+    const uint32_t size = (uint32_t)(off[blockIdx.x + 1] - a);
+    const uint8_t* const s = slots + (size_t)blockIdx.x * BZ_SLOT;
+    uint8_t* const d = out + a;
+    if (size > BZ_SLOT) return;
+    // the destination's first 16-byte boundary onward in whole 16-byte stores, the two ends byte-wise
+    const uint32_t to16 = (uint32_t)((16u - (reinterpret_cast<uintptr_t>(d) & 15u)) & 15u), head = to16 < size ? to16 : size;
+    const uint32_t n16 = (size - head) >> 4;
+    for (uint32_t i = threadIdx.x; i < head; i += 256u) d[i] = s[i];
+    for (uint32_t q = threadIdx.x; q < n16; q += 256u) { uint4 v; __builtin_memcpy(&v, s + head + (q << 4), 16); *reinterpret_cast<uint4*>(d + head + (q << 4)) = v; }
+    for (uint32_t i = head + (n16 << 4) + threadIdx.x; i < size; i += 256u) d[i] = s[i];
+}
+
+// ------------------------------------------------------------------------------------------------
+// BAM records
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool bm_op(char c) { return c == 'M' || c == 'I' || c == 'D'; } // all k_out_write ever puts into the pool
+__device__ __forceinline__ char bm_comp_char(char c) {                                      // as go_comp_char (gm_output.hip)
+    const char lo = (char)(c | 0x20);
+    const char up = (char)(c == lo ? 0 : 0x20);
+    switch (lo) {
+        case 'a': return (char)('t' - up); case 't': return (char)('a' - up);
+        case 'c': return (char)('g' - up); case 'g': return (char)('c' - up);
+        default: return c == '-' ? '-' : 'n';
+    }
+}
+// "=ACMGRSVTWYHKDBN", either case; anything else is N
+__device__ __forceinline__ uint32_t bm_nibble(char c) {
+    switch (c & ~0x20) {
+        case 'A': return 1; case 'C': return 2; case 'M': return 3; case 'G': return 4; case 'R': return 5; case 'S': return 6; case 'V': return 7;
+        case 'T': return 8; case 'W': return 9; case 'Y': return 10; case 'H': return 11; case 'K': return 12; case 'D': return 13; case 'B': return 14;
+        default: return c == '=' ? 0u : 15u;
+    }
+}
+// SAMv1 section 5.3
+__device__ __forceinline__ uint32_t bm_reg2bin(long long beg, long long end) {
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+__device__ __forceinline__ uint32_t bm_name_len(const GmDevText& t, uint32_t rd) {
+    const unsigned long long nl = t.name_off[rd + 1] - t.name_off[rd];
+    return nl > 254ull ? 254u : (uint32_t)nl;
+}
+
+__global__ void __launch_bounds__(256) k_bam_sizes(GmDevText t, uint32_t* __restrict__ meta) {
+    const unsigned long long k = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    if (k >= t.n_recs) return;
+    const GmDevSamRec r = t.recs[k];
+    const uint8_t* slot = t.slots + k * 64ull;
+    const uint32_t gout = (uint32_t)slot[58] | ((uint32_t)slot[59] << 8);          // the CIGAR field as the row prints it: bytes [0, gout) of the pool's
+    const char* cg = t.pool + r.cigar_off;
+    uint32_t n_ops = 0, v = 0;
+    unsigned long long ref_len = 0;
+    for (uint32_t i = 0; i < gout; ++i) {
+        const char c = cg[i];
+        if (c >= '0' && c <= '9') v = v * 10u + (uint32_t)(c - '0');
+        else { if (bm_op(c)) { ++n_ops; if (c != 'I') ref_len += v; } v = 0; }
+    }
+    if (!ref_len) ref_len = 1;
+    const long long pos0 = (long long)(int32_t)(uint32_t)(r.chr_pos - 1ull);
+    const uint32_t L = t.seq_len[r.read];
+    meta[2ull * k] = n_ops;
+    meta[2ull * k + 1ull] = bm_reg2bin(pos0, pos0 + (long long)ref_len);
+    t.row_len[k] = 4u + 32u + bm_name_len(t, r.read) + 1u + 4u * n_ops + ((L + 1u) >> 1) + L + 21u;
+}
+
+__device__ __forceinline__ void bm_put32(uint8_t* w, uint32_t v) { w[0] = (uint8_t)v; w[1] = (uint8_t)(v >> 8); w[2] = (uint8_t)(v >> 16); w[3] = (uint8_t)(v >> 24); }
+
+// one wavefront per record, four records per workgroup and step
+__global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, const uint32_t* __restrict__ meta) {
+    __shared__ uint8_t s_head[4][64];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    uint8_t* const hd = s_head[wv];
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 4ull; base < t.n_recs; base += (unsigned long long)gridDim.x * 4ull) {
+        const unsigned long long k = base + wv;
+        const bool live = k < t.n_recs;
+        GmDevSamRec r = {};
+        uint32_t n_ops = 0, nl = 0, L = 0;
+        if (live) {
+            r = t.recs[k];
+            n_ops = meta[2ull * k]; nl = bm_name_len(t, r.read); L = t.seq_len[r.read];
+            if (lane == 0) {                          // [0, 36) block_size and the core fields, [36, 57) the tags
+                const uint32_t size = (uint32_t)(t.row_off[k + 1] - t.row_off[k]);
+                const int32_t q = r.mapq < 0 ? 0 : r.mapq > 255 ? 255 : r.mapq;
+                bm_put32(hd, size - 4u); bm_put32(hd + 4, r.contig); bm_put32(hd + 8, (uint32_t)(r.chr_pos - 1ull));
+                hd[12] = (uint8_t)(nl + 1u); hd[13] = (uint8_t)q;
+                const uint32_t bin = meta[2ull * k + 1ull];
+                hd[14] = (uint8_t)bin; hd[15] = (uint8_t)(bin >> 8); hd[16] = (uint8_t)n_ops; hd[17] = (uint8_t)(n_ops >> 8);
+                hd[18] = r.strand ? 16 : 0; hd[19] = 0;
+                bm_put32(hd + 20, L); bm_put32(hd + 24, 0xFFFFFFFFu); bm_put32(hd + 28, 0xFFFFFFFFu); bm_put32(hd + 32, 0u);
+                hd[36] = 'X'; hd[37] = 'A'; hd[38] = 'f'; bm_put32(hd + 39, __float_as_uint((float)((double)r.a_score * t.inv_adjust)));
+                hd[43] = 'X'; hd[44] = 'P'; hd[45] = 'f'; bm_put32(hd + 46, __float_as_uint(r.post_prob));
+                hd[50] = 'X'; hd[51] = '0'; hd[52] = 'i'; bm_put32(hd + 53, (uint32_t)r.sim_matches);
+            }
+        }
+        __syncthreads();
+        if (live) {
+            const unsigned long long end = t.row_off[k + 1];
+            unsigned long long o = t.row_off[k];
+            uint8_t* const out = reinterpret_cast<uint8_t*>(t.text);
+            const uint8_t* slot = t.slots + k * 64ull;
+            const uint32_t gout = (uint32_t)slot[58] | ((uint32_t)slot[59] << 8);
+            const uint32_t rd = r.read;
+            const unsigned long long n0 = t.name_off[rd];
+            const unsigned long long q0 = t.qtail_off ? t.qtail_off[rd] : 0ull;
+            const uint32_t TL = t.qtail_off ? (uint32_t)(t.qtail_off[rd + 1] - q0) : 0u, QL = L + TL;
+            const bool neg = r.strand != 0;
+            // every store stays inside the span the scan gave this record, whatever the lengths say
+            if (lane < 36u && o + lane < end) out[o + lane] = hd[lane];
+            o += 36u;
+            for (uint32_t i = lane; i < nl; i += 64u) if (o + i < end) out[o + i] = (uint8_t)t.names[n0 + i];
+            if (lane == 0 && o + nl < end) out[o + nl] = 0;
+            o += nl + 1u;
+            {   // operation kk of the field in print order; on the reverse strand the row prints the tokens last to first
+                const char* cg = t.pool + r.cigar_off;
+                uint32_t seen = 0;
+                for (uint32_t i0 = 0; i0 < gout; i0 += 64u) {
+                    const uint32_t i = i0 + lane;
+                    const char c = i < gout ? cg[i] : '0';
+                    const bool is_op = bm_op(c);
+                    const unsigned long long m = __builtin_amdgcn_ballot_w64(is_op);
+                    if (is_op) {
+                        const uint32_t kk = seen + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                        uint32_t v = 0, mul = 1;
+                        for (uint32_t ts = i, d = 0; ts > 0 && d < 9u && cg[ts - 1u] >= '0' && cg[ts - 1u] <= '9'; --ts, ++d) { v += (uint32_t)(cg[ts - 1u] - '0') * mul; mul *= 10u; }
+                        const uint32_t word = (v << 4) | (c == 'M' ? 0u : c == 'I' ? 1u : 2u);
+                        const uint32_t j = neg ? n_ops - 1u - kk : kk;
+                        if (kk < n_ops)
+                            for (uint32_t q = 0; q < 4u; ++q) if (o + 4ull * j + q < end) out[o + 4ull * j + q] = (uint8_t)(word >> (8u * q));
+                    }
+                    seen += (uint32_t)__popcll(m);
+                }
+            }
+            o += 4ull * n_ops;
+            const uint8_t* bs = b.bases + (size_t)rd * b.stride; const uint8_t* qs = b.quals + (size_t)rd * b.stride;
+            const uint32_t half = (L + 1u) >> 1;
+            for (uint32_t i = lane; i < half; i += 64u) {
+                const uint32_t j0 = 2u * i, j1 = j0 + 1u;
+                const char c0 = neg ? bm_comp_char((char)bs[L - 1u - j0]) : (char)bs[j0];
+                uint32_t v = bm_nibble(c0) << 4;
+                if (j1 < L) v |= bm_nibble(neg ? bm_comp_char((char)bs[L - 1u - j1]) : (char)bs[j1]);
+                if (o + i < end) out[o + i] = (uint8_t)v;
+            }
+            o += half;
+            for (uint32_t i = lane; i < L; i += 64u) {
+                const uint32_t si = neg ? QL - 1u - i : i;         // the first L characters of the QUAL field the row prints (k_out_text_rows)
+                const uint8_t c = b.fasta ? (uint8_t)(t.fa_qual >> (8u * (((uint32_t)__popc(gm_iupac_mask(bs[si < L ? si : 0u])) - 1u) & 3u)))
+                                  : si < L ? qs[si] : (uint8_t)t.qtail[q0 + (si - L)];
+                if (o + i < end) out[o + i] = c > 33u ? (uint8_t)(c - 33u) : (uint8_t)0;
+            }
+            o += L;
+            if (lane < 21u && o + lane < end) out[o + lane] = hd[36u + lane];
+        }
+        __syncthreads();
+    }
+}
+
+inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// launchers and host code
+// ------------------------------------------------------------------------------------------------
+int gmk_bam_sizes(const GmDevText& t, uint32_t* meta, void* stream) {
+    if (t.n_recs == 0) return 0;
+    hipLaunchKernelGGL(k_bam_sizes, dim3(cdiv(t.n_recs, 256)), dim3(256), 0, S_(stream), t, meta);
+    return (int)hipGetLastError();
+}
+
+int gmk_bam_rows(const GmDevBatch& b, const GmDevText& t, const uint32_t* meta, void* stream) {
+    if (t.n_recs == 0) return 0;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((t.n_recs + 3) / 4, 4096);
+    hipLaunchKernelGGL(k_bam_rows, dim3(grid), dim3(256), 0, S_(stream), b, t, meta);
+    return (int)hipGetLastError();
+}
+
+void GmBgzfBufs::release() {
+    for (DevBuf* d : { &slots, &sizes, &offs, &tmp, &out }) d->release();
+    for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+}
+
+uint64_t gm_bgzf_bound(uint64_t n) { return n + (uint64_t)BZ_EXTRA * ((n + BZ_PAYLOAD - 1) / BZ_PAYLOAD); }
+
+// the most input bytes whose worst-case (stored) BGZF form fits in cap
+uint64_t gm_bgzf_room(uint64_t cap) {
+    const uint64_t per = (uint64_t)BZ_PAYLOAD + BZ_EXTRA, whole = cap / per, rest = cap % per;
+    return whole * BZ_PAYLOAD + (rest > BZ_EXTRA ? rest - BZ_EXTRA : 0);
+}
+
+// d_in[0, n) in HBM -> whole BGZF blocks side by side in z.out, *total bytes of them; synchronises the stream
+int gm_bgzf_device(const void* d_in, uint64_t n, int level, GmBgzfBufs& z, uint64_t* total, void* stream) {
+    *total = 0;
+    if (!n) return GM_OK;
+    if (level != 0 && level != 1) { gm_set_error("BGZF: the level is 0 (stored) or 1 (Huffman), not " + std::to_string(level)); return GM_E_ARG; }
+    const uint64_t nb64 = (n + BZ_PAYLOAD - 1) / BZ_PAYLOAD;
+    if (nb64 > 0x7FFFFFFFull) { gm_set_error("BGZF: more than 2^31 - 1 blocks in one call"); return GM_E_ARG; }
+    const uint32_t nb = (uint32_t)nb64;
+    hipStream_t st = S_(stream);
+    if (z.slots.ensure((size_t)nb * BZ_SLOT) || z.sizes.ensure((size_t)nb * 4) || z.offs.ensure(((size_t)nb + 1) * 8) || z.tmp.ensure(((size_t)nb / 1024 + 8) * 8) ||
+        z.out.ensure((size_t)gm_bgzf_bound(n) + 16)) return GM_E_NOMEM;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgzf_deflate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BZ_LDS));
+    if (z.timed) { for (auto& e : z.ev) if (!e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(z.ev[0], st)); }
+    hipLaunchKernelGGL(k_bgzf_deflate, dim3(nb), dim3(256), BZ_LDS, st, (const uint8_t*)d_in, (unsigned long long)n, level, z.slots.as<uint8_t>(), z.sizes.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    KCHK(gmk_scan_u32(z.sizes.as<uint32_t>(), nb, z.offs.as<uint64_t>(), z.tmp.as<unsigned long long>(), stream));
+    if (z.timed) HIPCHK(hipEventRecord(z.ev[1], st));
+    uint64_t sum = 0;
+    HIPCHK(hipMemcpyAsync(&sum, z.offs.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (sum > gm_bgzf_bound(n) || sum < 28ull * nb) { gm_set_error("BGZF: the blocks' sizes sum to " + std::to_string(sum) + " bytes for " + std::to_string(n) + " bytes of input"); return GM_E_HIP; }
+    if (z.timed) HIPCHK(hipEventRecord(z.ev[2], st));
+    hipLaunchKernelGGL(k_bgzf_compact, dim3(nb), dim3(256), 0, st, z.slots.as<uint8_t>(), z.offs.as<unsigned long long>(), z.out.as<uint8_t>());
+    HIPCHK(hipGetLastError());
+    if (z.timed) {
+        float a = 0, b = 0;
+        HIPCHK(hipEventRecord(z.ev[3], st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&a, z.ev[0], z.ev[1]));
+        HIPCHK(hipEventElapsedTime(&b, z.ev[2], z.ev[3]));
+        z.ms += (double)a + b; z.in_bytes += n; z.out_bytes += sum;
+    }
+    *total = sum;
+    return GM_OK;
+}
+
+extern "C" int gm_bgzf_compress(gm_index* ix, const void* data, uint64_t n, int level, void* out, uint64_t cap, uint64_t* n_out, void* hip_stream) {
+    if (!ix || !n_out) return GM_E_ARG;
+    *n_out = 0;
+    if (level != 0 && level != 1) { gm_set_error("gm_bgzf_compress: the level is 0 (stored) or 1 (Huffman), not " + std::to_string(level)); return GM_E_ARG; }
+    if (ix->host_only) { gm_set_error("gm_bgzf_compress: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (!n) return GM_OK;
+    if (!data || (!out && cap)) { gm_set_error("gm_bgzf_compress: data or out is NULL"); return GM_E_ARG; }
+    HIPCHK(hipSetDevice(ix->device));
+    hipStream_t st = S_(hip_stream);
+    Scoped<DevBuf> d_in;
+    Scoped<GmBgzfBufs> z;
+    if (d_in.ensure((size_t)n + 16)) return GM_E_NOMEM;
+    HIPCHK(hipMemcpyAsync(d_in.p, data, (size_t)n, hipMemcpyHostToDevice, st));
+    uint64_t total = 0;
+    if (const int rc = gm_bgzf_device(d_in.p, n, level, z, &total, hip_stream)) { (void)hipStreamSynchronize(st); return rc; }
+    *n_out = total;
+    if (total > cap) {
+        (void)hipStreamSynchronize(st);
+        gm_set_error("gm_bgzf_compress: the blocks take " + std::to_string(total) + " bytes, the buffer holds " + std::to_string(cap));
+        return GM_E_CAPACITY;
+    }
+    HIPCHK(hipMemcpyAsync(out, z.out.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GM_OK;
+}
+
+extern "C" int gm_bgzf_eof(void* out28) {
+    if (!out28) return GM_E_ARG;
+    static const uint8_t eof[28] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    memcpy(out28, eof, 28);
+    return GM_OK;
+}
+
+extern "C" int gm_bam_header(gm_index* ix, const char* sam_header, uint64_t n, void* out, uint64_t cap, uint64_t* n_out) {
+    if (!ix || !n_out || (!sam_header && n)) return GM_E_ARG;
+    const auto& contigs = ix->h.contigs;
+    uint64_t need = 4 + 4 + n + 4;
+    for (const auto& c : contigs) need += 4 + c.name.size() + 1 + 4;
+    *n_out = need;
+    if (n > 0x7FFFFFFFull) { gm_set_error("gm_bam_header: a header text of more than 2^31 - 1 bytes"); return GM_E_ARG; }
+    if (need > cap || !out) { gm_set_error("gm_bam_header: the header takes " + std::to_string(need) + " bytes, the buffer holds " + std::to_string(cap)); return GM_E_CAPACITY; }
+    uint8_t* w = (uint8_t*)out;
+    auto put32 = [&](uint32_t v) { w[0] = (uint8_t)v; w[1] = (uint8_t)(v >> 8); w[2] = (uint8_t)(v >> 16); w[3] = (uint8_t)(v >> 24); w += 4; };
+    memcpy(w, "BAM\1", 4); w += 4;
+    put32((uint32_t)n);
+    if (n) memcpy(w, sam_header, (size_t)n);
+    w += n;
+    put32((uint32_t)contigs.size());
+    for (const auto& c : contigs) {
+        put32((uint32_t)c.name.size() + 1u);
+        memcpy(w, c.name.c_str(), c.name.size() + 1); w += c.name.size() + 1;
+        put32(c.len);
+    }
+    return GM_OK;
+}

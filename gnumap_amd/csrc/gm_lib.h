@@ -90,3 +90,21 @@ int index_cnames(gm_index* ix);                                 // contig names 
 int gm_samsort_claim(gm_sam_sorter* s, const gm_index* ix, uint64_t seq);
 void gm_samsort_release(gm_sam_sorter* s, uint64_t seq);     // the claim back, when the call failed before a row of the block was added
 int gm_samsort_add(gm_sam_sorter* s, uint64_t seq, const GmDevSamRec* recs, uint64_t n_rows, const char* d_text, const uint64_t* d_rowoff, uint64_t text_len, void* stream);
+int gm_samsort_rows(gm_sam_sorter* s);                       // GM_ROWS_TEXT / GM_ROWS_BAM: what the blocks put into the arena
+
+// gm_bam.hip.  The record kernels run behind gmk_out_text_sizes on the same GmDevText: sizes overwrites row_len with the records' sizes
+// and leaves (operations, bin) per record in meta; rows writes the records at row_off into t.text.
+int gmk_bam_sizes(const GmDevText& t, uint32_t* meta, void* stream);
+int gmk_bam_rows(const GmDevBatch& b, const GmDevText& t, const uint32_t* meta, void* stream);
+// BGZF: the worst-case slots of the blocks, their sizes and the scan of those, and the blocks side by side
+struct GmBgzfBufs {
+    DevBuf slots, sizes, offs, tmp, out;
+    bool timed = false;                     // HIP events around k_bgzf_deflate + the scan and around k_bgzf_compact, summed into ms (one more wait per call)
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    double ms = 0; uint64_t in_bytes = 0, out_bytes = 0;
+    void release();
+};
+uint64_t gm_bgzf_bound(uint64_t n);                          // the most bytes the blocks of n input bytes take: n + 31 per started 65280
+uint64_t gm_bgzf_room(uint64_t cap);                         // the most input bytes whose blocks are sure to fit in cap
+// d_in[0, n) in HBM -> z.out[0, *total); synchronises the stream.  level 0 stored, 1 Huffman
+int gm_bgzf_device(const void* d_in, uint64_t n, int level, GmBgzfBufs& z, uint64_t* total, void* stream);

@@ -168,6 +168,8 @@ struct gm_sam_sorter {
     std::vector<char*> pieces; size_t used = 0;         // used: bytes of the last piece that hold rows
     std::map<uint64_t, SsBlock> blocks;                 // by sequence number
     uint64_t table_bytes = 0;
+    int rows = GM_ROWS_TEXT;                            // what the blocks put into the arena: SAM rows as text or BAM records (gm_sam_sorter_set_rows)
+    GmBgzfBufs bz;                                      // gm_sam_sorter_read_bgzf: the slab's blocks
     bool closed = false, finished = false;              // closed: finish was called, no more blocks; finished: it succeeded, the rows can be read
     int failed = GM_OK; std::string fail_text;          // finish failed: every later finish / read returns this
     uint64_t n_rows = 0, text_bytes = 0, next_row = 0, next_off = 0;
@@ -215,9 +217,21 @@ extern "C" void gm_sam_sorter_destroy(gm_sam_sorter* s) {
     for (char* p : s->pieces) (void)hipFree(p);
     for (auto& b : s->blocks) if (b.second.tab) (void)hipFree(b.second.tab);
     for (DevBuf* d : { &s->bound, &s->soff, &s->splace, &s->d_pieces, &s->slab, &s->spans }) d->release();
+    s->bz.release();
     for (auto e : s->ev) if (e) (void)hipEventDestroy(e);
     delete s;
 }
+
+extern "C" int gm_sam_sorter_set_rows(gm_sam_sorter* s, int rows) {
+    if (!s) return GM_E_ARG;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (rows != GM_ROWS_TEXT && rows != GM_ROWS_BAM) { gm_set_error("gm_sam_sorter_set_rows: GM_ROWS_TEXT or GM_ROWS_BAM"); return GM_E_ARG; }
+    if (!s->blocks.empty() || s->closed) { gm_set_error("gm_sam_sorter_set_rows: the sorter holds blocks already"); return GM_E_ARG; }
+    s->rows = rows;
+    return GM_OK;
+}
+
+int gm_samsort_rows(gm_sam_sorter* s) { std::lock_guard<std::mutex> lk(s->mu); return s->rows; }
 
 // the sequence number is taken before anything of the block is computed: a seq used twice or an add after finish deposits nothing
 int gm_samsort_claim(gm_sam_sorter* s, const gm_index* ix, uint64_t seq) {
@@ -404,32 +418,27 @@ static int ss_sort(gm_sam_sorter* s, void* stream) {
     return GM_OK;
 }
 
-extern "C" int gm_sam_sorter_read(gm_sam_sorter* s, char* text, uint64_t cap, uint64_t* n_out, void* stream) {
-    if (!s || !n_out) return GM_E_ARG;
-    *n_out = 0;
-    std::lock_guard<std::mutex> lk(s->mu);
+// the next whole rows that fit in `room` bytes, gathered into s->slab on `st` (not waited for): *bytes of them, 0 when none is left;
+// GM_E_CAPACITY with *bytes = the next row's length when that row alone is longer.  Under the sorter's mutex
+static int ss_gather_next(gm_sam_sorter* s, const char* who, uint64_t room, uint64_t* bytes_out, uint64_t* r1_out, uint64_t* off1_out, hipStream_t st) {
+    *bytes_out = 0;
     if (s->failed) { gm_set_error(s->fail_text); return s->failed; }
-    if (!s->finished) { gm_set_error("gm_sam_sorter_read: call gm_sam_sorter_finish first"); return GM_E_ARG; }
+    if (!s->finished) { gm_set_error(std::string(who) + ": call gm_sam_sorter_finish first"); return GM_E_ARG; }
+    *r1_out = s->next_row; *off1_out = s->next_off;
     if (s->next_row >= s->n_rows) return GM_OK;
-    if (!text && cap) { gm_set_error("gm_sam_sorter_read: text is NULL"); return GM_E_ARG; }
     HIPCHK(hipSetDevice(s->ix->device));
-    hipStream_t st = S_(stream);
     unsigned long long res[3] = { 0, 0, 0 };
-    hipLaunchKernelGGL(k_ss_bound, dim3(1), dim3(1), 0, st, s->soff.as<unsigned long long>(), (unsigned long long)s->next_row, (unsigned long long)s->n_rows, (unsigned long long)cap,
+    hipLaunchKernelGGL(k_ss_bound, dim3(1), dim3(1), 0, st, s->soff.as<unsigned long long>(), (unsigned long long)s->next_row, (unsigned long long)s->n_rows, (unsigned long long)room,
                        s->bound.as<unsigned long long>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(res, s->bound.p, 24, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const uint64_t r0 = s->next_row, r1 = res[0];
-    if (r1 < r0 || r1 > s->n_rows || res[1] < s->next_off || res[1] - s->next_off > cap) { gm_set_error("gm_sam_sorter_read: the sorted offsets do not ascend"); return GM_E_HIP; }
-    if (r1 == r0) {
-        *n_out = res[2];
-        gm_set_error("gm_sam_sorter_read: the next row is " + std::to_string(res[2]) + " bytes long, the buffer holds " + std::to_string(cap));
-        return GM_E_CAPACITY;
-    }
+    if (r1 < r0 || r1 > s->n_rows || res[1] < s->next_off || res[1] - s->next_off > room) { gm_set_error(std::string(who) + ": the sorted offsets do not ascend"); return GM_E_HIP; }
+    if (r1 == r0) { *bytes_out = res[2]; return GM_E_CAPACITY; }
     const uint64_t bytes = res[1] - s->next_off;
     const uint64_t n_spans64 = (bytes + SS_SPAN - 1) / SS_SPAN;
-    if (n_spans64 > 0x7FFFFFF0ull) { gm_set_error("gm_sam_sorter_read: a slab of more than 8 TB"); return GM_E_ARG; }
+    if (n_spans64 > 0x7FFFFFF0ull) { gm_set_error(std::string(who) + ": a slab of more than 8 TB"); return GM_E_ARG; }
     const uint32_t n_spans = (uint32_t)n_spans64;
     // the last lane's store may reach up to 15 bytes past `bytes`: the slab is a whole number of spans
     if (s->slab.ensure((size_t)n_spans * SS_SPAN + 64) || s->spans.ensure(((size_t)n_spans + 1) * 4)) return GM_E_NOMEM;
@@ -440,16 +449,67 @@ extern "C" int gm_sam_sorter_read(gm_sam_sorter* s, char* text, uint64_t cap, ui
                        (const char* const*)s->d_pieces.p, s->spans.as<uint32_t>(), (uint32_t)r0, n_spans, (unsigned long long)bytes, s->slab.as<char>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[1], st));
+    *bytes_out = bytes; *r1_out = r1; *off1_out = res[1];
+    return GM_OK;
+}
+
+// the gather has run and has been waited for: its time, and the rows count as read
+static int ss_consumed(gm_sam_sorter* s, uint64_t bytes, uint64_t r1, uint64_t off1) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+    s->st.gather_ms += ms; s->st.gather_bytes += bytes;
+    s->next_row = r1; s->next_off = off1;
+    return GM_OK;
+}
+
+extern "C" int gm_sam_sorter_read(gm_sam_sorter* s, char* text, uint64_t cap, uint64_t* n_out, void* stream) {
+    if (!s || !n_out) return GM_E_ARG;
+    *n_out = 0;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!text && cap && s->finished && s->next_row < s->n_rows) { gm_set_error("gm_sam_sorter_read: text is NULL"); return GM_E_ARG; }
+    hipStream_t st = S_(stream);
+    uint64_t bytes = 0, r1 = 0, off1 = 0;
+    const int rc = ss_gather_next(s, "gm_sam_sorter_read", cap, &bytes, &r1, &off1, st);
+    if (rc == GM_E_CAPACITY) {
+        *n_out = bytes;
+        gm_set_error("gm_sam_sorter_read: the next row is " + std::to_string(bytes) + " bytes long, the buffer holds " + std::to_string(cap));
+        return rc;
+    }
+    if (rc != GM_OK || !bytes) return rc;
     HIPCHK(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipMemcpyAsync(text, s->slab.p, (size_t)bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     s->st.download_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-    s->st.gather_ms += ms; s->st.gather_bytes += bytes;
-    s->next_row = r1; s->next_off = res[1];
+    if (const int r = ss_consumed(s, bytes, r1, off1)) return r;
     *n_out = bytes;
+    return GM_OK;
+}
+
+extern "C" int gm_sam_sorter_read_bgzf(gm_sam_sorter* s, int level, void* out, uint64_t cap, uint64_t* n_out, void* stream) {
+    if (!s || !n_out) return GM_E_ARG;
+    *n_out = 0;
+    if (level != 0 && level != 1) { gm_set_error("gm_sam_sorter_read_bgzf: the level is 0 (stored) or 1 (Huffman), not " + std::to_string(level)); return GM_E_ARG; }
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!out && cap && s->finished && s->next_row < s->n_rows) { gm_set_error("gm_sam_sorter_read_bgzf: out is NULL"); return GM_E_ARG; }
+    hipStream_t st = S_(stream);
+    uint64_t bytes = 0, r1 = 0, off1 = 0;
+    const int rc = ss_gather_next(s, "gm_sam_sorter_read_bgzf", gm_bgzf_room(cap), &bytes, &r1, &off1, st);
+    if (rc == GM_E_CAPACITY) {
+        *n_out = gm_bgzf_bound(bytes);
+        gm_set_error("gm_sam_sorter_read_bgzf: the next row is " + std::to_string(bytes) + " bytes long and may take " + std::to_string(*n_out) + " as BGZF, the buffer holds " + std::to_string(cap));
+        return rc;
+    }
+    if (rc != GM_OK || !bytes) return rc;
+    uint64_t total = 0;
+    if (const int r = gm_bgzf_device(s->slab.p, bytes, level, s->bz, &total, stream)) return r;
+    if (total > cap) { gm_set_error("gm_sam_sorter_read_bgzf: the blocks outgrew their worst case"); return GM_E_HIP; }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemcpyAsync(out, s->bz.out.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    s->st.download_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (const int r = ss_consumed(s, bytes, r1, off1)) return r;
+    *n_out = total;
     return GM_OK;
 }
 

@@ -64,6 +64,9 @@ struct Options {
     bool read_text_device = false;  // --read_text=device: chunk-mode blocks go up as FASTQ text and are cut into reads on the GPU (gm_batch_upload_text); host = parse_range + pack_block
     bool sam_sort = false;          // --sam_sort=coordinate: the rows stay in HBM, are sorted there once and written in coordinate order (implies --sam_text=device)
     bool sam_text_host_set = false; // an explicit --sam_text=host (refused with --sam_sort=coordinate)
+    bool bam = false;               // --sam_format=bam: <out>.bam instead of <out>.sam, records and BGZF written on the GPU (gm_output_batch_bam; implies --sam_text=device)
+    int bam_level = 1;              // --bam_level=0|1: stored blocks, or Huffman-coded ones
+    bool bam_level_set = false;     // (refused without --sam_format=bam)
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
 
@@ -116,7 +119,11 @@ struct Options {
             "      --sam_sort=none|coordinate   none (default): rows in input order.  coordinate: the rows stay on the GPU until the input is\n"
             "                               exhausted, are sorted there by (contig in @SQ order, position) - equal keys keep input order -\n"
             "                               and written once, behind a first header line @HD VN:1.0 SO:coordinate.  Implies --sam_text=device;\n"
-            "                               one GPU, one <out>.sam (not with --sam_text=host, --sam_shards above 1 or --gpus above 1)\n");
+            "                               one GPU, one <out>.sam (not with --sam_text=host, --sam_shards above 1 or --gpus above 1)\n"
+            "      --sam_format=sam|bam     sam (default): <out>.sam.  bam: <out>.bam and no <out>.sam - the records and their BGZF blocks are\n"
+            "                               written on the GPU; with --sam_sort=coordinate the file is a sorted BAM.  Implies --sam_text=device\n"
+            "                               (not with --sam_text=host or --sam_shards above 1)\n"
+            "      --bam_level=0|1          with --sam_format=bam: 0 = stored BGZF blocks, 1 (default) = Huffman-coded blocks (no LZ77 matches)\n");
     exit(rc);
 }
 
@@ -183,6 +190,15 @@ static void parse_args(int argc, char** argv, Options& o) {
                 else if (!strcmp(s + 9, "none")) o.sam_sort = false;
                 else { fprintf(stderr, "Error: --sam_sort takes none or coordinate, not: %s\n", s + 9); exit(1); }
             }
+            else if (starts(s, "sam_format=")) {
+                if (!strcmp(s + 11, "bam")) o.bam = true;
+                else if (!strcmp(s + 11, "sam")) o.bam = false;
+                else { fprintf(stderr, "Error: --sam_format takes sam or bam, not: %s\n", s + 11); exit(1); }
+            }
+            else if (starts(s, "bam_level=")) {
+                if (strcmp(s + 10, "0") && strcmp(s + 10, "1")) { fprintf(stderr, "Error: --bam_level takes 0 or 1, not: %s\n", s + 10); exit(1); }
+                o.bam_level = s[10] - '0'; o.bam_level_set = true;
+            }
             else if (starts(s, "sam_shards=")) {
                 char* end = nullptr;
                 const long k = strtol(s + 11, &end, 10);
@@ -241,6 +257,12 @@ static void parse_args(int argc, char** argv, Options& o) {
         if (o.sam_text_host_set) { fprintf(stderr, "Error: --sam_sort=coordinate sorts the rows the GPU formats: it cannot be combined with --sam_text=host\n"); exit(1); }
         if (o.sam_shards > 1) { fprintf(stderr, "Error: --sam_sort=coordinate writes one sorted <out>.sam: it cannot be combined with --sam_shards above 1\n"); exit(1); }
         if (o.gpus > 1) { fprintf(stderr, "Error: --sam_sort=coordinate sorts on one GPU: it cannot be combined with --gpus above 1 (there is no cross-device merge)\n"); exit(1); }
+        o.sam_text_device = true;
+    }
+    if (o.bam_level_set && !o.bam) { fprintf(stderr, "Error: --bam_level sets the compression of --sam_format=bam: give --sam_format=bam with --bam_level\n"); exit(1); }
+    if (o.bam) {                                             // refused before a device is opened or a file is written
+        if (o.sam_text_host_set) { fprintf(stderr, "Error: --sam_format=bam writes the records on the GPU: it cannot be combined with --sam_text=host\n"); exit(1); }
+        if (o.sam_shards > 1) { fprintf(stderr, "Error: --sam_format=bam writes one <out>.bam: it cannot be combined with --sam_shards above 1\n"); exit(1); }
         o.sam_text_device = true;
     }
     if (o.batch < 1) o.batch = 1;
@@ -831,19 +853,31 @@ static int process_block(Worker& w, const Options& o, const char* base, Block& b
         rc = resident ? gm_output_batch_sorted_resident(w.ix, &bp, w.batch, &hits, w.sorter, b.sort_seq, w.stream)
                       : gm_output_batch_sorted(w.ix, &bp, w.batch, &reads, &rt, &hits, w.sorter, b.sort_seq, w.stream);
     } else if (o.sam_text_device) {                         // the rows come back as text: no records, no CIGAR pool on the host
-        call = resident ? "gm_output_batch_text_resident" : "gm_output_batch_text";
+        call = o.bam ? (resident ? "gm_output_batch_bam_resident" : "gm_output_batch_bam") : resident ? "gm_output_batch_text_resident" : "gm_output_batch_text";
         if (!b.dtext) b.dtext = w.text_pool->get();
         const size_t name_bytes = resident ? b.text_hi - b.text_lo : (size_t)b.name_off[n];
         b.dtext->ensure(((size_t)n + (size_t)n / 16) * (2 * (size_t)b.maxlen + 64) + name_bytes + 4096);
-        gm_sam_text st;
-        for (;;) {
-            st.text = b.dtext->data(); st.text_cap = b.dtext->size(); st.text_len = 0; st.n_recs = 0; st.row_off = nullptr; st.row_cap = 0;
-            rc = resident ? gm_output_batch_text_resident(w.ix, &bp, w.batch, &hits, &st, w.stream)
-                          : gm_output_batch_text(w.ix, &bp, w.batch, &reads, &rt, &hits, &st, w.stream);
-            if (rc != GM_E_CAPACITY) break;
-            b.dtext->ensure((size_t)st.text_cap + 64);
+        if (o.bam) {                                        // the block's records as BGZF blocks: its run of <out>.bam
+            gm_bam_out bo{};
+            for (;;) {
+                bo.data = b.dtext->data(); bo.cap = b.dtext->size(); bo.level = o.bam_level;
+                rc = resident ? gm_output_batch_bam_resident(w.ix, &bp, w.batch, &hits, &bo, w.stream)
+                              : gm_output_batch_bam(w.ix, &bp, w.batch, &reads, &rt, &hits, &bo, w.stream);
+                if (rc != GM_E_CAPACITY) break;
+                b.dtext->ensure((size_t)bo.cap + 64);
+            }
+            n_recs = bo.n_recs; text_len = bo.len;
+        } else {
+            gm_sam_text st;
+            for (;;) {
+                st.text = b.dtext->data(); st.text_cap = b.dtext->size(); st.text_len = 0; st.n_recs = 0; st.row_off = nullptr; st.row_cap = 0;
+                rc = resident ? gm_output_batch_text_resident(w.ix, &bp, w.batch, &hits, &st, w.stream)
+                              : gm_output_batch_text(w.ix, &bp, w.batch, &reads, &rt, &hits, &st, w.stream);
+                if (rc != GM_E_CAPACITY) break;
+                b.dtext->ensure((size_t)st.text_cap + 64);
+            }
+            n_recs = st.n_recs; text_len = st.text_len;
         }
-        n_recs = st.n_recs; text_len = st.text_len;
     } else {
         call = "gm_output_batch";
         if (resident) {
@@ -991,7 +1025,7 @@ static int open_devices(Run& R) {
         if (gm_index_open(o.genome.c_str(), g, flags, &R.gpu_ix[(size_t)g]) != GM_OK) { fprintf(stderr, "ERROR: GPU %d: %s\n", g, gm_last_error()); return 1; }
     for (int g = 0; g < o.gpus; ++g)                                   // k-mer tables / records for these parameters: part of staging the index
         if (gm_index_prepare(R.gpu_ix[(size_t)g], &o.p) != GM_OK) { fprintf(stderr, "ERROR: GPU %d: %s\n", g, gm_last_error()); return 1; }
-    if (o.sam_sort && gm_sam_sorter_create(R.gpu_ix[0], &R.sorter) != GM_OK) return fail();
+    if (o.sam_sort && (gm_sam_sorter_create(R.gpu_ix[0], &R.sorter) != GM_OK || gm_sam_sorter_set_rows(R.sorter, o.bam ? GM_ROWS_BAM : GM_ROWS_TEXT) != GM_OK)) return fail();
     R.workers = std::vector<Worker>((size_t)o.gpus * (size_t)o.workers);
     for (int g = 0; g < o.gpus; ++g) {
         gm_index* ix = R.gpu_ix[(size_t)g];
@@ -1020,7 +1054,7 @@ static int open_outputs(Run& R) {
     R.ofds.assign((size_t)K, -1);
     R.file_offs.assign((size_t)K, 0);
     for (int k = 0; k < K; ++k) {
-        const std::string fn = K == 1 ? o.output + ".sam" : o.output + "." + std::to_string(k) + ".sam";
+        const std::string fn = o.bam ? o.output + ".bam" : K == 1 ? o.output + ".sam" : o.output + "." + std::to_string(k) + ".sam";
         R.ofds[(size_t)k] = ::open(fn.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (R.ofds[(size_t)k] < 0) { fprintf(stderr, "ERROR: cannot write %s\n", fn.c_str()); return 1; }
     }
@@ -1030,7 +1064,15 @@ static int open_outputs(Run& R) {
         hd << "@SQ\tSN:" << gm_index_contig_name(R.gpu_ix[0], i) << "\tLN:"
            << (gm_index_contig_offset(R.gpu_ix[0], i + 1) - gm_index_contig_offset(R.gpu_ix[0], i)) << "\n";
     hd << "@PG\tID:gnumap\tPN:gnumap\tVN:4.0.0 BETA\tCL:" << R.cl << "\n";
-    const std::string s = hd.str();
+    std::string s = hd.str();
+    if (o.bam) {                                                       // the same lines inside the BAM header, as BGZF blocks
+        uint64_t raw_len = 0, z_len = 0;
+        (void)gm_bam_header(R.gpu_ix[0], s.data(), s.size(), nullptr, 0, &raw_len);
+        std::string raw((size_t)raw_len, '\0'), z((size_t)(raw_len + 31 * (raw_len / 65280 + 1)), '\0');
+        if (gm_bam_header(R.gpu_ix[0], s.data(), s.size(), &raw[0], raw.size(), &raw_len) != GM_OK ||
+            gm_bgzf_compress(R.gpu_ix[0], raw.data(), raw.size(), o.bam_level, &z[0], z.size(), &z_len, nullptr) != GM_OK) return fail();
+        s.assign(z.data(), (size_t)z_len);
+    }
     if (!write_all(R.ofds[0], s.data(), s.size())) { fprintf(stderr, "ERROR: write failed\n"); return 1; }
     return 0;
 }
@@ -1253,14 +1295,15 @@ static int drain_sorter(Run& R) {
     size_t cap = slab_cap;                                           // what gm_sam_sorter_read may fill of either buffer
     for (int k = 0;;) {                                              // k: the buffer the next slab goes into, while the other one is written
         uint64_t got = 0;
-        int rc = gm_sam_sorter_read(R.sorter, slab[k].data(), cap, &got, stream);
+        int rc = R.o.bam ? gm_sam_sorter_read_bgzf(R.sorter, R.o.bam_level, slab[k].data(), cap, &got, stream)      // (compressed before it comes down)
+                         : gm_sam_sorter_read(R.sorter, slab[k].data(), cap, &got, stream);
         if (rc == GM_E_CAPACITY) {                                   // a row longer than a slab: both buffers grow to it, the same read again
             if (wr.joinable()) wr.join();
             cap = (size_t)got;
             slab[0].ensure(cap); slab[1].ensure(cap);
             continue;
         }
-        if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_sam_sorter_read: %s\n", gm_last_error()); R.failed = 1; break; }
+        if (rc != GM_OK) { fprintf(stderr, "ERROR: %s: %s\n", R.o.bam ? "gm_sam_sorter_read_bgzf" : "gm_sam_sorter_read", gm_last_error()); R.failed = 1; break; }
         if (wr.joinable()) wr.join();
         if (!got || wr_bad) break;
         const uint64_t off = R.file_offs[0];
@@ -1328,7 +1371,7 @@ static void report(const Run& R, double t_pipe, double t_cov, double secs) {
     const double t_scan = R.t_scan + t.t_scan;
     if (o.sam_text_device)                               // no formatter stage: the rows were text when they left the library
         fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, %s %.2f, %s %.2f, %s %.2f, write %.2f\n",
-                R.t_index, t_scan, pack, t.t_pack, map, t.t_map, text_blocks ? "gm_output_batch_text_resident" : "gm_output_batch_text", t.t_out, R.t_write);
+                R.t_index, t_scan, pack, t.t_pack, map, t.t_map, o.bam ? (text_blocks ? "gm_output_batch_bam_resident" : "gm_output_batch_bam") : text_blocks ? "gm_output_batch_text_resident" : "gm_output_batch_text", t.t_out, R.t_write);
     else
         fprintf(stderr, "stage seconds (summed over threads): index %.2f, scan %.2f, %s %.2f, %s %.2f, gm_output_batch %.2f, SAM format %.2f, write %.2f\n",
                 R.t_index, t_scan, pack, t.t_pack, map, t.t_map, t.t_out, R.t_fmt, R.t_write);
@@ -1353,6 +1396,12 @@ int main(int argc, char** argv) {
         run_pass(R, false);
     }
     if (R.o.sam_sort && !R.failed && drain_sorter(R)) return 1;
+    if (R.o.bam && !R.failed) {                        // the empty block that ends a BGZF file
+        char eof[28];
+        (void)gm_bgzf_eof(eof);
+        if (!pwrite_all(R.ofds[0], eof, sizeof eof, R.file_offs[0])) { fprintf(stderr, "ERROR: write failed\n"); return 1; }
+        R.file_offs[0] += sizeof eof;
+    }
     for (int fd : R.ofds) ::close(fd);
     if (R.failed) return 1;
     const double t_pipe = secs_since(R.t_pipe0);

@@ -375,6 +375,47 @@ int gm_sam_sorter_stats(gm_sam_sorter*, gm_sam_sort_stats* out);
 int gm_sam_sorter_add_rows(gm_sam_sorter*, uint64_t seq, const char* text, const uint64_t* row_off, const uint32_t* contig, const uint64_t* chr_pos,
                            uint64_t n_rows, void* hip_stream);
 
+/* ---- BAM: binary records (SAMv1 section 4.2) inside BGZF, both written on the device (gm_bam.hip) ----
+ * gm_bam_header: the uncompressed bytes that open a BAM file - "BAM\1", l_text, the n bytes of sam_header, n_ref, then per contig of
+ * the index l_name, the name with its NUL and l_ref.  Host only: works on a host-only index.  *n_out = the size; GM_E_CAPACITY when
+ * that exceeds cap (nothing is written). */
+int gm_bam_header(gm_index*, const char* sam_header, uint64_t n, void* out, uint64_t cap, uint64_t* n_out);
+/* any n bytes of the caller's -> whole BGZF blocks of at most 65280 input bytes each, compressed on the device: level 0 stored blocks,
+ * level 1 one dynamic-Huffman block over literals only (no LZ77 matches), written stored where that is not smaller.  The output is a
+ * function of the input bytes and the level alone.  n = 0: *n_out = 0.  GM_E_ARG for another level, GM_E_NO_DEVICE on a host-only
+ * index, GM_E_CAPACITY (*n_out = the bytes needed, nothing is written) when the blocks exceed cap; n + 31 per started 65280 always holds them. */
+int gm_bgzf_compress(gm_index*, const void* data, uint64_t n, int level, void* out, uint64_t cap, uint64_t* n_out, void* hip_stream);
+/* the 28-byte empty block that ends a BGZF file */
+int gm_bgzf_eof(void* out28);
+/* gm_output_batch_text / _text_resident with a different ending: the same fp64 pass, traceback and deposits, and the block's records - one
+ * per gm_sam_rec, in gm_output_batch's order - leave as BGZF blocks (records may span blocks).  A record is the SAM row of the text form
+ * in binary: refID = contig, pos = chr_pos - 1, mapq clamped to 0 .. 255, bin = reg2bin(pos, pos + reference length of the CIGAR, 1 when
+ * that is 0), flag 0 / 16, no mate; read_name = the first 254 bytes of the name (l_read_name is one byte; the SAM row keeps up to 1023);
+ * the CIGAR operations, SEQ and the first l_seq characters of QUAL as the row prints them (len << 4 | op; nibbles of "=ACMGRSVTWYHKDBN",
+ * anything else 15; minus 33, floored at 0); tags XA:f = (float)((double)a_score / adjust), XP:f = post_prob's bits, X0:i as int32.
+ * level as in gm_bgzf_compress.  len = bytes of the blocks, raw_len = bytes of the records.  GM_E_CAPACITY: cap holds the size needed and
+ * NOTHING has been deposited - repeat the call.  GM_E_UNSUPPORTED exactly where gm_output_batch_text returns it (an XA / XP outside the
+ * range the text form prints), so both forms accept the same blocks.  A block with no mapped read: len = 0.  No enqueue form. */
+typedef struct {
+    void* data;
+    uint64_t cap, len, raw_len, n_recs;
+    int level;
+} gm_bam_out;
+int gm_output_batch_bam(gm_index*, const gm_params*, gm_batch*, const gm_reads*, const gm_read_text*, const gm_hits*, gm_bam_out* out, void* hip_stream);
+int gm_output_batch_bam_resident(gm_index*, const gm_params*, gm_batch*, const gm_hits*, gm_bam_out* out, void* hip_stream);
+/* while gm_batch_set_profiling is on, the two calls above bracket their kernels with HIP events (two more waits per call).  Since the last
+ * call of this function: ms[0] = k_bam_sizes + k_bam_rows, ms[1] = k_bgzf_deflate + the scan of the sizes + k_bgzf_compact; bytes[0] = bytes
+ * of records written, bytes[1] = bytes into and bytes[2] = bytes out of the BGZF kernels (tools/bam_bench.py) */
+int gm_batch_bam_times(gm_batch*, double* ms /* [2] */, uint64_t* bytes /* [3] */);
+/* what gm_output_batch_sorted / _sorted_resident put into a sorter's arena: SAM rows as text (default) or BAM records.  Keys, stable
+ * order and pieces are the same; gm_sam_sorter_read then returns whole records.  Before the first block: GM_E_ARG afterwards. */
+enum { GM_ROWS_TEXT = 0, GM_ROWS_BAM = 1 };
+int gm_sam_sorter_set_rows(gm_sam_sorter*, int rows);
+/* gm_sam_sorter_read with the slab compressed on the device before the download: the next whole rows whose BGZF form is sure to fit in
+ * cap (reserved for the worst case, stored: the rows' bytes + 31 per started 65280), as whole BGZF blocks.  *n_out = 0: done.
+ * GM_E_CAPACITY when the next row alone needs more: *n_out = the cap it needs, nothing is consumed. */
+int gm_sam_sorter_read_bgzf(gm_sam_sorter*, int level, void* out, uint64_t cap, uint64_t* n_out, void* hip_stream);
+
 /* enqueue / wait forms: the call is queued on the batch's own service thread and runs there exactly as the synchronous form would;
  * the caller goes on (with another batch).  Calls queued on one batch run in order - gm_output_batch_enqueue may be queued right
  * behind the gm_map_batch_enqueue whose gm_hits it reads - and after a failing call the rest of the batch's queue is skipped.

@@ -60,7 +60,7 @@ def main():
 
     sam_bytes = 0
     for run, args in runs:
-        for f in [out + ext for ext in (".sam", ".sgr", ".gmp")] + shard_files():     # fresh output files each time (overwriting 8 GB of page cache is a different test)
+        for f in [out + ext for ext in (".sam", ".bam", ".sgr", ".gmp")] + shard_files():     # fresh output files each time (overwriting 8 GB of page cache is a different test)
             if os.path.exists(f):
                 os.remove(f)
         t0 = time.time()
@@ -74,6 +74,8 @@ def main():
         print("\n".join(l for l in err[-3000:].splitlines() if not l.startswith("[gm_")))
         print("track files:", ", ".join(f"{ext} {os.path.getsize(out + ext)} bytes" for ext in (".sgr", ".gmp") if os.path.exists(out + ext)))
         sam_bytes = sum(os.path.getsize(f) for f in ([out + ".sam"] if os.path.exists(out + ".sam") else []) + shard_files())
+        if os.path.exists(out + ".bam"):                          # --sam_format=bam
+            print("BAM bytes", os.path.getsize(out + ".bam"))
     print("SAM bytes", sam_bytes, "FASTQ bytes", os.path.getsize(fq))
 
 
