@@ -34,7 +34,8 @@ class gm_track_text_stats(C.Structure):
 
 class gm_sam_sort_stats(C.Structure):
     _fields_ = [("rows", u64), ("text_bytes", u64), ("pieces", u64), ("piece_bytes", u64), ("add_s", C.c_double), ("sort_s", C.c_double),
-                ("gather_ms", C.c_double), ("gather_bytes", u64), ("download_s", C.c_double)]
+                ("gather_ms", C.c_double), ("gather_bytes", u64), ("download_s", C.c_double), ("bai_ms", C.c_double), ("bai_bytes", u64),
+                ("bai_chunks", u64)]
 
 
 class gm_params(C.Structure):
@@ -131,7 +132,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_sam_sorter_create", "gm_sam_sorter_destroy", "gm_output_batch_sorted", "gm_output_batch_sorted_resident", "gm_sam_sorter_finish",
            "gm_sam_sorter_read", "gm_sam_sorter_stats", "gm_sam_sorter_add_rows",
            "gm_bam_header", "gm_bgzf_compress", "gm_bgzf_eof", "gm_output_batch_bam", "gm_output_batch_bam_resident", "gm_sam_sorter_set_rows",
-           "gm_sam_sorter_read_bgzf", "gm_batch_bam_times"]
+           "gm_sam_sorter_read_bgzf", "gm_batch_bam_times", "gm_sam_sorter_index_begin", "gm_sam_sorter_bai"]
 
 
 def library_path():
@@ -241,6 +242,8 @@ def load_library():
     L.gm_sam_sorter_set_rows.argtypes = [C.c_void_p, C.c_int]
     L.gm_batch_bam_times.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.gm_sam_sorter_read_bgzf.argtypes = [C.c_void_p, C.c_int, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
+    L.gm_sam_sorter_index_begin.argtypes = [C.c_void_p, u64]
+    L.gm_sam_sorter_bai.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
     _LIB = L
     return L
 
@@ -903,6 +906,28 @@ class SamSorter:
             raise e
         _chk(rc)
         return buf[:got.value].tobytes()
+
+    def index_begin(self, file_offset):
+        """gm_sam_sorter_index_begin: after finish() and before the first read_bgzf(), on rows="bam".  file_offset: where the first block
+        read_bgzf() returns will lie in the file (the bytes of the compressed header)"""
+        _chk(lib().gm_sam_sorter_index_begin(self.h, int(file_offset)))
+
+    def bai(self, cap=None, stream=None):
+        """gm_sam_sorter_bai: the .bai of the file whose blocks read_bgzf() returned, once all of them have been read.  cap None: asked
+        for once and read with the size it needs; a cap that is too small: GnumapError with code GM_E_CAPACITY and .needed = the size"""
+        want = 1 << 16 if cap is None else int(cap)
+        for _ in range(2):
+            buf = np.zeros(max(want, 1), np.uint8); got = u64()
+            rc = lib().gm_sam_sorter_bai(self.h, buf.ctypes.data, want, C.byref(got), stream)
+            if rc != GM_E_CAPACITY:
+                _chk(rc)
+                return buf[:got.value].tobytes()
+            if cap is not None:
+                break
+            want = int(got.value)
+        e = GnumapError(rc, lib().gm_last_error().decode())
+        e.needed = int(got.value); e.buffer = buf
+        raise e
 
     def text(self, cap=1 << 20):
         """every slab that is left, joined"""

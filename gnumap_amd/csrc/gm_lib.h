@@ -2,6 +2,7 @@
 // device / page-locked buffers, and the index itself.  Not part of the public ABI.
 #pragma once
 #include "gm_host.h"
+#include <functional>
 #include <map>
 #include <mutex>
 
@@ -108,3 +109,18 @@ uint64_t gm_bgzf_bound(uint64_t n);                          // the most bytes t
 uint64_t gm_bgzf_room(uint64_t cap);                         // the most input bytes whose blocks are sure to fit in cap
 // d_in[0, n) in HBM -> z.out[0, *total); synchronises the stream.  level 0 stored, 1 Huffman
 int gm_bgzf_device(const void* d_in, uint64_t n, int level, GmBgzfBufs& z, uint64_t* total, void* stream);
+
+// gm_bai.hip.  The per-row table of a sorted BAM's index, one entry per row of the sorted order: the virtual offsets of the record's
+// first byte and of the byte behind it, its reference (~0: none), its position, and bin | last 16 kbp window << 16 | unmapped << 31.
+// err[0 .. 3]: the first row that is no whole record / names no reference of the index / ends beyond 2^29 / breaks the order (~0: none)
+struct GmBaiRows {
+    unsigned long long* vbeg; unsigned long long* vend;
+    uint32_t* ref; int32_t* pos; uint32_t* pk; uint32_t* err;
+};
+using GmBaiAlloc = std::function<int(void** p, size_t bytes, const char* what)>;      // the sorter's ss_alloc
+uint64_t gm_bai_blocks(uint64_t bytes);                      // the BGZF blocks of a slab of that many bytes
+// rows [r0, r1) of the sorted order lie in slab[0, bytes), compressed into nb blocks at offs[] (nb + 1 entries) from file_off: their entries
+int gmk_bai_rows(const void* slab, const uint64_t* soff, uint64_t r0, uint64_t r1, uint64_t bytes, const uint64_t* offs, uint32_t nb, uint64_t file_off, uint32_t n_ref,
+                 const GmBaiRows& t, void* stream);
+// the finished file in HBM (*out, the caller's to hipFree); GM_E_ARG / GM_E_UNSUPPORTED for what err[] holds.  Synchronises the stream
+int gm_bai_build(const gm_index* ix, const GmBaiRows& t, uint64_t n_rows, const GmBaiAlloc& alloc, void** out, uint64_t* out_bytes, uint64_t* n_chunks, void* stream);

@@ -13,6 +13,7 @@
 //                 once, the row that owns a lane's bytes is found by a binary search there, the source is read with one unaligned
 //                 16-byte load and stored with one aligned 16-byte store; only the 16 bytes across a row boundary are put together
 //                 byte by byte
+// With BAM rows, gm_sam_sorter_index_begin / gm_sam_sorter_bai (below) build the .bai of the file the slabs make: kernels in gm_bai.hip
 #include "gm_lib.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -163,6 +164,7 @@ uint32_t bits_for(uint64_t v) { uint32_t b = 0; while (v >> b && b < 64) ++b; re
 
 struct gm_sam_sorter {
     gm_index* ix = nullptr;
+    int device = -1;                                    // ix->device, kept: gm_sam_sorter_destroy may run after the index was closed
     std::mutex mu;
     size_t piece_bytes = (size_t)1 << 30;
     std::vector<char*> pieces; size_t used = 0;         // used: bytes of the last piece that hold rows
@@ -175,6 +177,14 @@ struct gm_sam_sorter {
     uint64_t n_rows = 0, text_bytes = 0, next_row = 0, next_off = 0;
     DevBuf bound, soff, splace, d_pieces, slab, spans;
     hipEvent_t ev[2] = { nullptr, nullptr };
+    // gm_sam_sorter_index_begin: the per-row table of the .bai, filled slab by slab as gm_sam_sorter_read_bgzf hands the rows out
+    bool bai_on = false;
+    int bai_level = -1;                                 // the level of the reads so far (-1: none yet)
+    uint64_t bai_off = 0;                               // where the next block read_bgzf returns will lie in the file
+    void* bai_tab = nullptr;
+    GmBaiRows bai{};
+    void* bai_file = nullptr;                           // the finished index in HBM (gm_sam_sorter_bai builds it once)
+    hipEvent_t bai_ev[2] = { nullptr, nullptr };
     gm_sam_sort_stats st{};
     uint64_t held() const { return (uint64_t)pieces.size() * piece_bytes + table_bytes; }
 };
@@ -201,7 +211,7 @@ extern "C" int gm_sam_sorter_create(gm_index* ix, gm_sam_sorter** out) {
     if (ix->host_only) { gm_set_error("gm_sam_sorter_create: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
     HIPCHK(hipSetDevice(ix->device));
     std::unique_ptr<gm_sam_sorter> s(new gm_sam_sorter());
-    s->ix = ix;
+    s->ix = ix; s->device = ix->device;
     const long long want = gm_opt_ll("GM_SORT_PIECE", 1ll << 30);
     s->piece_bytes = (size_t)std::min<long long>(std::max<long long>(want, 64 << 10), 0xFFFF0000ll) & ~(size_t)15;    // a row's offset in its piece fits 32 bits
     if (s->bound.ensure(32)) return GM_E_NOMEM;
@@ -213,12 +223,15 @@ extern "C" int gm_sam_sorter_create(gm_index* ix, gm_sam_sorter** out) {
 
 extern "C" void gm_sam_sorter_destroy(gm_sam_sorter* s) {
     if (!s) return;
-    (void)hipSetDevice(s->ix->device);
+    (void)hipSetDevice(s->device);                  // not through s->ix: a sorter may outlive its index (one a garbage collector frees late), and a failing call here is what the next hipGetLastError of the thread reports
     for (char* p : s->pieces) (void)hipFree(p);
     for (auto& b : s->blocks) if (b.second.tab) (void)hipFree(b.second.tab);
     for (DevBuf* d : { &s->bound, &s->soff, &s->splace, &s->d_pieces, &s->slab, &s->spans }) d->release();
     s->bz.release();
     for (auto e : s->ev) if (e) (void)hipEventDestroy(e);
+    for (auto e : s->bai_ev) if (e) (void)hipEventDestroy(e);
+    if (s->bai_tab) (void)hipFree(s->bai_tab);
+    if (s->bai_file) (void)hipFree(s->bai_file);
     delete s;
 }
 
@@ -466,6 +479,7 @@ extern "C" int gm_sam_sorter_read(gm_sam_sorter* s, char* text, uint64_t cap, ui
     if (!s || !n_out) return GM_E_ARG;
     *n_out = 0;
     std::lock_guard<std::mutex> lk(s->mu);
+    if (s->bai_on) { gm_set_error("gm_sam_sorter_read: after gm_sam_sorter_index_begin the rows leave through gm_sam_sorter_read_bgzf"); return GM_E_ARG; }
     if (!text && cap && s->finished && s->next_row < s->n_rows) { gm_set_error("gm_sam_sorter_read: text is NULL"); return GM_E_ARG; }
     hipStream_t st = S_(stream);
     uint64_t bytes = 0, r1 = 0, off1 = 0;
@@ -492,6 +506,10 @@ extern "C" int gm_sam_sorter_read_bgzf(gm_sam_sorter* s, int level, void* out, u
     if (level != 0 && level != 1) { gm_set_error("gm_sam_sorter_read_bgzf: the level is 0 (stored) or 1 (Huffman), not " + std::to_string(level)); return GM_E_ARG; }
     std::lock_guard<std::mutex> lk(s->mu);
     if (!out && cap && s->finished && s->next_row < s->n_rows) { gm_set_error("gm_sam_sorter_read_bgzf: out is NULL"); return GM_E_ARG; }
+    if (s->bai_on && s->bai_level >= 0 && level != s->bai_level) {
+        gm_set_error("gm_sam_sorter_read_bgzf: level " + std::to_string(level) + " after reads at level " + std::to_string(s->bai_level) + ": one indexed file, one level");
+        return GM_E_ARG;
+    }
     hipStream_t st = S_(stream);
     uint64_t bytes = 0, r1 = 0, off1 = 0;
     const int rc = ss_gather_next(s, "gm_sam_sorter_read_bgzf", gm_bgzf_room(cap), &bytes, &r1, &off1, st);
@@ -504,12 +522,89 @@ extern "C" int gm_sam_sorter_read_bgzf(gm_sam_sorter* s, int level, void* out, u
     uint64_t total = 0;
     if (const int r = gm_bgzf_device(s->slab.p, bytes, level, s->bz, &total, stream)) return r;
     if (total > cap) { gm_set_error("gm_sam_sorter_read_bgzf: the blocks outgrew their worst case"); return GM_E_HIP; }
+    if (s->bai_on) {                                 // the slab and the scan of its blocks' sizes are still in place: where its rows lie in the file
+        HIPCHK(hipEventRecord(s->bai_ev[0], st));
+        KCHK(gmk_bai_rows(s->slab.p, s->soff.as<uint64_t>(), s->next_row, r1, bytes, s->bz.offs.as<uint64_t>(), (uint32_t)gm_bai_blocks(bytes), s->bai_off,
+                          (uint32_t)s->ix->h.contigs.size(), s->bai, stream));
+        HIPCHK(hipEventRecord(s->bai_ev[1], st));
+    }
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipMemcpyAsync(out, s->bz.out.p, (size_t)total, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     s->st.download_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (s->bai_on) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, s->bai_ev[0], s->bai_ev[1]));
+        s->st.bai_ms += ms;
+        s->bai_off += total; s->bai_level = level;
+    }
     if (const int r = ss_consumed(s, bytes, r1, off1)) return r;
     *n_out = total;
+    return GM_OK;
+}
+
+// ---- the .bai beside a sorted BAM (kernels: gm_bai.hip) ----
+extern "C" int gm_sam_sorter_index_begin(gm_sam_sorter* s, uint64_t file_offset) {
+    if (!s) return GM_E_ARG;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->failed) { gm_set_error(s->fail_text); return s->failed; }
+    if (s->rows != GM_ROWS_BAM) { gm_set_error("gm_sam_sorter_index_begin: the sorter holds SAM rows as text, a .bai indexes BAM records (gm_sam_sorter_set_rows)"); return GM_E_ARG; }
+    if (!s->finished) { gm_set_error("gm_sam_sorter_index_begin: call gm_sam_sorter_finish first"); return GM_E_ARG; }
+    if (s->bai_on) { gm_set_error("gm_sam_sorter_index_begin: called twice"); return GM_E_ARG; }
+    if (s->next_row || s->next_off) { gm_set_error("gm_sam_sorter_index_begin: rows have been read already, their places in the file are not known"); return GM_E_ARG; }
+    if (file_offset >> 47) { gm_set_error("gm_sam_sorter_index_begin: a file offset of 2^47 or more does not fit a virtual offset"); return GM_E_ARG; }
+    HIPCHK(hipSetDevice(s->ix->device));
+    const size_t n = (size_t)s->n_rows, bytes = n * 28 + 16 + 64;
+    if (const int rc = ss_alloc(s, &s->bai_tab, bytes, "the index's row table")) return rc;
+    char* p = (char*)s->bai_tab;
+    s->bai.vbeg = (unsigned long long*)p; p += n * 8;
+    s->bai.vend = (unsigned long long*)p; p += n * 8;
+    s->bai.ref = (uint32_t*)p; p += n * 4;
+    s->bai.pos = (int32_t*)p; p += n * 4;
+    s->bai.pk = (uint32_t*)p; p += n * 4;
+    s->bai.err = (uint32_t*)p;
+    hipError_t e = hipMemset(s->bai.err, 0xFF, 16);
+    for (auto& ev : s->bai_ev) if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e != hipSuccess) {
+        for (auto& ev : s->bai_ev) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+        (void)hipFree(s->bai_tab); s->bai_tab = nullptr;
+        gm_set_error(std::string("gm_sam_sorter_index_begin: ") + hipGetErrorString(e)); return GM_E_HIP;
+    }
+    s->table_bytes += bytes;
+    s->bai_on = true; s->bai_off = file_offset; s->bai_level = -1;
+    return GM_OK;
+}
+
+extern "C" int gm_sam_sorter_bai(gm_sam_sorter* s, void* out, uint64_t cap, uint64_t* n_out, void* stream) {
+    if (!s || !n_out) return GM_E_ARG;
+    *n_out = 0;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->failed) { gm_set_error(s->fail_text); return s->failed; }
+    if (!s->bai_on) { gm_set_error("gm_sam_sorter_bai: call gm_sam_sorter_index_begin before the first gm_sam_sorter_read_bgzf"); return GM_E_ARG; }
+    if (s->next_row < s->n_rows) {
+        gm_set_error("gm_sam_sorter_bai: " + std::to_string(s->n_rows - s->next_row) + " of " + std::to_string(s->n_rows) + " rows are still unread: their places in the file are not known");
+        return GM_E_ARG;
+    }
+    HIPCHK(hipSetDevice(s->ix->device));
+    hipStream_t st = S_(stream);
+    if (!s->bai_file) {
+        uint64_t bytes = 0, chunks = 0;
+        HIPCHK(hipEventRecord(s->bai_ev[0], st));
+        const int rc = gm_bai_build(s->ix, s->bai, s->n_rows, [s](void** p, size_t b, const char* what) { return ss_alloc(s, p, b, what); }, &s->bai_file, &bytes, &chunks, stream);
+        if (rc != GM_OK) { (void)hipStreamSynchronize(st); return rc; }
+        float ms = 0;
+        HIPCHK(hipEventRecord(s->bai_ev[1], st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&ms, s->bai_ev[0], s->bai_ev[1]));
+        s->st.bai_ms += ms; s->st.bai_bytes = bytes; s->st.bai_chunks = chunks;
+    }
+    *n_out = s->st.bai_bytes;
+    if (s->st.bai_bytes > cap || !out) {
+        gm_set_error("gm_sam_sorter_bai: the index takes " + std::to_string(s->st.bai_bytes) + " bytes, the buffer holds " + std::to_string(cap));
+        return GM_E_CAPACITY;
+    }
+    HIPCHK(hipMemcpyAsync(out, s->bai_file, (size_t)s->st.bai_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return GM_OK;
 }
 

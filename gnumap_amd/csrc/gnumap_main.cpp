@@ -67,6 +67,7 @@ struct Options {
     bool bam = false;               // --sam_format=bam: <out>.bam instead of <out>.sam, records and BGZF written on the GPU (gm_output_batch_bam; implies --sam_text=device)
     int bam_level = 1;              // --bam_level=0|1: stored blocks, or Huffman-coded ones
     bool bam_level_set = false;     // (refused without --sam_format=bam)
+    bool bam_index = false;         // --bam_index: <out>.bam.bai beside a sorted <out>.bam, built on the GPU from what the sorter holds (gm_sam_sorter_bai)
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
 
@@ -123,7 +124,10 @@ struct Options {
             "      --sam_format=sam|bam     sam (default): <out>.sam.  bam: <out>.bam and no <out>.sam - the records and their BGZF blocks are\n"
             "                               written on the GPU; with --sam_sort=coordinate the file is a sorted BAM.  Implies --sam_text=device\n"
             "                               (not with --sam_text=host or --sam_shards above 1)\n"
-            "      --bam_level=0|1          with --sam_format=bam: 0 = stored BGZF blocks, 1 (default) = Huffman-coded blocks (no LZ77 matches)\n");
+            "      --bam_level=0|1          with --sam_format=bam: 0 = stored BGZF blocks, 1 (default) = Huffman-coded blocks (no LZ77 matches)\n"
+            "      --bam_index              with --sam_format=bam --sam_sort=coordinate: also write <out>.bam.bai (SAMv1 section 5.2), built on the\n"
+            "                               GPU from the sorted records and their BGZF offsets; <out>.bam is written exactly as without the flag.\n"
+            "                               Records must end at or below 2^29 (there is no .csi)\n");
     exit(rc);
 }
 
@@ -199,6 +203,7 @@ static void parse_args(int argc, char** argv, Options& o) {
                 if (strcmp(s + 10, "0") && strcmp(s + 10, "1")) { fprintf(stderr, "Error: --bam_level takes 0 or 1, not: %s\n", s + 10); exit(1); }
                 o.bam_level = s[10] - '0'; o.bam_level_set = true;
             }
+            else if (!strcmp(s, "bam_index")) o.bam_index = true;
             else if (starts(s, "sam_shards=")) {
                 char* end = nullptr;
                 const long k = strtol(s + 11, &end, 10);
@@ -260,6 +265,8 @@ static void parse_args(int argc, char** argv, Options& o) {
         o.sam_text_device = true;
     }
     if (o.bam_level_set && !o.bam) { fprintf(stderr, "Error: --bam_level sets the compression of --sam_format=bam: give --sam_format=bam with --bam_level\n"); exit(1); }
+    if (o.bam_index && !o.bam) { fprintf(stderr, "Error: --bam_index writes the index of a sorted <out>.bam: give --sam_format=bam (and --sam_sort=coordinate) with --bam_index\n"); exit(1); }
+    if (o.bam_index && !o.sam_sort) { fprintf(stderr, "Error: --bam_index indexes a coordinate-sorted file: give --sam_sort=coordinate with --bam_index\n"); exit(1); }
     if (o.bam) {                                             // refused before a device is opened or a file is written
         if (o.sam_text_host_set) { fprintf(stderr, "Error: --sam_format=bam writes the records on the GPU: it cannot be combined with --sam_text=host\n"); exit(1); }
         if (o.sam_shards > 1) { fprintf(stderr, "Error: --sam_format=bam writes one <out>.bam: it cannot be combined with --sam_shards above 1\n"); exit(1); }
@@ -974,6 +981,7 @@ struct Run {
     TextPool text_pool, stage_pool;
     // one <out>.sam, or --sam_shards=K files <out>.<k>.sam: every shard has its own descriptor and offset counter (no two share an inode)
     std::vector<int> ofds; std::vector<uint64_t> file_offs;
+    std::string bai;                // --bam_index: the finished <out>.bam.bai, as gm_sam_sorter_bai returned it
     std::atomic<int> failed{ 0 };
     double t_index = 0, t_scan = 0, t_fmt = 0, t_write = 0;     // t_scan: the scanner thread's; t_fmt, t_write: summed under their locks
     std::mutex fmt_mu, tw_mu;                       // (t_write is summed by several writers with --sam_shards)
@@ -1291,6 +1299,7 @@ static int drain_sorter(Run& R) {
     slab[0].ensure(slab_cap); slab[1].ensure(slab_cap);
     const int ofd = R.ofds[0];
     std::thread wr; std::atomic<int> wr_bad{ 0 };
+    if (R.o.bam_index && gm_sam_sorter_index_begin(R.sorter, R.file_offs[0]) != GM_OK) { fprintf(stderr, "ERROR: gm_sam_sorter_index_begin: %s\n", gm_last_error()); return 1; }
     auto w0 = Clock::now();
     size_t cap = slab_cap;                                           // what gm_sam_sorter_read may fill of either buffer
     for (int k = 0;;) {                                              // k: the buffer the next slab goes into, while the other one is written
@@ -1314,6 +1323,17 @@ static int drain_sorter(Run& R) {
     }
     if (wr.joinable()) wr.join();
     if (wr_bad) { fprintf(stderr, "ERROR: write failed\n"); R.failed = 1; }
+    if (R.o.bam_index && !R.failed) {                                // every row has its place in the file: the index, grown once to its size
+        R.bai.resize(1 << 16);
+        for (;;) {
+            uint64_t got = 0;
+            const int rc = gm_sam_sorter_bai(R.sorter, &R.bai[0], R.bai.size(), &got, stream);
+            if (rc == GM_E_CAPACITY && got > R.bai.size()) { R.bai.resize((size_t)got); continue; }
+            if (rc != GM_OK) { fprintf(stderr, "ERROR: gm_sam_sorter_bai: %s\n", gm_last_error()); R.failed = 1; break; }
+            R.bai.resize((size_t)got);
+            break;
+        }
+    }
     R.t_write += secs_since(w0);
     return 0;
 }
@@ -1323,6 +1343,8 @@ static void report_sorter(const Run& R) {
     if (gm_sam_sorter_stats(R.sorter, &ss) != GM_OK) return;
     fprintf(stderr, "sam sort on the device: %lu rows, %lu text bytes in %lu pieces of %lu bytes; seconds: arena appends %.3f, sort %.3f, gather %.3f, download %.3f\n",
             (unsigned long)ss.rows, (unsigned long)ss.text_bytes, (unsigned long)ss.pieces, (unsigned long)ss.piece_bytes, ss.add_s, ss.sort_s, ss.gather_ms / 1e3, ss.download_s);
+    if (R.o.bam_index)
+        fprintf(stderr, "bam index on the device: %lu bytes, %lu chunks, %.3f ms in kernels\n", (unsigned long)ss.bai_bytes, (unsigned long)ss.bai_chunks, ss.bai_ms);
 }
 
 // coverage: all-reduce over the GPUs, then PrintFinalSGR / PrintFinalBisulfite / PrintFinalSNP, and the .vcf beside a .gmp
@@ -1384,7 +1406,8 @@ static void report(const Run& R, double t_pipe, double t_cov, double secs) {
 int main(int argc, char** argv) {
     Run R;
     parse_args(argc, argv, R.o);
-    for (int i = 0; i < argc; ++i) { R.cl += argv[i]; R.cl += " "; }
+    // (--bam_index stays out of the @PG line: <out>.bam is byte for byte the file of the run without it)
+    for (int i = 0; i < argc; ++i) if (strcmp(argv[i], "--bam_index")) { R.cl += argv[i]; R.cl += " "; }
     R.t0 = Clock::now();
     if (detect_read_format(R) || open_devices(R) || open_outputs(R)) return 1;
     R.t_pipe0 = Clock::now();
@@ -1401,6 +1424,13 @@ int main(int argc, char** argv) {
         (void)gm_bgzf_eof(eof);
         if (!pwrite_all(R.ofds[0], eof, sizeof eof, R.file_offs[0])) { fprintf(stderr, "ERROR: write failed\n"); return 1; }
         R.file_offs[0] += sizeof eof;
+    }
+    if (R.o.bam_index && !R.failed) {                  // <out>.bam.bai, behind the end marker of <out>.bam
+        const std::string fn = R.o.output + ".bam.bai";
+        const int fd = ::open(fn.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        const bool ok = fd >= 0 && write_all(fd, R.bai.data(), R.bai.size());
+        if (fd >= 0) ::close(fd);
+        if (!ok) { fprintf(stderr, "ERROR: cannot write %s\n", fn.c_str()); return 1; }
     }
     for (int fd : R.ofds) ::close(fd);
     if (R.failed) return 1;

@@ -357,6 +357,8 @@ typedef struct {
     double gather_ms;               /* device time of k_ss_spans + k_ss_gather over all reads (HIP events) */
     uint64_t gather_bytes;          /* bytes the gather kernel wrote */
     double download_s;              /* host seconds in the device-to-host copies of the reads */
+    double bai_ms;                  /* device time of the .bai's kernels: k_bai_rows per slab, and the build (HIP events around it) */
+    uint64_t bai_bytes, bai_chunks; /* the .bai: its bytes, the chunks of its bins (the pseudo-bins' aside); 0 before gm_sam_sorter_bai */
 } gm_sam_sort_stats;
 int gm_sam_sorter_create(gm_index*, gm_sam_sorter** out);
 void gm_sam_sorter_destroy(gm_sam_sorter*);
@@ -415,6 +417,28 @@ int gm_sam_sorter_set_rows(gm_sam_sorter*, int rows);
  * cap (reserved for the worst case, stored: the rows' bytes + 31 per started 65280), as whole BGZF blocks.  *n_out = 0: done.
  * GM_E_CAPACITY when the next row alone needs more: *n_out = the cap it needs, nothing is consumed. */
 int gm_sam_sorter_read_bgzf(gm_sam_sorter*, int level, void* out, uint64_t cap, uint64_t* n_out, void* hip_stream);
+/* ---- the .bai (SAMv1 section 5.2) of a sorted BAM, built on the device from what the sorter holds (gm_bai.hip) ----
+ * gm_sam_sorter_index_begin, after a successful finish and before the first read, on a sorter of GM_ROWS_BAM: from then on
+ * gm_sam_sorter_read_bgzf notes, in HBM and 28 bytes per row, where the records of every slab it hands out lie in the file - it takes the
+ * blocks it returns to be written back to back from file_offset (the bytes of the compressed header in front of them), at one level
+ * (GM_E_ARG for another), and notes nothing on a read that fails; gm_sam_sorter_read is refused (GM_E_ARG).  GM_E_ARG: text rows, not
+ * finished, a row already read, called twice.  GM_E_NOMEM as the sorter reports its own.
+ * gm_sam_sorter_bai, once every row is read (GM_E_ARG before, and without index_begin): the finished file.  *n_out = its bytes;
+ * GM_E_CAPACITY when that exceeds cap, nothing is written.  It may be called again.  The bytes are a function of the records, the
+ * level and file_offset alone.  The rules where the specification leaves a choice:
+ *   a record starts at the virtual offset (coffset << 16 | uoffset) of its block_size and ends at that of the byte behind it - (the next
+ *   block, 0) when it ends on a payload's end, (whatever follows the last block, 0) for the last record; refID, pos, flag and the CIGAR
+ *   are read from the record: beg = pos, end = pos + the CIGAR's reference length (1 when that is 0), bin = reg2bin(beg, end);
+ *   a chunk = a maximal run of consecutive records of one (refID, bin); two chunks of a bin are merged when the later one starts in the
+ *   compressed block in which the earlier one ends, or before; bins ascend; pseudo-bin 37450 last for every reference with records
+ *   (first start / last end; records with flag 0x4 clear / set); linear index: n_intv = ((max end - 1) >> 14) + 1, entry w = the smallest
+ *   start of the records that overlap window w, an empty window takes the entry before it, leading empty windows 0; n_no_coor = the
+ *   records with refID < 0.
+ * GM_E_UNSUPPORTED: a record ends beyond 2^29 (the message names reference, position and limit).  GM_E_ARG: the records do not ascend in
+ * (refID as unsigned, pos) - keys of gm_sam_sorter_add_rows that disagree with the records -, a row is no whole record, or names a
+ * reference the index does not have. */
+int gm_sam_sorter_index_begin(gm_sam_sorter*, uint64_t file_offset);
+int gm_sam_sorter_bai(gm_sam_sorter*, void* out, uint64_t cap, uint64_t* n_out, void* hip_stream);
 
 /* enqueue / wait forms: the call is queued on the batch's own service thread and runs there exactly as the synchronous form would;
  * the caller goes on (with another batch).  Calls queued on one batch run in order - gm_output_batch_enqueue may be queued right

@@ -20,6 +20,7 @@ def main():
     ap.add_argument("--args", default="-a 0.9")
     ap.add_argument("--dir", default="/tmp/gm_cli")
     ap.add_argument("--sweep", default="", help="further argument sets for the timed run, separated by ';' (each one more run on the same files)")
+    ap.add_argument("--bam_index", action="store_true", help="two more timed runs: --sam_format=bam --sam_sort=coordinate, then the same with --bam_index (<out>.bam.bai)")
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     fa = os.path.join(a.dir, "g%g.fa" % a.mbp); fq = os.path.join(a.dir, "r%d.fq" % a.reads)
@@ -55,12 +56,15 @@ def main():
     out = os.path.join(a.dir, "out")
     env = dict(os.environ)
     runs = [("index+map", a.args), ("map", a.args)] + [("map " + x.strip(), a.args + " " + x.strip()) for x in a.sweep.split(";") if x.strip()]
+    if a.bam_index:
+        sorted_bam = "--sam_format=bam --sam_sort=coordinate"
+        runs += [("map " + x, a.args + " " + x) for x in (sorted_bam, sorted_bam + " --bam_index")]
     def shard_files():                                           # <out>.<k>.sam of a --sam_shards=K run
         return [f for f in glob.glob(glob.escape(out) + ".*.sam") if f[len(out) + 1:-4].isdigit()]
 
     sam_bytes = 0
     for run, args in runs:
-        for f in [out + ext for ext in (".sam", ".bam", ".sgr", ".gmp")] + shard_files():     # fresh output files each time (overwriting 8 GB of page cache is a different test)
+        for f in [out + ext for ext in (".sam", ".bam", ".bam.bai", ".sgr", ".gmp")] + shard_files():     # fresh output files each time (overwriting 8 GB of page cache is a different test)
             if os.path.exists(f):
                 os.remove(f)
         t0 = time.time()
@@ -76,6 +80,8 @@ def main():
         sam_bytes = sum(os.path.getsize(f) for f in ([out + ".sam"] if os.path.exists(out + ".sam") else []) + shard_files())
         if os.path.exists(out + ".bam"):                          # --sam_format=bam
             print("BAM bytes", os.path.getsize(out + ".bam"))
+        if os.path.exists(out + ".bam.bai"):                      # --bam_index
+            print("BAI bytes", os.path.getsize(out + ".bam.bai"))
     print("SAM bytes", sam_bytes, "FASTQ bytes", os.path.getsize(fq))
 
 
