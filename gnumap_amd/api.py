@@ -12,6 +12,7 @@ GM_READ_OK, GM_READ_TOO_MANY, GM_READ_NONE, GM_READ_TOO_SHORT, GM_READ_TOO_POOR 
 GM_E_CAPACITY = -5
 GM_E_BATCH_TOO_LARGE = -9
 GM_ROWS_TEXT, GM_ROWS_BAM = 0, 1
+GM_BGZF_LZ77 = 0x100                    # ORed into a BGZF level of 1: LZ77 matches under the Huffman code
 
 u8p = C.POINTER(C.c_uint8)
 u64 = C.c_uint64
@@ -427,14 +428,15 @@ class Index:
         _chk(lib().gm_bam_header(self.h, text, len(text), buf.ctypes.data, int(need.value), C.byref(need)))
         return buf[:need.value].tobytes()
 
-    def bgzf_compress(self, data, level=1, cap=None, stream=None):
-        """gm_bgzf_compress: whole BGZF blocks around `data`, deflated on the device.  cap: the output buffer's size (None: the worst case);
+    def bgzf_compress(self, data, level=1, cap=None, stream=None, lz77=False):
+        """gm_bgzf_compress: whole BGZF blocks around `data`, deflated on the device.  lz77: level | GM_BGZF_LZ77, LZ77 matches under the
+        Huffman code of level 1.  cap: the output buffer's size (None: the worst case);
         GnumapError with code GM_E_CAPACITY and .needed = the size when the blocks exceed it"""
         src = np.frombuffer(bytes(data) + b"\0", np.uint8)
         n = len(src) - 1
         cap = n + 31 * ((n + 65279) // 65280) if cap is None else int(cap)
         out = np.zeros(cap + 64, np.uint8); got = u64()
-        rc = lib().gm_bgzf_compress(self.h, src.ctypes.data, n, int(level), out.ctypes.data, cap, C.byref(got), stream)
+        rc = lib().gm_bgzf_compress(self.h, src.ctypes.data, n, _bgzf_level(level, lz77), out.ctypes.data, cap, C.byref(got), stream)
         if rc == GM_E_CAPACITY:
             e = GnumapError(rc, lib().gm_last_error().decode())
             e.needed = int(got.value); e.buffer = out
@@ -802,19 +804,24 @@ class Batch:
         _chk(lib().gm_batch_bam_times(self.h, ms.ctypes.data, by.ctypes.data))
         return dict(rows_ms=float(ms[0]), bgzf_ms=float(ms[1]), raw_bytes=int(by[0]), bgzf_in=int(by[1]), bgzf_out=int(by[2]))
 
-    def output_bam(self, params, res, names, qual_tails=None, level=1, stream=None, bam_cap=None):
+    def output_bam(self, params, res, names, qual_tails=None, level=1, stream=None, bam_cap=None, lz77=False):
         """gm_output_batch_bam on the result of map(): the block's BAM records as BGZF blocks (bytes).  names / qual_tails as in output_text;
+        lz77 as in Index.bgzf_compress;
         bam_cap: first capacity to try.  self.bam_raw_len / self.bam_n_recs: bytes and number of the records"""
         rt, keep = _pack_read_text([bytes(x) for x in names], None if qual_tails is None else [bytes(x) for x in qual_tails], self.n)
         out = self._output_bam(lambda bo: lib().gm_output_batch_bam(self.index.h, C.byref(params.c), self.h, C.byref(res["_reads"]), C.byref(rt), C.byref(res["_struct"]),
-                                                                    C.byref(bo), stream), level, bam_cap, res["_reads"].stride)
+                                                                    C.byref(bo), stream), _bgzf_level(level, lz77), bam_cap, res["_reads"].stride)
         del keep
         return out
 
-    def output_bam_resident(self, params, res, level=1, stream=None, bam_cap=None):
+    def output_bam_resident(self, params, res, level=1, stream=None, bam_cap=None, lz77=False):
         """gm_output_batch_bam_resident on the result of map_text()"""
         return self._output_bam(lambda bo: lib().gm_output_batch_bam_resident(self.index.h, C.byref(params.c), self.h, C.byref(res["_struct"]), C.byref(bo), stream),
-                                level, bam_cap, self.stride)
+                                _bgzf_level(level, lz77), bam_cap, self.stride)
+
+
+def _bgzf_level(level, lz77):
+    return int(level) | (GM_BGZF_LZ77 if lz77 else 0)
 
 
 def bgzf_eof():
@@ -895,11 +902,12 @@ class SamSorter:
         _chk(rc)
         return buf[:got.value].tobytes()
 
-    def read_bgzf(self, cap, level=1, stream=None):
-        """gm_sam_sorter_read_bgzf: the next whole rows whose BGZF form is sure to fit in cap bytes, as BGZF blocks (b"" = done).  GnumapError
+    def read_bgzf(self, cap, level=1, stream=None, lz77=False):
+        """gm_sam_sorter_read_bgzf: the next whole rows whose BGZF form is sure to fit in cap bytes, as BGZF blocks (b"" = done).  lz77 as in
+        Index.bgzf_compress.  GnumapError
         with code GM_E_CAPACITY and .needed = the cap the next row needs when that row alone is too long"""
         buf = np.zeros(max(int(cap), 1), np.uint8); got = u64()
-        rc = lib().gm_sam_sorter_read_bgzf(self.h, int(level), buf.ctypes.data, int(cap), C.byref(got), stream)
+        rc = lib().gm_sam_sorter_read_bgzf(self.h, _bgzf_level(level, lz77), buf.ctypes.data, int(cap), C.byref(got), stream)
         if rc == GM_E_CAPACITY:
             e = GnumapError(rc, lib().gm_last_error().decode())
             e.needed = int(got.value)

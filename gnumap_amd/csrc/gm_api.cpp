@@ -2003,7 +2003,7 @@ extern "C" int gm_output_batch_text_resident(gm_index* ix, const gm_params* p, g
 // gm_output_batch_text / _text_resident with the rows as BAM records inside BGZF blocks (k_bam_sizes / k_bam_rows / k_bgzf_*, gm_bam.hip)
 static int bam_out_check(const char* who, gm_bam_out* out) {
     out->len = 0; out->raw_len = 0; out->n_recs = 0;
-    if (out->level != 0 && out->level != 1) { gm_set_error(std::string(who) + ": gm_bam_out.level is 0 (stored) or 1 (Huffman), not " + std::to_string(out->level)); return GM_E_ARG; }
+    if (!gm_bgzf_level_ok(out->level)) { gm_set_error(std::string(who) + ": gm_bam_out.level: " + gm_bgzf_level_text(out->level)); return GM_E_ARG; }
     if (!out->data && out->cap) { gm_set_error(std::string(who) + ": gm_bam_out.data is NULL"); return GM_E_ARG; }
     return GM_OK;
 }

@@ -10,12 +10,15 @@
 //                 crc(A|B) = crc(A) * x^(8|B|) ^ crc(B), then a stored block (level 0) or one dynamic-Huffman block over literals
 //                 only (level 1) - histogram in LDS, a length-limited code built by one lane, all lanes emit through a prefix sum of
 //                 their bit counts - into the payload's worst-case slot
+//   k_bgzf_deflate_lz  level 1 | GM_BGZF_LZ77: the same payload, slot and size, one dynamic-Huffman block over literals and LZ77 matches -
+//                 a persistent grid with a token area per workgroup; what it finds is described above the kernel and in DESIGN.md
 //   k_bgzf_compact  after the scan of the blocks' sizes: the slots side by side, so that one contiguous run crosses the link
 //
 // A record is pinned to the SAM row k_out_text_rows prints for it.  One difference is the format's own: l_read_name is one byte, so
 // read_name holds the first 254 bytes of the name (the SAM row keeps up to 1023).
-// The output bytes are a function of the input bytes and the level alone: the only atomics are integer adds into the histogram and ORs
-// into words of the bit stream, whose results do not depend on the order in which they land.
+// The output bytes are a function of the input bytes and the level alone: the only atomics are integer adds into the histograms, ORs
+// into words of the bit stream and, in k_bgzf_deflate_lz, maxima of positions into the hash table - none of their results depends on the
+// order in which they land, and a barrier lies between the maxima and the lookups that read them.
 #include "gm_lib.h"
 #include <algorithm>
 #include <memory>
@@ -208,6 +211,330 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate(const uint8_t* __restrict_
     if (tid == 0) sizes[blockIdx.x] = bsize;
 }
 
+// ------------------------------------------------------------------------------------------------
+// level 1 | GM_BGZF_LZ77: one dynamic-Huffman block over literals and LZ77 matches ("BGZF with LZ77 matches")
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t LZ_HEAD = 8192;                  // entries of the hash table; it lies where the bit stream is built afterwards
+constexpr uint32_t LZ_MIN = 4, LZ_MAX = 258, LZ_WINDOW = 32768;
+constexpr uint32_t LZ_NL = 286, LZ_ND = 30;         // literal/length and distance symbols
+constexpr uint32_t LZ_FIX_BITS = 3 + 5 + 5 + 4 + 19 * 3;     // BFINAL, BTYPE, HLIT, HDIST, HCLEN, the code-length code
+constexpr uint32_t LZ_MATCH = 0x80000000u;          // a token: a literal's byte, or LZ_MATCH | (length - 3) << 16 | (distance - 1)
+
+// the four bytes at byte q of an array of words (LDS takes no unaligned word); reads the word behind q's as well
+__device__ __forceinline__ uint32_t lz_get32(const uint32_t* w, uint32_t q) { return __builtin_amdgcn_alignbyte(w[(q >> 2) + 1u], w[q >> 2], q & 3u); }
+// RFC 1951 section 3.2.5: length - 3 -> symbol - 257, distance - 1 -> symbol; *nx extra bits of value *xv
+__device__ __forceinline__ uint32_t lz_len_sym(uint32_t y, uint32_t* nx, uint32_t* xv) {
+    if (y < 8u || y == 255u) { *nx = 0; *xv = 0; return y < 8u ? y : 28u; }
+    const uint32_t n = 31u - (uint32_t)__clz((int)y);
+    *nx = n - 2u; *xv = y & ((1u << (n - 2u)) - 1u);
+    return 4u * (n - 1u) + ((y >> (n - 2u)) & 3u);
+}
+__device__ __forceinline__ uint32_t lz_dist_sym(uint32_t x, uint32_t* nx, uint32_t* xv) {
+    if (x < 4u) { *nx = 0; *xv = 0; return x; }
+    const uint32_t n = 31u - (uint32_t)__clz((int)x);
+    *nx = n - 1u; *xv = x & ((1u << (n - 1u)) - 1u);
+    return 2u * n + ((x >> (n - 1u)) & 1u);
+}
+__device__ __forceinline__ uint32_t lz_len_extra(uint32_t i) { return i < 8u || i == 28u ? 0u : (i >> 2) - 1u; }      // of length symbol 257 + i
+__device__ __forceinline__ uint32_t lz_dist_extra(uint32_t d) { return d < 4u ? 0u : (d >> 1) - 1u; }
+
+// every symbol in use finds its rank in ascending (count, symbol) order: ord[rank] = symbol.  All lanes; a barrier before ord is read
+__device__ __forceinline__ void lz_rank(const uint32_t* hist, uint32_t nsym, uint16_t* ord, uint32_t tid) {
+    for (uint32_t s = tid; s < nsym; s += 256u) {
+        const uint32_t c = hist[s];
+        if (!c) continue;
+        uint32_t rank = 0;
+        for (uint32_t q = 0; q < nsym; ++q) { const uint32_t cq = hist[q]; rank += (cq && (cq < c || (cq == c && q < s))) ? 1u : 0u; }
+        ord[rank] = (uint16_t)s;
+    }
+}
+// One lane: the code of the symbols in use, as k_bgzf_deflate builds its own - Huffman's algorithm on the sorted leaves, flatter counts
+// and again while a leaf lies deeper than 15, canonical codes kept bit-reversed - into code[] (length << 16 | code; zero beforehand).
+// One symbol in use takes the one-bit code 0.  wt, par, dep: 2 * nsym entries each
+__device__ void lz_build_code(const uint32_t* hist, uint32_t nsym, const uint16_t* ord, uint32_t* wt, uint16_t* par, uint8_t* dep, uint32_t* code) {
+    uint32_t m = 0;
+    for (uint32_t s = 0; s < nsym; ++s) m += hist[s] ? 1u : 0u;
+    if (m == 0) return;
+    if (m == 1) { code[ord[0]] = 1u << 16; return; }
+    for (uint32_t i = 0; i < m; ++i) wt[i] = hist[ord[i]];
+    for (;;) {
+        uint32_t li = 0, ni = m, nn = m;
+        while (nn < 2u * m - 1u) {
+            uint32_t pick[2];
+            for (int k = 0; k < 2; ++k) pick[k] = (li < m && (ni >= nn || wt[li] <= wt[ni])) ? li++ : ni++;
+            wt[nn] = wt[pick[0]] + wt[pick[1]];
+            par[pick[0]] = par[pick[1]] = (uint16_t)nn;
+            ++nn;
+        }
+        dep[2u * m - 2u] = 0;
+        uint32_t deepest = 0;
+        for (uint32_t i = 2u * m - 2u; i-- > 0;) {
+            const uint32_t d = (uint32_t)dep[par[i]] + 1u;
+            dep[i] = (uint8_t)(d < 255u ? d : 255u);
+            if (i < m && d > deepest) deepest = d;
+        }
+        if (deepest <= 15u) break;
+        for (uint32_t i = 0; i < m; ++i) wt[i] = (wt[i] + 1u) >> 1;
+    }
+    uint32_t cnt[16], next[16];
+    for (int k = 0; k < 16; ++k) cnt[k] = 0;
+    for (uint32_t i = 0; i < m; ++i) { ++cnt[dep[i]]; code[ord[i]] = (uint32_t)dep[i] << 16; }
+    uint32_t c = 0;
+    next[0] = 0;
+    for (int k = 1; k < 16; ++k) { c = (c + cnt[k - 1]) << 1; next[k] = c; }
+    for (uint32_t s = 0; s < nsym; ++s) {
+        const uint32_t l = code[s] >> 16;
+        if (l) code[s] = (l << 16) | (__brev(next[l]++) >> (32u - l));
+    }
+}
+
+// A persistent grid: workgroup g takes payloads g, g + gridDim.x, ... and keeps their tokens in its own tokens[g * BZ_PAYLOAD ...).
+// Per payload:
+//   1. the payload into LDS, its CRC-32 and the histogram of its bytes, as k_bgzf_deflate does
+//   2. the matches, in tiles of 256 positions, one per lane: the lane's candidate is head[hash of its 4 bytes] - the largest position of
+//      an EARLIER tile with that hash, put there with atomicMax behind a barrier, so what a lane finds does not depend on timing -,
+//      compared forward byte for byte (up to 258, never past the payload's end); a match counts from 4 bytes and within 32768.  The
+//      greedy parse of the tile - from where the last token of the tile before ended, next[p] = p + max(length, 1) - is marked by
+//      pointer doubling in 8 steps; the marked positions are the tokens: counted into the two histograms, ranked by a prefix sum over
+//      the tile and written to the workgroup's token area
+//   3. the two codes, and level 1's code over the bytes, built side by side by one lane each of waves 0, 1 and 2; the smallest of the
+//      matched form, level 1's form and the stored form is written - so a block is never larger than level 1 writes it
+//   4. every lane a contiguous run of tokens (or bytes): its bit count, a prefix sum, its codes and extra bits ORed into the stream
+__global__ void __launch_bounds__(256) k_bgzf_deflate_lz(const uint8_t* __restrict__ in, unsigned long long n, uint32_t n_blocks, uint8_t* __restrict__ slots,
+                                                         uint32_t* __restrict__ sizes, uint32_t* tokens) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+    uint8_t* const s_in = s_dyn;
+    const uint32_t* const s_in32 = reinterpret_cast<const uint32_t*>(s_dyn);
+    uint32_t* const s_out = reinterpret_cast<uint32_t*>(s_dyn + BZ_PAYLOAD);
+    uint32_t* const s_head = s_out;                  // position + 1 (0: none) by hash, while the matches are looked for
+    constexpr uint32_t NS = LZ_NL + LZ_ND + 257u;     // the symbols of the three codes: literal/length, distance, and level 1's over the bytes
+    __shared__ uint32_t s_tab[256], s_lhist[LZ_NL], s_dhist[LZ_ND], s_bhist[257], s_lcode[LZ_NL], s_dcode[LZ_ND], s_bcode[257], s_wt[2 * NS], s_wave[4], s_misc[4];
+    __shared__ uint16_t s_par[2 * NS], s_ord[NS], s_jump[256];
+    __shared__ uint8_t s_dep[2 * NS], s_mark[256];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    uint32_t* const tk = tokens + (size_t)blockIdx.x * BZ_PAYLOAD;
+    {
+        uint32_t c = tid;
+        for (int k = 0; k < 8; ++k) c = (c & 1u) ? BZ_POLY ^ (c >> 1) : c >> 1;
+        s_tab[tid] = c;
+    }
+    for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+        const unsigned long long p0 = (unsigned long long)blk * BZ_PAYLOAD;
+        const uint32_t len = (uint32_t)(n - p0 < BZ_PAYLOAD ? n - p0 : BZ_PAYLOAD);
+        const uint8_t* const src = in + p0;
+        // ---- 1. the payload into LDS; empty histograms and hash table ----
+        if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
+            const uint32_t n16 = len >> 4;
+            for (uint32_t q = tid; q < n16; q += 256u) reinterpret_cast<uint4*>(s_in)[q] = reinterpret_cast<const uint4*>(src)[q];
+            for (uint32_t i = (n16 << 4) + tid; i < len; i += 256u) s_in[i] = src[i];
+        } else
+            for (uint32_t i = tid; i < len; i += 256u) s_in[i] = src[i];
+        for (uint32_t i = tid; i < LZ_NL; i += 256u) { s_lhist[i] = i == 256u ? 1u : 0u; s_lcode[i] = 0; }
+        if (tid < LZ_ND) { s_dhist[tid] = 0; s_dcode[tid] = 0; }
+        for (uint32_t i = tid; i < 257u; i += 256u) { s_bhist[i] = i == 256u ? 1u : 0u; s_bcode[i] = 0; }
+        for (uint32_t i = tid; i < LZ_HEAD; i += 256u) s_head[i] = 0;
+        if (tid == 0) s_misc[0] = 0;
+        __syncthreads();
+        const uint32_t chunk = (len + 255u) >> 8;
+        uint32_t crc_all;
+        {
+            const uint32_t a = tid * chunk < len ? tid * chunk : len, e = a + chunk < len ? a + chunk : len;
+            uint32_t crc = 0xFFFFFFFFu;
+            for (uint32_t i = a; i < e; ++i) {
+                const uint32_t by = s_in[i];
+                crc = s_tab[(crc ^ by) & 255u] ^ (crc >> 8);
+                atomicAdd(&s_bhist[by], 1u);
+            }
+            crc ^= 0xFFFFFFFFu;
+            uint32_t part = a < e ? bz_mul(bz_xpow8(len - e), crc) : 0u;
+            for (int off = 32; off; off >>= 1) part ^= __shfl_xor(part, off);
+            if (lane == 0) s_wave[wv] = part;
+            __syncthreads();
+            crc_all = s_wave[0] ^ s_wave[1] ^ s_wave[2] ^ s_wave[3];
+            __syncthreads();
+        }
+        // ---- 2. the matches and the tokens, tile by tile ----
+        uint32_t n_tok = 0;
+        for (uint32_t tb = 0; tb < len; tb += 256u) {
+            const uint32_t start = s_misc[0];         // where the next token begins (written behind the last barrier of the tile before)
+            const uint32_t p = tb + tid;
+            const bool hashed = p + LZ_MIN <= len;
+            uint32_t h = 0, mlen = 1, dist = 0;
+            if (hashed) {
+                h = (lz_get32(s_in32, p) * 0x9E3779B1u) >> 19;
+                const uint32_t c1 = s_head[h];
+                if (p >= start && c1 && p - (c1 - 1u) <= LZ_WINDOW) {
+                    const uint32_t c = c1 - 1u, mx = len - p < LZ_MAX ? len - p : LZ_MAX;
+                    uint32_t l = 0;
+                    while (l < mx) {                  // 16 bytes a trip: the eight reads are issued together (what lies behind mx is cut off below)
+                        uint32_t x[4];
+                        for (uint32_t k = 0; k < 4u; ++k) x[k] = lz_get32(s_in32, c + l + 4u * k) ^ lz_get32(s_in32, p + l + 4u * k);
+                        if (x[0] | x[1] | x[2] | x[3]) {
+                            const uint32_t k = x[0] ? 0u : x[1] ? 1u : x[2] ? 2u : 3u, xk = x[0] ? x[0] : x[1] ? x[1] : x[2] ? x[2] : x[3];
+                            l += 4u * k + ((uint32_t)__builtin_ctz(xk) >> 3);
+                            break;
+                        }
+                        l += 16u;
+                    }
+                    if (l > mx) l = mx;
+                    if (l >= LZ_MIN) { mlen = l; dist = p - c; }
+                }
+            }
+            const bool parse = start < tb + 256u;     // (uniform) a match of the tile before may cover this one
+            if (parse) {
+                s_jump[tid] = (uint16_t)(tid + mlen < 256u ? tid + mlen : 256u);
+                s_mark[tid] = p == start ? 1 : 0;
+            }
+            __syncthreads();                          // every lane has looked its candidate up: this tile's positions into the table
+            if (hashed) atomicMax(&s_head[h], p + 1u);
+            bool tok = false;
+            if (parse) {
+                for (int k = 0; k < 8; ++k) {
+                    const uint32_t j = s_jump[tid], m = s_mark[tid], jj = j < 256u ? s_jump[j] : 256u;
+                    __syncthreads();
+                    if (m && j < 256u) s_mark[j] = 1;
+                    s_jump[tid] = (uint16_t)jj;
+                    __syncthreads();
+                }
+                tok = s_mark[tid] && p < len;
+            }
+            const unsigned long long bal = __builtin_amdgcn_ballot_w64(tok);
+            if (lane == 0) s_wave[wv] = (uint32_t)__popcll(bal);
+            if (tok && (tid + mlen >= 256u || p + mlen >= len)) s_misc[0] = p + mlen;       // the one token that leaves the tile
+            __syncthreads();
+            uint32_t before = 0, all = 0;
+            for (uint32_t q = 0; q < 4u; ++q) { const uint32_t c = s_wave[q]; before += q < wv ? c : 0u; all += c; }
+            if (tok) {
+                const uint32_t at = n_tok + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                uint32_t t = s_in[p];
+                if (dist) {
+                    uint32_t nx, xv;
+                    t = LZ_MATCH | ((mlen - 3u) << 16) | (dist - 1u);
+                    atomicAdd(&s_lhist[257u + lz_len_sym(mlen - 3u, &nx, &xv)], 1u);
+                    atomicAdd(&s_dhist[lz_dist_sym(dist - 1u, &nx, &xv)], 1u);
+                } else
+                    atomicAdd(&s_lhist[t], 1u);
+                if (at < BZ_PAYLOAD) tk[at] = t;
+            }
+            n_tok += all;
+            __syncthreads();                          // s_wave and s_misc[0] are read; the next tile writes them again
+        }
+        // ---- 3. the codes: literal/length and distance over the tokens, and the literal code of level 1 over the bytes ----
+        for (uint32_t i = tid; i < BZ_OUT_WORDS; i += 256u) s_out[i] = 0;
+        lz_rank(s_lhist, LZ_NL, s_ord, tid);
+        lz_rank(s_dhist, LZ_ND, s_ord + LZ_NL, tid);
+        lz_rank(s_bhist, 257u, s_ord + LZ_NL + LZ_ND, tid);
+        __syncthreads();
+        if (tid == 0) lz_build_code(s_lhist, LZ_NL, s_ord, s_wt, s_par, s_dep, s_lcode);
+        if (tid == 64u) lz_build_code(s_dhist, LZ_ND, s_ord + LZ_NL, s_wt + 2 * LZ_NL, s_par + 2 * LZ_NL, s_dep + 2 * LZ_NL, s_dcode);
+        if (tid == 128u) lz_build_code(s_bhist, 257u, s_ord + LZ_NL + LZ_ND, s_wt + 2 * (LZ_NL + LZ_ND), s_par + 2 * (LZ_NL + LZ_ND), s_dep + 2 * (LZ_NL + LZ_ND), s_bcode);
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t nl = 257, nd = 1;
+            unsigned long long bits = 0, plain = BZ_HDR_BITS;
+            for (uint32_t s = 0; s < LZ_NL; ++s) {
+                const uint32_t c = s_lhist[s];
+                if (!c) continue;
+                if (s >= nl) nl = s + 1u;
+                bits += (unsigned long long)c * ((s_lcode[s] >> 16) + (s > 256u ? lz_len_extra(s - 257u) : 0u));
+            }
+            for (uint32_t d = 0; d < LZ_ND; ++d) {
+                const uint32_t c = s_dhist[d];
+                if (!c) continue;
+                if (d >= nd) nd = d + 1u;
+                bits += (unsigned long long)c * ((s_dcode[d] >> 16) + lz_dist_extra(d));
+            }
+            for (uint32_t s = 0; s < 257u; ++s) plain += (unsigned long long)s_bhist[s] * (s_bcode[s] >> 16);
+            uint32_t hdr = LZ_FIX_BITS + 4u * (nl + nd);
+            bits += hdr;
+            // the smallest of three: the matched form, level 1's block over the bytes (short far matches can cost more than their
+            // literals), the stored block.  Ties go to the simpler form
+            const bool matched = bits < plain;
+            if (!matched) { bits = plain; hdr = BZ_HDR_BITS; nl = 257; nd = 1; }
+            const bool use = (bits + 7u) / 8u < (unsigned long long)len + 5u;
+            s_misc[1] = use ? (matched ? 1u : 2u) : 0u; s_misc[2] = (uint32_t)bits; s_misc[3] = hdr;
+            if (use) {
+                const uint32_t* const lc = matched ? s_lcode : s_bcode;
+                BzBits w; w.start(s_out, 0);
+                w.put(1u, 1); w.put(2u, 2); w.put(nl - 257u, 5); w.put(nd - 1u, 5); w.put(15u, 4);
+                for (int k = 0; k < 19; ++k) w.put(k < 3 ? 0u : 4u, 3);                 // as k_bgzf_deflate: four bits per length, no run-length symbols
+                for (uint32_t s = 0; s < nl; ++s) w.put(__brev(lc[s] >> 16) >> 28, 4);
+                if (matched && s_dcode[nd - 1u])
+                    for (uint32_t d = 0; d < nd; ++d) w.put(__brev(s_dcode[d] >> 16) >> 28, 4);
+                else
+                    w.put(__brev(1u) >> 28, 4);      // no match: one distance code of length 1, never used
+                w.flush();
+            }
+        }
+        __syncthreads();
+        const bool huff = s_misc[1] != 0, matched = s_misc[1] == 1u;
+        const uint32_t total_bits = s_misc[2];
+        if (huff) {
+            // ---- 4. every lane's tokens (or, in level 1's form, bytes) into the stream behind the header ----
+            const uint32_t* const lc = matched ? s_lcode : s_bcode;
+            const uint32_t n_sym = matched ? n_tok : len, per = (n_sym + 255u) >> 8;
+            const uint32_t a = tid * per < n_sym ? tid * per : n_sym, e = a + per < n_sym ? a + per : n_sym;
+            uint32_t nbits = 0;
+            for (uint32_t i = a; i < e; ++i) {
+                const uint32_t t = matched ? tk[i] : s_in[i];
+                if (t & LZ_MATCH) {
+                    uint32_t nx, xv, nb = 0;
+                    nb += lc[257u + lz_len_sym((t >> 16) & 255u, &nx, &xv)] >> 16; nb += nx;
+                    nb += s_dcode[lz_dist_sym(t & 0x7FFFu, &nx, &xv)] >> 16; nb += nx;
+                    nbits += nb;
+                } else
+                    nbits += lc[t] >> 16;
+            }
+            uint32_t incl = nbits;
+            for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(incl, off); if ((int)lane >= off) incl += t; }
+            if (lane == 63u) s_wave[wv] = incl;
+            __syncthreads();
+            uint32_t before = 0;
+            for (uint32_t q = 0; q < wv; ++q) before += s_wave[q];
+            BzBits w; w.start(s_out, s_misc[3] + before + incl - nbits);
+            for (uint32_t i = a; i < e; ++i) {
+                const uint32_t t = matched ? tk[i] : s_in[i];
+                if (t & LZ_MATCH) {
+                    uint32_t nx, xv;
+                    uint32_t c = lc[257u + lz_len_sym((t >> 16) & 255u, &nx, &xv)];
+                    w.put(c & 0xFFFFu, c >> 16); w.put(xv, nx);
+                    c = s_dcode[lz_dist_sym(t & 0x7FFFu, &nx, &xv)];
+                    w.put(c & 0xFFFFu, c >> 16); w.put(xv, nx);
+                } else {
+                    const uint32_t c = lc[t];
+                    w.put(c & 0xFFFFu, c >> 16);
+                }
+            }
+            w.flush();
+            if (tid == 0) { const uint32_t c = lc[256]; BzBits z; z.start(s_out, total_bits - (c >> 16)); z.put(c & 0xFFFFu, c >> 16); z.flush(); }
+            __syncthreads();
+        }
+        // ---- the block into its slot: header, deflate stream, CRC-32, ISIZE ----
+        const uint32_t body = huff ? (total_bits + 7u) >> 3 : len + 5u;
+        const uint32_t bsize = 18u + body + 8u;
+        uint8_t* const o = slots + (size_t)blk * BZ_SLOT;
+        if (tid < 18u) {
+            const uint32_t bs1 = bsize - 1u;
+            const uint8_t hd[18] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)(bs1 & 255u), (uint8_t)(bs1 >> 8) };
+            o[tid] = hd[tid];
+        }
+        if (huff) {
+            const uint8_t* const sb = reinterpret_cast<const uint8_t*>(s_out);
+            for (uint32_t i = tid; i < body; i += 256u) o[18u + i] = sb[i];
+        } else {
+            if (tid < 5u) {
+                const uint32_t nl = ~len & 0xFFFFu;
+                const uint8_t sh[5] = { 1, (uint8_t)(len & 255u), (uint8_t)(len >> 8), (uint8_t)(nl & 255u), (uint8_t)(nl >> 8) };
+                o[18u + tid] = sh[tid];
+            }
+            for (uint32_t i = tid; i < len; i += 256u) o[23u + i] = s_in[i];
+        }
+        if (tid < 8u) { const uint32_t v = tid < 4u ? crc_all : len; o[18u + body + tid] = (uint8_t)(v >> (8u * (tid & 3u))); }
+        if (tid == 0) sizes[blk] = bsize;
+        __syncthreads();                              // the payload and the stream are read: the next payload may overwrite them
+    }
+}
+
 __global__ void __launch_bounds__(256) k_bgzf_compact(const uint8_t* __restrict__ slots, const unsigned long long* __restrict__ off, uint8_t* __restrict__ out) {
     const unsigned long long a = off[blockIdx.x];
     const uint32_t size = (uint32_t)(off[blockIdx.x + 1] - a);
@@ -392,7 +719,7 @@ int gmk_bam_rows(const GmDevBatch& b, const GmDevText& t, const uint32_t* meta, 
 }
 
 void GmBgzfBufs::release() {
-    for (DevBuf* d : { &slots, &sizes, &offs, &tmp, &out }) d->release();
+    for (DevBuf* d : { &slots, &sizes, &offs, &tmp, &out, &tokens }) d->release();
     for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
 }
 
@@ -404,20 +731,37 @@ uint64_t gm_bgzf_room(uint64_t cap) {
     return whole * BZ_PAYLOAD + (rest > BZ_EXTRA ? rest - BZ_EXTRA : 0);
 }
 
+std::string gm_bgzf_level_text(int level) {
+    return "the level is 0 (stored), 1 (Huffman) or 1 | GM_BGZF_LZ77 (257: Huffman over LZ77 matches), not " + std::to_string(level);
+}
+
 // d_in[0, n) in HBM -> whole BGZF blocks side by side in z.out, *total bytes of them; synchronises the stream
 int gm_bgzf_device(const void* d_in, uint64_t n, int level, GmBgzfBufs& z, uint64_t* total, void* stream) {
     *total = 0;
     if (!n) return GM_OK;
-    if (level != 0 && level != 1) { gm_set_error("BGZF: the level is 0 (stored) or 1 (Huffman), not " + std::to_string(level)); return GM_E_ARG; }
+    if (!gm_bgzf_level_ok(level)) { gm_set_error("BGZF: " + gm_bgzf_level_text(level)); return GM_E_ARG; }
     const uint64_t nb64 = (n + BZ_PAYLOAD - 1) / BZ_PAYLOAD;
     if (nb64 > 0x7FFFFFFFull) { gm_set_error("BGZF: more than 2^31 - 1 blocks in one call"); return GM_E_ARG; }
     const uint32_t nb = (uint32_t)nb64;
     hipStream_t st = S_(stream);
     if (z.slots.ensure((size_t)nb * BZ_SLOT) || z.sizes.ensure((size_t)nb * 4) || z.offs.ensure(((size_t)nb + 1) * 8) || z.tmp.ensure(((size_t)nb / 1024 + 8) * 8) ||
         z.out.ensure((size_t)gm_bgzf_bound(n) + 16)) return GM_E_NOMEM;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgzf_deflate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BZ_LDS));
+    const bool lz = (level & GM_BGZF_LZ77) != 0;
+    uint32_t lz_grid = 0;
+    if (lz) {
+        // one workgroup per compute unit (the LDS holds one), each with room for a payload's tokens
+        if (!z.lz_wgs) { int dev = 0, cus = 0; HIPCHK(hipGetDevice(&dev)); HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)); z.lz_wgs = (uint32_t)std::max(cus, 1); }
+        lz_grid = std::min(nb, z.lz_wgs);
+        if (z.tokens.ensure((size_t)lz_grid * BZ_PAYLOAD * 4)) return GM_E_NOMEM;
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgzf_deflate_lz), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BZ_LDS));
+    } else
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgzf_deflate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BZ_LDS));
     if (z.timed) { for (auto& e : z.ev) if (!e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(z.ev[0], st)); }
-    hipLaunchKernelGGL(k_bgzf_deflate, dim3(nb), dim3(256), BZ_LDS, st, (const uint8_t*)d_in, (unsigned long long)n, level, z.slots.as<uint8_t>(), z.sizes.as<uint32_t>());
+    if (lz)
+        hipLaunchKernelGGL(k_bgzf_deflate_lz, dim3(lz_grid), dim3(256), BZ_LDS, st, (const uint8_t*)d_in, (unsigned long long)n, nb, z.slots.as<uint8_t>(), z.sizes.as<uint32_t>(),
+                           z.tokens.as<uint32_t>());
+    else
+        hipLaunchKernelGGL(k_bgzf_deflate, dim3(nb), dim3(256), BZ_LDS, st, (const uint8_t*)d_in, (unsigned long long)n, level, z.slots.as<uint8_t>(), z.sizes.as<uint32_t>());
     HIPCHK(hipGetLastError());
     KCHK(gmk_scan_u32(z.sizes.as<uint32_t>(), nb, z.offs.as<uint64_t>(), z.tmp.as<unsigned long long>(), stream));
     if (z.timed) HIPCHK(hipEventRecord(z.ev[1], st));
@@ -443,7 +787,7 @@ int gm_bgzf_device(const void* d_in, uint64_t n, int level, GmBgzfBufs& z, uint6
 extern "C" int gm_bgzf_compress(gm_index* ix, const void* data, uint64_t n, int level, void* out, uint64_t cap, uint64_t* n_out, void* hip_stream) {
     if (!ix || !n_out) return GM_E_ARG;
     *n_out = 0;
-    if (level != 0 && level != 1) { gm_set_error("gm_bgzf_compress: the level is 0 (stored) or 1 (Huffman), not " + std::to_string(level)); return GM_E_ARG; }
+    if (!gm_bgzf_level_ok(level)) { gm_set_error("gm_bgzf_compress: " + gm_bgzf_level_text(level)); return GM_E_ARG; }
     if (ix->host_only) { gm_set_error("gm_bgzf_compress: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
     if (!n) return GM_OK;
     if (!data || (!out && cap)) { gm_set_error("gm_bgzf_compress: data or out is NULL"); return GM_E_ARG; }

@@ -100,6 +100,8 @@ int gmk_bam_rows(const GmDevBatch& b, const GmDevText& t, const uint32_t* meta, 
 // BGZF: the worst-case slots of the blocks, their sizes and the scan of those, and the blocks side by side
 struct GmBgzfBufs {
     DevBuf slots, sizes, offs, tmp, out;
+    DevBuf tokens;                          // GM_BGZF_LZ77: a payload's tokens per resident workgroup of k_bgzf_deflate_lz, from the first such call on
+    uint32_t lz_wgs = 0;                    // those workgroups: the device's compute units (0: not asked yet)
     bool timed = false;                     // HIP events around k_bgzf_deflate + the scan and around k_bgzf_compact, summed into ms (one more wait per call)
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
     double ms = 0; uint64_t in_bytes = 0, out_bytes = 0;
@@ -107,7 +109,9 @@ struct GmBgzfBufs {
 };
 uint64_t gm_bgzf_bound(uint64_t n);                          // the most bytes the blocks of n input bytes take: n + 31 per started 65280
 uint64_t gm_bgzf_room(uint64_t cap);                         // the most input bytes whose blocks are sure to fit in cap
-// d_in[0, n) in HBM -> z.out[0, *total); synchronises the stream.  level 0 stored, 1 Huffman
+// d_in[0, n) in HBM -> z.out[0, *total); synchronises the stream.  level 0 stored, 1 Huffman, 1 | GM_BGZF_LZ77 Huffman over LZ77 matches
+inline bool gm_bgzf_level_ok(int level) { return level == 0 || level == 1 || level == (1 | GM_BGZF_LZ77); }
+std::string gm_bgzf_level_text(int level);                   // "the level is ..., not <level>", for the GM_E_ARG of every entry point that takes one
 int gm_bgzf_device(const void* d_in, uint64_t n, int level, GmBgzfBufs& z, uint64_t* total, void* stream);
 
 // gm_bai.hip.  The per-row table of a sorted BAM's index, one entry per row of the sorted order: the virtual offsets of the record's

@@ -503,7 +503,7 @@ extern "C" int gm_sam_sorter_read(gm_sam_sorter* s, char* text, uint64_t cap, ui
 extern "C" int gm_sam_sorter_read_bgzf(gm_sam_sorter* s, int level, void* out, uint64_t cap, uint64_t* n_out, void* stream) {
     if (!s || !n_out) return GM_E_ARG;
     *n_out = 0;
-    if (level != 0 && level != 1) { gm_set_error("gm_sam_sorter_read_bgzf: the level is 0 (stored) or 1 (Huffman), not " + std::to_string(level)); return GM_E_ARG; }
+    if (!gm_bgzf_level_ok(level)) { gm_set_error("gm_sam_sorter_read_bgzf: " + gm_bgzf_level_text(level)); return GM_E_ARG; }
     std::lock_guard<std::mutex> lk(s->mu);
     if (!out && cap && s->finished && s->next_row < s->n_rows) { gm_set_error("gm_sam_sorter_read_bgzf: out is NULL"); return GM_E_ARG; }
     if (s->bai_on && s->bai_level >= 0 && level != s->bai_level) {

@@ -67,6 +67,7 @@ struct Options {
     bool bam = false;               // --sam_format=bam: <out>.bam instead of <out>.sam, records and BGZF written on the GPU (gm_output_batch_bam; implies --sam_text=device)
     int bam_level = 1;              // --bam_level=0|1: stored blocks, or Huffman-coded ones
     bool bam_level_set = false;     // (refused without --sam_format=bam)
+    bool bam_lz77 = false;          // --bam_lz77: LZ77 matches under the Huffman code of level 1; once the options are checked, GM_BGZF_LZ77 in bam_level
     bool bam_index = false;         // --bam_index: <out>.bam.bai beside a sorted <out>.bam, built on the GPU from what the sorter holds (gm_sam_sorter_bai)
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
@@ -125,6 +126,8 @@ struct Options {
             "                               written on the GPU; with --sam_sort=coordinate the file is a sorted BAM.  Implies --sam_text=device\n"
             "                               (not with --sam_text=host or --sam_shards above 1)\n"
             "      --bam_level=0|1          with --sam_format=bam: 0 = stored BGZF blocks, 1 (default) = Huffman-coded blocks (no LZ77 matches)\n"
+            "      --bam_lz77               with --sam_format=bam at level 1: LZ77 matches (4 - 258 bytes, within the block) under the Huffman code,\n"
+            "                               found on the GPU - a smaller <out>.bam with the same records (not with --bam_level=0)\n"
             "      --bam_index              with --sam_format=bam --sam_sort=coordinate: also write <out>.bam.bai (SAMv1 section 5.2), built on the\n"
             "                               GPU from the sorted records and their BGZF offsets; <out>.bam is written exactly as without the flag.\n"
             "                               Records must end at or below 2^29 (there is no .csi)\n");
@@ -203,6 +206,7 @@ static void parse_args(int argc, char** argv, Options& o) {
                 if (strcmp(s + 10, "0") && strcmp(s + 10, "1")) { fprintf(stderr, "Error: --bam_level takes 0 or 1, not: %s\n", s + 10); exit(1); }
                 o.bam_level = s[10] - '0'; o.bam_level_set = true;
             }
+            else if (!strcmp(s, "bam_lz77")) o.bam_lz77 = true;
             else if (!strcmp(s, "bam_index")) o.bam_index = true;
             else if (starts(s, "sam_shards=")) {
                 char* end = nullptr;
@@ -265,6 +269,9 @@ static void parse_args(int argc, char** argv, Options& o) {
         o.sam_text_device = true;
     }
     if (o.bam_level_set && !o.bam) { fprintf(stderr, "Error: --bam_level sets the compression of --sam_format=bam: give --sam_format=bam with --bam_level\n"); exit(1); }
+    if (o.bam_lz77 && !o.bam) { fprintf(stderr, "Error: --bam_lz77 sets the compression of --sam_format=bam: give --sam_format=bam with --bam_lz77\n"); exit(1); }
+    if (o.bam_lz77 && o.bam_level == 0) { fprintf(stderr, "Error: --bam_lz77 adds matches to the Huffman-coded blocks of --bam_level=1: it cannot be combined with --bam_level=0\n"); exit(1); }
+    if (o.bam_lz77) o.bam_level |= GM_BGZF_LZ77;
     if (o.bam_index && !o.bam) { fprintf(stderr, "Error: --bam_index writes the index of a sorted <out>.bam: give --sam_format=bam (and --sam_sort=coordinate) with --bam_index\n"); exit(1); }
     if (o.bam_index && !o.sam_sort) { fprintf(stderr, "Error: --bam_index indexes a coordinate-sorted file: give --sam_sort=coordinate with --bam_index\n"); exit(1); }
     if (o.bam) {                                             // refused before a device is opened or a file is written

@@ -383,9 +383,12 @@ int gm_sam_sorter_add_rows(gm_sam_sorter*, uint64_t seq, const char* text, const
  * that exceeds cap (nothing is written). */
 int gm_bam_header(gm_index*, const char* sam_header, uint64_t n, void* out, uint64_t cap, uint64_t* n_out);
 /* any n bytes of the caller's -> whole BGZF blocks of at most 65280 input bytes each, compressed on the device: level 0 stored blocks,
- * level 1 one dynamic-Huffman block over literals only (no LZ77 matches), written stored where that is not smaller.  The output is a
- * function of the input bytes and the level alone.  n = 0: *n_out = 0.  GM_E_ARG for another level, GM_E_NO_DEVICE on a host-only
- * index, GM_E_CAPACITY (*n_out = the bytes needed, nothing is written) when the blocks exceed cap; n + 31 per started 65280 always holds them. */
+ * level 1 one dynamic-Huffman block over literals only (no LZ77 matches), level 1 | GM_BGZF_LZ77 one dynamic-Huffman block over literals
+ * and LZ77 matches (length 4 - 258, distance up to 32768, inside the block's own input; what the matcher finds: DESIGN.md section 4), each
+ * written stored where that is not smaller.  The output is a function of the input bytes and the level word alone.  n = 0: *n_out = 0.
+ * GM_E_ARG for any other level word (0 | GM_BGZF_LZ77, 2, another bit), GM_E_NO_DEVICE on a host-only index, GM_E_CAPACITY (*n_out = the
+ * bytes needed, nothing is written) when the blocks exceed cap; n + 31 per started 65280 always holds them. */
+enum { GM_BGZF_LZ77 = 0x100 };
 int gm_bgzf_compress(gm_index*, const void* data, uint64_t n, int level, void* out, uint64_t cap, uint64_t* n_out, void* hip_stream);
 /* the 28-byte empty block that ends a BGZF file */
 int gm_bgzf_eof(void* out28);
@@ -395,7 +398,7 @@ int gm_bgzf_eof(void* out28);
  * that is 0), flag 0 / 16, no mate; read_name = the first 254 bytes of the name (l_read_name is one byte; the SAM row keeps up to 1023);
  * the CIGAR operations, SEQ and the first l_seq characters of QUAL as the row prints them (len << 4 | op; nibbles of "=ACMGRSVTWYHKDBN",
  * anything else 15; minus 33, floored at 0); tags XA:f = (float)((double)a_score / adjust), XP:f = post_prob's bits, X0:i as int32.
- * level as in gm_bgzf_compress.  len = bytes of the blocks, raw_len = bytes of the records.  GM_E_CAPACITY: cap holds the size needed and
+ * level as in gm_bgzf_compress (0, 1 or 1 | GM_BGZF_LZ77).  len = bytes of the blocks, raw_len = bytes of the records.  GM_E_CAPACITY: cap holds the size needed and
  * NOTHING has been deposited - repeat the call.  GM_E_UNSUPPORTED exactly where gm_output_batch_text returns it (an XA / XP outside the
  * range the text form prints), so both forms accept the same blocks.  A block with no mapped read: len = 0.  No enqueue form. */
 typedef struct {
@@ -406,7 +409,7 @@ typedef struct {
 int gm_output_batch_bam(gm_index*, const gm_params*, gm_batch*, const gm_reads*, const gm_read_text*, const gm_hits*, gm_bam_out* out, void* hip_stream);
 int gm_output_batch_bam_resident(gm_index*, const gm_params*, gm_batch*, const gm_hits*, gm_bam_out* out, void* hip_stream);
 /* while gm_batch_set_profiling is on, the two calls above bracket their kernels with HIP events (two more waits per call).  Since the last
- * call of this function: ms[0] = k_bam_sizes + k_bam_rows, ms[1] = k_bgzf_deflate + the scan of the sizes + k_bgzf_compact; bytes[0] = bytes
+ * call of this function: ms[0] = k_bam_sizes + k_bam_rows, ms[1] = k_bgzf_deflate (k_bgzf_deflate_lz with GM_BGZF_LZ77) + the scan of the sizes + k_bgzf_compact; bytes[0] = bytes
  * of records written, bytes[1] = bytes into and bytes[2] = bytes out of the BGZF kernels (tools/bam_bench.py) */
 int gm_batch_bam_times(gm_batch*, double* ms /* [2] */, uint64_t* bytes /* [3] */);
 /* what gm_output_batch_sorted / _sorted_resident put into a sorter's arena: SAM rows as text (default) or BAM records.  Keys, stable
@@ -415,7 +418,8 @@ enum { GM_ROWS_TEXT = 0, GM_ROWS_BAM = 1 };
 int gm_sam_sorter_set_rows(gm_sam_sorter*, int rows);
 /* gm_sam_sorter_read with the slab compressed on the device before the download: the next whole rows whose BGZF form is sure to fit in
  * cap (reserved for the worst case, stored: the rows' bytes + 31 per started 65280), as whole BGZF blocks.  *n_out = 0: done.
- * GM_E_CAPACITY when the next row alone needs more: *n_out = the cap it needs, nothing is consumed. */
+ * GM_E_CAPACITY when the next row alone needs more: *n_out = the cap it needs, nothing is consumed.  level as in gm_bgzf_compress
+ * (0, 1 or 1 | GM_BGZF_LZ77); on an indexed sorter every read takes the same level word. */
 int gm_sam_sorter_read_bgzf(gm_sam_sorter*, int level, void* out, uint64_t cap, uint64_t* n_out, void* hip_stream);
 /* ---- the .bai (SAMv1 section 5.2) of a sorted BAM, built on the device from what the sorter holds (gm_bai.hip) ----
  * gm_sam_sorter_index_begin, after a successful finish and before the first read, on a sorter of GM_ROWS_BAM: from then on
