@@ -25,23 +25,12 @@
 
 namespace {
 
-constexpr uint32_t BAI_PAYLOAD = 65280;             // input bytes per BGZF block (gm_bam.hip)
 constexpr long long BAI_MAX_END = 1ll << 29;
 constexpr uint32_t BAI_NONE = 0xFFFFFFFFu;          // the reference of a row without one
 constexpr uint32_t BAI_PSEUDO_BIN = 37450;
 
 __device__ __forceinline__ uint32_t bai_rd32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 __device__ __forceinline__ uint32_t bai_rd16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-// SAMv1 section 5.3
-__device__ __forceinline__ uint32_t bai_reg2bin(long long beg, long long end) {
-    --end;
-    if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
-    return 0;
-}
 __device__ __forceinline__ void bai_put64(uint8_t* o, unsigned long long v) {          // o is 4-byte aligned
     reinterpret_cast<uint32_t*>(o)[0] = (uint32_t)v; reinterpret_cast<uint32_t*>(o)[1] = (uint32_t)(v >> 32);
 }
@@ -77,15 +66,15 @@ __global__ void __launch_bounds__(256) k_bai_rows(const uint8_t* __restrict__ sl
                 const long long end = (long long)pos + (long long)(ref_len ? ref_len : 1ull);
                 if (ref >= n_ref) atomicMin(&t.err[1], i);
                 else if (pos < 0 || end > BAI_MAX_END) atomicMin(&t.err[2], i);
-                else pk = bai_reg2bin(pos, end) | (uint32_t)((end - 1) >> 14) << 16 | ((flag & 4u) ? 0x80000000u : 0u);
+                else pk = gm_reg2bin(pos, end) | (uint32_t)((end - 1) >> 14) << 16 | ((flag & 4u) ? 0x80000000u : 0u);
             }
         }
     }
     if (!ok) atomicMin(&t.err[0], i);
-    const uint32_t blk = (uint32_t)(u / BAI_PAYLOAD);
-    const unsigned long long eb = e / BAI_PAYLOAD;
-    t.vbeg[i] = (file_off + offs[blk < nb ? blk : nb]) << 16 | (u % BAI_PAYLOAD);
-    t.vend[i] = e >= bytes || eb >= nb ? (file_off + offs[nb]) << 16 : (file_off + offs[eb]) << 16 | (e % BAI_PAYLOAD);
+    const uint32_t blk = (uint32_t)(u / GM_BGZF_PAYLOAD);
+    const unsigned long long eb = e / GM_BGZF_PAYLOAD;
+    t.vbeg[i] = (file_off + offs[blk < nb ? blk : nb]) << 16 | (u % GM_BGZF_PAYLOAD);
+    t.vend[i] = e >= bytes || eb >= nb ? (file_off + offs[nb]) << 16 : (file_off + offs[eb]) << 16 | (e % GM_BGZF_PAYLOAD);
     t.ref[i] = ref; t.pos[i] = pos; t.pk[i] = pk;
 }
 
@@ -297,7 +286,7 @@ int gmk_bai_rows(const void* slab, const uint64_t* soff, uint64_t r0, uint64_t r
     return (int)hipGetLastError();
 }
 
-uint64_t gm_bai_blocks(uint64_t bytes) { return (bytes + BAI_PAYLOAD - 1) / BAI_PAYLOAD; }
+uint64_t gm_bai_blocks(uint64_t bytes) { return (bytes + GM_BGZF_PAYLOAD - 1) / GM_BGZF_PAYLOAD; }
 
 int gm_bai_build(const gm_index* ix, const GmBaiRows& t, uint64_t n_rows, const GmBaiAlloc& alloc, void** out, uint64_t* out_bytes, uint64_t* n_chunks, void* stream) {
     *out = nullptr; *out_bytes = 0; *n_chunks = 0;

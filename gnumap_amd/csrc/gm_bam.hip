@@ -6,10 +6,12 @@
 //                 prints it, reg2bin, the record's size
 //   k_bam_rows    one wavefront per record: the fixed 36 bytes and the three tags through LDS, then name, CIGAR, SEQ nibbles and QUAL
 //                 byte-wise; every store stays inside the span the scan gave the record
-//   k_bgzf_deflate  one workgroup per payload of at most 65280 bytes, held in LDS: CRC-32 by sub-chunks folded with
-//                 crc(A|B) = crc(A) * x^(8|B|) ^ crc(B), then a stored block (level 0) or one dynamic-Huffman block over literals
-//                 only (level 1) - histogram in LDS, a length-limited code built by one lane, all lanes emit through a prefix sum of
-//                 their bit counts - into the payload's worst-case slot
+//   bz_*          the steps of a BGZF block, written once for both deflate kernels: bz_load (the payload into LDS), bz_crc_table and
+//                 bz_crc_hist (CRC-32 by sub-chunks folded with crc(A|B) = crc(A) * x^(8|B|) ^ crc(B), the bytes into a histogram),
+//                 bz_rank and bz_build_code (a length-limited canonical code, built by one lane), bz_put_block_header, bz_lane_start
+//                 (a lane's first bit from the prefix sum of the lanes' bit counts), bz_put_eob, bz_write_member
+//   k_bgzf_deflate  one workgroup per payload of at most 65280 bytes, held in LDS: a stored block (level 0) or one dynamic-Huffman
+//                 block over literals only (level 1) into the payload's worst-case slot
 //   k_bgzf_deflate_lz  level 1 | GM_BGZF_LZ77: the same payload, slot and size, one dynamic-Huffman block over literals and LZ77 matches -
 //                 a persistent grid with a token area per workgroup; what it finds is described above the kernel and in DESIGN.md
 //   k_bgzf_compact  after the scan of the blocks' sizes: the slots side by side, so that one contiguous run crosses the link
@@ -20,18 +22,19 @@
 // into words of the bit stream and, in k_bgzf_deflate_lz, maxima of positions into the hash table - none of their results depends on the
 // order in which they land, and a barrier lies between the maxima and the lookups that read them.
 #include "gm_lib.h"
+#include "gm_fmt_dev.h"
 #include <algorithm>
 #include <memory>
 
 namespace {
 
-constexpr uint32_t BZ_PAYLOAD = 65280;              // bytes of input per BGZF block
+constexpr uint32_t BZ_PAYLOAD = GM_BGZF_PAYLOAD;    // bytes of input per BGZF block
 constexpr uint32_t BZ_EXTRA = 31;                   // 18 header + 5 stored-block header + 8 trailer: the largest block is BZ_PAYLOAD + BZ_EXTRA
 constexpr uint32_t BZ_SLOT = 65312;                 // worst-case slot of a block, a multiple of 16
 constexpr uint32_t BZ_OUT_WORDS = (BZ_PAYLOAD + 16) / 4;
 constexpr uint32_t BZ_LDS = BZ_PAYLOAD + BZ_OUT_WORDS * 4;
-// BFINAL, BTYPE, HLIT = 257, HDIST = 1, HCLEN = 19; 19 code-length code lengths of 3 bits; 257 + 1 code lengths of 4 bits, not run-length coded
-constexpr uint32_t BZ_HDR_BITS = 3 + 5 + 5 + 4 + 19 * 3 + 258 * 4;
+constexpr uint32_t BZ_FIX_BITS = 3 + 5 + 5 + 4 + 19 * 3;     // BFINAL, BTYPE, HLIT, HDIST, HCLEN = 19, the code-length code: 19 lengths of 3 bits
+constexpr uint32_t BZ_HDR_BITS = BZ_FIX_BITS + 4 * (257 + 1);        // the header over literals alone: 257 + 1 code lengths of 4 bits, not run-length coded
 constexpr uint32_t BZ_POLY = 0xEDB88320u;
 
 // a * b mod P over GF(2), operands and result bit-reflected as the CRC register is (x^0 = 0x80000000)
@@ -57,140 +60,143 @@ struct BzBits {                                     // one lane's writer into th
         acc |= (unsigned long long)v << nb; nb += n;
         if (nb >= 32u) { atomicOr(&out[w], (uint32_t)acc); acc >>= 32; nb -= 32u; ++w; }
     }
+    __device__ __forceinline__ void code(uint32_t c) { put(c & 0xFFFFu, c >> 16); }     // a symbol's code as bz_build_code leaves it
     __device__ __forceinline__ void flush() { if (nb) atomicOr(&out[w], (uint32_t)acc); }
 };
 
-__global__ void __launch_bounds__(256) k_bgzf_deflate(const uint8_t* __restrict__ in, unsigned long long n, int level, uint8_t* __restrict__ slots,
-                                                      uint32_t* __restrict__ sizes) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    uint8_t* const s_in = s_dyn;
-    uint32_t* const s_out = reinterpret_cast<uint32_t*>(s_dyn + BZ_PAYLOAD);
-    __shared__ uint32_t s_tab[256], s_hist[257], s_code[257], s_wt[514], s_wave[4], s_misc[4];
-    __shared__ uint16_t s_par[514], s_ord[257];
-    __shared__ uint8_t s_dep[514];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    const unsigned long long p0 = (unsigned long long)blockIdx.x * BZ_PAYLOAD;
-    if (p0 >= n) return;
-    const uint32_t len = (uint32_t)(n - p0 < BZ_PAYLOAD ? n - p0 : BZ_PAYLOAD);
-    const uint8_t* const src = in + p0;
-    // ---- the payload into LDS, the CRC table, an empty histogram and bit stream ----
+// ------------------------------------------------------------------------------------------------
+// The steps of a block, for the 256 lanes of a workgroup.  All of them are inlined into the kernels, so their pointers stay LDS
+// pointers.  The ones with a barrier inside are called by all lanes under uniform control flow.
+// ------------------------------------------------------------------------------------------------
+// lane tid's run [*a, *e) of n items cut into 256 contiguous runs
+__device__ __forceinline__ void bz_run(uint32_t n, uint32_t tid, uint32_t* a, uint32_t* e) {
+    const uint32_t per = (n + 255u) >> 8;
+    *a = tid * per < n ? tid * per : n; *e = *a + per < n ? *a + per : n;
+}
+// The payload into LDS, 16 bytes a load where the source is aligned.  No barrier: one before s_in is read
+__device__ __forceinline__ void bz_load(const uint8_t* __restrict__ src, uint32_t len, uint8_t* s_in, uint32_t tid) {
     if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
         const uint32_t n16 = len >> 4;
         for (uint32_t q = tid; q < n16; q += 256u) reinterpret_cast<uint4*>(s_in)[q] = reinterpret_cast<const uint4*>(src)[q];
         for (uint32_t i = (n16 << 4) + tid; i < len; i += 256u) s_in[i] = src[i];
     } else
         for (uint32_t i = tid; i < len; i += 256u) s_in[i] = src[i];
-    {
-        uint32_t c = tid;
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? BZ_POLY ^ (c >> 1) : c >> 1;
-        s_tab[tid] = c;
-    }
-    for (uint32_t i = tid; i < 257u; i += 256u) s_hist[i] = i == 256u ? 1u : 0u;          // the end-of-block symbol occurs once
-    if (level == 1) for (uint32_t i = tid; i < BZ_OUT_WORDS; i += 256u) s_out[i] = 0;
-    __syncthreads();
-    // ---- a lane's sub-chunk: its CRC-32, its bytes into the histogram ----
-    const uint32_t chunk = (len + 255u) >> 8;
-    const uint32_t a = tid * chunk < len ? tid * chunk : len, e = a + chunk < len ? a + chunk : len;
+}
+// The CRC-32 table, an entry per lane.  No barrier: one before bz_crc_hist
+__device__ __forceinline__ void bz_crc_table(uint32_t* s_tab, uint32_t tid) {
+    uint32_t c = tid;
+    for (int k = 0; k < 8; ++k) c = (c & 1u) ? BZ_POLY ^ (c >> 1) : c >> 1;
+    s_tab[tid] = c;
+}
+// A lane's run of the payload: its CRC-32 and, with count (uniform; level 0 has no use for the atomics), its bytes into hist; the
+// runs' CRCs folded into the payload's, which every lane gets back.  Two barriers: behind them hist is complete and s_wave is free again
+__device__ __forceinline__ uint32_t bz_crc_hist(const uint8_t* s_in, uint32_t len, const uint32_t* s_tab, bool count, uint32_t* hist, uint32_t* s_wave, uint32_t tid) {
+    uint32_t a, e;
+    bz_run(len, tid, &a, &e);
     uint32_t crc = 0xFFFFFFFFu;
     for (uint32_t i = a; i < e; ++i) {
         const uint32_t by = s_in[i];
         crc = s_tab[(crc ^ by) & 255u] ^ (crc >> 8);
-        if (level == 1) atomicAdd(&s_hist[by], 1u);
+        if (count) atomicAdd(&hist[by], 1u);
     }
-    crc ^= 0xFFFFFFFFu;                              // (an empty sub-chunk: 0)
+    crc ^= 0xFFFFFFFFu;                              // (an empty run: 0)
     uint32_t part = a < e ? bz_mul(bz_xpow8(len - e), crc) : 0u;
     for (int off = 32; off; off >>= 1) part ^= __shfl_xor(part, off);
-    if (lane == 0) s_wave[wv] = part;
+    if ((tid & 63u) == 0) s_wave[tid >> 6] = part;
     __syncthreads();
     const uint32_t crc_all = s_wave[0] ^ s_wave[1] ^ s_wave[2] ^ s_wave[3];
-    __syncthreads();                                 // (s_wave is used again below)
-    bool huff = false;
-    uint32_t total_bits = 0;
-    if (level == 1) {
-        // ---- the symbols in use in ascending (count, symbol) order: every symbol finds its own rank ----
-        for (uint32_t s = tid; s < 257u; s += 256u) {
-            const uint32_t c = s_hist[s];
-            if (!c) continue;
-            uint32_t rank = 0;
-            for (uint32_t q = 0; q < 257u; ++q) { const uint32_t cq = s_hist[q]; rank += (cq && (cq < c || (cq == c && q < s))) ? 1u : 0u; }
-            s_ord[rank] = (uint16_t)s;
-        }
-        for (uint32_t s = tid; s < 257u; s += 256u) s_code[s] = 0;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t m = 0;
-            for (uint32_t s = 0; s < 257u; ++s) m += s_hist[s] ? 1u : 0u;               // >= 2: a literal and the end of block
-            for (uint32_t i = 0; i < m; ++i) s_wt[i] = s_hist[s_ord[i]];
-            for (;;) {
-                // Huffman's algorithm on sorted leaves: leaves [0, m) and the nodes made so far [m, nn) are two ascending queues
-                uint32_t li = 0, ni = m, nn = m;
-                while (nn < 2u * m - 1u) {
-                    uint32_t pick[2];
-                    for (int k = 0; k < 2; ++k) pick[k] = (li < m && (ni >= nn || s_wt[li] <= s_wt[ni])) ? li++ : ni++;
-                    s_wt[nn] = s_wt[pick[0]] + s_wt[pick[1]];
-                    s_par[pick[0]] = s_par[pick[1]] = (uint16_t)nn;
-                    ++nn;
-                }
-                s_dep[2u * m - 2u] = 0;
-                uint32_t deepest = 0;
-                for (uint32_t i = 2u * m - 2u; i-- > 0;) {
-                    const uint32_t d = (uint32_t)s_dep[s_par[i]] + 1u;
-                    s_dep[i] = (uint8_t)(d < 255u ? d : 255u);
-                    if (i < m && d > deepest) deepest = d;
-                }
-                if (deepest <= 15u) break;
-                for (uint32_t i = 0; i < m; ++i) s_wt[i] = (s_wt[i] + 1u) >> 1;          // deeper than deflate allows: flatter counts (the order stays ascending), again
-            }
-            // canonical codes (RFC 1951 section 3.2.2), kept bit-reversed: Huffman codes enter the stream from their most significant bit
-            uint32_t cnt[16], next[16];
-            for (int k = 0; k < 16; ++k) cnt[k] = 0;
-            for (uint32_t i = 0; i < m; ++i) { ++cnt[s_dep[i]]; s_code[s_ord[i]] = (uint32_t)s_dep[i] << 16; }
-            uint32_t code = 0;
-            next[0] = 0;
-            for (int k = 1; k < 16; ++k) { code = (code + cnt[k - 1]) << 1; next[k] = code; }
-            unsigned long long bits = BZ_HDR_BITS;
-            for (uint32_t s = 0; s < 257u; ++s) {
-                const uint32_t l = s_code[s] >> 16;
-                if (!l) continue;
-                s_code[s] = (l << 16) | (__brev(next[l]++) >> (32u - l));
-                bits += (unsigned long long)s_hist[s] * l;
-            }
-            const bool use = (bits + 7u) / 8u < (unsigned long long)len + 5u;           // not smaller than stored: stored
-            s_misc[0] = use ? 1u : 0u; s_misc[1] = (uint32_t)bits;
-            if (use) {
-                BzBits w; w.start(s_out, 0);
-                w.put(1u, 1); w.put(2u, 2); w.put(0u, 5); w.put(0u, 5); w.put(15u, 4);
-                // code-length symbols 0 .. 15 take four bits each (their canonical code is their value), 16 .. 18 are not used;
-                // transmitted in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
-                for (int k = 0; k < 19; ++k) w.put(k < 3 ? 0u : 4u, 3);
-                for (uint32_t s = 0; s < 257u; ++s) w.put(__brev(s_code[s] >> 16) >> 28, 4);
-                w.put(__brev(1u) >> 28, 4);          // one distance code of length 1, never used
-                w.flush();
-            }
-        }
-        __syncthreads();
-        huff = s_misc[0] != 0; total_bits = s_misc[1];
-        if (huff) {
-            // ---- every lane's bit count, their prefix sum, and the lane's codes ORed into the stream behind the header ----
-            uint32_t nbits = 0;
-            for (uint32_t i = a; i < e; ++i) nbits += s_code[s_in[i]] >> 16;
-            uint32_t incl = nbits;
-            for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(incl, off); if ((int)lane >= off) incl += t; }
-            if (lane == 63u) s_wave[wv] = incl;
-            __syncthreads();
-            uint32_t before = 0;
-            for (uint32_t q = 0; q < wv; ++q) before += s_wave[q];
-            BzBits w; w.start(s_out, BZ_HDR_BITS + before + incl - nbits);
-            for (uint32_t i = a; i < e; ++i) { const uint32_t c = s_code[s_in[i]]; w.put(c & 0xFFFFu, c >> 16); }
-            w.flush();
-            if (tid == 0) { const uint32_t c = s_code[256]; BzBits z; z.start(s_out, total_bits - (c >> 16)); z.put(c & 0xFFFFu, c >> 16); z.flush(); }
-            __syncthreads();
-        }
+    __syncthreads();
+    return crc_all;
+}
+// Every symbol in use finds its rank in ascending (count, symbol) order: ord[rank] = symbol.  No barrier: one before ord is read
+__device__ __forceinline__ void bz_rank(const uint32_t* hist, uint32_t nsym, uint16_t* ord, uint32_t tid) {
+    for (uint32_t s = tid; s < nsym; s += 256u) {
+        const uint32_t c = hist[s];
+        if (!c) continue;
+        uint32_t rank = 0;
+        for (uint32_t q = 0; q < nsym; ++q) { const uint32_t cq = hist[q]; rank += (cq && (cq < c || (cq == c && q < s))) ? 1u : 0u; }
+        ord[rank] = (uint16_t)s;
     }
-    // ---- the block into its slot: header, deflate stream, CRC-32, ISIZE ----
+}
+// One lane: the code of the symbols in use into code[] (length << 16 | code; zero beforehand) - Huffman's algorithm on the sorted
+// leaves, flatter counts and again while a leaf lies deeper than deflate's 15 bits, canonical codes (RFC 1951 section 3.2.2) kept
+// bit-reversed: Huffman codes enter the stream from their most significant bit.  One symbol in use takes the one-bit code 0.
+// wt, par, dep: 2 * nsym entries each.  Returns the bits the symbols take under the code, sum of count * length.  No barrier
+__device__ __forceinline__ uint32_t bz_build_code(const uint32_t* hist, uint32_t nsym, const uint16_t* ord, uint32_t* wt, uint16_t* par, uint8_t* dep, uint32_t* code) {
+    uint32_t m = 0;
+    for (uint32_t s = 0; s < nsym; ++s) m += hist[s] ? 1u : 0u;
+    if (m == 0) return 0;
+    if (m == 1) { code[ord[0]] = 1u << 16; return hist[ord[0]]; }
+    for (uint32_t i = 0; i < m; ++i) wt[i] = hist[ord[i]];
+    for (;;) {
+        // the leaves [0, m) and the nodes made so far [m, nn) are two ascending queues
+        uint32_t li = 0, ni = m, nn = m;
+        while (nn < 2u * m - 1u) {
+            uint32_t pick[2];
+            for (int k = 0; k < 2; ++k) pick[k] = (li < m && (ni >= nn || wt[li] <= wt[ni])) ? li++ : ni++;
+            wt[nn] = wt[pick[0]] + wt[pick[1]];
+            par[pick[0]] = par[pick[1]] = (uint16_t)nn;
+            ++nn;
+        }
+        dep[2u * m - 2u] = 0;
+        uint32_t deepest = 0;
+        for (uint32_t i = 2u * m - 2u; i-- > 0;) {
+            const uint32_t d = (uint32_t)dep[par[i]] + 1u;
+            dep[i] = (uint8_t)(d < 255u ? d : 255u);
+            if (i < m && d > deepest) deepest = d;
+        }
+        if (deepest <= 15u) break;
+        for (uint32_t i = 0; i < m; ++i) wt[i] = (wt[i] + 1u) >> 1;      // (the order stays ascending)
+    }
+    uint32_t cnt[16], next[16];
+    for (int k = 0; k < 16; ++k) cnt[k] = 0;
+    for (uint32_t i = 0; i < m; ++i) { ++cnt[dep[i]]; code[ord[i]] = (uint32_t)dep[i] << 16; }
+    uint32_t c = 0, bits = 0;
+    next[0] = 0;
+    for (int k = 1; k < 16; ++k) { c = (c + cnt[k - 1]) << 1; next[k] = c; }
+    for (uint32_t s = 0; s < nsym; ++s) {
+        const uint32_t l = code[s] >> 16;
+        if (!l) continue;
+        code[s] = (l << 16) | (__brev(next[l]++) >> (32u - l));
+        bits += hist[s] * l;
+    }
+    return bits;
+}
+// One lane: the header of the dynamic block at bit 0 of s_out - BFINAL, BTYPE, HLIT, HDIST, HCLEN, then every code length in four
+// bits (code-length symbols 0 .. 15, whose canonical code is their value; 16 .. 18, the run lengths, are not used; the 19 lengths are
+// transmitted in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15): nl of lcode, nd of dcode.  dcode == nullptr, or no
+// distance in use: one distance code of length 1, never used.  BZ_FIX_BITS + 4 * (nl + nd) bits.  No barrier
+__device__ __forceinline__ void bz_put_block_header(uint32_t* s_out, const uint32_t* lcode, uint32_t nl, const uint32_t* dcode, uint32_t nd) {
+    BzBits w; w.start(s_out, 0);
+    w.put(1u, 1); w.put(2u, 2); w.put(nl - 257u, 5); w.put(nd - 1u, 5); w.put(15u, 4);
+    for (int k = 0; k < 19; ++k) w.put(k < 3 ? 0u : 4u, 3);
+    for (uint32_t s = 0; s < nl; ++s) w.put(__brev(lcode[s] >> 16) >> 28, 4);
+    if (dcode && dcode[nd - 1u])
+        for (uint32_t d = 0; d < nd; ++d) w.put(__brev(dcode[d] >> 16) >> 28, 4);
+    else
+        w.put(__brev(1u) >> 28, 4);
+    w.flush();
+}
+// The lane's first bit behind the header's end, from the prefix sum of the lanes' bit counts.  One barrier; s_wave is read behind it
+__device__ __forceinline__ uint32_t bz_lane_start(uint32_t nbits, uint32_t* s_wave, uint32_t lane, uint32_t wv) {
+    uint32_t incl = nbits;
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(incl, off); if ((int)lane >= off) incl += t; }
+    if (lane == 63u) s_wave[wv] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    for (uint32_t q = 0; q < wv; ++q) before += s_wave[q];
+    return before + incl - nbits;
+}
+// One lane: the end-of-block code c, the last bits of a stream of total_bits.  No barrier: one before the stream is read
+__device__ __forceinline__ void bz_put_eob(uint32_t* s_out, uint32_t c, uint32_t total_bits) {
+    BzBits z; z.start(s_out, total_bits - (c >> 16)); z.code(c); z.flush();
+}
+// The member into its slot o: the 18 bytes of header, the stream of total_bits in s_out (huff) or the stored block of s_in, CRC-32,
+// ISIZE.  Returns BSIZE.  No barrier: the stream is complete before, and s_in and s_out are still being read behind it
+__device__ __forceinline__ uint32_t bz_write_member(uint8_t* __restrict__ o, bool huff, uint32_t total_bits, uint32_t len, const uint32_t* s_out, const uint8_t* s_in,
+                                                    uint32_t crc_all, uint32_t tid) {
     const uint32_t body = huff ? (total_bits + 7u) >> 3 : len + 5u;
     const uint32_t bsize = 18u + body + 8u;
-    uint8_t* const o = slots + (size_t)blockIdx.x * BZ_SLOT;
     if (tid < 18u) {
         const uint32_t bs1 = bsize - 1u;
         const uint8_t hd[18] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)(bs1 & 255u), (uint8_t)(bs1 >> 8) };
@@ -208,6 +214,55 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate(const uint8_t* __restrict_
         for (uint32_t i = tid; i < len; i += 256u) o[23u + i] = s_in[i];
     }
     if (tid < 8u) { const uint32_t v = tid < 4u ? crc_all : len; o[18u + body + tid] = (uint8_t)(v >> (8u * (tid & 3u))); }
+    return bsize;
+}
+
+__global__ void __launch_bounds__(256) k_bgzf_deflate(const uint8_t* __restrict__ in, unsigned long long n, int level, uint8_t* __restrict__ slots,
+                                                      uint32_t* __restrict__ sizes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+    uint8_t* const s_in = s_dyn;
+    uint32_t* const s_out = reinterpret_cast<uint32_t*>(s_dyn + BZ_PAYLOAD);
+    __shared__ uint32_t s_tab[256], s_hist[257], s_code[257], s_wt[514], s_wave[4], s_misc[4];
+    __shared__ uint16_t s_par[514], s_ord[257];
+    __shared__ uint8_t s_dep[514];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const unsigned long long p0 = (unsigned long long)blockIdx.x * BZ_PAYLOAD;
+    if (p0 >= n) return;
+    const uint32_t len = (uint32_t)(n - p0 < BZ_PAYLOAD ? n - p0 : BZ_PAYLOAD);
+    // ---- the payload into LDS, the CRC table, an empty histogram and bit stream ----
+    bz_load(in + p0, len, s_in, tid);
+    bz_crc_table(s_tab, tid);
+    for (uint32_t i = tid; i < 257u; i += 256u) s_hist[i] = i == 256u ? 1u : 0u;          // the end-of-block symbol occurs once
+    if (level == 1) for (uint32_t i = tid; i < BZ_OUT_WORDS; i += 256u) s_out[i] = 0;
+    __syncthreads();
+    const uint32_t crc_all = bz_crc_hist(s_in, len, s_tab, level == 1, s_hist, s_wave, tid);
+    bool huff = false;
+    uint32_t total_bits = 0;
+    if (level == 1) {
+        bz_rank(s_hist, 257u, s_ord, tid);
+        for (uint32_t s = tid; s < 257u; s += 256u) s_code[s] = 0;
+        __syncthreads();
+        if (tid == 0) {                              // the code, the block's bits and its header in one stretch
+            const uint32_t bits = BZ_HDR_BITS + bz_build_code(s_hist, 257u, s_ord, s_wt, s_par, s_dep, s_code);
+            const bool use = (bits + 7u) / 8u < len + 5u;                                 // not smaller than stored: stored
+            s_misc[0] = use ? 1u : 0u; s_misc[1] = bits;
+            if (use) bz_put_block_header(s_out, s_code, 257u, nullptr, 1u);
+        }
+        __syncthreads();
+        huff = s_misc[0] != 0; total_bits = s_misc[1];
+        if (huff) {
+            // ---- every lane's bit count, their prefix sum, and the lane's codes ORed into the stream behind the header ----
+            uint32_t a, e, nbits = 0;
+            bz_run(len, tid, &a, &e);
+            for (uint32_t i = a; i < e; ++i) nbits += s_code[s_in[i]] >> 16;
+            BzBits w; w.start(s_out, BZ_HDR_BITS + bz_lane_start(nbits, s_wave, lane, wv));
+            for (uint32_t i = a; i < e; ++i) w.code(s_code[s_in[i]]);
+            w.flush();
+            if (tid == 0) bz_put_eob(s_out, s_code[256], total_bits);
+            __syncthreads();
+        }
+    }
+    const uint32_t bsize = bz_write_member(slots + (size_t)blockIdx.x * BZ_SLOT, huff, total_bits, len, s_out, s_in, crc_all, tid);
     if (tid == 0) sizes[blockIdx.x] = bsize;
 }
 
@@ -217,7 +272,6 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate(const uint8_t* __restrict_
 constexpr uint32_t LZ_HEAD = 8192;                  // entries of the hash table; it lies where the bit stream is built afterwards
 constexpr uint32_t LZ_MIN = 4, LZ_MAX = 258, LZ_WINDOW = 32768;
 constexpr uint32_t LZ_NL = 286, LZ_ND = 30;         // literal/length and distance symbols
-constexpr uint32_t LZ_FIX_BITS = 3 + 5 + 5 + 4 + 19 * 3;     // BFINAL, BTYPE, HLIT, HDIST, HCLEN, the code-length code
 constexpr uint32_t LZ_MATCH = 0x80000000u;          // a token: a literal's byte, or LZ_MATCH | (length - 3) << 16 | (distance - 1)
 
 // the four bytes at byte q of an array of words (LDS takes no unaligned word); reads the word behind q's as well
@@ -238,59 +292,10 @@ __device__ __forceinline__ uint32_t lz_dist_sym(uint32_t x, uint32_t* nx, uint32
 __device__ __forceinline__ uint32_t lz_len_extra(uint32_t i) { return i < 8u || i == 28u ? 0u : (i >> 2) - 1u; }      // of length symbol 257 + i
 __device__ __forceinline__ uint32_t lz_dist_extra(uint32_t d) { return d < 4u ? 0u : (d >> 1) - 1u; }
 
-// every symbol in use finds its rank in ascending (count, symbol) order: ord[rank] = symbol.  All lanes; a barrier before ord is read
-__device__ __forceinline__ void lz_rank(const uint32_t* hist, uint32_t nsym, uint16_t* ord, uint32_t tid) {
-    for (uint32_t s = tid; s < nsym; s += 256u) {
-        const uint32_t c = hist[s];
-        if (!c) continue;
-        uint32_t rank = 0;
-        for (uint32_t q = 0; q < nsym; ++q) { const uint32_t cq = hist[q]; rank += (cq && (cq < c || (cq == c && q < s))) ? 1u : 0u; }
-        ord[rank] = (uint16_t)s;
-    }
-}
-// One lane: the code of the symbols in use, as k_bgzf_deflate builds its own - Huffman's algorithm on the sorted leaves, flatter counts
-// and again while a leaf lies deeper than 15, canonical codes kept bit-reversed - into code[] (length << 16 | code; zero beforehand).
-// One symbol in use takes the one-bit code 0.  wt, par, dep: 2 * nsym entries each
-__device__ void lz_build_code(const uint32_t* hist, uint32_t nsym, const uint16_t* ord, uint32_t* wt, uint16_t* par, uint8_t* dep, uint32_t* code) {
-    uint32_t m = 0;
-    for (uint32_t s = 0; s < nsym; ++s) m += hist[s] ? 1u : 0u;
-    if (m == 0) return;
-    if (m == 1) { code[ord[0]] = 1u << 16; return; }
-    for (uint32_t i = 0; i < m; ++i) wt[i] = hist[ord[i]];
-    for (;;) {
-        uint32_t li = 0, ni = m, nn = m;
-        while (nn < 2u * m - 1u) {
-            uint32_t pick[2];
-            for (int k = 0; k < 2; ++k) pick[k] = (li < m && (ni >= nn || wt[li] <= wt[ni])) ? li++ : ni++;
-            wt[nn] = wt[pick[0]] + wt[pick[1]];
-            par[pick[0]] = par[pick[1]] = (uint16_t)nn;
-            ++nn;
-        }
-        dep[2u * m - 2u] = 0;
-        uint32_t deepest = 0;
-        for (uint32_t i = 2u * m - 2u; i-- > 0;) {
-            const uint32_t d = (uint32_t)dep[par[i]] + 1u;
-            dep[i] = (uint8_t)(d < 255u ? d : 255u);
-            if (i < m && d > deepest) deepest = d;
-        }
-        if (deepest <= 15u) break;
-        for (uint32_t i = 0; i < m; ++i) wt[i] = (wt[i] + 1u) >> 1;
-    }
-    uint32_t cnt[16], next[16];
-    for (int k = 0; k < 16; ++k) cnt[k] = 0;
-    for (uint32_t i = 0; i < m; ++i) { ++cnt[dep[i]]; code[ord[i]] = (uint32_t)dep[i] << 16; }
-    uint32_t c = 0;
-    next[0] = 0;
-    for (int k = 1; k < 16; ++k) { c = (c + cnt[k - 1]) << 1; next[k] = c; }
-    for (uint32_t s = 0; s < nsym; ++s) {
-        const uint32_t l = code[s] >> 16;
-        if (l) code[s] = (l << 16) | (__brev(next[l]++) >> (32u - l));
-    }
-}
 
 // A persistent grid: workgroup g takes payloads g, g + gridDim.x, ... and keeps their tokens in its own tokens[g * BZ_PAYLOAD ...).
 // Per payload:
-//   1. the payload into LDS, its CRC-32 and the histogram of its bytes, as k_bgzf_deflate does
+//   1. the payload into LDS, its CRC-32 and the histogram of its bytes
 //   2. the matches, in tiles of 256 positions, one per lane: the lane's candidate is head[hash of its 4 bytes] - the largest position of
 //      an EARLIER tile with that hash, put there with atomicMax behind a barrier, so what a lane finds does not depend on timing -,
 //      compared forward byte for byte (up to 258, never past the payload's end); a match counts from 4 bytes and within 32768.  The
@@ -313,46 +318,19 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate_lz(const uint8_t* __restri
     __shared__ uint8_t s_dep[2 * NS], s_mark[256];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
     uint32_t* const tk = tokens + (size_t)blockIdx.x * BZ_PAYLOAD;
-    {
-        uint32_t c = tid;
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? BZ_POLY ^ (c >> 1) : c >> 1;
-        s_tab[tid] = c;
-    }
+    bz_crc_table(s_tab, tid);
     for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
         const unsigned long long p0 = (unsigned long long)blk * BZ_PAYLOAD;
         const uint32_t len = (uint32_t)(n - p0 < BZ_PAYLOAD ? n - p0 : BZ_PAYLOAD);
-        const uint8_t* const src = in + p0;
         // ---- 1. the payload into LDS; empty histograms and hash table ----
-        if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
-            const uint32_t n16 = len >> 4;
-            for (uint32_t q = tid; q < n16; q += 256u) reinterpret_cast<uint4*>(s_in)[q] = reinterpret_cast<const uint4*>(src)[q];
-            for (uint32_t i = (n16 << 4) + tid; i < len; i += 256u) s_in[i] = src[i];
-        } else
-            for (uint32_t i = tid; i < len; i += 256u) s_in[i] = src[i];
+        bz_load(in + p0, len, s_in, tid);
         for (uint32_t i = tid; i < LZ_NL; i += 256u) { s_lhist[i] = i == 256u ? 1u : 0u; s_lcode[i] = 0; }
         if (tid < LZ_ND) { s_dhist[tid] = 0; s_dcode[tid] = 0; }
         for (uint32_t i = tid; i < 257u; i += 256u) { s_bhist[i] = i == 256u ? 1u : 0u; s_bcode[i] = 0; }
         for (uint32_t i = tid; i < LZ_HEAD; i += 256u) s_head[i] = 0;
         if (tid == 0) s_misc[0] = 0;
         __syncthreads();
-        const uint32_t chunk = (len + 255u) >> 8;
-        uint32_t crc_all;
-        {
-            const uint32_t a = tid * chunk < len ? tid * chunk : len, e = a + chunk < len ? a + chunk : len;
-            uint32_t crc = 0xFFFFFFFFu;
-            for (uint32_t i = a; i < e; ++i) {
-                const uint32_t by = s_in[i];
-                crc = s_tab[(crc ^ by) & 255u] ^ (crc >> 8);
-                atomicAdd(&s_bhist[by], 1u);
-            }
-            crc ^= 0xFFFFFFFFu;
-            uint32_t part = a < e ? bz_mul(bz_xpow8(len - e), crc) : 0u;
-            for (int off = 32; off; off >>= 1) part ^= __shfl_xor(part, off);
-            if (lane == 0) s_wave[wv] = part;
-            __syncthreads();
-            crc_all = s_wave[0] ^ s_wave[1] ^ s_wave[2] ^ s_wave[3];
-            __syncthreads();
-        }
+        const uint32_t crc_all = bz_crc_hist(s_in, len, s_tab, true, s_bhist, s_wave, tid);
         // ---- 2. the matches and the tokens, tile by tile ----
         uint32_t n_tok = 0;
         for (uint32_t tb = 0; tb < len; tb += 256u) {
@@ -421,13 +399,13 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate_lz(const uint8_t* __restri
         }
         // ---- 3. the codes: literal/length and distance over the tokens, and the literal code of level 1 over the bytes ----
         for (uint32_t i = tid; i < BZ_OUT_WORDS; i += 256u) s_out[i] = 0;
-        lz_rank(s_lhist, LZ_NL, s_ord, tid);
-        lz_rank(s_dhist, LZ_ND, s_ord + LZ_NL, tid);
-        lz_rank(s_bhist, 257u, s_ord + LZ_NL + LZ_ND, tid);
+        bz_rank(s_lhist, LZ_NL, s_ord, tid);
+        bz_rank(s_dhist, LZ_ND, s_ord + LZ_NL, tid);
+        bz_rank(s_bhist, 257u, s_ord + LZ_NL + LZ_ND, tid);
         __syncthreads();
-        if (tid == 0) lz_build_code(s_lhist, LZ_NL, s_ord, s_wt, s_par, s_dep, s_lcode);
-        if (tid == 64u) lz_build_code(s_dhist, LZ_ND, s_ord + LZ_NL, s_wt + 2 * LZ_NL, s_par + 2 * LZ_NL, s_dep + 2 * LZ_NL, s_dcode);
-        if (tid == 128u) lz_build_code(s_bhist, 257u, s_ord + LZ_NL + LZ_ND, s_wt + 2 * (LZ_NL + LZ_ND), s_par + 2 * (LZ_NL + LZ_ND), s_dep + 2 * (LZ_NL + LZ_ND), s_bcode);
+        if (tid == 0) bz_build_code(s_lhist, LZ_NL, s_ord, s_wt, s_par, s_dep, s_lcode);
+        if (tid == 64u) bz_build_code(s_dhist, LZ_ND, s_ord + LZ_NL, s_wt + 2 * LZ_NL, s_par + 2 * LZ_NL, s_dep + 2 * LZ_NL, s_dcode);
+        if (tid == 128u) bz_build_code(s_bhist, 257u, s_ord + LZ_NL + LZ_ND, s_wt + 2 * (LZ_NL + LZ_ND), s_par + 2 * (LZ_NL + LZ_ND), s_dep + 2 * (LZ_NL + LZ_ND), s_bcode);
         __syncthreads();
         if (tid == 0) {
             uint32_t nl = 257, nd = 1;
@@ -445,7 +423,7 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate_lz(const uint8_t* __restri
                 bits += (unsigned long long)c * ((s_dcode[d] >> 16) + lz_dist_extra(d));
             }
             for (uint32_t s = 0; s < 257u; ++s) plain += (unsigned long long)s_bhist[s] * (s_bcode[s] >> 16);
-            uint32_t hdr = LZ_FIX_BITS + 4u * (nl + nd);
+            uint32_t hdr = BZ_FIX_BITS + 4u * (nl + nd);
             bits += hdr;
             // the smallest of three: the matched form, level 1's block over the bytes (short far matches can cost more than their
             // literals), the stored block.  Ties go to the simpler form
@@ -453,18 +431,7 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate_lz(const uint8_t* __restri
             if (!matched) { bits = plain; hdr = BZ_HDR_BITS; nl = 257; nd = 1; }
             const bool use = (bits + 7u) / 8u < (unsigned long long)len + 5u;
             s_misc[1] = use ? (matched ? 1u : 2u) : 0u; s_misc[2] = (uint32_t)bits; s_misc[3] = hdr;
-            if (use) {
-                const uint32_t* const lc = matched ? s_lcode : s_bcode;
-                BzBits w; w.start(s_out, 0);
-                w.put(1u, 1); w.put(2u, 2); w.put(nl - 257u, 5); w.put(nd - 1u, 5); w.put(15u, 4);
-                for (int k = 0; k < 19; ++k) w.put(k < 3 ? 0u : 4u, 3);                 // as k_bgzf_deflate: four bits per length, no run-length symbols
-                for (uint32_t s = 0; s < nl; ++s) w.put(__brev(lc[s] >> 16) >> 28, 4);
-                if (matched && s_dcode[nd - 1u])
-                    for (uint32_t d = 0; d < nd; ++d) w.put(__brev(s_dcode[d] >> 16) >> 28, 4);
-                else
-                    w.put(__brev(1u) >> 28, 4);      // no match: one distance code of length 1, never used
-                w.flush();
-            }
+            if (use) bz_put_block_header(s_out, matched ? s_lcode : s_bcode, nl, matched ? s_dcode : nullptr, nd);
         }
         __syncthreads();
         const bool huff = s_misc[1] != 0, matched = s_misc[1] == 1u;
@@ -472,9 +439,8 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate_lz(const uint8_t* __restri
         if (huff) {
             // ---- 4. every lane's tokens (or, in level 1's form, bytes) into the stream behind the header ----
             const uint32_t* const lc = matched ? s_lcode : s_bcode;
-            const uint32_t n_sym = matched ? n_tok : len, per = (n_sym + 255u) >> 8;
-            const uint32_t a = tid * per < n_sym ? tid * per : n_sym, e = a + per < n_sym ? a + per : n_sym;
-            uint32_t nbits = 0;
+            uint32_t a, e, nbits = 0;
+            bz_run(matched ? n_tok : len, tid, &a, &e);
             for (uint32_t i = a; i < e; ++i) {
                 const uint32_t t = matched ? tk[i] : s_in[i];
                 if (t & LZ_MATCH) {
@@ -485,51 +451,21 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate_lz(const uint8_t* __restri
                 } else
                     nbits += lc[t] >> 16;
             }
-            uint32_t incl = nbits;
-            for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(incl, off); if ((int)lane >= off) incl += t; }
-            if (lane == 63u) s_wave[wv] = incl;
-            __syncthreads();
-            uint32_t before = 0;
-            for (uint32_t q = 0; q < wv; ++q) before += s_wave[q];
-            BzBits w; w.start(s_out, s_misc[3] + before + incl - nbits);
+            BzBits w; w.start(s_out, s_misc[3] + bz_lane_start(nbits, s_wave, lane, wv));
             for (uint32_t i = a; i < e; ++i) {
                 const uint32_t t = matched ? tk[i] : s_in[i];
                 if (t & LZ_MATCH) {
                     uint32_t nx, xv;
-                    uint32_t c = lc[257u + lz_len_sym((t >> 16) & 255u, &nx, &xv)];
-                    w.put(c & 0xFFFFu, c >> 16); w.put(xv, nx);
-                    c = s_dcode[lz_dist_sym(t & 0x7FFFu, &nx, &xv)];
-                    w.put(c & 0xFFFFu, c >> 16); w.put(xv, nx);
-                } else {
-                    const uint32_t c = lc[t];
-                    w.put(c & 0xFFFFu, c >> 16);
-                }
+                    w.code(lc[257u + lz_len_sym((t >> 16) & 255u, &nx, &xv)]); w.put(xv, nx);
+                    w.code(s_dcode[lz_dist_sym(t & 0x7FFFu, &nx, &xv)]); w.put(xv, nx);
+                } else
+                    w.code(lc[t]);
             }
             w.flush();
-            if (tid == 0) { const uint32_t c = lc[256]; BzBits z; z.start(s_out, total_bits - (c >> 16)); z.put(c & 0xFFFFu, c >> 16); z.flush(); }
+            if (tid == 0) bz_put_eob(s_out, lc[256], total_bits);
             __syncthreads();
         }
-        // ---- the block into its slot: header, deflate stream, CRC-32, ISIZE ----
-        const uint32_t body = huff ? (total_bits + 7u) >> 3 : len + 5u;
-        const uint32_t bsize = 18u + body + 8u;
-        uint8_t* const o = slots + (size_t)blk * BZ_SLOT;
-        if (tid < 18u) {
-            const uint32_t bs1 = bsize - 1u;
-            const uint8_t hd[18] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)(bs1 & 255u), (uint8_t)(bs1 >> 8) };
-            o[tid] = hd[tid];
-        }
-        if (huff) {
-            const uint8_t* const sb = reinterpret_cast<const uint8_t*>(s_out);
-            for (uint32_t i = tid; i < body; i += 256u) o[18u + i] = sb[i];
-        } else {
-            if (tid < 5u) {
-                const uint32_t nl = ~len & 0xFFFFu;
-                const uint8_t sh[5] = { 1, (uint8_t)(len & 255u), (uint8_t)(len >> 8), (uint8_t)(nl & 255u), (uint8_t)(nl >> 8) };
-                o[18u + tid] = sh[tid];
-            }
-            for (uint32_t i = tid; i < len; i += 256u) o[23u + i] = s_in[i];
-        }
-        if (tid < 8u) { const uint32_t v = tid < 4u ? crc_all : len; o[18u + body + tid] = (uint8_t)(v >> (8u * (tid & 3u))); }
+        const uint32_t bsize = bz_write_member(slots + (size_t)blk * BZ_SLOT, huff, total_bits, len, s_out, s_in, crc_all, tid);
         if (tid == 0) sizes[blk] = bsize;
         __syncthreads();                              // the payload and the stream are read: the next payload may overwrite them
     }
@@ -553,15 +489,6 @@ __global__ void __launch_bounds__(256) k_bgzf_compact(const uint8_t* __restrict_
 // BAM records
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool bm_op(char c) { return c == 'M' || c == 'I' || c == 'D'; } // all k_out_write ever puts into the pool
-__device__ __forceinline__ char bm_comp_char(char c) {                                      // as go_comp_char (gm_output.hip)
-    const char lo = (char)(c | 0x20);
-    const char up = (char)(c == lo ? 0 : 0x20);
-    switch (lo) {
-        case 'a': return (char)('t' - up); case 't': return (char)('a' - up);
-        case 'c': return (char)('g' - up); case 'g': return (char)('c' - up);
-        default: return c == '-' ? '-' : 'n';
-    }
-}
 // "=ACMGRSVTWYHKDBN", either case; anything else is N
 __device__ __forceinline__ uint32_t bm_nibble(char c) {
     switch (c & ~0x20) {
@@ -569,16 +496,6 @@ __device__ __forceinline__ uint32_t bm_nibble(char c) {
         case 'T': return 8; case 'W': return 9; case 'Y': return 10; case 'H': return 11; case 'K': return 12; case 'D': return 13; case 'B': return 14;
         default: return c == '=' ? 0u : 15u;
     }
-}
-// SAMv1 section 5.3
-__device__ __forceinline__ uint32_t bm_reg2bin(long long beg, long long end) {
-    --end;
-    if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
-    return 0;
 }
 __device__ __forceinline__ uint32_t bm_name_len(const GmDevText& t, uint32_t rd) {
     const unsigned long long nl = t.name_off[rd + 1] - t.name_off[rd];
@@ -603,7 +520,7 @@ __global__ void __launch_bounds__(256) k_bam_sizes(GmDevText t, uint32_t* __rest
     const long long pos0 = (long long)(int32_t)(uint32_t)(r.chr_pos - 1ull);
     const uint32_t L = t.seq_len[r.read];
     meta[2ull * k] = n_ops;
-    meta[2ull * k + 1ull] = bm_reg2bin(pos0, pos0 + (long long)ref_len);
+    meta[2ull * k + 1ull] = gm_reg2bin(pos0, pos0 + (long long)ref_len);
     t.row_len[k] = 4u + 32u + bm_name_len(t, r.read) + 1u + 4u * n_ops + ((L + 1u) >> 1) + L + 21u;
 }
 
@@ -679,9 +596,9 @@ __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, con
             const uint32_t half = (L + 1u) >> 1;
             for (uint32_t i = lane; i < half; i += 64u) {
                 const uint32_t j0 = 2u * i, j1 = j0 + 1u;
-                const char c0 = neg ? bm_comp_char((char)bs[L - 1u - j0]) : (char)bs[j0];
+                const char c0 = neg ? gm_comp_char((char)bs[L - 1u - j0]) : (char)bs[j0];
                 uint32_t v = bm_nibble(c0) << 4;
-                if (j1 < L) v |= bm_nibble(neg ? bm_comp_char((char)bs[L - 1u - j1]) : (char)bs[j1]);
+                if (j1 < L) v |= bm_nibble(neg ? gm_comp_char((char)bs[L - 1u - j1]) : (char)bs[j1]);
                 if (o + i < end) out[o + i] = (uint8_t)v;
             }
             o += half;

@@ -1,6 +1,7 @@
 // gm_fmt_dev.h — exact printf("%g") and printf("%.2e") that compile for the host and for the device: the XA / XP columns of a SAM row
 // (src/Driver.cpp:2196-2205) written by k_out_text_sizes (gm_output.hip), and the p-value of --snp's ninth .gmp column
 // (PrintSNPCall src/GenomeBwt.cpp:1011-1090) written by k_track_rows (gm_tracktext.hip).  No library calls, no division of wide integers.
+// Also gm_comp_char, the complement of a base as a reverse-strand row prints it (gm_output.hip, gm_bam.hip).
 //
 // Domain of gm_put_g6_hd: 0, -0, inf, nan and every double with 2^-200 <= |v| < 2^200 (every float, denormals included, times any
 // sensible 1 / adjust); of gm_put_e2_hd: +0.0 and 2^-200 <= v < 2^200 (a p-value).  Outside it they write nothing and return their
@@ -20,6 +21,18 @@
 #else
 #define GM_FMT_HD
 #endif
+
+// reverse_comp's table (SequenceOperations.h:56-96): a<->t, c<->g in both cases, '-' stays, everything else 'n'.  The bases of a
+// reverse-strand row, as text (k_out_text_rows, gm_output.hip) and as BAM nibbles (k_bam_rows, gm_bam.hip)
+GM_FMT_HD static inline char gm_comp_char(char c) {
+    const char lo = (char)(c | 0x20);
+    const char up = (char)(c == lo ? 0 : 0x20);            // subtracted again for an upper-case letter
+    switch (lo) {
+        case 'a': return (char)('t' - up); case 't': return (char)('a' - up);
+        case 'c': return (char)('g' - up); case 'g': return (char)('c' - up);
+        default: return c == '-' ? '-' : 'n';
+    }
+}
 
 struct gm_u256 { uint64_t w0, w1, w2, w3; };             // little endian; named words, never indexed (no scratch on the device)
 

@@ -93,6 +93,17 @@ void gm_samsort_release(gm_sam_sorter* s, uint64_t seq);     // the claim back, 
 int gm_samsort_add(gm_sam_sorter* s, uint64_t seq, const GmDevSamRec* recs, uint64_t n_rows, const char* d_text, const uint64_t* d_rowoff, uint64_t text_len, void* stream);
 int gm_samsort_rows(gm_sam_sorter* s);                       // GM_ROWS_TEXT / GM_ROWS_BAM: what the blocks put into the arena
 
+// gm_bam.hip and gm_bai.hip share these two.  The bytes of input per BGZF block, and the bin of [beg, end) (SAMv1 section 5.3)
+constexpr uint32_t GM_BGZF_PAYLOAD = 65280;
+__host__ __device__ inline uint32_t gm_reg2bin(long long beg, long long end) {
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
 // gm_bam.hip.  The record kernels run behind gmk_out_text_sizes on the same GmDevText: sizes overwrites row_len with the records' sizes
 // and leaves (operations, bin) per record in meta; rows writes the records at row_off into t.text.
 int gmk_bam_sizes(const GmDevText& t, uint32_t* meta, void* stream);

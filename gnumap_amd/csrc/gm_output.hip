@@ -668,16 +668,6 @@ __device__ __forceinline__ char* go_put_int(char* w, int32_t v) {
     return go_put_u64(w, (unsigned long long)v);
 }
 __device__ __forceinline__ bool go_cigar_digit(char c) { return c >= 48 && c <= 58; }      // ':' counts as a digit, SequenceOperations.h:109-123
-// reverse_comp's table (SequenceOperations.h:56-96): a<->t, c<->g in both cases, '-' stays, everything else 'n'
-__device__ __forceinline__ char go_comp_char(char c) {
-    const char lo = (char)(c | 0x20);
-    const char up = (char)(c == lo ? 0 : 0x20);            // subtracted again for an upper-case letter
-    switch (lo) {
-        case 'a': return (char)('t' - up); case 't': return (char)('a' - up);
-        case 'c': return (char)('g' - up); case 'g': return (char)('c' - up);
-        default: return c == '-' ? '-' : 'n';
-    }
-}
 
 // one lane per record: the numeric tail into the record's slot (through LDS, so that the slots leave as whole 16-byte stores) and
 // the length of the row
@@ -790,7 +780,7 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
             o += 7u;
             const uint8_t* bs = b.bases + (size_t)rd * b.stride; const uint8_t* qs = b.quals + (size_t)rd * b.stride;
             if (!neg) { for (uint32_t i = lane; i < L; i += 64u) if (o + i < end) out[o + i] = (char)bs[i]; }
-            else { for (uint32_t i = lane; i < L; i += 64u) if (o + i < end) out[o + i] = go_comp_char((char)bs[L - 1u - i]); }
+            else { for (uint32_t i = lane; i < L; i += 64u) if (o + i < end) out[o + i] = gm_comp_char((char)bs[L - 1u - i]); }
             o += L;
             if (lane == 0 && o < end) out[o] = '\t';
             o += 1u;

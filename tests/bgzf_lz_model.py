@@ -7,6 +7,7 @@ tokens(payload)  the greedy parse: [byte | (length, distance)].  Tiles of 256 po
 member(payload)  the BGZF member: one dynamic-Huffman block over the tokens (both codes by Huffman's algorithm on the sorted counts,
                  halved until no code is longer than 15 bits; code lengths sent as 4 bits each), or level 1's block over the bytes
                  where that is not larger, or a stored block where that is not larger
+matches=False    (deflate, member, compress) what k_bgzf_deflate writes at level 1: the block over the bytes, or the stored block
 """
 import struct
 import zlib
@@ -54,7 +55,7 @@ def tokens(d):
 
 
 def _code(hist):
-    """{symbol: (length, code as sent, first bit lowest)} as lz_build_code makes it"""
+    """{symbol: (length, code as sent, first bit lowest)} as bz_build_code makes it"""
     order = sorted((c, s) for s, c in enumerate(hist) if c)
     m = len(order)
     if m == 0:
@@ -123,9 +124,10 @@ def _header(w, lc, dc):
         w.put(rev4(1), 4)
 
 
-def deflate(d):
-    """the raw deflate stream of one payload: the smallest of the matched form, level 1's block over the bytes, and the stored block"""
-    toks = tokens(d)
+def deflate(d, matches=True):
+    """the raw deflate stream of one payload: the smallest of the matched form, level 1's block over the bytes, and the stored block.
+    matches=False: what k_bgzf_deflate writes at level 1 - the block over the bytes, or the stored block where that is not larger"""
+    toks = tokens(d) if matches else []
     lh, dh, bh = [0] * 286, [0] * 30, [0] * 257
     lh[256] = bh[256] = 1
     for t in toks:
@@ -150,7 +152,7 @@ def deflate(d):
     for b in d:
         plain.put(bc[b][1], bc[b][0])
     plain.put(bc[256][1], bc[256][0])
-    if plain.n <= w.n:                                       # ties go to the simpler form
+    if not matches or plain.n <= w.n:                        # ties go to the simpler form
         w = plain
     body = w.bytes()
     if len(body) >= len(d) + 5:
@@ -158,10 +160,10 @@ def deflate(d):
     return body
 
 
-def member(d):
-    body = deflate(d)
+def member(d, matches=True):
+    body = deflate(d, matches)
     return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(body) + 25) + body + struct.pack("<II", zlib.crc32(d), len(d)))
 
 
-def compress(data):
-    return b"".join(member(data[at:at + PAYLOAD]) for at in range(0, len(data), PAYLOAD))
+def compress(data, matches=True):
+    return b"".join(member(data[at:at + PAYLOAD], matches) for at in range(0, len(data), PAYLOAD))

@@ -144,11 +144,15 @@ def test_model_refuses(case):
                 raise zlib.error("the stream ends early")
 
 
-def test_restated_kernel_writes_valid_members_with_the_tokens_it_found(payloads):
-    """tests/bgzf_lz_model.py is what the GPU tests hold the device's bytes against: here it is held against zlib and the token model"""
+def model_cases(payloads):
     rng = np.random.default_rng(9)
     rep = rng.integers(0, 256, 300, dtype=np.uint8).tobytes()
-    cases = [b"a", b"abcabc", bytes(5000), (rep * 30)[:7000], payloads["records"], payloads["random"][:3000]]
+    return [b"a", b"abcabc", bytes(5000), (rep * 30)[:7000], payloads["records"], payloads["random"][:3000]]
+
+
+def test_restated_kernel_writes_valid_members_with_the_tokens_it_found(payloads):
+    """tests/bgzf_lz_model.py is what the GPU tests hold the device's bytes against: here it is held against zlib and the token model"""
+    cases = model_cases(payloads)
     for data in cases:
         z = lzm.compress(data)
         (payload, btype, size), = bm.parse_bgzf(z)
@@ -162,6 +166,26 @@ def test_restated_kernel_writes_valid_members_with_the_tokens_it_found(payloads)
     z1 = len(c.compress(payloads["records"]) + c.flush())
     huff = bm.zlib_huffman_only(payloads["records"])
     assert sizes[bm.PAYLOAD] - 26 <= (huff + z1) // 2, (sizes[bm.PAYLOAD], huff, z1)
+
+
+def test_restated_level_1_writes_literal_blocks_or_stored_ones(payloads):
+    """matches=False is k_bgzf_deflate at level 1 (tests/test_gpu_bgzf.py holds the device's bytes against it): one block over the bytes
+    alone, never larger than stored, and the very block the matched form falls back to where matches do not pay"""
+    for data in model_cases(payloads):
+        z = lzm.compress(data, matches=False)
+        (payload, btype, size), = bm.parse_bgzf(z)
+        assert payload == data and size == len(z) and size <= len(data) + 31
+        assert zlib.decompress(z[18:-8], -15) == data
+        if btype != 0:
+            r = dm.inflate(z[18:-8])
+            assert r.out == data and r.tokens == [("L", b) for b in data]
+            assert [(b["btype"], b["hlit"], b["hdist"]) for b in r.blocks] == [(2, 257, 1)]
+        zm = lzm.compress(data)
+        bl = dm.inflate(zm[18:-8]).blocks
+        if bl[0].get("hlit") == 257:
+            assert zm == z, len(data)
+    assert len(lzm.compress(b"a", matches=False)) == 32                     # stored
+    assert lzm.compress(payloads["records"], matches=False) != lzm.compress(payloads["records"])      # (the matched form does find matches there)
 
 
 def test_level_word_on_a_host_only_index(syn_fa):

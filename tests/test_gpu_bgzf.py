@@ -1,18 +1,21 @@
 """BGZF on the device (k_bgzf_deflate / k_bgzf_compact, gm_bam.hip) through gm_bgzf_compress, on bytes of the test's own: every output is
 walked member by member by tests/bam_model.parse_bgzf (magic, BC subfield, BSIZE, raw inflate up to the trailer, CRC-32, ISIZE), has to
-inflate to the input, and has to come out the same twice.
+inflate to the input, has to come out the same twice, and has to equal byte for byte what tests/bgzf_lz_model.py writes without matches.
 
 Sizes around the payload cut (65280), a payload of one byte value, one that cannot be compressed (stored, and never larger than stored),
 Fibonacci histograms whose unlimited Huffman code is deeper than deflate's 15 bits, and BAM-like records, whose Huffman form is
 measured against zlib's Z_HUFFMAN_ONLY raw deflate of the same payloads."""
 import gzip
 import os
+import struct
+import zlib
 
 import numpy as np
 import pytest
 
 import gnumap_amd as g
 import bam_model as bm
+import bgzf_lz_model as lzm
 from conftest import GOLDEN, read_fastq
 from gnumap_amd import api
 
@@ -121,6 +124,19 @@ def test_block_types_at_level_1(inputs, outputs):
         assert len(outputs[k, 1]) < len(outputs[k, 0]), k
     assert len(outputs["one_value", 1]) < 18 + 8 + 140 + 5000 // 8 + 8         # one bit per byte behind the code lengths
     assert [b for _, b, _ in bm.parse_bgzf(outputs["size_1", 1])] == [0]      # a Huffman block cannot beat 6 bytes
+
+
+def test_level_1_bytes_equal_the_model(inputs, outputs):
+    """byte for byte: level 1 against tests/bgzf_lz_model.py without matches (the code builder, the header, the bit stream, the rule
+    for the stored block, CRC-32 and ISIZE), level 0 against stored members built here"""
+    for k, data in inputs.items():
+        assert outputs[k, 1] == lzm.compress(data, matches=False), k
+        stored = b""
+        for at in range(0, len(data), P):
+            d = data[at:at + P]
+            stored += (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(d) + 30) + b"\x01" + struct.pack("<HH", len(d), len(d) ^ 0xFFFF) + d +
+                       struct.pack("<II", zlib.crc32(d), len(d)))
+        assert outputs[k, 0] == stored, k
 
 
 def test_capacity_one_byte_short(ix, inputs, outputs):

@@ -10,7 +10,7 @@ What the matcher cannot reach and the tests therefore do n
 Two cases the tests do not have.  A source that is not 16-byte aligned: every caller of gm_bgzf_device passes the start of an allocation
 and payloads begin at multiples of 65280, so no entry point reaches the kernel's byte-wise load.  An input on which the 15-bit limit
 acts on a code of the matched form: with matches taken out, the Fibonacci inputs of tests/test_gpu_bgzf.py no longer give a code deeper
-than 15 (13 for the one used here); the limit itself is asserted, and the builder is level 1's, restated."""
+than 15 (13 for the one used here); the limit itself is asserted, and the builder (bz_build_code) is the one level 1 runs, where fib21_eob reaches the limit."""
 import ctypes as C
 import os
 import struct

@@ -5,9 +5,11 @@ beside a device-to-device copy of the same number of bytes, in one process; the 
 The reads of --reads, --copies times over under names of their own, are mapped as ONE block; gm_output_batch_bam then writes that block's
 records and compresses them, --iters times per form (level 0, level 1, level 1 with LZ77 matches) after one untimed call, with gm_batch_set_profiling on: HIP events around the record
 kernels and around the BGZF kernels (gm_batch_bam_times).  GB/s are bytes of records (the BGZF kernels' payload) per second of kernel
-time; the matched form's output is also put beside zlib's Z_HUFFMAN_ONLY and level 1 on the same payloads.  The yardstick is torch's copy of a tensor of the records' size into another one, timed with events."""
+time; every form's BGZF bytes are named by their SHA-256 (the bytes are a function of the input and the level: a digest to hold a
+change of the kernels against); the matched form's output is also put beside zlib's Z_HUFFMAN_ONLY and level 1 on the same payloads.  The yardstick is torch's copy of a tensor of the records' size into another one, timed with events."""
 import argparse
 import gzip
+import hashlib
 import os
 import sys
 import zlib
@@ -57,6 +59,7 @@ def main():
         print(f"level {level}{' + lz77' if lz77 else ''}: {batch.bam_n_recs} records, {raw} bytes -> {len(out)} bytes of BGZF ({100.0 * len(out) / raw:.1f} %)")
         print(f"  k_bam_sizes + k_bam_rows: {rows_ms:.3f} ms = {raw / rows_ms / 1e6:.1f} GB/s of records written")
         print(f"  k_bgzf_deflate{'_lz' if lz77 else ''} + scan + k_bgzf_compact: {bgzf_ms:.3f} ms = {raw / bgzf_ms / 1e6:.1f} GB/s of payload")
+        print(f"  sha256 of the BGZF bytes: {hashlib.sha256(out).hexdigest()}")
     payload = gzip.decompress(out)                                              # (the matched form's, the last one written)
     assert len(payload) == raw
     huff = z1 = 0
