@@ -119,7 +119,7 @@ SNP_DTYPE = np.dtype([("pos", "<u8"), ("contig", "<u4"), ("chr_pos", "<u8"), ("t
 # every symbol include/gnumap_hip.h declares
 EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_parallel", "gm_index_build", "gm_index_build_on", "gm_index_open", "gm_index_close", "gm_index_prepare", "gm_index_get_info", "gm_index_contig_name",
            "gm_index_contig_offset", "gm_index_window", "gm_params_default", "gm_params_finalize", "gm_params_load_subst", "gm_batch_create", "gm_batch_destroy",
-           "gm_batch_upload", "gm_map_batch_device", "gm_batch_counters", "gm_batch_path", "gm_batch_set_profiling", "gm_batch_kernel_times", "gm_kernel_name",
+           "gm_batch_upload", "gm_map_batch_device", "gm_batch_counters", "gm_batch_path", "gm_batch_pair_flagged", "gm_batch_set_profiling", "gm_batch_kernel_times", "gm_kernel_name",
            "gm_batch_raw_hits", "gm_stream_create", "gm_stream_destroy", "gm_host_alloc", "gm_host_free", "gm_map_batch", "gm_output_batch",
            "gm_output_batch_text", "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait", "gm_dev_fmt_g6", "gm_dev_fmt_e2",
            "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
@@ -170,6 +170,7 @@ def load_library():
     L.gm_map_batch_device.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.c_void_p]
     L.gm_batch_counters.argtypes = [C.c_void_p, C.POINTER(gm_counters)]
     L.gm_batch_path.argtypes = [C.c_void_p]; L.gm_batch_path.restype = C.c_char_p
+    L.gm_batch_pair_flagged.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.gm_map_batch_enqueue.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_reads), C.POINTER(gm_hits), C.c_void_p]
     L.gm_output_batch_enqueue.argtypes = [C.c_void_p, C.POINTER(gm_params), C.c_void_p, C.POINTER(gm_reads), C.POINTER(gm_hits), C.POINTER(gm_sam_out), C.c_void_p]
     L.gm_batch_wait.argtypes = [C.c_void_p]
@@ -690,6 +691,12 @@ class Batch:
     def path(self):
         """which kernels the last map_device / map chose"""
         return lib().gm_batch_path(self.h).decode()
+
+    def pair_flagged(self):
+        """reads that k_vote_pair left to k_vote_bucket in the last map_device / map (0 when it did not run)"""
+        n = C.c_uint32()
+        _chk(lib().gm_batch_pair_flagged(self.h, C.byref(n)))
+        return int(n.value)
 
     def set_profiling(self, on=True):
         _chk(lib().gm_batch_set_profiling(self.h, int(on)))

@@ -78,6 +78,7 @@ struct gm_batch {
     uint32_t epoch_ctr = 0;
     uint64_t stamp = 0;                 // names the gm_map_batch result resident in g_matches / g_positions (gm_hits::stamp); 0 = none
     std::string path;                   // which kernels the last gm_map_batch_device chose (gm_batch_path)
+    uint32_t pair_flagged = 0;          // reads k_vote_pair handed to the list in it (gm_batch_pair_flagged): pair_list[0] as the status words brought it
     // gm_*_enqueue / gm_batch_wait: the batch's own service thread runs the queued calls in order, the caller goes on
     struct Service {
         std::thread th; std::mutex mu; std::condition_variable cv;
@@ -977,6 +978,7 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     int rc = sync_params(ix, p, dp, st, true);
     if (rc) return rc;
     b->mapped = false;
+    b->pair_flagged = 0;
     if ((rc = fasta_forced_form(b)) != GM_OK) return rc;
     if (b->n == 0) { b->n_cands = 0; b->n_raw = 0; b->mapped = true; memset(b->counters_host, 0, sizeof b->counters_host); return GM_OK; }
     const int use_full = ix->full_sa ? 1 : 0;
@@ -1155,11 +1157,11 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     };
     // candidates per shard: total and maximum are reduced on the device (gmk_shard_stats -> small[4], small[5]) and come back with the status words
     auto read_status = [&](uint64_t& total, uint32_t& mx) -> int {
-        KCHK(gmk_shard_stats(b->dev, b->small.as<uint32_t>() + 4, st));
+        KCHK(gmk_shard_stats(b->dev, b->small.as<uint32_t>() + 4, use_pair ? b->pair_list.as<uint32_t>() : nullptr, st));
         HIPCHK(hipMemcpyAsync(hs_small, b->small.p, 64, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(hs_ctr, b->counters.p, GMK_N * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        total = hs_small[4]; mx = hs_small[5];
+        total = hs_small[4]; mx = hs_small[5]; b->pair_flagged = hs_small[6];
         return GM_OK;
     };
     auto read_shards = read_status;
@@ -1304,6 +1306,12 @@ extern "C" int gm_batch_counters(gm_batch* b, gm_counters* o) {
 }
 
 extern "C" const char* gm_batch_path(gm_batch* b) { return b ? b->path.c_str() : ""; }
+
+extern "C" int gm_batch_pair_flagged(gm_batch* b, uint32_t* flagged) {
+    if (!b || !flagged) return GM_E_ARG;
+    *flagged = b->pair_flagged;
+    return GM_OK;
+}
 
 extern "C" const char* gm_kernel_name(int which) {
     static const char* names[GM_K_COUNT] = { "k_prep", "k_seed", "k_locate_sampled", "k_vote", "k_vote_retry", "k_nw", "k_compact(scan+scatter)" };

@@ -260,7 +260,7 @@ int gmk_scan_entries(const GmDevBatch& b, void* stream);
 int gmk_locate_sampled(const GmDevIndex& ix, const GmDevBatch& b, unsigned long long n_entries /* SA hits of the block = entries of coords[] */, void* stream);
 int gmk_vote(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, int use_full_sa, int dense, int slots_hint, void* stream);
 int gmk_cand_gather(const GmDevBatch& b, void* stream);
-int gmk_shard_stats(const GmDevBatch& b, uint32_t* out /* {total, max} in device memory */, void* stream);
+int gmk_shard_stats(const GmDevBatch& b, uint32_t* out /* {total, max, *pair_n (0 without)} in device memory */, const uint32_t* pair_n, void* stream);
 // gm_bucket.hip: the bucket table and the one-wave-per-read vote kernel that looks its seeds up in it
 int gmk_build_bucket(const uint2* tab, const uint32_t* full_sa, const uint8_t* pac, uint4* bucket, int T, int ctx, void* stream);
 // rlist / n_rlist (device memory) != null: only the reads of that list

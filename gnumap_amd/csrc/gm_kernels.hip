@@ -2862,7 +2862,7 @@ __global__ void __launch_bounds__(256) k_cand_gather(GmDevBatch b) {
 
 // total and maximum of the candidate shards' fill counts, for the host's sizing decision: 8 bytes come back instead of the 128 KB the
 // counters are spread over (one 128-byte line each)
-__global__ void __launch_bounds__(256) k_shard_stats(GmDevBatch b, uint32_t* out /* {total, max} */) {
+__global__ void __launch_bounds__(256) k_shard_stats(GmDevBatch b, uint32_t* out /* {total, max, reads on k_vote_pair's list} */, const uint32_t* pair_n) {
     __shared__ uint32_t s_sum[4], s_max[4];
     uint32_t sum = 0, mx = 0;
     unsigned long long dropped = 0;                       // word 1 of a shard: k-mers tried and dropped by the walks of k_vote_bucket (taken out as they are summed)
@@ -2888,6 +2888,7 @@ __global__ void __launch_bounds__(256) k_shard_stats(GmDevBatch b, uint32_t* out
     if (threadIdx.x == 0) {
         out[0] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
         out[1] = std::max(std::max(s_max[0], s_max[1]), std::max(s_max[2], s_max[3]));
+        out[2] = pair_n ? *pair_n : 0u;                   // (rides home with the status words: gm_batch_pair_flagged)
     }
 }
 
@@ -3459,8 +3460,8 @@ int gmk_vote_list(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& 
     return (int)hipGetLastError();
 }
 
-int gmk_shard_stats(const GmDevBatch& b, uint32_t* out, void* stream) {
-    hipLaunchKernelGGL(k_shard_stats, dim3(1), dim3(256), 0, S_(stream), b, out);
+int gmk_shard_stats(const GmDevBatch& b, uint32_t* out, const uint32_t* pair_n, void* stream) {
+    hipLaunchKernelGGL(k_shard_stats, dim3(1), dim3(256), 0, S_(stream), b, out, pair_n);
     return (int)hipGetLastError();
 }
 

@@ -20,9 +20,15 @@
 // k_cand_gather chose it) and its flagged reads to the list, one returning atomic each, and the work counters of the reads it kept
 // are summed per workgroup into shard counter words 2 / 3 (k_shard_stats adds them up); k_heavy_collect then visits the list only.
 //
-// Votes as in k_vote_bucket: one returning LDS atomic per hit into a 16384-bit filter of its strand (slot = low bits of the window
-// start), a second arrival's window start goes to the strand's key list unless it is the strand's latest key, one sweep per distinct key
-// ORs the tag bits of the seeds that hold it: votes = popcount, NW step = its -k-th lowest bit (inc/align_seq2_raw.cpp:262-274,
+// Records: the 8 lanes of a seed fetch its whole 128-byte record in one request, lane 0 the header word, lanes 1 .. 7 the positions; the
+// headers of a strand are summed (hits) and ORed (flag bits) out of the lane-0 words, which take no part in the votes.
+//
+// Votes: one returning LDS atomic per hit into a 512-word filter of its strand.  The word is chosen by bits 5 .. 13 of the window start,
+// and a hit marks two of its bits: bit (b & 31) and bit ((b >> 14) & 31).  A hit that finds both marks set is a second arrival: its window
+// start goes to the strand's key list unless it is the strand's latest key.  (k_vote_bucket marks the first bit only: there two window
+// starts that agree in their low 14 bits always list a key, here only when they agree in bits 14 .. 18 as well or other hits of the
+// word have set the marks between them.)  One sweep per distinct key ORs the tag bits of the seeds that hold it, so a key listed for
+// nothing costs an iteration and finds one vote: votes = popcount, NW step = its -k-th lowest bit (inc/align_seq2_raw.cpp:262-274,
 // process_hits :28-40).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -90,7 +96,7 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
         }
     };
     // state of the pair whose records are in flight (N) / being voted on (C)
-    uint32_t N_hdr = 0, N_ns = 0; bool N_fb = false; uint4 N_rc[STEPS]; uint4 N_hd4 = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t N_hdr = 0, N_ns = 0; bool N_fb = false; uint4 N_rc[STEPS];
     // codes of the pair from its words (which must have been requested before), its record loads, and the request of the words two pairs on
     auto issue = [&](const uint32_t prn) {
         const int lane = gmp_lane_again();
@@ -108,17 +114,15 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
         const uint32_t ns_q = (uint32_t)__popc(gmp_qbits(__builtin_amdgcn_ballot_w64(act), qsh));        // regular positions 0, jump, .. < last
         N_fb = has_n || (strand_on && !dead && (ns_q > 2u * STEPS || (jj == 15u && act && i_reg + jump < last)));       // more seeds than this form holds
         N_hdr = hdr; N_ns = ns_q;
-        // the record of seed 2 st + g of the strand: 8 lanes, one 16-byte load each; lanes q < STEPS also fetch lane 0's part of the record of
-        // seed 2 q + g - all headers of a strand are looked at once
+        // the record of seed 2 st + g of the strand: 8 lanes, one 16-byte load each - the WHOLE line in one request: lane q = 0 holds the
+        // record's header word in .x (rank and count of a `more than 28 hits` record in .y / .z), lanes 1 .. 7 its positions.  A seed slot
+        // that is not in use reads the zero record: header 0, no positions
         const int bp_base = (int)((qbase + g) << 2);
-        const uint32_t hslot = 2u * q + g;
-        const uint32_t hcode = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((qbase + hslot) << 2), (int)code);
 #pragma unroll
         for (int st = 0; st < STEPS; ++st) {
             const uint32_t cdv = (uint32_t)__builtin_amdgcn_ds_bpermute(bp_base + 8 * st, (int)code);
-            N_rc[st] = bucket[(size_t)((2u * (uint32_t)st + g < ns_q && q != 0u) ? cdv : zero_code) * 8u + q];
+            N_rc[st] = bucket[(size_t)(2u * (uint32_t)st + g < ns_q ? cdv : zero_code) * 8u + q];
         }
-        N_hd4 = bucket[(size_t)((q < (uint32_t)STEPS && hslot < ns_q) ? hcode : zero_code) * 8u];
         // (last: the words just consumed are dead by now, the new ones land in their registers - requested earlier, the loop-carried copy
         // of the old values makes the wavefront wait for the new loads right away)
         request_forms(prn + 1u);
@@ -141,7 +145,6 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
         uint4 rc[STEPS];
 #pragma unroll
         for (int st = 0; st < STEPS; ++st) rc[st] = N_rc[st];
-        const uint4 hd4 = N_hd4;
         issue(pr + 1u);                               // (unconditional: beyond the last pair it loads the zero record - a branch here makes the compiler copy the
                                                       //  freshly loaded words at the join, i.e. wait for them at once)
         {
@@ -157,19 +160,26 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
         uint32_t of1[STEPS];
 #pragma unroll
         for (int st = 0; st < STEPS; ++st) of1[st] = (2u * (uint32_t)st + g) * jump + 1u;
-        const uint32_t hslot = 2u * q + g;
-        const bool hv = q < (uint32_t)STEPS && hslot < ns_q;
         // ---- headers: a k-mer that does not occur, exceeds -h, keeps its hits in the suffix array or has an early position: not here ----
-        const uint32_t hc = hd4.x & 0xFFFFu;
-        fb |= hv && ((hd4.x & 0xE0000000u) != 0u || (p.hcap > 0 && hc > (uint32_t)p.hcap));
-        uint32_t c_lane = hv ? hc : 0u;
+        // (the q = 0 lanes' .x words, one per step; a slot not in use has header 0.  The flag bits of a strand: the OR of its headers; its
+        // hits: the low 16 bits of their sum - at most 16 x 28, and what the flag bits add up to carries upwards only)
+        uint32_t hsum = 0u, hor = 0u;
+#pragma unroll
+        for (int st = 0; st < STEPS; ++st) { hsum += rc[st].x; hor |= rc[st].x; }
+        bool hbad = (hor & 0xE0000000u) != 0u;
+        if (p.hcap > 0) {
+#pragma unroll
+            for (int st = 0; st < STEPS; ++st) hbad |= (rc[st].x & 0xFFFFu) > (uint32_t)p.hcap;
+        }
+        fb |= q == 0u && hbad;
+        uint32_t c_lane = q == 0u ? hsum : 0u;
         {   // hits of the strand: sum over its 16 lanes (one DPP row)
             uint32_t v = c_lane;
             v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
             v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
             v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
             v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
-            c_lane = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((qbase + 15u) << 2), (int)v);
+            c_lane = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((qbase + 15u) << 2), (int)v) & 0xFFFFu;
         }
         const uint32_t E_q = c_lane;
         fb |= E_q > GMP_ECAP || E_q > p.heavy_min;
@@ -189,20 +199,26 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
         const uint32_t filt_off = (uint32_t)(size_t)(reinterpret_cast<unsigned char*>(&S.filt[0]) - reinterpret_cast<unsigned char*>(&S)) + qt * (GMP_FWORDS * 4u);
         const uint32_t qm_lo = rd ? 0u : (0xFFFFu << (16u * sd)), qm_hi = rd ? (0xFFFFu << (16u * sd)) : 0u;       // this quarter's lanes in the two mask halves
         uint32_t* const keys = &S.keys[qt][0];
+        // a hit marks TWO bits of its filter word (the word: bits 5 .. 13 of the window start): bit (bp & 31) and bit ((bp >> 14) & 31), one
+        // returning OR.  Equal window starts have equal marks, so a second arrival always finds both set; another window start of the same
+        // word finds both only when its two bits are among the ones set so far (~0.4 % per earlier hit of the word instead of the 1 / 32
+        // of one bit) - most keys that a sweep would find to hold one vote are never listed.  The q = 0 lanes hold header words: no vote
+        const bool votel = vote && q != 0u;
         auto arrive = [&](const uint32_t v, const uint32_t bp, uint32_t& bit) -> uint32_t {
             uint32_t old = 0;
-            bit = 1u << (bp & 31u);
-            if (vote && v != 0u) {
+            bit = (1u << ((bp >> 14) & 31u)) | (1u << (bp & 31u));
+            if (votel && v != 0u) {
                 uint32_t addr;
                 asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(addr) : "v"(bp >> 3), "s"(0x7FCu), "v"(filt_off));
                 old = atomicOr(reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(&S) + addr), bit);
             }
             return old;
         };
+        // a hit that found both its marks set, at a window start other than the strand's latest key: listed
         auto settle = [&](const uint32_t bp, const uint32_t old, const uint32_t bit) {
-            const unsigned long long dm = __builtin_amdgcn_uicmp(old & bit, 0u, 33 /* != */) & __builtin_amdgcn_uicmp(bp, known, 33 /* != */);
+            const unsigned long long dm = __builtin_amdgcn_uicmp(old & bit, bit, 32 /* == */) & __builtin_amdgcn_uicmp(bp, known, 33 /* != */);
             if (dm != 0ull) {                             // rare: once per distinct window start that is met again
-                const bool dup = (old & bit) != 0u && bp != known;
+                const bool dup = (old & bit) == bit && bp != known;
                 const uint32_t dlo = (uint32_t)dm & qm_lo, dhi = (uint32_t)(dm >> 32) & qm_hi;
                 const uint32_t at = lc_q + __builtin_amdgcn_mbcnt_hi(dhi, __builtin_amdgcn_mbcnt_lo(dlo, 0u));
                 if (dup && at < GMP_LCAP) keys[at] = bp;
@@ -228,7 +244,7 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
             uint32_t orz = 0u, orw = 0u;
 #pragma unroll
             for (int st = 0; st < STEPS; ++st) { orz |= rc[st].z; orw |= rc[st].w; }
-            const unsigned long long anyz = __builtin_amdgcn_uicmp(vote ? orz : 0u, 0u, 33), anyw = __builtin_amdgcn_uicmp(vote ? orw : 0u, 0u, 33);
+            const unsigned long long anyz = __builtin_amdgcn_uicmp(votel ? orz : 0u, 0u, 33), anyw = __builtin_amdgcn_uicmp(votel ? orw : 0u, 0u, 33);
             if (anyz != 0ull) {
                 uint32_t bz[STEPS], oz[STEPS], tz[STEPS];
 #pragma unroll
@@ -241,7 +257,7 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
             if (anyw != 0ull) {
 #pragma unroll
                 for (int st = 0; st < STEPS; ++st)
-                    if (__builtin_amdgcn_uicmp(vote ? rc[st].w : 0u, 0u, 33) != 0ull) { const uint32_t bp = rc[st].w - of1[st]; uint32_t bit; const uint32_t old = arrive(rc[st].w, bp, bit); settle(bp, old, bit); }
+                    if (__builtin_amdgcn_uicmp(votel ? rc[st].w : 0u, 0u, 33) != 0ull) { const uint32_t bp = rc[st].w - of1[st]; uint32_t bit; const uint32_t old = arrive(rc[st].w, bp, bit); settle(bp, old, bit); }
             }
         }
         // more second arrivals than the key list holds (a repeat-rich read): flagged after all
@@ -279,6 +295,7 @@ __global__ void __launch_bounds__(64, 4) k_vote_pair(GmDevIndex ix, GmDevParams 
                 if (__builtin_amdgcn_uicmp(rc[st].w, 0u, 33) != 0ull) mt |= (rc[st].w - of1[st]) == key;
                 tl |= mt ? (1u << (2u * (uint32_t)st + g)) : 0u;
             }
+            tl = q != 0u ? tl : 0u;                       // (a header word is no position)
             tl |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tl, 0x111, 0xF, 0xF, true);
             tl |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tl, 0x112, 0xF, 0xF, true);
             tl |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tl, 0x114, 0xF, 0xF, true);

@@ -275,6 +275,9 @@ const char* gm_kernel_name(int which);
  * e.g. "reads=fastq seeds=bucket-table (in the vote kernel) vote=k_vote_bucket<4> locate=full-SA nw=k_nw_rows/pairs" (valid until the
  * next call on the batch) */
 const char* gm_batch_path(gm_batch*);
+/* reads that k_vote_pair left to k_vote_bucket in the last gm_map_batch_device on this batch (a k-mer that does not occur or has more
+ * than 28 hits, an early position, a base that is not ACGT, too many hits or second arrivals in a strand); 0 when k_vote_pair did not run */
+int gm_batch_pair_flagged(gm_batch*, uint32_t* flagged);
 /* raw device results (accepted candidates), for tests and for callers that post-process themselves */
 typedef struct { uint32_t read; uint32_t pos; float score; uint16_t step; uint8_t strand; uint8_t pad; } gm_raw_hit;
 int gm_batch_raw_hits(gm_batch*, gm_raw_hit* out, uint64_t cap, uint64_t* n_out,
