@@ -1708,51 +1708,77 @@ static int map_batch_rest(gm_index* ix, const gm_params* p, gm_batch* b, gm_hits
 // MAPQ = round(-10 log10(1 - p)): glibc exp / log / round).  Device: traceback of every kept sequence, run-length CIGAR text, SAM
 // rows, coverage deposit (+ the per-nucleotide track of -b / -d).  Nothing per read is done on the host beyond that pass.
 // ------------------------------------------------------------------------------------------------
-// `out` (records + CIGAR pool to the host: gm_output_batch) or `rt` + `tout` (finished SAM text: gm_output_batch_text), never both
-// rt == null with tout: names and tails are the ones gm_batch_upload_text left in t_names / t_qtail (gm_output_batch_text_resident)
-// sorter (with tout): the text is not downloaded - it goes into the sorter's arena under sequence number seq (gm_output_batch_sorted)
-// bout (with tout): the rows are BAM records and leave as BGZF blocks (gm_output_batch_bam); a sorter set to GM_ROWS_BAM keeps records too
-static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_hits* hits, gm_sam_out* out, const gm_read_text* rt,
-                             gm_sam_text* tout, void* stream, gm_sam_sorter* sorter = nullptr, uint64_t seq = 0, gm_bam_out* bout = nullptr) {
-    const bool pools = tout && !rt;
-    const bool bam = bout || (sorter && gm_samsort_rows(sorter) == GM_ROWS_BAM);      // the rows are BAM records, not text (gm_bam.hip)
-    if (hits->n != b->n || reads->n != b->n) { gm_set_error("hits / reads do not belong to the batch"); return GM_E_ARG; }
-    PhaseClock pc(tout ? "gm_output_batch_text" : "gm_output_batch");
-    gm_sam_out no_host_records{};              // text form: the records and the CIGAR pool stay in HBM
-    if (!out) out = &no_host_records;
-    if (tout) {
-        tout->text_len = 0; tout->n_recs = 0;
-        if (tout->row_off && tout->row_cap) tout->row_off[0] = 0;
-        const uint32_t n = hits->n;
-        bool asc = pools || (rt->names && rt->name_off && (rt->qual_tail != nullptr) == (rt->qual_tail_off != nullptr));
-        for (uint32_t i = 0; !pools && asc && i < n; ++i) asc = rt->name_off[i] <= rt->name_off[i + 1] && (!rt->qual_tail_off || rt->qual_tail_off[i] <= rt->qual_tail_off[i + 1]);
-        if (!asc) { gm_set_error("gm_read_text: names / name_off missing, qual_tail without qual_tail_off (or the reverse), or offsets that do not ascend"); return GM_E_ARG; }
-        // a FASTA record has no quality line: QUAL is str2qual's string, one character per base, and nothing can follow it
-        if (!pools && b->fasta && rt->qual_tail_off) { gm_set_error("gm_read_text: qual_tail / qual_tail_off must be NULL for a FASTA block (its QUAL is synthesised, one character per base)"); return GM_E_ARG; }
+// One call of the output step, as its entry point describes it.  The sink says where the records go, and names the one destination
+// that is set: records + CIGAR pool to the host (gm_output_batch), finished SAM text (gm_output_batch_text), rows kept in the sorter's
+// arena under sequence number seq (gm_output_batch_sorted), BAM records inside BGZF blocks (gm_output_batch_bam).
+// What a form needs besides the pointers every form takes: a caller's gm_read_text, or the names gm_batch_upload_text left in the batch
+// (such a form takes no gm_reads).  OUT_PLAIN_NO_DEVICE: the host-only message carries no name (gm_output_batch_text's never has).
+enum { OUT_NEEDS_RT = 1, OUT_NEEDS_POOLS = 2, OUT_PLAIN_NO_DEVICE = 4 };
+struct OutCall {
+    const char* who;                           // the entry point, for its messages
+    enum Sink { records, text, sorted, bam } sink;
+    int needs;
+    const gm_reads* reads; const gm_hits* hits;
+    const gm_read_text* rt;                    // the rows' names and tails; null: the pools gm_batch_upload_text left in t_names / t_qtail
+    uint64_t seq;                              // sorted: the block's sequence number
+    void* dest;                                // the sink's one destination, as what the sink makes of it:
+    gm_sam_out* recs_out() const { return static_cast<gm_sam_out*>(dest); }       gm_sam_text* text_out() const { return static_cast<gm_sam_text*>(dest); }
+    gm_sam_sorter* sorter() const { return static_cast<gm_sam_sorter*>(dest); }   gm_bam_out* bam_out() const { return static_cast<gm_bam_out*>(dest); }
+    bool rows() const { return sink != records; }                              // the records leave as rows; they and the CIGAR pool stay in HBM
+    bool bam_rows() const { return sink == bam || (sink == sorted && gm_samsort_rows(sorter()) == GM_ROWS_BAM); }   // BAM records, not text (gm_bam.hip)
+};
+
+// what the steps of one call hand on to each other, by the step that sets it
+struct OutState {
+    GmDevParams dp;                            // sync_params, in output_batch
+    uint32_t n, n_m; uint64_t n_p;             // out_check_hits: reads, kept sequences (matches), position slots in use,
+    bool resident, snp, nuc; uint32_t ops_words, codes_stride;                 // and what the mode and the stride make of them
+    uint64_t n_recs, cig_len; uint32_t max_span;                               // out_count_records
+    GmDevText t;                               // out_row_inputs (t.text: out_write_rows)
+    uint64_t text_len; unsigned long long bad_row;                             // out_count_rows
+};
+
+// The destination first, as the entry points always have; then that reads and hits are the batch's; then the caller's names
+static int out_check_call(const gm_batch* b, const OutCall& c) {
+    const gm_hits* hits = c.hits; const gm_read_text* rt = c.rt;
+    if (c.sink == OutCall::text && !c.text_out()->text && c.text_out()->text_cap) { gm_set_error("gm_sam_text: text is NULL"); return GM_E_ARG; }
+    if (c.sink == OutCall::bam) {
+        gm_bam_out* out = c.bam_out();
+        out->len = 0; out->raw_len = 0; out->n_recs = 0;
+        if (!gm_bgzf_level_ok(out->level)) { gm_set_error(std::string(c.who) + ": gm_bam_out.level: " + gm_bgzf_level_text(out->level)); return GM_E_ARG; }
+        if (!out->data && out->cap) { gm_set_error(std::string(c.who) + ": gm_bam_out.data is NULL"); return GM_E_ARG; }
     }
-    HIPCHK(hipSetDevice(ix->device));
-    hipStream_t st = S_(stream);
-    GmDevParams dp;
-    int rc = sync_params(ix, p, dp, st);
-    if (rc) return rc;
-    const uint32_t n = hits->n;
-    const uint64_t n_m64 = n ? hits->match_begin[n] : 0;
-    out->n_recs = 0; out->cigar_len = 0;
-    if (n_m64 == 0) return GM_OK;
+    if (hits->n != b->n || c.reads->n != b->n) { gm_set_error("hits / reads do not belong to the batch"); return GM_E_ARG; }
+    if (c.sink == OutCall::text) {
+        c.text_out()->text_len = 0; c.text_out()->n_recs = 0;
+        if (c.text_out()->row_off && c.text_out()->row_cap) c.text_out()->row_off[0] = 0;
+    }
+    if (!rt) return GM_OK;
+    bool asc = rt->names && rt->name_off && (rt->qual_tail != nullptr) == (rt->qual_tail_off != nullptr);
+    for (uint32_t i = 0; asc && i < hits->n; ++i) asc = rt->name_off[i] <= rt->name_off[i + 1] && (!rt->qual_tail_off || rt->qual_tail_off[i] <= rt->qual_tail_off[i + 1]);
+    if (!asc) { gm_set_error("gm_read_text: names / name_off missing, qual_tail without qual_tail_off (or the reverse), or offsets that do not ascend"); return GM_E_ARG; }
+    // a FASTA record has no quality line: QUAL is str2qual's string, one character per base, and nothing can follow it
+    if (b->fasta && rt->qual_tail_off) { gm_set_error("gm_read_text: qual_tail / qual_tail_off must be NULL for a FASTA block (its QUAL is synthesised, one character per base)"); return GM_E_ARG; }
+    return GM_OK;
+}
+
+// The block's limits, then the hits.  hits->stamp names this batch's resident result: its matches / positions are used where they are.
+// Otherwise `hits` may have been edited by the caller: everything the kernels index with is checked HERE, before the first enqueue (a
+// match of another read would make k_traceback read rows that do not exist, a position range beyond the buffer would make k_out_items
+// write past o_posmatch), and the records are uploaded again.  Last, --snp's two preconditions (they stay behind the empty block's GM_OK
+// in output_batch, so that answer is the one it always was) and the sizes the mode and the stride give: ops_words, codes_stride, nuc.
+static int out_check_hits(const gm_index* ix, const gm_params* p, const gm_batch* b, const gm_hits* hits, OutState& s) {
+    const uint32_t n = s.n = hits->n;
+    const uint64_t n_m64 = hits->match_begin[n];
     if (n_m64 > 0x7FFFFFFFull) { gm_set_error("too many matches in one batch; map the block in smaller pieces"); return GM_E_BATCH_TOO_LARGE; }
-    {   // test switch: the output stage treats a block of more reads as too large, as the two limits of this function would
+    {   // test switch: the output stage treats a block of more reads as too large, as the two limits of the output step would
         const uint32_t test_max = (uint32_t)gm_opt_ll("GM_TEST_MAX_OUT_BLOCK", 0);
         if (test_max && n > test_max) { gm_set_error("GM_TEST_MAX_OUT_BLOCK: block treated as too large"); return GM_E_BATCH_TOO_LARGE; }
     }
-    const uint32_t n_m = (uint32_t)n_m64;
-    // ---- device, part 1: everything that does not depend on the posteriors is enqueued BEFORE the host pass and runs under it ----
-    // hits->stamp names this batch's resident result: its matches / positions are used where they are.  Otherwise `hits` may have been
-    // edited by the caller: everything the kernels index with is checked HERE, before the first enqueue (a match of another read
-    // would make k_traceback read rows that do not exist, a position range beyond the buffer would make k_out_items write past
-    // o_posmatch), and the records are uploaded again.
-    const bool resident = hits->stamp != 0 && hits->stamp == b->stamp && b->cache_matches == n_m64 && b->cache_hits <= hits->positions_cap;
+    s.n_m = (uint32_t)n_m64;
+    s.resident = hits->stamp != 0 && hits->stamp == b->stamp && b->cache_matches == n_m64 && b->cache_hits <= hits->positions_cap;
     uint64_t n_p = 0;
-    if (resident) n_p = b->cache_hits;
+    if (s.resident) n_p = b->cache_hits;
     else {
         if (hits->match_begin[0] != 0) { gm_set_error("gm_hits: match_begin[0] must be 0"); return GM_E_ARG; }
         bool bad = false;
@@ -1769,19 +1795,25 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
         if (bad) { gm_set_error("gm_hits: a match does not belong to its read, or its positions / first position are out of range"); return GM_E_ARG; }
         if (b->cache_matches == n_m64 && b->cache_hits <= hits->positions_cap && b->cache_hits >= n_p) n_p = b->cache_hits;     // positions share the hit CSR
     }
-    const uint32_t ops_words = gm_ops_words(b->stride), codes_stride = 32u * ops_words;
-    const bool snp = p->mode == GM_MODE_SNP;
-    if (snp && b->fasta) { gm_set_error("GM_MODE_SNP with a FASTA block: the pair HMM of --snp takes FASTQ blocks only"); return GM_E_UNSUPPORTED; }
-    if (snp && !ix->nuc_on) { gm_set_error("GM_MODE_SNP deposits into the per-nucleotide tracks: call gm_coverage_enable_nuc first"); return GM_E_ARG; }
-    const bool nuc = p->mode != GM_MODE_NORMAL && !snp && ix->nuc_on;
+    s.n_p = n_p;
+    s.ops_words = gm_ops_words(b->stride); s.codes_stride = 32u * s.ops_words;
+    s.snp = p->mode == GM_MODE_SNP;
+    if (s.snp && b->fasta) { gm_set_error("GM_MODE_SNP with a FASTA block: the pair HMM of --snp takes FASTQ blocks only"); return GM_E_UNSUPPORTED; }
+    if (s.snp && !ix->nuc_on) { gm_set_error("GM_MODE_SNP deposits into the per-nucleotide tracks: call gm_coverage_enable_nuc first"); return GM_E_ARG; }
+    s.nuc = p->mode != GM_MODE_NORMAL && !s.snp && ix->nuc_on;
+    return GM_OK;
+}
+
+// Device, part 1: everything that does not depend on the posteriors is enqueued BEFORE the host pass and runs under it
+static int out_enqueue_traceback(gm_index* ix, const gm_params* p, gm_batch* b, const gm_hits* hits, const OutState& s, hipStream_t st) {
+    const uint32_t n = s.n, n_m = s.n_m; const uint64_t n_p = s.n_p;
     if (b->g_matches.ensure((size_t)n_m * sizeof(GmDevMatch)) || b->g_positions.ensure((size_t)(n_p + 1) * sizeof(GmDevPos)) ||
         b->o_posmatch.ensure((size_t)(n_p + 1) * 4) || b->o_post.ensure((size_t)n_m * 4) || b->o_mapq.ensure((size_t)n_m * 4) || b->o_emit.ensure(n_m) ||
-        b->tb_items.ensure((size_t)n_m * sizeof(GmCand)) || b->tb_ops.ensure((size_t)n_m * ops_words * 8) || b->tb_len.ensure((size_t)n_m * 2) ||
+        b->tb_items.ensure((size_t)n_m * sizeof(GmCand)) || b->tb_ops.ensure((size_t)n_m * s.ops_words * 8) || b->tb_len.ensure((size_t)n_m * 2) ||
         b->o_reccnt.ensure((size_t)n_m * 4) || b->o_cigcnt.ensure((size_t)n_m * 4) || b->o_cigall.ensure((size_t)n_m * 4) || b->o_recoff.ensure(((size_t)n_m + 1) * 8) ||
         b->o_cigoff.ensure(((size_t)n_m + 1) * 8) || b->scan_tmp.ensure(((size_t)std::max<uint32_t>(n_m, n) / 1024 + 8) * 8) || b->o_small.ensure(64) ||
-        (nuc && b->o_codes.ensure((size_t)n_m * codes_stride))) return GM_E_NOMEM;
-    const GmDevMatch* d_m = b->g_matches.as<GmDevMatch>(); const GmDevPos* d_p = b->g_positions.as<GmDevPos>();
-    if (!resident) {
+        (s.nuc && b->o_codes.ensure((size_t)n_m * s.codes_stride))) return GM_E_NOMEM;
+    if (!s.resident) {
         HIPCHK(hipMemcpyAsync(b->g_matches.p, hits->matches, (size_t)n_m * sizeof(gm_match), hipMemcpyHostToDevice, st));
         if (n_p) HIPCHK(hipMemcpyAsync(b->g_positions.p, hits->positions, (size_t)n_p * sizeof(gm_pos), hipMemcpyHostToDevice, st));
         b->stamp = 0;                                          // what is resident now is the caller's version
@@ -1790,14 +1822,20 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
     HIPCHK(hipMemsetAsync(b->o_small.p, 0, 64, st));
     if (p->max_gap != 3 && b->band_moves.ensure(gm_band_moves_words(n_m, b->stride) * 8)) return GM_E_NOMEM;
     fill_dev_batch(b);
+    const GmDevMatch* d_m = b->g_matches.as<GmDevMatch>();
     KCHK(gmk_out_items(d_m, n_m, 0, b->tb_items.as<GmCand>(), b->o_posmatch.as<uint32_t>(), st));
     // one traceback per ScoredSeq, oriented by its first strand (NormalScoredSeq::score, ScoredSeq::get_SAM); the kernel also leaves the
     // length of every sequence's CIGAR text and finds the longest aligned length
-    KCHK(gmk_traceback(ix->dev, dp, b->dev, b->tb_items.as<GmCand>(), n_m, b->tb_ops.as<unsigned long long>(), ops_words, b->tb_len.as<uint16_t>(),
+    KCHK(gmk_traceback(ix->dev, s.dp, b->dev, b->tb_items.as<GmCand>(), n_m, b->tb_ops.as<unsigned long long>(), s.ops_words, b->tb_len.as<uint16_t>(),
                        nullptr, b->o_cigall.as<uint32_t>(), b->o_small.as<uint32_t>(), st));
     if (!p->nw && !b->adaptor.empty()) KCHK(gmk_adaptor_cigar_room(d_m, n_m, b->full_len.as<uint16_t>(), std::min<uint32_t>(n, b->n), b->o_cigall.as<uint32_t>(), st));
-    pc.lap("enqueue");
-    // ---- host pass: ScoredSeq::get_SAM :300-309, is_greater :223-228, Driver.cpp:672-701 ----
+    return GM_OK;
+}
+
+// Host pass: posterior, winner and MAPQ of every match (ScoredSeq::get_SAM :300-309, is_greater :223-228, Driver.cpp:672-701) into the
+// batch's page-locked h_post / h_mapq / h_emit.  Nothing is enqueued here: the pass runs while part 1 does.
+static int out_host_posteriors(const gm_params* p, gm_batch* b, const gm_hits* hits, const OutState& s) {
+    const uint32_t n = s.n, n_m = s.n_m;
     if (b->h_post.ensure((size_t)n_m * 4) || b->h_mapq.ensure((size_t)n_m * 4) || b->h_emit.ensure(n_m)) return GM_E_NOMEM;
     float* post = b->h_post.as<float>(); int32_t* mapq = b->h_mapq.as<int32_t>(); uint8_t* emit = b->h_emit.as<uint8_t>();
     const double log10v = log(10), e_m1 = exp(-1.0);                   // e_m1: the empty NormalScoredSeq a winner has to beat, ScoredSeq.h:117-120
@@ -1836,124 +1874,175 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
             }
         }
     });
-    pc.lap("fp64");
-    // ---- device, part 2 ----
-    HIPCHK(hipMemcpyAsync(b->o_post.p, post, (size_t)n_m * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->o_mapq.p, mapq, (size_t)n_m * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->o_emit.p, emit, n_m, hipMemcpyHostToDevice, st));
-    KCHK(gmk_out_sizes(d_m, n_m, b->o_emit.as<uint8_t>(), b->o_cigall.as<uint32_t>(), b->o_reccnt.as<uint32_t>(), b->o_cigcnt.as<uint32_t>(), st));
+    return GM_OK;
+}
+
+// Device, part 2: the posteriors go up; how many records and CIGAR bytes they make, and the longest aligned length, come back
+static int out_count_records(gm_batch* b, OutState& s, hipStream_t st) {
+    const uint32_t n_m = s.n_m;
+    HIPCHK(hipMemcpyAsync(b->o_post.p, b->h_post.p, (size_t)n_m * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->o_mapq.p, b->h_mapq.p, (size_t)n_m * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->o_emit.p, b->h_emit.p, n_m, hipMemcpyHostToDevice, st));
+    KCHK(gmk_out_sizes(b->g_matches.as<GmDevMatch>(), n_m, b->o_emit.as<uint8_t>(), b->o_cigall.as<uint32_t>(), b->o_reccnt.as<uint32_t>(), b->o_cigcnt.as<uint32_t>(), st));
     KCHK(gmk_scan_u32(b->o_reccnt.as<uint32_t>(), n_m, b->o_recoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
     KCHK(gmk_scan_u32(b->o_cigcnt.as<uint32_t>(), n_m, b->o_cigoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
-    uint64_t n_recs = 0, cig_len = 0; uint32_t max_span = 0;
-    HIPCHK(hipMemcpyAsync(&n_recs, b->o_recoff.as<uint64_t>() + n_m, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&cig_len, b->o_cigoff.as<uint64_t>() + n_m, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&max_span, b->o_small.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&s.n_recs, b->o_recoff.as<uint64_t>() + n_m, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&s.cig_len, b->o_cigoff.as<uint64_t>() + n_m, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&s.max_span, b->o_small.p, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    pc.lap("traceback+count");
-    // capacity first: a call that is going to be repeated with larger buffers must not deposit coverage twice
-    out->n_recs = n_recs; out->cigar_len = cig_len;
-    if (!tout && (n_recs > out->recs_cap || cig_len > out->cigar_cap)) {
-        out->recs_cap = n_recs; out->cigar_cap = cig_len;
-        gm_set_error("output buffers too small");
-        return GM_E_CAPACITY;
+    return GM_OK;
+}
+
+// The records sink's capacity answer, then the records and the CIGAR pool: written in HBM for every sink, copied out for the records sink
+static int out_write_records(gm_index* ix, const gm_params* p, gm_batch* b, const OutCall& c, const OutState& s, hipStream_t st) {
+    const uint64_t n_recs = s.n_recs, cig_len = s.cig_len;
+    if (c.sink == OutCall::records) {
+        gm_sam_out* out = c.recs_out();
+        out->n_recs = n_recs; out->cigar_len = cig_len;
+        if (n_recs > out->recs_cap || cig_len > out->cigar_cap) {
+            out->recs_cap = n_recs; out->cigar_cap = cig_len;
+            gm_set_error("output buffers too small");
+            return GM_E_CAPACITY;
+        }
     }
     if (cig_len > 0xFFFFFFFFull) { gm_set_error("CIGAR pool beyond 4 GB in one batch; map the block in smaller pieces"); return GM_E_BATCH_TOO_LARGE; }
     if (b->o_recs.ensure((size_t)(n_recs + 1) * sizeof(GmDevSamRec)) || b->o_pool.ensure((size_t)cig_len + 16)) return GM_E_NOMEM;
     if (n_recs) {
         GmDevBatch wb = b->dev;                      // (k_out_write reads the lengths for --no_nw's "<L>M" only: consensus.size(), the whole line with -A, ScoredSeq.h:365)
         if (!b->adaptor.empty()) wb.len = b->full_len.as<uint16_t>();
-        KCHK(gmk_out_write(ix->dev, wb, d_m, d_p, n_m, b->o_emit.as<uint8_t>(), b->o_mapq.as<int32_t>(), b->o_post.as<float>(), b->tb_ops.as<unsigned long long>(),
-                           ops_words, b->tb_len.as<uint16_t>(), p->nw, b->o_recoff.as<uint64_t>(), b->o_cigoff.as<uint64_t>(),
-                           b->o_recs.as<GmDevSamRec>(), b->o_pool.as<char>(), st));
-        if (!tout) {
-            HIPCHK(hipMemcpyAsync(out->recs, b->o_recs.p, (size_t)n_recs * sizeof(gm_sam_rec), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(out->cigar_pool, b->o_pool.p, (size_t)cig_len, hipMemcpyDeviceToHost, st));
+        KCHK(gmk_out_write(ix->dev, wb, b->g_matches.as<GmDevMatch>(), b->g_positions.as<GmDevPos>(), s.n_m, b->o_emit.as<uint8_t>(), b->o_mapq.as<int32_t>(),
+                           b->o_post.as<float>(), b->tb_ops.as<unsigned long long>(), s.ops_words, b->tb_len.as<uint16_t>(), p->nw, b->o_recoff.as<uint64_t>(),
+                           b->o_cigoff.as<uint64_t>(), b->o_recs.as<GmDevSamRec>(), b->o_pool.as<char>(), st));
+    }
+    if (n_recs && c.sink == OutCall::records) {
+        HIPCHK(hipMemcpyAsync(c.recs_out()->recs, b->o_recs.p, (size_t)n_recs * sizeof(gm_sam_rec), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(c.recs_out()->cigar_pool, b->o_pool.p, (size_t)cig_len, hipMemcpyDeviceToHost, st));
+    }
+    if (c.sink == OutCall::text) c.text_out()->n_recs = n_recs;
+    return GM_OK;
+}
+
+// Rows, their inputs: the names and quality tails of the block in HBM (a caller's are uploaded, the pools of a text block are in
+// place), room for the row lengths and offsets, and the GmDevText the row kernels read
+static int out_row_inputs(gm_index* ix, const gm_params* p, gm_batch* b, const OutCall& c, OutState& s, hipStream_t st) {
+    const gm_read_text* rt = c.rt;
+    const bool pools = !rt, bam = c.bam_rows();
+    const uint32_t n = s.n; const uint64_t n_recs = s.n_recs;
+    if (const int rc = index_cnames(ix)) return rc;                // contig names, once per index
+    // the pools of a text block start at offset 0 and are in place; a block without a quality tail passes none, as a caller would
+    const bool tails = pools ? b->text_tail_bytes != 0 : rt->qual_tail_off != nullptr;
+    const uint64_t name0 = pools ? 0 : rt->name_off[0], tail0 = pools || !tails ? 0 : rt->qual_tail_off[0];
+    const uint64_t name_bytes = pools ? 0 : rt->name_off[n] - name0, tail_bytes = pools || !tails ? 0 : rt->qual_tail_off[n] - tail0;
+    if ((!pools && (b->t_names.ensure((size_t)name_bytes + 16) || b->t_nameoff.ensure(((size_t)n + 1) * 8))) || b->t_slots.ensure((size_t)n_recs * 64) ||
+        b->t_rowlen.ensure((size_t)n_recs * 4) || b->t_rowoff.ensure(((size_t)n_recs + 1) * 8) || b->t_bad.ensure(8) || (bam && b->t_bammeta.ensure((size_t)n_recs * 8)) ||
+        b->scan_tmp.ensure(((size_t)n_recs / 1024 + 8) * 8) ||
+        (!pools && tails && (b->t_qtail.ensure((size_t)tail_bytes + 16) || b->t_qtailoff.ensure(((size_t)n + 1) * 8)))) return GM_E_NOMEM;
+    if (!pools) {
+        b->text_pools = false;                                     // the caller's names take the place of the parse's
+        // the offsets are used as they are: the kernels index names - name_off[0] so that a caller may pass a window of a larger pool
+        if (name_bytes) HIPCHK(hipMemcpyAsync(b->t_names.p, rt->names + rt->name_off[0], (size_t)name_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b->t_nameoff.p, rt->name_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+    if (!pools && tails) {
+        if (tail_bytes) HIPCHK(hipMemcpyAsync(b->t_qtail.p, rt->qual_tail + rt->qual_tail_off[0], (size_t)tail_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b->t_qtailoff.p, rt->qual_tail_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+    GmDevText& t = s.t;
+    t.recs = b->o_recs.as<GmDevSamRec>(); t.n_recs = n_recs; t.pool = b->o_pool.as<char>();
+    t.names = b->t_names.as<char>() - name0; t.name_off = b->t_nameoff.as<uint64_t>();
+    t.qtail = tails ? b->t_qtail.as<char>() - tail0 : nullptr; t.qtail_off = tails ? b->t_qtailoff.as<uint64_t>() : nullptr;
+    t.cnames = ix->d_cnames.as<char>(); t.cname_off = ix->d_cname_off.as<uint32_t>();
+    t.slots = b->t_slots.as<uint8_t>(); t.row_len = b->t_rowlen.as<uint32_t>(); t.row_off = b->t_rowoff.as<uint64_t>();
+    t.inv_adjust = 1.0 / p->adjust; t.bad = b->t_bad.as<unsigned long long>();
+    t.seq_len = b->adaptor.empty() ? b->dev.len : b->full_len.as<uint16_t>();
+    t.fa_qual = fasta_qual_word();
+    return GM_OK;
+}
+
+// Rows, their sizes: tails + row lengths (the records' sizes take their place when the rows are BAM), their scan, and what comes back:
+// the length of all rows and the first record the device cannot print
+static int out_count_rows(gm_batch* b, const OutCall& c, OutState& s, hipStream_t st) {
+    const bool bam = c.bam_rows(), bam_timed = bam && b->profiling;
+    HIPCHK(hipMemsetAsync(b->t_bad.p, 0xFF, 8, st));
+    KCHK(gmk_out_text_sizes(b->dev, s.t, st));
+    if (bam_timed) { for (auto& e : b->bam_ev) if (!e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(b->bam_ev[0], st)); }
+    if (bam) KCHK(gmk_bam_sizes(s.t, b->t_bammeta.as<uint32_t>(), st));
+    if (bam_timed) HIPCHK(hipEventRecord(b->bam_ev[1], st));
+    KCHK(gmk_scan_u32(s.t.row_len, s.n_recs, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
+    s.bad_row = ~0ull;
+    HIPCHK(hipMemcpyAsync(&s.text_len, b->t_rowoff.as<uint64_t>() + s.n_recs, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&s.bad_row, b->t_bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GM_OK;
+}
+
+// The text sink's capacity answer, then the rows: SAM text or BAM records, in the batch's t_text
+static int out_write_rows(gm_batch* b, const OutCall& c, OutState& s, hipStream_t st) {
+    const bool bam = c.bam_rows(), bam_timed = bam && b->profiling;
+    const uint64_t n_recs = s.n_recs, text_len = s.text_len;
+    if (s.bad_row != ~0ull) {
+        gm_set_error("SAM record " + std::to_string(s.bad_row) + ": XA or XP is outside the range the device prints exactly (2^-200 <= |v| < 2^200)");
+        return GM_E_UNSUPPORTED;
+    }
+    if (c.sink == OutCall::text) {
+        gm_sam_text* tout = c.text_out();
+        tout->text_len = text_len;
+        const bool rows_fit = !tout->row_off || tout->row_cap >= n_recs + 1;
+        if (text_len > tout->text_cap || !rows_fit) {
+            tout->text_cap = text_len;
+            if (tout->row_off) tout->row_cap = n_recs + 1;
+            gm_set_error("output buffers too small");
+            return GM_E_CAPACITY;
         }
     }
-    if (tout) {
-        // ---- SAM text: tails + row lengths, their scan, then - once the caller's buffer is known to hold them - the rows ----
-        tout->n_recs = n_recs;
-        if (n_recs) {
-            if (const int rc = index_cnames(ix)) return rc;                // contig names, once per index
-            // the pools of a text block start at offset 0 and are in place; a block without a quality tail passes none, as a caller would
-            const bool tails = pools ? b->text_tail_bytes != 0 : rt->qual_tail_off != nullptr;
-            const uint64_t name0 = pools ? 0 : rt->name_off[0], tail0 = pools || !tails ? 0 : rt->qual_tail_off[0];
-            const uint64_t name_bytes = pools ? 0 : rt->name_off[n] - name0, tail_bytes = pools || !tails ? 0 : rt->qual_tail_off[n] - tail0;
-            if ((!pools && (b->t_names.ensure((size_t)name_bytes + 16) || b->t_nameoff.ensure(((size_t)n + 1) * 8))) || b->t_slots.ensure((size_t)n_recs * 64) ||
-                b->t_rowlen.ensure((size_t)n_recs * 4) || b->t_rowoff.ensure(((size_t)n_recs + 1) * 8) || b->t_bad.ensure(8) || (bam && b->t_bammeta.ensure((size_t)n_recs * 8)) ||
-                b->scan_tmp.ensure(((size_t)n_recs / 1024 + 8) * 8) ||
-                (!pools && tails && (b->t_qtail.ensure((size_t)tail_bytes + 16) || b->t_qtailoff.ensure(((size_t)n + 1) * 8)))) return GM_E_NOMEM;
-            if (!pools) b->text_pools = false;                             // the caller's names take the place of the parse's
-            // the offsets are used as they are: the kernels index names - name_off[0] so that a caller may pass a window of a larger pool
-            if (name_bytes) HIPCHK(hipMemcpyAsync(b->t_names.p, rt->names + rt->name_off[0], (size_t)name_bytes, hipMemcpyHostToDevice, st));
-            if (!pools) HIPCHK(hipMemcpyAsync(b->t_nameoff.p, rt->name_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-            if (!pools && tails) {
-                if (tail_bytes) HIPCHK(hipMemcpyAsync(b->t_qtail.p, rt->qual_tail + rt->qual_tail_off[0], (size_t)tail_bytes, hipMemcpyHostToDevice, st));
-                HIPCHK(hipMemcpyAsync(b->t_qtailoff.p, rt->qual_tail_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-            }
-            HIPCHK(hipMemsetAsync(b->t_bad.p, 0xFF, 8, st));
-            GmDevText t{};
-            t.recs = b->o_recs.as<GmDevSamRec>(); t.n_recs = n_recs; t.pool = b->o_pool.as<char>();
-            t.names = b->t_names.as<char>() - name0; t.name_off = b->t_nameoff.as<uint64_t>();
-            t.qtail = tails ? b->t_qtail.as<char>() - tail0 : nullptr; t.qtail_off = tails ? b->t_qtailoff.as<uint64_t>() : nullptr;
-            t.cnames = ix->d_cnames.as<char>(); t.cname_off = ix->d_cname_off.as<uint32_t>();
-            t.slots = b->t_slots.as<uint8_t>(); t.row_len = b->t_rowlen.as<uint32_t>(); t.row_off = b->t_rowoff.as<uint64_t>();
-            t.inv_adjust = 1.0 / p->adjust; t.bad = b->t_bad.as<unsigned long long>();
-            t.seq_len = b->adaptor.empty() ? b->dev.len : b->full_len.as<uint16_t>();
-            t.fa_qual = fasta_qual_word();
-            KCHK(gmk_out_text_sizes(b->dev, t, st));
-            const bool bam_timed = bam && b->profiling;
-            if (bam_timed) { for (auto& e : b->bam_ev) if (!e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(b->bam_ev[0], st)); }
-            if (bam) KCHK(gmk_bam_sizes(t, b->t_bammeta.as<uint32_t>(), st));      // the records' sizes take the place of the rows' lengths
-            if (bam_timed) HIPCHK(hipEventRecord(b->bam_ev[1], st));
-            KCHK(gmk_scan_u32(t.row_len, n_recs, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
-            uint64_t text_len = 0; unsigned long long bad = ~0ull;
-            HIPCHK(hipMemcpyAsync(&text_len, b->t_rowoff.as<uint64_t>() + n_recs, 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(&bad, b->t_bad.p, 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            pc.lap("text sizes");
-            if (bad != ~0ull) {
-                gm_set_error("SAM record " + std::to_string(bad) + ": XA or XP is outside the range the device prints exactly (2^-200 <= |v| < 2^200)");
-                return GM_E_UNSUPPORTED;
-            }
-            tout->text_len = text_len;
-            // capacity first, as above: nothing has been deposited yet, the repeated call deposits once
-            const bool rows_fit = !tout->row_off || tout->row_cap >= n_recs + 1;
-            if (!sorter && !bout && (text_len > tout->text_cap || !rows_fit)) {
-                tout->text_cap = text_len;
-                if (tout->row_off) tout->row_cap = n_recs + 1;
-                gm_set_error("output buffers too small");
-                return GM_E_CAPACITY;
-            }
-            if (b->t_text.ensure((size_t)text_len + 16)) return GM_E_NOMEM;
-            t.text = b->t_text.as<char>();
-            if (bam_timed) HIPCHK(hipEventRecord(b->bam_ev[2], st));
-            if (bam) KCHK(gmk_bam_rows(b->dev, t, b->t_bammeta.as<uint32_t>(), st));
-            else KCHK(gmk_out_text_rows(b->dev, t, st));
-            if (bam_timed) {
-                float ms_a = 0, ms_b = 0;
-                HIPCHK(hipEventRecord(b->bam_ev[3], st));
-                HIPCHK(hipStreamSynchronize(st));
-                HIPCHK(hipEventElapsedTime(&ms_a, b->bam_ev[0], b->bam_ev[1]));
-                HIPCHK(hipEventElapsedTime(&ms_b, b->bam_ev[2], b->bam_ev[3]));
-                b->bam_rows_ms += (double)ms_a + ms_b; b->bam_raw_bytes += text_len;
-            }
-            // sorted: the rows stay in HBM (the arena grows before the deposit below: out of room, nothing of the block has been deposited)
-            if (sorter) { if (const int rc = gm_samsort_add(sorter, seq, t.recs, n_recs, t.text, t.row_off, text_len, st)) return rc; }
-            else if (bout) {
-                // compressed where the records lie; capacity first, as above: the repeated call deposits once
-                uint64_t z_len = 0;
-                b->bz.timed = b->profiling;
-                if (const int rc = gm_bgzf_device(b->t_text.p, text_len, bout->level, b->bz, &z_len, st)) return rc;
-                bout->len = z_len; bout->raw_len = text_len; bout->n_recs = n_recs;
-                if (z_len > bout->cap) { bout->cap = z_len; bout->len = 0; gm_set_error("output buffers too small"); return GM_E_CAPACITY; }
-                HIPCHK(hipMemcpyAsync(bout->data, b->bz.out.p, (size_t)z_len, hipMemcpyDeviceToHost, st));
-            }
-            else HIPCHK(hipMemcpyAsync(tout->text, b->t_text.p, (size_t)text_len, hipMemcpyDeviceToHost, st));
-            if (!sorter && !bout && tout->row_off) HIPCHK(hipMemcpyAsync(tout->row_off, b->t_rowoff.p, ((size_t)n_recs + 1) * 8, hipMemcpyDeviceToHost, st));
-        }
+    if (b->t_text.ensure((size_t)text_len + 16)) return GM_E_NOMEM;
+    s.t.text = b->t_text.as<char>();
+    if (bam_timed) HIPCHK(hipEventRecord(b->bam_ev[2], st));
+    if (bam) KCHK(gmk_bam_rows(b->dev, s.t, b->t_bammeta.as<uint32_t>(), st));
+    else KCHK(gmk_out_text_rows(b->dev, s.t, st));
+    if (bam_timed) {
+        float ms_a = 0, ms_b = 0;
+        HIPCHK(hipEventRecord(b->bam_ev[3], st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&ms_a, b->bam_ev[0], b->bam_ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms_b, b->bam_ev[2], b->bam_ev[3]));
+        b->bam_rows_ms += (double)ms_a + ms_b; b->bam_raw_bytes += text_len;
     }
-    if (snp && ix->cov_bins && n_p) {
+    return GM_OK;
+}
+
+// The rows leave: to the caller's buffers; into the sorter's arena, where they stay in HBM (an arena that cannot grow: GM_E_NOMEM from
+// gm_samsort_add); or compressed where they lie, the BGZF blocks to the caller's buffer once it is known to hold them
+static int out_deliver_rows(gm_batch* b, const OutCall& c, const OutState& s, hipStream_t st) {
+    const uint64_t n_recs = s.n_recs, text_len = s.text_len;
+    switch (c.sink) {
+    case OutCall::text:
+        HIPCHK(hipMemcpyAsync(c.text_out()->text, b->t_text.p, (size_t)text_len, hipMemcpyDeviceToHost, st));
+        if (c.text_out()->row_off) HIPCHK(hipMemcpyAsync(c.text_out()->row_off, b->t_rowoff.p, ((size_t)n_recs + 1) * 8, hipMemcpyDeviceToHost, st));
+        return GM_OK;
+    case OutCall::sorted:
+        return gm_samsort_add(c.sorter(), c.seq, s.t.recs, n_recs, s.t.text, s.t.row_off, text_len, st);
+    case OutCall::bam: {
+        gm_bam_out* bout = c.bam_out();
+        uint64_t z_len = 0;
+        b->bz.timed = b->profiling;
+        if (const int rc = gm_bgzf_device(b->t_text.p, text_len, bout->level, b->bz, &z_len, st)) return rc;
+        bout->len = z_len; bout->raw_len = text_len; bout->n_recs = n_recs;
+        if (z_len > bout->cap) { bout->cap = z_len; bout->len = 0; gm_set_error("output buffers too small"); return GM_E_CAPACITY; }
+        HIPCHK(hipMemcpyAsync(bout->data, b->bz.out.p, (size_t)z_len, hipMemcpyDeviceToHost, st));
+        return GM_OK;
+    }
+    case OutCall::records: break;                                  // (copied out where they were written)
+    }
+    return GM_OK;
+}
+
+// The coverage deposit (+ the per-nucleotide tracks of -b / -d / --snp): the one step that cannot be taken back
+static int out_deposit(gm_index* ix, gm_batch* b, const OutState& s, hipStream_t st) {
+    const uint32_t n_m = s.n_m;
+    const GmDevMatch* d_m = b->g_matches.as<GmDevMatch>(); const GmDevPos* d_p = b->g_positions.as<GmDevPos>();
+    if (!ix->cov_bins || !s.n_p) return GM_OK;
+    if (s.snp) {
         // SNPScoredSeq::score: no traceback in the deposit - the pair HMM of every kept sequence against its window, chunk by chunk (a
         // lane's forward matrix is (L+1)^2 x 3 doubles of scratch), then coverage + the five tracks at every place of the sequence
         const uint32_t Lmax = b->stride;
@@ -1963,80 +2052,107 @@ static int output_batch_impl(gm_index* ix, const gm_params* p, gm_batch* b, cons
         GM_TRACE("snp deposit: %u kept sequences, chunks of %u: %u chunk%s", n_m, chunk, (n_m + chunk - 1) / chunk, (n_m + chunk - 1) / chunk == 1 ? "" : "s");
         for (uint32_t m0 = 0; m0 < n_m; m0 += chunk) {
             const uint32_t cnt = std::min<uint32_t>(chunk, n_m - m0);
-            KCHK(gmk_pair_hmm(ix->dev, dp, b->dev, b->tb_items.as<GmCand>() + m0, cnt, b->snp_scratch.as<double>(), Lmax, b->snp_hmm.as<float>(), st));
+            KCHK(gmk_pair_hmm(ix->dev, s.dp, b->dev, b->tb_items.as<GmCand>() + m0, cnt, b->snp_scratch.as<double>(), Lmax, b->snp_hmm.as<float>(), st));
             KCHK(gmk_snp_deposit(ix->d_cov.as<float>(), ix->d_nuc.as<float>(), ix->cov_bins, ix->cov_bin_size, b->dev, d_m, d_p, m0, cnt, b->o_post.as<float>(),
                                  b->snp_hmm.as<float>(), Lmax, st));
         }
-    } else if (ix->cov_bins && n_p && max_span) {
-        if (nuc) KCHK(gmk_out_codes(b->dev, dp, d_m, n_m, b->tb_ops.as<unsigned long long>(), ops_words, b->tb_len.as<uint16_t>(), b->o_codes.as<uint8_t>(), codes_stride, st));
-        KCHK(gmk_out_deposit(ix->d_cov.as<float>(), ix->cov_bins, ix->cov_bin_size, d_m, d_p, b->o_posmatch.as<uint32_t>(), n_p, b->tb_len.as<uint16_t>(),
-                             b->o_post.as<float>(), max_span, nuc ? ix->d_nuc.as<float>() : nullptr, nuc ? b->o_codes.as<uint8_t>() : nullptr, codes_stride, st));
+    } else if (s.max_span) {
+        const bool nuc = s.nuc;
+        if (nuc) KCHK(gmk_out_codes(b->dev, s.dp, d_m, n_m, b->tb_ops.as<unsigned long long>(), s.ops_words, b->tb_len.as<uint16_t>(), b->o_codes.as<uint8_t>(), s.codes_stride, st));
+        KCHK(gmk_out_deposit(ix->d_cov.as<float>(), ix->cov_bins, ix->cov_bin_size, d_m, d_p, b->o_posmatch.as<uint32_t>(), s.n_p, b->tb_len.as<uint16_t>(),
+                             b->o_post.as<float>(), s.max_span, nuc ? ix->d_nuc.as<float>() : nullptr, nuc ? b->o_codes.as<uint8_t>() : nullptr, s.codes_stride, st));
     }
+    return GM_OK;
+}
+
+// The steps of one call, in the order things happen.  ONE RULE orders them: nothing is deposited before every capacity answer has been
+// given.  A call that answers GM_E_CAPACITY is repeated with larger buffers, and the repeated call must deposit once, not twice: so the
+// deposit is the last step, and the three capacity answers (records, text, BGZF blocks) come from steps before it; so does every other
+// refusal, the sorter's among them (GM_E_NOMEM when its arena cannot grow).  What an earlier step does leave behind says so: the
+// batch's stamp is cleared once a caller's matches have taken the place of the resident ones, its text_pools once a caller's names have.
+static int output_batch(gm_index* ix, const gm_params* p, gm_batch* b, const OutCall& c, void* stream) {
+    if (const int rc = out_check_call(b, c)) return rc;
+    PhaseClock pc(c.rows() ? "gm_output_batch_text" : "gm_output_batch");
+    HIPCHK(hipSetDevice(ix->device));
+    hipStream_t st = S_(stream);
+    OutState s{};
+    if (const int rc = sync_params(ix, p, s.dp, st)) return rc;
+    if (c.sink == OutCall::records) { c.recs_out()->n_recs = 0; c.recs_out()->cigar_len = 0; }
+    if (!c.hits->n || !c.hits->match_begin[c.hits->n]) return GM_OK;           // nothing matched: no record, no row, no deposit
+    if (const int rc = out_check_hits(ix, p, b, c.hits, s)) return rc;
+    if (const int rc = out_enqueue_traceback(ix, p, b, c.hits, s, st)) return rc;
+    pc.lap("enqueue");
+    if (const int rc = out_host_posteriors(p, b, c.hits, s)) return rc;
+    pc.lap("fp64");
+    if (const int rc = out_count_records(b, s, st)) return rc;
+    pc.lap("traceback+count");
+    if (const int rc = out_write_records(ix, p, b, c, s, st)) return rc;
+    if (c.rows() && s.n_recs) {
+        if (const int rc = out_row_inputs(ix, p, b, c, s, st)) return rc;
+        if (const int rc = out_count_rows(b, c, s, st)) return rc;
+        pc.lap("text sizes");
+        if (const int rc = out_write_rows(b, c, s, st)) return rc;
+        if (const int rc = out_deliver_rows(b, c, s, st)) return rc;
+    }
+    if (const int rc = out_deposit(ix, b, s, st)) return rc;
     HIPCHK(hipStreamSynchronize(st));
     pc.lap("records+coverage");
     return GM_OK;
 }
 
-extern "C" int gm_output_batch(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_hits* hits, gm_sam_out* out, void* stream) {
-    if (!ix || !p || !b || !reads || !hits || !out) return GM_E_ARG;
-    return output_batch_impl(ix, p, b, reads, hits, out, nullptr, nullptr, stream);
-}
-
-// ------------------------------------------------------------------------------------------------
-// gm_output_batch_text = gm_output_batch with a different ending: the SAM rows leave as finished text (src/Driver.cpp:2146-2217,
-// ScoredSeq::get_SAM inc/ScoredSeq.h:293-404, reverse_comp / reverse_CIGAR inc/SequenceOperations.h:56-123), written by
-// k_out_text_sizes / k_out_text_rows (gm_output.hip) from the records and the CIGAR pool where k_out_write left them.
-// ------------------------------------------------------------------------------------------------
-extern "C" int gm_output_batch_text(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_read_text* rt, const gm_hits* hits, gm_sam_text* out,
-                                    void* stream) {
+// ---- the seven entry points: fill the call, run it ----
+// The check they share, in the order every one of them answers: ix, a host-only index, the other pointers, then what the form needs
+static int out_entry_check(const gm_index* ix, const gm_params* p, const gm_batch* b, const OutCall& c) {
+    auto named = [&c](const char* why) { return std::string(c.who) + ": " + why; };
     if (!ix) return GM_E_ARG;
-    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    if (!p || !b || !reads || !hits || !out) return GM_E_ARG;
-    if (!rt) { gm_set_error("gm_output_batch_text: gm_read_text is NULL"); return GM_E_ARG; }
-    if (!out->text && out->text_cap) { gm_set_error("gm_sam_text: text is NULL"); return GM_E_ARG; }
-    return output_batch_impl(ix, p, b, reads, hits, nullptr, rt, out, stream);
-}
-
-extern "C" int gm_output_batch_text_resident(gm_index* ix, const gm_params* p, gm_batch* b, const gm_hits* hits, gm_sam_text* out, void* stream) {
-    if (!ix) return GM_E_ARG;
-    if (ix->host_only) { gm_set_error("gm_output_batch_text_resident: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    if (!p || !b || !hits || !out) return GM_E_ARG;
-    if (!b->text_block || !b->text_pools) { gm_set_error("gm_output_batch_text_resident: the batch holds no names from gm_batch_upload_text"); return GM_E_ARG; }
-    if (!out->text && out->text_cap) { gm_set_error("gm_sam_text: text is NULL"); return GM_E_ARG; }
-    gm_reads reads{};
-    reads.n = b->n; reads.stride = b->stride;
-    return output_batch_impl(ix, p, b, &reads, hits, nullptr, nullptr, out, stream);
-}
-
-// gm_output_batch_text / _text_resident with the rows as BAM records inside BGZF blocks (k_bam_sizes / k_bam_rows / k_bgzf_*, gm_bam.hip)
-static int bam_out_check(const char* who, gm_bam_out* out) {
-    out->len = 0; out->raw_len = 0; out->n_recs = 0;
-    if (!gm_bgzf_level_ok(out->level)) { gm_set_error(std::string(who) + ": gm_bam_out.level: " + gm_bgzf_level_text(out->level)); return GM_E_ARG; }
-    if (!out->data && out->cap) { gm_set_error(std::string(who) + ": gm_bam_out.data is NULL"); return GM_E_ARG; }
+    if (ix->host_only) {
+        const char* why = "no usable HIP device (host-only index)";
+        gm_set_error(c.needs & OUT_PLAIN_NO_DEVICE ? std::string(why) : named(why));
+        return GM_E_NO_DEVICE;
+    }
+    if (!p || !b || (!c.reads && !(c.needs & OUT_NEEDS_POOLS)) || !c.hits || !c.dest) return GM_E_ARG;
+    if ((c.needs & OUT_NEEDS_RT) && !c.rt) { gm_set_error(named("gm_read_text is NULL")); return GM_E_ARG; }
+    if ((c.needs & OUT_NEEDS_POOLS) && (!b->text_block || !b->text_pools)) { gm_set_error(named("the batch holds no names from gm_batch_upload_text")); return GM_E_ARG; }
     return GM_OK;
 }
 
+// The check, then the steps.  A resident form takes no gm_reads (the steps ask it for n only).  The sorted sink claims its sequence
+// number before the steps and gives it back when they fail (a no-op once rows of the block are in the arena).
+static int output_call(gm_index* ix, const gm_params* p, gm_batch* b, OutCall c, void* stream) {
+    if (const int rc = out_entry_check(ix, p, b, c)) return rc;
+    gm_reads resident{};
+    if (c.needs & OUT_NEEDS_POOLS) { resident.n = b->n; resident.stride = b->stride; c.reads = &resident; }
+    if (c.sink != OutCall::sorted) return output_batch(ix, p, b, c, stream);
+    if (const int rc = gm_samsort_claim(c.sorter(), ix, c.seq)) return rc;
+    const int rc = output_batch(ix, p, b, c, stream);
+    if (rc != GM_OK) gm_samsort_release(c.sorter(), c.seq);
+    return rc;
+}
+
+extern "C" int gm_output_batch(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_hits* hits, gm_sam_out* out, void* stream) {
+    return output_call(ix, p, b, { "gm_output_batch", OutCall::records, 0, reads, hits, nullptr, 0, out }, stream);
+}
+
+// gm_output_batch with a different ending: the SAM rows leave as finished text (src/Driver.cpp:2146-2217, ScoredSeq::get_SAM
+// inc/ScoredSeq.h:293-404, reverse_comp / reverse_CIGAR inc/SequenceOperations.h:56-123), written by k_out_text_sizes / k_out_text_rows
+// (gm_output.hip) from the records and the CIGAR pool where k_out_write left them
+extern "C" int gm_output_batch_text(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_read_text* rt, const gm_hits* hits, gm_sam_text* out,
+                                    void* stream) {
+    return output_call(ix, p, b, { "gm_output_batch_text", OutCall::text, OUT_NEEDS_RT | OUT_PLAIN_NO_DEVICE, reads, hits, rt, 0, out }, stream);
+}
+
+extern "C" int gm_output_batch_text_resident(gm_index* ix, const gm_params* p, gm_batch* b, const gm_hits* hits, gm_sam_text* out, void* stream) {
+    return output_call(ix, p, b, { "gm_output_batch_text_resident", OutCall::text, OUT_NEEDS_POOLS, nullptr, hits, nullptr, 0, out }, stream);
+}
+
+// the rows as BAM records inside BGZF blocks (k_bam_sizes / k_bam_rows / k_bgzf_*, gm_bam.hip)
 extern "C" int gm_output_batch_bam(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_read_text* rt, const gm_hits* hits, gm_bam_out* out,
                                    void* stream) {
-    if (!ix) return GM_E_ARG;
-    if (ix->host_only) { gm_set_error("gm_output_batch_bam: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    if (!p || !b || !reads || !hits || !out) return GM_E_ARG;
-    if (!rt) { gm_set_error("gm_output_batch_bam: gm_read_text is NULL"); return GM_E_ARG; }
-    if (const int rc = bam_out_check("gm_output_batch_bam", out)) return rc;
-    gm_sam_text kept{};
-    return output_batch_impl(ix, p, b, reads, hits, nullptr, rt, &kept, stream, nullptr, 0, out);
+    return output_call(ix, p, b, { "gm_output_batch_bam", OutCall::bam, OUT_NEEDS_RT, reads, hits, rt, 0, out }, stream);
 }
 
 extern "C" int gm_output_batch_bam_resident(gm_index* ix, const gm_params* p, gm_batch* b, const gm_hits* hits, gm_bam_out* out, void* stream) {
-    if (!ix) return GM_E_ARG;
-    if (ix->host_only) { gm_set_error("gm_output_batch_bam_resident: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    if (!p || !b || !hits || !out) return GM_E_ARG;
-    if (!b->text_block || !b->text_pools) { gm_set_error("gm_output_batch_bam_resident: the batch holds no names from gm_batch_upload_text"); return GM_E_ARG; }
-    if (const int rc = bam_out_check("gm_output_batch_bam_resident", out)) return rc;
-    gm_reads reads{};
-    reads.n = b->n; reads.stride = b->stride;
-    gm_sam_text kept{};
-    return output_batch_impl(ix, p, b, &reads, hits, nullptr, nullptr, &kept, stream, nullptr, 0, out);
+    return output_call(ix, p, b, { "gm_output_batch_bam_resident", OutCall::bam, OUT_NEEDS_POOLS, nullptr, hits, nullptr, 0, out }, stream);
 }
 
 extern "C" int gm_batch_bam_times(gm_batch* b, double* ms, uint64_t* bytes) {
@@ -2047,32 +2163,14 @@ extern "C" int gm_batch_bam_times(gm_batch* b, double* ms, uint64_t* bytes) {
     return GM_OK;
 }
 
-// gm_output_batch_text / _text_resident with the text kept in HBM: appended to the sorter's arena under `seq` (gm_samsort.hip)
+// the rows kept in HBM: appended to the sorter's arena under `seq` (gm_samsort.hip)
 extern "C" int gm_output_batch_sorted(gm_index* ix, const gm_params* p, gm_batch* b, const gm_reads* reads, const gm_read_text* rt, const gm_hits* hits, gm_sam_sorter* sorter,
                                       uint64_t seq, void* stream) {
-    if (!ix) return GM_E_ARG;
-    if (ix->host_only) { gm_set_error("gm_output_batch_sorted: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    if (!p || !b || !reads || !hits || !sorter) return GM_E_ARG;
-    if (!rt) { gm_set_error("gm_output_batch_sorted: gm_read_text is NULL"); return GM_E_ARG; }
-    if (const int rc = gm_samsort_claim(sorter, ix, seq)) return rc;
-    gm_sam_text kept{};
-    const int rc = output_batch_impl(ix, p, b, reads, hits, nullptr, rt, &kept, stream, sorter, seq);
-    if (rc != GM_OK) gm_samsort_release(sorter, seq);             // (a no-op once rows of the block are in the arena)
-    return rc;
+    return output_call(ix, p, b, { "gm_output_batch_sorted", OutCall::sorted, OUT_NEEDS_RT, reads, hits, rt, seq, sorter }, stream);
 }
 
 extern "C" int gm_output_batch_sorted_resident(gm_index* ix, const gm_params* p, gm_batch* b, const gm_hits* hits, gm_sam_sorter* sorter, uint64_t seq, void* stream) {
-    if (!ix) return GM_E_ARG;
-    if (ix->host_only) { gm_set_error("gm_output_batch_sorted_resident: no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
-    if (!p || !b || !hits || !sorter) return GM_E_ARG;
-    if (!b->text_block || !b->text_pools) { gm_set_error("gm_output_batch_sorted_resident: the batch holds no names from gm_batch_upload_text"); return GM_E_ARG; }
-    if (const int rc = gm_samsort_claim(sorter, ix, seq)) return rc;
-    gm_reads reads{};
-    reads.n = b->n; reads.stride = b->stride;
-    gm_sam_text kept{};
-    const int rc = output_batch_impl(ix, p, b, &reads, hits, nullptr, nullptr, &kept, stream, sorter, seq);
-    if (rc != GM_OK) gm_samsort_release(sorter, seq);
-    return rc;
+    return output_call(ix, p, b, { "gm_output_batch_sorted_resident", OutCall::sorted, OUT_NEEDS_POOLS, nullptr, hits, nullptr, seq, sorter }, stream);
 }
 
 // gm_batch_upload_text on a batch of its own, the rows brought back (unit level, parity tests)

@@ -325,3 +325,67 @@ def test_sorter_read_bgzf_returns_whole_blocks(abi, level):
         api.SamSorter(abi["ix"]).read_bgzf(70000, level=2)
     assert e.value.code == -1
     s.destroy()
+
+
+# ---- a caller's own hits (stamp 0: validated and uploaded again) through every sink -------------------------------------------------
+def test_a_callers_own_hits_give_what_the_resident_hits_give_through_every_sink(syn_fa, syn_reads, syn_fq):
+    ix = g.Index(syn_fa, device=0, flags=g.GM_INDEX_FULL_SA)
+    p = g.Params()
+    rd = syn_reads[:300]
+    names = [r[0].encode() for r in rd]
+    B, Q, Ln = g.pack_reads([r[1] for r in rd], [r[2][:len(r[1])] for r in rd])
+    batch = g.Batch(ix, len(rd), B.shape[1])
+
+    def own(res):
+        h = api.gm_hits()
+        C.memmove(C.byref(h), C.byref(res["_struct"]), C.sizeof(h))
+        assert h.stamp != 0
+        h.stamp = 0
+        return dict(res, _struct=h)
+
+    def sorted_rows(res, rows, names):
+        s = api.SamSorter(ix, rows=rows)
+        s.add_block(batch, p, res, 0, names=names)
+        n_rows, n_bytes = s.finish()
+        out = s.text()
+        s.destroy()
+        return n_rows, n_bytes, out
+
+    def every_sink(res, names):
+        """(what each sink returned, the track after each); names None: the resident forms"""
+        sinks = [lambda: batch.output_text(p, res, names) if names else batch.output_text_resident(p, res),
+                 lambda: batch.output_bam(p, res, names, level=0) if names else batch.output_bam_resident(p, res, level=0),
+                 lambda: batch.output_bam(p, res, names, level=1) if names else batch.output_bam_resident(p, res, level=1),
+                 lambda: sorted_rows(res, "text", names), lambda: sorted_rows(res, "bam", names)]
+        got, cov = [], []
+        for sink in sinks:
+            ix.coverage_reset(8)
+            got.append(sink())
+            cov.append(ix.coverage_download())
+        return got, cov
+
+    res = batch.map(p, B, Q, Ln)
+    want, want_cov = every_sink(res, names)                                   # the resident hits first: a caller's version takes their place
+    got, got_cov = every_sink(own(res), names)
+    text, row_off = want[0]
+    assert text.count(b"\n") > 150 and len(row_off) == text.count(b"\n") + 1
+    assert got[0][0] == text and np.array_equal(got[0][1], row_off)
+    assert got[1:] == want[1:]
+    assert len(want[1]) > len(want[2]) > 28 and want[3][0] == want[4][0] == len(row_off) - 1 and want[3][2] != want[4][2]
+    for a, b in zip(got_cov, want_cov):
+        same_track(a, b)
+    batch.destroy()
+
+    # the pools of gm_batch_upload_text with a caller's own hits
+    lines = open(syn_fq, "rb").read().splitlines(keepends=True)
+    batch = g.Batch(ix, 300, 2048)
+    assert batch.upload_text(p, b"".join(lines[:4 * 300]), want_recs=False)["n"] == 300
+    res = batch.map_text(p)
+    ix.coverage_reset(8)
+    want = batch.output_text_resident(p, res)
+    want_cov = ix.coverage_download()
+    ix.coverage_reset(8)
+    got = batch.output_text_resident(p, own(res))
+    assert want[0].count(b"\n") > 150 and got[0] == want[0] and np.array_equal(got[1], want[1])
+    same_track(ix.coverage_download(), want_cov)
+    batch.destroy(); ix.close()

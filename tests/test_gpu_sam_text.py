@@ -281,6 +281,42 @@ def test_abi_text_capacity_reports_the_needed_size(syn_fa, syn_reads):
     batch.destroy(); ix.close()
 
 
+def test_abi_records_capacity_reports_the_needed_sizes_and_deposits_once(syn_fa, syn_reads):
+    """gm_output_batch with room for one record and one CIGAR byte: GM_E_CAPACITY with both sizes, nothing deposited; the call repeated
+    with exactly those sizes gives the records, CIGARs and track of a call that had room from the start"""
+    import ctypes as C
+    from gnumap_amd import api
+    ix = g.Index(syn_fa, device=0, flags=g.GM_INDEX_FULL_SA)
+    p = g.Params()
+    rd = syn_reads[:300]
+    B, Q, Ln = g.pack_reads([r[1] for r in rd], [r[2][:len(r[1])] for r in rd])
+    batch = g.Batch(ix, len(rd), B.shape[1])
+    ix.coverage_reset(8)
+    want_recs, want_cigars = batch.output(p, batch.map(p, B, Q, Ln))
+    want_cov = ix.coverage_download()
+    assert len(want_recs) > 150
+
+    def call(res, rcap, ccap):
+        recs = np.zeros(max(rcap, 1), api.SAM_DTYPE); pool = np.zeros(max(ccap, 1), np.uint8)
+        so = api.gm_sam_out(); so.recs = recs.ctypes.data; so.recs_cap = rcap; so.cigar_pool = pool.ctypes.data; so.cigar_cap = ccap
+        rc = g.lib().gm_output_batch(ix.h, C.byref(p.c), batch.h, C.byref(res["_reads"]), C.byref(res["_struct"]), C.byref(so), None)
+        return rc, so, recs, pool
+
+    ix.coverage_reset(8)
+    res = batch.map(p, B, Q, Ln)
+    rc, so, _, _ = call(res, 1, 1)
+    assert rc == api.GM_E_CAPACITY
+    assert so.recs_cap == so.n_recs == len(want_recs) and so.cigar_cap == so.cigar_len > len(want_recs)
+    assert float(ix.coverage_download().sum()) == 0.0                # returned before anything was deposited
+    rc, so2, recs, pool = call(res, int(so.recs_cap), int(so.cigar_cap))
+    assert rc == 0 and so2.n_recs == so.n_recs and so2.cigar_len == so.cigar_len
+    assert all(np.ascontiguousarray(recs[f]).tobytes() == np.ascontiguousarray(want_recs[f]).tobytes() for f in want_recs.dtype.names)
+    raw = pool.tobytes() + b"\0"
+    assert [raw[o:raw.index(b"\0", o)] for o in recs["cigar_off"]] == want_cigars
+    same_track(ix.coverage_download(), want_cov)                     # deposited once
+    batch.destroy(); ix.close()
+
+
 def test_abi_text_long_name_lower_case_n_bases_and_quality_tails(syn_fa, syn_reads):
     ix = g.Index(syn_fa, device=0, flags=g.GM_INDEX_FULL_SA)
     p = g.Params(print_all_sam=1)

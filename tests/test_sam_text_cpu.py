@@ -42,6 +42,17 @@ def test_text_calls_refuse_a_host_only_index(syn_fa):
     ix.close()
 
 
+def test_records_call_refuses_a_host_only_index(syn_fa):
+    ix = g.Index(syn_fa, flags=g.GM_INDEX_HOST_ONLY)
+    lib = g.lib()
+    p = g.Params()
+    reads = api.gm_reads(); hits = api.gm_hits(); out = api.gm_sam_out()
+    rc = lib.gm_output_batch(ix.h, C.byref(p.c), None, C.byref(reads), C.byref(hits), C.byref(out), None)
+    assert rc == GM_E_NO_DEVICE and b"no usable HIP device" in lib.gm_last_error()
+    assert lib.gm_output_batch(None, C.byref(p.c), None, C.byref(reads), C.byref(hits), C.byref(out), None) == GM_E_ARG
+    ix.close()
+
+
 @pytest.mark.parametrize("flag, word", [("--sam_shards=0", "sam_shards"), ("--sam_shards=65", "sam_shards"), ("--sam_shards=-3", "sam_shards"),
                                         ("--sam_shards=two", "sam_shards"), ("--sam_text=bogus", "sam_text")])
 def test_driver_rejects_bad_values_before_touching_a_device(flag, word, tmp_path):
