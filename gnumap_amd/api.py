@@ -121,7 +121,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_index_contig_offset", "gm_index_window", "gm_params_default", "gm_params_finalize", "gm_params_load_subst", "gm_batch_create", "gm_batch_destroy",
            "gm_batch_upload", "gm_map_batch_device", "gm_batch_counters", "gm_batch_path", "gm_batch_pair_flagged", "gm_batch_set_profiling", "gm_batch_kernel_times", "gm_kernel_name",
            "gm_batch_raw_hits", "gm_stream_create", "gm_stream_destroy", "gm_host_alloc", "gm_host_free", "gm_map_batch", "gm_output_batch",
-           "gm_output_batch_text", "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait", "gm_dev_fmt_g6", "gm_dev_fmt_e2",
+           "gm_output_batch_text", "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait", "gm_dev_fmt_g6", "gm_dev_fmt_e2", "gm_dev_scan_u32",
            "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
            "gm_coverage_device_ptr", "gm_coverage_add", "gm_coverage_download", "gm_coverage_allreduce", "gm_coverage_write_sgr", "gm_coverage_enable_nuc", "gm_coverage_nuc_device_ptr",
            "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls",
@@ -188,6 +188,7 @@ def load_library():
                                        C.POINTER(gm_sam_text), C.c_void_p]
     L.gm_dev_fmt_g6.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_fmt_e2.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.gm_dev_scan_u32.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p]
     L.gm_dev_sa_interval.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
     L.gm_dev_nw_score.argtypes = [C.c_void_p, C.POINTER(gm_params), C.POINTER(gm_reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -460,6 +461,13 @@ class Index:
         _chk(lib().gm_dev_fmt_e2(self.h, v.ctypes.data, n, out.ctypes.data, ln.ctypes.data))
         raw = out.tobytes()
         return [raw[16 * i:16 * i + int(ln[i])] for i in range(n)]
+
+    def dev_scan_u32(self, values):
+        """gm_dev_scan_u32: the exclusive 64-bit scan of uint32 values as the map and output steps compute their offsets; n + 1 uint64"""
+        v = np.ascontiguousarray(values, np.uint32); n = len(v)
+        out = np.zeros(n + 1, np.uint64)
+        _chk(lib().gm_dev_scan_u32(self.h, v.ctypes.data, n, out.ctypes.data))
+        return out
 
     # ---- coverage ----
     def coverage_reset(self, bin_size):

@@ -103,7 +103,7 @@ int gmk_adaptor_cigar_room(const GmDevMatch* matches, uint32_t n_m, const uint16
 int gmk_adaptor_trim(const uint8_t* bases, uint32_t stride, const uint16_t* len, uint32_t n, const uint8_t* adaptor, uint32_t a_len, uint16_t* out_len, void* stream) {
     if (n == 0) return 0;
     if (a_len == 0 || a_len > GM_ADAPTOR_MAX || stride % 8u != 0 || stride > GA_MAX_LEN) return (int)hipErrorInvalidValue;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3) / 4, 256ull * 8 * 4);
+    const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>(((uint64_t)n + 3) / 4, 256ull * 8 * 4));
     hipLaunchKernelGGL(k_adaptor_trim, dim3(grid), dim3(256), 0, S_(stream), bases, stride, len, n, adaptor, a_len, out_len);
     return (int)hipGetLastError();
 }

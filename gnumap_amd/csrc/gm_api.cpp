@@ -2234,6 +2234,29 @@ extern "C" int gm_dev_fmt_g6(gm_index* ix, const double* v, uint32_t n, char* ou
 // gm_put_e2_hd the same way: "%.2e" as k_track_rows prints the p-value of --snp's ninth column
 extern "C" int gm_dev_fmt_e2(gm_index* ix, const double* v, uint32_t n, char* out, uint8_t* len) { return dev_fmt_probe(ix, v, n, out, len, gmk_fmt_e2); }
 
+// gmk_scan_u32 on values of the caller's: out[i] = in[0] + .. + in[i - 1] in 64 bits, out[n] the total (the scan behind every offset
+// array of the map and output steps).  The scratch is sized as those steps size theirs
+extern "C" int gm_dev_scan_u32(gm_index* ix, const uint32_t* in, uint64_t n, uint64_t* out) {
+    if (!ix || !out || (n && !in)) return GM_E_ARG;
+    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    if (n > (1ull << 32)) { gm_set_error("gm_dev_scan_u32: more than 2^32 values"); return GM_E_ARG; }
+    HIPCHK(hipSetDevice(ix->device));
+    DevBuf din, dout, dtmp;
+    int rc = GM_OK;
+    if (din.ensure((size_t)n * 4 + 16) || dout.ensure(((size_t)n + 1) * 8) || dtmp.ensure(((size_t)n / 1024 + 8) * 8)) rc = GM_E_NOMEM;
+    auto run = [&]() -> int {
+        if (n) HIPCHK(hipMemcpy(din.p, in, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(dout.p, 0xFF, ((size_t)n + 1) * 8));                  // (a value the scan does not write shows)
+        KCHK(gmk_scan_u32(din.as<uint32_t>(), n, dout.as<uint64_t>(), dtmp.as<unsigned long long>(), nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(out, dout.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
+        return GM_OK;
+    };
+    if (rc == GM_OK) rc = run();
+    din.release(); dout.release(); dtmp.release();
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------------
 // enqueue / wait forms of the two batch calls: a caller thread hands a block to the batch's service thread and goes on with the next
 // block on another batch; uploads, device work and the fp64 passes of different batches overlap without one caller thread per batch.

@@ -630,7 +630,7 @@ int gmk_bam_sizes(const GmDevText& t, uint32_t* meta, void* stream) {
 
 int gmk_bam_rows(const GmDevBatch& b, const GmDevText& t, const uint32_t* meta, void* stream) {
     if (t.n_recs == 0) return 0;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((t.n_recs + 3) / 4, 4096);
+    const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_recs + 3) / 4, 4096));
     hipLaunchKernelGGL(k_bam_rows, dim3(grid), dim3(256), 0, S_(stream), b, t, meta);
     return (int)hipGetLastError();
 }

@@ -233,7 +233,7 @@ static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 int gmk_nw_band(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint32_t n_cands, int G, void* stream) {
     if (b.n == 0) return 0;
-    const uint32_t grid = std::min<uint32_t>(16384u, std::max<uint32_t>(256u, n_cands / 512u));
+    const uint32_t grid = gm_test_grid(std::min<uint32_t>(16384u, std::max<uint32_t>(256u, n_cands / 512u)));
     hipLaunchKernelGGL(k_nw_band, dim3(grid), dim3(GB_NT), 0, S_(stream), ix, p, b, n_cands, G);
     return (int)hipGetLastError();
 }
@@ -243,8 +243,12 @@ int gmk_traceback_band(const GmDevIndex& ix, const GmDevParams& p, const GmDevBa
                        uint32_t ops_words, uint16_t* ops_len, const uint8_t* emit, uint32_t* cig_cnt, uint32_t* max_span, int G, void* stream) {
     if (n == 0) return 0;
     const uint64_t rows = (uint64_t)b.stride + 1;
-    const uint64_t per = b.band_moves ? b.band_moves_words / rows : 0;
+    uint64_t per = b.band_moves ? b.band_moves_words / rows : 0;
     if (per == 0) return (int)hipErrorInvalidValue;
+    // (k_traceback_band takes one item per lane, no loop: the test cap on workgroups bounds the ITEMS of a launch instead, so that a small
+    //  block reaches the later launches with i0 > 0)
+    const long long test_cap = gm_opt_ll("GM_TEST_GRID_CAP", 0);
+    if (test_cap > 0) per = std::min<uint64_t>(per, (uint64_t)test_cap * GB_NT);
     for (uint64_t i0 = 0; i0 < n; i0 += per) {
         const uint32_t ni = (uint32_t)std::min<uint64_t>(per, n - i0);
         hipLaunchKernelGGL(k_traceback_band, dim3((ni + GB_NT - 1) / GB_NT), dim3(GB_NT), 0, S_(stream), ix, p, b, items, (uint32_t)i0, ni, b.band_moves, ops,

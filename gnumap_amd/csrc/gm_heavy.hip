@@ -146,7 +146,7 @@ int gmk_heavy_collect(const GmDevBatch& b, uint32_t heavy_min, uint32_t* n_heavy
     if (b.n == 0) return 0;
     // (list form: the count is on the device; the list is a few reads per thousand - a quarter of the full form's grid is plenty)
     const unsigned long long items = rlist ? (b.n + 3ull) / 4 : 2ull * b.n / 4;
-    const uint32_t grid = (uint32_t)std::min<unsigned long long>((items + 255) / 256 + 1, rlist ? 256ull : 1024ull);
+    const uint32_t grid = gm_test_grid((uint32_t)std::min<unsigned long long>((items + 255) / 256 + 1, rlist ? 256ull : 1024ull));
     hipLaunchKernelGGL(k_heavy_collect, dim3(grid), dim3(256), 0, S_(stream), b, heavy_min, n_heavy, heavy_list, sum_counters, rlist, n_rlist);
     return (int)hipGetLastError();
 }

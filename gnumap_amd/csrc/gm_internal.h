@@ -247,6 +247,13 @@ extern "C++" {
 const char* gm_opt(const char* name);
 inline long long gm_opt_ll(const char* name, long long dflt) { const char* e = gm_opt(name); return e && *e ? atoll(e) : dflt; }
 inline bool gm_opt_is(const char* name, const char* value) { const char* e = gm_opt(name); return e && !strcmp(e, value); }
+// TEST switch GM_TEST_GRID_CAP=N: at most N workgroups for a kernel that strides over its items with gridDim.x, so that a block of a few
+// hundred reads gives every workgroup several trips (what a 10 M-read block does at the launcher's own cap).  Unset or 0: `grid` as it is.
+// Only for launchers whose kernel loops: a kernel that takes one item per workgroup would drop items.
+inline uint32_t gm_test_grid(uint32_t grid) {
+    const long long cap = gm_opt_ll("GM_TEST_GRID_CAP", 0);
+    return cap > 0 && (long long)grid > cap ? (uint32_t)cap : grid;
+}
 int gmk_expand_full_sa(const GmDevIndex& ix, uint32_t* full_sa, void* stream);
 int gmk_build_occ_planes(const GmDevIndex& ix, uint4* planes, uint32_t nblk, void* stream);
 int gmk_build_kmer_table(const GmDevIndex& ix, uint2* tab, int T, void* stream);

@@ -3312,7 +3312,7 @@ int gmk_prep(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, vo
     tr = tr >= 256 ? 256 : (tr / 64) * 64;
     const uint32_t per = tr ? tr : 256;
     const uint32_t pg = resident_grid(k_prep, 256, rows * tr * b.stride, 256 * 3);
-    hipLaunchKernelGGL(k_prep, dim3((uint32_t)std::min<uint64_t>(cdiv(b.n, per), pg)), dim3(256), rows * tr * b.stride, S_(stream), ix, p, b, tr);
+    hipLaunchKernelGGL(k_prep, dim3(gm_test_grid((uint32_t)std::min<uint64_t>(cdiv(b.n, per), pg))), dim3(256), rows * tr * b.stride, S_(stream), ix, p, b, tr);
     return (int)hipGetLastError();
 }
 
@@ -3372,7 +3372,7 @@ int gmk_vote(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, in
         const bool slots_form = kenv ? !strcmp(kenv, "slots") : dense <= 2;      // dense == 2: the 64-slot form; 3: rounds of the block form
         if (slots_form) {                           // default: wave-uniform seed slots + the list kernel for what it hands over
             const int slot_form = dense == 2 ? 64 : slots_hint == 0 ? 0 : slots_hint < 0 ? -1 : slots_hint <= 14 ? 16 : slots_hint <= 22 ? 24 : GMS_SMAX;      // 0 = k_vote_tiny, -1 = k_vote_tiny2
-            const uint32_t lgrid = (uint32_t)std::min<uint64_t>(cdiv(2ull * b.n, 4), 256 * 20);
+            const uint32_t lgrid = gm_test_grid((uint32_t)std::min<uint64_t>(cdiv(2ull * b.n, 4), 256 * 20));
             // the fused form as persistent workgroups with the next read x strands' loads in flight (k_vote_slots_pp): `pp_chunk` consecutive read x
             // strands per workgroup - the pipeline's fill (three round trips) against ~64 votes.  Default for the 64-slot form only (its 20 KB of LDS
             // leave 8 workgroups per CU to hide the three round trips: 133.9 -> 112.8 ms at the chrX shape); the smaller forms have 13 - 16
@@ -3413,7 +3413,7 @@ int gmk_vote(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, in
     const bool sparse_form = !gm_opt_is("GM_VOTE_SPARSE", "0");
     if (sparse_form && b.max_seeds <= 64) {
         hipLaunchKernelGGL(k_vote_sparse, dim3(cdiv(2ull * b.n, 16)), dim3(256), 0, S_(stream), ix, p, b, use_full_sa);
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(cdiv(2ull * b.n, 4), 256 * 20);
+        const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>(cdiv(2ull * b.n, 4), 256 * 20));
         if (b.max_seeds <= 32) hipLaunchKernelGGL(k_vote_fast_list<false>, dim3(grid), dim3(256), 0, S_(stream), ix, p, b, use_full_sa);
         else hipLaunchKernelGGL(k_vote_fast_list<true>, dim3(grid), dim3(256), 0, S_(stream), ix, p, b, use_full_sa);
         return (int)hipGetLastError();
@@ -3454,7 +3454,7 @@ int gmk_vote_list(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& 
     if (b.n == 0) return 0;
     if (p.bucket != nullptr && b.fixed_cnt != nullptr)
         hipLaunchKernelGGL(k_big_collect, dim3((uint32_t)cdiv((2ull * b.n + 15) / 16, 256)), dim3(256), 0, S_(stream), b);
-    const uint32_t lgrid = (uint32_t)std::min<uint64_t>(cdiv(2ull * b.n, 4), 256 * 20);
+    const uint32_t lgrid = gm_test_grid((uint32_t)std::min<uint64_t>(cdiv(2ull * b.n, 4), 256 * 20));
     if (b.max_seeds > 32) hipLaunchKernelGGL(k_vote_fast_list<true>, dim3(lgrid), dim3(256), 0, S_(stream), ix, p, b, use_full_sa);
     else hipLaunchKernelGGL(k_vote_fast_list<false>, dim3(lgrid), dim3(256), 0, S_(stream), ix, p, b, use_full_sa);
     return (int)hipGetLastError();
@@ -3538,7 +3538,7 @@ int gmk_nw(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, uint
     uint32_t threads = 256;                                  // 32 candidates per workgroup; long reads: 8, to stay inside LDS
     if (GM_NW_HDR + (size_t)32 * Lp * 3 > 60 * 1024) threads = 64;
     size_t lds = GM_NW_HDR + (size_t)(threads / 8) * Lp * 3;
-    hipLaunchKernelGGL(k_nw, dim3(threads == 256 ? 2048 : 8192), dim3(threads), lds, S_(stream), ix, p, b, Lp);
+    hipLaunchKernelGGL(k_nw, dim3(gm_test_grid(threads == 256 ? 2048 : 8192)), dim3(threads), lds, S_(stream), ix, p, b, Lp);
     return (int)hipGetLastError();
 }
 
@@ -3549,7 +3549,7 @@ int gmk_scan_hits(const GmDevBatch& b, void* stream) {
 
 int gmk_scatter(const GmDevBatch& b, uint32_t grid, void* stream) {
     if (b.n == 0) return 0;
-    hipLaunchKernelGGL(k_scatter_hits, dim3(grid), dim3(256), 0, S_(stream), b);
+    hipLaunchKernelGGL(k_scatter_hits, dim3(gm_test_grid(grid)), dim3(256), 0, S_(stream), b);
     return (int)hipGetLastError();
 }
 
@@ -3584,12 +3584,14 @@ int gmk_traceback(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& 
             if (mv_bytes + (size_t)ntab * GM_TBV_ENTRIES * 16 > 65536) ntab = 0;          // (the default dynamic-LDS limit: long rows go without the table)
             const size_t lds = mv_bytes + (size_t)ntab * GM_TBV_ENTRIES * 16;
             uint32_t grid = cdiv(n, 128); if (grid > 16384) grid = 16384;
+            grid = gm_test_grid(grid);
             hipLaunchKernelGGL((k_traceback_lane<128>), dim3(grid), dim3(128), lds, S_(stream), ix, p, b, items, n, ops, ops_words, ops_len, Lp, emit, cig_cnt, max_span, ntab);
         } else {
             const size_t mv_bytes = ((size_t)(Lp + 1) * 64 * 2 + 15) & ~(size_t)15;
             if (mv_bytes + (size_t)ntab * GM_TBV_ENTRIES * 16 > 65536) ntab = 0;
             const size_t lds = mv_bytes + (size_t)ntab * GM_TBV_ENTRIES * 16;
             uint32_t grid = cdiv(n, 64); if (grid > 16384) grid = 16384;
+            grid = gm_test_grid(grid);
             hipLaunchKernelGGL((k_traceback_lane<64>), dim3(grid), dim3(64), lds, S_(stream), ix, p, b, items, n, ops, ops_words, ops_len, Lp, emit, cig_cnt, max_span, ntab);
         }
         return (int)hipGetLastError();
@@ -3600,6 +3602,7 @@ int gmk_traceback(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& 
     const uint32_t G = threads / 8;
     size_t lds = GM_NW_HDR + (size_t)G * Lp * 3 + (size_t)G * 7 * mvw * 4;
     uint32_t grid = cdiv(n, G); if (grid > 8192) grid = 8192;
+    grid = gm_test_grid(grid);
     hipLaunchKernelGGL(k_traceback, dim3(grid), dim3(threads), lds, S_(stream), ix, p, b, items, n, ops, ops_words, ops_len, Lp, mvw, emit, cig_cnt, max_span);
     return (int)hipGetLastError();
 }

@@ -820,17 +820,17 @@ int gmk_group_count(const GmDevIndex& ix, const GmDevBatch& b, const GmDevGroup&
     {   // reads with many accepted hits first: what this kernel cannot finish goes to the all-pairs kernel's list
         const size_t lds = (size_t)GO_SET_SLOTS * 16 + (size_t)GO_SET_LIMIT * 4 + 64;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_group_big), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        hipLaunchKernelGGL(k_group_big, dim3(std::min<uint32_t>(b.n, 4096u)), dim3(64), lds, S_(stream), ix, b, g, nw, unique_only, max_matches);
+        hipLaunchKernelGGL(k_group_big, dim3(gm_test_grid(std::min<uint32_t>(b.n, 4096u))), dim3(64), lds, S_(stream), ix, b, g, nw, unique_only, max_matches);
     }
-    hipLaunchKernelGGL(k_group_multi, dim3(std::min<uint32_t>(b.n, 16384u)), dim3(64), 0, S_(stream), ix, b, g, nw, unique_only, max_matches);
+    hipLaunchKernelGGL(k_group_multi, dim3(gm_test_grid(std::min<uint32_t>(b.n, 16384u))), dim3(64), 0, S_(stream), ix, b, g, nw, unique_only, max_matches);
     return (int)hipGetLastError();
 }
 
 int gmk_group_write(const GmDevBatch& b, const GmDevGroup& g, void* stream) {
     if (b.n == 0) return 0;
     hipLaunchKernelGGL(k_group_write_single, dim3(cdiv(b.n, 256)), dim3(256), 0, S_(stream), b, g);
-    hipLaunchKernelGGL(k_group_write_multi, dim3(std::min<uint32_t>(b.n, 16384u)), dim3(64), 0, S_(stream), b, g);
-    hipLaunchKernelGGL(k_group_write_big, dim3(std::min<uint32_t>(b.n, 4096u)), dim3(64), 0, S_(stream), b, g);
+    hipLaunchKernelGGL(k_group_write_multi, dim3(gm_test_grid(std::min<uint32_t>(b.n, 16384u))), dim3(64), 0, S_(stream), b, g);
+    hipLaunchKernelGGL(k_group_write_big, dim3(gm_test_grid(std::min<uint32_t>(b.n, 4096u))), dim3(64), 0, S_(stream), b, g);
     return (int)hipGetLastError();
 }
 
@@ -885,7 +885,7 @@ int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream) {
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_out_text_rows, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((t.n_recs + 3) / 4, (uint64_t)cus * (uint64_t)per_cu);
+    const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_recs + 3) / 4, (uint64_t)cus * (uint64_t)per_cu));
     hipLaunchKernelGGL(k_out_text_rows, dim3(grid), dim3(256), 0, S_(stream), b, t);
     return (int)hipGetLastError();
 }

@@ -426,7 +426,8 @@ int gmk_vote_pair(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& 
     // that small blocks still fill the chip
     const uint32_t npairs = (b.n + 1u) / 2u;
     uint32_t chunk = (uint32_t)std::max<long long>(16, gm_opt_ll("GM_PAIR_CHUNK", 32)) / 16u * 16u;
-    while (chunk > 16u && (npairs + chunk - 1u) / chunk < 4096u) chunk -= 16u;
+    const uint32_t min_grid = (uint32_t)std::max<long long>(1, gm_opt_ll("GM_TEST_PAIR_MIN_GRID", 4096));     // (test switch: 1 keeps GM_PAIR_CHUNK for a small block)
+    while (chunk > 16u && (npairs + chunk - 1u) / chunk < min_grid) chunk -= 16u;
     const dim3 grid((npairs + chunk - 1u) / chunk), blk(64);
     const bool direct = b.fixed_cands == nullptr;
     if (!direct && fallback == nullptr) return (int)hipErrorInvalidValue;

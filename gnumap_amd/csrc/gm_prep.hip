@@ -231,7 +231,7 @@ int gmk_prep_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& 
     if (b.n == 0) return 0;
     if (b.stride > 152) return (int)hipErrorInvalidValue;
     const size_t lds = b.pack ? (size_t)256 * b.pack_words * 4 : 0;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)b.n + 255) / 256, 256ull * 5 * 4);
+    const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>(((uint64_t)b.n + 255) / 256, 256ull * 5 * 4));
     if (b.stride <= 104) hipLaunchKernelGGL((k_prep_rows<13>), dim3(grid), dim3(256), lds, S_(stream), ix, p, b);
     else hipLaunchKernelGGL((k_prep_rows<19>), dim3(grid), dim3(256), lds, S_(stream), ix, p, b);
     return (int)hipGetLastError();

@@ -489,6 +489,9 @@ int gm_dev_fmt_g6(gm_index*, const double* v, uint32_t n, char* out /* n x 16 */
 /* printf("%.2e") as the device prints the p-value of --snp's ninth .gmp column (gm_put_e2_hd), same contract: always 8 characters
  * on its domain (+0.0, 2^-200 <= v < 2^200), len[i] = 0 outside it (negative, -0.0, nan, inf, anything else) */
 int gm_dev_fmt_e2(gm_index*, const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len);
+/* the exclusive scan behind every offset array of the map and output steps, on values of the caller's: out[i] = in[0] + .. + in[i - 1]
+ * in 64 bits, out[n] = the total.  n up to 2^32 */
+int gm_dev_scan_u32(gm_index*, const uint32_t* in, uint64_t n, uint64_t* out /* n + 1 */);
 
 /* bin_seq::pairHMM (src/bin_seq.cpp:60-244) of read read_idx[k] in the orientation of strand[k] against the window at pos[k]:
  * out[k][max_len][5] floats (a, c, g, t, n per window position), max_len = gm_reads.stride */
