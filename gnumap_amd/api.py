@@ -128,7 +128,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_coverage_write_sgr_device", "gm_coverage_write_gmp_device", "gm_coverage_text", "gm_coverage_text_stats",
            "gm_coverage_write_gmp_calls_device", "gm_coverage_calls_text", "gm_coverage_write_vcf",
            "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim",
-           "gm_batch_set_read_format", "gm_index_set_probe_format",
+           "gm_batch_set_read_format", "gm_index_set_probe_format", "gm_batch_set_unmapped_rows", "gm_batch_unmapped_rows",
            "gm_batch_upload_text", "gm_map_batch_text", "gm_output_batch_text_resident", "gm_dev_fastq_rows", "gm_dev_fastq_tile_bytes",
            "gm_sam_sorter_create", "gm_sam_sorter_destroy", "gm_output_batch_sorted", "gm_output_batch_sorted_resident", "gm_sam_sorter_finish",
            "gm_sam_sorter_read", "gm_sam_sorter_stats", "gm_sam_sorter_add_rows",
@@ -247,6 +247,8 @@ def load_library():
     L.gm_sam_sorter_read_bgzf.argtypes = [C.c_void_p, C.c_int, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
     L.gm_sam_sorter_index_begin.argtypes = [C.c_void_p, u64]
     L.gm_sam_sorter_bai.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
+    L.gm_batch_set_unmapped_rows.argtypes = [C.c_void_p, C.c_int]
+    L.gm_batch_unmapped_rows.argtypes = [C.c_void_p, C.POINTER(u64)]
     _LIB = L
     return L
 
@@ -603,6 +605,18 @@ class Batch:
     def set_adaptor(self, adaptor):
         """-A: trim this adaptor (bytes) from the reads of every block uploaded from now on; None or b"" clears it"""
         _chk(lib().gm_batch_set_adaptor(self.h, None if adaptor is None else bytes(adaptor)))
+
+    def set_unmapped_rows(self, on=True):
+        """gm_batch_set_unmapped_rows: from the next call on, output_text / output_text_resident / output_bam / output_bam_resident and
+        SamSorter.add_block write one flag-4 row (tag YU:i:<status>) for every read of the block they write no record for; output()
+        (the records form) is not affected.  Row counts and row offsets then count rows"""
+        _chk(lib().gm_batch_set_unmapped_rows(self.h, int(bool(on))))
+
+    def unmapped_rows(self):
+        """gm_batch_unmapped_rows: the rows of reads without a record that the last row-producing output call wrote"""
+        n = u64()
+        _chk(lib().gm_batch_unmapped_rows(self.h, C.byref(n)))
+        return int(n.value)
 
     def trimmed_len(self):
         """the lengths the kernels used for the block uploaded last (what the adaptor trim kept; the uploaded lengths without one)"""

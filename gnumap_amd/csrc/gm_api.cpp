@@ -58,6 +58,7 @@ struct gm_batch {
         snp_scratch, snp_hmm,           // --snp: forward matrices of a chunk of kept sequences, their 5 floats per window position
         t_names, t_nameoff, t_qtail, t_qtailoff, t_slots, t_rowlen, t_rowoff, t_text, t_bad,     // gm_output_batch_text: the block's names, tails and row offsets, the text
         t_bammeta,                      // gm_output_batch_bam: operations and bin of every record (k_bam_sizes)
+        t_status, t_rowcnt, t_rowflag, t_rowfirst, t_rowucum, t_rowsrc,        // gm_batch_set_unmapped_rows: the reads' status bytes and the row source (gmk_row_source)
         full_len, d_adaptor,            // -A: the lengths as uploaded (`len` then holds what k_adaptor_trim keeps), the adaptor's characters
         rt_text, rt_tilecnt, rt_tileoff, rt_lineat, rt_lsum, rt_lin, rt_recs, rt_nlen, rt_tlen, rt_meta;      // gm_batch_upload_text: the FASTQ text and what k_rt_* make of it
     GmBgzfBufs bz;                      // gm_output_batch_bam: the BGZF blocks of the block's records
@@ -69,6 +70,8 @@ struct gm_batch {
     PinBuf h_rt;                        // its read-backs
     std::string adaptor;                // gm_batch_set_adaptor; empty = none (no launch, no copy, no wait in gm_batch_upload)
     int read_format = GM_READS_FASTQ;   // gm_batch_set_read_format: the blocks uploaded from now on
+    bool unmapped_rows = false;         // gm_batch_set_unmapped_rows: a read without a record gets a flag-4 row from the row-producing output calls
+    uint64_t n_unmapped = 0;            // ... and how many the last output call wrote (gm_batch_unmapped_rows)
     bool fasta = false;                 // the block that is resident was uploaded as FASTA (GmDevBatch::fasta)
     bool adaptor_dirty = false;         // d_adaptor does not hold `adaptor` yet
     PinBuf h_top, h_hbegin, h_ord, h_post, h_mapq, h_emit, h_mhit, h_stat;      // h_stat: the small status words a phase reads back (page-locked: one short DMA)
@@ -557,6 +560,7 @@ extern "C" void gm_batch_destroy(gm_batch* b) {
                       &b->scan_tmp, &b->o_small, &b->o_posmatch, &b->o_post, &b->o_mapq, &b->o_emit, &b->o_reccnt, &b->o_cigcnt, &b->o_cigall, &b->o_recoff, &b->o_cigoff,
                       &b->o_recs, &b->o_pool, &b->o_codes, &b->snp_scratch, &b->snp_hmm, &b->pair_fb, &b->pair_list,
                       &b->t_names, &b->t_nameoff, &b->t_qtail, &b->t_qtailoff, &b->t_slots, &b->t_rowlen, &b->t_rowoff, &b->t_text, &b->t_bad, &b->t_bammeta, &b->full_len, &b->d_adaptor,
+                      &b->t_status, &b->t_rowcnt, &b->t_rowflag, &b->t_rowfirst, &b->t_rowucum, &b->t_rowsrc,
                       &b->rt_text, &b->rt_tilecnt, &b->rt_tileoff, &b->rt_lineat, &b->rt_lsum, &b->rt_lin, &b->rt_recs, &b->rt_nlen, &b->rt_tlen, &b->rt_meta };
     for (DevBuf* d : all) d->release();
     b->bz.release();
@@ -800,6 +804,20 @@ extern "C" int gm_batch_set_read_format(gm_batch* b, int format) {
     if (!b) { gm_set_error("gm_batch_set_read_format: batch is NULL"); return GM_E_ARG; }
     if (format != GM_READS_FASTQ && format != GM_READS_FASTA) { gm_set_error("gm_batch_set_read_format: GM_READS_FASTQ or GM_READS_FASTA"); return GM_E_ARG; }
     b->read_format = format;
+    return GM_OK;
+}
+
+// A defined extension: the reference prints no row for a read that does not map.  Takes effect with the next
+// row-producing output call; gm_output_batch (records) does not read it.
+extern "C" int gm_batch_set_unmapped_rows(gm_batch* b, int on) {
+    if (!b) { gm_set_error("gm_batch_set_unmapped_rows: batch is NULL"); return GM_E_ARG; }
+    b->unmapped_rows = on != 0;
+    return GM_OK;
+}
+
+extern "C" int gm_batch_unmapped_rows(gm_batch* b, uint64_t* n) {
+    if (!b || !n) { gm_set_error("gm_batch_unmapped_rows: batch or n is NULL"); return GM_E_ARG; }
+    *n = b->n_unmapped;
     return GM_OK;
 }
 
@@ -1734,6 +1752,8 @@ struct OutState {
     uint32_t n, n_m; uint64_t n_p;             // out_check_hits: reads, kept sequences (matches), position slots in use,
     bool resident, snp, nuc; uint32_t ops_words, codes_stride;                 // and what the mode and the stride make of them
     uint64_t n_recs, cig_len; uint32_t max_span;                               // out_count_records
+    bool unmapped;                             // output_batch: a rows sink on a batch with gm_batch_set_unmapped_rows on
+    uint64_t n_rows, n_unmapped;               // out_row_inputs: the rows (the records, + the reads without one when `unmapped`), and those reads
     GmDevText t;                               // out_row_inputs (t.text: out_write_rows)
     uint64_t text_len; unsigned long long bad_row;                             // out_count_rows
 };
@@ -1927,7 +1947,21 @@ static int out_write_records(gm_index* ix, const gm_params* p, gm_batch* b, cons
 static int out_row_inputs(gm_index* ix, const gm_params* p, gm_batch* b, const OutCall& c, OutState& s, hipStream_t st) {
     const gm_read_text* rt = c.rt;
     const bool pools = !rt, bam = c.bam_rows();
-    const uint32_t n = s.n; const uint64_t n_recs = s.n_recs;
+    const uint32_t n = s.n;
+    s.n_rows = s.n_recs; s.n_unmapped = 0;
+    if (s.unmapped) {
+        // the row source: the status bytes go up, the records are counted per read, and the one number the sizes below need comes back
+        if (b->t_status.ensure((size_t)n + 16) || b->t_rowcnt.ensure((size_t)n * 4) || b->t_rowflag.ensure((size_t)n * 4) || b->t_rowfirst.ensure(((size_t)n + 1) * 8) ||
+            b->t_rowucum.ensure(((size_t)n + 1) * 8) || b->t_rowsrc.ensure((size_t)(s.n_recs + n) * 8) || b->scan_tmp.ensure(((size_t)n / 1024 + 8) * 8)) return GM_E_NOMEM;
+        HIPCHK(hipMemcpyAsync(b->t_status.p, c.hits->status, n, hipMemcpyHostToDevice, st));
+        KCHK(gmk_row_source(s.n_recs ? b->o_recs.as<GmDevSamRec>() : nullptr, s.n_recs, n, b->t_rowcnt.as<uint32_t>(), b->t_rowflag.as<uint32_t>(), b->t_rowfirst.as<uint64_t>(),
+                            b->t_rowucum.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), b->t_rowsrc.as<unsigned long long>(), st));
+        HIPCHK(hipMemcpyAsync(&s.n_unmapped, b->t_rowucum.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (s.n_unmapped > n) { gm_set_error(std::string(c.who) + ": the row source counts more reads without a record than the block has reads"); return GM_E_HIP; }
+        s.n_rows = s.n_recs + s.n_unmapped;
+    }
+    const uint64_t n_recs = s.n_rows;                              // (what is sized below is per row)
     if (const int rc = index_cnames(ix)) return rc;                // contig names, once per index
     // the pools of a text block start at offset 0 and are in place; a block without a quality tail passes none, as a caller would
     const bool tails = pools ? b->text_tail_bytes != 0 : rt->qual_tail_off != nullptr;
@@ -1948,7 +1982,9 @@ static int out_row_inputs(gm_index* ix, const gm_params* p, gm_batch* b, const O
         HIPCHK(hipMemcpyAsync(b->t_qtailoff.p, rt->qual_tail_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
     }
     GmDevText& t = s.t;
-    t.recs = b->o_recs.as<GmDevSamRec>(); t.n_recs = n_recs; t.pool = b->o_pool.as<char>();
+    t.recs = b->o_recs.as<GmDevSamRec>(); t.n_recs = s.n_recs; t.pool = b->o_pool.as<char>();
+    t.n_rows = s.n_rows; t.n_reads = n;
+    t.row_src = s.unmapped ? b->t_rowsrc.as<unsigned long long>() : nullptr; t.status = s.unmapped ? b->t_status.as<int8_t>() : nullptr;
     t.names = b->t_names.as<char>() - name0; t.name_off = b->t_nameoff.as<uint64_t>();
     t.qtail = tails ? b->t_qtail.as<char>() - tail0 : nullptr; t.qtail_off = tails ? b->t_qtailoff.as<uint64_t>() : nullptr;
     t.cnames = ix->d_cnames.as<char>(); t.cname_off = ix->d_cname_off.as<uint32_t>();
@@ -1968,9 +2004,9 @@ static int out_count_rows(gm_batch* b, const OutCall& c, OutState& s, hipStream_
     if (bam_timed) { for (auto& e : b->bam_ev) if (!e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(b->bam_ev[0], st)); }
     if (bam) KCHK(gmk_bam_sizes(s.t, b->t_bammeta.as<uint32_t>(), st));
     if (bam_timed) HIPCHK(hipEventRecord(b->bam_ev[1], st));
-    KCHK(gmk_scan_u32(s.t.row_len, s.n_recs, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
+    KCHK(gmk_scan_u32(s.t.row_len, s.n_rows, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
     s.bad_row = ~0ull;
-    HIPCHK(hipMemcpyAsync(&s.text_len, b->t_rowoff.as<uint64_t>() + s.n_recs, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&s.text_len, b->t_rowoff.as<uint64_t>() + s.n_rows, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&s.bad_row, b->t_bad.p, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return GM_OK;
@@ -1979,14 +2015,15 @@ static int out_count_rows(gm_batch* b, const OutCall& c, OutState& s, hipStream_
 // The text sink's capacity answer, then the rows: SAM text or BAM records, in the batch's t_text
 static int out_write_rows(gm_batch* b, const OutCall& c, OutState& s, hipStream_t st) {
     const bool bam = c.bam_rows(), bam_timed = bam && b->profiling;
-    const uint64_t n_recs = s.n_recs, text_len = s.text_len;
+    const uint64_t n_recs = s.n_rows, text_len = s.text_len;       // (rows: the records, and with them the reads without one)
     if (s.bad_row != ~0ull) {
         gm_set_error("SAM record " + std::to_string(s.bad_row) + ": XA or XP is outside the range the device prints exactly (2^-200 <= |v| < 2^200)");
         return GM_E_UNSUPPORTED;
     }
+    b->n_unmapped = s.n_unmapped;
     if (c.sink == OutCall::text) {
         gm_sam_text* tout = c.text_out();
-        tout->text_len = text_len;
+        tout->text_len = text_len; tout->n_recs = n_recs;
         const bool rows_fit = !tout->row_off || tout->row_cap >= n_recs + 1;
         if (text_len > tout->text_cap || !rows_fit) {
             tout->text_cap = text_len;
@@ -2014,14 +2051,14 @@ static int out_write_rows(gm_batch* b, const OutCall& c, OutState& s, hipStream_
 // The rows leave: to the caller's buffers; into the sorter's arena, where they stay in HBM (an arena that cannot grow: GM_E_NOMEM from
 // gm_samsort_add); or compressed where they lie, the BGZF blocks to the caller's buffer once it is known to hold them
 static int out_deliver_rows(gm_batch* b, const OutCall& c, const OutState& s, hipStream_t st) {
-    const uint64_t n_recs = s.n_recs, text_len = s.text_len;
+    const uint64_t n_recs = s.n_rows, text_len = s.text_len;
     switch (c.sink) {
     case OutCall::text:
         HIPCHK(hipMemcpyAsync(c.text_out()->text, b->t_text.p, (size_t)text_len, hipMemcpyDeviceToHost, st));
         if (c.text_out()->row_off) HIPCHK(hipMemcpyAsync(c.text_out()->row_off, b->t_rowoff.p, ((size_t)n_recs + 1) * 8, hipMemcpyDeviceToHost, st));
         return GM_OK;
     case OutCall::sorted:
-        return gm_samsort_add(c.sorter(), c.seq, s.t.recs, n_recs, s.t.text, s.t.row_off, text_len, st);
+        return gm_samsort_add(c.sorter(), c.seq, s.t.recs, s.t.row_src, s.n_recs, n_recs, s.t.text, s.t.row_off, text_len, st);
     case OutCall::bam: {
         gm_bam_out* bout = c.bam_out();
         uint64_t z_len = 0;
@@ -2070,6 +2107,9 @@ static int out_deposit(gm_index* ix, gm_batch* b, const OutState& s, hipStream_t
 // deposit is the last step, and the three capacity answers (records, text, BGZF blocks) come from steps before it; so does every other
 // refusal, the sorter's among them (GM_E_NOMEM when its arena cannot grow).  What an earlier step does leave behind says so: the
 // batch's stamp is cleared once a caller's matches have taken the place of the resident ones, its text_pools once a caller's names have.
+// gm_batch_set_unmapped_rows (read by the rows sinks alone; the records sink ignores it): the four row steps size everything by ROWS -
+// the records plus one row for every read without a record - and a block in which nothing matched gives n rows with no traceback,
+// posterior pass or deposit instead of the early GM_OK.
 static int output_batch(gm_index* ix, const gm_params* p, gm_batch* b, const OutCall& c, void* stream) {
     if (const int rc = out_check_call(b, c)) return rc;
     PhaseClock pc(c.rows() ? "gm_output_batch_text" : "gm_output_batch");
@@ -2078,23 +2118,28 @@ static int output_batch(gm_index* ix, const gm_params* p, gm_batch* b, const Out
     OutState s{};
     if (const int rc = sync_params(ix, p, s.dp, st)) return rc;
     if (c.sink == OutCall::records) { c.recs_out()->n_recs = 0; c.recs_out()->cigar_len = 0; }
-    if (!c.hits->n || !c.hits->match_begin[c.hits->n]) return GM_OK;           // nothing matched: no record, no row, no deposit
-    if (const int rc = out_check_hits(ix, p, b, c.hits, s)) return rc;
-    if (const int rc = out_enqueue_traceback(ix, p, b, c.hits, s, st)) return rc;
-    pc.lap("enqueue");
-    if (const int rc = out_host_posteriors(p, b, c.hits, s)) return rc;
-    pc.lap("fp64");
-    if (const int rc = out_count_records(b, s, st)) return rc;
-    pc.lap("traceback+count");
-    if (const int rc = out_write_records(ix, p, b, c, s, st)) return rc;
-    if (c.rows() && s.n_recs) {
+    s.unmapped = c.rows() && b->unmapped_rows;
+    if (c.rows()) b->n_unmapped = 0;
+    const bool matched = c.hits->n && c.hits->match_begin[c.hits->n];
+    if (!matched && !(s.unmapped && c.hits->n)) return GM_OK;                  // nothing matched: no record, no row, no deposit
+    if (matched) {
+        if (const int rc = out_check_hits(ix, p, b, c.hits, s)) return rc;
+        if (const int rc = out_enqueue_traceback(ix, p, b, c.hits, s, st)) return rc;
+        pc.lap("enqueue");
+        if (const int rc = out_host_posteriors(p, b, c.hits, s)) return rc;
+        pc.lap("fp64");
+        if (const int rc = out_count_records(b, s, st)) return rc;
+        pc.lap("traceback+count");
+        if (const int rc = out_write_records(ix, p, b, c, s, st)) return rc;
+    } else s.n = c.hits->n;                                                    // n rows and no traceback, posterior pass or deposit
+    if (c.rows() && (s.n_recs || s.unmapped)) {
         if (const int rc = out_row_inputs(ix, p, b, c, s, st)) return rc;
         if (const int rc = out_count_rows(b, c, s, st)) return rc;
         pc.lap("text sizes");
         if (const int rc = out_write_rows(b, c, s, st)) return rc;
         if (const int rc = out_deliver_rows(b, c, s, st)) return rc;
     }
-    if (const int rc = out_deposit(ix, b, s, st)) return rc;
+    if (matched) if (const int rc = out_deposit(ix, b, s, st)) return rc;
     HIPCHK(hipStreamSynchronize(st));
     pc.lap("records+coverage");
     return GM_OK;

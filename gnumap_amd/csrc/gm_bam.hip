@@ -16,6 +16,8 @@
 //                 a persistent grid with a token area per workgroup; what it finds is described above the kernel and in DESIGN.md
 //   k_bgzf_compact  after the scan of the blocks' sizes: the slots side by side, so that one contiguous run crosses the link
 //
+// With a row source (GmDevText::row_src, gm_batch_set_unmapped_rows) both record kernels go over ROWS: a read without a record gets
+// refID -1, pos -1, bin 4680, MAPQ 0, flag 4, no operation, SEQ / QUAL of a plus-strand record and the one tag YU:i:<status>.
 // A record is pinned to the SAM row k_out_text_rows prints for it.  One difference is the format's own: l_read_name is one byte, so
 // read_name holds the first 254 bytes of the name (the SAM row keeps up to 1023).
 // The output bytes are a function of the input bytes and the level alone: the only atomics are integer adds into the histograms, ORs
@@ -497,6 +499,7 @@ __device__ __forceinline__ uint32_t bm_nibble(char c) {
         default: return c == '=' ? 0u : 15u;
     }
 }
+#define BM_UNMAPPED_BIN 4680u                     // reg2bin(-1, 0): the bin of a record without a position (SAMv1 section 4.2)
 __device__ __forceinline__ uint32_t bm_name_len(const GmDevText& t, uint32_t rd) {
     const unsigned long long nl = t.name_off[rd + 1] - t.name_off[rd];
     return nl > 254ull ? 254u : (uint32_t)nl;
@@ -504,8 +507,16 @@ __device__ __forceinline__ uint32_t bm_name_len(const GmDevText& t, uint32_t rd)
 
 __global__ void __launch_bounds__(256) k_bam_sizes(GmDevText t, uint32_t* __restrict__ meta) {
     const unsigned long long k = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
-    if (k >= t.n_recs) return;
-    const GmDevSamRec r = t.recs[k];
+    if (k >= t.n_rows) return;
+    unsigned long long rec = 0; uint32_t urd = 0;
+    if (!gm_row_is_record(t, k, rec, urd)) {
+        // a read without a record: no operation, bin reg2bin(-1, 0) = 4680, one int32 tag (YU); an entry that names no read: nothing
+        meta[2ull * k] = 0; meta[2ull * k + 1ull] = BM_UNMAPPED_BIN;
+        const uint32_t L = urd != 0xFFFFFFFFu ? t.seq_len[urd] : 0u;
+        t.row_len[k] = urd != 0xFFFFFFFFu ? 4u + 32u + bm_name_len(t, urd) + 1u + ((L + 1u) >> 1) + L + 7u : 0u;
+        return;
+    }
+    const GmDevSamRec r = t.recs[rec];
     const uint8_t* slot = t.slots + k * 64ull;
     const uint32_t gout = (uint32_t)slot[58] | ((uint32_t)slot[59] << 8);          // the CIGAR field as the row prints it: bytes [0, gout) of the pool's
     const char* cg = t.pool + r.cigar_off;
@@ -531,13 +542,29 @@ __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, con
     __shared__ uint8_t s_head[4][64];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     uint8_t* const hd = s_head[wv];
-    for (unsigned long long base = (unsigned long long)blockIdx.x * 4ull; base < t.n_recs; base += (unsigned long long)gridDim.x * 4ull) {
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 4ull; base < t.n_rows; base += (unsigned long long)gridDim.x * 4ull) {
         const unsigned long long k = base + wv;
-        const bool live = k < t.n_recs;
+        unsigned long long rec = 0; uint32_t urd = 0;
+        const bool is_rec = k < t.n_rows && gm_row_is_record(t, k, rec, urd);
+        const bool unm = k < t.n_rows && !is_rec && urd != 0xFFFFFFFFu;        // a read without a record: refID -1, pos -1, flag 4, tag YU
+        const bool live = is_rec || unm;
         GmDevSamRec r = {};
         uint32_t n_ops = 0, nl = 0, L = 0;
-        if (live) {
-            r = t.recs[k];
+        if (unm) {
+            r.read = urd;
+            nl = bm_name_len(t, urd); L = t.seq_len[urd];
+            if (lane == 0) {                          // [0, 36) block_size and the core fields, [36, 43) the tag
+                const uint32_t size = (uint32_t)(t.row_off[k + 1] - t.row_off[k]);
+                bm_put32(hd, size - 4u); bm_put32(hd + 4, 0xFFFFFFFFu); bm_put32(hd + 8, 0xFFFFFFFFu);
+                hd[12] = (uint8_t)(nl + 1u); hd[13] = 0;
+                hd[14] = (uint8_t)BM_UNMAPPED_BIN; hd[15] = (uint8_t)(BM_UNMAPPED_BIN >> 8); hd[16] = 0; hd[17] = 0;
+                hd[18] = 4; hd[19] = 0;
+                bm_put32(hd + 20, L); bm_put32(hd + 24, 0xFFFFFFFFu); bm_put32(hd + 28, 0xFFFFFFFFu); bm_put32(hd + 32, 0u);
+                hd[36] = 'Y'; hd[37] = 'U'; hd[38] = 'i'; bm_put32(hd + 39, (uint32_t)(int32_t)t.status[urd]);
+            }
+        }
+        if (is_rec) {
+            r = t.recs[rec];
             n_ops = meta[2ull * k]; nl = bm_name_len(t, r.read); L = t.seq_len[r.read];
             if (lane == 0) {                          // [0, 36) block_size and the core fields, [36, 57) the tags
                 const uint32_t size = (uint32_t)(t.row_off[k + 1] - t.row_off[k]);
@@ -559,7 +586,7 @@ __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, con
             unsigned long long o = t.row_off[k];
             uint8_t* const out = reinterpret_cast<uint8_t*>(t.text);
             const uint8_t* slot = t.slots + k * 64ull;
-            const uint32_t gout = (uint32_t)slot[58] | ((uint32_t)slot[59] << 8);
+            const uint32_t gout = (uint32_t)slot[58] | ((uint32_t)slot[59] << 8);      // (0 for a read without a record)
             const uint32_t rd = r.read;
             const unsigned long long n0 = t.name_off[rd];
             const unsigned long long q0 = t.qtail_off ? t.qtail_off[rd] : 0ull;
@@ -609,7 +636,7 @@ __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, con
                 if (o + i < end) out[o + i] = c > 33u ? (uint8_t)(c - 33u) : (uint8_t)0;
             }
             o += L;
-            if (lane < 21u && o + lane < end) out[o + lane] = hd[36u + lane];
+            if (lane < (unm ? 7u : 21u) && o + lane < end) out[o + lane] = hd[36u + lane];
         }
         __syncthreads();
     }
@@ -623,14 +650,14 @@ inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b
 // launchers and host code
 // ------------------------------------------------------------------------------------------------
 int gmk_bam_sizes(const GmDevText& t, uint32_t* meta, void* stream) {
-    if (t.n_recs == 0) return 0;
-    hipLaunchKernelGGL(k_bam_sizes, dim3(cdiv(t.n_recs, 256)), dim3(256), 0, S_(stream), t, meta);
+    if (t.n_rows == 0) return 0;
+    hipLaunchKernelGGL(k_bam_sizes, dim3(cdiv(t.n_rows, 256)), dim3(256), 0, S_(stream), t, meta);
     return (int)hipGetLastError();
 }
 
 int gmk_bam_rows(const GmDevBatch& b, const GmDevText& t, const uint32_t* meta, void* stream) {
-    if (t.n_recs == 0) return 0;
-    const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_recs + 3) / 4, 4096));
+    if (t.n_rows == 0) return 0;
+    const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_rows + 3) / 4, 4096));
     hipLaunchKernelGGL(k_bam_rows, dim3(grid), dim3(256), 0, S_(stream), b, t, meta);
     return (int)hipGetLastError();
 }

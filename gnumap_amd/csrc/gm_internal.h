@@ -175,7 +175,25 @@ struct GmDevText {
     unsigned long long* bad;                        // smallest record whose XA / XP lies outside gm_put_g6_hd's domain (~0: none)
     const uint16_t* seq_len;                        // characters of SEQ / QUAL a row prints: the block's lengths as uploaded (with -A the whole line, not the kept part)
     uint32_t fa_qual;                               // FASTA blocks: str2qual's character of a row with 1, 2, 3, 4 bases in its mask, in bytes 0 .. 3
+    // The row source.  n_rows rows are written: slots, row_len and row_off are per ROW.  row_src null (the default): row k is record k
+    // and n_rows == n_recs.  gm_batch_set_unmapped_rows: row k is record row_src[k], or - GM_ROW_UNMAPPED set - read
+    // row_src[k] & ~GM_ROW_UNMAPPED of the block, which has no record and gets a flag-4 row with YU:i:status[read] (gmk_row_source)
+    unsigned long long n_rows; const unsigned long long* row_src; const int8_t* status; uint32_t n_reads;
 };
+#define GM_ROW_UNMAPPED (1ull << 63)
+#if defined(__HIPCC__)
+// row k: true = it prints record `rec`; false = it stands for read `read`, which has no record.  An entry that names neither a record
+// nor a read of the block (gmk_row_source leaves none) comes back as read ~0: the row kernels write nothing for it
+__device__ __forceinline__ bool gm_row_is_record(const GmDevText& t, unsigned long long k, unsigned long long& rec, uint32_t& read) {
+    rec = k; read = 0xFFFFFFFFu;
+    if (!t.row_src) return true;
+    const unsigned long long e = t.row_src[k];
+    if (!(e & GM_ROW_UNMAPPED)) { rec = e; return e < t.n_recs; }
+    const unsigned long long r = e & ~GM_ROW_UNMAPPED;
+    if (r < t.n_reads) read = (uint32_t)r;
+    return false;
+}
+#endif
 
 // gm_snp_rec (layout asserted in gm_tracks.cpp): a row of --snp's .gmp that carries a 'Y' call, written by k_snp_gather (gm_snpcall.hip)
 struct GmDevSnpRec { unsigned long long pos; uint32_t contig, pad0; unsigned long long chr_pos; float total, nuc[5]; double p_val; uint8_t ref, alt1, alt2, diploid;
@@ -344,6 +362,11 @@ int gmk_out_deposit(float* cov, uint64_t bins, uint32_t bin_size, const GmDevMat
                     uint64_t n_p, const uint16_t* ops_len, const float* post, uint32_t max_span, float* nuc, const uint8_t* codes, uint32_t codes_stride,
                     void* stream);
 // SAM rows as text (gm_output_batch_text): tails + row lengths, then - after the scan of the lengths - the rows themselves
+// the row source of a block whose reads without a record get a row too: n reads, n_recs records in read order.  cnt / flag (n words
+// each), first / ucum (n + 1 scans: records, and reads without a record, in front of a read), row_src (n_recs + n entries of room).
+// ucum[n] = the rows of reads without a record (to be read back by the caller); the rows are n_recs + ucum[n]
+int gmk_row_source(const GmDevSamRec* recs, uint64_t n_recs, uint32_t n, uint32_t* cnt, uint32_t* flag, uint64_t* first, uint64_t* ucum, unsigned long long* tmp,
+                   unsigned long long* row_src, void* stream);
 int gmk_out_text_sizes(const GmDevBatch& b, const GmDevText& t, void* stream);
 int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream);
 int gmk_fmt_g6(const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len, void* stream);

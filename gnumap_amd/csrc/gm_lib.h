@@ -90,7 +90,9 @@ int index_cnames(gm_index* ix);                                 // contig names 
 // as k_out_text_rows left them in HBM - the records, n_rows + 1 offsets, the text - into the arena, on `stream` (GM_E_NOMEM, GM_E_UNSUPPORTED)
 int gm_samsort_claim(gm_sam_sorter* s, const gm_index* ix, uint64_t seq);
 void gm_samsort_release(gm_sam_sorter* s, uint64_t seq);     // the claim back, when the call failed before a row of the block was added
-int gm_samsort_add(gm_sam_sorter* s, uint64_t seq, const GmDevSamRec* recs, uint64_t n_rows, const char* d_text, const uint64_t* d_rowoff, uint64_t text_len, void* stream);
+// row_src null: row k is record k.  Else GmDevText::row_src of the block: a row of a read without a record gets the key of a row without a contig
+int gm_samsort_add(gm_sam_sorter* s, uint64_t seq, const GmDevSamRec* recs, const unsigned long long* row_src, uint64_t n_recs, uint64_t n_rows, const char* d_text,
+                   const uint64_t* d_rowoff, uint64_t text_len, void* stream);
 int gm_samsort_rows(gm_sam_sorter* s);                       // GM_ROWS_TEXT / GM_ROWS_BAM: what the blocks put into the arena
 
 // gm_bam.hip and gm_bai.hip share these two.  The bytes of input per BGZF block, and the bin of [beg, end) (SAMv1 section 5.3)

@@ -9,6 +9,8 @@
 //                    run-length CIGAR built from the traceback operations (src/bin_seq.cpp:578-698, fix_CIGAR_for_deletions
 //                    inc/SequenceOperations.h:32-42), and the coverage deposit of every kept sequence
 //                    (NormalScoredSeq::score src/NormalScoredSeq.cpp:66-75, BSScoredSeq::score src/BSScoredSeq.cpp:24-88).
+//   k_row_*          gm_batch_set_unmapped_rows (a defined extension): the map from row to (record | read without a
+//                    record), so that k_out_text_* and k_bam_* (gm_bam.hip) write one flag-4 row for every read the reference drops
 //
 // What stays on the host (gm_api.cpp) is only the order-dependent fp64 libm work on a flat array of scores:
 // denominator += exp(score) in processing order, posterior = exp(score) / denominator, MAPQ = round(-10 log10(1 - p)).
@@ -655,6 +657,7 @@ __global__ void __launch_bounds__(256) k_out_deposit(float* cov, uint64_t bins, 
 // ------------------------------------------------------------------------------------------------
 #define GO_TAIL_MAX 56u
 #define GO_NAME_MAX 1023u                                  // MAX_NAME_SZ - 1, inc/const_include.h:46
+#define GO_UNMAPPED_HEAD 17u                               // "\t4\t*\t0\t0\t*\t*\t0\t0\t": what a row without a record prints between its name and SEQ
 
 __device__ __forceinline__ uint32_t go_digits64(unsigned long long v) { uint32_t d = 1; while (v >= 10ull) { v /= 10ull; ++d; } return d; }
 __device__ __forceinline__ uint32_t go_int_chars(int32_t v) { return v < 0 ? 1u + go_digits64((unsigned long long)(-(long long)v)) : go_digits64((unsigned long long)v); }
@@ -674,8 +677,30 @@ __device__ __forceinline__ bool go_cigar_digit(char c) { return c >= 48 && c <= 
 __global__ void __launch_bounds__(256) k_out_text_sizes(GmDevBatch b, GmDevText t) {
     __shared__ __attribute__((aligned(16))) char s_slot[256][64];
     const unsigned long long k0 = (unsigned long long)blockIdx.x * 256ull, k = k0 + threadIdx.x;
-    if (k < t.n_recs) {
-        const GmDevSamRec r = t.recs[k];
+    unsigned long long rec = 0; uint32_t urd = 0;
+    const bool is_rec = k < t.n_rows && gm_row_is_record(t, k, rec, urd);
+    if (k < t.n_rows && !is_rec) {
+        // a read without a record: "YU:i:<status>\n" as the slot's tail, no CIGAR; name, the nine constant columns, SEQ and QUAL as a
+        // plus-strand row prints them ("*" and "*" for a read of length 0)
+        char* const s = s_slot[threadIdx.x];
+        uint32_t len = 0, tail = 0;
+        if (urd != 0xFFFFFFFFu) {
+            char* w = s;
+            w[0] = 'Y'; w[1] = 'U'; w[2] = ':'; w[3] = 'i'; w[4] = ':'; w += 5;
+            w = go_put_int(w, (int32_t)t.status[urd]);
+            *w++ = '\n';
+            tail = (uint32_t)(w - s);                         // <= 5 + 4 + 1
+            unsigned long long nl = t.name_off[urd + 1] - t.name_off[urd];
+            if (nl > GO_NAME_MAX) nl = GO_NAME_MAX;
+            const uint32_t L = t.seq_len[urd];
+            const uint32_t QL = L + (t.qtail_off ? (uint32_t)(t.qtail_off[urd + 1] - t.qtail_off[urd]) : 0u);
+            len = (uint32_t)nl + GO_UNMAPPED_HEAD + (L ? L + 1u + QL : 3u) + 1u + tail;
+        } else atomicMin(t.bad, k);
+        s[56] = s[57] = s[58] = s[59] = 0; s[60] = (char)tail;
+        t.row_len[k] = len;
+    }
+    if (is_rec) {
+        const GmDevSamRec r = t.recs[rec];
         char* const s = s_slot[threadIdx.x];
         char* w = s;
         bool ok = true;
@@ -708,7 +733,7 @@ __global__ void __launch_bounds__(256) k_out_text_sizes(GmDevBatch b, GmDevText 
     }
     __syncthreads();
     // the block's slots are one contiguous stretch of HBM: 16 bytes per lane and step
-    const unsigned long long left = t.n_recs - k0;
+    const unsigned long long left = t.n_rows - k0;
     const uint32_t chunks = (uint32_t)(left < 256ull ? left : 256ull) * 4u;
     const uint4* src = reinterpret_cast<const uint4*>(&s_slot[0][0]);
     uint4* dst = reinterpret_cast<uint4*>(t.slots + k0 * 64ull);
@@ -720,12 +745,23 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
     __shared__ char s_head[4][64];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     char* const hd = s_head[wv];
-    for (unsigned long long base = (unsigned long long)blockIdx.x * 4ull; base < t.n_recs; base += (unsigned long long)gridDim.x * 4ull) {
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 4ull; base < t.n_rows; base += (unsigned long long)gridDim.x * 4ull) {
         const unsigned long long k = base + wv;
-        const bool live = k < t.n_recs;
+        unsigned long long rec = 0; uint32_t urd = 0;
+        const bool is_rec = k < t.n_rows && gm_row_is_record(t, k, rec, urd);
+        const bool unm = k < t.n_rows && !is_rec && urd != 0xFFFFFFFFu;        // a read without a record: its flag-4 row
+        const bool live = is_rec || unm;
         GmDevSamRec r = {};
-        if (live) {
-            r = t.recs[k];
+        if (unm) {
+            r.read = urd;
+            if (lane == 0) {                                  // [0, 17) the nine constant columns
+                const char c[GO_UNMAPPED_HEAD + 1] = "\t4\t*\t0\t0\t*\t*\t0\t0\t";
+                for (uint32_t i = 0; i < GO_UNMAPPED_HEAD; ++i) hd[i] = c[i];
+                hd[62] = (char)GO_UNMAPPED_HEAD; hd[63] = 0;
+            }
+        }
+        if (is_rec) {
+            r = t.recs[rec];
             if (lane == 0) {                                  // the short head: [0, 4) "\t<flag>\t", [4, ..) "\t<chr_pos>\t<mapq>\t", [48, 55) the constant columns
                 char* w = hd;
                 *w++ = '\t';
@@ -749,11 +785,12 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
             const unsigned long long n0 = t.name_off[rd];
             unsigned long long nl64 = t.name_off[rd + 1] - n0;
             const uint32_t nl = nl64 > GO_NAME_MAX ? GO_NAME_MAX : (uint32_t)nl64;
-            const uint32_t c0 = t.cname_off[r.contig], cl = t.cname_off[r.contig + 1] - c0;
+            const uint32_t c0 = unm ? 0u : t.cname_off[r.contig], cl = unm ? 0u : t.cname_off[r.contig + 1] - c0;
             const unsigned long long q0 = t.qtail_off ? t.qtail_off[rd] : 0ull;
             const uint32_t TL = t.qtail_off ? (uint32_t)(t.qtail_off[rd + 1] - q0) : 0u, QL = L + TL;
             const uint32_t h1 = (uint8_t)hd[62], h2 = (uint8_t)hd[63];
             const bool neg = r.strand != 0;
+            const bool star = unm && L == 0u;                    // a read of length 0 without a record: SEQ and QUAL are "*"
             // every store stays inside the row the scan gave this record, whatever the lengths say
             for (uint32_t i = lane; i < nl; i += 64u) if (o + i < end) out[o + i] = t.names[n0 + i];
             o += nl;
@@ -776,27 +813,65 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
                 }
             }
             o += gout;
-            for (uint32_t i = lane; i < 7u; i += 64u) if (o + i < end) out[o + i] = hd[48 + i];
-            o += 7u;
+            if (!unm) {
+                for (uint32_t i = lane; i < 7u; i += 64u) if (o + i < end) out[o + i] = hd[48 + i];
+                o += 7u;
+            }
             const uint8_t* bs = b.bases + (size_t)rd * b.stride; const uint8_t* qs = b.quals + (size_t)rd * b.stride;
             if (!neg) { for (uint32_t i = lane; i < L; i += 64u) if (o + i < end) out[o + i] = (char)bs[i]; }
             else { for (uint32_t i = lane; i < L; i += 64u) if (o + i < end) out[o + i] = gm_comp_char((char)bs[L - 1u - i]); }
             o += L;
+            if (star) { if (lane == 0 && o < end) out[o] = '*'; o += 1u; }
             if (lane == 0 && o < end) out[o] = '\t';
             o += 1u;
-            for (uint32_t i = lane; i < QL; i += 64u) {
+            if (star) { if (lane == 0 && o < end) out[o] = '*'; o += 1u; }
+            else for (uint32_t i = lane; i < QL; i += 64u) {
                 const uint32_t si = neg ? QL - 1u - i : i;          // the whole quality line is reversed, its tail included
                 // FASTA block: str2qual's character (SequenceOperations.h:193-217) of the letter's row, by the number of bases in its mask
                 const char c = b.fasta ? (char)(t.fa_qual >> (8u * (((uint32_t)__popc(gm_iupac_mask(bs[si < L ? si : 0u])) - 1u) & 3u)))
                                : si < L ? (char)qs[si] : t.qtail[q0 + (si - L)];
                 if (o + i < end) out[o + i] = c;
             }
-            o += QL;
+            if (!star) o += QL;
             if (lane == 0 && o < end) out[o] = '\t';
             o += 1u;
             for (uint32_t i = lane; i < tail; i += 64u) if (o + i < end) out[o + i] = (char)slot[i];
         }
         __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The row source of gm_batch_set_unmapped_rows: which record, or which read without one, every row prints.  The records lie in read
+// order (k_out_write: match order, and the matches are a CSR over the reads), so a record's row is its index plus the reads without a
+// record in front of its read, and such a read's row is the records plus the reads without one in front of it.  Integer counts and
+// two scans: nothing depends on the order the counts arrive in.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_row_count(const GmDevSamRec* __restrict__ recs, unsigned long long n_recs, uint32_t n, uint32_t* __restrict__ cnt) {
+    const unsigned long long k = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    if (k >= n_recs) return;
+    const uint32_t rd = recs[k].read;
+    if (rd < n) atomicAdd(&cnt[rd], 1u);
+}
+
+__global__ void __launch_bounds__(256) k_row_flags(const uint32_t* __restrict__ cnt, uint32_t n, uint32_t* __restrict__ flag) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r < n) flag[r] = cnt[r] == 0u ? 1u : 0u;
+}
+
+// items [0, n_recs): the records; [n_recs, n_recs + n): the reads.  Every row index is checked against the number of rows
+__global__ void __launch_bounds__(256) k_row_fill(const GmDevSamRec* __restrict__ recs, unsigned long long n_recs, uint32_t n, const uint32_t* __restrict__ cnt,
+                                                  const uint64_t* __restrict__ first, const uint64_t* __restrict__ ucum, unsigned long long* __restrict__ row_src) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    const unsigned long long n_rows = n_recs + ucum[n];
+    if (i < n_recs) {
+        const uint32_t rd = recs[i].read;
+        const unsigned long long row = i + ucum[rd < n ? rd : n];
+        if (row < n_rows) row_src[row] = i;
+    } else if (i - n_recs < n) {
+        const uint32_t r = (uint32_t)(i - n_recs);
+        const unsigned long long row = first[r] + ucum[r];
+        if (cnt[r] == 0u && row < n_rows) row_src[row] = GM_ROW_UNMAPPED | r;
     }
 }
 
@@ -874,19 +949,33 @@ int gmk_out_deposit(float* cov, uint64_t bins, uint32_t bin_size, const GmDevMat
 }
 
 int gmk_out_text_sizes(const GmDevBatch& b, const GmDevText& t, void* stream) {
-    if (t.n_recs == 0) return 0;
-    hipLaunchKernelGGL(k_out_text_sizes, dim3(cdiv(t.n_recs, 256)), dim3(256), 0, S_(stream), b, t);
+    if (t.n_rows == 0) return 0;
+    hipLaunchKernelGGL(k_out_text_sizes, dim3(cdiv(t.n_rows, 256)), dim3(256), 0, S_(stream), b, t);
     return (int)hipGetLastError();
 }
 
 int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream) {
-    if (t.n_recs == 0) return 0;
+    if (t.n_rows == 0) return 0;
     // one resident round: as many workgroups of 4 waves as the device holds at once
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_out_text_rows, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
-    const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_recs + 3) / 4, (uint64_t)cus * (uint64_t)per_cu));
+    const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_rows + 3) / 4, (uint64_t)cus * (uint64_t)per_cu));
     hipLaunchKernelGGL(k_out_text_rows, dim3(grid), dim3(256), 0, S_(stream), b, t);
+    return (int)hipGetLastError();
+}
+
+int gmk_row_source(const GmDevSamRec* recs, uint64_t n_recs, uint32_t n, uint32_t* cnt, uint32_t* flag, uint64_t* first, uint64_t* ucum, unsigned long long* tmp,
+                   unsigned long long* row_src, void* stream) {
+    if (n == 0) return 0;
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)n * 4, S_(stream));
+    if (e == hipSuccess) e = hipMemsetAsync(row_src, 0xFF, (size_t)(n_recs + n) * 8, S_(stream));       // (an entry nothing fills names no row)
+    if (e != hipSuccess) return (int)e;
+    if (n_recs) hipLaunchKernelGGL(k_row_count, dim3(cdiv(n_recs, 256)), dim3(256), 0, S_(stream), recs, (unsigned long long)n_recs, n, cnt);
+    hipLaunchKernelGGL(k_row_flags, dim3(cdiv(n, 256)), dim3(256), 0, S_(stream), cnt, n, flag);
+    if (const int rc = gmk_scan_u32(cnt, n, first, tmp, stream)) return rc;
+    if (const int rc = gmk_scan_u32(flag, n, ucum, tmp, stream)) return rc;
+    hipLaunchKernelGGL(k_row_fill, dim3(cdiv(n_recs + n, 256)), dim3(256), 0, S_(stream), recs, (unsigned long long)n_recs, n, cnt, first, ucum, row_src);
     return (int)hipGetLastError();
 }
 

@@ -2,7 +2,8 @@
 // fixed-size pieces, with one (key, place, length) entry per row; when the input is exhausted the keys are sorted once and the rows
 // are gathered in key order, slab by slab, for the download.
 //
-//   k_ss_rows     per block: key = contig << 32 | chr_pos of every record (~0 without a contig), where its row lies in the arena, its length
+//   k_ss_rows     per block: key = contig << 32 | chr_pos of every ROW's record (~0 without a contig, and for the row of a read without a
+//                 record, gm_batch_set_unmapped_rows), where the row lies in the arena, its length
 //   k_ss_prepare  at finish, per block in sequence order: the sort key (contig and position packed into the bits in use, so the radix
 //                 sort runs over those only), the row ordinal, and the block's places / lengths into the run's tables
 //   rocprim::radix_sort_pairs (stable: equal keys keep ordinal = input order), k_ss_permute (places / lengths in sorted order),
@@ -26,11 +27,15 @@ namespace {
 
 constexpr uint32_t SS_SPAN = 4096;                  // destination bytes one wavefront of k_ss_gather moves: 64 lanes x 16 bytes x 4
 
-__global__ void __launch_bounds__(256) k_ss_rows(const GmDevSamRec* recs, const uint64_t* row_off, uint32_t n, uint32_t n_seqs, uint32_t piece, long long delta,
+// rows [row_a, row_a + n) of the block; row_src (null: row k is record k) as gmk_row_source left it, for the whole block
+__global__ void __launch_bounds__(256) k_ss_rows(const GmDevSamRec* recs, const unsigned long long* row_src, unsigned long long n_recs, unsigned long long row_a,
+                                                 const uint64_t* row_off, uint32_t n, uint32_t n_seqs, uint32_t piece, long long delta,
                                                  unsigned long long* key, unsigned long long* place, uint32_t* len) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const GmDevSamRec r = recs[i];
+    const unsigned long long src = row_src ? row_src[row_a + i] : row_a + i;
+    GmDevSamRec r = {}; r.contig = 0xFFFFFFFFu;                  // a read without a record: no contig, sorts last
+    if (src < n_recs) r = recs[src];
     key[i] = r.contig < n_seqs ? (unsigned long long)r.contig << 32 | (r.chr_pos & 0xFFFFFFFFull) : ~0ull;
     const unsigned long long a = row_off[i], b = row_off[i + 1];
     place[i] = (unsigned long long)piece << 32 | (unsigned long long)((long long)a + delta);
@@ -263,9 +268,11 @@ void gm_samsort_release(gm_sam_sorter* s, uint64_t seq) {
     if (it != s->blocks.end() && !it->second.n_rows && !it->second.tab) s->blocks.erase(it);
 }
 
-// the rows of a block as k_out_text_rows left them (text, n_rows + 1 offsets, the records), all in HBM, into the arena on `stream`
-int gm_samsort_add(gm_sam_sorter* s, uint64_t seq, const GmDevSamRec* recs, uint64_t n_rows, const char* d_text, const uint64_t* d_rowoff, uint64_t text_len,
-                   void* stream) {
+// the rows of a block as k_out_text_rows left them (text, n_rows + 1 offsets, the records), all in HBM, into the arena on `stream`.
+// The keys are per row: row_src (null: row k is record k) names the record of a row, or says that it has none - key ~0, behind every
+// contig, and among themselves such rows keep input order like all rows of one key
+int gm_samsort_add(gm_sam_sorter* s, uint64_t seq, const GmDevSamRec* recs, const unsigned long long* row_src, uint64_t n_recs, uint64_t n_rows, const char* d_text,
+                   const uint64_t* d_rowoff, uint64_t text_len, void* stream) {
     if (!n_rows) return GM_OK;
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t st = S_(stream);
@@ -331,7 +338,7 @@ int gm_samsort_add(gm_sam_sorter* s, uint64_t seq, const GmDevSamRec* recs, uint
         { std::lock_guard<std::mutex> lk(s->mu); dst = s->pieces[g.piece]; }
         HIPCHK(hipMemcpyAsync(dst + g.dst_off, d_text + g.src_off, (size_t)g.bytes, hipMemcpyDeviceToDevice, st));
         const uint32_t n = (uint32_t)(g.row_b - g.row_a);
-        hipLaunchKernelGGL(k_ss_rows, dim3((n + 255u) / 256u), dim3(256), 0, st, recs + g.row_a, d_rowoff + g.row_a, n, n_seqs, g.piece,
+        hipLaunchKernelGGL(k_ss_rows, dim3((n + 255u) / 256u), dim3(256), 0, st, recs, row_src, (unsigned long long)n_recs, (unsigned long long)g.row_a, d_rowoff + g.row_a, n, n_seqs, g.piece,
                            (long long)g.dst_off - (long long)g.src_off, key + g.row_a, place + g.row_a, len + g.row_a);
         HIPCHK(hipGetLastError());
     }
@@ -631,7 +638,7 @@ extern "C" int gm_sam_sorter_add_rows(gm_sam_sorter* s, uint64_t seq, const char
         HIPCHK(hipMemcpyAsync(d_recs.p, recs.data(), n_rows * sizeof(GmDevSamRec), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_off.p, off.data(), (n_rows + 1) * 8, hipMemcpyHostToDevice, st));
         if (text_len) HIPCHK(hipMemcpyAsync(d_text.p, text + off0, (size_t)text_len, hipMemcpyHostToDevice, st));
-        if (const int r = gm_samsort_add(s, seq, d_recs.as<GmDevSamRec>(), n_rows, d_text.as<char>(), d_off.as<uint64_t>(), text_len, stream)) return r;
+        if (const int r = gm_samsort_add(s, seq, d_recs.as<GmDevSamRec>(), nullptr, n_rows, n_rows, d_text.as<char>(), d_off.as<uint64_t>(), text_len, stream)) return r;
         HIPCHK(hipStreamSynchronize(st));
         return GM_OK;
     };

@@ -68,7 +68,8 @@ struct Options {
     int bam_level = 1;              // --bam_level=0|1: stored blocks, or Huffman-coded ones
     bool bam_level_set = false;     // (refused without --sam_format=bam)
     bool bam_lz77 = false;          // --bam_lz77: LZ77 matches under the Huffman code of level 1; once the options are checked, GM_BGZF_LZ77 in bam_level
-    bool bam_index = false;         // --bam_index: <out>.bam.bai beside a sorted <out>.bam, built on the GPU from what the sorter holds (gm_sam_sorter_bai)
+    bool sam_unmapped = false;      // --sam_unmapped: a read without a row gets a flag-4 row (gm_batch_set_unmapped_rows; implies --sam_text=device)
+    bool bam_index = false;       // --bam_index: <out>.bam.bai beside a sorted <out>.bam, built on the GPU from what the sorter holds (gm_sam_sorter_bai)
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
 
@@ -130,7 +131,11 @@ struct Options {
             "                               found on the GPU - a smaller <out>.bam with the same records (not with --bam_level=0)\n"
             "      --bam_index              with --sam_format=bam --sam_sort=coordinate: also write <out>.bam.bai (SAMv1 section 5.2), built on the\n"
             "                               GPU from the sorted records and their BGZF offsets; <out>.bam is written exactly as without the flag.\n"
-            "                               Records must end at or below 2^29 (there is no .csi)\n");
+            "                               Records must end at or below 2^29 (there is no .csi)\n"
+            "      --sam_unmapped           keep the reads that do not map: each gets one row (flag 4, no contig, no position, SEQ and QUAL as in\n"
+            "                               the read file, tag YU:i:<code>: 2 no match, 1 too many matches, -2 too short, -3 too poor, 0 nothing\n"
+            "                               printed) where its rows would stand; with --sam_sort=coordinate behind every contig, in input order.\n"
+            "                               Implies --sam_text=device (not with --sam_text=host).  Every other row is written as without the flag\n");
     exit(rc);
 }
 
@@ -208,6 +213,7 @@ static void parse_args(int argc, char** argv, Options& o) {
             }
             else if (!strcmp(s, "bam_lz77")) o.bam_lz77 = true;
             else if (!strcmp(s, "bam_index")) o.bam_index = true;
+            else if (!strcmp(s, "sam_unmapped")) o.sam_unmapped = true;
             else if (starts(s, "sam_shards=")) {
                 char* end = nullptr;
                 const long k = strtol(s + 11, &end, 10);
@@ -277,6 +283,10 @@ static void parse_args(int argc, char** argv, Options& o) {
     if (o.bam) {                                             // refused before a device is opened or a file is written
         if (o.sam_text_host_set) { fprintf(stderr, "Error: --sam_format=bam writes the records on the GPU: it cannot be combined with --sam_text=host\n"); exit(1); }
         if (o.sam_shards > 1) { fprintf(stderr, "Error: --sam_format=bam writes one <out>.bam: it cannot be combined with --sam_shards above 1\n"); exit(1); }
+        o.sam_text_device = true;
+    }
+    if (o.sam_unmapped) {                                    // refused before a device is opened or a file is written
+        if (o.sam_text_host_set) { fprintf(stderr, "Error: --sam_unmapped writes its rows on the GPU: it cannot be combined with --sam_text=host\n"); exit(1); }
         o.sam_text_device = true;
     }
     if (o.batch < 1) o.batch = 1;
@@ -773,8 +783,9 @@ struct Worker {
     PinVec<int8_t> status; PinVec<float> self_score; PinVec<double> top, den; PinVec<uint64_t> mbegin;
     PinVec<gm_match> matches; PinVec<gm_pos> positions;
     uint64_t n_reads = 0, n_matched = 0, n_records = 0;
+    uint64_t n_unmapped = 0;                // --sam_unmapped: rows of reads without a record, among n_records (or among the sorter's rows)
     double t_pack = 0, t_map = 0, t_out = 0, t_scan = 0;
-    gm_sam_sorter* sorter = nullptr;        // --sam_sort=coordinate: where the blocks' rows go instead of a host buffer
+    gm_sam_sorter* sorter = nullptr;       // --sam_sort=coordinate: where the blocks' rows go instead of a host buffer
     TextPool* stage_pool = nullptr;         // --read_text=device: page-locked buffers a block's FASTQ text is copied into for the upload
     // the result arrays of a block of n reads, and a gm_hits that points at them (filled again after a capacity retry has made them grow)
     void ensure_hits(uint32_t n) {
@@ -918,6 +929,7 @@ static int process_block(Worker& w, const Options& o, const char* base, Block& b
     b.n_recs = n_recs; b.dtext_len = text_len; b.gpu = w.gpu;
     w.t_pack += secs_between(c0, c1); w.t_map += secs_between(c1, c2); w.t_out += secs_since(c2);
     w.n_reads += n; w.n_records += n_recs;                  // (sorted: no records here, main takes their number from the sorter)
+    if (o.sam_unmapped) { uint64_t u = 0; if (gm_batch_unmapped_rows(w.batch, &u) == GM_OK) w.n_unmapped += u; }
     for (uint32_t i = 0; i < n; ++i) w.n_matched += (w.status[i] == GM_READ_OK || w.status[i] == GM_READ_TOO_MANY);
     return GM_OK;
 }
@@ -1049,7 +1061,7 @@ static int open_devices(Run& R) {
             Worker& w = R.workers[(size_t)g * (size_t)o.workers + (size_t)k];
             w.gpu = g; w.ix = ix; w.text_pool = &R.text_pool; w.stage_pool = &R.stage_pool; w.sorter = R.sorter;
             if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK ||
-                gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK ||
+                gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK || gm_batch_set_unmapped_rows(w.batch, o.sam_unmapped ? 1 : 0) != GM_OK ||
                 gm_batch_set_read_format(w.batch, o.fasta ? GM_READS_FASTA : GM_READS_FASTQ) != GM_OK) return fail();
         }
     }
@@ -1408,6 +1420,11 @@ static void report(const Run& R, double t_pipe, double t_cov, double secs) {
             t.n_reads / std::max(t_pipe, 1e-9) / 1e6, t_cov);
     fprintf(stderr, "Finished: %lu reads, %lu matched, %lu SAM records, %.2f s total (%.2f s after the index was resident)\n", (unsigned long)t.n_reads,
             (unsigned long)t.n_matched, (unsigned long)t.n_records, secs, secs - R.t_index);
+    if (o.sam_unmapped) {
+        uint64_t n_unmapped = 0;
+        for (const Worker& w : R.workers) n_unmapped += w.n_unmapped;
+        fprintf(stderr, "--sam_unmapped: %lu of the %lu SAM records are rows of reads that did not map (flag 4, YU:i:<code>)\n", (unsigned long)n_unmapped, (unsigned long)t.n_records);
+    }
 }
 
 int main(int argc, char** argv) {

@@ -309,6 +309,25 @@ int gm_output_batch(gm_index*, const gm_params*, gm_batch*, const gm_reads*, con
 int gm_output_batch_text(gm_index*, const gm_params*, gm_batch*, const gm_reads*, const gm_read_text*, const gm_hits*, gm_sam_text* out,
                          void* hip_stream);
 
+/* ---- rows for the reads that do not map (a defined extension: the reference prints none) ----
+ * Off by default: a read without a record has no row.  gm_batch_set_unmapped_rows(b, 1): from the next call on, the six row-producing
+ * output calls (gm_output_batch_text, _text_resident, _sorted, _sorted_resident, _bam, _bam_resident) give every read of the block for
+ * which they write no record - status GM_READ_NONE, _TOO_MANY, _TOO_SHORT, _TOO_POOR, or GM_READ_OK with nothing printed - exactly
+ * one row.  The block's rows ascend by read index: a read's records keep their order and their bytes, such a read's row stands where
+ * its records would.  SAM text:
+ *     name \t 4 \t * \t 0 \t 0 \t * \t * \t 0 \t 0 \t SEQ \t QUAL \t YU:i:<gm_hits.status of the read> \n
+ * with the name cut to 1023 bytes and SEQ / QUAL as a plus-strand row prints them (the bases as uploaded, whole even with an adaptor
+ * set; the quality line with its tail; str2qual's string for a FASTA block); a read of length 0 - gm_batch_upload takes one, its status
+ * is GM_READ_TOO_SHORT - prints "*" for both.  BAM: refID -1, pos -1, bin 4680, MAPQ 0, flag 4, no CIGAR operation, next refID -1, next
+ * pos -1, tlen 0, the name cut to 254 bytes, l_seq / SEQ / QUAL as for a plus-strand record, one tag YU of type i.  In the sorter such a
+ * row has the key of a row without a contig: it sorts behind every contig, and among themselves these rows keep input order.
+ * gm_sam_text.n_recs / row_off, gm_bam_out.n_recs and the sorter's row count then count ROWS; the capacity-first contract holds with
+ * sizes that include these rows.  A block in which nothing matched gives n rows (and no traceback, posterior pass or deposit); such a
+ * read deposits nothing anywhere.  gm_output_batch (the records form) does not read the setting: its records are the same either way.
+ * gm_batch_unmapped_rows: how many such rows the last row-producing output call on the batch wrote (0 with the setting off). */
+int gm_batch_set_unmapped_rows(gm_batch*, int on);
+int gm_batch_unmapped_rows(gm_batch*, uint64_t* n);
+
 /* ---- FASTQ text in: the reads cut into rows on the device ----
  * gm_batch_upload_text takes a byte range of FASTQ text as it stands in the file, uploads it verbatim and leaves the batch resident
  * exactly as gm_batch_upload would have with the rows a host had cut from it (n, stride, lengths, adaptor trim, --illumina fallback
