@@ -3,7 +3,7 @@
 * the driver with --sam_text=device against the outputs of the UNMODIFIED reference program, every mode of tests/golden/ref_runs/ and
   the celgen fixtures: SAM text byte-identical, tracks through test_gpu_driver_golden.compare_tracks;
 * --sam_shards=K: the concatenation of the shards is the single-file SAM, for both --sam_text values;
-* the ABI call against a formatter written out in this file (Python's "%g" is C's), with the capacity retry, a 1500-byte name, lower-case
+* the ABI call against the formatter of tests/sam_text_model.py (Python's "%g" is C's), with the capacity retry, a 1500-byte name, lower-case
   and N bases on the minus strand, and the coverage track deposited exactly once;
 * gm_dev_fmt_g6 against Python's "%g"."""
 import gzip
@@ -17,6 +17,7 @@ import pytest
 
 import gnumap_amd as g
 from conftest import CELGEN, GOLDEN, ROOT, read_fastq
+from sam_text_model import check_text, revcomp, reverse_cigar, sam_rows  # noqa: F401 (other test files import them from here)
 from test_gpu_driver_golden import compare_tracks
 
 pytestmark = pytest.mark.gpu
@@ -170,34 +171,7 @@ def test_cli_one_shard_is_the_single_file(text, tmp_path):
     check_against_reference("default", out)
 
 
-# ---- the ABI call against a formatter written out here -----------------------------------------------------------------------------
-COMP = {ord(a): ord(b) for a, b in zip("atcgATCG-", "tagcTAGC-")}
-
-
-def revcomp(s):
-    return bytes(COMP.get(c, ord("n")) for c in reversed(s))          # reverse_comp, inc/SequenceOperations.h:56-96
-
-
-def reverse_cigar(c):
-    # inc/SequenceOperations.h:109-123: tokens of "digits" (48..58, so ':' too) + one operation, in reverse order; digits after the last
-    # operation are dropped
-    return b"".join(reversed(re.findall(rb"[0-9:]*[^0-9:]", c)))
-
-
-def sam_rows(recs, cigars, names, seqs, quals, contigs, adjust):
-    inv = 1.0 / float(np.float32(adjust))
-    rows = []
-    for r, cg in zip(recs, cigars):
-        i = int(r["read"])
-        minus = int(r["strand"]) != 0
-        xa = "%g" % (float(np.float32(r["a_score"])) * inv)
-        xp = "1" if np.float32(r["post_prob"]) == np.float32(1.0) else "%g" % float(np.float32(r["post_prob"]))
-        rows.append(b"\t".join([names[i][:1023], b"16" if minus else b"0", contigs[int(r["contig"])].encode(), b"%d" % int(r["chr_pos"]), b"%d" % int(r["mapq"]),
-                                reverse_cigar(cg) if minus else cg, b"*", b"0", b"0", revcomp(seqs[i]) if minus else seqs[i],
-                                quals[i][::-1] if minus else quals[i], b"XA:f:" + xa.encode(), b"XP:f:" + xp.encode(), b"X0:i:%d" % int(r["sim_matches"])]) + b"\n")
-    return rows
-
-
+# ---- the ABI call against the formatter of tests/sam_text_model.py -----------------------------------------------------------------------------
 def test_the_reversal_helpers_of_this_file():
     assert reverse_cigar(b"77M1I22M1D") == b"1D22M1I77M" and reverse_cigar(b"5M3") == b"5M" and reverse_cigar(b"*") == b"*" and reverse_cigar(b"1:M2I") == b"2I1:M"
     assert revcomp(b"ACgtN-x") == b"n-nacGT"
@@ -218,17 +192,6 @@ def both_calls(ix, p, seqs, quals, names, qual_tails=None, bin_size=8, first_cap
     calls = batch.text_calls
     batch.destroy()
     return recs, cigars, text, row_off, cov_recs, cov_text, calls
-
-
-def check_text(ix, p, seqs, quals, names, recs, cigars, text, row_off):
-    contigs = [c for c, _ in ix.contigs()]
-    want = sam_rows(recs, cigars, names, seqs, quals, contigs, p.adjust)
-    assert len(row_off) == len(recs) + 1 and int(row_off[0]) == 0 and int(row_off[-1]) == len(text)
-    got = [text[int(row_off[k]):int(row_off[k + 1])] for k in range(len(recs))]
-    for k, (a, b) in enumerate(zip(got, want)):
-        assert a == b, (k, a, b)
-    assert text == b"".join(want)
-    assert all(r.endswith(b"\n") and r.count(b"\n") == 1 for r in got)
 
 
 def same_track(a, b):

@@ -36,6 +36,11 @@ def _ok_output(out):
     assert out["coverage_bins_checked"] > 100 and out["coverage_bin_mismatches"] == 0 and out["track_totals_ok"], out
 
 
+def _ok_track_text(out):
+    """the rows gm_coverage_text prints for the touched bins are the Python formatter's of the device's own values, beyond 2^31 too"""
+    assert out["track_text_rows_checked"] > 0 and out["track_text_rows_beyond_2_31"] > 0 and out["track_text_row_mismatches"] == 0, out
+
+
 def test_configs1_100mbp_m10_dense_vote_form(workdir):
     import scale_check
     out = scale_check.main(["--mbp", "100", "--contigs", "6", "--mer", "10", "--reads", "100000", "--sample", "200", "--steps", "1",
@@ -55,13 +60,14 @@ def test_headline_size_and_kernel_beyond_2_31_positions(workdir):
     """bench.py's default workload at its own size: 3.1 Gbp in 24 contigs, -m 14 -j 7, NW, the bucket-table kernel"""
     import scale_check
     out = scale_check.main(["--mbp", "3100", "--contigs", "24", "--mer", "14", "--reads", "200000", "--sample", "64", "--steps", "1",
-                            "--check-output", "32", "--keep", "--workdir", workdir])
+                            "--check-output", "32", "--check-track-text", "--keep", "--workdir", workdir])
     assert out["l_pac"] == 3_100_000_000 and out["l_pac"] > 2 ** 31
     assert "k_vote_bucket<4>" in out["path"], out["path"]
     _ok(out, 64); _ok_output(out)
     assert out["oracle_tail_reads"] >= 10                     # sampled reads that lie beyond 2^31
     assert out["max_reported_pos"] > 2 ** 31
     assert out["vote_retries"] == 0
+    _ok_track_text(out)                                       # the .sgr rows
 
 
 def test_configs4_no_nw_at_scale(workdir):
@@ -74,10 +80,11 @@ def test_configs4_no_nw_at_scale(workdir):
 def test_configs3_bisulfite_150bp_at_human_size(workdir):
     import scale_check
     out = scale_check.main(["--mbp", "3100", "--contigs", "24", "--mer", "14", "--mode", "1", "--read-len", "150", "--reads", "200000", "--sample", "48",
-                            "--steps", "1", "--check-output", "32", "--keep", "--workdir", workdir])
+                            "--steps", "1", "--check-output", "32", "--check-track-text", "--keep", "--workdir", workdir])
     assert "k_vote_bucket<6>" in out["path"], out["path"]
     _ok(out, 48); _ok_output(out)
     assert out["nuc_bins_checked"] > 1000 and out["nuc_bin_mismatches"] == 0, out
+    _ok_track_text(out)                                       # the .gmp rows at bin size 1
 
 
 def test_two_kernel_form_at_human_size(workdir):

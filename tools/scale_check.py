@@ -6,7 +6,9 @@ infrastructure, like the tests), check that exact reads recover their origin, an
 
     python3 tools/scale_check.py --mbp 2200 --reads 1000000 --mer 10 --max-kmer-hits 150
 
-Prints one JSON line.  --build-only stops after the index build (no GPU needed)."""
+Prints one JSON line.  --build-only stops after the index build (no GPU needed).  --check-output N also compares gm_output_batch's
+records and deposits of N reads with the oracle; with --check-track-text the .sgr / .gmp rows gm_coverage_text prints for the bins
+those reads touched are compared with a formatter in Python fed with the device's own bin values."""
 import argparse
 import json
 import os
@@ -50,17 +52,15 @@ def overlay_repeats(seq, rng, cons):
         seq[(at[:, None] + np.arange(span)[None, :]).reshape(-1)] = copies.reshape(-1)
 
 
-def write_genome(fa, G, n_contigs, seed, repeats=False):
-    """i.i.d. ACGT (optionally overlaid with repeat families) in 100-column FASTA, generated contig by contig in 64 Mbp
-    pieces (bounded memory); returns contig offsets"""
+def write_contigs(fa, contigs, seed, repeats=False):
+    """contigs = [(name, length)]: i.i.d. ACGT (optionally overlaid with repeat families) in 100-column FASTA, generated contig by
+    contig in 64 Mbp pieces (bounded memory); returns contig offsets"""
     rng = np.random.default_rng(seed)
     cons = [ACGT[rng.integers(0, 4, ln)] for _, ln, _, _, _ in FAMILIES]
-    sizes = [G // n_contigs // 100 * 100] * n_contigs
-    sizes[-1] += G - sum(sizes)
     offs = [0]
     with open(fa, "wb") as f:
-        for c, n in enumerate(sizes):
-            f.write(b">chr%d\n" % (c + 1))
+        for name, n in contigs:
+            f.write(b">" + (name.encode() if isinstance(name, str) else name) + b"\n")
             done = 0
             while done < n:
                 m = min(64_000_000, n - done)
@@ -79,9 +79,62 @@ def write_genome(fa, G, n_contigs, seed, repeats=False):
     return offs
 
 
-def check_output(g, ix, p, orc, oix, op, B, Q, Ln, L, pick):
+def write_genome(fa, G, n_contigs, seed, repeats=False):
+    """n_contigs contigs chr1.. of G bases in all (the last takes the remainder); returns contig offsets"""
+    sizes = [G // n_contigs // 100 * 100] * n_contigs
+    sizes[-1] += G - sum(sizes)
+    return write_contigs(fa, [("chr%d" % (c + 1), n) for c, n in enumerate(sizes)], seed, repeats)
+
+
+def track_rows(names, offs, pac, mode, bs, lo, cov, nuc):
+    """the rows of <out>.sgr (mode 0) or of the eight-column <out>.gmp of the bins [lo, lo + len(cov)) as [(bin, row)]: PrintFinalSGR /
+    PrintFinalBisulfite / PrintFinalSNP in Python, from the values handed in (cov[k - lo], nuc[q][k - lo]); offs = the contigs' offsets"""
+    want = {1: 1, 2: 2, 3: 0}.get(mode, 3)                  # the reference base of -b, --b2, -d (c, g, a), else t
+    out = []
+    for k in (lo + np.nonzero(cov > 0)[0]).tolist():
+        count = k * bs
+        v = float(cov[k - lo])
+        if mode == 0:
+            if not v > 0.001:
+                continue
+        elif mode == 5:
+            if not cov[k - lo] > np.float32(0.001):
+                continue
+        elif (int(pac[count >> 2]) >> ((~count & 3) << 1)) & 3 != want:
+            continue
+        c = int(np.searchsorted(offs, count, side="right")) - 1
+        row = "%s\t%d\t" % (names[c], count - int(offs[c]) + 1) + ("%f" if mode not in (0, 5) else "%.5f") % v
+        if mode:
+            row += "".join("\t%.5f" % float(nuc[q][k - lo]) for q in range(5))
+        out.append((k, (row + "\n").encode()))
+    return out
+
+
+def check_track_text(ix, p, fa, bs, touched, track, nt, bins):
+    """gm_coverage_text (k_track_sizes / k_track_rows) on the ranges the touched bins form, against track_rows fed with the DEVICE's own
+    values of those ranges: the text kernels at this size, not the values (check_output compares those with the oracle)"""
+    contigs = ix.contigs()
+    names = [n for n, _ in contigs]; offs = np.array([o for _, o in contigs], np.int64)
+    pac = np.memmap(fa + ".gnumap.pac", np.uint8, "r") if p.mode not in (0, 5) else None
+    keys = np.unique(np.asarray(touched, np.int64))
+    cuts = np.nonzero(np.diff(keys) > 64)[0] + 1                       # bins closer than 64 go into one range
+    checked = bad = far = 0
+    for grp in np.split(keys, cuts):
+        lo, hi = max(0, int(grp[0]) - 2), min(bins, int(grp[-1]) + 3)
+        cov = track[lo:hi].cpu().numpy()
+        nuc = [nt[q * bins + lo:q * bins + hi].cpu().numpy() for q in range(5)] if p.mode else None
+        want = track_rows(names, offs, pac, p.mode, bs, lo, cov, nuc)
+        got = ix.coverage_text(p if p.mode else None, lo, hi).splitlines(keepends=True)
+        checked += len(want)
+        bad += abs(len(got) - len(want)) + sum(a != b for a, (_, b) in zip(got, want))
+        far += sum(k * bs >= 1 << 31 for k, _ in want)
+    return dict(track_text_ranges=len(cuts) + 1, track_text_rows_checked=checked, track_text_row_mismatches=bad, track_text_rows_beyond_2_31=far)
+
+
+def check_output(g, ix, p, orc, oix, op, B, Q, Ln, L, pick, fa=None, track_text=False):
     """gm_map_batch + gm_output_batch on the picked reads: SAM records, coverage bins and (-b / -d) per-nucleotide bins against the
-    oracle's gmo_read_output; the device tracks are read through zero-copy views at the touched bins only"""
+    oracle's gmo_read_output; the device tracks are read through zero-copy views at the touched bins only.  track_text: the rows of the
+    touched bins from gm_coverage_text as well (check_track_text)"""
     import torch
     from gnumap_amd import dist as gd
     pick = np.asarray(sorted(set(int(x) for x in pick)))
@@ -118,6 +171,7 @@ def check_output(g, ix, p, orc, oix, op, B, Q, Ln, L, pick):
     bad_cov = int((np.abs(got - want) > 1e-5 * np.maximum(1.0, np.abs(want))).sum())
     total_ok = abs(float(track.sum().item()) - float(want.astype(np.float64).sum())) <= 1e-3 * max(1.0, float(want.sum()))
     bad_nuc = 0
+    nt = None
     if p.mode:
         nt = gd.DeviceTrack(ix.coverage_nuc_device_ptr(), 5 * bins).tensor(dev)
         nk = list(nuc.keys())
@@ -126,9 +180,10 @@ def check_output(g, ix, p, orc, oix, op, B, Q, Ln, L, pick):
         wantn = np.array([nuc[k] for k in nk], np.float32)
         bad_nuc = int((np.abs(gotn - wantn) > 1e-5 * np.maximum(1.0, np.abs(wantn))).sum())
         total_ok = total_ok and abs(float(nt.sum().item()) - float(wantn.astype(np.float64).sum())) <= 1e-3 * max(1.0, float(wantn.sum()))
+    text = check_track_text(ix, p, fa, bs, keys, track, nt, bins) if track_text else {}
     bt.destroy()
     return dict(output_reads=len(pick), output_records=len(want_recs), output_record_mismatch=bad_recs, coverage_bins_checked=len(cov),
-                coverage_bin_mismatches=bad_cov, nuc_bins_checked=len(nuc), nuc_bin_mismatches=bad_nuc, track_totals_ok=bool(total_ok))
+                coverage_bin_mismatches=bad_cov, nuc_bins_checked=len(nuc), nuc_bin_mismatches=bad_nuc, track_totals_ok=bool(total_ok), **text)
 
 
 def main(argv=None):
@@ -150,6 +205,8 @@ def main(argv=None):
     ap.add_argument("--jump", type=int, default=0)
     ap.add_argument("--mode", type=int, default=0, help="0 normal, 1 -b, 2 --b2, 3 -d")
     ap.add_argument("--check-output", type=int, default=0, help="reads whose gm_output_batch records and coverage / per-nucleotide deposits are compared with the oracle")
+    ap.add_argument("--check-track-text", action="store_true", help="with --check-output: the .sgr / .gmp rows of the touched bins from gm_coverage_text against a formatter "
+                                                                   "in Python fed with the device's own bin values")
     a = ap.parse_args(argv)
 
     import gnumap_amd as g
@@ -265,7 +322,7 @@ def main(argv=None):
                oracle_tail_reads=int((pos[pick] >= (1 << 31)).sum()))
 
     if a.check_output:
-        out.update(check_output(g, ix, p, orc, oix, op, B, Q, Ln, L, pick[:a.check_output]))
+        out.update(check_output(g, ix, p, orc, oix, op, B, Q, Ln, L, pick[:a.check_output], fa, a.check_track_text))
 
     # rate with the reads resident in HBM (block by block when --batch is set)
     batch.set_profiling(False)
