@@ -48,6 +48,7 @@ struct gm_batch {
     uint32_t len_max = 0;                 // longest read of the uploaded block
     uint32_t len_min = 0;                 // and the shortest
     uint32_t n = 0, stride = 0, max_seeds = 0, illumina_until = 0;
+    int up_illumina = 0;                  // gm_params.illumina of the upload that left the block resident: illumina_until was scanned under it
     DevBuf bases, quals, len, status, self_score, min_score, top_score, seeds, n_seeds, n_entries, entry_off, coords,
         rs_overflow, retry_list, retry_off, gtab_keys, gtab_vals, cands, fixed_cands, fixed_cnt, heavy_list, heavy_off, heavy_k0, heavy_k1, heavy_tmp, hit_count, hit_begin, hit_cursor, raw_hits, counters, small, shards, big_list,
         tb_items, tb_ops, tb_len, band_moves, pack,
@@ -575,10 +576,15 @@ extern "C" void gm_batch_destroy(gm_batch* b) {
     delete b;
 }
 
+// rows of the seed table: what one strand of a row of `stride` characters can yield under these -m / -j
+static uint32_t seed_rows(uint32_t stride, const gm_params* p) {
+    const uint32_t last = stride > (uint32_t)p->mer ? stride - (uint32_t)p->mer : 0;
+    return last / (uint32_t)p->jump + 2;
+}
+
 static int ensure_batch_buffers(gm_batch* b, const gm_params* p) {
     const size_t n = b->n, n2 = 2 * (size_t)b->n;
-    uint32_t last = b->stride > (uint32_t)p->mer ? b->stride - (uint32_t)p->mer : 0;
-    b->max_seeds = last / (uint32_t)p->jump + 2;
+    b->max_seeds = seed_rows(b->stride, p);
     int rc = 0;
     rc |= b->status.ensure(n); rc |= b->self_score.ensure(n * 4); rc |= b->min_score.ensure(n * 8); rc |= b->top_score.ensure(n * 4);
     rc |= b->seeds.ensure(n2 * b->max_seeds * sizeof(GmSeed)); rc |= b->n_seeds.ensure(n2 * 2); rc |= b->n_entries.ensure(n2 * 4);
@@ -658,7 +664,7 @@ extern "C" int gm_batch_upload(gm_batch* b, const gm_params* p, const gm_reads* 
     }
     // --illumina with automatic fallback (SeqReader.cpp:1171-1180): reads before the first one that shows a
     // quality below '@' keep Phred+64, that read and all later ones use Phred+33 (with -A only the kept characters are looked at, :1152)
-    b->illumina_until = 0;
+    b->illumina_until = 0; b->up_illumina = p->illumina != 0;
     if (p->illumina && !fasta) {                                   // (--illumina is accepted and ignored for FASTA, as in the reference)
         uint32_t until = r->n;
         for (uint32_t i = 0; i < r->n && until == r->n; ++i) {
@@ -781,7 +787,7 @@ extern "C" int gm_batch_upload_text(gm_batch* b, const gm_params* p, const char*
             for (uint32_t i = 0; i < n; ++i) { maxlen = std::max<uint32_t>(maxlen, b->len_host[i]); minlen = std::min<uint32_t>(minlen, b->len_host[i]); }
         }
     }
-    b->n = n; b->stride = stride; b->len_max = maxlen; b->len_min = minlen;
+    b->n = n; b->stride = stride; b->len_max = maxlen; b->len_min = minlen; b->up_illumina = p->illumina != 0;
     const int rc = ensure_batch_buffers(b, p);
     if (rc) { b->n = 0; b->len_host.clear(); return rc; }
     fill_dev_batch(b);
@@ -998,7 +1004,22 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     b->mapped = false;
     b->pair_flagged = 0;
     if ((rc = fasta_forced_form(b)) != GM_OK) return rc;
-    if (b->n == 0) { b->n_cands = 0; b->n_raw = 0; b->mapped = true; memset(b->counters_host, 0, sizeof b->counters_host); return GM_OK; }
+    if (b->n == 0) {                                 // nothing is launched: the counters and the path are this call's (all zero, no kernel), not the last block's
+        b->n_cands = 0; b->n_raw = 0; b->mapped = true; memset(b->counters_host, 0, sizeof b->counters_host); b->counters_on_host = true;
+        b->path = std::string("reads=") + (b->fasta ? "fasta" : "fastq") + " (empty block: no kernel)";
+        return GM_OK;
+    }
+    // what the upload bound and what it did not (gnumap_hip.h at gm_batch_upload): the fallback scan of --illumina read the host's
+    // quality rows then, so `illumina` cannot change; the seed rows follow THIS call's -m / -j, whatever the upload sized them for
+    if (!b->fasta && (p->illumina != 0) != (b->up_illumina != 0)) {
+        gm_set_error(std::string("gm_params.illumina = ") + (p->illumina ? "1" : "0") + " for a block uploaded with illumina = " + (b->up_illumina ? "1" : "0") +
+                     ": the upload binds this field (its fallback scan read the quality rows); upload the block again under the other value");
+        return GM_E_ARG;
+    }
+    if (const uint32_t ms = seed_rows(b->stride, p); ms != b->max_seeds) {
+        b->max_seeds = ms;
+        if (b->seeds.ensure(2 * (size_t)b->n * ms * sizeof(GmSeed))) return GM_E_NOMEM;      // (fill_dev_batch below, before the first launch)
+    }
     const int use_full = ix->full_sa ? 1 : 0;
     // which vote kernel: expected SA hits per seed ~ reference length / 4^mer (capped by -h), expected seeds per strand from the
     // longest read.  0 = sparse (<= 16 hits per read x strand fit a 16-lane group), 1 = k_vote_slots (its hits fit 40 slots of
@@ -1029,6 +1050,11 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
         uint32_t sub_n = 0;
         sub_n = (uint32_t)gm_opt_ll("GM_PIPELINE", 0);
         if (use_full && sub_n >= 4096 && b->n >= 3 * (uint64_t)sub_n) {
+            // the sub-batches run k_prep -> k_seed -> gmk_vote on shard candidates: no 2-bit read forms, no own slots.  These three are the
+            // LAST call's until the single pass below sets them, and map_pipelined fills its views from them: a `pack` left on by a
+            // bucket-table call made every sub-batch's k_prep write its read forms into a buffer sized for that earlier, smaller block
+            b->use_pack = false; b->use_fixed = false; b->fixed_epoch = 0;
+            b->path.clear();                             // the single-pass dispatch records its choice; a block the sub-batches map to the end has none (not the last call's)
             int prc = map_pipelined(ix, p, dp, b, st, dense, slots_hint, sub_n);
             if (prc <= 0) return prc;                    // done, or a real error
         }
@@ -1080,7 +1106,9 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
         if (b->use_fixed) {
             const size_t cap_before = b->fixed_cands.cap;       // by CAPACITY: hipFree + a larger hipMalloc may hand back the same base address
             if (b->fixed_cands.ensure(((2 * (size_t)b->n + 63) / 64) * 64 * GM_FIXED_C * sizeof(GmCand)) || b->fixed_cnt.ensure(2 * (size_t)b->n + 64)) return GM_E_NOMEM;
-            if (b->fixed_cands.cap != cap_before) { HIPCHK(hipMemsetAsync(b->fixed_cands.p, 0, b->fixed_cands.cap, st)); b->epoch_ctr = 0; }      // new memory: no stale launch stamps
+            // new memory: no stale launch stamps.  (TEST switch GM_TEST_EPOCH=<start>: the counter starts there, so that a few calls reach the
+            // NaN / inf / denormal bit patterns of the stamp and the 32-bit wrap)
+            if (b->fixed_cands.cap != cap_before) { HIPCHK(hipMemsetAsync(b->fixed_cands.p, 0, b->fixed_cands.cap, st)); b->epoch_ctr = (uint32_t)gm_opt_ll("GM_TEST_EPOCH", 0); }
         }
         b->fixed_epoch = 0;
     }
@@ -1640,7 +1668,9 @@ static int map_batch_rest(gm_index* ix, const gm_params* p, gm_batch* b, gm_hits
     b->cache_hits = b->cache_matches = 0; b->stamp = 0; out->stamp = 0;
     if (!resume) {
         HIPCHK(hipMemsetAsync(b->o_small.p, 0, 64, st));
-        if (p->unique_only && !p->nw) HIPCHK(hipMemsetAsync(b->g_positions.p, 0, nh * sizeof(GmDevPos), st));      // dropped hits leave holes
+        // hits that end up in no match leave holes in the positions: those -u --no_nw drops, and every hit of a read whose matches are
+        // dropped as a whole (GM_READ_TOO_MANY).  gm_hits.positions is copied out whole, so a hole must not hold the last block's entries
+        HIPCHK(hipMemsetAsync(b->g_positions.p, 0, nh * sizeof(GmDevPos), st));
         KCHK(gmk_group_count(ix->dev, b->dev, g, p->nw, p->unique_only, p->max_matches, st));
         KCHK(gmk_scan_u32(g.n_match, n, g.match_begin, b->scan_tmp.as<unsigned long long>(), st));
         KCHK(gmk_group_write(b->dev, g, st));

@@ -228,7 +228,12 @@ int gm_params_load_subst(gm_params*, const char* path);
 /* ---- batches: device-resident reads + workspace + raw results ---- */
 int gm_batch_create(gm_index*, uint32_t max_reads /* <= 16 000 000 */, uint32_t max_len /* <= 2048 */, gm_batch** out);
 void gm_batch_destroy(gm_batch*);
-int gm_batch_upload(gm_batch*, const gm_params*, const gm_reads*, void* hip_stream);       /* host -> HBM */
+/* host -> HBM.  Of gm_params an upload (gm_batch_upload, gm_batch_upload_text) BINDS one field, `illumina`: the --illumina fallback
+ * scan (the first read that shows a quality below '@') reads the quality rows while they are uploaded, and the block stays resident
+ * with its outcome.  gm_map_batch_device / gm_map_batch_text with the other value of `illumina` on a FASTQ block return GM_E_ARG
+ * (gm_last_error() names the field); a FASTA block ignores the field in both calls.  Every other field - mer, jump and the rest - is read
+ * from the map call's own gm_params: the upload's values of them only pre-size workspace, which the map call sizes again where they differ. */
+int gm_batch_upload(gm_batch*, const gm_params*, const gm_reads*, void* hip_stream);
 /* -A / --adaptor: trim adaptor sequence from the 3' end of every read of the blocks uploaded from now on.  Replaces the
  * `if(g_adaptor) J=FixReads2(sequence)` of SeqReader::get_more_fastq (src/SeqReader.cpp:1146-1150) with FixReads2 (:1356-1372) and
  * Compare (:1294-1305), as one device kernel (k_adaptor_trim) behind the copies of gm_batch_upload / gm_map_batch: a read keeps its
@@ -273,7 +278,7 @@ int gm_batch_kernel_times(gm_batch*, double* ms /* GM_K_COUNT */, uint64_t* laun
 const char* gm_kernel_name(int which);
 /* the block's read format and which seed lookup / vote kernel / locate form / DP kernel the last gm_map_batch_device on this batch chose,
  * e.g. "reads=fastq seeds=bucket-table (in the vote kernel) vote=k_vote_bucket<4> locate=full-SA nw=k_nw_rows/pairs" (valid until the
- * next call on the batch) */
+ * next call on the batch).  "" after a call that the sub-batch pipeline (GM_PIPELINE) mapped to the end; an empty block names no kernel */
 const char* gm_batch_path(gm_batch*);
 /* reads that k_vote_pair left to k_vote_bucket in the last gm_map_batch_device on this batch (a k-mer that does not occur or has more
  * than 28 hits, an early position, a base that is not ACGT, too many hits or second arrivals in a strand); 0 when k_vote_pair did not run */
