@@ -78,8 +78,7 @@ struct gm_batch {
     PinBuf h_top, h_hbegin, h_ord, h_post, h_mapq, h_emit, h_mhit, h_stat;      // h_stat: the small status words a phase reads back (page-locked: one short DMA)
     std::vector<double> h_exp;          // exp(score) of every accepted hit of the last gm_map_batch (reused by gm_output_batch)
     uint64_t cache_hits = 0, cache_matches = 0;
-    uint32_t fixed_epoch = 0;           // launch stamp of the own-slot candidates of k_vote_bucket (GmDevBatch::fixed_epoch); 0 = the count array form
-    uint32_t epoch_ctr = 0;
+    uint32_t epoch_ctr = 0;             // launch stamps handed out so far for the own-slot candidates of k_vote_bucket (map_vote_attempt takes the next one)
     uint64_t stamp = 0;                 // names the gm_map_batch result resident in g_matches / g_positions (gm_hits::stamp); 0 = none
     std::string path;                   // which kernels the last gm_map_batch_device chose (gm_batch_path)
     uint32_t pair_flagged = 0;          // reads k_vote_pair handed to the list in it (gm_batch_pair_flagged): pair_list[0] as the status words brought it
@@ -90,10 +89,8 @@ struct gm_batch {
         bool busy = false, quit = false;
         int rc = GM_OK; std::string err;
     } svc;
-    bool use_pack = false;              // the fused seed lookup is on for this pass (k_prep writes the 2-bit read forms)
     const void* resume_ptr = nullptr;   // set when gm_map_batch returned GM_E_CAPACITY: the next call with the same reads resumes at the copies
     uint32_t cand_cap = 0;
-    bool use_fixed = false;             // k_vote_tiny* leave their candidates in per read x strand slots (gathered by k_cand_gather)
     uint64_t raw_cap = 0;
     uint32_t n_cands = 0;
     uint64_t n_raw = 0;
@@ -597,6 +594,8 @@ static int ensure_batch_buffers(gm_batch* b, const gm_params* p) {
     return rc ? GM_E_NOMEM : GM_OK;
 }
 
+// what the resident block defines.  The kernel form of a map call (pack, fixed_cands, fixed_cnt, fixed_epoch) is not the batch's: it
+// stays null / 0 here, and map_fill_dev puts it on top for the length of that call
 static void fill_dev_batch(gm_batch* b) {
     GmDevBatch& d = b->dev;
     d.n = b->n; d.stride = b->stride; d.max_seeds = b->max_seeds; d.illumina_until = b->illumina_until; d.read_base = 0; d.fasta = b->fasta ? 1u : 0u;
@@ -608,13 +607,13 @@ static void fill_dev_batch(gm_batch* b) {
     d.gtab_keys = b->gtab_keys.as<uint32_t>(); d.gtab_vals = b->gtab_vals.as<uint32_t>();
     d.cands = b->cands.as<GmCand>(); d.cand_cap = b->cand_cap; d.cand_region = b->cand_cap / GM_NSHARD;
     d.shard_cnt = b->shards.as<uint32_t>();
-    d.fixed_cands = b->use_fixed ? b->fixed_cands.as<GmCand>() : nullptr; d.fixed_cnt = b->use_fixed ? b->fixed_cnt.as<uint8_t>() : nullptr; d.fixed_epoch = b->use_fixed ? b->fixed_epoch : 0u;
+    d.fixed_cands = nullptr; d.fixed_cnt = nullptr; d.fixed_epoch = 0;
     d.hit_count = b->hit_count.as<uint32_t>(); d.hit_begin = b->hit_begin.as<uint64_t>(); d.hit_cursor = b->hit_cursor.as<uint32_t>();
     d.raw_hits = b->raw_hits.as<GmRawHit>(); d.raw_cap = b->raw_cap;
     d.counters = b->counters.as<unsigned long long>();
     d.n_retry = b->small.as<uint32_t>() + 1; d.n_big = b->small.as<uint32_t>() + 2; d.big_list = b->big_list.as<uint32_t>();
     d.band_moves = b->band_moves.as<unsigned long long>(); d.band_moves_words = b->band_moves.cap / 8;
-    d.pack = b->use_pack ? b->pack.as<uint32_t>() : nullptr; d.pack_w2 = gm_pack_w2(b->stride); d.pack_words = gm_pack_words(b->stride);
+    d.pack = nullptr; d.pack_w2 = gm_pack_w2(b->stride); d.pack_words = gm_pack_words(b->stride);
 }
 
 extern "C" int gm_batch_upload(gm_batch* b, const gm_params* p, const gm_reads* r, void* stream) {
@@ -890,11 +889,158 @@ extern "C" int gm_dev_adaptor_trim(gm_index* ix, const gm_reads* reads, const ch
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// gm_map_batch_device: prep -> seed -> vote -> NW -> compaction of the resident block, as named steps
+//
+// MapForm: which kernels one call runs.  map_choose_form decides it once, from the index, this call's parameters, the resident block
+// and the GM_* switches; it is a value of the call, never stored in the batch.
+struct MapForm {
+    int use_full = 0;                   // the index holds the full suffix array (no sampled-SA locate pass)
+    int dense = 0;                      // gmk_vote's kernel class: 0 = sparse, 1 = k_vote_slots / k_vote_tiny*, 2 = the 64-slot form, 3 = k_vote_block
+    int slots_hint = 40;                // expected 64-lane slots per read x strand (picks the k_vote_slots form; 0 / -1: k_vote_tiny / k_vote_tiny2)
+    int fused = 0;                      // the vote kernels look their seeds up themselves: no k_seed launch (GmDevParams::fused)
+    bool use_bucket = false;            // ... in the bucket table: k_vote_bucket + the list kernel instead of gmk_vote
+    uint32_t bucket_reg = 0;            // its seed positions per strand (the kernel's template size)
+    bool use_pair = false;              // k_vote_pair in front of k_vote_bucket: two reads per wavefront
+    bool pair_direct = false;           // ... handing its results straight to the shards and the flagged reads' list
+    bool use_fixed = false;             // candidates in own slots per read x strand, gathered by k_cand_gather
+    bool use_pack = false;              // k_prep writes the 2-bit read forms of the fused seed lookup
+    uint32_t heavy_min = 0;             // read x strands with more SA hits go to the sorted-key path of gm_heavy.hip
+    uint64_t heavy_budget = 0;          // keys per chunk of that path
+    uint32_t sub_n = 0;                 // GM_PIPELINE: the sub-batch size asked for
+    bool pipeline = false;              // ... and the block is large enough for map_pipelined to be tried first
+};
+
+// Decides, and nothing else: no launch, no memset, no ensure().
+static MapForm map_choose_form(const gm_index* ix, const gm_params* p, const gm_batch* b, const GmDevParams& dp) {
+    MapForm f;
+    f.use_full = ix->full_sa ? 1 : 0;
+    // which vote kernel: expected SA hits per seed ~ reference length / 4^mer (capped by -h), expected seeds per strand from the
+    // longest read.  0 = sparse (<= 16 hits per read x strand fit a 16-lane group), 1 = k_vote_slots (its hits fit 40 slots of
+    // 64 lanes), 2 = its 64-slot form, 3 = k_vote_block (more: rounds of 2048 hits).  GM_VOTE=wave|block|big|rounds forces 0..3, GM_VOTE_KERNEL the dense form.
+    {
+        double per_seed = (double)ix->h.seq_len / pow(4.0, (double)std::min(p->mer, 31));
+        if (p->max_kmer_hits > 0) per_seed = std::min(per_seed, (double)p->max_kmer_hits);
+        const double L = (double)b->stride;
+        double ns = L > p->mer ? floor((L - p->mer - 1) / std::max(1, p->jump)) + 1 : 1;
+        if (p->nw && p->fast) ns = 1;
+        ns = std::min(ns, (double)b->max_seeds);
+        const double e_exp = ns * (1.0 + per_seed);                                      // the true locus + chance hits
+        const double slots_exp = ns * ceil((per_seed + 3.0 * sqrt(per_seed) + 1.0) / 64.0);
+        f.dense = e_exp > 14.0 ? (slots_exp <= 38.0 ? 1 : slots_exp <= 60.0 ? 2 : 3) : 0;
+        f.slots_hint = (int)std::min(1000.0, slots_exp);
+        // few hits in many short runs (long seeds on a large reference): one wave per read x strand, 16-rank groups (k_vote_tiny)
+        const double groups_exp = ns * ceil((per_seed + 3.0 * sqrt(per_seed) + 1.0) / 16.0);
+        if (f.dense == 1 && p->min_seed_hits >= 2 && e_exp + 4.0 * sqrt(e_exp) <= 230.0 && groups_exp <= 28.0) f.slots_hint = 0;
+        else if (f.dense == 1 && p->min_seed_hits >= 2 && e_exp + 4.0 * sqrt(e_exp) <= 350.0 && groups_exp <= 56.0) f.slots_hint = -1;      // k_vote_tiny2
+        if (const char* ev = gm_opt("GM_VOTE_SLOTS")) { if (*ev) f.slots_hint = atoi(ev); }
+        if (const char* ev = gm_opt("GM_VOTE")) f.dense = !strcmp(ev, "block") ? 1 : !strcmp(ev, "big") ? 2 : !strcmp(ev, "rounds") ? 3 : !strcmp(ev, "wave") ? 0 : f.dense;
+    }
+    // optional sub-batch pipeline over several streams for large full-SA batches (GM_PIPELINE=<sub-batch size>).  Measured
+    // +4 % at configs[1]: three vote kernels end up sharing the LDS rather than hiding seed / NW work, and per-kernel
+    // timings stop being attributable, so it is off by default.
+    f.sub_n = (uint32_t)gm_opt_ll("GM_PIPELINE", 0);
+    f.pipeline = f.use_full && f.sub_n >= 4096 && b->n >= 3 * (uint64_t)f.sub_n;
+    // read x strands with very many SA hits (repeat seeds without -h) leave the ordinary vote kernels before they start: sorted-key
+    // path of gm_heavy.hip, routed by the seed search's own hit count.  GM_HEAVY_MIN / GM_HEAVY_BUDGET (keys per chunk) are test switches.
+    f.heavy_min = (uint32_t)gm_opt_ll("GM_HEAVY_MIN", 16384);
+    f.heavy_budget = (uint64_t)gm_opt_ll("GM_HEAVY_BUDGET", 1ll << 27);
+    // seed lookup inside the vote kernels that take one read x strand per wave / workgroup (full SA, the k-mer table covering the
+    // whole seed): no k_seed launch, no seed rows through HBM.  A k-mer that does not occur changes the positions of all later ones;
+    // the wave then walks again round by round (gm_seed_rewalk_ool), one probe round trip per failing k-mer.  That stays rare while
+    // even a k-mer with a sequencing error still occurs somewhere by chance - every k-mer expected >= 4 times in the reference
+    // (measured on 100 Mbp: -m 12, 6 per k-mer: 21.0 ms fused against 27.7; -m 14, 0.4 per k-mer: an erroneous k-mer dies one or two
+    // characters before its end, the walk creeps past the error in ~9 rounds, 207 against 29.5 ms - k_seed amortises those serial
+    // steps over 64 lanes).  GM_SEED_FUSED=0 / 1: never / whenever possible.
+    const bool no_kernel_env = !gm_opt("GM_VOTE_KERNEL");
+    const int fused_env = (int)gm_opt_ll("GM_SEED_FUSED", -1);
+    const double occ = (double)ix->h.seq_len / pow(4.0, (double)std::min(p->mer, 31));
+    // -h: on a real reference the k-mers of repeats exceed any cap, and each of them makes the walk slide base by base (:213-217) in
+    // one lane - not measurable on the synthetic references of bench.py, so a capped run keeps k_seed unless forced
+    const bool pays = occ >= 4.0 && p->max_kmer_hits == 0;
+    f.fused = (fused_env < 0 ? pays : fused_env != 0) && f.use_full && (f.dense == 1 || f.dense == 2) && no_kernel_env && b->max_seeds <= 64 && dp.kmer_tab &&
+              dp.kmer_ctab && dp.kmer_T == p->mer && p->mer <= 16 && p->jump >= 1 && !(dp.dbg & 128);
+    // ... or in the bucket table (one read per wave, both strands; handles -h and k-mers that do not occur by walking again):
+    // every seed is ONE random line
+    const uint32_t lastmax = b->len_max > (uint32_t)p->mer ? b->len_max - (uint32_t)p->mer : 0;      // (the longest read of the block, not the row stride)
+    const uint32_t max_reg = (lastmax + (uint32_t)p->jump - 1) / (uint32_t)p->jump;
+    f.use_bucket = dp.bucket && f.use_full && dp.kmer_tab && dp.kmer_T == dp.bucket_T && dp.bucket_T == p->mer && p->min_seed_hits >= 2 && max_reg <= 32 && b->max_seeds <= 34 && no_kernel_env &&
+                   !gm_opt("GM_VOTE") && f.sub_n == 0 && !(dp.dbg & 128) && fused_env != 0;
+    // -A: the minus strand's k-mers come from another stretch of the row than its DP (see k_seed): only k_seed knows that form
+    if (!b->adaptor.empty()) { f.fused = 0; f.use_bucket = false; }
+    if (f.use_bucket) { f.fused = 1; f.bucket_reg = max_reg; }
+    // ... two reads per wavefront (gm_pair.hip) where a strand has at most 16 seeds; GM_VOTE_PAIR=0: one read per wavefront always
+    f.use_pair = f.use_bucket && !dp.bucket_ctx && max_reg <= 16 && !(p->nw && p->fast) && !gm_opt_is("GM_VOTE_PAIR", "0") && !(dp.dbg & (64 | 256 | 512 | 1024 | 2048));       // (GM_DBG 4096 .. 32768: timing experiments of k_vote_pair)
+    // hand-off of k_vote_pair's results: straight into the candidate shards and the flagged reads' list at each 16-pair flush (default),
+    // or GM_PAIR_HANDOFF=gather: own candidate slots + one flag byte per read, read back by k_cand_gather / k_pair_collect / k_heavy_collect
+    f.pair_direct = f.use_pair && !gm_opt_is("GM_PAIR_HANDOFF", "gather");
+    f.use_pack = f.fused != 0;
+    // the one-wave vote kernels leave their candidates in per read x strand slots (no bump counter on the wave's critical path)
+    f.use_fixed = !gm_opt_is("GM_VOTE_FIXED", "0") && !f.pair_direct && (f.use_bucket || ((f.dense == 1 || f.dense == 2) && no_kernel_env));      // k_vote_bucket, k_vote_tiny*, k_vote_slots (all forms)
+    return f;
+}
+
+// the buffers only some forms use
+static int map_form_buffers(gm_batch* b, const MapForm& f, hipStream_t st) {
+    if (f.use_pair && b->pair_list.ensure(((size_t)b->n + 16) * 4)) return GM_E_NOMEM;
+    if (f.use_pair && !f.pair_direct && b->pair_fb.ensure((size_t)b->n + 64)) return GM_E_NOMEM;
+    if (f.use_pack && b->pack.ensure((size_t)b->n * gm_pack_words(b->stride) * 4 + 64)) return GM_E_NOMEM;
+    if (f.use_fixed) {
+        const size_t cap_before = b->fixed_cands.cap;       // by CAPACITY: hipFree + a larger hipMalloc may hand back the same base address
+        if (b->fixed_cands.ensure(((2 * (size_t)b->n + 63) / 64) * 64 * GM_FIXED_C * sizeof(GmCand)) || b->fixed_cnt.ensure(2 * (size_t)b->n + 64)) return GM_E_NOMEM;
+        // new memory: no stale launch stamps.  (TEST switch GM_TEST_EPOCH=<start>: the counter starts there, so that a few calls reach the
+        // NaN / inf / denormal bit patterns of the stamp and the 32-bit wrap)
+        if (b->fixed_cands.cap != cap_before) { HIPCHK(hipMemsetAsync(b->fixed_cands.p, 0, b->fixed_cands.cap, st)); b->epoch_ctr = (uint32_t)gm_opt_ll("GM_TEST_EPOCH", 0); }
+    }
+    return GM_OK;
+}
+
+// what path() says of the form.  gmk_vote's own branches are copied here: more than 64 seeds per strand leave the one-workgroup kernels
+// for the ordered k_vote, GM_VOTE_KERNEL picks the dense form whatever `dense` says, GM_VOTE_SPARSE=0 runs k_vote_fast for every read x strand
+static std::string map_form_name(const MapForm& f, const gm_batch* b, const GmDevParams& dp) {
+    char buf[224];
+    const int pp_env = (int)gm_opt_ll("GM_SLOTS_PIPE", -1);                                               // (gmk_vote's condition for the pipelined form of k_vote_slots)
+    const bool slots_pp = f.use_full && !gm_opt("GM_VOTE_KERNEL") && (pp_env < 0 ? f.dense == 2 : pp_env != 0) && !(dp.dbg & 64);
+    const char* kenv = gm_opt("GM_VOTE_KERNEL"); if (kenv && !*kenv) kenv = nullptr;
+    const bool wg_form = f.dense != 0 && b->max_seeds <= 64;
+    const bool slots_form = wg_form && (kenv ? !strcmp(kenv, "slots") : f.dense <= 2);
+    const uint32_t reg = f.bucket_reg;
+    snprintf(buf, sizeof buf, "seeds=%s vote=%s locate=%s cands=%s", f.use_bucket ? "bucket-table (in the vote kernel)" : f.fused ? "k-mer table (in the vote kernel)" : "k_seed",
+             f.use_pair ? (reg <= 8 ? "k_vote_pair<4> + k_vote_bucket<2>" : reg <= 14 ? "k_vote_pair<7> + k_vote_bucket<4>" : "k_vote_pair<8> + k_vote_bucket<4>")
+             : f.use_bucket ? (reg <= 8 ? "k_vote_bucket<2>" : reg <= 16 ? "k_vote_bucket<4>" : reg <= 24 ? "k_vote_bucket<6>" : "k_vote_bucket<8>")
+                            : !wg_form ? (b->max_seeds > 64 ? "k_vote" : gm_opt_is("GM_VOTE_SPARSE", "0") ? "k_vote_fast" : "sparse") : !slots_form ? "k_vote_block"
+                            : f.dense == 2 ? (slots_pp ? "k_vote_slots_pp<64>" : "k_vote_slots<64>") : f.slots_hint == 0 ? "k_vote_tiny" : f.slots_hint < 0 ? "k_vote_tiny2" : slots_pp ? "k_vote_slots_pp" : "k_vote_slots",
+             f.use_full ? "full-SA" : "sampled-SA", f.use_fixed ? "own-slots" : "shards");
+    return buf;
+}
+
+// shared by the single pass and the sub-batch pipeline: k_prep counted the quality characters below the offset ...
+static int map_check_quals(const gm_batch* b, const unsigned long long* ctr) {
+    if (ctr[GMK_BAD_QUAL] && !b->fasta) { gm_set_error("Invalid Fastq Character? (negative base probability)"); return GM_E_BAD_QUAL; }
+    return GM_OK;
+}
+
+// ... and those above 127: one read length in the block and none of them (a FASTA block has no quality characters) is what the DP kernel
+// with the rows in DP order takes, 0 = another form
+static uint32_t map_nw_rows_len(const gm_batch* b, const unsigned long long* ctr) {
+    return (b->len_min == b->len_max && (b->fasta || ctr[GMK_HIGH_QUAL] == 0)) ? b->len_max : 0u;
+}
+
+// ... and the tables of gmk_vote_retry, all handed out at once: `slots` empty keys and zero counts
+static int map_retry_tables(DevBuf& keys, DevBuf& vals, size_t slots, hipStream_t st) {
+    if (keys.ensure(slots * 4) || vals.ensure(slots * 4)) return GM_E_NOMEM;
+    HIPCHK(hipMemsetAsync(keys.p, 0xFF, slots * 4, st));
+    HIPCHK(hipMemsetAsync(vals.p, 0, slots * 4, st));
+    return GM_OK;
+}
+
 // Large batches in full-SA mode: the batch is cut into sub-batches that go through prep -> seed -> vote -> NW on NS
 // streams, so that the LDS-bound vote kernel of one sub-batch runs beside the seed / NW kernels of its neighbours.
 // Returns 1 when a candidate shard overflowed (the caller then takes the single-pass path, which can grow the list).
-static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp, gm_batch* b, hipStream_t st, int dense, int slots_hint, uint32_t sub_n) {
-    const uint32_t n = b->n;
+// Of the form it takes dense, slots_hint and sub_n: the sub-batches run k_prep -> k_seed -> gmk_vote on shard candidates, and their views
+// are cut from a b->dev that carries no form (no 2-bit read forms, no own slots).
+static int map_pipelined(gm_index* ix, const GmDevParams& dp, gm_batch* b, const MapForm& form, hipStream_t st) {
+    const uint32_t n = b->n, sub_n = form.sub_n;
     const uint32_t nsb = (n + sub_n - 1) / sub_n;
     for (int i = 0; i < gm_batch::NS; ++i)
         if (!b->sub_streams[i]) HIPCHK(hipStreamCreateWithFlags(&b->sub_streams[i], hipStreamNonBlocking));
@@ -912,7 +1058,7 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
     auto make_view = [&](uint32_t i) {
         GmDevBatch v = b->dev;
         const uint32_t lo = i * sub_n, cnt = std::min(sub_n, n - lo);
-        v.n = cnt; v.read_base = lo; v.fixed_cands = nullptr;
+        v.n = cnt; v.read_base = lo;
         v.illumina_until = b->illumina_until > lo ? std::min(b->illumina_until - lo, cnt) : 0;
         v.bases += (size_t)lo * b->stride; v.quals += (size_t)lo * b->stride; v.len += lo;
         v.status += lo; v.self_score += lo; v.min_score += lo; v.top_score += lo;
@@ -934,16 +1080,13 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
         HIPCHK(hipMemcpyAsync(ctr, view[i].counters, sizeof ctr, hipMemcpyDeviceToHost, ss));
         HIPCHK(hipMemcpyAsync(shard_host.data(), view[i].shard_cnt, shard_bytes, hipMemcpyDeviceToHost, ss));
         HIPCHK(hipStreamSynchronize(ss));
-        if (ctr[GMK_BAD_QUAL] && !b->fasta) { gm_set_error("Invalid Fastq Character? (negative base probability)"); return GM_E_BAD_QUAL; }
+        if (int rc = map_check_quals(b, ctr)) return rc;
         auto tally = [&](uint64_t& total, uint32_t& mx) { total = 0; mx = 0; for (int q = 0; q < GM_NSHARD; ++q) { uint32_t c = shard_host[(size_t)q * GM_SHARD_STRIDE]; total += c; mx = std::max(mx, c); } };
         uint64_t total; uint32_t mx;
         tally(total, mx);
         if (small[1] && mx <= region) {
-            size_t slots = (size_t)ctr[GMK_HEAVY_SLOTS];
-            if (b->sub_gk[s].ensure(slots * 4) || b->sub_gv[s].ensure(slots * 4)) return GM_E_NOMEM;
+            if (int rc = map_retry_tables(b->sub_gk[s], b->sub_gv[s], (size_t)ctr[GMK_HEAVY_SLOTS], ss)) return rc;
             view[i].gtab_keys = b->sub_gk[s].as<uint32_t>(); view[i].gtab_vals = b->sub_gv[s].as<uint32_t>();
-            HIPCHK(hipMemsetAsync(b->sub_gk[s].p, 0xFF, slots * 4, ss));
-            HIPCHK(hipMemsetAsync(b->sub_gv[s].p, 0, slots * 4, ss));
             { KTimer t(b, GM_K_VOTE_RETRY, ss); KCHK(gmk_vote_retry(ix->dev, dp, view[i], 1, 0, small[1], ss)); }
             HIPCHK(hipMemcpyAsync(shard_host.data(), view[i].shard_cnt, shard_bytes, hipMemcpyDeviceToHost, ss));
             HIPCHK(hipStreamSynchronize(ss));
@@ -951,7 +1094,7 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
         }
         if (mx > region) { overflow = true; return GM_OK; }
         ncand[i] = (uint32_t)total;
-        { KTimer t(b, GM_K_NW, ss); KCHK(gmk_nw(ix->dev, dp, view[i], ncand[i], (b->len_min == b->len_max && (b->fasta || !ctr[GMK_HIGH_QUAL])) ? b->len_max : 0u, gm_qual_lo(ctr), gm_qual_hi(ctr), small[1] != 0, ss)); }
+        { KTimer t(b, GM_K_NW, ss); KCHK(gmk_nw(ix->dev, dp, view[i], ncand[i], map_nw_rows_len(b, ctr), gm_qual_lo(ctr), gm_qual_hi(ctr), small[1] != 0, ss)); }
         return GM_OK;
     };
     uint32_t next_finish = 0;
@@ -965,7 +1108,7 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
         HIPCHK(hipMemsetAsync(view[i].rs_overflow, 0, 2 * (size_t)view[i].n, ss));
         { KTimer t(b, GM_K_PREP, ss); KCHK(gmk_prep(ix->dev, dp, view[i], ss)); }
         { KTimer t(b, GM_K_SEED, ss); KCHK(gmk_seed(ix->dev, dp, view[i], ss, b->adaptor.empty() ? nullptr : b->full_len.as<uint16_t>() + view[i].read_base)); }
-        { KTimer t(b, GM_K_VOTE, ss); KCHK(gmk_vote(ix->dev, dp, view[i], 1, dense, slots_hint, ss)); }
+        { KTimer t(b, GM_K_VOTE, ss); KCHK(gmk_vote(ix->dev, dp, view[i], 1, form.dense, form.slots_hint, ss)); }
         if (i + 1 >= (uint32_t)gm_batch::NS) { int rc = finish(next_finish++); if (rc) return rc; }
     }
     while (next_finish < nsb && !overflow) { int rc = finish(next_finish++); if (rc) return rc; }
@@ -994,23 +1137,47 @@ static int map_pipelined(gm_index* ix, const gm_params* p, const GmDevParams& dp
     return GM_OK;
 }
 
-extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b, void* stream) {
-    if (!ix || !p || !b || !p->finalized || b->ix != ix) return GM_E_ARG;
-    HIPCHK(hipSetDevice(ix->device));
-    hipStream_t st = S_(stream);
+// what the steps of the single pass hand each other
+struct MapState {
     GmDevParams dp;
-    int rc = sync_params(ix, p, dp, st, true);
-    if (rc) return rc;
-    b->mapped = false;
-    b->pair_flagged = 0;
-    if ((rc = fasta_forced_form(b)) != GM_OK) return rc;
-    if (b->n == 0) {                                 // nothing is launched: the counters and the path are this call's (all zero, no kernel), not the last block's
-        b->n_cands = 0; b->n_raw = 0; b->mapped = true; memset(b->counters_host, 0, sizeof b->counters_host); b->counters_on_host = true;
-        b->path = std::string("reads=") + (b->fasta ? "fasta" : "fastq") + " (empty block: no kernel)";
-        return GM_OK;
-    }
-    // what the upload bound and what it did not (gnumap_hip.h at gm_batch_upload): the fallback scan of --illumina read the host's
-    // quality rows then, so `illumina` cannot change; the seed rows follow THIS call's -m / -j, whatever the upload sized them for
+    MapForm form;
+    uint32_t epoch = 0;                             // the attempt's launch stamp for the own slots of k_vote_bucket; 0 = the count array form
+    unsigned long long ctr[GMK_N];                  // the work counters as the last vote attempt's wait brought them
+    std::vector<uint32_t> heavy;                    // {rs, n_seeds, SA hits} triples of the heavy path
+    // status words of a phase come back in ONE short DMA into page-locked memory (b->h_stat): [0..15] = b->small (n_retry, n_big, n_heavy,
+    // shard total, shard maximum), [16..] = the work counters
+    uint32_t* hs_small = nullptr;
+    unsigned long long* hs_ctr = nullptr;
+    uint64_t total = 0; uint32_t mx = 0;            // candidates in all shards and in the fullest one (gmk_shard_stats)
+    // of the last attempt: k_nw_rows loads rs_overflow bytes only when this is set.  The bytes are written by the vote kernels next to
+    // n_retry alone; the heavy path does not write them and is included only to stay on the safe side
+    bool any_superseded = false;
+};
+
+// b->dev for the launches of this call: the resident block, this call's form and the attempt's stamp on top.  Every ensure() inside the
+// call that may move a buffer is followed by this before the next launch (never by fill_dev_batch alone), and so is every vote attempt.
+static void map_fill_dev(gm_batch* b, const MapState& s) {
+    fill_dev_batch(b);
+    if (s.form.use_pack) b->dev.pack = b->pack.as<uint32_t>();
+    if (s.form.use_fixed) { b->dev.fixed_cands = b->fixed_cands.as<GmCand>(); b->dev.fixed_cnt = b->fixed_cnt.as<uint8_t>(); b->dev.fixed_epoch = s.epoch; }
+}
+
+// ... and off again however the call ends
+struct MapFormScope {
+    gm_batch* b;
+    ~MapFormScope() { b->dev.pack = nullptr; b->dev.fixed_cands = nullptr; b->dev.fixed_cnt = nullptr; b->dev.fixed_epoch = 0; }
+};
+
+// nothing is launched: the counters and the path are this call's (all zero, no kernel), not the last block's
+static int map_empty_block(gm_batch* b) {
+    b->n_cands = 0; b->n_raw = 0; b->mapped = true; memset(b->counters_host, 0, sizeof b->counters_host); b->counters_on_host = true;
+    b->path = std::string("reads=") + (b->fasta ? "fasta" : "fastq") + " (empty block: no kernel)";
+    return GM_OK;
+}
+
+// what the upload bound and what it did not (gnumap_hip.h at gm_batch_upload): the fallback scan of --illumina read the host's
+// quality rows then, so `illumina` cannot change; the seed rows follow THIS call's -m / -j, whatever the upload sized them for
+static int map_check_binding(const gm_params* p, gm_batch* b) {
     if (!b->fasta && (p->illumina != 0) != (b->up_illumina != 0)) {
         gm_set_error(std::string("gm_params.illumina = ") + (p->illumina ? "1" : "0") + " for a block uploaded with illumina = " + (b->up_illumina ? "1" : "0") +
                      ": the upload binds this field (its fallback scan read the quality rows); upload the block again under the other value");
@@ -1018,323 +1185,263 @@ extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b
     }
     if (const uint32_t ms = seed_rows(b->stride, p); ms != b->max_seeds) {
         b->max_seeds = ms;
-        if (b->seeds.ensure(2 * (size_t)b->n * ms * sizeof(GmSeed))) return GM_E_NOMEM;      // (fill_dev_batch below, before the first launch)
+        if (b->seeds.ensure(2 * (size_t)b->n * ms * sizeof(GmSeed))) return GM_E_NOMEM;      // (map_fill_dev comes before the first launch)
     }
-    const int use_full = ix->full_sa ? 1 : 0;
-    // which vote kernel: expected SA hits per seed ~ reference length / 4^mer (capped by -h), expected seeds per strand from the
-    // longest read.  0 = sparse (<= 16 hits per read x strand fit a 16-lane group), 1 = k_vote_slots (its hits fit 40 slots of
-    // 64 lanes), 2 = its 64-slot form, 3 = k_vote_block (more: rounds of 2048 hits).  GM_VOTE=wave|block|big|rounds forces 0..3, GM_VOTE_KERNEL the dense form.
-    int dense = 0, slots_hint = 40;                  // slots_hint: expected 64-lane slots per read x strand (picks the k_vote_slots form)
-    {
-        double per_seed = (double)ix->h.seq_len / pow(4.0, (double)std::min(p->mer, 31));
-        if (p->max_kmer_hits > 0) per_seed = std::min(per_seed, (double)p->max_kmer_hits);
-        const double L = (double)b->stride;
-        double ns = L > p->mer ? floor((L - p->mer - 1) / std::max(1, p->jump)) + 1 : 1;
-        if (p->nw && p->fast) ns = 1;
-        ns = std::min(ns, (double)b->max_seeds);
-        const double e_exp = ns * (1.0 + per_seed);                                      // the true locus + chance hits
-        const double slots_exp = ns * ceil((per_seed + 3.0 * sqrt(per_seed) + 1.0) / 64.0);
-        dense = e_exp > 14.0 ? (slots_exp <= 38.0 ? 1 : slots_exp <= 60.0 ? 2 : 3) : 0;
-        slots_hint = (int)std::min(1000.0, slots_exp);
-        // few hits in many short runs (long seeds on a large reference): one wave per read x strand, 16-rank groups (k_vote_tiny)
-        const double groups_exp = ns * ceil((per_seed + 3.0 * sqrt(per_seed) + 1.0) / 16.0);
-        if (dense == 1 && p->min_seed_hits >= 2 && e_exp + 4.0 * sqrt(e_exp) <= 230.0 && groups_exp <= 28.0) slots_hint = 0;
-        else if (dense == 1 && p->min_seed_hits >= 2 && e_exp + 4.0 * sqrt(e_exp) <= 350.0 && groups_exp <= 56.0) slots_hint = -1;      // k_vote_tiny2
-        if (const char* ev = gm_opt("GM_VOTE_SLOTS")) { if (*ev) slots_hint = atoi(ev); }
-        if (const char* ev = gm_opt("GM_VOTE")) dense = !strcmp(ev, "block") ? 1 : !strcmp(ev, "big") ? 2 : !strcmp(ev, "rounds") ? 3 : !strcmp(ev, "wave") ? 0 : dense;
-    }
-    b->counters_on_host = false;
-    {   // optional sub-batch pipeline over several streams for large full-SA batches (GM_PIPELINE=<sub-batch size>).  Measured
-        // +4 % at configs[1]: three vote kernels end up sharing the LDS rather than hiding seed / NW work, and per-kernel
-        // timings stop being attributable, so it is off by default.
-        uint32_t sub_n = 0;
-        sub_n = (uint32_t)gm_opt_ll("GM_PIPELINE", 0);
-        if (use_full && sub_n >= 4096 && b->n >= 3 * (uint64_t)sub_n) {
-            // the sub-batches run k_prep -> k_seed -> gmk_vote on shard candidates: no 2-bit read forms, no own slots.  These three are the
-            // LAST call's until the single pass below sets them, and map_pipelined fills its views from them: a `pack` left on by a
-            // bucket-table call made every sub-batch's k_prep write its read forms into a buffer sized for that earlier, smaller block
-            b->use_pack = false; b->use_fixed = false; b->fixed_epoch = 0;
-            b->path.clear();                             // the single-pass dispatch records its choice; a block the sub-batches map to the end has none (not the last call's)
-            int prc = map_pipelined(ix, p, dp, b, st, dense, slots_hint, sub_n);
-            if (prc <= 0) return prc;                    // done, or a real error
-        }
-    }
-    // read x strands with very many SA hits (repeat seeds without -h) leave the ordinary vote kernels before they start: sorted-key
-    // path of gm_heavy.hip, routed by the seed search's own hit count.  GM_HEAVY_MIN / GM_HEAVY_BUDGET (keys per chunk) are test switches.
-    const uint32_t heavy_min = (uint32_t)gm_opt_ll("GM_HEAVY_MIN", 16384);
-    const uint64_t heavy_budget = (uint64_t)gm_opt_ll("GM_HEAVY_BUDGET", 1ll << 27);
-    dp.heavy_min = heavy_min;
-    bool use_bucket = false, use_pair = false, pair_direct = false; uint32_t bucket_reg = 0;
-    // seed lookup inside the vote kernels that take one read x strand per wave / workgroup (full SA, the k-mer table covering the
-    // whole seed): no k_seed launch, no seed rows through HBM.  A k-mer that does not occur changes the positions of all later ones;
-    // the wave then walks again round by round (gm_seed_rewalk_ool), one probe round trip per failing k-mer.  That stays rare while
-    // even a k-mer with a sequencing error still occurs somewhere by chance - every k-mer expected >= 4 times in the reference
-    // (measured on 100 Mbp: -m 12, 6 per k-mer: 21.0 ms fused against 27.7; -m 14, 0.4 per k-mer: an erroneous k-mer dies one or two
-    // characters before its end, the walk creeps past the error in ~9 rounds, 207 against 29.5 ms - k_seed amortises those serial
-    // steps over 64 lanes).  GM_SEED_FUSED=0 / 1: never / whenever possible.
-    {
-        const int fused_env = (int)gm_opt_ll("GM_SEED_FUSED", -1);
-        const double occ = (double)ix->h.seq_len / pow(4.0, (double)std::min(p->mer, 31));
-        // -h: on a real reference the k-mers of repeats exceed any cap, and each of them makes the walk slide base by base (:213-217) in
-        // one lane - not measurable on the synthetic references of bench.py, so a capped run keeps k_seed unless forced
-        const bool pays = occ >= 4.0 && p->max_kmer_hits == 0;
-        dp.fused = (fused_env < 0 ? pays : fused_env != 0) && use_full && (dense == 1 || dense == 2) && !gm_opt("GM_VOTE_KERNEL") && b->max_seeds <= 64 && dp.kmer_tab &&
-                   dp.kmer_ctab && dp.kmer_T == p->mer && p->mer <= 16 && p->jump >= 1 && !(dp.dbg & 128);
-        // ... or in the bucket table (one read per wave, both strands; handles -h and k-mers that do not occur by walking again):
-        // every seed is ONE random line
-        const uint32_t lastmax = b->len_max > (uint32_t)p->mer ? b->len_max - (uint32_t)p->mer : 0;      // (the longest read of the block, not the row stride)
-        const uint32_t max_reg = (lastmax + (uint32_t)p->jump - 1) / (uint32_t)p->jump;
-        use_bucket = dp.bucket && use_full && dp.kmer_tab && dp.kmer_T == dp.bucket_T && dp.bucket_T == p->mer && p->min_seed_hits >= 2 && max_reg <= 32 && b->max_seeds <= 34 && !gm_opt("GM_VOTE_KERNEL") &&
-                     !gm_opt("GM_VOTE") && gm_opt_ll("GM_PIPELINE", 0) == 0 && !(dp.dbg & 128) && fused_env != 0;
-        // -A: the minus strand's k-mers come from another stretch of the row than its DP (see k_seed): only k_seed knows that form
-        if (!b->adaptor.empty()) { dp.fused = 0; use_bucket = false; }
-        if (use_bucket) { dp.fused = 1; bucket_reg = max_reg; } else dp.bucket = nullptr;
-        // ... two reads per wavefront (gm_pair.hip) where a strand has at most 16 seeds; GM_VOTE_PAIR=0: one read per wavefront always
-        use_pair = use_bucket && !dp.bucket_ctx && max_reg <= 16 && !(p->nw && p->fast) && !gm_opt_is("GM_VOTE_PAIR", "0") && !(dp.dbg & (64 | 256 | 512 | 1024 | 2048));       // (GM_DBG 4096 .. 32768: timing experiments of k_vote_pair)
-        // hand-off of k_vote_pair's results: straight into the candidate shards and the flagged reads' list at each 16-pair flush (default),
-        // or GM_PAIR_HANDOFF=gather: own candidate slots + one flag byte per read, read back by k_cand_gather / k_pair_collect / k_heavy_collect
-        pair_direct = use_pair && !gm_opt_is("GM_PAIR_HANDOFF", "gather");
-        if (use_pair && b->pair_list.ensure(((size_t)b->n + 16) * 4)) return GM_E_NOMEM;
-        if (use_pair && !pair_direct && b->pair_fb.ensure((size_t)b->n + 64)) return GM_E_NOMEM;
-        b->use_pack = dp.fused != 0;
-        if (b->use_pack && b->pack.ensure((size_t)b->n * gm_pack_words(b->stride) * 4 + 64)) return GM_E_NOMEM;
-    }
-    // the one-wave vote kernels leave their candidates in per read x strand slots (no bump counter on the wave's critical path)
-    {
-        const bool fixed_ok = !gm_opt_is("GM_VOTE_FIXED", "0");
-        b->use_fixed = fixed_ok && !pair_direct && (use_bucket || ((dense == 1 || dense == 2) && !gm_opt("GM_VOTE_KERNEL")));      // k_vote_bucket, k_vote_tiny*, k_vote_slots (all forms)
-        if (b->use_fixed) {
-            const size_t cap_before = b->fixed_cands.cap;       // by CAPACITY: hipFree + a larger hipMalloc may hand back the same base address
-            if (b->fixed_cands.ensure(((2 * (size_t)b->n + 63) / 64) * 64 * GM_FIXED_C * sizeof(GmCand)) || b->fixed_cnt.ensure(2 * (size_t)b->n + 64)) return GM_E_NOMEM;
-            // new memory: no stale launch stamps.  (TEST switch GM_TEST_EPOCH=<start>: the counter starts there, so that a few calls reach the
-            // NaN / inf / denormal bit patterns of the stamp and the 32-bit wrap)
-            if (b->fixed_cands.cap != cap_before) { HIPCHK(hipMemsetAsync(b->fixed_cands.p, 0, b->fixed_cands.cap, st)); b->epoch_ctr = (uint32_t)gm_opt_ll("GM_TEST_EPOCH", 0); }
-        }
-        b->fixed_epoch = 0;
-    }
-    {
-        char buf[224];
-        const int pp_env = (int)gm_opt_ll("GM_SLOTS_PIPE", -1);                                               // (gmk_vote's condition for the pipelined form of k_vote_slots)
-        const bool slots_pp = use_full && !gm_opt("GM_VOTE_KERNEL") && (pp_env < 0 ? dense == 2 : pp_env != 0) && !(dp.dbg & 64);
-        // gmk_vote's own branches: more than 64 seeds per strand leave the one-workgroup kernels for the ordered k_vote, GM_VOTE_KERNEL picks
-        // the dense form whatever `dense` says, GM_VOTE_SPARSE=0 runs k_vote_fast for every read x strand
-        const char* kenv = gm_opt("GM_VOTE_KERNEL"); if (kenv && !*kenv) kenv = nullptr;
-        const bool wg_form = dense != 0 && b->max_seeds <= 64;
-        const bool slots_form = wg_form && (kenv ? !strcmp(kenv, "slots") : dense <= 2);
-        snprintf(buf, sizeof buf, "seeds=%s vote=%s locate=%s cands=%s", use_bucket ? "bucket-table (in the vote kernel)" : dp.fused ? "k-mer table (in the vote kernel)" : "k_seed",
-                 use_pair ? (bucket_reg <= 8 ? "k_vote_pair<4> + k_vote_bucket<2>" : bucket_reg <= 14 ? "k_vote_pair<7> + k_vote_bucket<4>" : "k_vote_pair<8> + k_vote_bucket<4>")
-                 : use_bucket ? (bucket_reg <= 8 ? "k_vote_bucket<2>" : bucket_reg <= 16 ? "k_vote_bucket<4>" : bucket_reg <= 24 ? "k_vote_bucket<6>" : "k_vote_bucket<8>")
-                            : !wg_form ? (b->max_seeds > 64 ? "k_vote" : gm_opt_is("GM_VOTE_SPARSE", "0") ? "k_vote_fast" : "sparse") : !slots_form ? "k_vote_block"
-                            : dense == 2 ? (slots_pp ? "k_vote_slots_pp<64>" : "k_vote_slots<64>") : slots_hint == 0 ? "k_vote_tiny" : slots_hint < 0 ? "k_vote_tiny2" : slots_pp ? "k_vote_slots_pp" : "k_vote_slots",
-                 use_full ? "full-SA" : "sampled-SA", b->use_fixed ? "own-slots" : "shards");
-        b->path = std::string("reads=") + (b->fasta ? "fasta " : "fastq ") + buf;
-        GM_TRACE("path: %s", buf);
-    }
-    fill_dev_batch(b);
+    return GM_OK;
+}
+
+// k_prep, k_seed unless the vote kernels look the seeds up, and on a sampled-SA index the locate pass with its one wait
+static int map_prep_seed(gm_index* ix, gm_batch* b, MapState& s, hipStream_t st) {
+    map_fill_dev(b, s);
     HIPCHK(hipMemsetAsync(b->counters.p, 0, GMK_N * 8, st));
-    { KTimer t(b, GM_K_PREP, st); KCHK(gmk_prep(ix->dev, dp, b->dev, st)); }
-    if (!dp.fused) { KTimer t(b, GM_K_SEED, st); KCHK(gmk_seed(ix->dev, dp, b->dev, st, b->adaptor.empty() ? nullptr : b->full_len.as<uint16_t>())); }
-    unsigned long long ctr[GMK_N];
-    if (!use_full) {
+    { KTimer t(b, GM_K_PREP, st); KCHK(gmk_prep(ix->dev, s.dp, b->dev, st)); }
+    if (!s.form.fused) { KTimer t(b, GM_K_SEED, st); KCHK(gmk_seed(ix->dev, s.dp, b->dev, st, b->adaptor.empty() ? nullptr : b->full_len.as<uint16_t>())); }
+    if (!s.form.use_full) {
         // faithful mode: locate every SA hit by LF walks into coords[] first (exact size from the seed kernel)
-        HIPCHK(hipMemcpyAsync(ctr, b->counters.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(s.ctr, b->counters.p, sizeof s.ctr, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        if (b->coords.ensure((size_t)ctr[GMK_SA_HITS] * 4 + 64)) return GM_E_NOMEM;
-        fill_dev_batch(b);
+        if (b->coords.ensure((size_t)s.ctr[GMK_SA_HITS] * 4 + 64)) return GM_E_NOMEM;
+        map_fill_dev(b, s);
         KCHK(gmk_scan_entries(b->dev, st));
-        { KTimer t(b, GM_K_LOCATE, st); KCHK(gmk_locate_sampled(ix->dev, b->dev, ctr[GMK_SA_HITS], st)); }
+        { KTimer t(b, GM_K_LOCATE, st); KCHK(gmk_locate_sampled(ix->dev, b->dev, s.ctr[GMK_SA_HITS], st)); }
     }
-    std::vector<uint32_t> heavy;                     // {rs, n_seeds, SA hits} triples
-    if (b->heavy_list.ensure(3 * 2 * (size_t)b->n * 4 + 64)) return GM_E_NOMEM;
-    // the list of the heavy path: right after k_seed, or (fused form) after the first vote launch, which left them alone
-    // status words of a phase come back in ONE short DMA into page-locked memory: [0..15] = b->small (n_retry, n_big, n_heavy, shard total,
-    // shard maximum), [16..] = the work counters
-    if (b->h_stat.ensure(64 + GMK_N * 8 + 64)) return GM_E_NOMEM;
-    uint32_t* const hs_small = b->h_stat.as<uint32_t>();
-    unsigned long long* const hs_ctr = reinterpret_cast<unsigned long long*>(b->h_stat.as<uint8_t>() + 64);
-    auto collect_heavy_enqueue = [&]() -> int {      // (the count is read back with the phase's status words)
-        HIPCHK(hipMemsetAsync(b->small.as<uint32_t>() + 3, 0, 4, st));
-        KCHK(gmk_heavy_collect(b->dev, heavy_min, b->small.as<uint32_t>() + 3, b->heavy_list.as<uint32_t>(), dp.fused,
-                               pair_direct ? b->pair_list.as<uint32_t>() + 4 : nullptr, pair_direct ? b->pair_list.as<uint32_t>() : nullptr, st));
-        return GM_OK;
-    };
-    auto fetch_heavy = [&](uint32_t nh) -> int {
-        GM_TRACE("map_device: %u reads, seeds done, %u read x strands on the heavy path (> %u SA hits)", b->n, nh, heavy_min);
-        heavy.clear();
-        if (nh) {
-            heavy.resize(3 * (size_t)nh);
-            HIPCHK(hipMemcpy(heavy.data(), b->heavy_list.p, heavy.size() * 4, hipMemcpyDeviceToHost));
-        }
-        return GM_OK;
-    };
-    auto collect_heavy = [&]() -> int {              // the two-kernel form: right after k_seed
-        int rc2 = collect_heavy_enqueue();
-        if (rc2) return rc2;
-        HIPCHK(hipMemcpyAsync(hs_small, b->small.p, 64, hipMemcpyDeviceToHost, st));
+    if (b->heavy_list.ensure(3 * 2 * (size_t)b->n * 4 + 64) || b->h_stat.ensure(64 + GMK_N * 8 + 64)) return GM_E_NOMEM;
+    s.hs_small = b->h_stat.as<uint32_t>();
+    s.hs_ctr = reinterpret_cast<unsigned long long*>(b->h_stat.as<uint8_t>() + 64);
+    return GM_OK;
+}
+
+// the list of the heavy path: collected right after k_seed, or (fused form) after the first vote launch, which left those read x strands
+// alone.  Enqueued here; the count comes back with the phase's status words, then the triples are fetched
+static int map_heavy_enqueue(gm_batch* b, const MapState& s, hipStream_t st) {
+    const bool direct = s.form.pair_direct;
+    HIPCHK(hipMemsetAsync(b->small.as<uint32_t>() + 3, 0, 4, st));
+    KCHK(gmk_heavy_collect(b->dev, s.form.heavy_min, b->small.as<uint32_t>() + 3, b->heavy_list.as<uint32_t>(), s.form.fused,
+                           direct ? b->pair_list.as<uint32_t>() + 4 : nullptr, direct ? b->pair_list.as<uint32_t>() : nullptr, st));
+    return GM_OK;
+}
+
+static int map_heavy_fetch(gm_batch* b, MapState& s) {
+    const uint32_t nh = s.hs_small[3];
+    GM_TRACE("map_device: %u reads, seeds done, %u read x strands on the heavy path (> %u SA hits)", b->n, nh, s.form.heavy_min);
+    s.heavy.clear();
+    if (nh) {
+        s.heavy.resize(3 * (size_t)nh);
+        HIPCHK(hipMemcpy(s.heavy.data(), b->heavy_list.p, s.heavy.size() * 4, hipMemcpyDeviceToHost));
+    }
+    return GM_OK;
+}
+
+static int map_heavy_after_seed(gm_batch* b, MapState& s, hipStream_t st) {      // the two-kernel form
+    if (int rc = map_heavy_enqueue(b, s, st)) return rc;
+    HIPCHK(hipMemcpyAsync(s.hs_small, b->small.p, 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return map_heavy_fetch(b, s);
+}
+
+// candidates per shard: total and maximum are reduced on the device (gmk_shard_stats -> small[4], small[5]) and come back with the
+// status words and the counters in one wait
+static int map_read_status(gm_batch* b, MapState& s, hipStream_t st) {
+    KCHK(gmk_shard_stats(b->dev, b->small.as<uint32_t>() + 4, s.form.use_pair ? b->pair_list.as<uint32_t>() : nullptr, st));
+    HIPCHK(hipMemcpyAsync(s.hs_small, b->small.p, 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(s.hs_ctr, b->counters.p, GMK_N * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    s.total = s.hs_small[4]; s.mx = s.hs_small[5]; b->pair_flagged = s.hs_small[6];
+    return GM_OK;
+}
+
+// one attempt at the vote: the per-attempt clears, the launch group, the heavy list when fused, and the ONE wait of the vote phase
+static int map_vote_attempt(gm_index* ix, gm_batch* b, MapState& s, hipStream_t st) {
+    const MapForm& f = s.form;
+    HIPCHK(hipMemsetAsync(b->small.p, 0, 64, st));
+    HIPCHK(hipMemsetAsync(b->shards.p, 0, (size_t)GM_NSHARD * GM_SHARD_STRIDE * 4, st));
+    HIPCHK(hipMemsetAsync(b->rs_overflow.p, 0, 2 * (size_t)b->n, st));
+    HIPCHK(hipMemsetAsync(b->counters.as<unsigned long long>() + GMK_HEAVY_SLOTS, 0, 8, st));
+    HIPCHK(hipMemsetAsync(b->counters.as<unsigned long long>() + GMK_OVERFLOW_RS, 0, 8, st));
+    if (f.use_fixed && f.use_bucket) {          // own-slot candidates carry the launch's stamp: nothing to zero but the flags "goes to the list kernel"
+        HIPCHK(hipMemsetAsync(b->fixed_cnt.p, 0, 2 * (size_t)b->n + 32, st));
+        if (++b->epoch_ctr == 0) { HIPCHK(hipMemsetAsync(b->fixed_cands.p, 0, b->fixed_cands.cap, st)); b->epoch_ctr = 1; }
+        s.epoch = b->epoch_ctr;
+    } else if (f.use_fixed) HIPCHK(hipMemsetAsync(b->fixed_cnt.p, 0, 2 * (size_t)b->n, st));
+    map_fill_dev(b, s);                          // every attempt starts from b->dev filled anew: the stamp, and the list map_grow_cands moved
+    if (f.fused) {                               // the seed search runs inside the vote launch: its work counters start over with it
+        HIPCHK(hipMemsetAsync(b->counters.as<unsigned long long>() + GMK_KMERS, 0, 4 * 8, st));            // KMERS, OCC, SEEDS, SA_HITS
+        HIPCHK(hipMemsetAsync(b->counters.as<unsigned long long>() + GMK_OCC_BLOCKS, 0, 2 * 8, st));       // OCC_BLOCKS, TAB_LOOKUPS
+    }
+    {
+        KTimer t(b, GM_K_VOTE, st);
+        uint32_t* const plist = b->pair_list.as<uint32_t>();
+        if (f.use_bucket && f.use_pair) {
+            // two reads per wavefront for the reads without complications; the flagged ones go through k_vote_bucket (direct hand-off:
+            // no own slots - k_vote_bucket and the list kernel append their candidates and list entries as they go)
+            if (!f.pair_direct) HIPCHK(hipMemsetAsync(b->pair_fb.p, 0, (size_t)b->n + 16, st));
+            HIPCHK(hipMemsetAsync(b->pair_list.p, 0, 16, st));
+            KCHK(gmk_vote_pair(ix->dev, s.dp, b->dev, f.bucket_reg, f.pair_direct ? nullptr : b->pair_fb.as<uint8_t>(), plist + 4, plist, st));
+            KCHK(gmk_vote_bucket(ix->dev, s.dp, b->dev, f.bucket_reg, plist + 4, plist, st));
+            KCHK(gmk_vote_list(ix->dev, s.dp, b->dev, f.use_full, st));
+        } else if (f.use_bucket) { KCHK(gmk_vote_bucket(ix->dev, s.dp, b->dev, f.bucket_reg, nullptr, nullptr, st)); KCHK(gmk_vote_list(ix->dev, s.dp, b->dev, f.use_full, st)); }
+        else KCHK(gmk_vote(ix->dev, s.dp, b->dev, f.use_full, f.dense, f.slots_hint, st));
+        KCHK(gmk_cand_gather(b->dev, st));
+    }
+    if (f.fused) { if (int rc = map_heavy_enqueue(b, s, st)) return rc; }
+    if (int rc = map_read_status(b, s, st)) return rc;
+    memcpy(s.ctr, s.hs_ctr, sizeof s.ctr);
+    return f.fused ? map_heavy_fetch(b, s) : GM_OK;
+}
+
+// GM_DBG 64: sampled phase clocks of the vote kernel (cycles of one lane per sampled workgroup)
+static void map_print_vote_phases(const MapState& s) {
+    const unsigned long long* ctr = s.ctr;
+    const double ns = (double)std::max<unsigned long long>(1, ctr[GMK_DBG8]);
+    if (s.form.use_bucket) fprintf(stderr, "[gm_dbg] k_vote_bucket phases (mean clock ticks of lane 0 per sampled read, %llu samples; reads that leave early do not reach the later marks): forms + codes %.0f, "
+                    "records %.0f, first walk %.0f, routing %.0f, filter pass %.0f, sweeps %.0f, store %.0f\n", ctr[GMK_DBG8], ctr[GMK_DBG0] / ns, ctr[GMK_DBG1] / ns, ctr[GMK_DBG2] / ns,
+                    ctr[GMK_DBG3] / ns, ctr[GMK_DBG4] / ns, ctr[GMK_DBG5] / ns, ctr[GMK_DBG6] / ns);
+    else
+    fprintf(stderr, "[gm_dbg] vote phases (mean cycles per sampled read x strand, %llu samples): desc %.0f, loads+window %.0f, pass1 %.0f, pass2a %.0f, scan %.0f, "
+                    "filter2 %.0f, table %.0f, emit %.0f\n", ctr[GMK_DBG8], ctr[GMK_DBG0] / ns, ctr[GMK_DBG1] / ns, ctr[GMK_DBG2] / ns, ctr[GMK_DBG3] / ns, ctr[GMK_DBG4] / ns,
+            ctr[GMK_DBG5] / ns, ctr[GMK_DBG6] / ns, ctr[GMK_DBG7] / ns);
+}
+
+// the n_retry read x strands whose hits did not fit their vote kernel, through hash tables in HBM: all at once, or when the tables of all
+// of them exceed GM_RETRY_BUDGET (table slots per launch: 2 GB of keys + counts; the switch is for tests) in groups.  Ends with the shards' new status
+static int map_retry(gm_index* ix, gm_batch* b, MapState& s, uint32_t n_retry, hipStream_t st) {
+    const size_t slots = (size_t)s.ctr[GMK_HEAVY_SLOTS];
+    const size_t budget = (size_t)gm_opt_ll("GM_RETRY_BUDGET", 1ll << 28);
+    if (slots <= budget) {
+        if (int rc = map_retry_tables(b->gtab_keys, b->gtab_vals, slots, st)) return rc;
+        map_fill_dev(b, s);
+        { KTimer t(b, GM_K_VOTE_RETRY, st); KCHK(gmk_vote_retry(ix->dev, s.dp, b->dev, s.form.use_full, 0, n_retry, st)); }
+    } else {
+        // many read x strands at once (a kernel choice that did not fit the data): the tables are handed out again per
+        // launch instead of all at once
+        std::vector<uint32_t> list(n_retry), nent((size_t)2 * b->n);
+        HIPCHK(hipMemcpyAsync(list.data(), b->retry_list.p, (size_t)n_retry * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(nent.data(), b->n_entries.p, nent.size() * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        return fetch_heavy(hs_small[3]);
-    };
-    if (!dp.fused) { rc = collect_heavy(); if (rc) return rc; }
-    auto run_heavy = [&]() -> int {                  // expand + sort + run-length vote, chunk by chunk under the key budget
-        const uint32_t nh = (uint32_t)(heavy.size() / 3);
-        std::vector<unsigned long long> off;
-        for (uint32_t j = 0; j < nh;) {
+        if (b->gtab_keys.ensure(budget * 4) || b->gtab_vals.ensure(budget * 4)) return GM_E_NOMEM;
+        map_fill_dev(b, s);
+        std::vector<unsigned long long> off(n_retry);
+        KTimer t(b, GM_K_VOTE_RETRY, st);
+        for (uint32_t j = 0; j < n_retry;) {
             const uint32_t j0 = j;
-            unsigned long long acc = 0;
-            off.clear();
-            while (j < nh && j - j0 < 65536u) {
-                const unsigned long long e = heavy[3 * (size_t)j + 2];
-                if (e == 0xFFFFFFFFull || e > heavy_budget) { gm_set_error("a read x strand with more SA hits than one heavy-path chunk holds; use -h"); return GM_E_BATCH_TOO_LARGE; }
-                if (acc + e > heavy_budget) break;
-                off.push_back(acc); acc += e; ++j;
+            size_t acc = 0;
+            while (j < n_retry) {
+                size_t need = 2 * (size_t)nent[list[j]], sz = 1024;
+                while (sz < need && sz < 0x80000000u) sz <<= 1;
+                if (sz > budget) { gm_set_error("a read x strand with more SA hits than the retry table budget; use -h"); return GM_E_BATCH_TOO_LARGE; }
+                if (acc + sz > budget) break;
+                off[j] = acc; acc += sz; ++j;
             }
-            const uint32_t nj = j - j0;
-            unsigned item_bits = 1; while ((1u << item_bits) < nj) ++item_bits;
-            const size_t tmp_bytes = gmk_heavy_sort_temp_bytes((size_t)acc);
-            if (b->heavy_k0.ensure((size_t)acc * 8 + 64) || b->heavy_k1.ensure((size_t)acc * 8 + 64) || b->heavy_tmp.ensure(tmp_bytes + 64) ||
-                b->heavy_off.ensure((size_t)nj * 8 + 64)) return GM_E_NOMEM;
-            HIPCHK(hipMemcpyAsync(b->heavy_off.p, off.data(), (size_t)nj * 8, hipMemcpyHostToDevice, st));
-            KCHK(gmk_heavy_chunk(ix->dev, dp, b->dev, use_full, b->heavy_list.as<uint32_t>(), j0, nj, b->heavy_off.as<unsigned long long>(),
-                                 b->heavy_k0.as<unsigned long long>(), b->heavy_k1.as<unsigned long long>(), acc, b->heavy_tmp.p, tmp_bytes, item_bits, st));
-            HIPCHK(hipStreamSynchronize(st));        // off[] and the key buffers are reused by the next chunk
-            GM_TRACE("heavy chunk: items %u..%u of %u, %llu keys sorted", j0, j, nh, acc);
+            HIPCHK(hipMemcpyAsync(b->retry_off.as<unsigned long long>() + j0, off.data() + j0, (size_t)(j - j0) * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemsetAsync(b->gtab_keys.p, 0xFF, acc * 4, st));
+            HIPCHK(hipMemsetAsync(b->gtab_vals.p, 0, acc * 4, st));
+            KCHK(gmk_vote_retry(ix->dev, s.dp, b->dev, s.form.use_full, j0, j - j0, st));
+            HIPCHK(hipStreamSynchronize(st));        // off[] is reused by the next group
         }
-        return GM_OK;
-    };
-    // candidates per shard: total and maximum are reduced on the device (gmk_shard_stats -> small[4], small[5]) and come back with the status words
-    auto read_status = [&](uint64_t& total, uint32_t& mx) -> int {
-        KCHK(gmk_shard_stats(b->dev, b->small.as<uint32_t>() + 4, use_pair ? b->pair_list.as<uint32_t>() : nullptr, st));
-        HIPCHK(hipMemcpyAsync(hs_small, b->small.p, 64, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(hs_ctr, b->counters.p, GMK_N * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        total = hs_small[4]; mx = hs_small[5]; b->pair_flagged = hs_small[6];
-        return GM_OK;
-    };
-    auto read_shards = read_status;
-    // of the last attempt: k_nw_rows loads rs_overflow bytes only when this is set.  The bytes are written by the vote kernels next to
-    // n_retry alone; the heavy path does not write them and is included only to stay on the safe side
-    bool any_superseded = false;
-    for (int attempt = 0;; ++attempt) {
-        HIPCHK(hipMemsetAsync(b->small.p, 0, 64, st));
-        HIPCHK(hipMemsetAsync(b->shards.p, 0, (size_t)GM_NSHARD * GM_SHARD_STRIDE * 4, st));
-        HIPCHK(hipMemsetAsync(b->rs_overflow.p, 0, 2 * (size_t)b->n, st));
-        HIPCHK(hipMemsetAsync(b->counters.as<unsigned long long>() + GMK_HEAVY_SLOTS, 0, 8, st));
-        HIPCHK(hipMemsetAsync(b->counters.as<unsigned long long>() + GMK_OVERFLOW_RS, 0, 8, st));
-        if (b->use_fixed && use_bucket) {           // own-slot candidates carry the launch's stamp: nothing to zero but the flags "goes to the list kernel"
-            HIPCHK(hipMemsetAsync(b->fixed_cnt.p, 0, 2 * (size_t)b->n + 32, st));
-            if (++b->epoch_ctr == 0) { HIPCHK(hipMemsetAsync(b->fixed_cands.p, 0, b->fixed_cands.cap, st)); b->epoch_ctr = 1; }
-            b->fixed_epoch = b->epoch_ctr;
-            fill_dev_batch(b);
-        } else if (b->use_fixed) HIPCHK(hipMemsetAsync(b->fixed_cnt.p, 0, 2 * (size_t)b->n, st));
-        if (dp.fused) {                              // the seed search runs inside the vote launch: its work counters start over with it
-            HIPCHK(hipMemsetAsync(b->counters.as<unsigned long long>() + GMK_KMERS, 0, 4 * 8, st));            // KMERS, OCC, SEEDS, SA_HITS
-            HIPCHK(hipMemsetAsync(b->counters.as<unsigned long long>() + GMK_OCC_BLOCKS, 0, 2 * 8, st));       // OCC_BLOCKS, TAB_LOOKUPS
-        }
-        {
-            KTimer t(b, GM_K_VOTE, st);
-            if (use_bucket && use_pair) {
-                // two reads per wavefront for the reads without complications; the flagged ones go through k_vote_bucket (direct hand-off:
-                // no own slots - k_vote_bucket and the list kernel append their candidates and list entries as they go)
-                if (!pair_direct) HIPCHK(hipMemsetAsync(b->pair_fb.p, 0, (size_t)b->n + 16, st));
-                HIPCHK(hipMemsetAsync(b->pair_list.p, 0, 16, st));
-                KCHK(gmk_vote_pair(ix->dev, dp, b->dev, bucket_reg, pair_direct ? nullptr : b->pair_fb.as<uint8_t>(), b->pair_list.as<uint32_t>() + 4, b->pair_list.as<uint32_t>(), st));
-                KCHK(gmk_vote_bucket(ix->dev, dp, b->dev, bucket_reg, b->pair_list.as<uint32_t>() + 4, b->pair_list.as<uint32_t>(), st));
-                KCHK(gmk_vote_list(ix->dev, dp, b->dev, use_full, st));
-            } else if (use_bucket) { KCHK(gmk_vote_bucket(ix->dev, dp, b->dev, bucket_reg, nullptr, nullptr, st)); KCHK(gmk_vote_list(ix->dev, dp, b->dev, use_full, st)); }
-            else KCHK(gmk_vote(ix->dev, dp, b->dev, use_full, dense, slots_hint, st));
-            KCHK(gmk_cand_gather(b->dev, st));
-        }
-        if (dp.fused) { rc = collect_heavy_enqueue(); if (rc) return rc; }
-        uint64_t total = 0; uint32_t mx = 0;
-        rc = read_status(total, mx);                 // the one wait of the vote phase
-        if (rc) return rc;
-        memcpy(ctr, hs_ctr, sizeof ctr);
-        const uint32_t small[2] = { hs_small[0], hs_small[1] };
-        if (dp.fused) { rc = fetch_heavy(hs_small[3]); if (rc) return rc; }
-        if (dp.dbg & 64) {                           // sampled phase clocks of the vote kernel (cycles of one lane per sampled workgroup)
-            const double ns = (double)std::max<unsigned long long>(1, ctr[GMK_DBG8]);
-            if (use_bucket) fprintf(stderr, "[gm_dbg] k_vote_bucket phases (mean clock ticks of lane 0 per sampled read, %llu samples; reads that leave early do not reach the later marks): forms + codes %.0f, "
-                            "records %.0f, first walk %.0f, routing %.0f, filter pass %.0f, sweeps %.0f, store %.0f\n", ctr[GMK_DBG8], ctr[GMK_DBG0] / ns, ctr[GMK_DBG1] / ns, ctr[GMK_DBG2] / ns,
-                            ctr[GMK_DBG3] / ns, ctr[GMK_DBG4] / ns, ctr[GMK_DBG5] / ns, ctr[GMK_DBG6] / ns);
-            else
-            fprintf(stderr, "[gm_dbg] vote phases (mean cycles per sampled read x strand, %llu samples): desc %.0f, loads+window %.0f, pass1 %.0f, pass2a %.0f, scan %.0f, "
-                            "filter2 %.0f, table %.0f, emit %.0f\n", ctr[GMK_DBG8], ctr[GMK_DBG0] / ns, ctr[GMK_DBG1] / ns, ctr[GMK_DBG2] / ns, ctr[GMK_DBG3] / ns, ctr[GMK_DBG4] / ns,
-                    ctr[GMK_DBG5] / ns, ctr[GMK_DBG6] / ns, ctr[GMK_DBG7] / ns);
-        }
-        if (ctr[GMK_BAD_QUAL] && !b->fasta) { gm_set_error("Invalid Fastq Character? (negative base probability)"); return GM_E_BAD_QUAL; }
-        uint32_t n_retry = small[1];
-        any_superseded = n_retry != 0 || !heavy.empty();
-        if (n_retry && mx <= b->dev.cand_region) {
-            size_t slots = (size_t)ctr[GMK_HEAVY_SLOTS];
-            const size_t budget = (size_t)gm_opt_ll("GM_RETRY_BUDGET", 1ll << 28);   // table slots per launch (2 GB of keys + counts; the switch is for tests)
-            if (slots <= budget) {
-                if (b->gtab_keys.ensure(slots * 4) || b->gtab_vals.ensure(slots * 4)) return GM_E_NOMEM;
-                fill_dev_batch(b);
-                HIPCHK(hipMemsetAsync(b->gtab_keys.p, 0xFF, slots * 4, st));
-                HIPCHK(hipMemsetAsync(b->gtab_vals.p, 0, slots * 4, st));
-                { KTimer t(b, GM_K_VOTE_RETRY, st); KCHK(gmk_vote_retry(ix->dev, dp, b->dev, use_full, 0, n_retry, st)); }
-            } else {
-                // many read x strands at once (a kernel choice that did not fit the data): the tables are handed out again per
-                // launch instead of all at once
-                std::vector<uint32_t> list(n_retry), nent((size_t)2 * b->n);
-                HIPCHK(hipMemcpyAsync(list.data(), b->retry_list.p, (size_t)n_retry * 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipMemcpyAsync(nent.data(), b->n_entries.p, nent.size() * 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                if (b->gtab_keys.ensure(budget * 4) || b->gtab_vals.ensure(budget * 4)) return GM_E_NOMEM;
-                fill_dev_batch(b);
-                std::vector<unsigned long long> off(n_retry);
-                KTimer t(b, GM_K_VOTE_RETRY, st);
-                for (uint32_t j = 0; j < n_retry;) {
-                    const uint32_t j0 = j;
-                    size_t acc = 0;
-                    while (j < n_retry) {
-                        size_t need = 2 * (size_t)nent[list[j]], sz = 1024;
-                        while (sz < need && sz < 0x80000000u) sz <<= 1;
-                        if (sz > budget) { gm_set_error("a read x strand with more SA hits than the retry table budget; use -h"); return GM_E_BATCH_TOO_LARGE; }
-                        if (acc + sz > budget) break;
-                        off[j] = acc; acc += sz; ++j;
-                    }
-                    HIPCHK(hipMemcpyAsync(b->retry_off.as<unsigned long long>() + j0, off.data() + j0, (size_t)(j - j0) * 8, hipMemcpyHostToDevice, st));
-                    HIPCHK(hipMemsetAsync(b->gtab_keys.p, 0xFF, acc * 4, st));
-                    HIPCHK(hipMemsetAsync(b->gtab_vals.p, 0, acc * 4, st));
-                    KCHK(gmk_vote_retry(ix->dev, dp, b->dev, use_full, j0, j - j0, st));
-                    HIPCHK(hipStreamSynchronize(st));        // off[] is reused by the next group
-                }
-            }
-            rc = read_shards(total, mx);
-            if (rc) return rc;
-        }
-        if (!heavy.empty() && mx <= b->dev.cand_region) {
-            KTimer t(b, GM_K_VOTE_RETRY, st);
-            rc = run_heavy();
-            if (rc) return rc;
-            rc = read_shards(total, mx);
-            if (rc) return rc;
-        }
-        if (mx > b->dev.cand_region) {                  // a candidate shard overflowed: grow the list and vote again
-            if (attempt > 8) { gm_set_error("candidate list keeps overflowing"); return GM_E_NOMEM; }
-            size_t want = ((size_t)mx + mx / 4 + 64) * GM_NSHARD;
-            if (want > 0x7FFFFFFFu) { gm_set_error("more than 2^31 candidates in one batch; map the block in smaller pieces (or use -h)"); return GM_E_BATCH_TOO_LARGE; }
-            b->cand_cap = (uint32_t)want;
-            if (b->cands.ensure((size_t)b->cand_cap * sizeof(GmCand))) return GM_E_NOMEM;
-            fill_dev_batch(b);
-            continue;
-        }
-        b->n_cands = (uint32_t)total;
-        GM_TRACE("vote done: %llu candidates (attempt %d)", (unsigned long long)total, attempt);
-        break;
     }
+    return map_read_status(b, s, st);
+}
+
+// the heavy list: expand + sort + run-length vote, chunk by chunk under the key budget.  Ends with the shards' new status
+static int map_heavy_chunks(gm_index* ix, gm_batch* b, MapState& s, hipStream_t st) {
+    KTimer t(b, GM_K_VOTE_RETRY, st);
+    const std::vector<uint32_t>& heavy = s.heavy;
+    const uint64_t heavy_budget = s.form.heavy_budget;
+    const uint32_t nh = (uint32_t)(heavy.size() / 3);
+    std::vector<unsigned long long> off;
+    for (uint32_t j = 0; j < nh;) {
+        const uint32_t j0 = j;
+        unsigned long long acc = 0;
+        off.clear();
+        while (j < nh && j - j0 < 65536u) {
+            const unsigned long long e = heavy[3 * (size_t)j + 2];
+            if (e == 0xFFFFFFFFull || e > heavy_budget) { gm_set_error("a read x strand with more SA hits than one heavy-path chunk holds; use -h"); return GM_E_BATCH_TOO_LARGE; }
+            if (acc + e > heavy_budget) break;
+            off.push_back(acc); acc += e; ++j;
+        }
+        const uint32_t nj = j - j0;
+        unsigned item_bits = 1; while ((1u << item_bits) < nj) ++item_bits;
+        const size_t tmp_bytes = gmk_heavy_sort_temp_bytes((size_t)acc);
+        if (b->heavy_k0.ensure((size_t)acc * 8 + 64) || b->heavy_k1.ensure((size_t)acc * 8 + 64) || b->heavy_tmp.ensure(tmp_bytes + 64) ||
+            b->heavy_off.ensure((size_t)nj * 8 + 64)) return GM_E_NOMEM;
+        HIPCHK(hipMemcpyAsync(b->heavy_off.p, off.data(), (size_t)nj * 8, hipMemcpyHostToDevice, st));
+        KCHK(gmk_heavy_chunk(ix->dev, s.dp, b->dev, s.form.use_full, b->heavy_list.as<uint32_t>(), j0, nj, b->heavy_off.as<unsigned long long>(),
+                             b->heavy_k0.as<unsigned long long>(), b->heavy_k1.as<unsigned long long>(), acc, b->heavy_tmp.p, tmp_bytes, item_bits, st));
+        HIPCHK(hipStreamSynchronize(st));        // off[] and the key buffers are reused by the next chunk
+        GM_TRACE("heavy chunk: items %u..%u of %u, %llu keys sorted", j0, j, nh, acc);
+    }
+    return map_read_status(b, s, st);
+}
+
+// a candidate shard overflowed: grow the list for the next attempt, or give up after the ninth
+static int map_grow_cands(gm_batch* b, const MapState& s, int attempt) {
+    if (attempt > 8) { gm_set_error("candidate list keeps overflowing"); return GM_E_NOMEM; }
+    const size_t want = ((size_t)s.mx + s.mx / 4 + 64) * GM_NSHARD;
+    if (want > 0x7FFFFFFFu) { gm_set_error("more than 2^31 candidates in one batch; map the block in smaller pieces (or use -h)"); return GM_E_BATCH_TOO_LARGE; }
+    b->cand_cap = (uint32_t)want;
+    return b->cands.ensure((size_t)b->cand_cap * sizeof(GmCand)) ? GM_E_NOMEM : GM_OK;      // (map_vote_attempt fills b->dev)
+}
+
+static int map_nw_compact(gm_index* ix, gm_batch* b, const MapState& s, hipStream_t st) {
     if (b->raw_cap < b->n_cands + 16ull) b->raw_cap = b->n_cands + 16ull;
     if (b->raw_hits.ensure(b->raw_cap * sizeof(GmRawHit))) return GM_E_NOMEM;
-    fill_dev_batch(b);
-    // one read length in the block and no quality character above 127 (k_prep counted them): the DP kernel with the rows in DP order
-    const uint32_t nw_rows_len = (b->len_min == b->len_max && (b->fasta || ctr[GMK_HIGH_QUAL] == 0)) ? b->len_max : 0u;      // (a FASTA block has no quality characters)
-    b->path += std::string(" nw=") + gmk_nw_form(dp, b->dev, b->n_cands, nw_rows_len, gm_qual_lo(ctr), gm_qual_hi(ctr));
-    { KTimer t(b, GM_K_NW, st); KCHK(gmk_nw(ix->dev, dp, b->dev, b->n_cands, nw_rows_len, gm_qual_lo(ctr), gm_qual_hi(ctr), any_superseded, st)); }
+    map_fill_dev(b, s);
+    const uint32_t rows_len = map_nw_rows_len(b, s.ctr), lo = gm_qual_lo(s.ctr), hi = gm_qual_hi(s.ctr);
+    b->path += std::string(" nw=") + gmk_nw_form(s.dp, b->dev, b->n_cands, rows_len, lo, hi);
+    { KTimer t(b, GM_K_NW, st); KCHK(gmk_nw(ix->dev, s.dp, b->dev, b->n_cands, rows_len, lo, hi, s.any_superseded, st)); }
     { KTimer t(b, GM_K_COMPACT, st); KCHK(gmk_compact(b->dev, st)); }
     if (gm_trace_on()) { HIPCHK(hipStreamSynchronize(st)); GM_TRACE("NW + compaction done"); }
     b->mapped = true;
     return GM_OK;
+}
+
+// The form is this call's.  Outside gm_map_batch_device b->dev carries none: fill_dev_batch leaves pack, fixed_cands and fixed_cnt null
+// and fixed_epoch 0, which is what every other caller of it gets (the two uploads, out_enqueue_traceback, the gm_dev_* probes) and what
+// map_pipelined cuts its views from; none of their kernels reads those fields (k_prep, the vote kernels and k_cand_gather alone do).
+// Inside, map_fill_dev puts the form on top and MapFormScope takes it off.
+extern "C" int gm_map_batch_device(gm_index* ix, const gm_params* p, gm_batch* b, void* stream) {
+    if (!ix || !p || !b || !p->finalized || b->ix != ix) return GM_E_ARG;
+    HIPCHK(hipSetDevice(ix->device));
+    hipStream_t st = S_(stream);
+    MapState s;
+    int rc = sync_params(ix, p, s.dp, st, true);
+    if (rc) return rc;
+    b->mapped = false;
+    b->pair_flagged = 0;
+    if ((rc = fasta_forced_form(b)) != GM_OK) return rc;
+    if (b->n == 0) return map_empty_block(b);
+    if ((rc = map_check_binding(p, b)) != GM_OK) return rc;
+    const MapForm& f = s.form = map_choose_form(ix, p, b, s.dp);
+    b->counters_on_host = false;
+    if (f.pipeline) {
+        b->path.clear();                             // the single-pass dispatch records its choice; a block the sub-batches map to the end has none (not the last call's)
+        if ((rc = map_pipelined(ix, s.dp, b, f, st)) <= 0) return rc;      // done, or a real error; 1: a shard overflowed, the single pass can grow the list
+    }
+    MapFormScope scope{ b };
+    if ((rc = map_form_buffers(b, f, st)) != GM_OK) return rc;
+    s.dp.heavy_min = f.heavy_min; s.dp.fused = f.fused;
+    if (!f.use_bucket) s.dp.bucket = nullptr;
+    const std::string name = map_form_name(f, b, s.dp);
+    b->path = std::string("reads=") + (b->fasta ? "fasta " : "fastq ") + name;
+    GM_TRACE("path: %s", name.c_str());
+    if ((rc = map_prep_seed(ix, b, s, st)) != GM_OK) return rc;
+    if (!f.fused && (rc = map_heavy_after_seed(b, s, st)) != GM_OK) return rc;
+    for (int attempt = 0;; ++attempt) {
+        if ((rc = map_vote_attempt(ix, b, s, st)) != GM_OK) return rc;
+        if (s.dp.dbg & 64) map_print_vote_phases(s);
+        if ((rc = map_check_quals(b, s.ctr)) != GM_OK) return rc;
+        const uint32_t n_retry = s.hs_small[1], region = b->dev.cand_region;
+        s.any_superseded = n_retry != 0 || !s.heavy.empty();
+        if (n_retry && s.mx <= region && (rc = map_retry(ix, b, s, n_retry, st)) != GM_OK) return rc;
+        if (!s.heavy.empty() && s.mx <= region && (rc = map_heavy_chunks(ix, b, s, st)) != GM_OK) return rc;
+        if (s.mx <= region) {
+            b->n_cands = (uint32_t)s.total;
+            GM_TRACE("vote done: %llu candidates (attempt %d)", (unsigned long long)s.total, attempt);
+            break;
+        }
+        if ((rc = map_grow_cands(b, s, attempt)) != GM_OK) return rc;      // a candidate shard overflowed: vote again
+    }
+    return map_nw_compact(ix, b, s, st);
 }
 
 extern "C" int gm_batch_counters(gm_batch* b, gm_counters* o) {

@@ -9,6 +9,7 @@ life exists for."""
 import os
 
 import numpy as np
+import pytest
 
 import fasta_model as fm
 import gnumap_amd as g
@@ -22,9 +23,12 @@ PIPE = 4096                              # GM_PIPELINE's smallest sub-batch; the
 
 
 class Block:
-    def __init__(self, name, reads, kw=None, opts=None, fasta=False, adaptor=None, stride=None):
-        """reads: (name, sequence, quality line) triples; kw: gm_params keywords; opts: {switch: value} for this block's calls only"""
+    def __init__(self, name, reads, kw=None, opts=None, fasta=False, adaptor=None, stride=None, fails=None, upload_kw=None):
+        """reads: (name, sequence, quality line) triples; kw: gm_params keywords; opts: {switch: value} for this block's calls only.
+        fails: (error code, a part of its text) - the block is uploaded (under upload_kw where the upload's gm_params differ from the map
+        call's) and gm_map_batch_device has to return that error; the handle then goes on to the next block"""
         self.name, self.reads, self.kw, self.opts, self.fasta, self.adaptor = name, list(reads), dict(kw or {}), dict(opts or {}), fasta, adaptor
+        self.fails, self.up = fails, g.Params(**(kw if upload_kw is None else upload_kw) or {})
         self.n = len(self.reads)
         self.names = [r[0] if isinstance(r[0], bytes) else str(r[0]).encode() for r in self.reads]
         self.seqs = [r[1] for r in self.reads]
@@ -62,10 +66,24 @@ def run_block(batch, blk, life_opts=None):
     """the block through this handle: gm_map_batch (upload + gm_map_batch_device + grouping), then what the handle says about the call"""
     with Switches(life_opts or {}, blk.opts):
         batch.set_adaptor(blk.adaptor)
+        if blk.fails:
+            return failed_call(batch, blk)
         res = batch.map(blk.p, blk.B, blk.Q, blk.Ln, fasta=blk.fasta)
         raw, status, self_score, top = batch.raw_hits()
         return dict(res=res, raw=np.sort(raw, order=["read", "pos", "strand"]), status=status, self_score=self_score, top=top, path=batch.path(),
                     flagged=batch.pair_flagged(), ctr=batch.counters(), n=blk.n, name=blk.name)
+
+
+def failed_call(batch, blk):
+    """a map call that returns an error is part of the life too: the upload goes through, gm_map_batch_device raises blk.fails - before
+    its first launch (the `illumina` binding) or behind the vote kernels (a quality character below the offset) - and whatever it had
+    set up by then is the next block's inheritance"""
+    code, text = blk.fails
+    batch.upload(blk.up, blk.B, blk.Q, blk.Ln, fasta=blk.fasta)
+    with pytest.raises(g.GnumapError) as e:
+        batch.map_device(blk.p)
+    assert e.value.code == code and text in str(e.value), (blk.name, str(e.value))
+    return dict(failed=str(e.value), path="(" + text + ")", flagged=0, ctr={}, n=blk.n, name=blk.name)
 
 
 def fresh_block(ix, blk, life_opts=None):
@@ -87,6 +105,9 @@ def same_run(a, b, what):
     zeroes the work counters per call (the hipMemsetAsync of `counters` in front of k_prep, those of the fused seed search and of
     GMK_OVERFLOW_RS per attempt), the sub-batch pipeline sums its own per call, and an empty block reports zeros"""
     assert a["n"] == b["n"], what
+    if "failed" in a or "failed" in b:                   # a refused call: refused in the same words on the fresh handle, and nothing else to compare
+        assert a.get("failed") == b.get("failed"), (what, a.get("failed"), b.get("failed"))
+        return
     assert len(a["raw"]) == len(b["raw"]), (what, len(a["raw"]), len(b["raw"]))
     for f in ("read", "pos", "strand", "step"):
         assert np.array_equal(a["raw"][f], b["raw"][f]), (what, "raw", f)
@@ -209,7 +230,15 @@ def syn_groups(ix, syn_reads, pipeline):
     b["gather_small"] = Block("gather_small", small, opts=dict(GM_PAIR_HANDOFF="gather"))
     b["nopair_small"] = Block("nopair_small", small, opts=dict(GM_VOTE_PAIR="0"))
     b["slots"] = Block("slots", one, opts=dict(GM_VOTE="block"))                                  # a count-array own-slots form beside the bucket table
-    groups = [[b["one_len"]], [b["mixed"]], [b["small"]], [b["grown"]], [b["empty"]], [b["wide_qual"], b["narrow"]], [b["ill_on"], b["ill_off"]],
+    # calls that fail: behind the vote kernels (one quality character below the offset: "Invalid Fastq Character") and in front of every
+    # launch (`illumina` other than the upload's).  Behind a bucket-table block and in front of a GM_VOTE=wave block of more reads: what the
+    # failed or the earlier call chose - 2-bit read forms, own candidate slots, sized for 60 or 40 reads - is not the wave block's
+    spoil = lambda reads, at: [(nm, s, q[:7] + b" " + q[8:]) if i == at else (nm, s, q) for i, (nm, s, q) in enumerate(reads)]
+    b["bad_qual"] = Block("bad_qual", spoil(one[:40], 17), fails=(-8, "Invalid Fastq Character"))
+    b["illumina_refused"] = Block("illumina_refused", one[:40], dict(illumina=1), upload_kw={}, fails=(-1, "illumina"))
+    b["wave_vote"] = Block("wave_vote", one, opts=dict(GM_VOTE="wave"))
+    groups = [[b["small"], b["bad_qual"], b["wave_vote"]], [b["small"], b["illumina_refused"], b["wave_vote"]]]
+    groups += [[b["one_len"]], [b["mixed"]], [b["small"]], [b["grown"]], [b["empty"]], [b["wide_qual"], b["narrow"]], [b["ill_on"], b["ill_off"]],
               [b["M5"]], [b["bs"]], [b["m8_j5"]], [b["no_nw"], b["fasta"], b["u"]], [b["adaptor"], b["adaptor_off"]], [b["lane"]], [b["wave"]],
               [b["gather"]], [b["fixed0"]], [b["nopair"]], [b["gather_small"]], [b["nopair_small"]], [b["slots"]]]
     if pipeline:
@@ -220,6 +249,9 @@ def syn_groups(ix, syn_reads, pipeline):
         b["pipeline_tiled"] = Block("pipeline_tiled", (one * reps)[:3 * PIPE + 100], opts=dict(GM_PIPELINE=str(PIPE)))
         b["pipeline"] = Block("pipeline", _reads_from_reference(ix, 3 * PIPE + 100, 100, ord("#"), ord("F"), seed=11), opts=dict(GM_PIPELINE=str(PIPE)))
         groups.append([b["small"], b["pipeline"], b["small"], b["pipeline_tiled"], b["small"]])       # a bucket-table block on either side in every order
+        # the bad quality character met by the sub-batches (map_pipelined's own check, in the first of them)
+        b["pipeline_bad_qual"] = Block("pipeline_bad_qual", spoil(b["pipeline"].reads, 5), opts=dict(GM_PIPELINE=str(PIPE)), fails=(-8, "Invalid Fastq Character"))
+        groups.append([b["small"], b["pipeline_bad_qual"], b["wave_vote"]])
     return b, groups
 
 

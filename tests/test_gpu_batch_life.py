@@ -120,6 +120,14 @@ def test_life_on_the_full_sa_index(order, world):
     t = next(k for k, b in enumerate(seq) if b.name == "pipeline_tiled")                        # the pipeline gave up, the single pass mapped the block
     assert "seeds=k_seed" in paths[t] and "cands=" in paths[t], (what, paths[t])
     assert "seeds=bucket-table" in paths[t - 1] and "seeds=bucket-table" in paths[t + 1], (what, paths[t - 1:t + 2])
+    # the calls that failed (same_run held the block behind each to its fresh handle): a bucket-table block on one side, the GM_VOTE=wave
+    # block on the other
+    for name in ("bad_qual", "illumina_refused", "pipeline_bad_qual"):
+        k = next(k for k, b in enumerate(seq) if b.name == name)
+        assert "failed" in calls[k], (what, name)
+        around = {seq[k - 1].name: paths[k - 1], seq[k + 1].name: paths[k + 1]}
+        assert set(around) == {"small", "wave_vote"}, (what, name, list(around))
+        assert "seeds=bucket-table" in around["small"] and "seeds=k_seed vote=sparse" in around["wave_vote"], (what, name, around)
 
 
 @pytest.mark.parametrize("order", ORDERS)
@@ -127,8 +135,9 @@ def test_life_on_the_sampled_sa_index(order, world):
     seq, calls = live("sampled", world["sampled"], order)
     assert_common_transitions(seq, calls, ("sampled", order))
     paths = [c["path"] for c in calls]
-    assert all("seeds=k_seed" in p and "locate=sampled-SA" in p for p, b in zip(paths, seq) if b.n), paths
-    assert all(c["ctr"]["lf_steps"] > 0 for c, b in zip(calls, seq) if b.n)
+    assert all("seeds=k_seed" in p and "locate=sampled-SA" in p for p, b in zip(paths, seq) if b.n and not b.fails), paths
+    assert all(c["ctr"]["lf_steps"] > 0 for c, b in zip(calls, seq) if b.n and not b.fails)
+    assert sum("failed" in c for c in calls) == 2                       # bad_qual and illumina_refused: the blocks behind them are their fresh handles' (same_run)
 
 
 @pytest.mark.parametrize("order", ORDERS)
