@@ -12,6 +12,8 @@ GM_READ_OK, GM_READ_TOO_MANY, GM_READ_NONE, GM_READ_TOO_SHORT, GM_READ_TOO_POOR 
 GM_E_CAPACITY = -5
 GM_E_BATCH_TOO_LARGE = -9
 GM_ROWS_TEXT, GM_ROWS_BAM = 0, 1
+GM_ROW_TAG_MD = 1                       # gm_batch_set_row_tags: NM:i and MD:Z
+GM_CIGAR_GNUMAP, GM_CIGAR_FORWARD = 0, 1
 GM_BGZF_LZ77 = 0x100                    # ORed into a BGZF level of 1: LZ77 matches under the Huffman code
 
 u8p = C.POINTER(C.c_uint8)
@@ -104,7 +106,7 @@ class gm_counters(C.Structure):
     _fields_ = [(n, u64) for n in ("reads", "kmers_searched", "occ_calls", "occ_blocks", "seeds_used", "sa_hits", "lf_steps", "candidates",
                                    "nw_cells", "accepted", "vote_retries", "table_lookups")]
 
-GM_K_COUNT = 7
+GM_K_COUNT = 8
 
 
 RAW_HIT_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u4"), ("score", "<f4"), ("step", "<u2"), ("strand", "u1"), ("pad", "u1")])
@@ -129,6 +131,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_coverage_write_gmp_calls_device", "gm_coverage_calls_text", "gm_coverage_write_vcf",
            "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim",
            "gm_batch_set_read_format", "gm_index_set_probe_format", "gm_batch_set_unmapped_rows", "gm_batch_unmapped_rows",
+           "gm_batch_set_row_tags", "gm_batch_set_cigar_order",
            "gm_batch_upload_text", "gm_map_batch_text", "gm_output_batch_text_resident", "gm_dev_fastq_rows", "gm_dev_fastq_tile_bytes",
            "gm_sam_sorter_create", "gm_sam_sorter_destroy", "gm_output_batch_sorted", "gm_output_batch_sorted_resident", "gm_sam_sorter_finish",
            "gm_sam_sorter_read", "gm_sam_sorter_stats", "gm_sam_sorter_add_rows",
@@ -249,6 +252,8 @@ def load_library():
     L.gm_sam_sorter_bai.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64), C.c_void_p]
     L.gm_batch_set_unmapped_rows.argtypes = [C.c_void_p, C.c_int]
     L.gm_batch_unmapped_rows.argtypes = [C.c_void_p, C.POINTER(u64)]
+    L.gm_batch_set_row_tags.argtypes = [C.c_void_p, C.c_uint32]
+    L.gm_batch_set_cigar_order.argtypes = [C.c_void_p, C.c_int]
     _LIB = L
     return L
 
@@ -617,6 +622,19 @@ class Batch:
         n = u64()
         _chk(lib().gm_batch_unmapped_rows(self.h, C.byref(n)))
         return int(n.value)
+
+    def set_row_tags(self, md=True):
+        """gm_batch_set_row_tags: from the next call on, every row of the row-producing output calls that prints a record whose CIGAR is
+        not "*" carries NM:i and MD:Z behind X0 - of the row as printed, so they agree with the CIGAR order that is set.  GnumapError
+        GM_E_UNSUPPORTED with an adaptor set, GM_E_IO when the index has no readable <fa>.gnumap.amb"""
+        _chk(lib().gm_batch_set_row_tags(self.h, GM_ROW_TAG_MD if md else 0))
+
+    def set_cigar_order(self, order="gnumap"):
+        """gm_batch_set_cigar_order: "gnumap" - a minus-strand row prints its CIGAR tokens last to first, as the reference does (the
+        default); "forward" - in the order the traceback computed them against the forward window, as a plus-strand row does"""
+        if order not in ("gnumap", "forward"):
+            raise ValueError('set_cigar_order: "gnumap" or "forward"')
+        _chk(lib().gm_batch_set_cigar_order(self.h, GM_CIGAR_FORWARD if order == "forward" else GM_CIGAR_GNUMAP))
 
     def trimmed_len(self):
         """the lengths the kernels used for the block uploaded last (what the adaptor trim kept; the uploaded lengths without one)"""

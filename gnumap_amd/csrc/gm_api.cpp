@@ -60,6 +60,7 @@ struct gm_batch {
         t_names, t_nameoff, t_qtail, t_qtailoff, t_slots, t_rowlen, t_rowoff, t_text, t_bad,     // gm_output_batch_text: the block's names, tails and row offsets, the text
         t_bammeta,                      // gm_output_batch_bam: operations and bin of every record (k_bam_sizes)
         t_status, t_rowcnt, t_rowflag, t_rowfirst, t_rowucum, t_rowsrc,        // gm_batch_set_unmapped_rows: the reads' status bytes and the row source (gmk_row_source)
+        t_md,                           // gm_batch_set_row_tags: {NM, MD bytes} of every row (k_md_sizes)
         full_len, d_adaptor,            // -A: the lengths as uploaded (`len` then holds what k_adaptor_trim keeps), the adaptor's characters
         rt_text, rt_tilecnt, rt_tileoff, rt_lineat, rt_lsum, rt_lin, rt_recs, rt_nlen, rt_tlen, rt_meta;      // gm_batch_upload_text: the FASTQ text and what k_rt_* make of it
     GmBgzfBufs bz;                      // gm_output_batch_bam: the BGZF blocks of the block's records
@@ -73,6 +74,8 @@ struct gm_batch {
     int read_format = GM_READS_FASTQ;   // gm_batch_set_read_format: the blocks uploaded from now on
     bool unmapped_rows = false;         // gm_batch_set_unmapped_rows: a read without a record gets a flag-4 row from the row-producing output calls
     uint64_t n_unmapped = 0;            // ... and how many the last output call wrote (gm_batch_unmapped_rows)
+    uint32_t row_tags = 0;              // gm_batch_set_row_tags: GM_ROW_TAG_MD = the rows of the row-producing output calls carry NM:i and MD:Z
+    int cigar_order = GM_CIGAR_GNUMAP;  // gm_batch_set_cigar_order: GM_CIGAR_FORWARD = a minus-strand row prints its CIGAR in reference order
     bool fasta = false;                 // the block that is resident was uploaded as FASTA (GmDevBatch::fasta)
     bool adaptor_dirty = false;         // d_adaptor does not hold `adaptor` yet
     PinBuf h_top, h_hbegin, h_ord, h_post, h_mapq, h_emit, h_mhit, h_stat;      // h_stat: the small status words a phase reads back (page-locked: one short DMA)
@@ -457,6 +460,7 @@ extern "C" void gm_index_close(gm_index* ix) {
         (void)hipSetDevice(ix->device);
         ix->d_bwt.release(); ix->d_sa.release(); ix->d_full.release(); ix->d_pac.release(); ix->d_contig.release();
         ix->d_cov.release(); ix->d_ptab.release(); ix->d_planes.release(); ix->d_nuc.release(); ix->d_cnames.release(); ix->d_cname_off.release();
+        ix->d_holes.release();
         for (auto& kv : ix->ptabs) kv.second.release();
         for (auto& kv : ix->kmer_tabs) kv.second.release();
         for (auto& kv : ix->kmer_ctabs) kv.second.release();
@@ -496,6 +500,16 @@ int index_cnames(gm_index* ix) {
     HIPCHK(hipMemcpy(ix->d_cnames.p, all.data(), all.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ix->d_cname_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
     ix->cnames_on = true;
+    return GM_OK;
+}
+
+// the holes of <fa>.gnumap.amb in HBM, once per index: what the walk of gm_batch_set_row_tags looks a row's first column up in
+int index_holes(gm_index* ix) {
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->holes_on) return GM_OK;
+    if (ix->d_holes.ensure(ix->h.holes.size() * 4 + 16)) return GM_E_NOMEM;
+    if (!ix->h.holes.empty()) HIPCHK(hipMemcpy(ix->d_holes.p, ix->h.holes.data(), ix->h.holes.size() * 4, hipMemcpyHostToDevice));
+    ix->holes_on = true;
     return GM_OK;
 }
 
@@ -794,11 +808,19 @@ extern "C" int gm_batch_upload_text(gm_batch* b, const gm_params* p, const char*
     return GM_OK;
 }
 
+// gm_batch_set_row_tags with gm_batch_set_adaptor: with -A a row's SEQ is the whole read and its CIGAR covers the kept part, so a tag
+// of the row as printed would describe nothing.  Whichever setter comes second refuses, so no output call meets the two together
+static std::string row_tags_adaptor_text(const char* who) {
+    return std::string(who) + ": GM_ROW_TAG_MD (gm_batch_set_row_tags) and an adaptor (gm_batch_set_adaptor) on one batch: with an adaptor SEQ is the whole read and the "
+           "CIGAR covers the kept part, so NM / MD of the row as printed would describe nothing";
+}
+
 // -A / --adaptor (Driver.cpp:2793-2798: the string exactly as given).  Takes effect with the next upload; NULL or "" clears it.
 extern "C" int gm_batch_set_adaptor(gm_batch* b, const char* adaptor) {
     if (!b) { gm_set_error("gm_batch_set_adaptor: batch is NULL"); return GM_E_ARG; }
     const size_t n = adaptor ? strlen(adaptor) : 0;
     if (n > GM_ADAPTOR_MAX) { gm_set_error("gm_batch_set_adaptor: an adaptor of at most 256 characters"); return GM_E_ARG; }
+    if (n && b->row_tags) { gm_set_error(row_tags_adaptor_text("gm_batch_set_adaptor")); return GM_E_UNSUPPORTED; }
     b->adaptor.assign(adaptor ? adaptor : "", n);
     b->adaptor_dirty = n != 0;
     return GM_OK;
@@ -823,6 +845,29 @@ extern "C" int gm_batch_set_unmapped_rows(gm_batch* b, int on) {
 extern "C" int gm_batch_unmapped_rows(gm_batch* b, uint64_t* n) {
     if (!b || !n) { gm_set_error("gm_batch_unmapped_rows: batch or n is NULL"); return GM_E_ARG; }
     *n = b->n_unmapped;
+    return GM_OK;
+}
+
+// Two more defined extensions, read by the six row-producing output calls from the next call on; gm_output_batch
+// (records) reads neither.  Row tags: NM:i and MD:Z of the row as printed, behind X0, on every row whose CIGAR field is not "*".
+extern "C" int gm_batch_set_row_tags(gm_batch* b, uint32_t tags) {
+    if (!b) { gm_set_error("gm_batch_set_row_tags: batch is NULL"); return GM_E_ARG; }
+    if (tags & ~(uint32_t)GM_ROW_TAG_MD) { gm_set_error("gm_batch_set_row_tags: GM_ROW_TAG_MD or 0, not " + std::to_string(tags)); return GM_E_ARG; }
+    if (tags && !b->adaptor.empty()) { gm_set_error(row_tags_adaptor_text("gm_batch_set_row_tags")); return GM_E_UNSUPPORTED; }
+    if (tags && !b->ix->h.amb_found) {
+        gm_set_error("gm_batch_set_row_tags: cannot read or parse " + b->ix->h.amb_path + ": MD:Z prints the reference's own letter where the FASTA holds another than ACGT");
+        return GM_E_IO;
+    }
+    b->row_tags = tags;
+    return GM_OK;
+}
+
+// Minus-strand rows: GM_CIGAR_GNUMAP prints the tokens last to first, as the reference does; GM_CIGAR_FORWARD prints the pool's bytes as
+// a plus-strand row does - the order the traceback computed them in, against the forward window
+extern "C" int gm_batch_set_cigar_order(gm_batch* b, int order) {
+    if (!b) { gm_set_error("gm_batch_set_cigar_order: batch is NULL"); return GM_E_ARG; }
+    if (order != GM_CIGAR_GNUMAP && order != GM_CIGAR_FORWARD) { gm_set_error("gm_batch_set_cigar_order: GM_CIGAR_GNUMAP or GM_CIGAR_FORWARD, not " + std::to_string(order)); return GM_E_ARG; }
+    b->cigar_order = order;
     return GM_OK;
 }
 
@@ -1467,7 +1512,7 @@ extern "C" int gm_batch_pair_flagged(gm_batch* b, uint32_t* flagged) {
 }
 
 extern "C" const char* gm_kernel_name(int which) {
-    static const char* names[GM_K_COUNT] = { "k_prep", "k_seed", "k_locate_sampled", "k_vote", "k_vote_retry", "k_nw", "k_compact(scan+scatter)" };
+    static const char* names[GM_K_COUNT] = { "k_prep", "k_seed", "k_locate_sampled", "k_vote", "k_vote_retry", "k_nw", "k_compact(scan+scatter)", "k_md_sizes" };
     return which >= 0 && which < GM_K_COUNT ? names[which] : "?";
 }
 
@@ -2129,6 +2174,16 @@ static int out_row_inputs(gm_index* ix, const gm_params* p, gm_batch* b, const O
     t.inv_adjust = 1.0 / p->adjust; t.bad = b->t_bad.as<unsigned long long>();
     t.seq_len = b->adaptor.empty() ? b->dev.len : b->full_len.as<uint16_t>();
     t.fa_qual = fasta_qual_word();
+    t.cigar_forward = b->cigar_order == GM_CIGAR_FORWARD ? 1u : 0u;
+    t.md = nullptr; t.pac = nullptr; t.contig_off = nullptr; t.l_pac = t.n_seqs = 0; t.holes = nullptr; t.n_holes = 0;
+    if (b->row_tags & GM_ROW_TAG_MD) {
+        // {NM, MD bytes} per row, the reference and its holes: allocated, uploaded and read only with the setting on
+        if (const int rc = index_holes(ix)) return rc;
+        if (b->t_md.ensure((size_t)n_recs * 8 + 16)) return GM_E_NOMEM;
+        t.md = b->t_md.as<uint32_t>();
+        t.pac = ix->dev.pac; t.contig_off = ix->dev.contig_off; t.l_pac = ix->dev.l_pac; t.n_seqs = ix->dev.n_seqs;
+        t.holes = ix->d_holes.as<uint32_t>(); t.n_holes = (uint32_t)(ix->h.holes.size() / 3);
+    }
     return GM_OK;
 }
 
@@ -2141,6 +2196,7 @@ static int out_count_rows(gm_batch* b, const OutCall& c, OutState& s, hipStream_
     if (bam_timed) { for (auto& e : b->bam_ev) if (!e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(b->bam_ev[0], st)); }
     if (bam) KCHK(gmk_bam_sizes(s.t, b->t_bammeta.as<uint32_t>(), st));
     if (bam_timed) HIPCHK(hipEventRecord(b->bam_ev[1], st));
+    if (s.t.md) { KTimer kt(b, GM_K_MD_SIZES, st); KCHK(gmk_md_sizes(b->dev, s.t, bam ? 1 : 0, st)); }      // gm_batch_set_row_tags: the two tags' bytes onto row_len
     KCHK(gmk_scan_u32(s.t.row_len, s.n_rows, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
     s.bad_row = ~0ull;
     HIPCHK(hipMemcpyAsync(&s.text_len, b->t_rowoff.as<uint64_t>() + s.n_rows, 8, hipMemcpyDeviceToHost, st));

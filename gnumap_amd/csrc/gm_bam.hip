@@ -25,6 +25,7 @@
 // order in which they land, and a barrier lies between the maxima and the lookups that read them.
 #include "gm_lib.h"
 #include "gm_fmt_dev.h"
+#include "gm_mdtag_dev.h"
 #include <algorithm>
 #include <memory>
 
@@ -491,14 +492,7 @@ __global__ void __launch_bounds__(256) k_bgzf_compact(const uint8_t* __restrict_
 // BAM records
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool bm_op(char c) { return c == 'M' || c == 'I' || c == 'D'; } // all k_out_write ever puts into the pool
-// "=ACMGRSVTWYHKDBN", either case; anything else is N
-__device__ __forceinline__ uint32_t bm_nibble(char c) {
-    switch (c & ~0x20) {
-        case 'A': return 1; case 'C': return 2; case 'M': return 3; case 'G': return 4; case 'R': return 5; case 'S': return 6; case 'V': return 7;
-        case 'T': return 8; case 'W': return 9; case 'Y': return 10; case 'H': return 11; case 'K': return 12; case 'D': return 13; case 'B': return 14;
-        default: return c == '=' ? 0u : 15u;
-    }
-}
+__device__ __forceinline__ uint32_t bm_nibble(char c) { return gm_bam_nibble(c); }      // "=ACMGRSVTWYHKDBN": gm_fmt_dev.h, shared with the NM / MD walk
 #define BM_UNMAPPED_BIN 4680u                     // reg2bin(-1, 0): the bin of a record without a position (SAMv1 section 4.2)
 __device__ __forceinline__ uint32_t bm_name_len(const GmDevText& t, uint32_t rd) {
     const unsigned long long nl = t.name_off[rd + 1] - t.name_off[rd];
@@ -537,7 +531,9 @@ __global__ void __launch_bounds__(256) k_bam_sizes(GmDevText t, uint32_t* __rest
 
 __device__ __forceinline__ void bm_put32(uint8_t* w, uint32_t v) { w[0] = (uint8_t)v; w[1] = (uint8_t)(v >> 8); w[2] = (uint8_t)(v >> 16); w[3] = (uint8_t)(v >> 24); }
 
-// one wavefront per record, four records per workgroup and step
+// one wavefront per record, four records per workgroup and step.  TAGS: gm_batch_set_row_tags is on (t.md is there) - an instance of
+// its own, so that the walk's registers cost the records without tags no occupancy
+template <bool TAGS>
 __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, const uint32_t* __restrict__ meta) {
     __shared__ uint8_t s_head[4][64];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -611,7 +607,7 @@ __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, con
                         uint32_t v = 0, mul = 1;
                         for (uint32_t ts = i, d = 0; ts > 0 && d < 9u && cg[ts - 1u] >= '0' && cg[ts - 1u] <= '9'; --ts, ++d) { v += (uint32_t)(cg[ts - 1u] - '0') * mul; mul *= 10u; }
                         const uint32_t word = (v << 4) | (c == 'M' ? 0u : c == 'I' ? 1u : 2u);
-                        const uint32_t j = neg ? n_ops - 1u - kk : kk;
+                        const uint32_t j = neg && !t.cigar_forward ? n_ops - 1u - kk : kk;      // GM_CIGAR_FORWARD: operation kk goes to slot kk
                         if (kk < n_ops)
                             for (uint32_t q = 0; q < 4u; ++q) if (o + 4ull * j + q < end) out[o + 4ull * j + q] = (uint8_t)(word >> (8u * q));
                     }
@@ -637,6 +633,19 @@ __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, con
             }
             o += L;
             if (lane < (unm ? 7u : 21u) && o + lane < end) out[o + lane] = hd[36u + lane];
+            if constexpr (TAGS) if (const uint32_t md_len = is_rec ? t.md[2ull * k + 1ull] : 0u) {
+                // gm_batch_set_row_tags, behind X0: NM i <int32>, MD Z <the string of the walk> NUL
+                o += 21u;
+                if (lane < 10u) {
+                    const uint32_t nm = t.md[2ull * k];
+                    const uint8_t c[10] = { 'N', 'M', 'i', (uint8_t)nm, (uint8_t)(nm >> 8), (uint8_t)(nm >> 16), (uint8_t)(nm >> 24), 'M', 'D', 'Z' };
+                    if (o + lane < end) out[o + lane] = c[lane];
+                }
+                o += 10u;
+                uint32_t nm_w, len_w;
+                gm_md_walk<true>(t, r, bs, L, t.pool + r.cigar_off, gout, neg && !t.cigar_forward, lane, out, o, end, &nm_w, &len_w);
+                if (lane == 0 && o + md_len < end) out[o + md_len] = 0;
+            }
         }
         __syncthreads();
     }
@@ -658,7 +667,7 @@ int gmk_bam_sizes(const GmDevText& t, uint32_t* meta, void* stream) {
 int gmk_bam_rows(const GmDevBatch& b, const GmDevText& t, const uint32_t* meta, void* stream) {
     if (t.n_rows == 0) return 0;
     const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_rows + 3) / 4, 4096));
-    hipLaunchKernelGGL(k_bam_rows, dim3(grid), dim3(256), 0, S_(stream), b, t, meta);
+    hipLaunchKernelGGL(t.md ? k_bam_rows<true> : k_bam_rows<false>, dim3(grid), dim3(256), 0, S_(stream), b, t, meta);
     return (int)hipGetLastError();
 }
 

@@ -34,6 +34,16 @@ GM_FMT_HD static inline char gm_comp_char(char c) {
     }
 }
 
+// The BAM nibble of a base, "=ACMGRSVTWYHKDBN" in either case; anything else is N (15).  One function for the SEQ nibbles of a
+// record (k_bam_rows, gm_bam.hip) and for the comparison behind NM / MD (gm_md_walk, gm_mdtag_dev.h): the two cannot drift apart
+GM_FMT_HD static inline uint32_t gm_bam_nibble(char c) {
+    switch (c & ~0x20) {
+        case 'A': return 1; case 'C': return 2; case 'M': return 3; case 'G': return 4; case 'R': return 5; case 'S': return 6; case 'V': return 7;
+        case 'T': return 8; case 'W': return 9; case 'Y': return 10; case 'H': return 11; case 'K': return 12; case 'D': return 13; case 'B': return 14;
+        default: return c == '=' ? 0u : 15u;
+    }
+}
+
 struct gm_u256 { uint64_t w0, w1, w2, w3; };             // little endian; named words, never indexed (no scratch on the device)
 
 GM_FMT_HD static inline uint64_t gm_mulhi64(uint64_t a, uint64_t b) {

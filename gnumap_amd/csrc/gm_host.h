@@ -15,6 +15,11 @@ struct GmHostIndex {
     std::vector<uint64_t> sa;
     std::vector<uint8_t> pac;
     std::vector<GmContig> contigs;
+    // <fa>.gnumap.amb (bns_dump src/bntseq.c:85-96), read when the file is there: the stretches the FASTA holds other letters than ACGT
+    // in (the pac holds a drawn letter there).  {offset on the concatenated reference, length, upper-cased character}, ascending
+    std::vector<uint32_t> holes;
+    bool amb_found = false;
+    std::string amb_path;
 };
 
 bool gm_host_index_files_exist(const std::string& fa);

@@ -85,6 +85,29 @@ int gm_host_index_load(const std::string& fa, GmHostIndex& ix, std::string& err)
     ix.pac.assign(raw.begin(), raw.end());
     ix.pac.resize(ix.pac.size() + 64, 0);
     if (ix.l_pac != ix.seq_len) { err = "index holds both strands; GNUMAP indexes the forward strand only"; return GM_E_IO; }
+    // .amb, when present: mapping never reads it (the reference does not either); gm_batch_set_row_tags needs the holes' characters
+    ix.amb_path = fa + ".gnumap.amb";
+    ix.holes.clear(); ix.amb_found = false;
+    if ((f = fopen(ix.amb_path.c_str(), "r")) != nullptr) {
+        // a file that does not parse counts as not found: opening the index never depended on it.  The table holds 32-bit offsets:
+        // a reference of 2^32 bases or more keeps none (the device side refuses such a reference anyway, GM_E_UNSUPPORTED at gm_index_open)
+        long long lp; int ns; unsigned nh = 0;
+        bool ok = fscanf(f, "%lld%d%u", &lp, &ns, &nh) == 3 && ix.l_pac < (1ull << 32);
+        std::vector<std::pair<uint64_t, std::pair<uint32_t, char>>> hs;
+        for (unsigned i = 0; ok && i < nh; ++i) {
+            long long off; int len; char c[2];
+            ok = fscanf(f, "%lld%d%1s", &off, &len, c) == 3 && off >= 0 && len >= 0;
+            if (ok && len > 0 && (uint64_t)off < ix.l_pac) hs.push_back({ (uint64_t)off, { (uint32_t)std::min<uint64_t>((uint64_t)len, ix.l_pac - (uint64_t)off), c[0] } });
+        }
+        fclose(f);
+        std::sort(hs.begin(), hs.end());
+        for (size_t i = 0; ok && i < hs.size(); ++i) {
+            const char c = hs[i].second.second;
+            ix.holes.push_back((uint32_t)hs[i].first); ix.holes.push_back(hs[i].second.first);
+            ix.holes.push_back((uint32_t)(uint8_t)(c >= 'a' && c <= 'z' ? c - 32 : c));
+        }
+        ix.amb_found = ok;
+    }
     return GM_OK;
 }
 

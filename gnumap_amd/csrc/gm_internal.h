@@ -179,6 +179,15 @@ struct GmDevText {
     // and n_rows == n_recs.  gm_batch_set_unmapped_rows: row k is record row_src[k], or - GM_ROW_UNMAPPED set - read
     // row_src[k] & ~GM_ROW_UNMAPPED of the block, which has no record and gets a flag-4 row with YU:i:status[read] (gmk_row_source)
     unsigned long long n_rows; const unsigned long long* row_src; const int8_t* status; uint32_t n_reads;
+    // gm_batch_set_cigar_order: 1 = a minus-strand row prints its CIGAR in pool order, as a plus-strand row does (0: token by token reversed)
+    uint32_t cigar_forward;
+    // gm_batch_set_row_tags (null / 0 with the setting off: nothing below is read).  md: {NM, bytes of the MD string} per row, left by
+    // k_md_sizes; 0 bytes = the row gets no tags (no record, or CIGAR "*").  The walk (gm_mdtag_dev.h) reads the reference as pac
+    // letters, or inside a hole of <fa>.gnumap.amb that hole's character: holes = {offset, length, upper-cased character} per hole,
+    // ascending offsets, uploaded once per index
+    uint32_t* md;
+    const uint8_t* pac; const uint32_t* contig_off; uint32_t l_pac, n_seqs;
+    const uint32_t* holes; uint32_t n_holes;
 };
 #define GM_ROW_UNMAPPED (1ull << 63)
 #if defined(__HIPCC__)
@@ -369,6 +378,9 @@ int gmk_row_source(const GmDevSamRec* recs, uint64_t n_recs, uint32_t n, uint32_
                    unsigned long long* row_src, void* stream);
 int gmk_out_text_sizes(const GmDevBatch& b, const GmDevText& t, void* stream);
 int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream);
+// gm_batch_set_row_tags: behind gmk_out_text_sizes / gmk_bam_sizes and before the scan of row_len.  {NM, MD bytes} of every row into
+// t.md, and the bytes the two tags take (SAM text, or bam != 0 BAM) added to row_len
+int gmk_md_sizes(const GmDevBatch& b, const GmDevText& t, int bam, void* stream);
 int gmk_fmt_g6(const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len, void* stream);
 // gm_adaptor.hip: -A / --adaptor (SeqReader::FixReads2): out_len[r] = the length read r keeps; len = the lengths as uploaded, stride a multiple of 8
 int gmk_adaptor_cigar_room(const GmDevMatch* matches, uint32_t n_m, const uint16_t* full_len, uint32_t n, uint32_t* cig_all, void* stream);      // --no_nw with -A: room for "<whole length>M"

@@ -67,6 +67,8 @@ struct gm_index {
     DevBuf d_bwt, d_sa, d_full, d_pac, d_contig, d_cov, d_ptab, d_planes, d_nuc;
     DevBuf d_cnames, d_cname_off;           // contig names back to back + n_seqs + 1 offsets: what k_out_text_rows prints (uploaded by the first gm_output_batch_text)
     bool cnames_on = false;
+    DevBuf d_holes;                         // GmHostIndex::holes in HBM, for the walk of gm_batch_set_row_tags (uploaded by the first output call with the setting on)
+    bool holes_on = false;
     bool nuc_on = false;
     GmDevIndex dev{};
     uint64_t cov_bins = 0;
@@ -85,6 +87,7 @@ struct gm_index {
 unsigned host_threads();                                        // these three: gm_api.cpp.  GM_HOST_THREADS, else min(16, hardware threads); read once per process
 uint32_t host_pos2rid(const GmHostIndex& h, uint64_t pos);      // the contig that holds a concatenated position
 int index_cnames(gm_index* ix);                                 // contig names + offsets into HBM (d_cnames / d_cname_off), once per index
+int index_holes(gm_index* ix);                                  // the holes of <fa>.gnumap.amb into HBM (d_holes), once per index
 // gm_samsort.hip: what gm_output_batch_sorted (gm_api.cpp) does with a block besides gm_output_batch_text's work.  claim: the sequence number,
 // before anything of the block is computed (GM_E_ARG: used before, the sorter is finished or belongs to another index).  add: the rows
 // as k_out_text_rows left them in HBM - the records, n_rows + 1 offsets, the text - into the arena, on `stream` (GM_E_NOMEM, GM_E_UNSUPPORTED)

@@ -11,6 +11,8 @@
 //                    (NormalScoredSeq::score src/NormalScoredSeq.cpp:66-75, BSScoredSeq::score src/BSScoredSeq.cpp:24-88).
 //   k_row_*          gm_batch_set_unmapped_rows (a defined extension): the map from row to (record | read without a
 //                    record), so that k_out_text_* and k_bam_* (gm_bam.hip) write one flag-4 row for every read the reference drops
+//   k_md_sizes       gm_batch_set_row_tags (a defined extension as well): NM:i and MD:Z of every row as printed, sized here and written by
+//                    k_out_text_rows / k_bam_rows through the one walk of gm_mdtag_dev.h
 //
 // What stays on the host (gm_api.cpp) is only the order-dependent fp64 libm work on a flat array of scores:
 // denominator += exp(score) in processing order, posterior = exp(score) / denominator, MAPQ = round(-10 log10(1 - p)).
@@ -19,6 +21,7 @@
 #include <cstdlib>
 #include "gm_internal.h"
 #include "gm_fmt_dev.h"
+#include "gm_mdtag_dev.h"
 
 namespace {
 
@@ -721,7 +724,7 @@ __global__ void __launch_bounds__(256) k_out_text_sizes(GmDevBatch b, GmDevText 
         const char* cg = t.pool + r.cigar_off;
         uint32_t gl = 0, last_op = 0;
         for (char c; gl < 0xFFFFu && (c = cg[gl]) != 0; ++gl) if (!go_cigar_digit(c)) last_op = gl + 1;
-        const uint32_t gout = r.strand ? last_op : gl;
+        const uint32_t gout = r.strand && !t.cigar_forward ? last_op : gl;      // GM_CIGAR_FORWARD: all gl bytes, as a plus-strand row prints them
         s[56] = (char)(gl & 255u); s[57] = (char)(gl >> 8); s[58] = (char)(gout & 255u); s[59] = (char)(gout >> 8); s[60] = (char)tail;
         const uint32_t rd = r.read;
         unsigned long long nl = t.name_off[rd + 1] - t.name_off[rd];
@@ -740,7 +743,9 @@ __global__ void __launch_bounds__(256) k_out_text_sizes(GmDevBatch b, GmDevText 
     for (uint32_t q = threadIdx.x; q < chunks; q += 256u) dst[q] = src[q];
 }
 
-// one wavefront per row, four rows per workgroup and step; the grid is one resident round
+// one wavefront per row, four rows per workgroup and step; the grid is one resident round.  TAGS: gm_batch_set_row_tags is on (t.md
+// is there) - an instance of its own, so that the walk's registers cost the rows without tags no occupancy
+template <bool TAGS>
 __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t) {
     __shared__ char s_head[4][64];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -801,7 +806,8 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
             for (uint32_t i = lane; i < h2; i += 64u) if (o + i < end) out[o + i] = hd[4 + i];
             o += h2;
             const char* cg = t.pool + r.cigar_off;
-            if (!neg) { for (uint32_t i = lane; i < gl; i += 64u) if (o + i < end) out[o + i] = cg[i]; }
+            const bool rev = neg && !t.cigar_forward;            // (GM_CIGAR_FORWARD: gout == gl, the bytes in pool order on either strand)
+            if (!rev) { for (uint32_t i = lane; i < gl; i += 64u) if (o + i < end) out[o + i] = cg[i]; }
             else {
                 // reverse_cigar: the tokens (digits + operation) in reverse order; byte i of token [ts, te] goes behind the tokens that
                 // follow it: (gout - (te + 1)) + (i - ts).  Digits after the last operation belong to no token and are dropped.
@@ -835,9 +841,57 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
             if (!star) o += QL;
             if (lane == 0 && o < end) out[o] = '\t';
             o += 1u;
-            for (uint32_t i = lane; i < tail; i += 64u) if (o + i < end) out[o + i] = (char)slot[i];
+            const uint32_t md_len = TAGS && is_rec ? t.md[2ull * k + 1ull] : 0u;
+            if (!TAGS || !md_len) { for (uint32_t i = lane; i < tail; i += 64u) if (o + i < end) out[o + i] = (char)slot[i]; }
+            else if constexpr (TAGS) {
+                // gm_batch_set_row_tags: the tail without its newline, "\tNM:i:<nm>\tMD:Z:", the string of the walk, the newline
+                const uint32_t body = tail ? tail - 1u : 0u, nm = t.md[2ull * k], dn = md_digits(nm);
+                for (uint32_t i = lane; i < body; i += 64u) if (o + i < end) out[o + i] = (char)slot[i];
+                o += body;
+                if (lane < 12u) {
+                    const char c[13] = "\tNM:i:\tMD:Z:";
+                    const unsigned long long at = o + lane + (lane < 6u ? 0u : dn);
+                    if (at < end) out[at] = c[lane];
+                }
+                if (lane == 12u) md_put(reinterpret_cast<uint8_t*>(out), o + 6u, end, nm, dn);
+                o += 12u + dn;
+                uint32_t nm_w, len_w;
+                gm_md_walk<true>(t, r, bs, L, cg, gout, rev, lane, reinterpret_cast<uint8_t*>(out), o, end, &nm_w, &len_w);
+                o += md_len;
+                if (lane == 0 && o < end) out[o] = '\n';
+            }
         }
         __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// gm_batch_set_row_tags: NM:i and MD:Z of the row as printed (the walk: gm_mdtag_dev.h).  The sizes pass, behind k_out_text_sizes /
+// k_bam_sizes and in front of the scan of row_len: one wavefront per row, four rows per workgroup and step.  {NM, MD bytes} into t.md
+// (0 bytes: the row gets no tags - it prints no record, or a CIGAR of "*"), and the bytes of the two tags added to row_len:
+// "\tNM:i:<nm>\tMD:Z:<md>" in SAM text, NM i int32 + MD Z <md> NUL in BAM.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_md_sizes(GmDevBatch b, GmDevText t, int bam) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 4ull; base < t.n_rows; base += (unsigned long long)gridDim.x * 4ull) {
+        const unsigned long long k = base + wv;
+        if (k >= t.n_rows) continue;                          // (the whole wavefront: k is the same in its 64 lanes, and there is no barrier)
+        unsigned long long rec = 0; uint32_t urd = 0;
+        uint32_t nm = 0, md_len = 0;
+        if (gm_row_is_record(t, k, rec, urd)) {
+            const GmDevSamRec r = t.recs[rec];
+            const uint8_t* slot = t.slots + k * 64ull;
+            const uint32_t gout = (uint32_t)slot[58] | ((uint32_t)slot[59] << 8);
+            const char* cg = t.pool + r.cigar_off;
+            if (md_row_has_tags(cg, gout)) {
+                const uint32_t rd = r.read;                   // (as the row kernels index the block)
+                gm_md_walk<false>(t, r, b.bases + (size_t)rd * b.stride, t.seq_len[rd], cg, gout, r.strand != 0 && !t.cigar_forward, lane, nullptr, 0ull, 0ull, &nm, &md_len);
+            }
+        }
+        if (lane == 0) {
+            t.md[2ull * k] = nm; t.md[2ull * k + 1ull] = md_len;
+            if (md_len) t.row_len[k] += bam ? md_len + 11u : 12u + md_digits(nm) + md_len;
+        }
     }
 }
 
@@ -959,9 +1013,17 @@ int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream) {
     // one resident round: as many workgroups of 4 waves as the device holds at once
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_out_text_rows, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
+    void (*const kern)(GmDevBatch, GmDevText) = t.md ? k_out_text_rows<true> : k_out_text_rows<false>;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
     const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_rows + 3) / 4, (uint64_t)cus * (uint64_t)per_cu));
-    hipLaunchKernelGGL(k_out_text_rows, dim3(grid), dim3(256), 0, S_(stream), b, t);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, S_(stream), b, t);
+    return (int)hipGetLastError();
+}
+
+int gmk_md_sizes(const GmDevBatch& b, const GmDevText& t, int bam, void* stream) {
+    if (t.n_rows == 0) return 0;
+    const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_rows + 3) / 4, 4096));
+    hipLaunchKernelGGL(k_md_sizes, dim3(grid), dim3(256), 0, S_(stream), b, t, bam);
     return (int)hipGetLastError();
 }
 

@@ -69,6 +69,8 @@ struct Options {
     bool bam_level_set = false;     // (refused without --sam_format=bam)
     bool bam_lz77 = false;          // --bam_lz77: LZ77 matches under the Huffman code of level 1; once the options are checked, GM_BGZF_LZ77 in bam_level
     bool sam_unmapped = false;      // --sam_unmapped: a read without a row gets a flag-4 row (gm_batch_set_unmapped_rows; implies --sam_text=device)
+    bool sam_md = false;            // --sam_md: NM:i and MD:Z of every row as printed, behind X0 (gm_batch_set_row_tags; implies --sam_text=device)
+    bool sam_cigar_set = false, sam_cigar_forward = false;      // --sam_cigar=gnumap|forward: a minus-strand row's CIGAR as the reference prints it, or in reference order (gm_batch_set_cigar_order; implies --sam_text=device)
     bool bam_index = false;       // --bam_index: <out>.bam.bai beside a sorted <out>.bam, built on the GPU from what the sorter holds (gm_sam_sorter_bai)
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
 };
@@ -135,7 +137,13 @@ struct Options {
             "      --sam_unmapped           keep the reads that do not map: each gets one row (flag 4, no contig, no position, SEQ and QUAL as in\n"
             "                               the read file, tag YU:i:<code>: 2 no match, 1 too many matches, -2 too short, -3 too poor, 0 nothing\n"
             "                               printed) where its rows would stand; with --sam_sort=coordinate behind every contig, in input order.\n"
-            "                               Implies --sam_text=device (not with --sam_text=host).  Every other row is written as without the flag\n");
+            "                               Implies --sam_text=device (not with --sam_text=host).  Every other row is written as without the flag\n"
+            "      --sam_md                 NM:i and MD:Z behind X0 on every row whose CIGAR is not *, computed on the GPU from the row as printed\n"
+            "                               (POS, CIGAR, SEQ) and the reference - what samtools calmd would add.  Implies --sam_text=device\n"
+            "                               (not with --sam_text=host or -A/--adaptor)\n"
+            "      --sam_cigar=gnumap|forward  the CIGAR of a minus-strand row: gnumap (default) = its tokens last to first, as GNUMAP prints it;\n"
+            "                               forward = in reference order, as the alignment was computed - the order POS and SEQ of the row are in.\n"
+            "                               Implies --sam_text=device (not with --sam_text=host)\n");
     exit(rc);
 }
 
@@ -214,6 +222,11 @@ static void parse_args(int argc, char** argv, Options& o) {
             else if (!strcmp(s, "bam_lz77")) o.bam_lz77 = true;
             else if (!strcmp(s, "bam_index")) o.bam_index = true;
             else if (!strcmp(s, "sam_unmapped")) o.sam_unmapped = true;
+            else if (!strcmp(s, "sam_md")) o.sam_md = true;
+            else if (starts(s, "sam_cigar=")) {
+                if (strcmp(s + 10, "gnumap") && strcmp(s + 10, "forward")) { fprintf(stderr, "Error: --sam_cigar takes gnumap or forward, not \"%s\"\n", s + 10); exit(1); }
+                o.sam_cigar_set = true; o.sam_cigar_forward = !strcmp(s + 10, "forward");
+            }
             else if (starts(s, "sam_shards=")) {
                 char* end = nullptr;
                 const long k = strtol(s + 11, &end, 10);
@@ -283,6 +296,16 @@ static void parse_args(int argc, char** argv, Options& o) {
     if (o.bam) {                                             // refused before a device is opened or a file is written
         if (o.sam_text_host_set) { fprintf(stderr, "Error: --sam_format=bam writes the records on the GPU: it cannot be combined with --sam_text=host\n"); exit(1); }
         if (o.sam_shards > 1) { fprintf(stderr, "Error: --sam_format=bam writes one <out>.bam: it cannot be combined with --sam_shards above 1\n"); exit(1); }
+        o.sam_text_device = true;
+    }
+    if (o.sam_md || o.sam_cigar_set) {                       // refused before a device is opened or a file is written
+        const char* flag = o.sam_md ? "--sam_md" : "--sam_cigar";
+        if (o.sam_text_host_set) { fprintf(stderr, "Error: %s is applied where the GPU writes the rows: it cannot be combined with --sam_text=host\n", flag); exit(1); }
+        if (o.sam_md && !o.adaptor.empty()) {
+            fprintf(stderr, "Error: --sam_md cannot be combined with -A/--adaptor: with an adaptor SEQ is the whole read and the CIGAR covers the kept part, "
+                            "so NM / MD of the row as printed would describe nothing\n");
+            exit(1);
+        }
         o.sam_text_device = true;
     }
     if (o.sam_unmapped) {                                    // refused before a device is opened or a file is written
@@ -1062,6 +1085,7 @@ static int open_devices(Run& R) {
             w.gpu = g; w.ix = ix; w.text_pool = &R.text_pool; w.stage_pool = &R.stage_pool; w.sorter = R.sorter;
             if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK ||
                 gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK || gm_batch_set_unmapped_rows(w.batch, o.sam_unmapped ? 1 : 0) != GM_OK ||
+                gm_batch_set_row_tags(w.batch, o.sam_md ? GM_ROW_TAG_MD : 0u) != GM_OK || gm_batch_set_cigar_order(w.batch, o.sam_cigar_forward ? GM_CIGAR_FORWARD : GM_CIGAR_GNUMAP) != GM_OK ||
                 gm_batch_set_read_format(w.batch, o.fasta ? GM_READS_FASTA : GM_READS_FASTQ) != GM_OK) return fail();
         }
     }

@@ -186,8 +186,9 @@ typedef struct {
 
 /* kernels of gm_map_batch_device, for the HIP-event timing of gm_batch_kernel_times.  GM_K_SEED has no launches when the seed
  * lookup runs inside the vote kernel (full SA, k-mer table as long as the seed, k-mers expected >= 4 times in the reference, no -h;
- * env GM_SEED_FUSED=0|1 overrides): its time is then part of GM_K_VOTE; the work counters are the same either way */
-enum { GM_K_PREP = 0, GM_K_SEED, GM_K_LOCATE, GM_K_VOTE, GM_K_VOTE_RETRY, GM_K_NW, GM_K_COMPACT, GM_K_COUNT };
+ * env GM_SEED_FUSED=0|1 overrides): its time is then part of GM_K_VOTE; the work counters are the same either way.
+ * GM_K_MD_SIZES belongs to the row-producing output calls: the sizes pass of gm_batch_set_row_tags (no launches with the setting off) */
+enum { GM_K_PREP = 0, GM_K_SEED, GM_K_LOCATE, GM_K_VOTE, GM_K_VOTE_RETRY, GM_K_NW, GM_K_COMPACT, GM_K_MD_SIZES, GM_K_COUNT };
 
 const char* gm_last_error(void);
 const char* gm_version(void);
@@ -332,6 +333,38 @@ int gm_output_batch_text(gm_index*, const gm_params*, gm_batch*, const gm_reads*
  * gm_batch_unmapped_rows: how many such rows the last row-producing output call on the batch wrote (0 with the setting off). */
 int gm_batch_set_unmapped_rows(gm_batch*, int on);
 int gm_batch_unmapped_rows(gm_batch*, uint64_t* n);
+
+/* ---- NM:i and MD:Z on the rows, and CIGARs in reference order (two defined extensions) ----
+ * Both are per-batch settings, off by default, read by the six row-producing output calls from the next call on; gm_output_batch
+ * (the records form) reads neither.  With both at their defaults no byte and no launch changes.
+ *
+ * gm_batch_set_cigar_order(b, GM_CIGAR_FORWARD): a minus-strand row writes its CIGAR field exactly as a plus-strand row writes the
+ * same pool entry - all its bytes in pool order; in BAM operation k goes to slot k.  GM_CIGAR_GNUMAP (the default) prints the tokens
+ * last to first, as the reference program does - beside a SEQ that is already reverse-complemented, at a POS in forward coordinates,
+ * which is the wrong way round for every row with an indel (the traceback ran against the forward window).  Reference length and bin
+ * do not depend on the order.  Any other value: GM_E_ARG.
+ *
+ * gm_batch_set_row_tags(b, GM_ROW_TAG_MD): every row that prints a record whose CIGAR field is not "*" gains, behind X0,
+ *     SAM text  \t NM:i:<nm> \t MD:Z:<md>            BAM  NM i <int32>, MD Z <md> NUL   (block_size includes them)
+ * A row with CIGAR "*" and the row of a read without a record keep their bytes.  The tags describe THE ROW AS PRINTED - what
+ * `samtools calmd` derives from the row's POS, CIGAR field, SEQ and the reference - so they agree with whichever CIGAR order is set:
+ *     x = POS-1; z = 0; u = 0; nm = 0; md = ""
+ *     for every token (n, op) of the CIGAR field as printed (n = 0 contributes nothing):
+ *       M: n times: if z >= len(SEQ) or x >= len(contig): the walk ends
+ *                   if code(SEQ[z]) == code(T[x]) and that code != 15: u += 1     else: md += str(u) + T[x]; u = 0; nm += 1
+ *                   x += 1; z += 1
+ *       I: z += n; nm += n
+ *       D: md += str(u) + "^"; u = 0; nm += n; then n times, while x < len(contig): md += T[x]; x += 1
+ *     md += str(u)
+ * T is the contig's text in upper case: the pac letter, or inside a hole of <fa>.gnumap.amb that hole's character; code() is the BAM
+ * nibble of a character ("=ACMGRSVTWYHKDBN", either case, anything else 15) - so an N on either side is a mismatch and the IUPAC letters
+ * of a FASTA block compare by nibble.  Any bit but GM_ROW_TAG_MD: GM_E_ARG.  GM_E_UNSUPPORTED: the batch has an adaptor set (SEQ is then
+ * the whole read and the CIGAR covers the kept part; gm_batch_set_adaptor refuses likewise while the tags are on).  GM_E_IO: the index
+ * was opened without a <fa>.gnumap.amb that can be read and parsed; gm_last_error() names the file. */
+#define GM_ROW_TAG_MD 1u
+enum { GM_CIGAR_GNUMAP = 0, GM_CIGAR_FORWARD = 1 };
+int gm_batch_set_row_tags(gm_batch*, uint32_t tags);
+int gm_batch_set_cigar_order(gm_batch*, int order);
 
 /* ---- FASTQ text in: the reads cut into rows on the device ----
  * gm_batch_upload_text takes a byte range of FASTQ text as it stands in the file, uploads it verbatim and leaves the batch resident

@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--sweep", default="", help="further argument sets for the timed run, separated by ';' (each one more run on the same files)")
     ap.add_argument("--bam_index", action="store_true", help="two more timed runs: --sam_format=bam --sam_sort=coordinate, then the same with --bam_index (<out>.bam.bai)")
     ap.add_argument("--bam_lz77", action="store_true", help="three more timed runs: --sam_format=bam, the same with --bam_lz77, and --sam_format=bam --sam_sort=coordinate --bam_lz77 --bam_index")
+    ap.add_argument("--sam_md", action="store_true", help="four more timed runs: --sam_text=device and --sam_format=bam, each without and with --sam_md --sam_cigar=forward")
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     fa = os.path.join(a.dir, "g%g.fa" % a.mbp); fq = os.path.join(a.dir, "r%d.fq" % a.reads)
@@ -62,6 +63,9 @@ def main():
         runs += [("map " + x, a.args + " " + x) for x in (sorted_bam, sorted_bam + " --bam_index")]
     if a.bam_lz77:
         runs += [("map " + x, a.args + " " + x) for x in ("--sam_format=bam", "--sam_format=bam --bam_lz77", "--sam_format=bam --sam_sort=coordinate --bam_lz77 --bam_index")]
+    if a.sam_md:
+        tags = " --sam_md --sam_cigar=forward"
+        runs += [("map " + x, a.args + " " + x) for x in ("--sam_text=device", "--sam_text=device" + tags, "--sam_format=bam", "--sam_format=bam" + tags)]
     def shard_files():                                           # <out>.<k>.sam of a --sam_shards=K run
         return [f for f in glob.glob(glob.escape(out) + ".*.sam") if f[len(out) + 1:-4].isdigit()]
 
