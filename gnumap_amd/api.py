@@ -106,7 +106,7 @@ class gm_counters(C.Structure):
     _fields_ = [(n, u64) for n in ("reads", "kmers_searched", "occ_calls", "occ_blocks", "seeds_used", "sa_hits", "lf_steps", "candidates",
                                    "nw_cells", "accepted", "vote_retries", "table_lookups")]
 
-GM_K_COUNT = 8
+GM_K_COUNT = 9
 
 
 RAW_HIT_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u4"), ("score", "<f4"), ("step", "<u2"), ("strand", "u1"), ("pad", "u1")])
@@ -115,6 +115,8 @@ MATCH_DTYPE = np.dtype([("read", "<u4"), ("score", "<f4"), ("first_pos", "<u8"),
 POS_DTYPE = np.dtype([("pos", "<u8"), ("strand", "u1")], align=True)
 SAM_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u8"), ("contig", "<u4"), ("chr_pos", "<u8"), ("strand", "u1"), ("mapq", "<i4"),
                       ("a_score", "<f4"), ("post_prob", "<f4"), ("sim_matches", "<i4"), ("cigar_off", "<u4")], align=True)
+MATE_ROW_DTYPE = np.dtype([("flag", "<u4"), ("rnext", "<i4"), ("pnext", "<u4"), ("tlen", "<i4")])     # gm_mate_row
+MATE_STATS = ("pairs", "both_mapped", "proper", "one_mapped", "none_mapped")                          # gm_mate_stats, in its order
 SNP_DTYPE = np.dtype([("pos", "<u8"), ("contig", "<u4"), ("chr_pos", "<u8"), ("total", "<f4"), ("nuc", "<f4", (5,)), ("p_val", "<f8"), ("ref", "u1"),
                       ("alt1", "u1"), ("alt2", "u1"), ("diploid", "u1")], align=True)
 
@@ -131,7 +133,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_coverage_write_gmp_calls_device", "gm_coverage_calls_text", "gm_coverage_write_vcf",
            "gm_batch_set_adaptor", "gm_batch_trimmed_len", "gm_batch_adaptor_time", "gm_dev_adaptor_trim",
            "gm_batch_set_read_format", "gm_index_set_probe_format", "gm_batch_set_unmapped_rows", "gm_batch_unmapped_rows",
-           "gm_batch_set_row_tags", "gm_batch_set_cigar_order",
+           "gm_batch_set_row_tags", "gm_batch_set_cigar_order", "gm_batch_set_mates", "gm_batch_mate_rows", "gm_batch_mate_stats",
            "gm_batch_upload_text", "gm_map_batch_text", "gm_output_batch_text_resident", "gm_dev_fastq_rows", "gm_dev_fastq_tile_bytes",
            "gm_sam_sorter_create", "gm_sam_sorter_destroy", "gm_output_batch_sorted", "gm_output_batch_sorted_resident", "gm_sam_sorter_finish",
            "gm_sam_sorter_read", "gm_sam_sorter_stats", "gm_sam_sorter_add_rows",
@@ -253,6 +255,9 @@ def load_library():
     L.gm_batch_set_unmapped_rows.argtypes = [C.c_void_p, C.c_int]
     L.gm_batch_unmapped_rows.argtypes = [C.c_void_p, C.POINTER(u64)]
     L.gm_batch_set_row_tags.argtypes = [C.c_void_p, C.c_uint32]
+    L.gm_batch_set_mates.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]
+    L.gm_batch_mate_rows.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]
+    L.gm_batch_mate_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.gm_batch_set_cigar_order.argtypes = [C.c_void_p, C.c_int]
     _LIB = L
     return L
@@ -628,6 +633,31 @@ class Batch:
         not "*" carries NM:i and MD:Z behind X0 - of the row as printed, so they agree with the CIGAR order that is set.  GnumapError
         GM_E_UNSUPPORTED with an adaptor set, GM_E_IO when the index has no readable <fa>.gnumap.amb"""
         _chk(lib().gm_batch_set_row_tags(self.h, GM_ROW_TAG_MD if md else 0))
+
+    def set_mates(self, on=True, min_insert=0, max_insert=500):
+        """gm_batch_set_mates: from the next call on, reads 2i and 2i + 1 of a block are the mates of pair i in every output call: the
+        pair is resolved on the device (include/gnumap_hip.h has the rule) and the rows carry the paired flag, RNEXT, PNEXT and TLEN.
+        An odd block, min_insert > max_insert and a pair whose printed names differ make the OUTPUT call raise GM_E_ARG"""
+        _chk(lib().gm_batch_set_mates(self.h, int(bool(on)), int(min_insert), int(max_insert)))
+
+    def mate_rows(self, cap=None):
+        """gm_batch_mate_rows: the {flag, rnext, pnext, tlen} of every row the last output call produced (MATE_ROW_DTYPE), in row
+        order; for output() one per record.  cap: the room to offer (None: ask first); GM_E_CAPACITY raises when it is too small"""
+        n = u64()
+        if cap is None:
+            rc = lib().gm_batch_mate_rows(self.h, None, 0, C.byref(n))
+            if rc != GM_E_CAPACITY:
+                _chk(rc)
+            cap = int(n.value)
+        out = np.zeros(max(int(cap), 1), MATE_ROW_DTYPE)
+        _chk(lib().gm_batch_mate_rows(self.h, out.ctypes.data, int(cap), C.byref(n)))
+        return out[:int(n.value)]
+
+    def mate_stats(self):
+        """gm_batch_mate_stats: dict(pairs, both_mapped, proper, one_mapped, none_mapped) of the last output call"""
+        v = np.zeros(5, np.uint64)
+        _chk(lib().gm_batch_mate_stats(self.h, v.ctypes.data))
+        return {k: int(x) for k, x in zip(MATE_STATS, v)}
 
     def set_cigar_order(self, order="gnumap"):
         """gm_batch_set_cigar_order: "gnumap" - a minus-strand row prints its CIGAR tokens last to first, as the reference does (the

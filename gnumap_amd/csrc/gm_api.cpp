@@ -61,6 +61,8 @@ struct gm_batch {
         t_bammeta,                      // gm_output_batch_bam: operations and bin of every record (k_bam_sizes)
         t_status, t_rowcnt, t_rowflag, t_rowfirst, t_rowucum, t_rowsrc,        // gm_batch_set_unmapped_rows: the reads' status bytes and the row source (gmk_row_source)
         t_md,                           // gm_batch_set_row_tags: {NM, MD bytes} of every row (k_md_sizes)
+        m_span, m_first, m_end, m_prim, m_proper, m_meta, m_fields,            // gm_batch_set_mates: what the k_mate_* kernels leave (GmDevMates), the fields of every row
+        m_namelen, m_nameoff, m_names,  // ... and the names after the QNAME rule's cuts, a pool of their own
         full_len, d_adaptor,            // -A: the lengths as uploaded (`len` then holds what k_adaptor_trim keeps), the adaptor's characters
         rt_text, rt_tilecnt, rt_tileoff, rt_lineat, rt_lsum, rt_lin, rt_recs, rt_nlen, rt_tlen, rt_meta;      // gm_batch_upload_text: the FASTQ text and what k_rt_* make of it
     GmBgzfBufs bz;                      // gm_output_batch_bam: the BGZF blocks of the block's records
@@ -75,6 +77,10 @@ struct gm_batch {
     bool unmapped_rows = false;         // gm_batch_set_unmapped_rows: a read without a record gets a flag-4 row from the row-producing output calls
     uint64_t n_unmapped = 0;            // ... and how many the last output call wrote (gm_batch_unmapped_rows)
     uint32_t row_tags = 0;              // gm_batch_set_row_tags: GM_ROW_TAG_MD = the rows of the row-producing output calls carry NM:i and MD:Z
+    bool mates = false;                 // gm_batch_set_mates: reads 2i and 2i + 1 are the mates of pair i in every output call
+    uint32_t mate_min = 0, mate_max = 500;      // ... the insert limits of a concordant combination, both inclusive
+    uint64_t mate_n_rows = 0;           // ... the rows the last output call left fields for in m_fields (gm_batch_mate_rows)
+    gm_mate_stats mate_stats{};         // ... and its pair counters (gm_batch_mate_stats)
     int cigar_order = GM_CIGAR_GNUMAP;  // gm_batch_set_cigar_order: GM_CIGAR_FORWARD = a minus-strand row prints its CIGAR in reference order
     bool fasta = false;                 // the block that is resident was uploaded as FASTA (GmDevBatch::fasta)
     bool adaptor_dirty = false;         // d_adaptor does not hold `adaptor` yet
@@ -573,6 +579,7 @@ extern "C" void gm_batch_destroy(gm_batch* b) {
                       &b->o_recs, &b->o_pool, &b->o_codes, &b->snp_scratch, &b->snp_hmm, &b->pair_fb, &b->pair_list,
                       &b->t_names, &b->t_nameoff, &b->t_qtail, &b->t_qtailoff, &b->t_slots, &b->t_rowlen, &b->t_rowoff, &b->t_text, &b->t_bad, &b->t_bammeta, &b->full_len, &b->d_adaptor,
                       &b->t_status, &b->t_rowcnt, &b->t_rowflag, &b->t_rowfirst, &b->t_rowucum, &b->t_rowsrc,
+                      &b->m_span, &b->m_first, &b->m_end, &b->m_prim, &b->m_proper, &b->m_meta, &b->m_fields, &b->m_namelen, &b->m_nameoff, &b->m_names,
                       &b->rt_text, &b->rt_tilecnt, &b->rt_tileoff, &b->rt_lineat, &b->rt_lsum, &b->rt_lin, &b->rt_recs, &b->rt_nlen, &b->rt_tlen, &b->rt_meta };
     for (DevBuf* d : all) d->release();
     b->bz.release();
@@ -850,6 +857,32 @@ extern "C" int gm_batch_unmapped_rows(gm_batch* b, uint64_t* n) {
 
 // Two more defined extensions, read by the six row-producing output calls from the next call on; gm_output_batch
 // (records) reads neither.  Row tags: NM:i and MD:Z of the row as printed, behind X0, on every row whose CIGAR field is not "*".
+// gm_batch_set_mates: the setting is only stored here; an odd block and limits the wrong way round are refused by the output call
+extern "C" int gm_batch_set_mates(gm_batch* b, int on, uint32_t min_insert, uint32_t max_insert) {
+    if (!b) { gm_set_error("gm_batch_set_mates: batch is NULL"); return GM_E_ARG; }
+    b->mates = on != 0; b->mate_min = min_insert; b->mate_max = max_insert;
+    return GM_OK;
+}
+
+static_assert(sizeof(gm_mate_row) == 16 && sizeof(GmDevMateRow) == 16 && offsetof(gm_mate_row, rnext) == offsetof(GmDevMateRow, rnext) &&
+              offsetof(gm_mate_row, pnext) == offsetof(GmDevMateRow, pnext) && offsetof(gm_mate_row, tlen) == offsetof(GmDevMateRow, tlen), "gm_mate_row layout");
+extern "C" int gm_batch_mate_rows(gm_batch* b, gm_mate_row* out, uint64_t cap, uint64_t* n) {
+    if (!b || !n) { gm_set_error("gm_batch_mate_rows: batch or n is NULL"); return GM_E_ARG; }
+    *n = b->mate_n_rows;
+    if (b->mate_n_rows > cap) { gm_set_error("gm_batch_mate_rows: room for " + std::to_string(cap) + " rows, the last output call left " + std::to_string(b->mate_n_rows)); return GM_E_CAPACITY; }
+    if (!b->mate_n_rows) return GM_OK;
+    if (!out) { gm_set_error("gm_batch_mate_rows: out is NULL"); return GM_E_ARG; }
+    HIPCHK(hipSetDevice(b->ix->device));
+    HIPCHK(hipMemcpy(out, b->m_fields.p, (size_t)b->mate_n_rows * sizeof(gm_mate_row), hipMemcpyDeviceToHost));
+    return GM_OK;
+}
+
+extern "C" int gm_batch_mate_stats(gm_batch* b, gm_mate_stats* out) {
+    if (!b || !out) { gm_set_error("gm_batch_mate_stats: batch or out is NULL"); return GM_E_ARG; }
+    *out = b->mate_stats;
+    return GM_OK;
+}
+
 extern "C" int gm_batch_set_row_tags(gm_batch* b, uint32_t tags) {
     if (!b) { gm_set_error("gm_batch_set_row_tags: batch is NULL"); return GM_E_ARG; }
     if (tags & ~(uint32_t)GM_ROW_TAG_MD) { gm_set_error("gm_batch_set_row_tags: GM_ROW_TAG_MD or 0, not " + std::to_string(tags)); return GM_E_ARG; }
@@ -1512,7 +1545,7 @@ extern "C" int gm_batch_pair_flagged(gm_batch* b, uint32_t* flagged) {
 }
 
 extern "C" const char* gm_kernel_name(int which) {
-    static const char* names[GM_K_COUNT] = { "k_prep", "k_seed", "k_locate_sampled", "k_vote", "k_vote_retry", "k_nw", "k_compact(scan+scatter)", "k_md_sizes" };
+    static const char* names[GM_K_COUNT] = { "k_prep", "k_seed", "k_locate_sampled", "k_vote", "k_vote_retry", "k_nw", "k_compact(scan+scatter)", "k_md_sizes", "k_mate_*" };
     return which >= 0 && which < GM_K_COUNT ? names[which] : "?";
 }
 
@@ -1951,6 +1984,14 @@ static int out_check_call(const gm_batch* b, const OutCall& c) {
         if (!out->data && out->cap) { gm_set_error(std::string(c.who) + ": gm_bam_out.data is NULL"); return GM_E_ARG; }
     }
     if (hits->n != b->n || c.reads->n != b->n) { gm_set_error("hits / reads do not belong to the batch"); return GM_E_ARG; }
+    if (b->mates && (hits->n & 1u)) {
+        gm_set_error(std::string(c.who) + ": gm_batch_set_mates is on and the block has an odd number of reads (" + std::to_string(hits->n) + "): reads 2i and 2i + 1 are the mates of pair i");
+        return GM_E_ARG;
+    }
+    if (b->mates && b->mate_min > b->mate_max) {
+        gm_set_error(std::string(c.who) + ": gm_batch_set_mates: min_insert " + std::to_string(b->mate_min) + " is above max_insert " + std::to_string(b->mate_max));
+        return GM_E_ARG;
+    }
     if (c.sink == OutCall::text) {
         c.text_out()->text_len = 0; c.text_out()->n_recs = 0;
         if (c.text_out()->row_off && c.text_out()->row_cap) c.text_out()->row_off[0] = 0;
@@ -2175,6 +2216,7 @@ static int out_row_inputs(gm_index* ix, const gm_params* p, gm_batch* b, const O
     t.seq_len = b->adaptor.empty() ? b->dev.len : b->full_len.as<uint16_t>();
     t.fa_qual = fasta_qual_word();
     t.cigar_forward = b->cigar_order == GM_CIGAR_FORWARD ? 1u : 0u;
+    t.mate = nullptr;                                          // (out_mates sets it)
     t.md = nullptr; t.pac = nullptr; t.contig_off = nullptr; t.l_pac = t.n_seqs = 0; t.holes = nullptr; t.n_holes = 0;
     if (b->row_tags & GM_ROW_TAG_MD) {
         // {NM, MD bytes} per row, the reference and its holes: allocated, uploaded and read only with the setting on
@@ -2187,6 +2229,52 @@ static int out_row_inputs(gm_index* ix, const gm_params* p, gm_batch* b, const O
     return GM_OK;
 }
 
+// gm_batch_set_mates: the pairs are resolved on the records where out_write_records left them, and every row gets its fields.  A rows
+// sink comes here with the GmDevText of out_row_inputs (the row source, the names in HBM): the names are cut by the QNAME rule into a
+// pool of their own, which the row kernels then read, and a pair whose printed names differ ends the call - before a row is
+// written, a capacity is answered or anything is deposited.  The records sink has no rows and no names: its rows are its records.
+// One read-back: the five counters and the first such pair
+static int out_mates(gm_batch* b, const OutCall& c, OutState& s, hipStream_t st) {
+    const uint32_t n = s.n;
+    GmDevText& t = s.t;
+    if (!c.rows() || !(s.n_recs || s.unmapped)) {              // no row step: the records are the rows
+        t = GmDevText{};
+        t.recs = s.n_recs ? b->o_recs.as<GmDevSamRec>() : nullptr; t.n_recs = s.n_recs; t.n_rows = s.n_recs; t.n_reads = n;
+    }
+    const bool names = c.rows() && t.names != nullptr;
+    const uint64_t name_room = !names ? 0 : c.rt ? c.rt->name_off[n] - c.rt->name_off[0] : b->text_name_bytes;
+    if (b->m_span.ensure((size_t)s.n_recs * 4 + 16) || b->m_first.ensure((size_t)n * 8 + 16) || b->m_end.ensure((size_t)n * 8 + 16) || b->m_prim.ensure((size_t)n * 8 + 16) ||
+        b->m_proper.ensure((size_t)n / 2 + 16) || b->m_meta.ensure(MT_META_N * 8) || b->m_fields.ensure((size_t)t.n_rows * sizeof(GmDevMateRow) + 16) ||
+        b->scan_tmp.ensure(((size_t)n / 1024 + 8) * 8) ||
+        (names && (b->m_namelen.ensure((size_t)n * 4 + 16) || b->m_nameoff.ensure(((size_t)n + 1) * 8) || b->m_names.ensure((size_t)name_room + 16)))) return GM_E_NOMEM;
+    GmDevMates m{};
+    m.recs = t.recs; m.n_recs = s.n_recs; m.pool = b->o_pool.as<char>(); m.n_reads = n; m.min_insert = b->mate_min; m.max_insert = b->mate_max;
+    m.span = b->m_span.as<uint32_t>(); m.first = b->m_first.as<unsigned long long>(); m.end = b->m_end.as<unsigned long long>();
+    m.prim = b->m_prim.as<unsigned long long>(); m.proper = b->m_proper.as<uint8_t>(); m.meta = b->m_meta.as<unsigned long long>();
+    unsigned long long meta[MT_META_N] = { 0 };
+    {
+        KTimer kt(b, GM_K_MATES, st);
+        KCHK(gmk_mate_resolve(m, st));
+        if (names) {
+            KCHK(gmk_mate_names(t.names, t.name_off, n, b->m_namelen.as<uint32_t>(), b->m_nameoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), b->m_names.as<char>(),
+                                name_room, c.bam_rows() ? 254u : 1023u, m.meta, st));
+            t.names = b->m_names.as<char>(); t.name_off = b->m_nameoff.as<uint64_t>();
+        }
+        KCHK(gmk_mate_fields(m, t, b->m_fields.as<GmDevMateRow>(), st));
+    }
+    HIPCHK(hipMemcpyAsync(meta, m.meta, sizeof meta, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (names && meta[MT_META_BAD_PAIR] != ~0ull) {
+        gm_set_error(std::string(c.who) + ": gm_batch_set_mates: the names of pair " + std::to_string(meta[MT_META_BAD_PAIR]) + " (reads " + std::to_string(2 * meta[MT_META_BAD_PAIR]) +
+                     " and " + std::to_string(2 * meta[MT_META_BAD_PAIR] + 1) + " of the block) differ as printed: the two files are not in step");
+        return GM_E_ARG;
+    }
+    t.mate = b->m_fields.as<GmDevMateRow>();
+    b->mate_n_rows = t.n_rows;
+    b->mate_stats = { meta[MT_META_PAIRS], meta[MT_META_BOTH], meta[MT_META_PROPER], meta[MT_META_ONE], meta[MT_META_NONE] };
+    return GM_OK;
+}
+
 // Rows, their sizes: tails + row lengths (the records' sizes take their place when the rows are BAM), their scan, and what comes back:
 // the length of all rows and the first record the device cannot print
 static int out_count_rows(gm_batch* b, const OutCall& c, OutState& s, hipStream_t st) {
@@ -2196,6 +2284,7 @@ static int out_count_rows(gm_batch* b, const OutCall& c, OutState& s, hipStream_
     if (bam_timed) { for (auto& e : b->bam_ev) if (!e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(b->bam_ev[0], st)); }
     if (bam) KCHK(gmk_bam_sizes(s.t, b->t_bammeta.as<uint32_t>(), st));
     if (bam_timed) HIPCHK(hipEventRecord(b->bam_ev[1], st));
+    if (s.t.mate && !bam) { KTimer kt(b, GM_K_MATES, st); KCHK(gmk_mate_row_len(s.t, st)); }               // gm_batch_set_mates: the flag and the mate columns onto row_len (a BAM record's size does not move)
     if (s.t.md) { KTimer kt(b, GM_K_MD_SIZES, st); KCHK(gmk_md_sizes(b->dev, s.t, bam ? 1 : 0, st)); }      // gm_batch_set_row_tags: the two tags' bytes onto row_len
     KCHK(gmk_scan_u32(s.t.row_len, s.n_rows, b->t_rowoff.as<uint64_t>(), b->scan_tmp.as<unsigned long long>(), st));
     s.bad_row = ~0ull;
@@ -2313,8 +2402,12 @@ static int output_batch(gm_index* ix, const gm_params* p, gm_batch* b, const Out
     if (c.sink == OutCall::records) { c.recs_out()->n_recs = 0; c.recs_out()->cigar_len = 0; }
     s.unmapped = c.rows() && b->unmapped_rows;
     if (c.rows()) b->n_unmapped = 0;
+    b->mate_n_rows = 0; b->mate_stats = gm_mate_stats{};
     const bool matched = c.hits->n && c.hits->match_begin[c.hits->n];
-    if (!matched && !(s.unmapped && c.hits->n)) return GM_OK;                  // nothing matched: no record, no row, no deposit
+    if (!matched && !(s.unmapped && c.hits->n)) {                              // nothing matched: no record, no row, no deposit
+        if (b->mates) b->mate_stats.pairs = b->mate_stats.none_mapped = c.hits->n / 2;
+        return GM_OK;
+    }
     if (matched) {
         if (const int rc = out_check_hits(ix, p, b, c.hits, s)) return rc;
         if (const int rc = out_enqueue_traceback(ix, p, b, c.hits, s, st)) return rc;
@@ -2327,11 +2420,13 @@ static int output_batch(gm_index* ix, const gm_params* p, gm_batch* b, const Out
     } else s.n = c.hits->n;                                                    // n rows and no traceback, posterior pass or deposit
     if (c.rows() && (s.n_recs || s.unmapped)) {
         if (const int rc = out_row_inputs(ix, p, b, c, s, st)) return rc;
+        if (b->mates) if (const int rc = out_mates(b, c, s, st)) return rc;
         if (const int rc = out_count_rows(b, c, s, st)) return rc;
         pc.lap("text sizes");
         if (const int rc = out_write_rows(b, c, s, st)) return rc;
         if (const int rc = out_deliver_rows(b, c, s, st)) return rc;
     }
+    else if (b->mates) { if (const int rc = out_mates(b, c, s, st)) return rc; }      // (the records sink, and rows sinks with nothing to print)
     if (matched) if (const int rc = out_deposit(ix, b, s, st)) return rc;
     HIPCHK(hipStreamSynchronize(st));
     pc.lap("records+coverage");

@@ -530,10 +530,16 @@ __global__ void __launch_bounds__(256) k_bam_sizes(GmDevText t, uint32_t* __rest
 }
 
 __device__ __forceinline__ void bm_put32(uint8_t* w, uint32_t v) { w[0] = (uint8_t)v; w[1] = (uint8_t)(v >> 8); w[2] = (uint8_t)(v >> 16); w[3] = (uint8_t)(v >> 24); }
+// gm_batch_set_mates: the four core fields a row takes from its mate fields ("=" is the contig's own index; next_pos = PNEXT - 1, -1 for 0)
+__device__ __forceinline__ void bm_put_mate(uint8_t* hd, const GmDevMateRow f) {
+    hd[18] = (uint8_t)f.flag; hd[19] = (uint8_t)(f.flag >> 8);
+    bm_put32(hd + 24, (uint32_t)f.rnext); bm_put32(hd + 28, f.pnext - 1u); bm_put32(hd + 32, (uint32_t)f.tlen);
+}
 
 // one wavefront per record, four records per workgroup and step.  TAGS: gm_batch_set_row_tags is on (t.md is there) - an instance of
-// its own, so that the walk's registers cost the records without tags no occupancy
-template <bool TAGS>
+// its own, so that the walk's registers cost the records without tags no occupancy.  MATES: gm_batch_set_mates is on (t.mate is there):
+// flag, next_refID, next_pos and tlen come from the row's fields - instances of their own as well
+template <bool TAGS, bool MATES>
 __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, const uint32_t* __restrict__ meta) {
     __shared__ uint8_t s_head[4][64];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -557,6 +563,7 @@ __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, con
                 hd[18] = 4; hd[19] = 0;
                 bm_put32(hd + 20, L); bm_put32(hd + 24, 0xFFFFFFFFu); bm_put32(hd + 28, 0xFFFFFFFFu); bm_put32(hd + 32, 0u);
                 hd[36] = 'Y'; hd[37] = 'U'; hd[38] = 'i'; bm_put32(hd + 39, (uint32_t)(int32_t)t.status[urd]);
+                if constexpr (MATES) bm_put_mate(hd, t.mate[k]);
             }
         }
         if (is_rec) {
@@ -574,6 +581,7 @@ __global__ void __launch_bounds__(256) k_bam_rows(GmDevBatch b, GmDevText t, con
                 hd[36] = 'X'; hd[37] = 'A'; hd[38] = 'f'; bm_put32(hd + 39, __float_as_uint((float)((double)r.a_score * t.inv_adjust)));
                 hd[43] = 'X'; hd[44] = 'P'; hd[45] = 'f'; bm_put32(hd + 46, __float_as_uint(r.post_prob));
                 hd[50] = 'X'; hd[51] = '0'; hd[52] = 'i'; bm_put32(hd + 53, (uint32_t)r.sim_matches);
+                if constexpr (MATES) bm_put_mate(hd, t.mate[k]);
             }
         }
         __syncthreads();
@@ -667,7 +675,9 @@ int gmk_bam_sizes(const GmDevText& t, uint32_t* meta, void* stream) {
 int gmk_bam_rows(const GmDevBatch& b, const GmDevText& t, const uint32_t* meta, void* stream) {
     if (t.n_rows == 0) return 0;
     const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_rows + 3) / 4, 4096));
-    hipLaunchKernelGGL(t.md ? k_bam_rows<true> : k_bam_rows<false>, dim3(grid), dim3(256), 0, S_(stream), b, t, meta);
+    void (*const kern)(GmDevBatch, GmDevText, const uint32_t*) = t.mate ? (t.md ? k_bam_rows<true, true> : k_bam_rows<false, true>)
+                                                                        : (t.md ? k_bam_rows<true, false> : k_bam_rows<false, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, S_(stream), b, t, meta);
     return (int)hipGetLastError();
 }
 

@@ -159,6 +159,10 @@ struct GmDevPos { unsigned long long pos; uint8_t strand; uint8_t pad[7]; };
 struct GmDevSamRec { uint32_t read, pad0; unsigned long long pos; uint32_t contig, pad1; unsigned long long chr_pos; uint8_t strand; uint8_t pad2[3];
                      int32_t mapq; float a_score, post_prob; int32_t sim_matches; uint32_t cigar_off; };
 
+// gm_mate_row (layout asserted in gm_api.cpp): what a row prints of its mate - flag, contig of the mate's primary (-1: none), its POS
+// (0: none), TLEN
+struct GmDevMateRow { uint32_t flag; int32_t rnext; uint32_t pnext; int32_t tlen; };
+
 // what the SAM text kernels (k_out_text_*, gm_output.hip) read and write besides the block itself
 struct GmDevText {
     const GmDevSamRec* recs; unsigned long long n_recs;
@@ -188,6 +192,9 @@ struct GmDevText {
     uint32_t* md;
     const uint8_t* pac; const uint32_t* contig_off; uint32_t l_pac, n_seqs;
     const uint32_t* holes; uint32_t n_holes;
+    // gm_batch_set_mates (null with the setting off: the instances of the row kernels that read it are not launched).  One entry per
+    // row, in row order, left by k_mate_fields (gm_mates.hip).  names / name_off are then the names after the QNAME rule's cuts
+    const GmDevMateRow* mate;
 };
 #define GM_ROW_UNMAPPED (1ull << 63)
 #if defined(__HIPCC__)
@@ -203,6 +210,18 @@ __device__ __forceinline__ bool gm_row_is_record(const GmDevText& t, unsigned lo
     return false;
 }
 #endif
+
+// what the mate kernels (k_mate_*, gm_mates.hip) read and write: the block's records in read order and their CIGAR pool in; per record
+// its span, per read its record range [first, end) and its primary (a record index, ~0: none), per pair whether it is proper
+enum { MT_META_PAIRS = 0, MT_META_BOTH, MT_META_PROPER, MT_META_ONE, MT_META_NONE,     // gm_mate_stats, in its order
+       MT_META_BAD_PAIR,            // the first pair whose printed names differ (~0: none)
+       MT_META_N = 8 };
+struct GmDevMates {
+    const GmDevSamRec* recs; unsigned long long n_recs; const char* pool;
+    uint32_t n_reads, min_insert, max_insert;
+    uint32_t* span; unsigned long long* first; unsigned long long* end; unsigned long long* prim; uint8_t* proper;
+    unsigned long long* meta;
+};
 
 // gm_snp_rec (layout asserted in gm_tracks.cpp): a row of --snp's .gmp that carries a 'Y' call, written by k_snp_gather (gm_snpcall.hip)
 struct GmDevSnpRec { unsigned long long pos; uint32_t contig, pad0; unsigned long long chr_pos; float total, nuc[5]; double p_val; uint8_t ref, alt1, alt2, diploid;
@@ -382,6 +401,16 @@ int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream);
 // t.md, and the bytes the two tags take (SAM text, or bam != 0 BAM) added to row_len
 int gmk_md_sizes(const GmDevBatch& b, const GmDevText& t, int bam, void* stream);
 int gmk_fmt_g6(const double* v, uint32_t n, char* out /* n x 16 */, uint8_t* len, void* stream);
+// gm_mates.hip: gm_batch_set_mates.  resolve: spans, record ranges, primaries and the pair counters (m.meta, zeroed here).  names: the
+// QNAME rule - len (n_reads words) and new_off (n_reads + 1) are scratch, `out` takes the cut names (room: the block's own name bytes
+// always hold them), cut = the bytes of a name the sink prints; m.meta[MT_META_BAD_PAIR] = the first pair whose printed names differ.
+// fields: one GmDevMateRow per row of t (t.recs, t.n_recs, t.n_rows, t.row_src, t.n_reads are read).  row_len: SAM text only, behind
+// gmk_out_text_sizes and before the scan - the bytes the flag and the mate columns add to every row
+int gmk_mate_resolve(const GmDevMates& m, void* stream);
+int gmk_mate_names(const char* names, const uint64_t* name_off, uint32_t n_reads, uint32_t* len, uint64_t* new_off, unsigned long long* tmp, char* out, uint64_t room,
+                   uint32_t cut, unsigned long long* meta, void* stream);
+int gmk_mate_fields(const GmDevMates& m, const GmDevText& t, GmDevMateRow* out, void* stream);
+int gmk_mate_row_len(const GmDevText& t, void* stream);
 // gm_adaptor.hip: -A / --adaptor (SeqReader::FixReads2): out_len[r] = the length read r keeps; len = the lengths as uploaded, stride a multiple of 8
 int gmk_adaptor_cigar_room(const GmDevMatch* matches, uint32_t n_m, const uint16_t* full_len, uint32_t n, uint32_t* cig_all, void* stream);      // --no_nw with -A: room for "<whole length>M"
 int gmk_adaptor_trim(const uint8_t* bases, uint32_t stride, const uint16_t* len, uint32_t n, const uint8_t* adaptor, uint32_t a_len, uint16_t* out_len, void* stream);

@@ -744,10 +744,15 @@ __global__ void __launch_bounds__(256) k_out_text_sizes(GmDevBatch b, GmDevText 
 }
 
 // one wavefront per row, four rows per workgroup and step; the grid is one resident round.  TAGS: gm_batch_set_row_tags is on (t.md
-// is there) - an instance of its own, so that the walk's registers cost the rows without tags no occupancy
-template <bool TAGS>
+// is there) - an instance of its own, so that the walk's registers cost the rows without tags no occupancy.  MATES: gm_batch_set_mates
+// is on (t.mate is there) - instances of their own as well, with a head of their own: a flag of up to four digits does not fit
+// hd[0, 4), nor a contig name in RNEXT the seven constant bytes.  Its layout: [0, 16) "\t<flag>\t" (a read without a record:
+// "\t<flag>\t*\t0\t0\t*"), [16, 50) "\t<chr_pos>\t<mapq>\t", [50, 52) "\t" and "=" / "*" unless RNEXT is a contig's name, [56, 80)
+// "\t<PNEXT>\t<TLEN>\t"; the four lengths in [124, 128)
+template <bool TAGS, bool MATES>
 __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t) {
-    __shared__ char s_head[4][64];
+    constexpr uint32_t HD = MATES ? 128u : 64u, H2_AT = MATES ? 16u : 4u, LEN1_AT = MATES ? 124u : 62u, LEN2_AT = MATES ? 125u : 63u;
+    __shared__ char s_head[4][HD];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     char* const hd = s_head[wv];
     for (unsigned long long base = (unsigned long long)blockIdx.x * 4ull; base < t.n_rows; base += (unsigned long long)gridDim.x * 4ull) {
@@ -757,12 +762,20 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
         const bool unm = k < t.n_rows && !is_rec && urd != 0xFFFFFFFFu;        // a read without a record: its flag-4 row
         const bool live = is_rec || unm;
         GmDevSamRec r = {};
+        GmDevMateRow mf = {};
+        if constexpr (MATES) if (live) mf = t.mate[k];
         if (unm) {
             r.read = urd;
-            if (lane == 0) {                                  // [0, 17) the nine constant columns
-                const char c[GO_UNMAPPED_HEAD + 1] = "\t4\t*\t0\t0\t*\t*\t0\t0\t";
-                for (uint32_t i = 0; i < GO_UNMAPPED_HEAD; ++i) hd[i] = c[i];
-                hd[62] = (char)GO_UNMAPPED_HEAD; hd[63] = 0;
+            if (lane == 0) {
+                if constexpr (MATES) {                        // "\t<flag>\t*\t0\t0\t*": the mate columns follow as on every row
+                    char* w = hd;
+                    *w++ = '\t'; w = go_put_u64(w, mf.flag); *w++ = '\t'; *w++ = '*'; *w++ = '\t'; *w++ = '0'; *w++ = '\t'; *w++ = '0'; *w++ = '\t'; *w++ = '*';
+                    hd[LEN1_AT] = (char)(w - hd); hd[LEN2_AT] = 0;
+                } else {                                      // [0, 17) the nine constant columns
+                    const char c[GO_UNMAPPED_HEAD + 1] = "\t4\t*\t0\t0\t*\t*\t0\t0\t";
+                    for (uint32_t i = 0; i < GO_UNMAPPED_HEAD; ++i) hd[i] = c[i];
+                    hd[LEN1_AT] = (char)GO_UNMAPPED_HEAD; hd[LEN2_AT] = 0;
+                }
             }
         }
         if (is_rec) {
@@ -770,14 +783,24 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
             if (lane == 0) {                                  // the short head: [0, 4) "\t<flag>\t", [4, ..) "\t<chr_pos>\t<mapq>\t", [48, 55) the constant columns
                 char* w = hd;
                 *w++ = '\t';
-                if (r.strand) { *w++ = '1'; *w++ = '6'; } else *w++ = '0';
+                if constexpr (MATES) w = go_put_u64(w, mf.flag);
+                else { if (r.strand) { *w++ = '1'; *w++ = '6'; } else *w++ = '0'; }
                 *w++ = '\t';
-                hd[62] = (char)(w - hd);
-                w = hd + 4;
+                hd[LEN1_AT] = (char)(w - hd);
+                w = hd + H2_AT;
                 *w++ = '\t'; w = go_put_u64(w, r.chr_pos); *w++ = '\t'; w = go_put_int(w, r.mapq); *w++ = '\t';      // <= 1 + 20 + 1 + 11 + 1 = 34
-                hd[63] = (char)(w - (hd + 4));
-                hd[48] = '\t'; hd[49] = '*'; hd[50] = '\t'; hd[51] = '0'; hd[52] = '\t'; hd[53] = '0'; hd[54] = '\t';
+                hd[LEN2_AT] = (char)(w - (hd + H2_AT));
+                if constexpr (!MATES) { hd[48] = '\t'; hd[49] = '*'; hd[50] = '\t'; hd[51] = '0'; hd[52] = '\t'; hd[53] = '0'; hd[54] = '\t'; }
             }
+        }
+        // RNEXT is "=" on the row's own contig, "*" without a mate primary, else that contig's name (from the name pool, like RNAME)
+        const bool rn_named = MATES && live && mf.rnext >= 0 && !(is_rec && (uint32_t)mf.rnext == r.contig);
+        if constexpr (MATES) if (live && lane == 0) {
+            hd[50] = '\t'; hd[51] = mf.rnext < 0 ? '*' : '=';
+            hd[126] = rn_named ? 1 : 2;
+            char* w = hd + 56;
+            *w++ = '\t'; w = go_put_u64(w, mf.pnext); *w++ = '\t'; w = go_put_int(w, mf.tlen); *w++ = '\t';              // <= 1 + 10 + 1 + 11 + 1 = 24
+            hd[127] = (char)(w - (hd + 56));
         }
         __syncthreads();
         if (live) {
@@ -793,7 +816,7 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
             const uint32_t c0 = unm ? 0u : t.cname_off[r.contig], cl = unm ? 0u : t.cname_off[r.contig + 1] - c0;
             const unsigned long long q0 = t.qtail_off ? t.qtail_off[rd] : 0ull;
             const uint32_t TL = t.qtail_off ? (uint32_t)(t.qtail_off[rd + 1] - q0) : 0u, QL = L + TL;
-            const uint32_t h1 = (uint8_t)hd[62], h2 = (uint8_t)hd[63];
+            const uint32_t h1 = (uint8_t)hd[LEN1_AT], h2 = (uint8_t)hd[LEN2_AT];
             const bool neg = r.strand != 0;
             const bool star = unm && L == 0u;                    // a read of length 0 without a record: SEQ and QUAL are "*"
             // every store stays inside the row the scan gave this record, whatever the lengths say
@@ -803,7 +826,7 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
             o += h1;
             for (uint32_t i = lane; i < cl; i += 64u) if (o + i < end) out[o + i] = t.cnames[c0 + i];
             o += cl;
-            for (uint32_t i = lane; i < h2; i += 64u) if (o + i < end) out[o + i] = hd[4 + i];
+            for (uint32_t i = lane; i < h2; i += 64u) if (o + i < end) out[o + i] = hd[H2_AT + i];
             o += h2;
             const char* cg = t.pool + r.cigar_off;
             const bool rev = neg && !t.cigar_forward;            // (GM_CIGAR_FORWARD: gout == gl, the bytes in pool order on either strand)
@@ -819,7 +842,18 @@ __global__ void __launch_bounds__(256) k_out_text_rows(GmDevBatch b, GmDevText t
                 }
             }
             o += gout;
-            if (!unm) {
+            if constexpr (MATES) {
+                const uint32_t ha = (uint8_t)hd[126], hb = (uint8_t)hd[127];
+                if (lane < ha && o + lane < end) out[o + lane] = hd[50 + lane];
+                o += ha;
+                if (rn_named) {
+                    const uint32_t m0 = t.cname_off[mf.rnext], ml = t.cname_off[mf.rnext + 1] - m0;
+                    for (uint32_t i = lane; i < ml; i += 64u) if (o + i < end) out[o + i] = t.cnames[m0 + i];
+                    o += ml;
+                }
+                if (lane < hb && o + lane < end) out[o + lane] = hd[56 + lane];
+                o += hb;
+            } else if (!unm) {
                 for (uint32_t i = lane; i < 7u; i += 64u) if (o + i < end) out[o + i] = hd[48 + i];
                 o += 7u;
             }
@@ -1013,7 +1047,8 @@ int gmk_out_text_rows(const GmDevBatch& b, const GmDevText& t, void* stream) {
     // one resident round: as many workgroups of 4 waves as the device holds at once
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    void (*const kern)(GmDevBatch, GmDevText) = t.md ? k_out_text_rows<true> : k_out_text_rows<false>;
+    void (*const kern)(GmDevBatch, GmDevText) = t.mate ? (t.md ? k_out_text_rows<true, true> : k_out_text_rows<false, true>)
+                                                       : (t.md ? k_out_text_rows<true, false> : k_out_text_rows<false, false>);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
     const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>((t.n_rows + 3) / 4, (uint64_t)cus * (uint64_t)per_cu));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, S_(stream), b, t);

@@ -73,6 +73,10 @@ struct Options {
     bool sam_cigar_set = false, sam_cigar_forward = false;      // --sam_cigar=gnumap|forward: a minus-strand row's CIGAR as the reference prints it, or in reference order (gm_batch_set_cigar_order; implies --sam_text=device)
     bool bam_index = false;       // --bam_index: <out>.bam.bai beside a sorted <out>.bam, built on the GPU from what the sorter holds (gm_sam_sorter_bai)
     bool fasta = false;             // the read file starts with '>' (SeqReader::find_type): FASTA records, gm_batch_set_read_format(GM_READS_FASTA)
+    std::string mates;              // --mates=FILE2: the second mates' file; the positional file holds the first mates (gm_batch_set_mates; implies --sam_text=device)
+    bool interleaved = false;       // --interleaved: the positional file holds the mates in alternation
+    uint32_t min_insert = 0, max_insert = 500; const char* insert_opt = nullptr;      // --min_insert / --max_insert (insert_opt: the one that was given)
+    bool paired() const { return interleaved || !mates.empty(); }
 };
 
 [[noreturn]] static void usage(int rc, const char* msg) {
@@ -143,7 +147,19 @@ struct Options {
             "                               (not with --sam_text=host or -A/--adaptor)\n"
             "      --sam_cigar=gnumap|forward  the CIGAR of a minus-strand row: gnumap (default) = its tokens last to first, as GNUMAP prints it;\n"
             "                               forward = in reference order, as the alignment was computed - the order POS and SEQ of the row are in.\n"
-            "                               Implies --sam_text=device (not with --sam_text=host)\n");
+            "                               Implies --sam_text=device (not with --sam_text=host)\n"
+            "      --mates=FILE2            paired-end reads: FILE2 holds the second mates, <file_to_parse> the first, in the same order and format.\n"
+            "                               Each mate is mapped as a single read; the pair is resolved on the GPU: among the places of the two\n"
+            "                               mates the forward/reverse combination on one contig with min_insert <= insert <= max_insert and the\n"
+            "                               largest product of posteriors gives the primary rows (flag 0x2), the other rows are secondary (0x100);\n"
+            "                               every row carries 0x1, 0x40 / 0x80, 0x20 / 0x8, RNEXT, PNEXT and TLEN.  Names are cut at the first blank,\n"
+            "                               a trailing /1 and /2 is dropped, and two files that are not in step end the run.  The files are read in\n"
+            "                               file order by one thread and a malformed record ends the run.  Implies --sam_text=device (not with\n"
+            "                               --sam_text=host or --read_text=device); --batch=N must be even\n"
+            "      --interleaved            the same for one file that holds first and second mates in alternation\n"
+            "      --min_insert=N           smallest (default 0) and\n"
+            "      --max_insert=N           largest (default 500) insert of a proper pair, both inclusive: from the plus-strand mate's POS to the\n"
+            "                               last reference base of the minus-strand mate\n");
     exit(rc);
 }
 
@@ -233,6 +249,14 @@ static void parse_args(int argc, char** argv, Options& o) {
                 if (end == s + 11 || *end || k < 1 || k > 64) { fprintf(stderr, "Error: --sam_shards takes 1 .. 64, not: %s\n", s + 11); exit(1); }
                 o.sam_shards = (int)k;
             }
+            else if (starts(s, "mates=")) o.mates = s + 6;
+            else if (!strcmp(s, "interleaved")) o.interleaved = true;
+            else if (starts(s, "min_insert=") || starts(s, "max_insert=")) {
+                char* end = nullptr;
+                const unsigned long long v = strtoull(s + 11, &end, 10);
+                if (end == s + 11 || *end || s[11] == '-' || v > 0xFFFFFFFFull) { fprintf(stderr, "Error: --%.10s takes a number of bases, not: %s\n", s, s + 11); exit(1); }
+                (s[1] == 'i' ? o.min_insert : o.max_insert) = (uint32_t)v; o.insert_opt = s[1] == 'i' ? "--min_insert" : "--max_insert";
+            }
             else if (!strcmp(s, "help")) usage(0, "");
             else { fprintf(stderr, "No matching arg in: %s\n", a); exit(1); }
             continue;
@@ -312,7 +336,18 @@ static void parse_args(int argc, char** argv, Options& o) {
         if (o.sam_text_host_set) { fprintf(stderr, "Error: --sam_unmapped writes its rows on the GPU: it cannot be combined with --sam_text=host\n"); exit(1); }
         o.sam_text_device = true;
     }
+    if (!o.mates.empty() && o.interleaved) { fprintf(stderr, "Error: --mates=FILE2 names a second file and --interleaved says there is none: give one of them\n"); exit(1); }
+    if (o.insert_opt && !o.paired()) { fprintf(stderr, "Error: %s sets the insert limits of paired reads: give --mates=FILE2 or --interleaved with it\n", o.insert_opt); exit(1); }
+    if (o.paired()) {                                        // refused before a device is opened or a file is written
+        const char* flag = o.interleaved ? "--interleaved" : "--mates";
+        if (o.min_insert > o.max_insert) { fprintf(stderr, "Error: --min_insert=%u is above --max_insert=%u\n", o.min_insert, o.max_insert); exit(1); }
+        if (o.sam_text_host_set) { fprintf(stderr, "Error: %s resolves the pairs where the GPU writes the rows: it cannot be combined with --sam_text=host\n", flag); exit(1); }
+        if (o.read_text_device) { fprintf(stderr, "Error: %s reads its files in file order on the host: it cannot be combined with --read_text=device\n", flag); exit(1); }
+        if (o.batch_set && (o.batch & 1u)) { fprintf(stderr, "Error: %s needs blocks of whole pairs: --batch=%u is odd\n", flag, o.batch); exit(1); }
+        o.sam_text_device = true;
+    }
     if (o.batch < 1) o.batch = 1;
+    if (o.paired() && (o.batch & 1u)) ++o.batch;            // (--chunk_reads: a block of whole pairs)
     if (o.workers < 1) o.workers = 1;
     if (o.fmt_threads < 1) o.fmt_threads = (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
 }
@@ -391,6 +426,7 @@ struct Block {
     // the text from text_lo on (page-locked; only filled for the host formatter)
     bool text_dev = false; PinVec<gm_text_rec> trecs;
     bool failed = false;
+    std::unique_ptr<Block> mate_src[2];     // --mates=FILE2: the records of the two files this block's views alternate over (a FASTA record's joined lines live there)
     // what the three parsers share: no record, one more record (`head` = its name line with the '@' or '>'), the row stride behind the last
     void reset() { n = 0; maxlen = 0; name.clear(); seq.clear(); qual.clear(); name_len.clear(); qual_len.clear(); len.clear(); fa_text.clear(); }
     void append(const char* head, size_t head_len, const char* sq, size_t sl, const char* ql, size_t qll) {
@@ -807,6 +843,7 @@ struct Worker {
     PinVec<gm_match> matches; PinVec<gm_pos> positions;
     uint64_t n_reads = 0, n_matched = 0, n_records = 0;
     uint64_t n_unmapped = 0;                // --sam_unmapped: rows of reads without a record, among n_records (or among the sorter's rows)
+    gm_mate_stats mates{};                  // --mates / --interleaved: the pair counters of this worker's blocks
     double t_pack = 0, t_map = 0, t_out = 0, t_scan = 0;
     gm_sam_sorter* sorter = nullptr;       // --sam_sort=coordinate: where the blocks' rows go instead of a host buffer
     TextPool* stage_pool = nullptr;         // --read_text=device: page-locked buffers a block's FASTQ text is copied into for the upload
@@ -953,6 +990,12 @@ static int process_block(Worker& w, const Options& o, const char* base, Block& b
     w.t_pack += secs_between(c0, c1); w.t_map += secs_between(c1, c2); w.t_out += secs_since(c2);
     w.n_reads += n; w.n_records += n_recs;                  // (sorted: no records here, main takes their number from the sorter)
     if (o.sam_unmapped) { uint64_t u = 0; if (gm_batch_unmapped_rows(w.batch, &u) == GM_OK) w.n_unmapped += u; }
+    if (o.paired()) {
+        gm_mate_stats ms;
+        if (gm_batch_mate_stats(w.batch, &ms) == GM_OK) {
+            w.mates.pairs += ms.pairs; w.mates.both_mapped += ms.both_mapped; w.mates.proper += ms.proper; w.mates.one_mapped += ms.one_mapped; w.mates.none_mapped += ms.none_mapped;
+        }
+    }
     for (uint32_t i = 0; i < n; ++i) w.n_matched += (w.status[i] == GM_READ_OK || w.status[i] == GM_READ_TOO_MANY);
     return GM_OK;
 }
@@ -961,7 +1004,7 @@ static int process_block(Worker& w, const Options& o, const char* base, Block& b
 // without -h) is mapped as two halves, recursively; the halves' records are put back together in read order
 static int process_block_split(Worker& w, const Options& o, const char* base, Block& b, int depth) {
     int rc = process_block(w, o, base, b);
-    if (rc != GM_E_BATCH_TOO_LARGE || b.n < 2 || depth > 20) return rc;
+    if (rc != GM_E_BATCH_TOO_LARGE || b.n < (o.paired() ? 4u : 2u) || depth > 20) return rc;
     if (b.text_dev) {                                       // a text block that is too large: the host parser cuts the same records, and the halves go the host's way
         size_t cur = b.text_lo, bad_at = 0; bool stop = false, too_long = false;
         const uint32_t n_dev = b.n;
@@ -969,7 +1012,7 @@ static int process_block_split(Worker& w, const Options& o, const char* base, Bl
         b.text_dev = false;
         if (b.n != n_dev) { fprintf(stderr, "ERROR: the host parser finds %u reads where the device found %u\n", b.n, n_dev); return GM_E_ARG; }
     }
-    const uint32_t half = b.n / 2;
+    const uint32_t half = o.paired() ? (b.n / 2) & ~1u : b.n / 2;      // (paired: a pair never straddles the halves)
     uint64_t total = 0; size_t pool_len = 0;
     std::vector<gm_sam_rec> recs; std::vector<char> pool, text;
     for (int part = 0; part < 2; ++part) {
@@ -1017,6 +1060,8 @@ struct Run {
     std::string cl;                                 // the command line, for @PG (Driver.cpp:1032-1039)
     Clock::time_point t0, t_pipe0;
     FastqScanner fq; bool reads_open = false; char fasta_qual[256];
+    FastqScanner fq2;                               // --mates=FILE2: the second mates' file, read in step with fq
+    bool next_mates(Block& b, uint32_t max_reads, bool* too_long, bool* bad);
     std::vector<gm_index*> gpu_ix; gm_index_info info;
     std::vector<Worker> workers;
     gm_sam_sorter* sorter = nullptr; uint64_t sorted_rows = 0;
@@ -1028,7 +1073,7 @@ struct Run {
     double t_index = 0, t_scan = 0, t_fmt = 0, t_write = 0;     // t_scan: the scanner thread's; t_fmt, t_write: summed under their locks
     std::mutex fmt_mu, tw_mu;                       // (t_write is summed by several writers with --sam_shards)
     uint64_t seq_base = 0;                          // --sam_sort: blocks handed out by the passes before this one
-    bool file_order() const { return o.batch_set || o.p.illumina; }
+    bool file_order() const { return o.batch_set || o.p.illumina || o.paired(); }       // (paired: byte ranges cannot keep two files, or an even count, in step)
 };
 
 static bool write_all(int fd, const char* p, size_t n) {
@@ -1038,6 +1083,49 @@ static bool write_all(int fd, const char* p, size_t n) {
 static bool pwrite_all(int fd, const char* p, size_t n, uint64_t off) {
     while (n) { ssize_t k = ::pwrite(fd, p, n, (off_t)off); if (k <= 0) return false; p += k; n -= (size_t)k; off += (uint64_t)k; }
     return true;
+}
+
+// Paired input, one block of whole pairs in file order.  The records are cut strictly: the reference's recovery from a malformed record
+// skips lines and would lose the pairing, so such a record ends the run (*bad), and so do two files that end after different numbers
+// of reads and an interleaved file with an odd number.  --mates=FILE2: half the block from either file, the views alternating
+bool Run::next_mates(Block& b, uint32_t max_reads, bool* too_long, bool* bad) {
+    auto cut = [&](FastqScanner& f, Block& dst, uint32_t want, const std::string& fn) {
+        if (f.at >= f.size) { dst.reset(); dst.finish(); return; }
+        if (o.fasta) { FastqScanner::parse_range_fasta(f.base, f.at, f.size, dst, want, too_long, fasta_qual); return; }
+        bool stop = false; size_t bad_at = 0;
+        FastqScanner::parse_range(f.base, f.at, f.size, dst, want, &stop, &bad_at, too_long);
+        if (stop) {
+            const char* nm = f.base + bad_at; const char* e = (const char*)memchr(nm, '\n', f.size - bad_at);
+            fprintf(stderr, "ERROR: %s: malformed FASTQ record at byte %zu (%.*s): with paired reads there is no recovery, it would lose the pairing\n", fn.c_str(), bad_at,
+                    (int)std::min<size_t>(e ? (size_t)(e - nm) : f.size - bad_at, 200), nm);
+            *bad = true;
+        }
+    };
+    if (o.interleaved) {
+        cut(fq, b, max_reads, o.reads);
+        if (*bad || *too_long) return false;
+        if (b.n & 1u) { fprintf(stderr, "ERROR: %s: --interleaved and an odd number of reads: the last read has no mate\n", o.reads.c_str()); *bad = true; return false; }
+        return b.n > 0;
+    }
+    for (auto& m : b.mate_src) if (!m) m.reset(new Block());
+    Block& A = *b.mate_src[0]; Block& B = *b.mate_src[1];
+    cut(fq, A, max_reads / 2, o.reads);
+    if (!*bad && !*too_long) cut(fq2, B, max_reads / 2, o.mates);
+    if (*bad || *too_long) return false;
+    if (A.n != B.n) {
+        fprintf(stderr, "ERROR: %s and %s end after different numbers of reads (%s has more): the files are not the two halves of one paired run\n", o.reads.c_str(), o.mates.c_str(),
+                A.n > B.n ? o.reads.c_str() : o.mates.c_str());
+        *bad = true;
+        return false;
+    }
+    b.reset();
+    for (uint32_t i = 0; i < A.n; ++i)
+        for (Block* m : { &A, &B }) {
+            b.name.push_back(m->name[i]); b.name_len.push_back(m->name_len[i]); b.seq.push_back(m->seq[i]); b.len.push_back(m->len[i]);
+            b.qual.push_back(m->qual[i]); b.qual_len.push_back(m->qual_len[i]);
+        }
+    b.n = 2 * A.n; b.maxlen = std::max(A.maxlen, B.maxlen);
+    return b.finish();
 }
 
 // the read file's format from its first byte, as SeqReader::find_type (src/SeqReader.cpp:175-244) - and what a FASTA input rules out -
@@ -1062,6 +1150,14 @@ static int detect_read_format(Run& R) {
         fprintf(stderr, "ERROR: %s starts with neither '@' (FASTQ) nor '>' (FASTA): the _prb.txt and _int.txt read formats are not supported\n", o.reads.c_str());
         return 1;
     }
+    if (!o.mates.empty()) {                                 // the second file: there, and in the first one's format
+        if (!R.fq2.open(o.mates)) { fprintf(stderr, "ERROR: --mates: cannot open %s\n", o.mates.c_str()); return 1; }
+        if (R.fq2.size && R.fq2.base[0] != (o.fasta ? '>' : '@')) {
+            fprintf(stderr, "ERROR: --mates: %s is %s and %s is not: the two files of a paired run have one format\n", o.reads.c_str(), o.fasta ? "FASTA" : "FASTQ", o.mates.c_str());
+            return 1;
+        }
+        if (o.fasta && R.fq2.size && !fasta_check(R.fq2.base, R.fq2.size, o.mates.c_str())) return 1;
+    }
     return 0;
 }
 
@@ -1083,10 +1179,11 @@ static int open_devices(Run& R) {
         for (int k = 0; k < o.workers; ++k) {
             Worker& w = R.workers[(size_t)g * (size_t)o.workers + (size_t)k];
             w.gpu = g; w.ix = ix; w.text_pool = &R.text_pool; w.stage_pool = &R.stage_pool; w.sorter = R.sorter;
-            if (gm_batch_create(w.ix, o.batch_set || o.p.illumina ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK ||
+            if (gm_batch_create(w.ix, R.file_order() ? o.batch : 16000000u, 2048, &w.batch) != GM_OK || gm_stream_create(w.ix, &w.stream) != GM_OK ||
                 gm_batch_set_adaptor(w.batch, o.adaptor.c_str()) != GM_OK || gm_batch_set_unmapped_rows(w.batch, o.sam_unmapped ? 1 : 0) != GM_OK ||
                 gm_batch_set_row_tags(w.batch, o.sam_md ? GM_ROW_TAG_MD : 0u) != GM_OK || gm_batch_set_cigar_order(w.batch, o.sam_cigar_forward ? GM_CIGAR_FORWARD : GM_CIGAR_GNUMAP) != GM_OK ||
-                gm_batch_set_read_format(w.batch, o.fasta ? GM_READS_FASTA : GM_READS_FASTQ) != GM_OK) return fail();
+                gm_batch_set_read_format(w.batch, o.fasta ? GM_READS_FASTA : GM_READS_FASTQ) != GM_OK ||
+                gm_batch_set_mates(w.batch, o.paired() ? 1 : 0, o.min_insert, o.max_insert) != GM_OK) return fail();
         }
     }
     gm_index_get_info(R.gpu_ix[0], &R.info);
@@ -1191,9 +1288,10 @@ struct Pass {
             b->lazy = false; b->text_dev = false;
             bool too_long = false;
             b->first_byte = fq.at;
-            const bool more = chunks ? fq.next_chunk(*b, o.batch) : fq.next(*b, o.batch, &too_long);
+            bool bad_pairs = false;
+            const bool more = chunks ? fq.next_chunk(*b, o.batch) : o.paired() ? R.next_mates(*b, o.batch, &too_long, &bad_pairs) : fq.next(*b, o.batch, &too_long);
             R.t_scan += secs_since(s0);
-            if (too_long) R.failed = 1;
+            if (too_long || bad_pairs) R.failed = 1;
             if (!more || R.failed) { free_q.push(b); break; }
             b->index = idx++; b->failed = false;
             b->sort_seq = (R.seq_base + b->index) << 21;
@@ -1444,6 +1542,13 @@ static void report(const Run& R, double t_pipe, double t_cov, double secs) {
             t.n_reads / std::max(t_pipe, 1e-9) / 1e6, t_cov);
     fprintf(stderr, "Finished: %lu reads, %lu matched, %lu SAM records, %.2f s total (%.2f s after the index was resident)\n", (unsigned long)t.n_reads,
             (unsigned long)t.n_matched, (unsigned long)t.n_records, secs, secs - R.t_index);
+    if (o.paired()) {
+        gm_mate_stats m{};
+        for (const Worker& w : R.workers) { m.pairs += w.mates.pairs; m.both_mapped += w.mates.both_mapped; m.proper += w.mates.proper; m.one_mapped += w.mates.one_mapped; m.none_mapped += w.mates.none_mapped; }
+        fprintf(stderr, "%s: %lu pairs: %lu with both mates mapped (%lu of them proper: forward/reverse on one contig, insert %u .. %u), %lu with one mate mapped, %lu with none\n",
+                o.interleaved ? "--interleaved" : "--mates", (unsigned long)m.pairs, (unsigned long)m.both_mapped, (unsigned long)m.proper, o.min_insert, o.max_insert,
+                (unsigned long)m.one_mapped, (unsigned long)m.none_mapped);
+    }
     if (o.sam_unmapped) {
         uint64_t n_unmapped = 0;
         for (const Worker& w : R.workers) n_unmapped += w.n_unmapped;

@@ -187,8 +187,9 @@ typedef struct {
 /* kernels of gm_map_batch_device, for the HIP-event timing of gm_batch_kernel_times.  GM_K_SEED has no launches when the seed
  * lookup runs inside the vote kernel (full SA, k-mer table as long as the seed, k-mers expected >= 4 times in the reference, no -h;
  * env GM_SEED_FUSED=0|1 overrides): its time is then part of GM_K_VOTE; the work counters are the same either way.
- * GM_K_MD_SIZES belongs to the row-producing output calls: the sizes pass of gm_batch_set_row_tags (no launches with the setting off) */
-enum { GM_K_PREP = 0, GM_K_SEED, GM_K_LOCATE, GM_K_VOTE, GM_K_VOTE_RETRY, GM_K_NW, GM_K_COMPACT, GM_K_MD_SIZES, GM_K_COUNT };
+ * GM_K_MD_SIZES belongs to the row-producing output calls: the sizes pass of gm_batch_set_row_tags (no launches with the setting off).
+ * GM_K_MATES belongs to every output call: the k_mate_* kernels of gm_batch_set_mates (no launches with the setting off) */
+enum { GM_K_PREP = 0, GM_K_SEED, GM_K_LOCATE, GM_K_VOTE, GM_K_VOTE_RETRY, GM_K_NW, GM_K_COMPACT, GM_K_MD_SIZES, GM_K_MATES, GM_K_COUNT };
 
 const char* gm_last_error(void);
 const char* gm_version(void);
@@ -365,6 +366,50 @@ int gm_batch_unmapped_rows(gm_batch*, uint64_t* n);
 enum { GM_CIGAR_GNUMAP = 0, GM_CIGAR_FORWARD = 1 };
 int gm_batch_set_row_tags(gm_batch*, uint32_t tags);
 int gm_batch_set_cigar_order(gm_batch*, int order);
+
+/* ---- paired-end reads: mate choice and mate fields on the device (a defined extension: the reference has no paired mode; gm_mates.hip) ----
+ * gm_batch_set_mates(b, 1, min_insert, max_insert): a per-batch setting, off by default, sticky, read by ALL SEVEN output calls from
+ * the next call on (the records form runs the step too, so that gm_batch_mate_rows has something to return).  With it off no byte and
+ * no launch changes.  The map step is not touched: each mate is mapped exactly as a single read.  With it on, reads 2i and 2i + 1 of
+ * a block are the first and the second mate of pair i, and the rule below is a function of the block's records alone - gm_sam_rec in
+ * record order, and the CIGAR pool.  GM_E_ARG at the output call for an odd n and for min_insert > max_insert.
+ *
+ * Span: the sum of the M and D runs of a record's CIGAR in the pool; 1 where that is 0 - "*" (the .bai's rule).  END = chr_pos + span - 1.
+ * Concordant: a record a of one mate and a record b of the other lie on one contig, their strands differ, and with f the plus-strand
+ *   record and r the minus-strand one  POS_f <= POS_r  and  min_insert <= END_r - POS_f + 1 <= max_insert  (forward/reverse layout
+ *   only, both limits inclusive).
+ * Primaries: if any concordant combination exists, the one with the largest a.post_prob * b.post_prob (ONE fp32 multiply), ties to
+ *   the smallest record index of the first mate, then of the second: those two records are the primaries and the pair is PROPER.
+ *   Otherwise each mate's primary is its record with the largest post_prob, the first one on ties.  A read without a record has none.
+ * Rows of a mapped read: flag = 0x1 | 0x40 (first mate) or 0x80 (second) | 0x10 (this row is on the minus strand) | 0x20 (the mate's
+ *   primary is on the minus strand) | 0x8 (the mate has no primary) | 0x2 (on the two primaries of a proper pair, and only there) |
+ *   0x100 (every row that is not its read's primary).  RNEXT "=" when the mate's primary is on this row's contig, else that contig's
+ *   name, "*" without a mate primary; PNEXT the mate primary's POS, or 0.  TLEN on primary rows whose mate's primary is on the same
+ *   contig: max(END) - min(POS) + 1, positive on the row with the smaller POS, negative on the other, on equal POS positive on the
+ *   first mate; 0 in every other case (secondary rows, another contig, no mate primary, a value beyond 2^31 - 1).
+ * Rows of a read without a record (only with gm_batch_set_unmapped_rows): RNAME "*" and POS 0 stay; flag 0x4 | 0x1 | 0x40 / 0x80,
+ *   plus 0x20 / 0x8 as above; RNEXT the mate primary's contig name or "*", PNEXT its POS or 0, TLEN 0; YU stays.
+ * QNAME: the name is cut at its first space or tab; then, if the first mate's name ends in "/1" and the second's in "/2", those two
+ *   bytes are dropped from both; the cuts to 1023 (text) / 254 (BAM) bytes apply after that.  If the two printed names of a pair
+ *   differ the output call fails with GM_E_ARG and gm_last_error() names the first such pair by index (nothing is deposited).  The
+ *   records form has no names and checks none.
+ * BAM: flag, next_refID (the contig index, this record's own for "=", -1 for "*"), next_pos = PNEXT - 1 and tlen from the same
+ *   fields; bin, refID and pos stay as they are; NM / MD follow as without mates.
+ *
+ * gm_batch_mate_rows: the fields of the last output call on the batch, one entry per row that call produced, in row order (with
+ * gm_batch_set_unmapped_rows that order includes the rows of reads without a record; for gm_output_batch: one per record).
+ * *n = the number of rows; GM_E_CAPACITY when that exceeds cap (nothing is written).  0 rows with the setting off.
+ * gm_batch_mate_stats: the pair counters of the last output call. */
+typedef struct {
+    uint32_t flag;
+    int32_t rnext;              /* contig index of the mate's primary; -1: none ("*").  "=" is rnext == the row's own contig */
+    uint32_t pnext;             /* 1-based POS of the mate's primary; 0: none */
+    int32_t tlen;
+} gm_mate_row;
+typedef struct { uint64_t pairs, both_mapped, proper, one_mapped, none_mapped; } gm_mate_stats;
+int gm_batch_set_mates(gm_batch*, int on, uint32_t min_insert, uint32_t max_insert);
+int gm_batch_mate_rows(gm_batch*, gm_mate_row* out, uint64_t cap, uint64_t* n);
+int gm_batch_mate_stats(gm_batch*, gm_mate_stats* out);
 
 /* ---- FASTQ text in: the reads cut into rows on the device ----
  * gm_batch_upload_text takes a byte range of FASTQ text as it stands in the file, uploads it verbatim and leaves the batch resident

@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--bam_index", action="store_true", help="two more timed runs: --sam_format=bam --sam_sort=coordinate, then the same with --bam_index (<out>.bam.bai)")
     ap.add_argument("--bam_lz77", action="store_true", help="three more timed runs: --sam_format=bam, the same with --bam_lz77, and --sam_format=bam --sam_sort=coordinate --bam_lz77 --bam_index")
     ap.add_argument("--sam_md", action="store_true", help="four more timed runs: --sam_text=device and --sam_format=bam, each without and with --sam_md --sam_cigar=forward")
+    ap.add_argument("--mates", action="store_true", help="paired reads (inserts around 300 bases) in two files, and four more timed runs: the two files concatenated and mapped "
+                                                         "unpaired, and --mates=, each as --sam_text=device and as --sam_format=bam --sam_sort=coordinate")
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     fa = os.path.join(a.dir, "g%g.fa" % a.mbp); fq = os.path.join(a.dir, "r%d.fq" % a.reads)
@@ -54,6 +56,40 @@ def main():
             rec[:, 11] = 10; rec[:, 12:12 + L] = acgt[c]; rec[:, 12 + L] = 10; rec[:, 13 + L] = ord("+"); rec[:, 14 + L] = 10
             rec[:, 15 + L:15 + 2 * L] = q; rec[:, 15 + 2 * L] = 10
             f.write(rec.tobytes())
+    def write_records(f, first, c, q):                           # m records "@r<9 digits>\n<bases>\n+\n<qualities>\n"
+        m = len(c)
+        rec = np.empty((m, 2 * L + 16), np.uint8)
+        names = np.char.zfill((np.arange(first, first + m)).astype(str), 9).astype("S9")
+        rec[:, 0] = ord("@"); rec[:, 1] = ord("r"); rec[:, 2:11] = np.frombuffer(names.tobytes(), np.uint8).reshape(m, 9)
+        rec[:, 11] = 10; rec[:, 12:12 + L] = acgt[c]; rec[:, 12 + L] = 10; rec[:, 13 + L] = ord("+"); rec[:, 14 + L] = 10
+        rec[:, 15 + L:15 + 2 * L] = q; rec[:, 15 + 2 * L] = 10
+        f.write(rec.tobytes())
+
+    fq1, fq2, fq12 = (os.path.join(a.dir, "p%d_%s.fq" % (n, k)) for k in ("1", "2", "12"))
+    if a.mates:
+        # n / 2 pairs: the plus-strand mate at a random place, the minus-strand mate ending `insert` bases on (normal around 300, sd 30,
+        # at least L); the first mate is the minus one in half of the pairs; 1 % substitutions.  fq12 = fq1 followed by fq2: the same
+        # reads for an unpaired run
+        with open(fq1, "wb") as f1, open(fq2, "wb") as f2:
+            for s in range(0, n // 2, 250_000):
+                m = min(250_000, n // 2 - s)
+                ins = np.clip(np.rint(rng.normal(300, 30, m)).astype(np.int64), L, 600)
+                pos = rng.integers(0, len(codes) - 700, m)
+                cf = codes[pos[:, None] + np.arange(L)[None, :]].astype(np.int64)
+                cr = 3 - codes[(pos + ins - L)[:, None] + np.arange(L)[None, :]].astype(np.int64)[:, ::-1]
+                cf = np.where(rng.random((m, L)) < 0.01, (cf + rng.integers(1, 4, (m, L))) % 4, cf)
+                cr = np.where(rng.random((m, L)) < 0.01, (cr + rng.integers(1, 4, (m, L))) % 4, cr)
+                swap = (rng.random(m) < 0.5)[:, None]
+                write_records(f1, s, np.where(swap, cr, cf), (rng.integers(20, 41, (m, L)) + 33).astype(np.uint8))
+                write_records(f2, s, np.where(swap, cf, cr), (rng.integers(20, 41, (m, L)) + 33).astype(np.uint8))
+        with open(fq12, "wb") as f:
+            for src in (fq1, fq2):
+                with open(src, "rb") as g:
+                    while True:
+                        buf = g.read(1 << 26)
+                        if not buf:
+                            break
+                        f.write(buf)
     exe = os.path.join(ROOT, "gnumap_amd", "bin", "gnumap")
     out = os.path.join(a.dir, "out")
     env = dict(os.environ)
@@ -66,6 +102,11 @@ def main():
     if a.sam_md:
         tags = " --sam_md --sam_cigar=forward"
         runs += [("map " + x, a.args + " " + x) for x in ("--sam_text=device", "--sam_text=device" + tags, "--sam_format=bam", "--sam_format=bam" + tags)]
+    reads_of = {}                                                # run -> its read file, where that is not fq
+    if a.mates:
+        for form in ("--sam_text=device", "--sam_format=bam --sam_sort=coordinate"):
+            runs.append(("map unpaired, both files " + form, a.args + " " + form)); reads_of[runs[-1][0]] = fq12
+            runs.append(("map --mates= " + form, a.args + " " + form + " --mates=" + fq2)); reads_of[runs[-1][0]] = fq1
     def shard_files():                                           # <out>.<k>.sam of a --sam_shards=K run
         return [f for f in glob.glob(glob.escape(out) + ".*.sam") if f[len(out) + 1:-4].isdigit()]
 
@@ -76,7 +117,7 @@ def main():
                 os.remove(f)
         t0 = time.time()
         with open(out + ".stderr", "w+") as log:                  # os.wait4: this child's own peak resident set
-            child = subprocess.Popen([exe, "-g", fa, "-o", out, "-v", "1"] + args.split() + [fq], stdout=subprocess.DEVNULL, stderr=log, env=env)
+            child = subprocess.Popen([exe, "-g", fa, "-o", out, "-v", "1"] + args.split() + [reads_of.get(run, fq)], stdout=subprocess.DEVNULL, stderr=log, env=env)
             _, status, usage = os.wait4(child.pid, 0)
             child.returncode = os.waitstatus_to_exitcode(status)
             dt = time.time() - t0
