@@ -117,6 +117,7 @@ SAM_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u8"), ("contig", "<u4"), ("chr_
                       ("a_score", "<f4"), ("post_prob", "<f4"), ("sim_matches", "<i4"), ("cigar_off", "<u4")], align=True)
 MATE_ROW_DTYPE = np.dtype([("flag", "<u4"), ("rnext", "<i4"), ("pnext", "<u4"), ("tlen", "<i4")])     # gm_mate_row
 MATE_STATS = ("pairs", "both_mapped", "proper", "one_mapped", "none_mapped")                          # gm_mate_stats, in its order
+ROW_UNMAPPED = 1 << 63                                                                                # a row source entry that names a read without a record
 SNP_DTYPE = np.dtype([("pos", "<u8"), ("contig", "<u4"), ("chr_pos", "<u8"), ("total", "<f4"), ("nuc", "<f4", (5,)), ("p_val", "<f8"), ("ref", "u1"),
                       ("alt1", "u1"), ("alt2", "u1"), ("diploid", "u1")], align=True)
 
@@ -126,7 +127,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_batch_upload", "gm_map_batch_device", "gm_batch_counters", "gm_batch_path", "gm_batch_pair_flagged", "gm_batch_set_profiling", "gm_batch_kernel_times", "gm_kernel_name",
            "gm_batch_raw_hits", "gm_stream_create", "gm_stream_destroy", "gm_host_alloc", "gm_host_free", "gm_map_batch", "gm_output_batch",
            "gm_output_batch_text", "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait", "gm_dev_fmt_g6", "gm_dev_fmt_e2", "gm_dev_scan_u32",
-           "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
+           "gm_dev_mate_resolve", "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
            "gm_coverage_device_ptr", "gm_coverage_add", "gm_coverage_download", "gm_coverage_allreduce", "gm_coverage_write_sgr", "gm_coverage_enable_nuc", "gm_coverage_nuc_device_ptr",
            "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls",
            "gm_coverage_write_sgr_device", "gm_coverage_write_gmp_device", "gm_coverage_text", "gm_coverage_text_stats",
@@ -194,6 +195,8 @@ def load_library():
     L.gm_dev_fmt_g6.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_fmt_e2.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_scan_u32.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p]
+    L.gm_dev_mate_resolve.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, u64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gm_dev_sa_interval.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
     L.gm_dev_nw_score.argtypes = [C.c_void_p, C.POINTER(gm_params), C.POINTER(gm_reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -480,6 +483,22 @@ class Index:
         out = np.zeros(n + 1, np.uint64)
         _chk(lib().gm_dev_scan_u32(self.h, v.ctypes.data, n, out.ctypes.data))
         return out
+
+    def dev_mate_resolve(self, recs, pool, n_reads, min_insert, max_insert, row_src=None):
+        """gm_dev_mate_resolve: the mate kernels of set_mates on records of the caller's.  recs: SAM_DTYPE in record order, pool: the
+        bytes their cigar_off point into (NUL-terminated strings), row_src: None (one row per record) or uint64 entries, a record
+        index or ROW_UNMAPPED | read.  dict(span uint32[n_recs], prim uint64[n_reads] (~0: none), proper uint8[n_reads / 2],
+        stats dict, rows MATE_ROW_DTYPE[n_rows])"""
+        recs = np.ascontiguousarray(recs, SAM_DTYPE); n = len(recs)
+        pool = np.frombuffer(bytes(pool), np.uint8)
+        src = None if row_src is None else np.ascontiguousarray(row_src, np.uint64)
+        n_rows = n if src is None else len(src)
+        span = np.zeros(max(n, 1), np.uint32); prim = np.zeros(max(int(n_reads), 1), np.uint64); proper = np.zeros(max(int(n_reads) // 2, 1), np.uint8)
+        st = np.zeros(5, np.uint64); rows = np.zeros(max(n_rows, 1), MATE_ROW_DTYPE)
+        _chk(lib().gm_dev_mate_resolve(self.h, recs.ctypes.data, n, pool.ctypes.data if len(pool) else None, len(pool), int(n_reads), int(min_insert), int(max_insert),
+                                       None if src is None else src.ctypes.data, n_rows, span.ctypes.data, prim.ctypes.data, proper.ctypes.data,
+                                       st.ctypes.data, rows.ctypes.data))
+        return dict(span=span[:n], prim=prim[:int(n_reads)], proper=proper[:int(n_reads) // 2], stats={k: int(x) for k, x in zip(MATE_STATS, st)}, rows=rows[:n_rows])
 
     # ---- coverage ----
     def coverage_reset(self, bin_size):

@@ -2590,6 +2590,70 @@ extern "C" int gm_dev_scan_u32(gm_index* ix, const uint32_t* in, uint64_t n, uin
     return rc;
 }
 
+// gmk_mate_resolve and gmk_mate_fields on records, a CIGAR pool and a row source of the caller's: the GmDevMates / GmDevText that
+// out_mates fills for a block, with nothing of a mapped batch behind them.  Everything a kernel would index with is checked here, on
+// the host, before anything is uploaded: a refused call launches nothing
+extern "C" int gm_dev_mate_resolve(gm_index* ix, const gm_sam_rec* recs, uint64_t n_recs, const char* cigar_pool, uint64_t cigar_bytes, uint32_t n_reads,
+                                   uint32_t min_insert, uint32_t max_insert, const uint64_t* row_src, uint64_t n_rows,
+                                   uint32_t* span, uint64_t* prim, uint8_t* proper, gm_mate_stats* stats, gm_mate_row* rows) {
+    if (!ix || !stats || (n_recs && (!recs || !cigar_pool || !span)) || (n_reads && (!prim || !proper))) { gm_set_error("gm_dev_mate_resolve: a NULL argument"); return GM_E_ARG; }
+    if (!row_src) n_rows = n_recs;
+    if (n_rows && !rows) { gm_set_error("gm_dev_mate_resolve: rows is NULL"); return GM_E_ARG; }
+    if (n_reads & 1u) { gm_set_error("gm_dev_mate_resolve: an odd number of reads (" + std::to_string(n_reads) + ")"); return GM_E_ARG; }
+    if (min_insert > max_insert) { gm_set_error("gm_dev_mate_resolve: min_insert " + std::to_string(min_insert) + " is above max_insert " + std::to_string(max_insert)); return GM_E_ARG; }
+    if (n_recs >= (1ull << 32) || n_rows >= (1ull << 32)) { gm_set_error("gm_dev_mate_resolve: fewer than 2^32 records and rows"); return GM_E_ARG; }
+    // k_mate_spans walks a CIGAR from cigar_off to its NUL: the pool ends in one, and every offset lies inside it
+    if (n_recs && (cigar_bytes == 0 || cigar_pool[cigar_bytes - 1] != 0)) { gm_set_error("gm_dev_mate_resolve: the CIGAR pool does not end in a NUL"); return GM_E_ARG; }
+    for (uint64_t k = 0; k < n_recs; ++k) {
+        if (recs[k].cigar_off >= cigar_bytes) { gm_set_error("gm_dev_mate_resolve: cigar_off of record " + std::to_string(k) + " lies outside the pool"); return GM_E_ARG; }
+        if (recs[k].read >= n_reads || (k && recs[k].read < recs[k - 1].read)) {
+            gm_set_error("gm_dev_mate_resolve: record " + std::to_string(k) + " is not in read order, or names no read of the block"); return GM_E_ARG;
+        }
+    }
+    if (ix->host_only) { gm_set_error("no usable HIP device (host-only index)"); return GM_E_NO_DEVICE; }
+    HIPCHK(hipSetDevice(ix->device));
+    DevBuf d_recs, d_pool, d_span, d_first, d_end, d_prim, d_proper, d_meta, d_src, d_rows;
+    int rc = GM_OK;
+    if (d_recs.ensure((size_t)n_recs * sizeof(GmDevSamRec) + 16) || d_pool.ensure((size_t)cigar_bytes + 16) || d_span.ensure((size_t)n_recs * 4 + 16) ||
+        d_first.ensure((size_t)n_reads * 8 + 16) || d_end.ensure((size_t)n_reads * 8 + 16) || d_prim.ensure((size_t)n_reads * 8 + 16) ||
+        d_proper.ensure((size_t)n_reads / 2 + 16) || d_meta.ensure(MT_META_N * 8) || d_src.ensure((size_t)n_rows * 8 + 16) ||
+        d_rows.ensure((size_t)n_rows * sizeof(GmDevMateRow) + 16)) rc = GM_E_NOMEM;
+    auto run = [&]() -> int {
+        if (n_recs) {
+            HIPCHK(hipMemcpy(d_recs.p, recs, (size_t)n_recs * sizeof(GmDevSamRec), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_pool.p, cigar_pool, (size_t)cigar_bytes, hipMemcpyHostToDevice));
+        }
+        if (row_src && n_rows) HIPCHK(hipMemcpy(d_src.p, row_src, (size_t)n_rows * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(d_span.p, 0xFF, (size_t)n_recs * 4 + 16));                // (a value the kernels do not write shows)
+        HIPCHK(hipMemset(d_prim.p, 0xEE, (size_t)n_reads * 8 + 16));
+        HIPCHK(hipMemset(d_proper.p, 0xEE, (size_t)n_reads / 2 + 16));
+        HIPCHK(hipMemset(d_rows.p, 0xEE, (size_t)n_rows * sizeof(GmDevMateRow) + 16));
+        GmDevMates m{};
+        m.recs = n_recs ? d_recs.as<GmDevSamRec>() : nullptr; m.n_recs = n_recs; m.pool = d_pool.as<char>(); m.n_reads = n_reads; m.min_insert = min_insert; m.max_insert = max_insert;
+        m.span = d_span.as<uint32_t>(); m.first = d_first.as<unsigned long long>(); m.end = d_end.as<unsigned long long>();
+        m.prim = d_prim.as<unsigned long long>(); m.proper = d_proper.as<uint8_t>(); m.meta = d_meta.as<unsigned long long>();
+        GmDevText t{};
+        t.recs = m.recs; t.n_recs = n_recs; t.n_rows = n_rows; t.n_reads = n_reads;
+        t.row_src = row_src ? d_src.as<unsigned long long>() : nullptr;
+        KCHK(gmk_mate_resolve(m, nullptr));
+        KCHK(gmk_mate_fields(m, t, d_rows.as<GmDevMateRow>(), nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        unsigned long long meta[MT_META_N] = { 0 };
+        HIPCHK(hipMemcpy(meta, d_meta.p, sizeof meta, hipMemcpyDeviceToHost));
+        *stats = { meta[MT_META_PAIRS], meta[MT_META_BOTH], meta[MT_META_PROPER], meta[MT_META_ONE], meta[MT_META_NONE] };
+        if (n_recs) HIPCHK(hipMemcpy(span, d_span.p, (size_t)n_recs * 4, hipMemcpyDeviceToHost));
+        if (n_reads) {
+            HIPCHK(hipMemcpy(prim, d_prim.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(proper, d_proper.p, (size_t)n_reads / 2, hipMemcpyDeviceToHost));
+        }
+        if (n_rows) HIPCHK(hipMemcpy(rows, d_rows.p, (size_t)n_rows * sizeof(gm_mate_row), hipMemcpyDeviceToHost));
+        return GM_OK;
+    };
+    if (rc == GM_OK) rc = run();
+    for (DevBuf* d : { &d_recs, &d_pool, &d_span, &d_first, &d_end, &d_prim, &d_proper, &d_meta, &d_src, &d_rows }) d->release();
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------------
 // enqueue / wait forms of the two batch calls: a caller thread hands a block to the batch's service thread and goes on with the next
 // block on another batch; uploads, device work and the fp64 passes of different batches overlap without one caller thread per batch.

@@ -42,29 +42,35 @@ __global__ void __launch_bounds__(256) k_mate_spans(GmDevMates m) {
     if (k + 1 == m.n_recs || m.recs[k + 1].read != rd) m.end[rd] = k + 1;
 }
 
-// is (prod, a, b) better than (prod0, a0, b0)?  The larger product; on a tie the smaller index of the first mate's record, then of
-// the second's.  An entry without a combination has prod -1 and both indices MT_NONE: it loses to every combination (a product of
-// two posteriors is never negative), and a NaN product never wins
+// x ranks above y: the larger number, and any number above a NaN (include/gnumap_hip.h: a NaN posterior or product ranks below every
+// number; two NaNs rank alike, and so do +0 and -0).  Neither above the other = a tie, which the index decides
+__device__ __forceinline__ bool mt_above(float x, float y) { return x > y || (x == x && y != y); }
+
+// is (prod, a, b) better than (prod0, a0, b0)?  The product that ranks above; on a tie the smaller index of the first mate's record,
+// then of the second's.  An entry without a combination has both indices MT_NONE: it loses to every combination, also to one whose
+// product is NaN
 __device__ __forceinline__ bool mt_better(float prod, uint32_t a, uint32_t b, float prod0, uint32_t a0, uint32_t b0) {
     if (a == MT_NONE) return false;
     if (a0 == MT_NONE) return true;
-    if (prod != prod0) return prod > prod0;
+    if (mt_above(prod, prod0)) return true;
+    if (mt_above(prod0, prod)) return false;
     return a != a0 ? a < a0 : b < b0;
 }
-// is record idx with posterior p a better single primary than (p0, idx0)?  The larger posterior, the first one on ties
+// is record idx with posterior p a better single primary than (p0, idx0)?  The posterior that ranks above, the first one on ties
 __device__ __forceinline__ bool mt_better1(float p, uint32_t idx, float p0, uint32_t idx0) {
     if (idx == MT_NONE) return false;
     if (idx0 == MT_NONE) return true;
-    if (p != p0) return p > p0;
+    if (mt_above(p, p0)) return true;
+    if (mt_above(p0, p)) return false;
     return idx < idx0;
 }
 
-// the record of [first, first + cnt) with the largest post_prob, the first on ties: every lane gets the answer (MT_NONE for cnt == 0)
+// the record of [first, first + cnt) whose post_prob ranks highest, the first on ties: every lane gets the answer (MT_NONE for cnt == 0)
 __device__ __forceinline__ uint32_t mt_best_single(const GmDevSamRec* recs, unsigned long long first, uint32_t cnt, uint32_t lane) {
     float p = 0.0f; uint32_t idx = MT_NONE;
     for (uint32_t i = lane; i < cnt; i += 64u) {
         const float q = recs[first + i].post_prob;
-        if (idx == MT_NONE || q > p) { p = q; idx = i; }
+        if (idx == MT_NONE || mt_above(q, p)) { p = q; idx = i; }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -76,7 +82,7 @@ __device__ __forceinline__ uint32_t mt_best_single(const GmDevSamRec* recs, unsi
 
 // One wavefront per pair, the workgroups (one wavefront each) stride over the pairs.  The first mate's records go across the 64 lanes
 // in trips of 64; the second mate's are staged through LDS MT_CHUNK at a time and every lane walks them in order, so a lane meets its
-// combinations in ascending (first, second) order and a strict `>` keeps the first of equals.  1000 x 1000 records are 16 trips
+// combinations in ascending (first, second) order and a strict mt_above keeps the first of equals.  1000 x 1000 records are 16 trips
 // of 4 chunks: 16 000 combinations per lane.
 __global__ void __launch_bounds__(64) k_mate_resolve(GmDevMates m) {
     __shared__ unsigned long long s_pos[MT_CHUNK], s_end[MT_CHUNK];
@@ -91,7 +97,7 @@ __global__ void __launch_bounds__(64) k_mate_resolve(GmDevMates m) {
         if (eb > m.n_recs) eb = m.n_recs;
         const uint32_t ca = ea > fa ? (uint32_t)std::min<unsigned long long>(ea - fa, 0xFFFFFFFEull) : 0u;
         const uint32_t cb = eb > fb ? (uint32_t)std::min<unsigned long long>(eb - fb, 0xFFFFFFFEull) : 0u;
-        float best = -1.0f; uint32_t ba = MT_NONE, bb = MT_NONE;
+        float best = 0.0f; uint32_t ba = MT_NONE, bb = MT_NONE;              // (best counts once ba is set)
         if (ca && cb) {
             for (uint32_t a0 = 0; a0 < ca; a0 += 64u) {
                 const uint32_t ai = a0 + lane;
@@ -118,7 +124,7 @@ __global__ void __launch_bounds__(64) k_mate_resolve(GmDevMates m) {
                             const unsigned long long ins = er - pf + 1ull;
                             if (ins < m.min_insert || ins > m.max_insert) continue;
                             const float prod = a_post * s_post[q];
-                            if (prod > best) { best = prod; ba = ai; bb = b0 + q; }       // (best starts at -1: below every product)
+                            if (ba == MT_NONE || mt_above(prod, best)) { best = prod; ba = ai; bb = b0 + q; }     // (a NaN product is a combination too)
                         }
                 }
             }

@@ -381,6 +381,10 @@ int gm_batch_set_cigar_order(gm_batch*, int order);
  * Primaries: if any concordant combination exists, the one with the largest a.post_prob * b.post_prob (ONE fp32 multiply), ties to
  *   the smallest record index of the first mate, then of the second: those two records are the primaries and the pair is PROPER.
  *   Otherwise each mate's primary is its record with the largest post_prob, the first one on ties.  A read without a record has none.
+ *   NaN: a NaN post_prob, and a NaN product, ranks below every number (a zero or a negative one included), and two NaNs rank alike.
+ *   So among records that are all NaN the first one is the primary, a NaN never displaces a number whichever comes first, and a
+ *   pair whose concordant combinations all have NaN products is still PROPER, with the first of them in (first mate, second mate)
+ *   order.  Being concordant does not look at post_prob at all.
  * Rows of a mapped read: flag = 0x1 | 0x40 (first mate) or 0x80 (second) | 0x10 (this row is on the minus strand) | 0x20 (the mate's
  *   primary is on the minus strand) | 0x8 (the mate has no primary) | 0x2 (on the two primaries of a proper pair, and only there) |
  *   0x100 (every row that is not its read's primary).  RNEXT "=" when the mate's primary is on this row's contig, else that contig's
@@ -403,7 +407,7 @@ int gm_batch_set_cigar_order(gm_batch*, int order);
 typedef struct {
     uint32_t flag;
     int32_t rnext;              /* contig index of the mate's primary; -1: none ("*").  "=" is rnext == the row's own contig */
-    uint32_t pnext;             /* 1-based POS of the mate's primary; 0: none */
+    uint32_t pnext;             /* 1-based POS of the mate's primary; 0: none (its low 32 bits: a contig is shorter than 2^32) */
     int32_t tlen;
 } gm_mate_row;
 typedef struct { uint64_t pairs, both_mapped, proper, one_mapped, none_mapped; } gm_mate_stats;
@@ -594,6 +598,16 @@ int gm_dev_fmt_e2(gm_index*, const double* v, uint32_t n, char* out /* n x 16 */
 /* the exclusive scan behind every offset array of the map and output steps, on values of the caller's: out[i] = in[0] + .. + in[i - 1]
  * in 64 bits, out[n] = the total.  n up to 2^32 */
 int gm_dev_scan_u32(gm_index*, const uint32_t* in, uint64_t n, uint64_t* out /* n + 1 */);
+/* the mate kernels of gm_batch_set_mates (k_mate_spans, k_mate_resolve, k_mate_fields) on inputs of the caller's, none from a mapped
+ * batch: n_recs records in record order (ascending `read`, every one below n_reads), a CIGAR pool of cigar_bytes bytes that ends in a
+ * NUL and that every cigar_off points into, and the limits.  row_src: n_rows 64-bit entries, a record index, or bit 63 set and a
+ * read of the block that has no record (the rows of gm_batch_set_unmapped_rows); NULL = one row per record, n_rows is not read.
+ * Out: span[n_recs], prim[n_reads] (a record index, ~0: none), proper[n_reads / 2], the counters, rows[n_rows] (a row that names
+ * neither a record nor a read comes back with flag 0). GM_E_ARG, before anything is uploaded or launched, for an odd n_reads, for
+ * min_insert > max_insert, for a cigar_off outside the pool or a pool without its last NUL, and for records out of read order */
+int gm_dev_mate_resolve(gm_index*, const gm_sam_rec* recs, uint64_t n_recs, const char* cigar_pool, uint64_t cigar_bytes, uint32_t n_reads,
+                        uint32_t min_insert, uint32_t max_insert, const uint64_t* row_src, uint64_t n_rows,
+                        uint32_t* span, uint64_t* prim, uint8_t* proper, gm_mate_stats* stats, gm_mate_row* rows);
 
 /* bin_seq::pairHMM (src/bin_seq.cpp:60-244) of read read_idx[k] in the orientation of strand[k] against the window at pos[k]:
  * out[k][max_len][5] floats (a, c, g, t, n per window position), max_len = gm_reads.stride */

@@ -50,7 +50,17 @@ def concordant(a, sa, b, sb, lo, hi):
     return lo <= (pr + sr - 1) - pf + 1 <= hi
 
 
+def above(x, y):
+    """x ranks above y: the larger number, and any number above a NaN; two NaNs rank alike (the header's NaN rule)"""
+    return bool(x > y) or bool(x == x and y != y)
+
+
 def resolve(recs, cigars, n, lo, hi):
+    with np.errstate(all="ignore"):                     # (a product of the test cases may underflow, or be inf * 0)
+        return _resolve(recs, cigars, n, lo, hi)
+
+
+def _resolve(recs, cigars, n, lo, hi):
     assert n % 2 == 0 and lo <= hi
     rng = _ranges(recs, n)
     sp = [span(c) for c in cigars]
@@ -58,25 +68,26 @@ def resolve(recs, cigars, n, lo, hi):
     prim, proper = [None] * n, [False] * (n // 2)
     for i in range(n // 2):
         A, B = rng[2 * i], rng[2 * i + 1]
-        best, pick = np.float32(-1), None
-        for a in A:                                     # ascending (first, second): a strict > keeps the first of equals
+        best, pick = None, None
+        for a in A:                                     # ascending (first, second): a strict "above" keeps the first of equals
             for b in B:
                 if concordant(recs[a], sp[a], recs[b], sp[b], lo, hi):
                     prod = post[a] * post[b]            # one fp32 multiply
-                    if prod > best:
+                    if pick is None or above(prod, best):
                         best, pick = prod, (a, b)
         if pick:
             prim[2 * i], prim[2 * i + 1], proper[i] = pick[0], pick[1], True
             continue
         for rd, R in ((2 * i, A), (2 * i + 1, B)):
             for k in R:
-                if prim[rd] is None or post[k] > post[prim[rd]]:
+                if prim[rd] is None or above(post[k], post[prim[rd]]):
                     prim[rd] = k
     return prim, proper
 
 
-def row_fields(recs, cigars, n, lo, hi, rows=None):
-    prim, proper = resolve(recs, cigars, n, lo, hi)
+def row_fields(recs, cigars, n, lo, hi, rows=None, resolved=None):
+    """resolved: resolve()'s answer for the same arguments, where the caller has it already"""
+    prim, proper = resolved if resolved is not None else resolve(recs, cigars, n, lo, hi)
     sp = [span(c) for c in cigars]
     if rows is None:
         rows = [("r", k) for k in range(len(recs))]
@@ -91,7 +102,7 @@ def row_fields(recs, cigars, n, lo, hi, rows=None):
         else:
             m = recs[pm]
             flag |= 0x20 if m["strand"] else 0
-            rnext, pnext = int(m["contig"]), int(m["chr_pos"])
+            rnext, pnext = int(m["contig"]), int(m["chr_pos"]) & 0xFFFFFFFF      # gm_mate_row.pnext has 32 bits (no index has a longer POS)
         if kind == "u":
             flag |= 0x4
         else:
@@ -112,9 +123,9 @@ def row_fields(recs, cigars, n, lo, hi, rows=None):
     return out
 
 
-def stats(recs, cigars, n, lo, hi):
+def stats(recs, cigars, n, lo, hi, resolved=None):
     rng = _ranges(recs, n)
-    _, proper = resolve(recs, cigars, n, lo, hi)
+    _, proper = resolved if resolved is not None else resolve(recs, cigars, n, lo, hi)
     have = [len(r) > 0 for r in rng]
     pairs = n // 2
     both = sum(have[2 * i] and have[2 * i + 1] for i in range(pairs))

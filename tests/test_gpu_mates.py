@@ -5,7 +5,9 @@ elsewhere) and tests/mates_model.py: with the setting on, every row is the mates
 the model, which runs on the records Batch.output gives for the same hits.  Every comparison is of bytes, for equality, and no row is
 left out.  The world is tests/mates_fixture.py (110 pairs, built once per module); its self_check asserts from the mates-off records that
 every situation it exists for is there - among them the repeat pair whose concordant place is record 67 of 70, which a choice without
-the mate (record 0) gets wrong."""
+the mate (record 0) gets wrong.  Two more worlds have a test each: tests/mates_repeat2_fixture.py (both mates inside a repeat, 70 x 70
+records) and tests/wide_fixture.py as one block of 85 pairs (mate columns of nine and ten characters).  The resolver alone, at sizes and
+ties no mapped block gives it, is tests/test_gpu_mate_resolve.py."""
 import os
 import struct
 import subprocess
@@ -417,6 +419,90 @@ def test_insert_limits_are_inclusive(env):
     assert rows == r.want_rows(lo=LO - 1, hi=HI + 1)
     flags = {int(k): int(x.split(b"\t")[1]) for x, k in zip(rows, r.recs["read"])}
     assert all(flags[2 * w.pair_of(k)[0]] & 0x2 for k in ("ins_max", "ins_over", "ins_min", "ins_under"))
+
+
+# ---- 4b. two more worlds: both mates inside a repeat, and columns of nine and ten characters --------------------------------------
+def test_two_sided_repeat_70_x_70(tmp_path):
+    """tests/mates_repeat2_fixture.py: both mates have 70 records, 70 of the 4900 combinations are concordant and all have one product,
+    so the primaries are the first records of both mates - the tie goes to the smallest index of the first mate, then of the second"""
+    import mates_repeat2_fixture as r2
+    w = r2.World(tmp_path, g.index_build)
+    ix = g.Index(w.fa, device=0, flags=g.GM_INDEX_FULL_SA)
+    r = Run(ix, g.Params(), w.reads)
+    lo, hi = r2.MIN_INSERT, r2.MAX_INSERT
+    try:
+        assert r2.self_check(w, r.recs, r.cigars) == len(r.recs) == 422         # from the mates-off records
+        off_bam = r.bam()
+        r.on(lo, hi)
+        try:
+            rows, _ = r.text()
+            fields = [tuple(int(v) for v in x) for x in r.batch.mate_rows()]
+            stats = r.batch.mate_stats()
+            got_bam = r.bam()
+        finally:
+            r.off()
+        assert rows == r.want_rows(lo=lo, hi=hi) and fields == r.fields(lo=lo, hi=hi) and got_bam == r.want_bam(off_bam, lo=lo, hi=hi)
+        assert stats == mm.stats(r.recs, r.cigars, r.n, lo, hi) == dict(pairs=4, both_mapped=4, proper=4, one_mapped=0, none_mapped=0)
+        for i in range(3):
+            mine = [(k, f) for k, f in enumerate(fields) if int(r.recs["read"][k]) >> 1 == i]
+            assert len(mine) == 140 and [k - mine[0][0] for k, f in mine if not f[0] & 0x100] == [0, 70]       # the first record of either mate
+            assert all(f[0] & 0x2 for k, f in mine if not f[0] & 0x100) and all(f[3] == 0 for k, f in mine if f[0] & 0x100)
+            assert sorted(f[3] for k, f in mine if not f[0] & 0x100) == [-300, 300]
+    finally:
+        r.destroy()
+        ix.close()
+
+
+@pytest.fixture(scope="module")
+def wide(tmp_path_factory):
+    """the world of tests/wide_fixture.py (a 100 Mbp contig and 41 short ones), its 170 reads as ONE block of 85 pairs with equal names"""
+    import wide_fixture as wf
+    w = wf.World(tmp_path_factory.mktemp("mates_wide"), g.index_build)
+    ix = g.Index(w.fa, device=0, flags=g.GM_INDEX_FULL_SA)
+    assert len(w.reads) == 170
+    run = Run(ix, g.Params(**wf.KW), [(b"wide:%d" % (i >> 1), r.seq, r.qual) for i, r in enumerate(w.reads)])
+    yield run
+    run.destroy()
+    ix.close()
+
+
+def test_wide_columns(wide):
+    """PNEXT and TLEN of nine and ten characters, RNEXT a contig's name: k_mate_row_len's digit counts and the row kernels' mate columns
+    where tests/mates_fixture.py's 40 000-base contigs never take them.  Every pair of records on one contig with different strands and
+    POS_f <= POS_r is concordant under [0, 2^32 - 1]"""
+    r = wide
+    lo, hi = 0, 0xFFFFFFFF
+    assert len(r.cnames) == 42 and len(r.recs) == 154
+    want = r.want_rows(lo=lo, hi=hi)
+    cols = [x.split(b"\t") for x in want]
+    assert any(len(c[7]) == 9 for c in cols)                                                      # PNEXT of nine digits
+    assert any(len(c[8]) >= 8 and not c[8].startswith(b"-") for c in cols) and any(len(c[8]) >= 9 and c[8].startswith(b"-") for c in cols)
+    named = {c[6] for c in cols} - {b"=", b"*"}
+    assert named and named <= {n.encode() for n in r.cnames}                                      # RNEXT that is a contig's name
+    assert any(c[6] == b"=" for c in cols) and any(int(c[1]) & 0x2 for c in cols)
+    off_bam = r.bam()
+    r.batch.set_unmapped_rows(True)
+    try:
+        off_bam_un = r.bam()
+    finally:
+        r.batch.set_unmapped_rows(False)
+    r.on(lo, hi)
+    try:
+        rows, off = r.text()
+        got_bam = r.bam()
+        r.batch.set_unmapped_rows(True)
+        try:
+            rows_un, _ = r.text()
+            got_bam_un = r.bam()
+        finally:
+            r.batch.set_unmapped_rows(False)
+    finally:
+        r.off()
+    assert rows == want and [int(x) for x in off] == [0] + list(np.cumsum([len(x) for x in want]))
+    want_un = r.want_rows(unmapped=True, lo=lo, hi=hi)
+    assert rows_un == want_un and len(want_un) == 170 and any(int(x.split(b"\t")[1]) & 0x4 and len(x.split(b"\t")[7]) >= 8 for x in want_un)
+    assert got_bam == r.want_bam(off_bam, lo=lo, hi=hi)
+    assert got_bam_un == r.want_bam(off_bam_un, unmapped=True, lo=lo, hi=hi)
 
 
 # ---- 5. refusals -----------------------------------------------------------------------------------------------------------------
