@@ -127,7 +127,7 @@ EXPORTS = ["gm_last_error", "gm_version", "gm_set_option", "gm_selftest_pass_par
            "gm_batch_upload", "gm_map_batch_device", "gm_batch_counters", "gm_batch_path", "gm_batch_pair_flagged", "gm_batch_set_profiling", "gm_batch_kernel_times", "gm_kernel_name",
            "gm_batch_raw_hits", "gm_stream_create", "gm_stream_destroy", "gm_host_alloc", "gm_host_free", "gm_map_batch", "gm_output_batch",
            "gm_output_batch_text", "gm_map_batch_enqueue", "gm_output_batch_enqueue", "gm_batch_wait", "gm_dev_fmt_g6", "gm_dev_fmt_e2", "gm_dev_scan_u32",
-           "gm_dev_mate_resolve", "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
+           "gm_dev_mate_resolve", "gm_dev_sa_interval", "gm_dev_locate", "gm_dev_nw_score", "gm_dev_traceback", "gm_dev_prep", "gm_dev_pair_hmm", "gm_coverage_reset", "gm_coverage_bins",
            "gm_coverage_device_ptr", "gm_coverage_add", "gm_coverage_download", "gm_coverage_allreduce", "gm_coverage_write_sgr", "gm_coverage_enable_nuc", "gm_coverage_nuc_device_ptr",
            "gm_coverage_download_nuc", "gm_coverage_write_gmp", "gm_snp_calls", "gm_dev_snp_stat", "gm_coverage_write_gmp_calls",
            "gm_coverage_write_sgr_device", "gm_coverage_write_gmp_device", "gm_coverage_text", "gm_coverage_text_stats",
@@ -202,6 +202,8 @@ def load_library():
     L.gm_dev_nw_score.argtypes = [C.c_void_p, C.POINTER(gm_params), C.POINTER(gm_reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.gm_dev_traceback.argtypes = [C.c_void_p, C.POINTER(gm_params), C.POINTER(gm_reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                    C.c_void_p, C.c_uint32, C.c_void_p]
+    L.gm_dev_prep.argtypes = [C.c_void_p, C.POINTER(gm_params), C.POINTER(gm_reads), C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p]
     L.gm_dev_pair_hmm.argtypes = [C.c_void_p, C.POINTER(gm_params), C.POINTER(gm_reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.gm_coverage_reset.argtypes = [C.c_void_p, C.c_uint32]
     L.gm_coverage_bins.argtypes = [C.c_void_p]; L.gm_coverage_bins.restype = u64
@@ -403,6 +405,20 @@ class Index:
         self._probe(fasta, lambda: lib().gm_dev_traceback(self.h, C.byref(params.c), C.byref(r), read_idx.ctypes.data, strand.ctypes.data, pos.ctypes.data, n,
                                                           ops.ctypes.data, stride, ln.ctypes.data))
         return [ops[i, :ln[i]].tobytes() for i in range(n)]
+
+    def dev_prep(self, params, B, Q, Ln, first_row=0, exact=False, fasta=False):
+        """gm_dev_prep: the prep kernel alone on rows first_row .. n - 1 (a sub-batch view): dict(status, self_score, min_score,
+        pack [n, pack_words], bad_qual, high_qual, qual_lo, qual_hi).  exact: rows in allocations of exactly n x stride bytes"""
+        r = _reads_struct(B, Q, Ln)
+        n = B.shape[0]
+        status = np.zeros(n, np.int8); self_score = np.zeros(n, np.float32); min_score = np.zeros(n, np.float64)
+        pw = C.c_uint32(); work = np.zeros(4, np.uint64)
+        flat = np.zeros(n * (2 * ((B.shape[1] + 15) // 16) + 16), np.uint32)            # (room for any row layout; cut to pack_words below)
+        self._probe(fasta, lambda: lib().gm_dev_prep(self.h, C.byref(params.c), C.byref(r), first_row, int(exact), status.ctypes.data, self_score.ctypes.data,
+                                                     min_score.ctypes.data, flat.ctypes.data, C.byref(pw), work.ctypes.data))
+        assert n * pw.value <= flat.size
+        return dict(status=status, self_score=self_score, min_score=min_score, pack=flat[:n * pw.value].reshape(n, pw.value).copy(),
+                    bad_qual=int(work[0]), high_qual=int(work[1]), qual_lo=int(work[2]), qual_hi=int(work[3]))
 
     def dev_pair_hmm(self, params, B, Q, Ln, read_idx, strand, pos):
         """bin_seq::pairHMM of read read_idx[k] (oriented by strand[k]) against the window at pos[k]: [n][stride][5] floats"""

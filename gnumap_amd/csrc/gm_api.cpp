@@ -2779,6 +2779,55 @@ static int unit_batch(gm_index* ix, const gm_params* p, const gm_reads* reads, g
     return GM_OK;
 }
 
+extern "C" int gm_dev_prep(gm_index* ix, const gm_params* p, const gm_reads* reads, uint32_t first_row, int exact, int8_t* status, float* self_score,
+                           double* min_score, uint32_t* pack, uint32_t* pack_words, uint64_t* work) {
+    if (!ix || !p || !reads || !status || !self_score || !min_score || !pack_words || !work || !p->finalized) return GM_E_ARG;
+    if (first_row > reads->n || (exact && first_row)) return GM_E_ARG;
+    if (ix->host_only) return GM_E_NO_DEVICE;
+    HIPCHK(hipSetDevice(ix->device));
+    gm_batch* b; GmDevParams dp;
+    int rc = unit_batch(ix, p, reads, &b, dp);           // (uploads, and runs the prep kernel once over the whole block without 2-bit rows)
+    if (rc) return rc;
+    const uint32_t n = b->n, lo = first_row, pw = gm_pack_words(b->stride);
+    *pack_words = pw;
+    DevBuf xb, xq;
+    unsigned long long ctr[GMK_N];
+    do {
+        if (b->pack.ensure((size_t)n * pw * 4 + 64)) { rc = GM_E_NOMEM; break; }
+        if (hipMemset(b->pack.p, 0, (size_t)n * pw * 4) != hipSuccess || hipMemset(b->counters.p, 0, GMK_N * 8) != hipSuccess) { rc = GM_E_HIP; break; }
+        GmDevBatch v = b->dev;
+        v.n = n - lo; v.read_base = lo;
+        v.illumina_until = b->illumina_until > lo ? b->illumina_until - lo : 0;
+        v.bases += (size_t)lo * b->stride; v.quals += (size_t)lo * b->stride; v.len += lo;
+        v.status += lo; v.self_score += lo; v.min_score += lo; v.top_score += lo; v.hit_count += lo; v.hit_cursor += lo;
+        v.pack = b->pack.as<uint32_t>() + (size_t)lo * pw;
+        const size_t row_bytes = (size_t)n * b->stride;
+        if (exact && row_bytes) {                             // rows in allocations that end with the last row
+            if (hipMalloc(&xb.p, row_bytes) != hipSuccess) { rc = GM_E_NOMEM; break; }
+            xb.cap = row_bytes;
+            if (hipMemcpy(xb.p, b->bases.p, row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) { rc = GM_E_HIP; break; }
+            v.bases = xb.as<uint8_t>();
+            if (!b->fasta) {
+                if (hipMalloc(&xq.p, row_bytes) != hipSuccess) { rc = GM_E_NOMEM; break; }
+                xq.cap = row_bytes;
+                if (hipMemcpy(xq.p, b->quals.p, row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) { rc = GM_E_HIP; break; }
+                v.quals = xq.as<uint8_t>();
+            }
+        }
+        if (gmk_prep(ix->dev, dp, v, nullptr)) { rc = GM_E_HIP; break; }
+        if (hipMemcpy(ctr, b->counters.p, sizeof ctr, hipMemcpyDeviceToHost) != hipSuccess) { rc = GM_E_HIP; break; }
+        if (n && (hipMemcpy(status, b->status.p, n, hipMemcpyDeviceToHost) != hipSuccess ||
+                  hipMemcpy(self_score, b->self_score.p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                  hipMemcpy(min_score, b->min_score.p, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                  (pack && hipMemcpy(pack, b->pack.p, (size_t)n * pw * 4, hipMemcpyDeviceToHost) != hipSuccess))) { rc = GM_E_HIP; break; }
+    } while (0);
+    xb.release(); xq.release();
+    gm_batch_destroy(b);
+    if (rc) { gm_set_error("gm_dev_prep: HIP failure"); return rc; }
+    work[0] = ctr[GMK_BAD_QUAL]; work[1] = ctr[GMK_HIGH_QUAL]; work[2] = gm_qual_lo(ctr); work[3] = gm_qual_hi(ctr);
+    return GM_OK;
+}
+
 extern "C" int gm_dev_nw_score(gm_index* ix, const gm_params* p, const gm_reads* reads, const uint32_t* read_idx, const uint8_t* strand,
                                const uint64_t* pos, uint32_t n, float* score, uint8_t* valid) {
     if (!ix || !p || !reads || !read_idx || !strand || !pos || !score || !p->finalized) return GM_E_ARG;

@@ -2,13 +2,17 @@
 //
 // k_prep stages a tile of reads into LDS with coalesced loads, computes, and stages the next: its wavefronts spent 72 % of their time
 // waiting (profiles/r04_sq_counters_1M.txt: SQ_WAIT_ANY / SQ_WAVE_CYCLES), the vector units 35 % busy - the load phase of a tile is not
-// overlapped with anything, and three workgroups per CU (50 KB of LDS each) is all that fits.  Here a lane loads its own row (bases and
-// qualities: 2 x NCH 8-byte words) into registers up front - all loads of a lane go out back to back, every line is fetched once, the
-// trick k_nw_lane's register form measured (4.17 -> 0.66 GB per 1 M candidates) - and works from the registers at compile-time byte
-// positions: no tile, no barrier between load and compute, the loads of one wavefront overlap the arithmetic of the others (LDS only for
-// the term / class tables and the output transpose).  The 2-bit forms of a wavefront's 64 reads are ONE contiguous stretch in HBM
-// (64 x pack_words x 4 bytes): they are collected in LDS and written out as whole 16-byte pieces, coalesced, instead of word by word from
-// a lane's strided row.
+// overlapped with anything, and three workgroups per CU (50 KB of LDS each) is all that fits.  Here a lane holds its own row (bases and
+// qualities: 2 x NCH 8-byte words) in registers and works from them at compile-time byte positions: no tile, no workgroup barrier between
+// load and compute, the loads of one wavefront overlap the arithmetic of the others.
+//
+// The 64 rows of a wavefront are ONE contiguous stretch in HBM (64 x stride bytes = 52 whole lines at stride 104), and so are its 64 rows
+// of 2-bit forms (64 x pack_words x 4 bytes).  Both cross LDS as whole 16-byte pieces, lane after lane: on the way in every load
+// instruction of the wavefront covers eight consecutive lines and every line is asked for once (a lane that loads its own row makes
+// every instruction touch 64 lines, each of them again by seven more instructions: it is fetched once only if it survives in L1 in
+// between); all loads of both arrays are issued first, then the bases cross the wavefront's stage and each lane picks its row up, then
+// the qualities cross the same bytes, and at the end of the trip the same bytes collect the 2-bit forms on their way out.  The stage is
+// private to its wavefront, so the hand-overs need no workgroup barrier.
 //
 // Arithmetic and outputs are k_prep's, statement by statement (self score = fp32 sum in index order of the per-base terms - the term of a
 // base is looked up in the (class, quality character) table built with the reference's expression, bin_seq.cpp:975-987; status / cutoff /
@@ -20,12 +24,81 @@
 
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// LDS of one wavefront: its 64 input rows of one array (+ 16 bytes: the stretch lies at its HBM address modulo 16) or, later in the same
+// trip, its 64 rows of 2-bit forms, whichever is larger (both multiples of 16)
+__host__ __device__ static inline uint32_t gm_prep_wave_bytes(uint32_t pw, uint32_t stride) {
+    const uint32_t in = 64u * stride + 16u, out = 64u * pw * 4u;
+    return in > out ? in : out;
+}
+
+// A wavefront's rows r0 .. r0 + rows - 1 of one input array: one contiguous stretch of rows x stride bytes, 8-byte aligned (stride is a
+// multiple of 8; a sub-batch view starts at any row).  It is cut at the 16-byte boundaries of HBM: `head` bytes (0 or 8) before the first
+// one, `nfull` whole 16-byte pieces, `tail` bytes (0 or 8) after the last - so no load reaches before the first row or past the last one.
+struct GmStretch { const uint8_t* p; uint32_t head, nfull, tail; };
+
+__device__ __forceinline__ GmStretch gm_stretch(const uint8_t* rows0, uint32_t r0, uint32_t rows, uint32_t stride) {
+    GmStretch s;
+    s.p = rows0 + (size_t)(rows ? r0 : 0u) * stride;
+    const uint32_t bytes = rows * stride;
+    s.head = bytes ? (uint32_t)(reinterpret_cast<uintptr_t>(s.p) & 8u) : 0u;
+    s.nfull = (bytes - s.head) >> 4;
+    s.tail = (bytes - s.head) & 8u;
+    return s;
+}
+
+// lane q takes pieces q, q + 64, ...: a load instruction of the wavefront covers 1 KB of consecutive bytes (eight whole lines).  The head
+// and the tail ride in one 8-byte load of lanes 0 and 1.
+template <int NP>
+__device__ __forceinline__ void gm_stretch_load(const GmStretch& s, uint32_t lane, uint4 (&P)[NP], uint2& E) {
+    const uint4* const body = reinterpret_cast<const uint4*>(s.p + s.head);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t q = lane + 64u * (uint32_t)j;
+        P[j] = make_uint4(0u, 0u, 0u, 0u);
+        if (q < s.nfull) P[j] = body[q];
+    }
+    E = make_uint2(0u, 0u);
+    if (lane == 0 && s.head) E = *reinterpret_cast<const uint2*>(s.p);
+    if (lane == 1 && s.tail) E = *reinterpret_cast<const uint2*>(s.p + s.head + 16u * (size_t)s.nfull);
+}
+
+// the stretch in LDS: byte x at stage + head + x, so that the whole pieces are 16-byte aligned there as they are in HBM
+template <int NP>
+__device__ __forceinline__ void gm_stretch_store(const GmStretch& s, uint32_t lane, uint8_t* stage, const uint4 (&P)[NP], const uint2& E) {
+    uint4* const body = reinterpret_cast<uint4*>(stage + 2u * s.head);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t q = lane + 64u * (uint32_t)j;
+        if (q < s.nfull) body[q] = P[j];
+    }
+    if (lane == 0 && s.head) *reinterpret_cast<uint2*>(stage + s.head) = E;
+    if (lane == 1 && s.tail) *reinterpret_cast<uint2*>(stage + 2u * s.head + 16u * (size_t)s.nfull) = E;
+}
+
+// a lane's own row out of the stage: the words that hold bases of the read, zero beyond them (and for a lane without a read: L = 0)
 template <int NCH>
-__global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p, GmDevBatch b) {
+__device__ __forceinline__ void gm_row_from_stage(const uint8_t* row, uint32_t L, uint2 (&R)[NCH]) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        R[k] = make_uint2(0u, 0u);
+        if ((uint32_t)(8 * k) < L) R[k] = *reinterpret_cast<const uint2*>(row + 8 * k);
+    }
+}
+
+// the stage belongs to one wavefront: its LDS accesses complete in program order, the compiler has to keep that order across lanes
+__device__ __forceinline__ void gm_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// (waves per SIMD: <13> fits 128 registers without scratch when asked to - 133 and three waves otherwise; <19> holds 10 + 10 pieces: 177)
+template <int NCH>
+__global__ void __launch_bounds__(256, NCH <= 13 ? 4 : 2) k_prep_rows(GmDevIndex ix, GmDevParams p, GmDevBatch b) {
     __shared__ float s_term[2][10][128];                   // [phred table][char class][quality character & 127]
     __shared__ uint8_t s_cls[256];
     __shared__ int s_other_uniform;
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_rows[];        // [4 waves][64 lanes][pack_words]: the 2-bit forms on their way out
+    // per wave: its 64 rows of one input array on their way in, then [64 lanes][pack_words] of 2-bit forms on their way out
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_wave[];
+    constexpr int NP = (32 * NCH + 63) / 64;               // 16-byte pieces per lane of a stretch of 64 rows of NCH words
     const float4* const S4 = reinterpret_cast<const float4*>(p.S256);
     if (threadIdx.x == 0) s_other_uniform = 1;
     __syncthreads();
@@ -55,41 +128,39 @@ __global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p,
     __syncthreads();
     const bool uni = b.fasta || s_other_uniform != 0;        // (FASTA: class 8 has every character's own term)
     const uint32_t pw = b.pack ? b.pack_words : 0u;
-    uint32_t* const myrow = s_rows + (size_t)threadIdx.x * pw;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;      // (wave: in a scalar register, and what follows from it)
+    uint8_t* const stage = s_wave + (size_t)wave * gm_prep_wave_bytes(pw, b.stride);
+    uint32_t* const myrow = reinterpret_cast<uint32_t*>(stage) + (size_t)lane * pw;
     unsigned long long bad = 0, high = 0;
     uint32_t qlo = 255u, qhi = 0u;                           // the range of the quality characters (below 128 when it matters: GMK_QUAL_MIN)
     for (uint32_t base = blockIdx.x * 256u; base < b.n; base += gridDim.x * 256u) {
         const uint32_t r = base + threadIdx.x;
         const bool rv = r < b.n;
         const uint32_t L = rv ? b.len[r] : 0u;
-        // ---- the row into registers: every load of the lane in flight at once ----
+        // ---- the wavefront's stretch of rows through LDS, then the lane's own row into registers ----
         uint2 RB[NCH], RQ[NCH];
         {
-            const uint8_t* rb = b.bases + (size_t)(rv ? r : 0u) * b.stride;
-            const uint8_t* rq = b.quals + (size_t)(rv ? r : 0u) * b.stride;
-            // 16 bytes per load where the read reaches into both halves (rows are 8-byte aligned, the loads need 4): half as many address
-            // cycles in the texture path, where a wavefront's 64 rows are 64 different lines for every load instruction
+            const uint32_t r0 = base + 64u * wave;
+            const uint32_t rows = r0 < b.n ? (b.n - r0 < 64u ? b.n - r0 : 64u) : 0u;
+            const GmStretch sb = gm_stretch(b.bases, r0, rows, b.stride);
+            const GmStretch sq = gm_stretch(b.fasta ? b.bases : b.quals, r0, b.fasta ? 0u : rows, b.stride);
+            uint4 PB[NP], PQ[NP];
+            uint2 EB, EQ;
+            // every load of both arrays goes out before the first LDS store
+            gm_stretch_load<NP>(sb, lane, PB, EB);
+            gm_stretch_load<NP>(sq, lane, PQ, EQ);
+            gm_stretch_store<NP>(sb, lane, stage, PB, EB);
+            gm_wave_lds_sync();
+            gm_row_from_stage<NCH>(stage + sb.head + (size_t)lane * b.stride, L, RB);
+            gm_wave_lds_sync();                           // (every lane has its letters: the stage takes the qualities)
+            if (b.fasta) {                                // no quality rows: the letters (7 bits) stand in their place
 #pragma unroll
-            for (int k = 0; k < NCH; k += 2) {
-                RB[k] = make_uint2(0u, 0u); RQ[k] = make_uint2(0u, 0u);
-                if (k + 1 < NCH) { RB[k + 1] = make_uint2(0u, 0u); RQ[k + 1] = make_uint2(0u, 0u); }
-                if (b.fasta) {                            // no quality rows: the letters (7 bits) stand in their place
-                    if (k + 1 < NCH && (uint32_t)(8 * k + 8) < L) {
-                        uint4 tb;
-                        __builtin_memcpy(&tb, rb + 8 * k, 16);
-                        RB[k] = make_uint2(tb.x, tb.y);
-                        if (k + 1 < NCH) RB[k + 1] = make_uint2(tb.z, tb.w);
-                    } else if ((uint32_t)(8 * k) < L) RB[k] = *reinterpret_cast<const uint2*>(rb + 8 * k);
-                    RQ[k] = make_uint2(RB[k].x & 0x7F7F7F7Fu, RB[k].y & 0x7F7F7F7Fu);
-                    if (k + 1 < NCH) RQ[k + 1] = make_uint2(RB[k + 1].x & 0x7F7F7F7Fu, RB[k + 1].y & 0x7F7F7F7Fu);
-                } else if (k + 1 < NCH && (uint32_t)(8 * k + 8) < L) {
-                    uint4 tb, tq;
-                    __builtin_memcpy(&tb, rb + 8 * k, 16); __builtin_memcpy(&tq, rq + 8 * k, 16);
-                    RB[k] = make_uint2(tb.x, tb.y); RQ[k] = make_uint2(tq.x, tq.y);
-                    if (k + 1 < NCH) { RB[k + 1] = make_uint2(tb.z, tb.w); RQ[k + 1] = make_uint2(tq.z, tq.w); }
-                } else if ((uint32_t)(8 * k) < L) {
-                    RB[k] = *reinterpret_cast<const uint2*>(rb + 8 * k); RQ[k] = *reinterpret_cast<const uint2*>(rq + 8 * k);
-                }
+                for (int k = 0; k < NCH; ++k) RQ[k] = make_uint2(RB[k].x & 0x7F7F7F7Fu, RB[k].y & 0x7F7F7F7Fu);
+            } else {
+                gm_stretch_store<NP>(sq, lane, stage, PQ, EQ);
+                gm_wave_lds_sync();
+                gm_row_from_stage<NCH>(stage + sq.head + (size_t)lane * b.stride, L, RQ);
+                gm_wave_lds_sync();                       // (the same bytes take the 2-bit forms below)
             }
         }
         if (pw) {                                         // the lane's row of the output stretch starts out zero
@@ -210,12 +281,11 @@ __global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p,
         if (pw) {
             // the wavefront's 64 rows are one stretch of pack[]: out in 16-byte pieces, lane after lane
             __syncthreads();
-            const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
             const uint32_t r0 = base + 64u * wave;
             if (r0 < b.n) {
                 const uint32_t rows = b.n - r0 < 64u ? b.n - r0 : 64u;
                 const uint32_t pieces = rows * pw / 4u;                         // (pack_words is a multiple of 4)
-                const uint4* src = reinterpret_cast<const uint4*>(s_rows + (size_t)wave * 64u * pw);
+                const uint4* src = reinterpret_cast<const uint4*>(stage);
                 uint4* dst = reinterpret_cast<uint4*>(b.pack + (size_t)r0 * pw);
                 for (uint32_t q = lane; q < pieces; q += 64u) dst[q] = src[q];
             }
@@ -230,7 +300,8 @@ __global__ void __launch_bounds__(256) k_prep_rows(GmDevIndex ix, GmDevParams p,
 int gmk_prep_rows(const GmDevIndex& ix, const GmDevParams& p, const GmDevBatch& b, void* stream) {
     if (b.n == 0) return 0;
     if (b.stride > 152) return (int)hipErrorInvalidValue;
-    const size_t lds = b.pack ? (size_t)256 * b.pack_words * 4 : 0;
+    if ((reinterpret_cast<uintptr_t>(b.bases) | reinterpret_cast<uintptr_t>(b.quals) | b.stride) & 7u) return (int)hipErrorInvalidValue;
+    const size_t lds = (size_t)4 * gm_prep_wave_bytes(b.pack ? b.pack_words : 0u, b.stride);
     const uint32_t grid = gm_test_grid((uint32_t)std::min<uint64_t>(((uint64_t)b.n + 255) / 256, 256ull * 5 * 4));
     if (b.stride <= 104) hipLaunchKernelGGL((k_prep_rows<13>), dim3(grid), dim3(256), lds, S_(stream), ix, p, b);
     else hipLaunchKernelGGL((k_prep_rows<19>), dim3(grid), dim3(256), lds, S_(stream), ix, p, b);

@@ -572,6 +572,14 @@ int gm_dev_traceback(gm_index*, const gm_params*, const gm_reads*, const uint32_
                      const uint64_t* pos, uint32_t n, char* ops /* n x ops_stride, 'M','I','D', NUL padded */,
                      uint32_t ops_stride, uint16_t* ops_len);
 
+/* the prep kernel alone (the form GM_PREP chooses) on rows first_row .. reads->n - 1 of the block, as a sub-batch view of a pipelined
+ * call sees them, with the 2-bit rows.  status / self_score / min_score take reads->n entries (rows before first_row: those of a pass over
+ * the whole block), pack reads->n x *pack_words words (zero before first_row; NULL: not wanted), work[4] = reads with a negative
+ * probability, reads with a quality character above 127, the lowest and the highest quality character.  exact (first_row = 0 only): the
+ * kernel reads the rows from allocations of exactly reads->n x stride bytes */
+int gm_dev_prep(gm_index*, const gm_params*, const gm_reads*, uint32_t first_row, int exact, int8_t* status, float* self_score, double* min_score,
+                uint32_t* pack, uint32_t* pack_words, uint64_t* work);
+
 /* the format in which the unit probes above (and gm_dev_pair_hmm, which refuses FASTA) read their gm_reads from now on: GM_READS_FASTQ
  * (default) or GM_READS_FASTA - see gm_batch_set_read_format.  Per index, not thread-safe against probes running at the same time */
 int gm_index_set_probe_format(gm_index*, int format);
